@@ -86,7 +86,13 @@ def parse():
     ap.add_argument("--no-f16-leg", action="store_true", help="skip the f16-operand throughput + parity leg (`f16_operating_point`) that follows the contract run")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous / collation rehearsal without a GPU: every rank fabricates its "
                     "shard's results instead of aligning (CPU tests of the --gpus N self-launch with WCA_DIST_BACKEND=gloo)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float64): the "
+                         "collated word start / end times of its utterances with their word counts, and rank 0's DTW jump frames and top-k head indices")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args):
@@ -158,6 +164,8 @@ def dry_run(args, dist, rank, world):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_step_outputs(merged, args.steps - 1, args.batch, world))
         total = world * args.batch * args.steps
         print(json.dumps({"metric": METRIC, "value": total / elapsed, "unit": "utterances/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "none",
@@ -167,6 +175,36 @@ def dry_run(args, dist, rank, world):
                                      "dist_backend": dist.get_backend() if dist is not None else None, "collated_utterances": len(merged),
                                      "collective_calls": dict(shard.COLLECTIVE_CALLS)},
                           "roofline": None, "cpu_baseline": None}), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def last_step_outputs(merged, step, batch, world, jump=None, sel=None):
+    """{name: float64 array} of what timed step `step` returned: the word start / end times (s) of its world x batch utterances, concatenated
+    in utterance-id order (`word_counts` words each), and (rank 0's shard) the per-token DTW jump frames and the selected top-k heads."""
+    ids = sorted(u for u in merged if (u // world) // batch == step)   # utterance id = (step * batch + j) * world + rank
+    starts = [np.asarray(merged[u][0], dtype=np.float64) for u in ids]
+    ends = [np.asarray(merged[u][1], dtype=np.float64) for u in ids]
+    out = {"utterance_ids": np.asarray(ids, dtype=np.float64), "word_counts": np.asarray([len(st) for st in starts], dtype=np.float64),
+           "word_start_s": np.concatenate(starts or [np.zeros(0)]), "word_end_s": np.concatenate(ends or [np.zeros(0)])}
+    if jump is not None:
+        out["jump_frames"] = np.asarray(jump, dtype=np.float64)
+    if sel is not None:
+        out["topk_heads"] = np.asarray(sel, dtype=np.float64)
+    return out
+
+
+def dump_outputs(path, arrays):
+    bad = [name for name, a in arrays.items() if not np.isfinite(a).all()]
+    if bad:
+        raise SystemExit("--dump-outputs: non-finite values in %s" % ", ".join(bad))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def build_inputs(syn, tok_mod, retok, args, n_batches, rank, world, device):
@@ -562,12 +600,14 @@ def main():
             _words, st, en = timing.words_from_jump_frames(jump[j], b["texts"][j], tok, "char", want_words=False)
             if collect is not None:
                 collect[(i * args.batch + j) * world + rank] = (st, en)
+        return jump, _sel
 
     SITES = ("qkv", "attention", "out_proj", "fc1", "fc2", "ln1", "ln2")
 
     def timed_region(steps, warmup):
         """W untimed warm-up steps, then EXACTLY `steps` steps bracketed by barrier + synchronize on both sides, the product's
-        collation inside the bracket, max over ranks. Returns (elapsed s, per-site HIP-event sums, sampled steps, stage ms, #collated)."""
+        collation inside the bracket, max over ranks. Returns (elapsed s, per-site HIP-event sums, sampled steps, stage ms, #collated,
+        what the last step returned)."""
         for i in range(warmup):
             enqueue(i)
             finish(i)
@@ -599,7 +639,7 @@ def main():
                 finish(i - 1, results)
             if i % 8 == 7 and i + 1 < steps:
                 sample_sites()
-        finish(steps - 1, results)
+        jump, sel = finish(steps - 1, results)
         # collate exactly like infer_ali.py does: packed (index, n, starts, ends) records through one size gather + one
         # all-gather, and the 3-counter all-reduce (the only collectives on the path; no-ops for one rank)
         coll_dev = device if (dist is None or dist.get_backend() == "nccl") else torch.device("cpu")
@@ -617,7 +657,8 @@ def main():
             tmax = torch.tensor([elapsed], device=coll_dev, dtype=torch.float64)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax.item())
-        return elapsed, {s_: tuple(site_acc[s_]) for s_ in SITES}, sampled, stage_ms, len(merged)
+        last = last_step_outputs(merged, steps - 1, args.batch, world, jump, sel)
+        return elapsed, {s_: tuple(site_acc[s_]) for s_ in SITES}, sampled, stage_ms, len(merged), last
 
     def kernel_table(sites, precision):
         sym = dict(SITE_SYMBOL)
@@ -643,9 +684,11 @@ def main():
                            "achieved": ach, "unit": "TFLOP/s" if mfma else "GB/s", "frac": ach / (MFMA_F16_DENSE_PEAK_TFLOPS if mfma else HBM_PEAK_GBS)}
         return kernels, sym
 
-    elapsed, sites, sampled_steps, stage_ms, n_collated = timed_region(args.steps, args.warmup)
+    elapsed, sites, sampled_steps, stage_ms, n_collated, last_outputs = timed_region(args.steps, args.warmup)
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_outputs)
         total_utts = world * args.batch * args.steps
         kernels, sym = kernel_table(sites, args.precision)
         dom = max(kernels, key=lambda s_: kernels[s_]["total_ms"])
@@ -714,7 +757,7 @@ def main():
                 contract_mode = args.precision
                 model.set_precision("f16")
                 steps2 = max(8, args.steps // 2)
-                el2, sites2, _n2, _st2, _c2 = timed_region(steps2, 2)
+                el2, sites2, _n2, _st2, _c2, _o2 = timed_region(steps2, 2)
                 k2, _sym2 = kernel_table(sites2, "f16")
                 args.precision = "f16"
                 par2 = parity_against_oracle(args, model, tok, opts, timing, retok, syn, oracle_times, device)

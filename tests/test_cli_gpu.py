@@ -393,6 +393,32 @@ def test_bench_collation_through_the_c_abi():
     assert cfg["collective_calls"]["all_gather"] == 2 and cfg["collective_calls"]["all_reduce"] == 1
 
 
+def test_bench_dump_outputs_repeat_exactly(tmp_path):
+    """bench.py --dump-outputs: two runs with the same arguments time exactly --steps steps and write the same outputs of the last
+    step (the word times a caller receives, the DTW jump frames, the top-k heads), so two builds can be compared output for output."""
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in range(2):
+        out = tmp_path / ("run%d" % run)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--model", "tiny", "--batch", "4", "--steps", "3", "--warmup", "1",
+                            "--distinct-batches", "2", "--seconds", "4", "--chars", "24", "--no-cpu-baseline", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
+        assert d["steps"] == 3 and d["config"]["collated_utterances"] == 12 and d["ms_per_step"] > 0
+        dumps.append({f.stem: np.load(f) for f in out.glob("*.npy")})
+    a, b = dumps
+    assert set(a) == {"utterance_ids", "word_counts", "word_start_s", "word_end_s", "jump_frames", "topk_heads"}
+    assert a["utterance_ids"].tolist() == [8, 9, 10, 11]   # the last of the 3 timed steps
+    assert (a["word_counts"] >= 1).all() and a["word_start_s"].shape == a["word_end_s"].shape == (int(a["word_counts"].sum()),)
+    assert a["jump_frames"].shape[0] == 4 and a["topk_heads"].shape == (4, 10)
+    for k in a:
+        assert a[k].dtype == np.float64 and np.isfinite(a[k]).all() and np.array_equal(a[k], b[k]), k
+
+
 def test_rccl_collation_through_the_c_abi(wca):
     """wca_comm_* / wca_allgather_results / wca_allreduce_counters: the end-of-run collation straight from libwca.so over
     librccl, no torch.distributed. One rank on this one-GPU box (a communicator of one): packed records survive the size gather +

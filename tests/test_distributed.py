@@ -112,10 +112,13 @@ def _bench(args, env_extra):
     return r, [json.loads(ln) for ln in lines]
 
 
-def test_bench_gpus_n_self_launches_n_ranks():
+def test_bench_gpus_n_self_launches_n_ranks(tmp_path):
     """`python bench.py --gpus 2` run plainly (the driver's command shape, WORLD_SIZE unset) must start 2 ranks itself, run the
-    product's collation over the process group and print exactly ONE line with n_gpus == 2 (gloo + --dry-run: no GPU here)."""
-    r, recs = _bench(["--gpus", "2", "--steps", "3", "--batch", "5", "--warmup", "0", "--dry-run"], {"WCA_DIST_BACKEND": "gloo"})
+    product's collation over the process group and print exactly ONE line with n_gpus == 2 (gloo + --dry-run: no GPU here).
+    --dump-outputs writes the collated word times of the LAST step's utterances of both ranks."""
+    import numpy as np
+    r, recs = _bench(["--gpus", "2", "--steps", "3", "--batch", "5", "--warmup", "0", "--dry-run", "--dump-outputs", str(tmp_path / "out")],
+                     {"WCA_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-3000:]
     assert len(recs) == 1, r.stdout
     d = recs[0]
@@ -123,6 +126,12 @@ def test_bench_gpus_n_self_launches_n_ranks():
     cfg = d["config"]
     assert cfg["dist_ranks"] == 2 and cfg["dist_backend"] == "gloo" and cfg["collated_utterances"] == 2 * 3 * 5
     assert cfg["collective_calls"]["all_gather"] == 2 and cfg["collective_calls"]["all_reduce"] == 1
+    ids = np.load(tmp_path / "out" / "utterance_ids.npy")
+    st, en = np.load(tmp_path / "out" / "word_start_s.npy"), np.load(tmp_path / "out" / "word_end_s.npy")
+    assert ids.dtype == np.float64 and ids.tolist() == list(range(2 * 2 * 5, 3 * 2 * 5))   # step 2 of 3, 5 utterances per rank
+    counts = np.load(tmp_path / "out" / "word_counts.npy")
+    assert counts.shape == (10,) and (counts >= 1).all() and st.shape == en.shape == (int(counts.sum()),)
+    assert np.isfinite(st).all() and np.abs(en - st - 0.02).max() < 1e-9   # the fabricated words are one frame long
 
 
 def test_bench_gpus_n_refuses_when_devices_are_missing():
