@@ -29,6 +29,10 @@
  *                          (log-mel -> forward+capture -> medfilt/softmax -> scores/top-k ->
  *                          aggregate -> DTW) for a micro-batch of utterances, results = the frame
  *                          at which the DTW path enters every token row (timing.py:110-111 `jumps`)
+ *   wca_align_batch_enqueue_ex / wca_align_batch_fetch_ex, wca_token_logprobs
+ *                          timing.py:146-150 (`text_token_probs`: softmax of logits[len(sot_sequence):, :eot] at the
+ *                          teacher token) and timing.py:181-184 (`word_probabilities`, the per-word mean the host forms):
+ *                          the teacher-token log-probabilities, computed and kept on the GPU
  *
  * Conventions
  *   - plain C types only; no torch / HIP types in signatures (streams are passed as void*).
@@ -257,6 +261,29 @@ int wca_align_batch_enqueue(wca_engine* e, const float* pcm_dev, int64_t pcm_str
                             const int32_t* max_frames_host, int batch, const wca_align_opts* opts);
 int wca_align_batch_fetch(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host,
                           int32_t* sel_idx_host);
+
+/* Teacher-token log-probabilities (timing.py:146-150 of the reference: text_token_probs = softmax(logits[len(sot_sequence):, :eot]) at
+ * the teacher token, here in log space; the per-word mean of timing.py:181-184 is the caller's). For utterance b with
+ * tokens = [*sot_sequence, no_timestamps, *text, eot] and n_text = n_tok[b] - sot_len - 2, entry i < n_text is
+ *   log_softmax(logits[b][sot_len + i][0 : vocab_end])[tokens[b][sot_len + 1 + i]];
+ * the prediction of eot is not scored, as in the reference.
+ * _enqueue_ex: wca_align_batch_enqueue with vocab_end (= tokenizer.eot) in (0, n_vocab]; 0 = no log-probs, exactly the path of
+ *   wca_align_batch_enqueue. With log-probs the decoder finishes its last layer and the n_text rows of every utterance go through the final
+ *   LayerNorm, the vocabulary projection (tok_emb rows [0, vocab_end)) and a log-sum-exp kernel on the engine's second stream; the
+ *   [rows][vocab] logits never reach the host. A teacher token >= vocab_end has no value: NaN, and _fetch_ex returns WCA_ERR_INVALID.
+ *   The jump frames and top-k heads are the same with and without log-probs.
+ * _fetch_ex: wca_align_batch_fetch plus token_logprob_host [batch][n_tok_max] f32 (nullable): entries [0, n_text_b) of row b, the rest 0.
+ *   WCA_ERR_STATE (and nothing consumed) when token_logprob_host is given but the pending batch was enqueued with vocab_end = 0. */
+int wca_align_batch_enqueue_ex(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
+                               const int64_t* tokens_dev, int n_tok_max, const int32_t* n_tok_host,
+                               const int32_t* max_frames_host, int batch, const wca_align_opts* opts, int32_t vocab_end);
+int wca_align_batch_fetch_ex(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host,
+                             int32_t* sel_idx_host, float* token_logprob_host);
+/* The same log-sum-exp kernel on caller-supplied logits (timing.py:146-149 on the logits wca_get_attentions returns): logits_dev [rows][ld]
+ * f32 (ld >= vocab_end), targets_dev [rows] int64, out_dev [rows] f32 = log_softmax(logits[r][0 : vocab_end])[targets[r]]. Synchronous
+ * on the engine stream; a target outside [0, vocab_end) gives NaN there and WCA_ERR_INVALID. */
+int wca_token_logprobs(wca_engine* e, const float* logits_dev, int rows, int ld, int vocab_end, const int64_t* targets_dev,
+                       float* out_dev);
 
 /* ---- audio I/O on the host (no GPU work, no engine): dataset.py:31,104 read the corpora through torchaudio.load; the
  * LibriSpeech originals are FLAC. buf = the whole .flac file in memory.

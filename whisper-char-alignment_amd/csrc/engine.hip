@@ -187,7 +187,8 @@ struct wca_engine {
   size_t sk_big_bytes = 0;
   int n_cu = 0;
   int* err_dev = nullptr;    // device flags raised by kernels. Word 0: phase 2 / synchronous entry points (bit 0 token id outside the
-                             // vocabulary, bit 1 LayerNorm hand-off timeout); words 1, 2: phase 1 of the batch in cross-K/V slot 0, 1 (bit 1
+                             // vocabulary, bit 1 LayerNorm hand-off timeout, bit 2 teacher token outside [0, vocab_end) of the token log-probs;
+                             // word 3: the same bit of wca_token_logprobs); words 1, 2: phase 1 of the batch in cross-K/V slot 0, 1 (bit 1
                              // only), cleared on `stream` before that batch's encoder and read with the batch's results, so that neither the
                              // phase-2 clear of this batch nor the next batch's encoder (concurrent on `stream`) can wipe or alias it
   int* ln_err = nullptr;     // where the encoder's out_mode-3 GEMMs raise their time-out bit (err_dev, or err_dev + 1 + slot in run_phase1)
@@ -212,6 +213,10 @@ struct wca_engine {
   size_t res_host_ints[2] = {0, 0};
   hipEvent_t res_ev[2] = {};
   int res_topk[2] = {0, 0}, res_ntok[2] = {0, 0}, res_batch[2] = {0, 0};
+  bool res_lp[2] = {false, false};   // the batch in that slot was enqueued with token log-probs (its staging slot holds them)
+  // teacher-token log-probs of wca_align_batch_enqueue_ex (phase 2's stream): compact f32 rows, their final-LayerNorm output (pairs when DEC
+  // is split), the row map, the chunked [rows][ldc] f32 logits scratch and the [B][n_tok_max] results
+  GrowBuf lp_x, lp_xn, lp_map, lp_logits, lp_out;
   unsigned long enq_count = 0, fetch_count = 0;
   int last_batch = 0;
 
@@ -972,7 +977,7 @@ int run_cross_kv(wca_engine* e, int B, half_t* kvbuf = nullptr, bool skip_last_v
 // cross-attention on q / K / V pairs): separate LayerNorm launches, the tile GEMMs (the few-row kernel of gemm_rows.hip has no pair
 // output), attn_split_kernel where the attention is split. The captured logits of a split CAPTURE are the three-pass fp32 sums.
 int run_decoder_sites(wca_engine* e, const int64_t* tokens_dev, int B, int n, float* cap, int Fpad, int Fcap, float* logits_out, hipStream_t s,
-                      const half_t* kvbuf) {
+                      const half_t* kvbuf, bool finish_last = false) {
   const wca_model_dims& D = e->dims;
   const int dt = D.n_text_state, H = D.n_text_head, L = D.n_text_layer;
   const int M = B * n;
@@ -1052,7 +1057,7 @@ int run_decoder_sites(wca_engine* e, const int64_t* tokens_dev, int B, int n, fl
       a.causal = 0;
       HIPCHK(launch_attention(a, s));
     }
-    if (li == L - 1 && !logits_out) break;
+    if (li == L - 1 && !logits_out && !finish_last) break;
     WCA_TRY(mm(e->att_d, cs, l.co_w, w.co_w, l.co_b, e->xd, dt, dt, dt, 0, 2, 0, 2));
     WCA_TRY(ln(l.ln2_g, l.ln2_b));
     WCA_TRY(mm(e->xdn, gs, l.fc1_w, w.fc1_w, l.fc1_b, e->hid_d, omg * 4 * dt, 4 * dt, dt, 1, 0, gs ? 4 * dt : 0, 2));
@@ -1066,13 +1071,15 @@ int run_decoder_sites(wca_engine* e, const int64_t* tokens_dev, int B, int n, fl
 }
 
 // decoder with capture. tokens_dev [B][n]; capture -> cap [B][L*H][n][Fpad] (first Fcap keys)
+// finish_last: the last layer runs to its end (cross-out, ln2, MLP) also without logits_out: e->xd then holds the final residual stream
+// (the token log-probs of wca_align_batch_enqueue_ex take it from there)
 int run_decoder(wca_engine* e, const int64_t* tokens_dev, int B, int n, float* cap, int Fpad, int Fcap, float* logits_out,
-                hipStream_t s = nullptr, const half_t* kvbuf = nullptr) {
+                hipStream_t s = nullptr, const half_t* kvbuf = nullptr, bool finish_last = false) {
   const wca_model_dims& D = e->dims;
   const int dt = D.n_text_state, H = D.n_text_head, L = D.n_text_layer;
   if (!s) s = e->stream;
   if (!kvbuf) kvbuf = e->kv;
-  if (site_on(e, WCA_PSITE_DEC) || site_on(e, WCA_PSITE_CAPTURE)) return run_decoder_sites(e, tokens_dev, B, n, cap, Fpad, Fcap, logits_out, s, kvbuf);
+  if (site_on(e, WCA_PSITE_DEC) || site_on(e, WCA_PSITE_CAPTURE)) return run_decoder_sites(e, tokens_dev, B, n, cap, Fpad, Fcap, logits_out, s, kvbuf, finish_last);
   const int M = B * n;
   const float scale = 1.0f / std::sqrt((float)(dt / H));
   HIPCHK(launch_embed(tokens_dev, e->tok_emb, e->dec_pos, e->xd, B, n, dt, D.n_vocab, e->err_dev, s));
@@ -1125,7 +1132,7 @@ int run_decoder(wca_engine* e, const int64_t* tokens_dev, int B, int n, float* c
       HIPCHK(launch_attention(a, s));
     }
     // the last layer's cross-attention logits are captured by now: without logits nothing downstream is read
-    if (li == L - 1 && !logits_out) break;
+    if (li == L - 1 && !logits_out && !finish_last) break;
     WCA_TRY(dec_gemm(e, s, 0, e->att_d, dt, nullptr, nullptr, nullptr, nullptr, l.co_w, dt, l.co_b, e->xd, dt, M, dt, dt, 0, 2, 2));
     WCA_TRY(dec_gemm(e, s, 0, nullptr, 0, e->xd, l.ln2_g, l.ln2_b, e->xdn, l.fc1_w, dt, l.fc1_b, e->hid_d, 4 * dt, M, 4 * dt, dt, 1, 0, 2));
     WCA_TRY(dec_gemm(e, s, 0, e->hid_d, 4 * dt, nullptr, nullptr, nullptr, nullptr, l.fc2_w, 4 * dt, l.fc2_b, e->xd, dt, M, dt, 4 * dt, 0, 2, 2));
@@ -1465,13 +1472,49 @@ int ensure_res_host(wca_engine* e, int slot, size_t ints) {
   return WCA_OK;
 }
 
+constexpr int ERR_TARGET_VOCAB = 4;   // err_dev bit: a teacher token outside [0, vocab_end) (its log-prob is NaN)
+
+// Teacher-token log-probs of one aligned micro-batch on stream s (timing.py:146-149 of the reference in log space), after
+// run_decoder(..., finish_last = true) left the final residual stream in e->xd. Only the R = sum_b n_text_b rows that predict a text token go
+// on: gathered (row_off_dev: device [B] prefix sums of n_text), final LayerNorm (pairs when DEC is split), the vocabulary projection against
+// tok_emb rows [0, vocab_end) in row chunks whose f32 logits stay under 256 MB (1 024 x 50 257 x 4 B = 206 MB), token_logprob_kernel per chunk.
+// out [B][n_tok_max]: entries [0, n_text_b) of row b, the rest 0.
+int run_token_logprobs(wca_engine* e, hipStream_t s, const int64_t* tokens_dev, int B, int n_tok_max, int sot_len, int vocab_end,
+                       const int* n_tok_dev, const int* row_off_dev, int R, int n_text_max, float* out) {
+  const int dt = e->dims.n_text_state;
+  const bool gs = site_on(e, WCA_PSITE_DEC);
+  const int omg = gs ? 2 : 1;
+  HIPCHK(hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * n_tok_max, s));
+  if (R <= 0) return WCA_OK;
+  HIPCHK(e->lp_x.ensure(sizeof(float) * (size_t)R * dt));
+  HIPCHK(e->lp_xn.ensure(sizeof(half_t) * (size_t)omg * R * dt));
+  HIPCHK(e->lp_map.ensure(sizeof(int) * (size_t)R));
+  float* xr = (float*)e->lp_x.p;
+  half_t* xn = (half_t*)e->lp_xn.p;
+  int* map = (int*)e->lp_map.p;
+  HIPCHK(launch_gather_text_rows(e->xd, n_tok_max, dt, sot_len, n_tok_dev, row_off_dev, B, n_text_max, xr, map, s));
+  HIPCHK(launch_layernorm_f16(xr, e->lnf_g, e->lnf_b, xn, R, dt, 1e-5f, s, omg * dt, gs ? dt : 0));
+  const int ldc = (int)align_up((size_t)vocab_end, 64);   // (the aligned f32 store path of the GEMM epilogue)
+  const int chunk = std::min(R, std::max(1, std::min(1024, (int)(((size_t)256 << 20) / ((size_t)ldc * sizeof(float))))));
+  HIPCHK(e->lp_logits.ensure(sizeof(float) * (size_t)chunk * ldc));
+  float* lg = (float*)e->lp_logits.p;
+  for (int r0 = 0; r0 < R; r0 += chunk) {
+    const int m = std::min(chunk, R - r0);
+    const GemmOpnd o = pick_operands(gs, gs, e->tok_emb, e->split ? e->sw.tok_emb : e->tok_emb, dt, m, vocab_end, 1, e);
+    HIPCHK(gemm(s, xn + (size_t)r0 * omg * dt, o.lda, o.W, o.ldw, nullptr, lg, ldc, m, vocab_end, o.K, 0, 1, 3, nullptr, 0, 0, o.a_lo, e, o.Wp, o.Kp));
+    HIPCHK(launch_token_logprob(lg, ldc, vocab_end, m, tokens_dev, map + r0, sot_len + 1, out, e->err_dev, ERR_TARGET_VOCAB, s));
+  }
+  return WCA_OK;
+}
+
 }  // namespace
 
 // =================================================================================== C ABI
 extern "C" {
 
 const char* wca_last_error(void) { return g_err.c_str(); }
-int wca_version(void) { return 5; }   // (round 5: a new engine is in the contract mode; wca_engine_create_ex, W_lo slab, switch table)
+int wca_version(void) { return 6; }   // 6: teacher-token log-probs (wca_align_batch_enqueue_ex / _fetch_ex, wca_token_logprobs); 5: a new engine is in
+                                      // the contract mode; wca_engine_create_ex, W_lo slab, switch table
 
 int wca_engine_create(const wca_model_dims* dims, int device_ordinal, int max_batch, wca_engine** out) {
   return wca_engine_create_ex(dims, device_ordinal, max_batch, WCA_PRECISION_REFERENCE, out);   // the CONTRACT mode is the default (round 5)
@@ -2377,9 +2420,17 @@ int wca_default_find_alignment(wca_engine* e, const float* ws_dev, int L, int H,
 int wca_align_batch_enqueue(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
                             const int64_t* tokens_dev, int n_tok_max, const int32_t* n_tok_host, const int32_t* max_frames_host,
                             int batch, const wca_align_opts* o) {
+  return wca_align_batch_enqueue_ex(e, pcm_dev, pcm_stride, n_samples_host, tokens_dev, n_tok_max, n_tok_host, max_frames_host, batch, o, 0);
+}
+
+int wca_align_batch_enqueue_ex(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
+                               const int64_t* tokens_dev, int n_tok_max, const int32_t* n_tok_host, const int32_t* max_frames_host,
+                               int batch, const wca_align_opts* o, int32_t vocab_end) {
   int rc = check_ready(e);
   if (rc) return rc;
   if (!tokens_dev || !n_tok_host || !max_frames_host || !o) return fail(WCA_ERR_INVALID, "null argument");
+  if (vocab_end < 0 || vocab_end > e->dims.n_vocab) return fail(WCA_ERR_INVALID, "vocab_end %d outside (0, %d] (0 = no token log-probs)", vocab_end, e->dims.n_vocab);
+  const bool want_lp = vocab_end > 0;
   const bool reuse_enc = (pcm_dev == nullptr);  // consume the oldest encoded state (wca_encode_batch / wca_greedy_decode)
   if (reuse_enc && (e->enc_q.empty() || e->enc_q.front().batch != batch))
     return fail(WCA_ERR_STATE, "pcm_dev == NULL re-uses the oldest state left by wca_encode_batch / wca_greedy_decode for the same batch; there is none");
@@ -2415,6 +2466,20 @@ int wca_align_batch_enqueue(wca_engine* e, const float* pcm_dev, int64_t pcm_str
   rc = stage_meta(e, batch, reuse_enc ? nullptr : n_samples_host, n_tok_host, max_frames_host, dn.data(), rows,
                   reuse_enc ? s2 : nullptr);
   if (rc) return rc;
+  // token log-probs: the rows that predict text token i of utterance b (row sot_len + i, i < n_text_b = n_tok - sot_len - 2) are compacted;
+  // utterance b's first compact row (the prefix sum of n_text) travels through the metadata ring, the row map is built from it on the device
+  int* lp_rows[4] = {nullptr, nullptr, nullptr, nullptr};
+  int lp_R = 0, lp_nmax = 0;
+  if (want_lp) {
+    std::vector<int32_t> off(batch);
+    for (int b = 0; b < batch; ++b) {
+      const int nt = std::max(0, n_tok_host[b] - o->sot_len - 2);
+      off[b] = lp_R;
+      lp_R += nt;
+      lp_nmax = std::max(lp_nmax, nt);
+    }
+    if ((rc = stage_meta(e, batch, off.data(), nullptr, nullptr, nullptr, lp_rows, reuse_enc ? s2 : nullptr))) return rc;
+  }
   // ---- phase 1 on `stream`: log-mel, encoder, cross-K/V of all decoder layers into a free K/V slot (a slot is busy
   // from its encode until the alignment that read it has been fetched; at most 2 alignments are in flight), or the
   // slot of the encoded state this call consumes.
@@ -2430,7 +2495,8 @@ int wca_align_batch_enqueue(wca_engine* e, const float* pcm_dev, int64_t pcm_str
     bs = take_kv_slot(e);
     if (bs < 0) return fail(WCA_ERR_STATE, "both cross-K/V slots hold live batches: fetch or consume one first");
     e->slot_busy[bs] = true;
-    rc = run_phase1(e, nullptr, pcm_dev, pcm_stride, rows[0], batch, bs, /*skip_last_v=*/true);  // this path never asks for logits
+    // (without token log-probs this path never reads the last layer's cross-attention output: its value projection is skipped)
+    rc = run_phase1(e, nullptr, pcm_dev, pcm_stride, rows[0], batch, bs, /*skip_last_v=*/!want_lp);
     if (rc) {
       e->slot_busy[bs] = false;
       return rc;
@@ -2442,7 +2508,7 @@ int wca_align_batch_enqueue(wca_engine* e, const float* pcm_dev, int64_t pcm_str
   HIPCHK(hipStreamWaitEvent(s2, e->ev_kv[bs], 0));
   HIPCHK(hipMemsetAsync(e->err_dev, 0, sizeof(int), s2));
   HIPCHK(e->cap.ensure(sizeof(float) * (size_t)batch * LH * n_tok_max * Fpad));
-  rc = run_decoder(e, tokens_dev, batch, n_tok_max, (float*)e->cap.p, Fpad, Fmax, nullptr, s2, kvbuf);
+  rc = run_decoder(e, tokens_dev, batch, n_tok_max, (float*)e->cap.p, Fpad, Fmax, nullptr, s2, kvbuf, /*finish_last=*/want_lp);
   if (rc) return rc;
   record(e, 4, s2);
   // the softmaxed maps are NOT materialised on this path (53 MB per utterance): head_stats keeps per-row
@@ -2480,12 +2546,21 @@ int wca_align_batch_enqueue(wca_engine* e, const float* pcm_dev, int64_t pcm_str
   rm.rowstats = h.rowstats;
   rc = run_select_aggregate_dtw(e, nullptr, batch, LH, n_tok_max, Fmax, rows[1], rows[2], rows[3], o, D.n_text_layer, &rm, s2);
   if (rc) return rc;
+  if (want_lp) {
+    HIPCHK(e->lp_out.ensure(sizeof(float) * (size_t)batch * n_tok_max));
+    rc = run_token_logprobs(e, s2, tokens_dev, batch, n_tok_max, o->sot_len, vocab_end, rows[1], lp_rows[0], lp_R, lp_nmax, (float*)e->lp_out.p);
+    if (rc) return rc;
+  }
   record(e, 7, s2);
-  // results -> pinned staging (ring of 2 so the host can post-process batch i while batch i+1 runs)
+  // results -> pinned staging (ring of 2 so the host can post-process batch i while batch i+1 runs): jump frames [batch][n_tok_max],
+  // top-k heads [batch][max(k, 1)], the two flag words, then (token log-probs only) the log-probs [batch][n_tok_max] as f32
   const int k = o->aggregation == WCA_AGGR_TOPK ? o->topk : 0;
   const int rs = (int)(e->enq_count & 1);
-  rc = ensure_res_host(e, rs, (size_t)batch * n_tok_max + (size_t)batch * (k > 0 ? k : 1) + 2);
+  const size_t lp_at = (size_t)batch * n_tok_max + (size_t)batch * (k > 0 ? k : 1) + 2;
+  rc = ensure_res_host(e, rs, lp_at + (want_lp ? (size_t)batch * n_tok_max : 0));
   if (rc) return rc;
+  if (want_lp)
+    HIPCHK(hipMemcpyAsync(e->res_host[rs] + lp_at, e->lp_out.p, sizeof(float) * (size_t)batch * n_tok_max, hipMemcpyDeviceToHost, s2));
   // the flags of this batch travel with its results (last two ints of the staging slot): phase 2's word, and the word phase 1
   // raised for this batch's cross-K/V slot (complete: s2 waited for ev_kv[bs], recorded behind that encoder)
   HIPCHK(hipMemcpyAsync(e->res_host[rs] + (size_t)batch * n_tok_max + (size_t)batch * (k > 0 ? k : 1), e->err_dev, sizeof(int),
@@ -2501,6 +2576,7 @@ int wca_align_batch_enqueue(wca_engine* e, const float* pcm_dev, int64_t pcm_str
   e->res_batch[rs] = batch;
   e->res_ntok[rs] = n_tok_max;
   e->res_topk[rs] = k;
+  e->res_lp[rs] = want_lp;
   e->res_kvslot[rs] = bs;
   e->last_batch = batch;
   e->enq_count++;
@@ -2693,12 +2769,19 @@ int wca_greedy_decode(wca_engine* e, const float* mel_dev, const float* pcm_dev,
 }
 
 int wca_align_batch_fetch(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host, int32_t* sel_idx_host) {
+  return wca_align_batch_fetch_ex(e, batch, n_tok_max, topk, jump_frame_host, sel_idx_host, nullptr);
+}
+
+int wca_align_batch_fetch_ex(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host, int32_t* sel_idx_host,
+                             float* token_logprob_host) {
   if (!e) return fail(WCA_ERR_INVALID, "null engine");
   HIPCHK(hipSetDevice(e->device));
   if (e->fetch_count >= e->enq_count) return fail(WCA_ERR_STATE, "nothing to fetch");
   const int rs = (int)(e->fetch_count & 1);  // oldest un-fetched batch
   if (batch != e->res_batch[rs] || n_tok_max != e->res_ntok[rs]) return fail(WCA_ERR_STATE, "fetch does not match the oldest pending enqueue");
   if (sel_idx_host && e->res_topk[rs] > 0 && topk != e->res_topk[rs]) return fail(WCA_ERR_STATE, "topk does not match the pending enqueue");
+  // (checked before anything is consumed: the caller can fetch the same batch again without them)
+  if (token_logprob_host && !e->res_lp[rs]) return fail(WCA_ERR_STATE, "token log-probs requested, but the pending batch was enqueued without them (vocab_end = 0)");
   HIPCHK(hipEventSynchronize(e->res_ev[rs]));
   if (jump_frame_host) memcpy(jump_frame_host, e->res_host[rs], sizeof(int) * (size_t)batch * n_tok_max);
   if (sel_idx_host && e->res_topk[rs] > 0)
@@ -2708,8 +2791,11 @@ int wca_align_batch_fetch(wca_engine* e, int batch, int n_tok_max, int topk, int
   e->fetch_count++;
   const int kk = e->res_topk[rs];
   const size_t fo = (size_t)batch * n_tok_max + (size_t)batch * (kk > 0 ? kk : 1);
+  if (token_logprob_host) memcpy(token_logprob_host, e->res_host[rs] + fo + 2, sizeof(float) * (size_t)batch * n_tok_max);
   const int flag = e->res_host[rs][fo] | (e->res_host[rs][fo + 1] & 2);
   if (flag & 2) return fail(WCA_ERR_HIP, "LayerNorm statistics hand-off timed out inside a GEMM epilogue (a workgroup of a row panel never arrived)");
+  if (flag == ERR_TARGET_VOCAB)
+    return fail(WCA_ERR_INVALID, "a teacher token is outside the scored vocabulary [0, vocab_end) (its log-prob is NaN)");
   if (flag)
     return fail(WCA_ERR_INVALID, "a token id is outside the model's vocabulary [0, %d) (tokenizer / checkpoint mismatch?)", e->dims.n_vocab);
   return WCA_OK;
@@ -2721,6 +2807,23 @@ int wca_align_batch(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, con
   int rc = wca_align_batch_enqueue(e, pcm_dev, pcm_stride, n_samples_host, tokens_dev, n_tok_max, n_tok_host, max_frames_host, batch, o);
   if (rc) return rc;
   return wca_align_batch_fetch(e, batch, n_tok_max, o->aggregation == WCA_AGGR_TOPK ? o->topk : 0, jump_frame_host, sel_idx_host);
+}
+
+int wca_token_logprobs(wca_engine* e, const float* logits_dev, int rows, int ld, int vocab_end, const int64_t* targets_dev, float* out_dev) {
+  if (!e) return fail(WCA_ERR_INVALID, "null engine");
+  if (!logits_dev || !targets_dev || !out_dev) return fail(WCA_ERR_INVALID, "null argument");
+  if (vocab_end < 1 || vocab_end > e->dims.n_vocab) return fail(WCA_ERR_INVALID, "vocab_end %d outside (0, %d]", vocab_end, e->dims.n_vocab);
+  if (rows < 0 || ld < vocab_end) return fail(WCA_ERR_INVALID, "rows %d / ld %d (need rows >= 0, ld >= vocab_end = %d)", rows, ld, vocab_end);
+  HIPCHK(hipSetDevice(e->device));
+  if (int rc = join_phase2(e)) return rc;
+  if (rows == 0) return WCA_OK;
+  int* err = e->err_dev + 3;   // (words 0-2 belong to the aligned batches)
+  HIPCHK(hipMemsetAsync(err, 0, sizeof(int), e->stream));
+  HIPCHK(launch_token_logprob(logits_dev, ld, vocab_end, rows, targets_dev, nullptr, 0, out_dev, err, ERR_TARGET_VOCAB, e->stream));
+  HIPCHK(hipMemcpyAsync(e->err_host + 3, err, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  if (e->err_host[3]) return fail(WCA_ERR_INVALID, "a target token is outside [0, vocab_end = %d) (its log-prob is NaN)", vocab_end);
+  return WCA_OK;
 }
 
 // ---------------------------------------------------------------- collation over RCCL (no torch involved)

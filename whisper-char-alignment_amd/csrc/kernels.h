@@ -151,6 +151,15 @@ hipError_t launch_decode_select(const DecodeSelectArgs& a, int B, hipStream_t s)
 // out[b] = softmax(logits[b])[token]  (no_speech_prob: the <|nospeech|> probability at the <|sot|> position)
 hipError_t launch_token_prob(const float* logits, int ld, int n_vocab, int token, float* out, int B, hipStream_t s);
 hipError_t launch_f32_to_f16(const float* in, half_t* out, size_t n, hipStream_t s);
+// ---------------------------------------------------------------- teacher-token log-probabilities (token_prob.hip)
+// the f32 rows that predict a text token: row (b, sot_len + i) of x [B * n_tok_max][d] for i < n_tok[b] - sot_len - 2 -> out [row_off[b] + i][d],
+// row_map[row_off[b] + i] = b * n_tok_max + i (n_tok, row_off: device [B]; n_text_max >= every n_text)
+hipError_t launch_gather_text_rows(const float* x, int n_tok_max, int d, int sot_len, const int* n_tok, const int* row_off, int B, int n_text_max,
+                                   float* out, int* row_map, hipStream_t s);
+// out[idx] = log_softmax(logits[r][0 : vocab_end])[targets[idx + tgt_off]] for r < rows, idx = row_map ? row_map[r] : r (logits rows ld floats
+// apart); a target outside [0, vocab_end) gives NaN and raises err_bit in *err
+hipError_t launch_token_logprob(const float* logits, long ld, int vocab_end, int rows, const int64_t* targets, const int* row_map, int tgt_off,
+                                float* out, int* err, int err_bit, hipStream_t s);
 
 // ---------------------------------------------------------------- log-mel (logmel.hip)
 struct LogMelArgs {

@@ -353,18 +353,24 @@ class WhisperAMD:
         return _lib.AlignOpts(_lib.AGGR_TOPK if aggregation == "topk" else _lib.AGGR_MEAN, int(topk), float(w_colnorm),
                               float(w_rownorm), float(w_coverage), int(sot_len), int(medfilt_width), float(qk_scale))
 
-    def align_batch(self, pcm, n_samples, tokens, n_tok, max_frames, opts, enqueue_only=False):
-        """Fused pipeline. pcm [B,stride] f32 cuda, tokens [B,n_max] int64 cuda. Returns (jump_frames [B,n_max] int32, sel [B,topk])."""
+    def align_batch(self, pcm, n_samples, tokens, n_tok, max_frames, opts, enqueue_only=False, token_logprobs_vocab_end=None):
+        """Fused pipeline. pcm [B,stride] f32 cuda, tokens [B,n_max] int64 cuda. Returns (jump_frames [B,n_max] int32, sel [B,topk]).
+        token_logprobs_vocab_end (tokenizer.eot): the teacher tokens' log-probabilities are computed on the GPU as well
+        (wca_align_batch_enqueue_ex) and returned as a third value [B,n_max] f32 (row b: n_tok[b] - sot_len - 2 entries, then 0);
+        after enqueue_only=True, fetch them with fetch(..., with_token_logprobs=True)."""
         B, n_max = tokens.shape
         self._bind_stream()
         # pcm=None re-uses the encoder state left by the preceding greedy_decode of the same batch
         args = (self._h, _ptr(pcm) if pcm is not None else None, pcm.shape[1] if pcm is not None else 0,
                 _lib.i32_array(n_samples) if n_samples is not None else None, _ptr(tokens), n_max, _lib.i32_array(n_tok),
                 _lib.i32_array(max_frames), B, C.byref(opts))
-        _lib.check(self._lib.wca_align_batch_enqueue(*args))
+        if token_logprobs_vocab_end is None:
+            _lib.check(self._lib.wca_align_batch_enqueue(*args))
+        else:
+            _lib.check(self._lib.wca_align_batch_enqueue_ex(*args, int(token_logprobs_vocab_end)))
         if enqueue_only:
             return None
-        return self.fetch(B, n_max, opts)
+        return self.fetch(B, n_max, opts, with_token_logprobs=token_logprobs_vocab_end is not None)
 
     def encode_batch(self, mel=None, pcm=None, n_samples=None):
         """C ABI wca_encode_batch: enqueue log-mel/encoder/cross-K/V of a micro-batch (no host sync). The state is picked up
@@ -419,13 +425,20 @@ class WhisperAMD:
         from . import decoding
         return decoding.decode(self, mel, options if options is not None else decoding.DecodingOptions())
 
-    def fetch(self, B, n_max, opts):
+    def fetch(self, B, n_max, opts, with_token_logprobs=False):
+        """Results of the oldest enqueued align_batch: (jump, sel), or (jump, sel, token_logprobs [B,n_max] f32) with
+        with_token_logprobs (the batch must have been enqueued with token_logprobs_vocab_end)."""
         k = opts.topk if opts.aggregation == _lib.AGGR_TOPK else 0
         jump = np.zeros((B, n_max), dtype=np.int32)
         sel = np.zeros((B, max(k, 1)), dtype=np.int32)
-        _lib.check(self._lib.wca_align_batch_fetch(self._h, B, n_max, k, jump.ctypes.data_as(_lib._pi32),
-                                                   sel.ctypes.data_as(_lib._pi32)))
-        return jump, (sel if k > 0 else None)
+        if not with_token_logprobs:
+            _lib.check(self._lib.wca_align_batch_fetch(self._h, B, n_max, k, jump.ctypes.data_as(_lib._pi32),
+                                                       sel.ctypes.data_as(_lib._pi32)))
+            return jump, (sel if k > 0 else None)
+        lp = np.zeros((B, n_max), dtype=np.float32)
+        _lib.check(self._lib.wca_align_batch_fetch_ex(self._h, B, n_max, k, jump.ctypes.data_as(_lib._pi32),
+                                                      sel.ctypes.data_as(_lib._pi32), lp.ctypes.data_as(_lib._pf)))
+        return jump, (sel if k > 0 else None), lp
 
     def set_profiling(self, on):
         _lib.check(self._lib.wca_set_profiling(self._h, 1 if on else 0))

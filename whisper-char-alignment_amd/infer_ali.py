@@ -47,7 +47,8 @@ from .dataset import AMI, TIMIT, LibriSpeech  # noqa: E402
 from .engine import WhisperAMD, dims_for, MAX_FRAMES, MAX_LENGTH  # noqa: E402
 from .metrics import eval_n1, eval_n1_strict, get_seg_metrics  # noqa: E402
 from .retokenize import encode, remove_punctuation  # noqa: E402
-from .timing import words_from_jump_frames, default_find_alignment  # noqa: E402
+from .timing import words_from_jump_frames, default_find_alignment, word_probabilities  # noqa: E402
+from .timing import get_attentions, token_logprobs, _default_alignment_from_weights  # noqa: E402
 from .audio import log_mel_spectrogram, pad_or_trim  # noqa: E402
 from .tokenizer import get_tokenizer  # noqa: E402
 from .decoding import DecodingOptions, decode  # noqa: E402
@@ -170,6 +171,9 @@ def infer_dataset(args, model=None):
     corrects = total_preds = total_gts = 0
     all_predictions = {}
     local_times = {}
+    local_conf = {}   # --word_confidence: utterance index -> per-word probabilities
+    word_conf = bool(getattr(args, "word_confidence", False))
+    lp_vocab_end = tokenizer.eot if word_conf else None   # teacher-token log-probs over the text vocabulary [:eot]
     stager = PinnedStager(device)
 
     def prepare(n, item):
@@ -186,14 +190,19 @@ def infer_dataset(args, model=None):
         return dict(index=n, pcm=pcm, tokens=tokens, text_tokens=text_tokens, max_frames=int(max_frames), texts=texts,
                     starts=starts, ends=ends, fid=fid, skip_early=skip)
 
-    def score(b, words, start_times, end_times):
-        """infer_ali.py:114-132 for one utterance."""
+    def score(b, words, start_times, end_times, confidence=None):
+        """infer_ali.py:114-132 for one utterance. confidence (--word_confidence): (per-word probabilities, sum of the teacher
+        tokens' log-probs)."""
         nonlocal corrects, total_preds, total_gts
         ends_hat = end_times
         local_times[b["index"]] = (np.asarray(start_times, dtype=np.float64), np.asarray(end_times, dtype=np.float64))
+        if confidence is not None:
+            local_conf[b["index"]] = np.asarray(confidence[0], dtype=np.float64)
         if args.save_prediction:
             all_predictions[b["index"]] = dict(starts=b["starts"], ends=b["ends"], texts=b["texts"].split(), starts_hat=start_times,
                                                ends_hat=ends_hat, predwords=words, fids=b["fid"])
+            if confidence is not None:
+                all_predictions[b["index"]].update(word_probs_hat=confidence[0], text_logprob=confidence[1])
         if not args.strict:
             c, _ = eval_n1(b["ends"], ends_hat, args.tolerance)
             total_gts += len(b["ends"])
@@ -223,12 +232,17 @@ def infer_dataset(args, model=None):
     def finish(entry):
         """Host tail of a micro-batch whose GPU work was enqueued earlier: fetch the jump frames, merge words, score."""
         batch, n_max, _keep = entry
-        jump, _ = model.fetch(len(batch), n_max, opts)
+        res = model.fetch(len(batch), n_max, opts, with_token_logprobs=word_conf)
+        jump = res[0]
         for j, b in enumerate(batch):
             if b.get("skip"):
                 continue
             words, start_times, end_times = words_from_jump_frames(jump[j], b["text_tokens"], tokenizer, args.aligned_unit_type)
-            score(b, words, start_times, end_times)
+            confidence = None
+            if word_conf:
+                lp = res[2][j][:len(b["text_tokens"])]
+                confidence = (word_probabilities(lp, b["text_tokens"], tokenizer, args.aligned_unit_type), float(np.sum(lp, dtype=np.float64)))
+            score(b, words, start_times, end_times, confidence)
 
     enqueued = collections.deque()  # micro-batches in flight in the engine (at most 2)
 
@@ -239,7 +253,7 @@ def infer_dataset(args, model=None):
         pcm_dev, n_samples = stager.upload(batch)
         toks_dev, n_max = token_matrix(batch)
         model.align_batch(pcm_dev, n_samples, toks_dev, [len(b["tokens"]) for b in batch], [b["max_frames"] for b in batch], opts,
-                          enqueue_only=True)
+                          enqueue_only=True, token_logprobs_vocab_end=lp_vocab_end)
         enqueued.append((batch, n_max, (pcm_dev, toks_dev)))  # the device buffers stay alive until the fetch
         while len(enqueued) > 1:
             finish(enqueued.popleft())
@@ -265,7 +279,8 @@ def infer_dataset(args, model=None):
                 b["text_tokens"] = []
                 b["tokens"] = [*tokenizer.sot_sequence, tokenizer.no_timestamps, tokenizer.eot]
         toks_dev, n_max = token_matrix(batch)
-        model.align_batch(None, None, toks_dev, [len(b["tokens"]) for b in batch], [b["max_frames"] for b in batch], opts, enqueue_only=True)
+        model.align_batch(None, None, toks_dev, [len(b["tokens"]) for b in batch], [b["max_frames"] for b in batch], opts, enqueue_only=True,
+                          token_logprobs_vocab_end=lp_vocab_end)
         finish((batch, n_max, toks_dev))
 
     pending, in_flight = [], []
@@ -284,9 +299,20 @@ def infer_dataset(args, model=None):
                 if len(text_tokens) + len(tokenizer.sot_sequence) + 2 > MAX_LENGTH:
                     print(b["fid"])
                     continue
-            words, start_times, end_times, _ws, _ = default_find_alignment(model, tokenizer, text_tokens, mel, b["max_frames"],
-                                                                         medfilt_width=args.medfilt_width)
-            score(b, words, start_times, end_times)  # honours --strict / --save_prediction like infer_ali.py:114-132
+            if not word_conf:
+                words, start_times, end_times, _ws, _ = default_find_alignment(model, tokenizer, text_tokens, mel, b["max_frames"],
+                                                                             medfilt_width=args.medfilt_width)
+                confidence = None
+            else:
+                # default_find_alignment's own steps, keeping the forward's logits (timing.py:146-150): one forward serves both
+                tokens = torch.tensor([*tokenizer.sot_sequence, tokenizer.no_timestamps, *text_tokens, tokenizer.eot]).to(model.device)
+                weights, logits = get_attentions(mel, tokens, model, tokenizer, b["max_frames"], args.medfilt_width)
+                words, start_times, end_times, _ws, _ = _default_alignment_from_weights(model, weights.contiguous(), model.alignment_heads,
+                                                                                      text_tokens, tokenizer)
+                lp = token_logprobs(logits, tokens.tolist(), tokenizer).cpu().numpy()
+                # (this path's words come from tokenizer.split_to_word_tokens, timing.py:173, whatever --aligned_unit_type says)
+                confidence = (word_probabilities(lp, text_tokens, tokenizer, "subword"), float(np.sum(lp, dtype=np.float64)))
+            score(b, words, start_times, end_times, confidence)  # honours --strict / --save_prediction like infer_ali.py:114-132
             n_done += 1
             continue
         pending.append(b)
@@ -313,6 +339,9 @@ def infer_dataset(args, model=None):
 
     corrects, total_preds, total_gts = _shard.allreduce_counters(corrects, total_preds, total_gts)
     all_times = _shard.allgather_results(local_times)
+    if word_conf:
+        # the word probabilities travel in the same packed collective as the word times (both halves of an entry carry them)
+        all_conf = _shard.allgather_results({i: (p, p) for i, p in local_conf.items()})
     if args.save_prediction:
         all_predictions = _shard.gather_predictions(all_predictions)  # every rank's dict on rank 0 (None elsewhere)
     if rank == 0:
@@ -323,10 +352,13 @@ def infer_dataset(args, model=None):
         filename = datetime.datetime.fromtimestamp(time.time()).strftime("%Y-%m-%d-%H:%M:%S")
         os.makedirs(args.output_dir, exist_ok=True)
         notes = {}
+        if word_conf:
+            conf = np.concatenate([p for p, _ in all_conf.values()]) if all_conf else np.zeros(0)
+            notes["mean_word_prob"] = float(np.mean(conf)) if conf.size else None
         if args.teacher == "text":
             notes["teacher_note"] = "ground-truth transcript teacher-forced; the reference aligns the ASR hypothesis (infer_ali.py:60-68)"
         with open(os.path.join(args.output_dir, filename + ".json"), "w") as f:
-            json.dump({**vars(args), **results, **notes, "utterances": len(all_times), "seconds": elapsed}, f)
+            json.dump({**{k: v for k, v in vars(args).items() if k != "word_confidence" or v}, **results, **notes, "utterances": len(all_times), "seconds": elapsed}, f)
         if args.save_prediction:
             import joblib
             joblib.dump(all_predictions, os.path.join(args.output_dir, filename + "-predictions.pkl"))
@@ -369,6 +401,10 @@ def parse_args(argv=None):
                         "against the exact f16 weights (the reference's fp32 forward to fp32 summation noise; word times equal the CPU reference's); "
                         "f16: operands rounded to f16 once -- 1.9x faster, word times within one frame for ~98.5 %% of the boundaries")
     p.add_argument("--readers", type=int, default=4, help="reader threads (audio decode + tokenisation ahead of the GPU)")
+    p.add_argument("--word_confidence", action="store_true",
+                   help="per-word probabilities (openai-whisper's word `probability`: the mean over a word's tokens of the teacher token's "
+                        "softmax probability over the text vocabulary [:eot]), computed on the GPU; with --save_prediction every record "
+                        "gains word_probs_hat and text_logprob, and the result JSON gains mean_word_prob")
     return p.parse_args(argv)
 
 

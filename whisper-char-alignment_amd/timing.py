@@ -205,6 +205,60 @@ def default_find_alignment(model, tokenizer, text_tokens, mel, max_frames, *, me
     return _default_alignment_from_weights(model, weights.contiguous(), model.alignment_heads, text_tokens, tokenizer)
 
 
+def token_logprobs(logits, tokens, tokenizer):
+    """Teacher-token log-probabilities of one utterance (timing.py:146-149 in log space) through wca_token_logprobs:
+    logits (n, V) f32 as get_attentions returns them, tokens the same 1-D sequence [*sot_sequence, no_timestamps, *text, eot].
+    Returns a float32 GPU tensor of n_text = n - len(sot_sequence) - 2 values,
+    out[i] = log_softmax(logits[len(sot_sequence) + i, :eot])[tokens[len(sot_sequence) + 1 + i]] (eot itself is not scored).
+    A text token >= eot raises WcaError (upstream raises IndexError)."""
+    logits = _as_cuda_f32(logits)
+    sot_len = len(tokenizer.sot_sequence)
+    n, V = logits.shape
+    n_text = len(tokens) - sot_len - 2
+    if n < len(tokens):
+        raise ValueError("logits have %d rows for %d tokens" % (n, len(tokens)))
+    out = torch.zeros(max(n_text, 0), device=logits.device, dtype=torch.float32)
+    if n_text <= 0:
+        return out
+    vocab_end = int(tokenizer.eot)
+    if vocab_end > V:
+        raise ValueError("tokenizer.eot %d outside the logits' %d columns" % (vocab_end, V))
+    rows = logits[sot_len:sot_len + n_text]
+    targets = torch.as_tensor(tokens)[sot_len + 1:sot_len + 1 + n_text].to(logits.device, torch.int64).contiguous()
+    eng = _engine_for(logits.device)
+    eng._bind_stream()
+    _lib.check(eng._lib.wca_token_logprobs(eng._h, C.c_void_p(rows.data_ptr()), n_text, V, vocab_end, C.c_void_p(targets.data_ptr()),
+                                           C.c_void_p(out.data_ptr())))
+    return out
+
+
+def _word_boundaries(text_tokens, tokenizer, aligned_unit_type):
+    """The word_boundaries of force_align / words_from_jump_frames for `text_tokens` + [eot] (char_word_starts on the char fast
+    path, split_tokens_on_spaces otherwise), or None when the text has at most one word (timing.py:106-107)."""
+    from .retokenize import char_word_starts
+    toks = list(text_tokens) + [tokenizer.eot]
+    starts = char_word_starts(toks, tokenizer) if aligned_unit_type == "char" else None
+    if starts is None:
+        _words, word_tokens = split_tokens_on_spaces(toks, tokenizer, aligned_unit_type)
+        if len(word_tokens) <= 1:
+            return None
+        return np.pad(np.cumsum([len(t) for t in word_tokens[:-1]]), (1, 0))
+    return starts if len(starts) > 1 else None
+
+
+def word_probabilities(token_logprobs, text_tokens, tokenizer, aligned_unit_type="char"):
+    """Per-word confidence (timing.py:181-184): the mean over each word's tokens of exp(token log-prob), one value per returned word
+    (aligned with force_align's / words_from_jump_frames' start_times and end_times); [] when the text has at most one word.
+    token_logprobs: the n_text = len(text_tokens) values of one utterance (a row of align_batch's token log-probs, or
+    token_logprobs()); a word's span is clipped to the text tokens like the reference's list slice."""
+    wb = _word_boundaries(text_tokens, tokenizer, aligned_unit_type)
+    if wb is None:
+        return []
+    lp = token_logprobs.detach().cpu().numpy() if isinstance(token_logprobs, torch.Tensor) else np.asarray(token_logprobs)
+    probs = np.exp(lp[:len(text_tokens)].astype(np.float64)).tolist()
+    return [float(np.mean(probs[i:j])) for i, j in zip(wb[:-1], wb[1:])]
+
+
 def words_from_jump_frames(jump_frames, tokens, tokenizer, aligned_unit_type="char", want_words=True):
     """Host tail of the fused wca_align_batch path: `jump_frames[i]` is the frame at which the DTW path
     enters text row i (= time_indices[jumps], timing.py:110-111); returns (words, start_times, end_times)
