@@ -16,14 +16,20 @@ all-reduce) inside the timed region.
 
 The forward runs in the engine's REFERENCE precision mode (wca_set_precision(WCA_PRECISION_REFERENCE = SPLIT): every stage on f16
 (hi, lo) operand pairs -- the only site set that reproduces the fp32 CPU reference's word times with margin on the 301-utterance
-parity leg, profiles/r04_precision_ablation.txt) -- that is `value`. The f16-operand fast mode of the same engine is timed right
+parity leg, profiles/r04_precision_ablation.txt) -- that is `value`. With --full, the f16-operand fast mode of the same engine is timed
 after it and reported as the secondary object `f16_operating_point` (it misses the one-frame tolerance on ~1.5 % of the boundaries).
 
 Prints ONE JSON line on rank 0 (contract in the task statement) including
   * `roofline`: the encoder kernel with the LARGEST total time in the step (HIP-event pairs around every launch of every
-    encoder kernel site, recorded live on the stream the kernels run on), `kernels`: the same figures for every site;
+    encoder kernel site, recorded live on the stream the kernels run on), `kernels`: the same figures for every site.
+
+A plain run does only what that line needs: set up, warm up, time the steps, write --dump-outputs, print. `--full` adds, after
+the timed steps and outside them (one rank only):
   * `cpu_baseline`: the oracle's PyTorch-CPU restatement of the same pipeline timed on this box's host cores on a bounded
-    sample, and the parity of the GPU path against it at exactly the timed configuration.
+    sample, and the parity of the GPU path against it at exactly the timed configuration;
+  * `f16_operating_point` (contract precision only): the f16-operand mode timed on a shorter region, with its parity;
+  * `cpu_baseline.parity_alignment_like`: the parity leg on the alignment-like checkpoint.
+Without --full, `cpu_baseline` is null.
 """
 import argparse
 import importlib
@@ -65,7 +71,9 @@ def parse():
     ap.add_argument("--chars", type=int, default=64)
     ap.add_argument("--topk", type=int, default=10)
     ap.add_argument("--medfilt_width", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the CPU baseline, its parity legs and the f16 operating point "
+                    "(one rank only; a plain run prints the headline line without them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and everything that follows it")
     ap.add_argument("--cpu-utts", type=int, default=32, help="utterances timed by the CPU baseline (after 1 warm-up)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (0 = every core this process may use, measured; recorded in the line)")
     ap.add_argument("--aligned-utts", type=int, default=8, help="utterances of the second parity leg (alignment-like planted checkpoint: "
@@ -746,7 +754,7 @@ def main():
             print("stage ms/step (last step): " + ", ".join("%s=%.3f" % (n, v) for n, v in zip(names, stage_ms)), file=sys.stderr)
             print("encoder kernel sites (%d sampled steps of the timed region): " % sampled_steps + ", ".join("%s=%.3f ms x%d (%.0f %s)" % (
                 s_, k["avg_launch_ms"], k["launches"], k["achieved"], k["unit"]) for s_, k in kernels.items()), file=sys.stderr)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             oracle_times = []
             out["cpu_baseline"] = cpu_baseline(args, sd, dims, syn, audio_mod, oracle_times)
             # same utterances through the GPU path at the timed configuration, checked against the oracle's word times

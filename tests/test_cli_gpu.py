@@ -341,7 +341,7 @@ print("snippet ok")
 
 
 def test_bench_line_contract_and_rccl_collation_path():
-    """bench.py end to end on a tiny model: ONE JSON line with the contract's keys + roofline + cpu_baseline, the oracle parity
+    """bench.py --full end to end on a tiny model: ONE JSON line with the contract's keys + roofline + cpu_baseline, the oracle parity
     leg at the timed configuration, and (WCA_FORCE_DIST=1) the RCCL process group / GPU all-gather / barrier path that the
     N > 1 runs take, with one rank."""
     import json
@@ -351,8 +351,8 @@ def test_bench_line_contract_and_rccl_collation_path():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, WCA_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--model", "tiny", "--batch", "4", "--steps", "4", "--warmup", "1",
-                        "--distinct-batches", "2", "--seconds", "4", "--chars", "24", "--cpu-utts", "2", "--aligned-utts", "2"], capture_output=True, text=True,
-                       timeout=600, env=env, cwd=root)
+                        "--distinct-batches", "2", "--seconds", "4", "--chars", "24", "--cpu-utts", "2", "--aligned-utts", "2", "--full"], capture_output=True,
+                       text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -375,6 +375,25 @@ def test_bench_line_contract_and_rccl_collation_path():
     assert par["precision"] == "reference" and par["batch_invariant"] and par["within_one_frame"] == par["word_boundaries"], par   # no exclusions
     pal = cb["parity_alignment_like"]
     assert pal["utterances"] == 2 and pal["word_boundaries"] > 0 and pal["within_one_frame"] == pal["word_boundaries"], pal
+
+
+def test_bench_plain_run_leaves_the_full_legs_out():
+    """bench.py without --full prints the headline line only: no CPU baseline, none of its parity legs, no f16 operating point (those
+    run with --full, test_bench_line_contract_and_rccl_collation_path)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--model", "tiny", "--batch", "4", "--steps", "3", "--warmup", "1",
+                        "--distinct-batches", "2", "--seconds", "4", "--chars", "24", "--cpu-utts", "2", "--aligned-utts", "2"], capture_output=True,
+                       text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["config"]["collated_utterances"] == 12
+    assert d["dtype"].startswith("f16x2") and d["config"]["precision"].startswith("reference") and "kernels" in d and d["roofline"]["achieved"] > 0
+    assert d["cpu_baseline"] is None and "f16_operating_point" not in d
+    assert "cpu baseline utterance" not in r.stderr and "alignment-like parity" not in r.stderr
 
 
 def test_bench_collation_through_the_c_abi():
