@@ -95,7 +95,7 @@ typedef struct {
 } wca_align_opts;
 
 const char* wca_last_error(void);
-int wca_version(void);
+int wca_version(void);   /* 7: the engine has exactly two precision modes, F16 and SPLIT (the per-stage precision mask is gone) */
 
 /* ---- engine lifetime ------------------------------------------------------------------------ */
 /* A new engine is in the CONTRACT precision mode (WCA_PRECISION_REFERENCE: every stage on (hi, lo) operand pairs = the fp32 forward of
@@ -120,7 +120,7 @@ int wca_finalize_weights(wca_engine* e);
  * positional embeddings stay fp32. An fp32 source tensor whose values are NOT f16-representable (a fine-tuned fp32 state dict, which the
  * reference runs in true fp32) is not rounded away: wca_load_weight keeps the remainder lo = f16(w - f16(w)) of every such element in a second
  * slab (w = hi + lo to 2^-22 |w|, the representation the activations travel in) and counts the elements per tensor (wca_weights_inexact:
- * tensors, values, name of the first one). While a precision site is on pairs its GEMMs multiply the extra term A_hi W_lo^T for those
+ * tensors, values, name of the first one). In split mode the GEMMs multiply the extra term A_hi W_lo^T for those
  * matrices (one more f16 pass: an accumulating launch for the residual GEMMs, a pre-activation addend for the others; the embedding adds
  * hi + lo) -- slower, never a narrower model. wca_set_allow_rounded_weights(e, 1) drops the remainders (the engine then computes what the
  * f16-rounded checkpoint computes); the f16 mode (approximate by definition) ignores them. */
@@ -431,46 +431,18 @@ int wca_set_fuse_ln(wca_engine* e, int on);
  *     the fp32 accumulator); attention runs three passes per product (hi.hi + hi.lo + lo.hi), GELU uses erff, the log-mel
  *     DFT accumulates in f64. What is left is fp32 summation-order noise, like between two fp32 BLAS libraries. Costs
  *     ~2.3x the MFMA work, twice the operand memory and a second copy of the weights ([N][2K]).
+ *   WCA_PRECISION_REFERENCE = WCA_PRECISION_SPLIT: the CONTRACT mode. A new engine (wca_engine_create), bench.py's `value` and the CLI
+ *     run in this mode. Every stage is split: the log-mel DFT, the conv stem, the encoder blocks' GEMMs and self-attention, ln_post and
+ *     the cross-attention key / value projection, the teacher-forced decoder and the hooked cross-attention (timing.py:50-55). The
+ *     per-stage ablation on the 301-utterance parity leg (profiles/r04_precision_ablation.txt) showed that nothing from the encoder
+ *     blocks on can be left on single f16 operands, and that leaving only the log-mel and the conv stem on them moves the head
+ *     selection scores by 1e-4 relative (all stages split: 4e-6) and misses two near-tied utterances of a 700-utterance leg
+ *     (profiles/r04_parity_leg_700utt.txt).
  * The greedy ASR pre-pass (wca_greedy_decode) computes in f16 in both modes, like whisper.decode's fp16 default.
  * Switching re-creates the activation arena: no batch may be in flight, encoded-but-unconsumed states are dropped. */
-/*   WCA_PRECISION_REFERENCE = WCA_PRECISION_SPLIT: the CONTRACT mode -- every site split. A new engine (wca_engine_create), bench.py's
- *     `value` and the CLI run in this mode. The per-site ablation on the 301-utterance parity leg (profiles/r04_precision_ablation.txt, tools/precision_ablation.py)
- *     shows that nothing from the encoder blocks on can be left on single f16 operands: every smaller site set misses at least one
- *     utterance whose 10th / 11th oracle head scores are within 5e-5 of each other. Leaving only the log-mel and the conv stem on
- *     single operands changes no boundary on that leg and costs 1 % less, but moves the selection scores by 1e-4 relative
- *     (all sites split: 4e-6), and on a second leg of 700 utterances (profiles/r04_parity_leg_700utt.txt) it misses two utterances
- *     whose oracle scores are tied to 1e-5 while all sites give 14 234 / 14 234 boundaries identical: it is not the contract. */
-enum { WCA_PRECISION_F16 = 0, WCA_PRECISION_SPLIT = 1, WCA_PRECISION_REFERENCE = 1, WCA_PRECISION_MIXED = 2 };
+enum { WCA_PRECISION_F16 = 0, WCA_PRECISION_SPLIT = 1, WCA_PRECISION_REFERENCE = 1 };
 int wca_set_precision(wca_engine* e, int mode);   /* F16 or SPLIT (= REFERENCE) */
-int wca_get_precision(wca_engine* e);  /* F16: no site is split; SPLIT: every site; MIXED: some (wca_get_precision_sites) */
-/* Per-site precision control: WHICH stages of the forward of timing.py:58 carry their operands as (hi, lo) pairs. A set bit
- * puts that stage on reference-precision arithmetic (above); a clear bit leaves it on single f16 operands. Seams need no
- * conversion pass: a producer stores the pair when its consumer is split (every GEMM / LayerNorm / log-mel epilogue can), a
- * single-precision consumer of a pair buffer reads the hi halves (hi IS f16(x)), and a split GEMM behind a single-precision
- * attention reads the single f16 rows it got.
- *   LOGMEL     log-mel DFT + filterbank sums in f64 (dataset.py:46-48 -> whisper.log_mel_spectrogram)
- *   CONV       conv stem: conv1 + GELU, conv2 + GELU + positional embedding (AudioEncoder.forward)
- *   ENC_GEMM   encoder blocks >= enc_first_layer: attn_ln / mlp_ln outputs as pairs, QKV / out-projection / fc1 / fc2 K-doubled
- *   ENC_ATTN   encoder blocks >= enc_first_layer: three-pass self-attention on q / k / v pairs
- *   CROSS_KV   ln_post output as pairs + the fused cross-attention key / value projection of every decoder layer K-doubled
- *   DEC        teacher-forced decoder: its LayerNorms, QKV / out / cross-query / cross-out / MLP GEMMs and causal self-attention
- *   CAPTURE    the hooked cross-attention (timing.py:50-55): q and the cross K / V rows as pairs, three-pass q.k^T (the captured
- *              logits) and P.V
- * wca_set_precision(SPLIT) == wca_set_precision_sites(WCA_PSITE_ALL, 0); F16 == mask 0. enc_first_layer in [0, n_audio_layer].
- * Same state rules as wca_set_precision (no batch in flight). The arena is widened (and the K-doubled weight copies exist)
- * whenever any bit is set. */
-enum {
-  WCA_PSITE_LOGMEL = 1,
-  WCA_PSITE_CONV = 2,
-  WCA_PSITE_ENC_GEMM = 4,
-  WCA_PSITE_ENC_ATTN = 8,
-  WCA_PSITE_CROSS_KV = 16,
-  WCA_PSITE_DEC = 32,
-  WCA_PSITE_CAPTURE = 64,
-  WCA_PSITE_ALL = 127
-};
-int wca_set_precision_sites(wca_engine* e, unsigned mask, int enc_first_layer);
-int wca_get_precision_sites(wca_engine* e, unsigned* mask_out, int* enc_first_layer_out);
+int wca_get_precision(wca_engine* e);             /* F16 or SPLIT */
 /* on (default): phase 2 (decoder, post-processing, DTW) of a batch runs on the engine's second stream beside the next
  * batch's phase 1; off: everything on one stream, so that rocprofv3 per-kernel durations are not inflated by sharing
  * the CUs (profiling aid; throughput drops by the overlap's worth). No batch may be in flight when it is changed. */

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""Which stages of the forward need reference-precision operands?
+"""The precision modes, and the passes of the split mode's attention, against the fp32 oracle
 
-For every row of a table of precision-site masks (wca_set_precision_sites) this aligns the SAME utterances -- bench.py's parity
-leg: whisper-medium dims, peaky seeded weights, 10 s audio, 64-char text, topk 10, medfilt 3, fused wca_align_batch at B = 64 --
-against the fp32 CPU oracle's word times and measures the throughput of the same loop bench.py times.
+For every row -- the f16 mode, the full split mode (wca_set_precision), or with --attn-drop the split mode without some of the
+encoder pair attention's passes -- this aligns the SAME utterances -- bench.py's parity leg: whisper-medium dims, peaky seeded
+weights, 10 s audio, 64-char text, topk 10, medfilt 3, fused wca_align_batch at B = 64 -- against the fp32 CPU oracle's word times
+and measures the throughput of the same loop bench.py times. (profiles/r04_precision_ablation.txt also holds rows of single
+stages on pairs: the engine no longer has that control.)
 
   python tools/precision_ablation.py [--utts 301] [--steps 24] [--rows NAME,NAME...] [--out gpurun_out/r04_precision_ablation.txt]
 
@@ -23,21 +25,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-# name -> (sites, first encoder block of the ENC_* bits)
+# name -> (precision mode, pass mask of the encoder's pair attention: wca_test_set_attn_split_drop)
 ROWS = [
-    ("f16", "", 0),
-    ("capture", "capture", 0),
-    ("cross_kv+capture", "cross_kv,capture", 0),
-    ("dec+cross_kv+capture", "dec,cross_kv,capture", 0),
-    ("decoder side + logmel + conv", "logmel,conv,dec,cross_kv,capture", 0),
-    ("decoder side + enc_attn (all 24)", "enc_attn,dec,cross_kv,capture", 0),
-    ("decoder side + enc last 6", "enc_gemm,enc_attn,dec,cross_kv,capture", 18),
-    ("decoder side + enc last 12", "enc_gemm,enc_attn,dec,cross_kv,capture", 12),
-    ("decoder side + enc_gemm (all 24)", "enc_gemm,dec,cross_kv,capture", 0),
-    ("decoder side + enc all 24 (no logmel/conv)", "enc_gemm,enc_attn,dec,cross_kv,capture", 0),
-    ("encoder side only (logmel,conv,enc)", "logmel,conv,enc_gemm,enc_attn", 0),
-    ("all but enc_attn", "logmel,conv,enc_gemm,cross_kv,dec,capture", 0),
-    ("full split", "all", 0),
+    ("f16", "f16", 0),
+    ("full split", "split", 0),
 ]
 
 
@@ -101,9 +92,9 @@ def main():
     ap.add_argument("--chars", type=int, default=64)
     ap.add_argument("--topk", type=int, default=10)
     ap.add_argument("--medfilt_width", type=int, default=3)
-    ap.add_argument("--rows", default="", help="comma-separated row names (default: every row of the table); 'sites:a+b@first' adds a row")
+    ap.add_argument("--rows", default="", help="comma-separated row names (default: every row of the table)")
     ap.add_argument("--attn-drop", default="", help="comma-separated pass masks of the encoder's pair attention (wca_test_set_attn_split_drop: 1 K_lo Q_hi, 2 K_hi Q_lo, "
-                    "4 V_lo P_hi, 8 V_hi P_lo; 0, 1, 2, 3, 4, 8, 12, 15 exist): every mask becomes a row in the all-sites mode (VERDICT r4 item 2)")
+                    "4 V_lo P_hi, 8 V_hi P_lo; 0, 1, 2, 3, 4, 8, 12, 15 exist): every mask becomes a row in the split mode (VERDICT r4 item 2)")
     ap.add_argument("--oracle-only", action="store_true", help="compute / complete the oracle cache and stop (CPU only: runs without a GPU)")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "r04_precision_ablation.txt"))
     args = ap.parse_args()
@@ -143,30 +134,22 @@ def main():
     rows = list(ROWS)
     if args.rows:
         want = [r.strip() for r in args.rows.split(",") if r.strip()]
-        sel = []
-        for w in want:
-            if w.startswith("sites:"):
-                spec, _, first = w[6:].partition("@")
-                sel.append((w, spec.replace("+", ","), int(first or 0)))
-            else:
-                sel += [r for r in ROWS if r[0] == w]
-        rows = sel
+        rows = [r for w in want for r in ROWS if r[0] == w]
 
     drop_names = {0: "all six passes (contract)", 1: "without K_lo Q_hi", 2: "without K_hi Q_lo", 3: "S from K_hi Q_hi alone", 4: "without V_lo P_hi",
                   8: "without V_hi P_lo", 9: "without K_lo Q_hi and V_hi P_lo", 12: "O from V_hi P_hi alone", 15: "one pass per product (pair operands elsewhere)"}
     if args.attn_drop:
-        rows = [("attention passes: %s [mask %d]" % (drop_names.get(int(x), "?"), int(x)), "all", -1 - int(x)) for x in args.attn_drop.split(",")]
+        rows = [("attention passes: %s [mask %d]" % (drop_names.get(int(x), "?"), int(x)), "split", int(x)) for x in args.attn_drop.split(",")]
 
     lines = []
-    hdr = "%-46s %9s %9s | %7s %7s %7s | %5s %5s | %s" % ("sites (encoder bits from block)", "utt/s", "ms/step", "bounds", "within", "ident", "utts", "clean", "head-score deviation from the oracle (relative, all L x H heads) | offenders (utt:boundaries off, same heads?, oracle k/k+1 gap)")
+    hdr = "%-46s %9s %9s | %7s %7s %7s | %5s %5s | %s" % ("precision", "utt/s", "ms/step", "bounds", "within", "ident", "utts", "clean", "head-score deviation from the oracle (relative, all L x H heads) | offenders (utt:boundaries off, same heads?, oracle k/k+1 gap)")
     lines.append(hdr)
     print(hdr, flush=True)
     records = []
-    for name, sites, first in rows:
-        if first < 0:   # an attention-pass row: all sites on pairs, the mask on the encoder's pair attention
-            wca._lib.check(model._lib.wca_test_set_attn_split_drop(-1 - first))
-            first = 0
-        model.set_precision_sites(sites, first)
+    for name, mode, drop in rows:
+        if args.attn_drop:   # an attention-pass row: the split mode, the mask on the encoder's pair attention
+            wca._lib.check(model._lib.wca_test_set_attn_split_drop(drop))
+        model.set_precision(mode)
         # ---- parity
         total = within = ident = clean = 0
         offenders = []
@@ -222,12 +205,11 @@ def main():
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
         rate = args.batch * args.steps / el
-        label = "%s%s" % (name, (" [from %d]" % first) if first else "")
         sc_rms = (sc_dev_sq / max(sc_n, 1)) ** 0.5
-        line = "%-46s %9.1f %9.2f | %7d %7d %7d | %5d %5d | score dev max %.1e rms %.1e | %s" % (label, rate, 1e3 * el / args.steps, total, within, ident, len(ids), clean, sc_dev_max, sc_rms, " ".join(offenders[:12]))
+        line = "%-46s %9.1f %9.2f | %7d %7d %7d | %5d %5d | score dev max %.1e rms %.1e | %s" % (name, rate, 1e3 * el / args.steps, total, within, ident, len(ids), clean, sc_dev_max, sc_rms, " ".join(offenders[:12]))
         lines.append(line)
         print(line, flush=True)
-        records.append(dict(row=name, sites=sites, enc_first_layer=first, utt_per_s=rate, ms_per_step=1e3 * el / args.steps, boundaries=total, within_one_frame=within,
+        records.append(dict(row=name, precision=mode, attn_drop=drop, utt_per_s=rate, ms_per_step=1e3 * el / args.steps, boundaries=total, within_one_frame=within,
                             identical=ident, utterances=len(ids), utterances_clean=clean, offenders=offenders,
                             score_rel_dev_max=sc_dev_max, score_rel_dev_rms=sc_rms))
     if args.attn_drop:

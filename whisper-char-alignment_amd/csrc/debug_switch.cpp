@@ -23,7 +23,7 @@ Sw g_sw[DBG_SWITCH_COUNT] = {
     {"head_stats_general", "WCA_HEAD_STATS_GENERAL", {0}, {0}},     // 1: the general head-statistics kernel
     {"gemm_supertile", "WCA_GEMM_SUPERTILE", {0}, {0}},             // > 0: m-panels per supertile of the persistent GEMM's tile order
     {"ln_pair_v4", "WCA_LN_PAIR_V4", {0}, {0}},                     // 1: the four-wide pair LayerNorm
-    {"fail_precision_alloc", "WCA_TEST_FAIL_PRECISION_ALLOC", {0}, {0}},  // 1: inject an allocation failure into wca_set_precision_sites
+    {"fail_precision_alloc", "WCA_TEST_FAIL_PRECISION_ALLOC", {0}, {0}},  // 1: inject an allocation failure into wca_set_precision
     {"attn_split_drop", nullptr, {0}, {0}},                         // pass mask of the encoder's pair attention (wca_test_set_attn_split_drop)
     {"gemm_ring", "WCA_GEMM_RING", {0}, {0}},                       // 1: the pair GEMM on round 4's two-slot rings (default: three A slots + one W slot)
 };

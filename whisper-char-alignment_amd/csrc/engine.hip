@@ -133,9 +133,9 @@ struct wca_engine {
   bool profiling = false;
   std::set<std::string> loaded;
   std::map<std::string, size_t> inexact;  // tensors stored as f16 whose fp32 source values were NOT f16-representable: name -> count of rounded elements
-  bool allow_rounded = false;             // wca_set_allow_rounded_weights: run pair sites on the ROUNDED weights (faster; not the fp32 model's arithmetic)
+  bool allow_rounded = false;             // wca_set_allow_rounded_weights: run split mode on the ROUNDED weights (faster; not the fp32 model's arithmetic)
   char* wslab_lo = nullptr;               // W_lo slab, same layout as wslab (allocated when the first inexact tensor arrives): lo = f16(w - f16(w)) of every
-                                          // weight matrix element, zero where the f16 value is exact. A pair site multiplies the extra term A_hi W_lo^T
+                                          // weight matrix element, zero where the f16 value is exact. A pair GEMM multiplies the extra term A_hi W_lo^T
   std::set<const void*> wlo_bases;        // weight matrices (base pointer the GEMM call sites use) that hold at least one non-zero lo element
   GrowBuf wlo_tmp[2];                     // f32 [M][N] scratch of the extra term for the non-accumulating output modes: [0] launches on `stream` (phase 1),
                                           // [1] on any other stream (phase 2 runs beside the next batch's phase 1)
@@ -228,9 +228,7 @@ struct wca_engine {
   // hi = f16(x), lo = f16(x - hi) in ONE row [hi(K) | lo(K)], and every weight matrix as [W | W] ([N][2K], built once on the
   // device from the f16 weights, which are exact): A.W^T = [A_hi | A_lo].[W | W]^T is then a K-doubled call of the SAME GEMM
   // kernels with f16 x f16 products exact in the fp32 accumulator. Activation operand buffers are twice as wide.
-  bool split = false;        // some site is split (sites != 0): the arena is wide and the K-doubled weight copies exist
-  unsigned sites = 0;        // WCA_PSITE_* bits: which stages run on (hi, lo) operand pairs (wca_set_precision_sites)
-  int enc_from = 0;          // encoder blocks >= enc_from take the ENC_GEMM / ENC_ATTN bits
+  bool split = false;        // split mode: every stage runs on (hi, lo) operand pairs, the arena is wide and the K-doubled weight copies exist
   char* wslab2 = nullptr;    // the K-doubled weight copies (allocated while split is on)
   bool sw_dirty = true;      // a weight was (re)loaded since the copies were built
   struct SplitW {
@@ -277,14 +275,8 @@ inline const half_t* wlo_of(const wca_engine* e, const half_t* w) {
   return reinterpret_cast<const half_t*>(e->wslab_lo + (reinterpret_cast<const char*>(w) - e->wslab));
 }
 
-// ---- per-site precision (wca_set_precision_sites): which stages compute on (hi, lo) operand pairs
-inline bool site_on(const wca_engine* e, unsigned bit) { return (e->sites & bit) != 0; }
-inline bool enc_gemm_split(const wca_engine* e, int li) { return (e->sites & WCA_PSITE_ENC_GEMM) && li >= e->enc_from && li < e->dims.n_audio_layer; }
-inline bool enc_attn_split(const wca_engine* e, int li) { return (e->sites & WCA_PSITE_ENC_ATTN) && li >= e->enc_from && li < e->dims.n_audio_layer; }
-
-// Operands of one GEMM at a seam. a_pair: the A buffer holds [hi(K) | lo(K)] rows (row stride 2 K); want: the GEMM's site is
-// split. Both: the K-doubled product [A_hi | A_lo] [W | W]^T. A single-precision site behind a pair producer reads the hi halves
-// (hi IS f16(x)); a split site behind a single-precision producer multiplies the f16 rows it got (there is no lo to add).
+// Operands of one GEMM. pair (split mode): the A buffer holds [hi(K) | lo(K)] rows (row stride 2 K) and the product is the
+// K-doubled [A_hi | A_lo] [W | W]^T (W2 = the [W | W] copy); otherwise the plain f16 product A W1^T.
 // Where launch_gemm takes the persistent 256 x 256 kernel (M, N given), the pair product runs in its SPLITW form: plain W, each W
 // K-tile staged once (a_lo = K); elsewhere as the K-doubled call on the [W | W] copy.
 struct GemmOpnd {
@@ -294,12 +286,12 @@ struct GemmOpnd {
   const half_t* Wp;   // the plain [N][K] matrix when the product is a PAIR product (null otherwise): where the W_lo term of an inexact matrix comes from
   int Kp;
 };
-inline GemmOpnd pick_operands(bool a_pair, bool want, const half_t* W1, const half_t* W2, int K, int M = 0, int N = 0, int out_mode = 0, const wca_engine* wlo_e = nullptr) {
-  const bool use = a_pair && want;
+inline GemmOpnd pick_operands(bool pair, const half_t* W1, const half_t* W2, int K, int M = 0, int N = 0, int out_mode = 0, const wca_engine* wlo_e = nullptr) {
   // (a matrix with a W_lo remainder takes the K-doubled call for its non-accumulating products: their extra term enters through the generic epilogue's addend)
   const bool no_splitw = wlo_e != nullptr && out_mode != 2 && use_wlo(wlo_e) && wlo_e->wlo_bases.count(W1) != 0;
-  if (use && !no_splitw && M > 0 && gemm_splitw_supported(M, N, K, 2 * K, out_mode)) return GemmOpnd{W1, 2 * K, K, K, (long)K, W1, K};
-  return GemmOpnd{use ? W2 : W1, a_pair ? 2 * K : K, use ? 2 * K : K, use ? 2 * K : K, 0, use ? W1 : nullptr, K};
+  if (pair && !no_splitw && M > 0 && gemm_splitw_supported(M, N, K, 2 * K, out_mode)) return GemmOpnd{W1, 2 * K, K, K, (long)K, W1, K};
+  const int k = pair ? 2 * K : K;
+  return GemmOpnd{pair ? W2 : W1, k, k, k, 0, pair ? W1 : nullptr, K};
 }
 
 // ---- weight slab layout (two passes: size, then carve)
@@ -619,10 +611,12 @@ int dec_gemm(wca_engine* e, hipStream_t s, int ws, const half_t* A, int lda, con
 // x (f32 residual stream, [M][N]) += A W^T + bias, then xn (f16) = LayerNorm(x) with (gamma, beta): ONE kernel where the
 // persistent GEMM can exchange the row statistics between the workgroups of a 256-row panel (gemm_epilogue.h, out_mode 3);
 // otherwise (few tiles: the decoder, small batches) the read-modify-write GEMM followed by the LayerNorm kernel.
+// Split mode never fuses: no fused form writes the [hi(N) | lo(N)] rows its consumer reads, and only the separate GEMM adds the
+// A_hi W_lo^T term of an inexact checkpoint; the f16 mode has no W_lo term.
 // ev_gemm / ev_ln (profiling): event slots {site, layer} for the GEMM and for the LayerNorm launch; the fused kernel is timed
 // as the GEMM's site alone.
 int gemm_residual_ln(wca_engine* e, hipStream_t s, const half_t* A, int lda, const half_t* W, int ldw, const float* bias, float* x, int M, int N,
-                     int K, const float* gamma, const float* beta, half_t* xn, bool ln_pair, int site, bool allow_fused = true, int ev_gemm_site = -1,
+                     int K, const float* gamma, const float* beta, half_t* xn, int site, bool allow_fused = true, int ev_gemm_site = -1,
                      int ev_gemm_li = 0, int ev_ln_site = -1, int ev_ln_li = 0, long a_lo = 0, const half_t* w_plain = nullptr, int k_plain = 0) {
   auto ev = [&](int st, int li, int which) {
     if (e->profiling && st >= 0 && li >= 0 && li < 33) {
@@ -631,8 +625,7 @@ int gemm_residual_ln(wca_engine* e, hipStream_t s, const half_t* A, int lda, con
     }
   };
   ev(ev_gemm_site, ev_gemm_li, 0);
-  const int om = ln_pair ? 2 : 1;  // the LayerNorm's consumer is split: xn rows are [hi(N) | lo(N)] (no fused form writes pairs)
-  if (allow_fused && !ln_pair && a_lo == 0 && gemm_ln_supported(M, N, K, e->n_cu)) {
+  if (allow_fused && !e->split && gemm_ln_supported(M, N, K, e->n_cu)) {
     GemmArgs g{};
     g.A = A;
     g.lda = lda;
@@ -661,7 +654,7 @@ int gemm_residual_ln(wca_engine* e, hipStream_t s, const half_t* A, int lda, con
   HIPCHK(gemm(s, A, lda, W, ldw, bias, x, N, M, N, K, 0, 2, site, e->sk_big[0], e->sk_big_bytes, 0, a_lo, e, w_plain, k_plain));
   ev(ev_gemm_site, ev_gemm_li, 1);
   ev(ev_ln_site, ev_ln_li, 0);
-  HIPCHK(launch_layernorm_f16(x, gamma, beta, xn, M, N, 1e-5f, s, om * N, ln_pair ? N : 0));
+  HIPCHK(launch_layernorm_f16(x, gamma, beta, xn, M, N, 1e-5f, s, (e->split ? 2 : 1) * N, e->split ? N : 0));
   ev(ev_ln_site, ev_ln_li, 1);
   return WCA_OK;
 }
@@ -670,7 +663,7 @@ int gemm_residual_ln(wca_engine* e, hipStream_t s, const half_t* A, int lda, con
 // Every weight matrix is f16 AT REST here, like every openai checkpoint ("weights stored fp16, loaded into fp32 params",
 // /root/reference/infer_ali.py:36-37), which is what makes A W^T exact-operand arithmetic in the pair mode. An fp32 source whose values are not
 // f16-representable (a fine-tuned fp32 state dict) keeps its REMAINDER lo = f16(w - f16(w)) in the W_lo slab (same offset as the f16 value in wslab;
-// allocated when the first such tensor arrives), and the pair sites multiply the extra term A_hi W_lo^T (gemm()): w = hi + lo to 2^-22 |w|, the same
+// allocated when the first such tensor arrives), and the pair GEMMs multiply the extra term A_hi W_lo^T (gemm()): w = hi + lo to 2^-22 |w|, the same
 // representation the activations travel in. *n_inexact counts the elements with a non-zero remainder (NaN == NaN for this purpose); `base` is the matrix
 // the GEMM call sites address (a fused matrix holds several tensors).
 int ensure_wlo_slab(wca_engine* e) {
@@ -806,36 +799,36 @@ int join_phase2(wca_engine* e) {
 }
 
 // ---- encoder: mel_tm (f16 time-major) -> xn = ln_post(x) (f16) and optionally x (f32)
-// Per-site precision (e->sites): a split stage runs the same launches on [hi | lo] operand rows (row width 2 * width, lo half
-// `width` elements after the hi half) against the K-doubled weight copies; a producer stores pairs (out_mode 4 / the LayerNorm's
-// lo_off) exactly when its consumer is split; the fp32 residual stream is the same in every mode.
+// Split mode runs the same launches on [hi | lo] operand rows (row width 2 * width, lo half `width` elements after the hi half)
+// against the K-doubled weight copies; every producer stores pairs (out_mode 4 / the LayerNorm's lo_off); the fp32 residual
+// stream is the same in both modes.
 int run_encoder(wca_engine* e, int B) {
   const wca_model_dims& D = e->dims;
   const int d = D.n_audio_state, H = D.n_audio_head;
-  const bool cv = site_on(e, WCA_PSITE_CONV);
-  const int omc = cv ? 2 : 1;
+  const bool sp = e->split;
+  const int om = sp ? 2 : 1;  // f16 operand rows: [hi | lo] pairs in split mode
   hipStream_t s = e->stream;
   {
     GemmArgs g{};
     g.A = e->mel_tm;
-    g.lda = omc * D.n_mels;
+    g.lda = om * D.n_mels;
     g.a_rows_per_batch = N_FRAMES;
-    g.a_batch_stride = (long)(N_FRAMES + 2) * omc * D.n_mels;
-    g.W = cv ? e->sw.conv1_w : e->conv1_w;
-    g.ldw = cv ? e->sw.k1pad : e->k1pad;
+    g.a_batch_stride = (long)(N_FRAMES + 2) * om * D.n_mels;
+    g.W = sp ? e->sw.conv1_w : e->conv1_w;
+    g.ldw = sp ? e->sw.k1pad : e->k1pad;
     g.bias = e->conv1_b;
-    g.C = e->h1pad + omc * d;  // output frame t lands in padded row t + 1
-    g.ldc = omc * d;
+    g.C = e->h1pad + om * d;  // output frame t lands in padded row t + 1
+    g.ldc = om * d;
     g.c_rows_per_batch = N_FRAMES;
-    g.c_batch_stride = (long)(N_FRAMES + 2) * omc * d;
-    g.c_lo = cv ? d : 0;
+    g.c_batch_stride = (long)(N_FRAMES + 2) * om * d;
+    g.c_lo = sp ? d : 0;
     g.M = B * N_FRAMES;
     g.N = d;
     g.K = g.ldw;
     g.gelu = 1;
-    g.out_mode = cv ? 4 : 0;
+    g.out_mode = sp ? 4 : 0;
     g.site = 3;
-    if (cv && use_wlo(e) && e->wlo_bases.count(e->conv1_w)) {   // inexact conv1 weights: the A_hi W_lo^T term, added before the GELU
+    if (sp && use_wlo(e) && e->wlo_bases.count(e->conv1_w)) {   // inexact conv1 weights: the A_hi W_lo^T term, added before the GELU
       GemmArgs x = g;
       x.W = e->sw.conv1_wlo;
       x.bias = nullptr;
@@ -855,11 +848,11 @@ int run_encoder(wca_engine* e, int B) {
   {
     GemmArgs g{};
     g.A = e->h1pad;
-    g.lda = 2 * omc * d;  // stride 2
+    g.lda = 2 * om * d;  // stride 2
     g.a_rows_per_batch = N_CTX;
-    g.a_batch_stride = (long)(N_FRAMES + 2) * omc * d;
-    g.W = cv ? e->sw.conv2_w : e->conv2_w;
-    g.ldw = 3 * omc * d;
+    g.a_batch_stride = (long)(N_FRAMES + 2) * om * d;
+    g.W = sp ? e->sw.conv2_w : e->conv2_w;
+    g.ldw = 3 * om * d;
     g.bias = e->conv2_b;
     g.C = e->x;
     g.ldc = d;
@@ -867,11 +860,11 @@ int run_encoder(wca_engine* e, int B) {
     g.pos_period = N_CTX;
     g.M = B * N_CTX;
     g.N = d;
-    g.K = 3 * omc * d;
+    g.K = 3 * om * d;
     g.gelu = 1;
     g.out_mode = 1;
     g.site = 3;
-    if (cv && use_wlo(e) && e->wlo_bases.count(e->conv2_w)) {
+    if (sp && use_wlo(e) && e->wlo_bases.count(e->conv2_w)) {
       GemmArgs x = g;
       x.W = e->sw.conv2_wlo;
       x.bias = nullptr;
@@ -897,34 +890,28 @@ int run_encoder(wca_engine* e, int B) {
     }
   };
   // LayerNorms ride in the epilogue of the GEMM that produces their input (gemm_residual_ln) where wca_set_fuse_ln allows it and
-  // their consumer reads single f16 rows: mlp_ln in the attention out-projection, the NEXT layer's attn_ln (ln_post after the
-  // last layer) in fc2; only layer 0's attn_ln is always a launch
-  {
-    const bool p0 = enc_gemm_split(e, 0);
-    mark(WCA_SITE_LN1, 0, 0);
-    HIPCHK(launch_layernorm_f16(e->x, e->enc[0].ln1_g, e->enc[0].ln1_b, e->xn, M, d, 1e-5f, s, (p0 ? 2 : 1) * d, p0 ? d : 0));
-    mark(WCA_SITE_LN1, 0, 1);
-  }
+  // the mode is f16: mlp_ln in the attention out-projection, the NEXT layer's attn_ln (ln_post after the last layer) in fc2;
+  // only layer 0's attn_ln is always a launch
+  mark(WCA_SITE_LN1, 0, 0);
+  HIPCHK(launch_layernorm_f16(e->x, e->enc[0].ln1_g, e->enc[0].ln1_b, e->xn, M, d, 1e-5f, s, om * d, sp ? d : 0));
+  mark(WCA_SITE_LN1, 0, 1);
   for (int li = 0; li < D.n_audio_layer; ++li) {
     const LayerW& l = e->enc[li];
-    const bool gs = enc_gemm_split(e, li), as = enc_attn_split(e, li);
-    const LayerW& w2 = e->split ? e->sw.enc[li] : l;  // the K-doubled copies [N][2K] = [W | W] (present while any site is split)
-    const int oma = as ? 2 : 1;  // q / k / v rows and the attention output: pairs iff the attention is split
-    // q / k / v projection: xn is a pair buffer iff this layer's GEMMs are split (its LayerNorm wrote it for them)
-    const GemmOpnd oq = pick_operands(gs, gs, l.qkv_w, w2.qkv_w, d, M, 3 * d, as ? 4 : 0, e);
+    const LayerW& w2 = sp ? e->sw.enc[li] : l;  // the K-doubled copies [N][2K] = [W | W] (present in split mode)
+    const GemmOpnd oq = pick_operands(sp, l.qkv_w, w2.qkv_w, d, M, 3 * d, sp ? 4 : 0, e);
     mark(WCA_SITE_QKV, li, 0);
-    HIPCHK(gemm(s, e->xn, oq.lda, oq.W, oq.ldw, l.qkv_b, e->qkv, oma * 3 * d, M, 3 * d, oq.K, 0, 0, 1, nullptr, 0, as ? 3 * d : 0, oq.a_lo, e, oq.Wp, oq.Kp));
+    HIPCHK(gemm(s, e->xn, oq.lda, oq.W, oq.ldw, l.qkv_b, e->qkv, om * 3 * d, M, 3 * d, oq.K, 0, 0, 1, nullptr, 0, sp ? 3 * d : 0, oq.a_lo, e, oq.Wp, oq.Kp));
     mark(WCA_SITE_QKV, li, 1);
     AttnArgs a{};
     a.Q = e->qkv;
     a.K = e->qkv + d;
     a.V = e->qkv + 2 * d;
-    a.q_bs = a.k_bs = a.v_bs = (long)N_CTX * oma * 3 * d;
-    a.q_rs = a.k_rs = a.v_rs = oma * 3 * d;
+    a.q_bs = a.k_bs = a.v_bs = (long)N_CTX * om * 3 * d;
+    a.q_rs = a.k_rs = a.v_rs = om * 3 * d;
     a.O = e->att;
-    a.o_bs = (long)N_CTX * oma * d;
-    a.o_rs = oma * d;
-    a.split = as ? 1 : 0;
+    a.o_bs = (long)N_CTX * om * d;
+    a.o_rs = om * d;
+    a.split = sp ? 1 : 0;
     a.q_lo = a.k_lo = a.v_lo = 3 * d;
     a.o_lo = d;
     a.nq = N_CTX;
@@ -938,20 +925,19 @@ int run_encoder(wca_engine* e, int B) {
     mark(WCA_SITE_ATTN, li, 1);
     // sites OUT / FC2 = the GEMM alone (or the fused GEMM + LayerNorm kernel); the LayerNorm launches: mlp_ln = LN2[li], the next
     // layer's attn_ln / ln_post = LN1[li + 1]
-    const GemmOpnd oo = pick_operands(as, gs, l.out_w, w2.out_w, d, M, d, 2, e);
-    if (int rc = gemm_residual_ln(e, s, e->att, oo.lda, oo.W, oo.ldw, l.out_b, e->x, M, d, oo.K, l.ln2_g, l.ln2_b, e->xn, gs, 1, e->fuse_ln, WCA_SITE_OUT, li,
+    const GemmOpnd oo = pick_operands(sp, l.out_w, w2.out_w, d, M, d, 2, e);
+    if (int rc = gemm_residual_ln(e, s, e->att, oo.lda, oo.W, oo.ldw, l.out_b, e->x, M, d, oo.K, l.ln2_g, l.ln2_b, e->xn, 1, e->fuse_ln, WCA_SITE_OUT, li,
                                   WCA_SITE_LN2, li, oo.a_lo, oo.Wp, oo.Kp))
       return rc;
-    const GemmOpnd o1 = pick_operands(gs, gs, l.fc1_w, w2.fc1_w, d, M, 4 * d, gs ? 4 : 0, e);
+    const GemmOpnd o1 = pick_operands(sp, l.fc1_w, w2.fc1_w, d, M, 4 * d, sp ? 4 : 0, e);
     mark(WCA_SITE_FC1, li, 0);
-    HIPCHK(gemm(s, e->xn, o1.lda, o1.W, o1.ldw, l.fc1_b, e->hid, (gs ? 2 : 1) * 4 * d, M, 4 * d, o1.K, 1, 0, 1, nullptr, 0, gs ? 4 * d : 0, o1.a_lo, e, o1.Wp, o1.Kp));
+    HIPCHK(gemm(s, e->xn, o1.lda, o1.W, o1.ldw, l.fc1_b, e->hid, om * 4 * d, M, 4 * d, o1.K, 1, 0, 1, nullptr, 0, sp ? 4 * d : 0, o1.a_lo, e, o1.Wp, o1.Kp));
     mark(WCA_SITE_FC1, li, 1);
     const bool last = li + 1 == D.n_audio_layer;
     // the LayerNorm behind fc2 feeds the next layer's q / k / v projection, or (ln_post) the cross-K/V projection
-    const bool next_pair = last ? site_on(e, WCA_PSITE_CROSS_KV) : enc_gemm_split(e, li + 1);
-    const GemmOpnd o2 = pick_operands(gs, gs, l.fc2_w, w2.fc2_w, 4 * d, M, d, 2, e);
+    const GemmOpnd o2 = pick_operands(sp, l.fc2_w, w2.fc2_w, 4 * d, M, d, 2, e);
     if (int rc = gemm_residual_ln(e, s, e->hid, o2.lda, o2.W, o2.ldw, l.fc2_b, e->x, M, d, o2.K, last ? e->lnpost_g : e->enc[li + 1].ln1_g,
-                                  last ? e->lnpost_b : e->enc[li + 1].ln1_b, e->xn, next_pair, 4, e->fuse_ln, WCA_SITE_FC2, li, WCA_SITE_LN1, li + 1, o2.a_lo, o2.Wp, o2.Kp))
+                                  last ? e->lnpost_b : e->enc[li + 1].ln1_b, e->xn, 4, e->fuse_ln, WCA_SITE_FC2, li, WCA_SITE_LN1, li + 1, o2.a_lo, o2.Wp, o2.Kp))
       return rc;
   }
   return WCA_OK;
@@ -960,42 +946,40 @@ int run_encoder(wca_engine* e, int B) {
 // cross-attention K/V of every decoder layer in one GEMM: kv[b*1500 + t][(2l + {0,1})*dt + c]
 // skip_last_v: the value projection of the LAST decoder layer (the final dt columns) is only read by that layer's
 // P.V product, whose result nobody uses when the caller wants the captured logits but no output logits.
-// The rows are pairs [hi(L*2*dt) | lo(L*2*dt)] iff the hooked cross-attention (CAPTURE) is split.
+// The rows are pairs [hi(L*2*dt) | lo(L*2*dt)] in split mode.
 int run_cross_kv(wca_engine* e, int B, half_t* kvbuf = nullptr, bool skip_last_v = false) {
   if (!kvbuf) kvbuf = e->kv;
   const wca_model_dims& D = e->dims;
   const int d = D.n_audio_state, dt = D.n_text_state, L = D.n_text_layer;
   const int n_cols = L * 2 * dt - (skip_last_v ? dt : 0);
-  const bool ks = site_on(e, WCA_PSITE_CROSS_KV), cs = site_on(e, WCA_PSITE_CAPTURE);
-  const GemmOpnd o = pick_operands(ks, ks, e->kv_w, e->split ? e->sw.kv_w : e->kv_w, d, B * N_CTX, n_cols, cs ? 4 : 0, e);
-  HIPCHK(gemm(e->stream, e->xn, o.lda, o.W, o.ldw, e->kv_b, kvbuf, (cs ? 2 : 1) * L * 2 * dt, B * N_CTX, n_cols, o.K, 0, 0, 3, nullptr, 0,
-              cs ? (long)L * 2 * dt : 0, o.a_lo, e, o.Wp, o.Kp));
+  const bool sp = e->split;
+  const GemmOpnd o = pick_operands(sp, e->kv_w, sp ? e->sw.kv_w : e->kv_w, d, B * N_CTX, n_cols, sp ? 4 : 0, e);
+  HIPCHK(gemm(e->stream, e->xn, o.lda, o.W, o.ldw, e->kv_b, kvbuf, (sp ? 2 : 1) * L * 2 * dt, B * N_CTX, n_cols, o.K, 0, 0, 3, nullptr, 0,
+              sp ? (long)L * 2 * dt : 0, o.a_lo, e, o.Wp, o.Kp));
   return WCA_OK;
 }
 
-// The teacher-forced decoder with a split site (DEC: its LayerNorms / GEMMs / causal self-attention on pairs; CAPTURE: the hooked
-// cross-attention on q / K / V pairs): separate LayerNorm launches, the tile GEMMs (the few-row kernel of gemm_rows.hip has no pair
-// output), attn_split_kernel where the attention is split. The captured logits of a split CAPTURE are the three-pass fp32 sums.
-int run_decoder_sites(wca_engine* e, const int64_t* tokens_dev, int B, int n, float* cap, int Fpad, int Fcap, float* logits_out, hipStream_t s,
+// The teacher-forced decoder in split mode (its LayerNorms, GEMMs, causal self-attention and the hooked cross-attention on pairs):
+// separate LayerNorm launches, the tile GEMMs (the few-row kernel of gemm_rows.hip has no pair output), attn_split_kernel. The
+// captured logits are the three-pass fp32 sums. Every f16 operand row is [hi | lo], twice as wide as in the f16 mode.
+int run_decoder_split(wca_engine* e, const int64_t* tokens_dev, int B, int n, float* cap, int Fpad, int Fcap, float* logits_out, hipStream_t s,
                       const half_t* kvbuf, bool finish_last = false) {
   const wca_model_dims& D = e->dims;
   const int dt = D.n_text_state, H = D.n_text_head, L = D.n_text_layer;
   const int M = B * n;
   const float scale = 1.0f / std::sqrt((float)(dt / H));
-  const bool gs = site_on(e, WCA_PSITE_DEC), cs = site_on(e, WCA_PSITE_CAPTURE);
-  const int omg = gs ? 2 : 1, omx = cs ? 2 : 1;
-  const int kv_ld = omx * L * 2 * dt;
+  const int kv_ld = 2 * L * 2 * dt;
   const long kv_lo = (long)L * 2 * dt;
   HIPCHK(launch_embed(tokens_dev, e->tok_emb, e->dec_pos, e->xd, B, n, dt, D.n_vocab, e->err_dev, s,
-                      (gs && use_wlo(e) && e->wlo_bases.count(e->tok_emb)) ? wlo_of(e, e->tok_emb) : nullptr));
+                      (use_wlo(e) && e->wlo_bases.count(e->tok_emb)) ? wlo_of(e, e->tok_emb) : nullptr));
   auto ln = [&](const float* g, const float* b) -> int {
-    HIPCHK(launch_layernorm_f16(e->xd, g, b, e->xdn, M, dt, 1e-5f, s, omg * dt, gs ? dt : 0));
+    HIPCHK(launch_layernorm_f16(e->xd, g, b, e->xdn, M, dt, 1e-5f, s, 2 * dt, dt));
     return WCA_OK;
   };
-  // C = A W^T (+ bias ...): a_pair = the A buffer holds [hi | lo] rows of K values each; c_lo > 0: f16 pair output
-  auto mm = [&](const half_t* A, bool a_pair, const half_t* W1, const half_t* W2, const float* bias, void* C, int ldc, int N, int K, int gelu, int out_mode,
+  // C = A W^T (+ bias ...) on [hi | lo] rows of K values each; c_lo > 0: f16 pair output
+  auto mm = [&](const half_t* A, const half_t* W1, const half_t* W2, const float* bias, void* C, int ldc, int N, int K, int gelu, int out_mode,
                 long c_lo, int site) -> int {
-    const GemmOpnd o = pick_operands(a_pair, gs, W1, W2, K, M, N, (c_lo > 0 && out_mode == 0) ? 4 : out_mode, e);
+    const GemmOpnd o = pick_operands(true, W1, W2, K, M, N, (c_lo > 0 && out_mode == 0) ? 4 : out_mode, e);
     HIPCHK(gemm(s, A, o.lda, o.W, o.ldw, bias, C, ldc, M, N, o.K, gelu, out_mode, site, e->sk_big[1], e->sk_big_bytes, c_lo, o.a_lo, e, o.Wp, o.Kp));
     return WCA_OK;
   };
@@ -1003,18 +987,18 @@ int run_decoder_sites(wca_engine* e, const int64_t* tokens_dev, int B, int n, fl
     const LayerW& l = e->dec[li];
     const LayerW& w = e->sw.dec[li];
     WCA_TRY(ln(l.ln1_g, l.ln1_b));
-    WCA_TRY(mm(e->xdn, gs, l.qkv_w, w.qkv_w, l.qkv_b, e->qkv_d, omg * 3 * dt, 3 * dt, dt, 0, 0, gs ? 3 * dt : 0, 2));
+    WCA_TRY(mm(e->xdn, l.qkv_w, w.qkv_w, l.qkv_b, e->qkv_d, 2 * 3 * dt, 3 * dt, dt, 0, 0, 3 * dt, 2));
     {
       AttnArgs a{};
       a.Q = e->qkv_d;
       a.K = e->qkv_d + dt;
       a.V = e->qkv_d + 2 * dt;
-      a.q_bs = a.k_bs = a.v_bs = (long)n * omg * 3 * dt;
-      a.q_rs = a.k_rs = a.v_rs = omg * 3 * dt;
+      a.q_bs = a.k_bs = a.v_bs = (long)n * 2 * 3 * dt;
+      a.q_rs = a.k_rs = a.v_rs = 2 * 3 * dt;
       a.O = e->att_d;
-      a.o_bs = (long)n * omg * dt;
-      a.o_rs = omg * dt;
-      a.split = gs ? 1 : 0;
+      a.o_bs = (long)n * 2 * dt;
+      a.o_rs = 2 * dt;
+      a.split = 1;
       a.q_lo = a.k_lo = a.v_lo = 3 * dt;
       a.o_lo = dt;
       a.nq = n;
@@ -1025,22 +1009,22 @@ int run_decoder_sites(wca_engine* e, const int64_t* tokens_dev, int B, int n, fl
       a.causal = 1;
       HIPCHK(launch_attention(a, s));
     }
-    WCA_TRY(mm(e->att_d, gs, l.out_w, w.out_w, l.out_b, e->xd, dt, dt, dt, 0, 2, 0, 2));
+    WCA_TRY(mm(e->att_d, l.out_w, w.out_w, l.out_b, e->xd, dt, dt, dt, 0, 2, 0, 2));
     WCA_TRY(ln(l.lnc_g, l.lnc_b));
-    WCA_TRY(mm(e->xdn, gs, l.cq_w, w.cq_w, l.cq_b, e->q_d, omx * dt, dt, dt, 0, 0, cs ? dt : 0, 2));
+    WCA_TRY(mm(e->xdn, l.cq_w, w.cq_w, l.cq_b, e->q_d, 2 * dt, dt, dt, 0, 0, dt, 2));
     {
       AttnArgs a{};
       a.Q = e->q_d;
-      a.q_bs = (long)n * omx * dt;
-      a.q_rs = omx * dt;
+      a.q_bs = (long)n * 2 * dt;
+      a.q_rs = 2 * dt;
       a.K = kvbuf + (size_t)(2 * li) * dt;
       a.V = kvbuf + (size_t)(2 * li + 1) * dt;
       a.k_bs = a.v_bs = (long)N_CTX * kv_ld;
       a.k_rs = a.v_rs = kv_ld;
       a.O = e->att_d;
-      a.o_bs = (long)n * omx * dt;
-      a.o_rs = omx * dt;
-      a.split = cs ? 1 : 0;
+      a.o_bs = (long)n * 2 * dt;
+      a.o_rs = 2 * dt;
+      a.split = 1;
       a.q_lo = dt;
       a.k_lo = a.v_lo = kv_lo;
       a.o_lo = dt;
@@ -1058,14 +1042,14 @@ int run_decoder_sites(wca_engine* e, const int64_t* tokens_dev, int B, int n, fl
       HIPCHK(launch_attention(a, s));
     }
     if (li == L - 1 && !logits_out && !finish_last) break;
-    WCA_TRY(mm(e->att_d, cs, l.co_w, w.co_w, l.co_b, e->xd, dt, dt, dt, 0, 2, 0, 2));
+    WCA_TRY(mm(e->att_d, l.co_w, w.co_w, l.co_b, e->xd, dt, dt, dt, 0, 2, 0, 2));
     WCA_TRY(ln(l.ln2_g, l.ln2_b));
-    WCA_TRY(mm(e->xdn, gs, l.fc1_w, w.fc1_w, l.fc1_b, e->hid_d, omg * 4 * dt, 4 * dt, dt, 1, 0, gs ? 4 * dt : 0, 2));
-    WCA_TRY(mm(e->hid_d, gs, l.fc2_w, w.fc2_w, l.fc2_b, e->xd, dt, dt, 4 * dt, 0, 2, 0, 2));
+    WCA_TRY(mm(e->xdn, l.fc1_w, w.fc1_w, l.fc1_b, e->hid_d, 2 * 4 * dt, 4 * dt, dt, 1, 0, 4 * dt, 2));
+    WCA_TRY(mm(e->hid_d, l.fc2_w, w.fc2_w, l.fc2_b, e->xd, dt, dt, 4 * dt, 0, 2, 0, 2));
   }
   if (logits_out) {
     WCA_TRY(ln(e->lnf_g, e->lnf_b));
-    WCA_TRY(mm(e->xdn, gs, e->tok_emb, e->sw.tok_emb, nullptr, logits_out, D.n_vocab, D.n_vocab, dt, 0, 1, 0, 3));
+    WCA_TRY(mm(e->xdn, e->tok_emb, e->sw.tok_emb, nullptr, logits_out, D.n_vocab, D.n_vocab, dt, 0, 1, 0, 3));
   }
   return WCA_OK;
 }
@@ -1079,7 +1063,7 @@ int run_decoder(wca_engine* e, const int64_t* tokens_dev, int B, int n, float* c
   const int dt = D.n_text_state, H = D.n_text_head, L = D.n_text_layer;
   if (!s) s = e->stream;
   if (!kvbuf) kvbuf = e->kv;
-  if (site_on(e, WCA_PSITE_DEC) || site_on(e, WCA_PSITE_CAPTURE)) return run_decoder_sites(e, tokens_dev, B, n, cap, Fpad, Fcap, logits_out, s, kvbuf, finish_last);
+  if (e->split) return run_decoder_split(e, tokens_dev, B, n, cap, Fpad, Fcap, logits_out, s, kvbuf, finish_last);
   const int M = B * n;
   const float scale = 1.0f / std::sqrt((float)(dt / H));
   HIPCHK(launch_embed(tokens_dev, e->tok_emb, e->dec_pos, e->xd, B, n, dt, D.n_vocab, e->err_dev, s));
@@ -1165,7 +1149,7 @@ int run_decode_step(wca_engine* e, hipStream_t s, int ws, const half_t* kvbuf, c
   half_t* q_d = e->q_d + (size_t)b0 * dt;
   half_t* hid_d = e->hid_d + (size_t)b0 * 4 * dt;
   // split mode: the cross-K/V rows are [hi | lo]; the greedy pre-pass (whisper.decode runs in fp16 itself) reads the hi halves
-  const int kv_ld = (site_on(e, WCA_PSITE_CAPTURE) ? 2 : 1) * L * 2 * dt;
+  const int kv_ld = (e->split ? 2 : 1) * L * 2 * dt;
   const half_t* kvb = kvbuf + (size_t)b0 * N_CTX * kv_ld;
   if (phase == -2 || phase == -1)
     HIPCHK(launch_embed_step(tokens + (size_t)b0 * T_max, T_max, t, e->tok_emb, e->dec_pos, xd, B, dt, D.n_vocab, s));
@@ -1262,10 +1246,9 @@ int run_logmel(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const in
   a.twiddle = e->twiddle;
   a.mel_out = mel_out;
   a.mel_tm = want_tm ? e->mel_tm : nullptr;
-  const bool cv = site_on(e, WCA_PSITE_CONV);  // the conv stem reads pairs
-  a.n_mels_pad = (cv ? 2 : 1) * e->dims.n_mels;
-  a.tm_lo = cv ? e->dims.n_mels : 0;
-  a.precise = site_on(e, WCA_PSITE_LOGMEL) ? 1 : 0;
+  a.n_mels_pad = (e->split ? 2 : 1) * e->dims.n_mels;   // split mode: the conv stem reads pairs, the DFT accumulates in f64
+  a.tm_lo = e->split ? e->dims.n_mels : 0;
+  a.precise = e->split ? 1 : 0;
   a.scratch = e->mel_scratch;
   a.gmax = e->gmax;
   a.n_mels = e->dims.n_mels;
@@ -1292,8 +1275,7 @@ int mel_to_tm(wca_engine* e, const float* mel_dev, int batch) {
   const wca_model_dims& D = e->dims;
   const size_t nel = (size_t)D.n_mels * N_FRAMES;
   dim3 grid((unsigned)((nel + 255) / 256), batch);
-  const bool cv = site_on(e, WCA_PSITE_CONV);
-  hipLaunchKernelGGL(mel_to_tm_kernel, grid, dim3(256), 0, e->stream, mel_dev, e->mel_tm, D.n_mels, batch, (cv ? 2 : 1) * D.n_mels, cv ? D.n_mels : 0);
+  hipLaunchKernelGGL(mel_to_tm_kernel, grid, dim3(256), 0, e->stream, mel_dev, e->mel_tm, D.n_mels, batch, (e->split ? 2 : 1) * D.n_mels, e->split ? D.n_mels : 0);
   HIPCHK(hipGetLastError());
   return WCA_OK;
 }
@@ -1476,32 +1458,32 @@ constexpr int ERR_TARGET_VOCAB = 4;   // err_dev bit: a teacher token outside [0
 
 // Teacher-token log-probs of one aligned micro-batch on stream s (timing.py:146-149 of the reference in log space), after
 // run_decoder(..., finish_last = true) left the final residual stream in e->xd. Only the R = sum_b n_text_b rows that predict a text token go
-// on: gathered (row_off_dev: device [B] prefix sums of n_text), final LayerNorm (pairs when DEC is split), the vocabulary projection against
+// on: gathered (row_off_dev: device [B] prefix sums of n_text), final LayerNorm (pairs in split mode), the vocabulary projection against
 // tok_emb rows [0, vocab_end) in row chunks whose f32 logits stay under 256 MB (1 024 x 50 257 x 4 B = 206 MB), token_logprob_kernel per chunk.
 // out [B][n_tok_max]: entries [0, n_text_b) of row b, the rest 0.
 int run_token_logprobs(wca_engine* e, hipStream_t s, const int64_t* tokens_dev, int B, int n_tok_max, int sot_len, int vocab_end,
                        const int* n_tok_dev, const int* row_off_dev, int R, int n_text_max, float* out) {
   const int dt = e->dims.n_text_state;
-  const bool gs = site_on(e, WCA_PSITE_DEC);
-  const int omg = gs ? 2 : 1;
+  const bool sp = e->split;
+  const int om = sp ? 2 : 1;
   HIPCHK(hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * n_tok_max, s));
   if (R <= 0) return WCA_OK;
   HIPCHK(e->lp_x.ensure(sizeof(float) * (size_t)R * dt));
-  HIPCHK(e->lp_xn.ensure(sizeof(half_t) * (size_t)omg * R * dt));
+  HIPCHK(e->lp_xn.ensure(sizeof(half_t) * (size_t)om * R * dt));
   HIPCHK(e->lp_map.ensure(sizeof(int) * (size_t)R));
   float* xr = (float*)e->lp_x.p;
   half_t* xn = (half_t*)e->lp_xn.p;
   int* map = (int*)e->lp_map.p;
   HIPCHK(launch_gather_text_rows(e->xd, n_tok_max, dt, sot_len, n_tok_dev, row_off_dev, B, n_text_max, xr, map, s));
-  HIPCHK(launch_layernorm_f16(xr, e->lnf_g, e->lnf_b, xn, R, dt, 1e-5f, s, omg * dt, gs ? dt : 0));
+  HIPCHK(launch_layernorm_f16(xr, e->lnf_g, e->lnf_b, xn, R, dt, 1e-5f, s, om * dt, sp ? dt : 0));
   const int ldc = (int)align_up((size_t)vocab_end, 64);   // (the aligned f32 store path of the GEMM epilogue)
   const int chunk = std::min(R, std::max(1, std::min(1024, (int)(((size_t)256 << 20) / ((size_t)ldc * sizeof(float))))));
   HIPCHK(e->lp_logits.ensure(sizeof(float) * (size_t)chunk * ldc));
   float* lg = (float*)e->lp_logits.p;
   for (int r0 = 0; r0 < R; r0 += chunk) {
     const int m = std::min(chunk, R - r0);
-    const GemmOpnd o = pick_operands(gs, gs, e->tok_emb, e->split ? e->sw.tok_emb : e->tok_emb, dt, m, vocab_end, 1, e);
-    HIPCHK(gemm(s, xn + (size_t)r0 * omg * dt, o.lda, o.W, o.ldw, nullptr, lg, ldc, m, vocab_end, o.K, 0, 1, 3, nullptr, 0, 0, o.a_lo, e, o.Wp, o.Kp));
+    const GemmOpnd o = pick_operands(sp, e->tok_emb, sp ? e->sw.tok_emb : e->tok_emb, dt, m, vocab_end, 1, e);
+    HIPCHK(gemm(s, xn + (size_t)r0 * om * dt, o.lda, o.W, o.ldw, nullptr, lg, ldc, m, vocab_end, o.K, 0, 1, 3, nullptr, 0, 0, o.a_lo, e, o.Wp, o.Kp));
     HIPCHK(launch_token_logprob(lg, ldc, vocab_end, m, tokens_dev, map + r0, sot_len + 1, out, e->err_dev, ERR_TARGET_VOCAB, s));
   }
   return WCA_OK;
@@ -1513,8 +1495,9 @@ int run_token_logprobs(wca_engine* e, hipStream_t s, const int64_t* tokens_dev, 
 extern "C" {
 
 const char* wca_last_error(void) { return g_err.c_str(); }
-int wca_version(void) { return 6; }   // 6: teacher-token log-probs (wca_align_batch_enqueue_ex / _fetch_ex, wca_token_logprobs); 5: a new engine is in
-                                      // the contract mode; wca_engine_create_ex, W_lo slab, switch table
+int wca_version(void) { return 7; }   // 7: two precision modes only (the per-stage precision mask, its setter / getter and the mixed
+                                      // state are gone); 6: teacher-token log-probs (wca_align_batch_enqueue_ex / _fetch_ex, wca_token_logprobs);
+                                      // 5: a new engine is in the contract mode; wca_engine_create_ex, W_lo slab, switch table
 
 int wca_engine_create(const wca_model_dims* dims, int device_ordinal, int max_batch, wca_engine** out) {
   return wca_engine_create_ex(dims, device_ordinal, max_batch, WCA_PRECISION_REFERENCE, out);   // the CONTRACT mode is the default (round 5)
@@ -1553,8 +1536,6 @@ int wca_engine_create_ex(const wca_model_dims* dims, int device_ordinal, int max
   layout_weights(e, e->wslab);
   if (precision_mode == WCA_PRECISION_REFERENCE) {   // born in the contract mode: the wide arena and the K-doubled weight copies from the start
     e->split = true;
-    e->sites = (unsigned)WCA_PSITE_ALL;
-    e->enc_from = 0;
     const size_t wbytes = layout_split_weights(e, nullptr);
     HIPCHK(hipMalloc((void**)&e->wslab2, wbytes));
     HIPCHK(hipMemset(e->wslab2, 0, wbytes));
@@ -1701,33 +1682,30 @@ int wca_last_kernel_ms(wca_engine* e, int site, int* n_launches, float* total_ms
   *n_launches = nl;
   *total_ms = tot;
   // algorithmic work of ONE launch at the last batch size (M = batch * 1500 rows, d = n_audio_state). Bytes: operands read once, outputs
-  // written once; an operand / output of a split site is an f16 PAIR (4 bytes per element instead of 2), the weights are read once
+  // written once; in split mode every operand / output is an f16 PAIR (4 bytes per element instead of 2), the weights are read once
   const double d = e->dims.n_audio_state, M = (double)e->last_batch * N_CTX, H = e->dims.n_audio_head;
-  const int lastl = e->dims.n_audio_layer - 1;
-  const double pg = enc_gemm_split(e, lastl) ? 2.0 : 1.0, pa = enc_attn_split(e, lastl) ? 2.0 : 1.0;   // (the last block's flags: all blocks alike in the named modes)
-  const double pin_out = (pg > 1.0 && pa > 1.0) ? 2.0 : 1.0;   // the out-projection multiplies pairs only behind a split attention
+  const double p = e->split ? 2.0 : 1.0;
+  const double fused_ln = e->fuse_ln && !e->split ? 2 : 0;   // the fused LayerNorm's f16 output (the f16 mode only)
   double fl = 0, by = 0;
   switch (site) {
-    case WCA_SITE_QKV: fl = 2 * M * 3 * d * d; by = 2 * (pg * M * d + 3 * d * d + pa * M * 3 * d); break;
-    case WCA_SITE_ATTN: fl = 4.0 * e->last_batch * H * (double)N_CTX * N_CTX * 64; by = 2 * pa * (M * 3 * d + M * d); break;
-    case WCA_SITE_OUT: fl = 2 * M * d * d; by = 2 * (pin_out * M * d + d * d) + 8 * M * d + (e->fuse_ln && pg == 1.0 ? 2 : 0) * M * d; break;  // f32 residual read + write (+ the fused LayerNorm's f16 output)
-    case WCA_SITE_FC1: fl = 2 * M * 4 * d * d; by = 2 * (pg * M * d + 4 * d * d + pg * M * 4 * d); break;
-    case WCA_SITE_FC2: fl = 2 * M * 4 * d * d; by = 2 * (pg * M * 4 * d + 4 * d * d) + 8 * M * d + (e->fuse_ln && pg == 1.0 ? 2 : 0) * M * d; break;
+    case WCA_SITE_QKV: fl = 2 * M * 3 * d * d; by = 2 * (p * M * d + 3 * d * d + p * M * 3 * d); break;
+    case WCA_SITE_ATTN: fl = 4.0 * e->last_batch * H * (double)N_CTX * N_CTX * 64; by = 2 * p * (M * 3 * d + M * d); break;
+    case WCA_SITE_OUT: fl = 2 * M * d * d; by = 2 * (p * M * d + d * d) + 8 * M * d + fused_ln * M * d; break;  // f32 residual read + write
+    case WCA_SITE_FC1: fl = 2 * M * 4 * d * d; by = 2 * (p * M * d + 4 * d * d + p * M * 4 * d); break;
+    case WCA_SITE_FC2: fl = 2 * M * 4 * d * d; by = 2 * (p * M * 4 * d + 4 * d * d) + 8 * M * d + fused_ln * M * d; break;
     case WCA_SITE_LN1:
-    case WCA_SITE_LN2: fl = 8 * M * d; by = (4 + 2 * pg) * M * d; break;                         // read f32, write f16 (or the f16 pair)
+    case WCA_SITE_LN2: fl = 8 * M * d; by = (4 + 2 * p) * M * d; break;                         // read f32, write f16 (or the f16 pair)
   }
   *flops_per_launch = fl;
   *bytes_per_launch = by;
   return WCA_OK;
 }
 
-int wca_set_precision_sites(wca_engine* e, unsigned mask, int enc_first_layer) {
+int wca_set_precision(wca_engine* e, int mode) {
   if (!e) return fail(WCA_ERR_INVALID, "null engine");
-  if (mask & ~(unsigned)WCA_PSITE_ALL) return fail(WCA_ERR_INVALID, "precision site mask 0x%x has unknown bits", mask);
-  if (enc_first_layer < 0 || enc_first_layer > e->dims.n_audio_layer)
-    return fail(WCA_ERR_INVALID, "enc_first_layer %d outside [0, %d]", enc_first_layer, e->dims.n_audio_layer);
-  if (!(mask & (WCA_PSITE_ENC_GEMM | WCA_PSITE_ENC_ATTN))) enc_first_layer = 0;  // (unused: keep the state canonical)
-  if (mask == e->sites && enc_first_layer == e->enc_from) return WCA_OK;
+  if (mode != WCA_PRECISION_F16 && mode != WCA_PRECISION_SPLIT) return fail(WCA_ERR_INVALID, "precision mode %d", mode);
+  const bool want = mode == WCA_PRECISION_SPLIT, was = e->split;
+  if (want == was) return WCA_OK;
   if (e->enq_count != e->fetch_count) return fail(WCA_ERR_STATE, "fetch the batches in flight before changing the precision mode");
   for (auto& st : e->enc_q)
     if (!st.decoded) return fail(WCA_ERR_STATE, "an encoded batch is waiting: consume it before changing the precision mode");
@@ -1735,77 +1713,49 @@ int wca_set_precision_sites(wca_engine* e, unsigned mask, int enc_first_layer) {
   HIPCHK(hipStreamSynchronize(e->stream));
   HIPCHK(hipStreamSynchronize(e->stream2));
   HIPCHK(hipStreamSynchronize(e->stream3));
-  const bool want = mask != 0;
-  if (want != e->split) {
-    // The activation arena is laid out per mode (operand buffers are twice as wide while any site is split) and the K-doubled
-    // weight copies exist only then. Allocate the NEW arena (and copies) first; the old ones are released and the engine's
-    // state committed only when both allocations succeeded, so a failed switch leaves a working engine in its previous mode.
-    const bool was = e->split;
-    e->split = want;
-    const size_t abytes = layout_arena(e, nullptr);
-    e->split = was;
-    char* na = nullptr;
-    char* nw = nullptr;
-    size_t wbytes = 0;
-    hipError_t he = hipMalloc((void**)&na, abytes);
-    if (he == hipSuccess && want) {
-      wbytes = layout_split_weights(e, nullptr);
-      he = hipMalloc((void**)&nw, wbytes);
-    }
-    if (he == hipSuccess) he = hipMemset(na, 0, abytes);  // zero pad rows of mel_tm / h1pad, counters, flags and all slack
-    if (he == hipSuccess && nw) he = hipMemset(nw, 0, wbytes);  // K padding of the conv1 copy stays zero
-    if (he == hipSuccess && debug_switch(DBG_FAIL_PRECISION_ALLOC)) he = hipErrorOutOfMemory;  // fault injection (wca_test_set_switch) for the test of the path below
-    if (he != hipSuccess) {
-      if (na) (void)hipFree(na);
-      if (nw) (void)hipFree(nw);
-      (void)hipGetLastError();
-      layout_arena(e, e->aslab);  // (the sizing pass above moved the arena pointers: restore them)
-      if (was) layout_split_weights(e, e->wslab2);
-      return fail(WCA_ERR_HIP, "precision switch: allocating the %s arena (%zu + %zu bytes) failed: %s; the engine keeps its previous mode",
-                  want ? "wide" : "narrow", abytes, wbytes, hipGetErrorString(he));
-    }
-    (void)hipFree(e->aslab);
-    if (e->wslab2) (void)hipFree(e->wslab2);
-    e->aslab = na;
-    e->wslab2 = nw;
-    e->split = want;
-    layout_arena(e, e->aslab);
-    if (want) {
-      layout_split_weights(e, e->wslab2);
-      e->sw_dirty = true;  // built on the next entry point that runs the model (after the weights are final)
-    }
-    e->ln_err = nullptr;
-  } else if (want) {
-    // same arena, other row layouts inside it (a buffer's rows are [hi | lo] or single per site): the zero pad rows of the
-    // time-major conv images move with the row width, so wipe the arena once
-    const size_t abytes = layout_arena(e, nullptr);
-    layout_arena(e, e->aslab);
-    HIPCHK(hipMemset(e->aslab, 0, abytes));
+  // The activation arena is laid out per mode (operand buffers are twice as wide in split mode) and the K-doubled weight copies
+  // exist only then. Allocate the NEW arena (and copies) first; the old ones are released and the engine's state committed only
+  // when both allocations succeeded, so a failed switch leaves a working engine in its previous mode.
+  e->split = want;
+  const size_t abytes = layout_arena(e, nullptr);
+  e->split = was;
+  char* na = nullptr;
+  char* nw = nullptr;
+  size_t wbytes = 0;
+  hipError_t he = hipMalloc((void**)&na, abytes);
+  if (he == hipSuccess && want) {
+    wbytes = layout_split_weights(e, nullptr);
+    he = hipMalloc((void**)&nw, wbytes);
   }
-  for (auto& st : e->enc_q) e->slot_busy[st.slot] = false;  // decoded-but-never-aligned states die with the arena / its layout
+  if (he == hipSuccess) he = hipMemset(na, 0, abytes);  // zero pad rows of mel_tm / h1pad, counters, flags and all slack
+  if (he == hipSuccess && nw) he = hipMemset(nw, 0, wbytes);  // K padding of the conv1 copy stays zero
+  if (he == hipSuccess && debug_switch(DBG_FAIL_PRECISION_ALLOC)) he = hipErrorOutOfMemory;  // fault injection (wca_test_set_switch) for the test of the path below
+  if (he != hipSuccess) {
+    if (na) (void)hipFree(na);
+    if (nw) (void)hipFree(nw);
+    (void)hipGetLastError();
+    layout_arena(e, e->aslab);  // (the sizing pass above moved the arena pointers: restore them)
+    if (was) layout_split_weights(e, e->wslab2);
+    return fail(WCA_ERR_HIP, "precision switch: allocating the %s arena (%zu + %zu bytes) failed: %s; the engine keeps its previous mode",
+                want ? "wide" : "narrow", abytes, wbytes, hipGetErrorString(he));
+  }
+  (void)hipFree(e->aslab);
+  if (e->wslab2) (void)hipFree(e->wslab2);
+  e->aslab = na;
+  e->wslab2 = nw;
+  e->split = want;
+  layout_arena(e, e->aslab);
+  if (want) {
+    layout_split_weights(e, e->wslab2);
+    e->sw_dirty = true;  // built on the next entry point that runs the model (after the weights are final)
+  }
+  e->ln_err = nullptr;
+  for (auto& st : e->enc_q) e->slot_busy[st.slot] = false;  // decoded-but-never-aligned states die with the arena
   e->enc_q.clear();
-  e->sites = mask;
-  e->enc_from = enc_first_layer;
   return WCA_OK;
 }
 
-int wca_get_precision_sites(wca_engine* e, unsigned* mask_out, int* enc_first_layer_out) {
-  if (!e) return fail(WCA_ERR_INVALID, "null engine");
-  if (mask_out) *mask_out = e->sites;
-  if (enc_first_layer_out) *enc_first_layer_out = e->enc_from;
-  return WCA_OK;
-}
-
-int wca_set_precision(wca_engine* e, int mode) {
-  if (!e) return fail(WCA_ERR_INVALID, "null engine");
-  if (mode != WCA_PRECISION_F16 && mode != WCA_PRECISION_SPLIT) return fail(WCA_ERR_INVALID, "precision mode %d", mode);
-  return wca_set_precision_sites(e, mode == WCA_PRECISION_SPLIT ? (unsigned)WCA_PSITE_ALL : 0u, 0);
-}
-
-int wca_get_precision(wca_engine* e) {
-  if (!e || e->sites == 0) return WCA_PRECISION_F16;
-  return (e->sites == (unsigned)WCA_PSITE_ALL && e->enc_from == 0) ? WCA_PRECISION_SPLIT : WCA_PRECISION_MIXED;
-}
+int wca_get_precision(wca_engine* e) { return e && e->split ? WCA_PRECISION_SPLIT : WCA_PRECISION_F16; }
 
 int wca_set_fuse_ln(wca_engine* e, int on) {
   if (!e) return fail(WCA_ERR_INVALID, "null engine");
@@ -3313,7 +3263,7 @@ int wca_test_encoder(wca_engine* e, const float* mel_dev, int batch, float* xa_o
   if (rc) return rc;
   // xn holds ln_post(x) in f16 (split mode: hi + lo pairs); widen for the caller
   const size_t n = (size_t)batch * N_CTX * D.n_audio_state;
-  if (site_on(e, WCA_PSITE_CROSS_KV))  // ln_post wrote pairs for the cross-K/V projection
+  if (e->split)
     hipLaunchKernelGGL(widen_split_kernel, dim3(2048), dim3(256), 0, e->stream, e->xn, xa_out_dev, (size_t)batch * N_CTX, D.n_audio_state);
   else
     hipLaunchKernelGGL(widen_kernel, dim3(2048), dim3(256), 0, e->stream, e->xn, xa_out_dev, n);

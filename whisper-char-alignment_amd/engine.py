@@ -499,8 +499,8 @@ class WhisperAMD:
         return tuple(int(v) for v in arr)
 
     def set_precision(self, mode):
-        """'f16' (the engine's construction default): operands rounded to f16 once, fp32 accumulation. 'split' = 'reference' (the
-        contract mode: what bench.py's `value` and the CLI default use): every operand of every stage as an f16 (hi, lo) pair against
+        """'f16': operands rounded to f16 once, fp32 accumulation. 'split' = 'reference' (the contract mode and the engine's
+        construction default: what bench.py's `value` and the CLI default use): every operand of every stage as an f16 (hi, lo) pair against
         the exact f16 weights, three-pass attention (wca.h: wca_set_precision) -- the reference's fp32 forward to fp32 summation noise.
         No batch may be in flight; the activation arena is re-created when the engine leaves or enters f16."""
         modes = {"f16": 0, "split": 1, "reference": 1}
@@ -509,34 +509,14 @@ class WhisperAMD:
         _lib.check(self._lib.wca_set_precision(self._h, modes[mode]))
         return self
 
-    def set_precision_sites(self, sites, enc_first_layer=0):
-        """Per-stage precision (wca.h: wca_set_precision_sites). `sites`: an iterable of names from _lib.PRECISION_SITES
-        ('logmel', 'conv', 'enc_gemm', 'enc_attn', 'cross_kv', 'dec', 'capture'), the string 'all', or the integer mask; the
-        named stages compute on (hi, lo) operand pairs, the others on single f16 operands. The encoder bits apply to blocks
-        >= enc_first_layer."""
-        if isinstance(sites, str):
-            sites = list(_lib.PRECISION_SITES) if sites == "all" else [x for x in sites.replace("+", ",").split(",") if x]
-        if isinstance(sites, int):
-            mask = sites
-        else:
-            unknown = [x for x in sites if x not in _lib.PRECISION_SITES]
-            if unknown:
-                raise ValueError("unknown precision site(s) %s (known: %s)" % (unknown, sorted(_lib.PRECISION_SITES)))
-            mask = 0
-            for x in sites:
-                mask |= _lib.PRECISION_SITES[x]
-        _lib.check(self._lib.wca_set_precision_sites(self._h, mask, int(enc_first_layer)))
-        return self
-
     @property
     def precision_sites(self):
-        mask, first = C.c_uint(0), C.c_int(0)
-        _lib.check(self._lib.wca_get_precision_sites(self._h, C.byref(mask), C.byref(first)))
-        return sorted((n for n, b in _lib.PRECISION_SITES.items() if mask.value & b), key=lambda n: _lib.PRECISION_SITES[n]), first.value
+        """(stages on (hi, lo) operand pairs, first encoder block): every stage in split mode, none in f16."""
+        return (list(_lib.PRECISION_SITES) if self.precision == "split" else []), 0
 
     @property
     def precision(self):
-        return {0: "f16", 1: "split", 2: "mixed"}[self._lib.wca_get_precision(self._h)]   # ("reference" is an alias of "split")
+        return {0: "f16", 1: "split"}[self._lib.wca_get_precision(self._h)]   # ("reference" is an alias of "split")
 
     def set_fuse_ln(self, on):
         """LayerNorm in the residual GEMMs' epilogue (needs the GPU to itself: wca.h) or as separate launches (the default)."""
