@@ -25,6 +25,8 @@
  *                          whisper.decode(model, mels, DecodingOptions(language="en")) -- the greedy ASR pre-pass
  *                          that produces the teacher text (upstream decoding.py: KV-cached autoregressive
  *                          decoder, SuppressBlank / SuppressTokens / ApplyTimestampRules, GreedyDecoder)
+ *   wca_greedy_decode_ex   the same with DecodingOptions(prompt=..., prefix=...) (transcribe(initial_prompt=...)): any
+ *                          initial token row, <|sot|> at sot_index, and the batched prefill of upstream's first forward
  *   wca_align_batch        infer_ali.py:93-101 + dataset.py:47-48: the whole per-utterance pipeline
  *                          (log-mel -> forward+capture -> medfilt/softmax -> scores/top-k ->
  *                          aggregate -> DTW) for a micro-batch of utterances, results = the frame
@@ -95,7 +97,7 @@ typedef struct {
 } wca_align_opts;
 
 const char* wca_last_error(void);
-int wca_version(void);   /* 7: the engine has exactly two precision modes, F16 and SPLIT (the per-stage precision mask is gone) */
+int wca_version(void);   /* 8: wca_greedy_decode_ex (prompt / prefix: sot_index, batched prefill); 7: exactly two precision modes */
 
 /* ---- engine lifetime ------------------------------------------------------------------------ */
 /* A new engine is in the CONTRACT precision mode (WCA_PRECISION_REFERENCE: every stage on (hi, lo) operand pairs = the fp32 forward of
@@ -213,7 +215,7 @@ int wca_align_batch(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, con
 
 /* whisper.DecodingOptions as the reference uses it (infer_ali.py:40: language="en", everything else default:
  * task transcribe, temperature 0 -> greedy, no beam, sample_len n_text_ctx // 2, suppress_blank, suppress_tokens "-1",
- * without_timestamps False, max_initial_timestamp 1.0, no prompt / prefix). */
+ * without_timestamps False, max_initial_timestamp 1.0, no prompt / prefix: those take wca_decode_opts_ex). */
 typedef struct {
   int32_t sample_len;                  /* maximum number of sampled tokens (224)                              */
   int32_t eot;                         /* tokenizer.eot                                                       */
@@ -222,6 +224,22 @@ typedef struct {
   int32_t max_initial_timestamp_index; /* round(max_initial_timestamp / 0.02) = 50; < 0 = no limit            */
   int32_t no_speech;                   /* tokenizer.no_speech (<|nospeech|>) for no_speech_prob; < 0 = skip   */
 } wca_decode_opts;
+
+/* wca_decode_opts plus what a prompted decode (DecodingOptions(prompt=..., prefix=...)) needs. */
+typedef struct {
+  int32_t sample_len;                  /* maximum number of sampled tokens                                    */
+  int32_t eot;
+  int32_t timestamp_begin;
+  int32_t apply_timestamp_rules;
+  int32_t max_initial_timestamp_index;
+  int32_t no_speech;
+  int32_t sot_index;                   /* position of <|startoftranscript|> in the initial tokens: no_speech_prob is read
+                                          from its logits (after a prompt: [sot_prev, prompt..., sot, ...])   */
+  int32_t prefill;                     /* 0: the initial tokens go through the decoder one position at a time (one decode
+                                          step each, as wca_greedy_decode does); 1: one batched forward over all of them
+                                          (causal self-attention, each layer's cross-K/V read once), upstream's first
+                                          forward. The two agree up to f16 / fp32 summation order. */
+} wca_decode_opts_ex;
 
 /* Greedy ASR pre-pass for a micro-batch. At most one of mel_dev ([batch][n_mels][3000] f32, what whisper.decode
  * takes) and pcm_dev ([batch][pcm_stride] f32 + n_samples_host, log-mel computed on the device) is non-NULL; with
@@ -252,6 +270,21 @@ int wca_greedy_decode(wca_engine* e, const float* mel_dev, const float* pcm_dev,
                       const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host, const wca_decode_opts* opts,
                       int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
                       float* no_speech_prob_host);
+/* Prompted greedy decode: wca_greedy_decode with opts->sot_index and opts->prefill (wca_greedy_decode is this call with
+ * sot_index = 0, prefill = 0, and the tighter bound n_initial + sample_len <= n_text_ctx). initial_tokens_host [n_initial] is
+ * upstream's _get_initial_tokens: [sot_prev, prompt..., ] sot_sequence [, no_timestamps] [, prefix...]; the first sampled
+ * position (SuppressBlank, the first-timestamp rules) is n_initial. Upstream samples until the sequence is longer than
+ * n_text_ctx, so n_initial + sample_len <= n_text_ctx + 1 is allowed (the last token is sampled, never embedded: no positional
+ * row past n_text_ctx - 1 is read); n_initial > n_text_ctx is refused (WCA_ERR_TOO_LONG). tokens_out_host is
+ * [batch][n_initial + sample_len]; no_speech_prob_host is the <|nospeech|> probability at sot_index. */
+int wca_greedy_decode_ex(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride,
+                         const int32_t* n_samples_host, int batch, const int32_t* initial_tokens_host, int n_initial,
+                         const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host, const wca_decode_opts_ex* opts,
+                         int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
+                         float* no_speech_prob_host);
+/* positions per row that the last wca_greedy_decode* fed through the batched prefill (n_initial, or 0) and one position at a
+ * time (decode steps, the sampling steps after the first included) */
+int wca_last_decode_positions(wca_engine* e, int32_t* prefill_positions, int32_t* step_positions);
 
 /* Same pipeline, but only enqueues the work on the engine stream (no host sync; results stay in the engine's
  * pinned staging ring until wca_align_batch_fetch). Up to TWO batches may be in flight: _fetch returns the

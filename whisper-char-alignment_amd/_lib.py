@@ -37,6 +37,10 @@ class DecodeOpts(C.Structure):
                 ("apply_timestamp_rules", C.c_int32), ("max_initial_timestamp_index", C.c_int32), ("no_speech", C.c_int32)]
 
 
+class DecodeOptsEx(C.Structure):
+    _fields_ = DecodeOpts._fields_ + [("sot_index", C.c_int32), ("prefill", C.c_int32)]
+
+
 ERR_TOO_LONG = -2   # WCA_ERR_TOO_LONG
 AGGR_MEAN, AGGR_TOPK = 0, 1
 PRECISION_SITES = ("logmel", "conv", "enc_gemm", "enc_attn", "cross_kv", "dec", "capture")  # the stages on (hi, lo) pairs in split mode
@@ -80,6 +84,8 @@ SIGNATURES = {
     "wca_token_logprobs": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "wca_encode_batch": (_i, [_vp, _vp, _vp, _i64, _pi32, _i]),
     "wca_greedy_decode": (_i, [_vp, _vp, _vp, _i64, _pi32, _i, _pi32, _i, _vp, _vp, C.POINTER(DecodeOpts), _pi32, _pi32, _pf, _pf]),
+    "wca_greedy_decode_ex": (_i, [_vp, _vp, _vp, _i64, _pi32, _i, _pi32, _i, _vp, _vp, C.POINTER(DecodeOptsEx), _pi32, _pi32, _pf, _pf]),
+    "wca_last_decode_positions": (_i, [_vp, _pi32, _pi32]),
     "wca_test_decode_select": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, C.POINTER(DecodeOpts), _vp, _vp]),
     "wca_test_gemm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "wca_test_gemm_ln": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),

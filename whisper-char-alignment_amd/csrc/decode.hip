@@ -3,6 +3,9 @@
 // restated from its published algorithm): the per-step device kernels of the autoregressive loop.
 //   * embed_step:     x[b] = token_embedding[tokens[b][t]] + positional_embedding[t]
 //   * kv_append:      self-attention K/V of the new position into the per-layer cache [B][T_max][d]
+//   * prefill (embed_prefix, kv_scatter, gather_rows): the batched first forward over all n initial tokens of a prompted
+//                     decode (upstream DecodingTask._main_loop, i == 0): embeddings of positions [0, n), their K/V into the
+//                     cache, and the compact rows whose logits are needed (the last initial position, <|sot|>)
 //   * decode_select:  the logit filters (SuppressBlank, SuppressTokens, ApplyTimestampRules), GreedyDecoder.update
 //                     (argmax at temperature 0, log-softmax of the FILTERED logits for sum_logprobs, EOT latching)
 //                     for one batch row per workgroup; integer / index work, bit-exact against the oracle on the same
@@ -37,6 +40,42 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const half_t* __restrict
     ko[c] = k[c];
     vo[c] = v[c];
   }
+}
+
+// x[b * n + i] = token_embedding[tokens[b][i]] + positional_embedding[i] for i < n (the prefill's rows; n <= n_text_ctx)
+__global__ __launch_bounds__(256) void embed_prefix_kernel(const int* __restrict__ tokens, int T_max, int n, const half_t* __restrict__ tok_emb,
+                                                           const float* __restrict__ pos_emb, float* __restrict__ x, int d, int n_vocab) {
+  const int r = blockIdx.x;  // b * n + i
+  const int b = r / n, i = r - b * n;
+  long tok = tokens[(long)b * T_max + i];
+  tok = (tok < 0 || tok >= n_vocab) ? 0 : tok;  // the initial tokens were validated on the host; never read out of bounds
+  const half_t* e = tok_emb + tok * d;
+  const float* p = pos_emb + (long)i * d;
+  float* o = x + (long)r * d;
+  for (int c = threadIdx.x; c < d; c += blockDim.x) o[c] = (float)e[c] + p[c];
+}
+
+// qkv [B * n][3d] (q | k | v) -> kc / vc [B][T_max][d] at positions [0, n) (8 halfs per thread)
+__global__ __launch_bounds__(256) void kv_scatter_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ kc, half_t* __restrict__ vc,
+                                                         int n, int T_max, int d) {
+  const int r = blockIdx.x;
+  const int b = r / n, i = r - b * n;
+  const half8* k = reinterpret_cast<const half8*>(qkv + (long)r * 3 * d + d);
+  const half8* v = reinterpret_cast<const half8*>(qkv + (long)r * 3 * d + 2 * d);
+  half8* ko = reinterpret_cast<half8*>(kc + ((long)b * T_max + i) * d);
+  half8* vo = reinterpret_cast<half8*>(vc + ((long)b * T_max + i) * d);
+  for (int c = threadIdx.x; c < d / 8; c += blockDim.x) {
+    ko[c] = k[c];
+    vo[c] = v[c];
+  }
+}
+
+// out[j * B + b] = x[b * n + pos_j] for the positions pos_0 = blockIdx.y == 0 ? p0 : p1 (f32 residual rows)
+__global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ x, float* __restrict__ out, int n, int p0, int p1, int d) {
+  const int b = blockIdx.x, j = blockIdx.y, B = gridDim.x;
+  const float* src = x + ((long)b * n + (j == 0 ? p0 : p1)) * d;
+  float* o = out + ((long)j * B + b) * d;
+  for (int c = threadIdx.x; c < d; c += blockDim.x) o[c] = src[c];
 }
 
 __device__ __forceinline__ float block_max(float v, float* red) {
@@ -215,6 +254,25 @@ hipError_t launch_embed_step(const int* tokens, int T_max, int t, const half_t* 
 hipError_t launch_kv_append(const half_t* qkv, half_t* kc, half_t* vc, int B, int T_max, int t, int d, hipStream_t s) {
   if ((d & 7) != 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kv_append_kernel, dim3(B), dim3(256), 0, s, qkv, kc, vc, T_max, t, d);
+  return hipGetLastError();
+}
+
+hipError_t launch_embed_prefix(const int* tokens, int T_max, int n, const half_t* tok_emb, const float* pos_emb, float* x, int B, int d,
+                               int n_vocab, hipStream_t s) {
+  if (n < 1 || n > T_max) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(embed_prefix_kernel, dim3(B * n), dim3(256), 0, s, tokens, T_max, n, tok_emb, pos_emb, x, d, n_vocab);
+  return hipGetLastError();
+}
+
+hipError_t launch_kv_scatter(const half_t* qkv, half_t* kc, half_t* vc, int B, int n, int T_max, int d, hipStream_t s) {
+  if ((d & 7) != 0 || n < 1 || n > T_max) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kv_scatter_kernel, dim3(B * n), dim3(256), 0, s, qkv, kc, vc, n, T_max, d);
+  return hipGetLastError();
+}
+
+hipError_t launch_gather_rows(const float* x, float* out, int B, int n, int p0, int p1, int d, hipStream_t s) {
+  if (p0 < 0 || p0 >= n || p1 >= n) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(B, p1 >= 0 ? 2 : 1), dim3(256), 0, s, x, out, n, p0, p1, d);
   return hipGetLastError();
 }
 

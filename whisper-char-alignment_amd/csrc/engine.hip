@@ -200,7 +200,9 @@ struct wca_engine {
   int probe_LH = 0, probe_N = 0;
   // greedy ASR pre-pass (wca_greedy_decode): self-attention K/V cache [L][2][B][T_max][d], token rows, masks, logits
   GrowBuf dec_cache, dec_tokens, dec_masks, dec_logits, dec_state;
+  GrowBuf dec_gather;            // prefill: the f32 residual rows whose logits are needed ([2B][d]: last initial position, <|sot|>)
   int* dec_done_host = nullptr;  // pinned: completion counter read back while the loop runs
+  int dec_prefill_positions = 0, dec_step_positions = 0;  // the last decode: positions per row fed by the prefill / one at a time
   // Encoded micro-batches (log-mel + encoder + cross-K/V done, recorded on `stream`) that no alignment has consumed
   // yet: wca_encode_batch / wca_greedy_decode push, wca_align_batch_enqueue(pcm_dev = NULL) pops the oldest. A K/V
   // slot stays busy from its encode until the alignment that consumed it has been fetched.
@@ -1211,6 +1213,82 @@ int run_decode_step(wca_engine* e, hipStream_t s, int ws, const half_t* kvbuf, c
   return WCA_OK;
 }
 
+// Prefill of a prompted greedy decode (upstream DecodingTask._main_loop, i == 0: the first forward runs every initial token):
+// positions [0, n) of all B rows in one teacher-forced pass on M = B n rows, with run_decoder's f16 structure but the step
+// path's operands -- plain f16 weights and f16 activations in both precision modes (whisper.decode runs in fp16), the
+// cross-K/V hi halves in split mode. Each layer's self-attention K/V go into the cache at positions [0, n) ([L][2][B][T_max][d],
+// the step loop continues at t = n); each layer's cross-K/V is read once for all n queries of a row. Only the rows whose logits
+// are needed get the final LayerNorm and the vocabulary projection: position n - 1 -> e->dec_logits rows [0, B), and, with
+// sot_index >= 0, position sot_index -> rows [B, 2B).
+int run_decode_prefill(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, int n, int T_max, int sot_index) {
+  const wca_model_dims& D = e->dims;
+  const int dt = D.n_text_state, H = D.n_text_head, L = D.n_text_layer;
+  const int M = B * n;
+  const float scale = 1.0f / std::sqrt((float)(dt / H));
+  half_t* cache = (half_t*)e->dec_cache.p;
+  const size_t plane = (size_t)B * T_max * dt;
+  const int kv_ld = (e->split ? 2 : 1) * L * 2 * dt;
+  // the scratch is carved for max_batch x n_text_ctx rows; the GEMMs on more than DEC_ROWS_MAX rows take dec_gemm's separate
+  // LayerNorm + gemm() launches, which are given no lo operands, so the products stay single f16 ones in split mode too
+  HIPCHK(launch_embed_prefix(tokens, T_max, n, e->tok_emb, e->dec_pos, e->xd, B, dt, D.n_vocab, s));
+  for (int li = 0; li < L; ++li) {
+    const LayerW& l = e->dec[li];
+    half_t* kc = cache + (size_t)(2 * li) * plane;
+    half_t* vc = kc + plane;
+    WCA_TRY(dec_gemm(e, s, 0, nullptr, 0, e->xd, l.ln1_g, l.ln1_b, e->xdn, l.qkv_w, dt, l.qkv_b, e->qkv_d, 3 * dt, M, 3 * dt, dt, 0, 0, 2));
+    HIPCHK(launch_kv_scatter(e->qkv_d, kc, vc, B, n, T_max, dt, s));
+    {
+      AttnArgs a{};
+      a.Q = e->qkv_d;
+      a.K = e->qkv_d + dt;
+      a.V = e->qkv_d + 2 * dt;
+      a.q_bs = a.k_bs = a.v_bs = (long)n * 3 * dt;
+      a.q_rs = a.k_rs = a.v_rs = 3 * dt;
+      a.O = e->att_d;
+      a.o_bs = (long)n * dt;
+      a.o_rs = dt;
+      a.nq = n;
+      a.nk = n;
+      a.H = H;
+      a.B = B;
+      a.scale = scale;
+      a.causal = 1;
+      HIPCHK(launch_attention(a, s));
+    }
+    WCA_TRY(dec_gemm(e, s, 0, e->att_d, dt, nullptr, nullptr, nullptr, nullptr, l.out_w, dt, l.out_b, e->xd, dt, M, dt, dt, 0, 2, 2));
+    WCA_TRY(dec_gemm(e, s, 0, nullptr, 0, e->xd, l.lnc_g, l.lnc_b, e->xdn, l.cq_w, dt, l.cq_b, e->q_d, dt, M, dt, dt, 0, 0, 2));
+    {
+      AttnArgs a{};
+      a.Q = e->q_d;
+      a.q_bs = (long)n * dt;
+      a.q_rs = dt;
+      a.K = kvbuf + (size_t)(2 * li) * dt;
+      a.V = kvbuf + (size_t)(2 * li + 1) * dt;
+      a.k_bs = a.v_bs = (long)N_CTX * kv_ld;
+      a.k_rs = a.v_rs = kv_ld;
+      a.O = e->att_d;
+      a.o_bs = (long)n * dt;
+      a.o_rs = dt;
+      a.nq = n;
+      a.nk = N_CTX;
+      a.H = H;
+      a.B = B;
+      a.scale = scale;
+      a.causal = 0;
+      HIPCHK(launch_attention(a, s));
+    }
+    WCA_TRY(dec_gemm(e, s, 0, e->att_d, dt, nullptr, nullptr, nullptr, nullptr, l.co_w, dt, l.co_b, e->xd, dt, M, dt, dt, 0, 2, 2));
+    WCA_TRY(dec_gemm(e, s, 0, nullptr, 0, e->xd, l.ln2_g, l.ln2_b, e->xdn, l.fc1_w, dt, l.fc1_b, e->hid_d, 4 * dt, M, 4 * dt, dt, 1, 0, 2));
+    WCA_TRY(dec_gemm(e, s, 0, e->hid_d, 4 * dt, nullptr, nullptr, nullptr, nullptr, l.fc2_w, 4 * dt, l.fc2_b, e->xd, dt, M, dt, 4 * dt, 0, 2, 2));
+  }
+  const int R = (sot_index >= 0 ? 2 : 1) * B;
+  float* xg = (float*)e->dec_gather.p;
+  HIPCHK(launch_gather_rows(e->xd, xg, B, n, n - 1, sot_index, dt, s));
+  WCA_TRY(dec_gemm(e, s, 0, nullptr, 0, xg, e->lnf_g, e->lnf_b, e->xdn, e->tok_emb, dt, nullptr, (float*)e->dec_logits.p, D.n_vocab, R, D.n_vocab,
+                   dt, 0, 1, 3));
+  return WCA_OK;
+}
+
 int check_ready(wca_engine* e) {
   if (!e) return fail(WCA_ERR_INVALID, "null engine");
   if (!e->finalized) return fail(WCA_ERR_STATE, "weights not finalized (call wca_finalize_weights)");
@@ -1495,7 +1573,7 @@ int run_token_logprobs(wca_engine* e, hipStream_t s, const int64_t* tokens_dev, 
 extern "C" {
 
 const char* wca_last_error(void) { return g_err.c_str(); }
-int wca_version(void) { return 7; }   // 7: two precision modes only (the per-stage precision mask, its setter / getter and the mixed
+int wca_version(void) { return 8; }   // 8: prompted greedy decode (wca_greedy_decode_ex, batched prefill); 7: two precision modes only (the per-stage precision mask, its setter / getter and the mixed
                                       // state are gone); 6: teacher-token log-probs (wca_align_batch_enqueue_ex / _fetch_ex, wca_token_logprobs);
                                       // 5: a new engine is in the contract mode; wca_engine_create_ex, W_lo slab, switch table
 
@@ -1600,6 +1678,7 @@ void wca_engine_destroy(wca_engine* e) {
   e->dec_masks.release();
   e->dec_logits.release();
   e->dec_state.release();
+  e->dec_gather.release();
   e->probe_jump.release();
   for (int i = 0; i < 2; ++i) {
     if (e->res_host[i]) (void)hipHostFree(e->res_host[i]);
@@ -2561,6 +2640,27 @@ int wca_greedy_decode(wca_engine* e, const float* mel_dev, const float* pcm_dev,
                       int batch, const int32_t* initial_tokens_host, int n_initial, const uint8_t* suppress_mask_host,
                       const uint8_t* blank_mask_host, const wca_decode_opts* o, int32_t* tokens_out_host, int32_t* n_tokens_host,
                       float* sum_logprob_host, float* no_speech_prob_host) {
+  if (!e) return fail(WCA_ERR_INVALID, "null engine");
+  if (!o) return fail(WCA_ERR_INVALID, "null argument");
+  if (n_initial + o->sample_len > e->dims.n_text_ctx)
+    return fail(WCA_ERR_TOO_LONG, "n_initial %d + sample_len %d exceeds n_text_ctx %d", n_initial, o->sample_len, e->dims.n_text_ctx);
+  wca_decode_opts_ex x{};
+  x.sample_len = o->sample_len;
+  x.eot = o->eot;
+  x.timestamp_begin = o->timestamp_begin;
+  x.apply_timestamp_rules = o->apply_timestamp_rules;
+  x.max_initial_timestamp_index = o->max_initial_timestamp_index;
+  x.no_speech = o->no_speech;
+  x.sot_index = 0;
+  x.prefill = 0;
+  return wca_greedy_decode_ex(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, initial_tokens_host, n_initial, suppress_mask_host,
+                              blank_mask_host, &x, tokens_out_host, n_tokens_host, sum_logprob_host, no_speech_prob_host);
+}
+
+int wca_greedy_decode_ex(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
+                         int batch, const int32_t* initial_tokens_host, int n_initial, const uint8_t* suppress_mask_host,
+                         const uint8_t* blank_mask_host, const wca_decode_opts_ex* o, int32_t* tokens_out_host, int32_t* n_tokens_host,
+                         float* sum_logprob_host, float* no_speech_prob_host) {
   int rc = check_ready(e);
   if (rc) return rc;
   if (mel_dev != nullptr && pcm_dev != nullptr) return fail(WCA_ERR_INVALID, "pass at most one of mel_dev / pcm_dev");
@@ -2569,8 +2669,12 @@ int wca_greedy_decode(wca_engine* e, const float* mel_dev, const float* pcm_dev,
   if (pcm_dev && !n_samples_host) return fail(WCA_ERR_INVALID, "null argument");
   if (batch < 1 || batch > e->max_batch) return fail(WCA_ERR_INVALID, "batch %d outside [1,%d]", batch, e->max_batch);
   const wca_model_dims& D = e->dims;
-  if (n_initial < 1 || o->sample_len < 1 || n_initial + o->sample_len > D.n_text_ctx)
-    return fail(WCA_ERR_TOO_LONG, "n_initial %d + sample_len %d exceeds n_text_ctx %d", n_initial, o->sample_len, D.n_text_ctx);
+  // upstream samples until the sequence is longer than n_ctx: the (n_text_ctx + 1)-th token is sampled, never embedded
+  if (n_initial < 1 || o->sample_len < 1 || n_initial > D.n_text_ctx || n_initial + o->sample_len > D.n_text_ctx + 1)
+    return fail(WCA_ERR_TOO_LONG, "n_initial %d + sample_len %d exceeds n_text_ctx + 1 = %d (or n_initial exceeds n_text_ctx)", n_initial,
+                o->sample_len, D.n_text_ctx + 1);
+  if (o->sot_index < 0 || o->sot_index >= n_initial) return fail(WCA_ERR_INVALID, "sot_index %d outside [0,%d)", o->sot_index, n_initial);
+  if (o->prefill != 0 && o->prefill != 1) return fail(WCA_ERR_INVALID, "prefill must be 0 or 1");
   if (o->eot < 0 || o->eot >= D.n_vocab || o->timestamp_begin < 0 || o->timestamp_begin > D.n_vocab)
     return fail(WCA_ERR_INVALID, "eot / timestamp_begin outside the vocabulary");
   for (int i = 0; i < n_initial; ++i)
@@ -2608,9 +2712,12 @@ int wca_greedy_decode(wca_engine* e, const float* mel_dev, const float* pcm_dev,
   HIPCHK(e->dec_cache.ensure(sizeof(half_t) * (size_t)L * 2 * batch * T_max * dt));
   HIPCHK(e->dec_tokens.ensure(sizeof(int) * (size_t)batch * T_max));
   HIPCHK(e->dec_masks.ensure((size_t)2 * V));
-  HIPCHK(e->dec_logits.ensure(sizeof(float) * (size_t)batch * V));
-  HIPCHK(e->dec_state.ensure(sizeof(float) * 2 * batch + sizeof(int) * (size_t)T_max));
   const bool want_nsp = no_speech_prob_host != nullptr && o->no_speech >= 0 && o->no_speech < V;
+  const bool prefill = o->prefill == 1;
+  // the prefill's logits: rows [0, B) at the last initial position, rows [B, 2B) at sot_index
+  HIPCHK(e->dec_logits.ensure(sizeof(float) * (size_t)((prefill && want_nsp) ? 2 : 1) * batch * V));
+  HIPCHK(e->dec_state.ensure(sizeof(float) * 2 * batch + sizeof(int) * (size_t)T_max));
+  if (prefill) HIPCHK(e->dec_gather.ensure(sizeof(float) * 2 * (size_t)batch * dt));
   if (!e->dec_done_host) HIPCHK(hipHostMalloc((void**)&e->dec_done_host, sizeof(int) * 4, hipHostMallocDefault));
   std::vector<int32_t> init((size_t)batch * T_max, o->eot);
   for (int b = 0; b < batch; ++b)
@@ -2640,30 +2747,47 @@ int wca_greedy_decode(wca_engine* e, const float* mel_dev, const float* pcm_dev,
   sel.max_initial_timestamp_index = o->max_initial_timestamp_index;
   sel.sum_logprob = sum_lp;
   sel.n_done = n_done;
-  // the prompt is fed one position at a time (it is 3 tokens: sot, language, task); sampling starts after its last token.
+  // prefill = 0: the initial tokens are fed one position at a time (the plain start is 3 tokens: sot, language, task);
+  // prefill = 1: one batched forward over all of them on s2 for the whole batch (run_decode_prefill), its first choice made
+  // there too, and the step loop (forked only then) continues at t = n_initial. Sampling starts after the last initial token.
   // The batch is decoded as two half-batches on two streams: a step is ~200 dependent launches of 5-10 us plus one
   // HBM-bound cross-attention per layer, and the halves are independent, so one half's small kernels run under the other
   // half's cross-K/V stream. Rows never interact (per-row kernels, per-row cache planes); n_done is an atomic counter.
   const int n_half = (e->dec_streams == 2 && batch >= 16) ? 2 : 1;
   const int hb[3] = {0, n_half == 2 ? (batch / 2 + 7) / 8 * 8 : batch, batch};
   hipStream_t hs[2] = {s2, e->stream3};
-  if (n_half == 2) {
-    HIPCHK(hipEventRecord(e->ev_fork, s2));
-    HIPCHK(hipStreamWaitEvent(e->stream3, e->ev_fork, 0));
-  }
-  int steps = 0;
+  auto fork = [&]() -> int {
+    if (n_half == 2) {
+      HIPCHK(hipEventRecord(e->ev_fork, s2));
+      HIPCHK(hipStreamWaitEvent(e->stream3, e->ev_fork, 0));
+    }
+    return WCA_OK;
+  };
+  if (!prefill && (rc = fork())) return rc;
+  int steps = 0, step_positions = 0;
   static const bool dbg_host = std::getenv("WCA_DEC_DEBUG") != nullptr;   // (read once)
   double host_us = 0.0;
-  for (int t = 0; t < T_max - 1; ++t) {
+  for (int t = prefill ? n_initial - 1 : 0; t < T_max - 1; ++t) {
     const bool sample = (t >= n_initial - 1);
-    const bool sot_logits = (t == 0 && want_nsp);  // probs_at_sot of DecodingTask._main_loop (sot_index = 0: no prompt)
+    const bool sot_logits = (t == o->sot_index && want_nsp);  // probs_at_sot of DecodingTask._main_loop
     const auto h0 = std::chrono::steady_clock::now();
-    for (int phase = -1; phase <= L; ++phase)
-      for (int h = 0; h < n_half; ++h) {
-        rc = run_decode_step(e, hs[h], h, kvbuf, tokens_dev, hb[h], hb[h + 1] - hb[h], batch, t, T_max, sample || sot_logits, phase);
-        if (rc) return rc;
-      }
-    for (int h = 0; h < n_half; ++h) {
+    if (prefill && t == n_initial - 1) {
+      rc = run_decode_prefill(e, s2, kvbuf, tokens_dev, batch, n_initial, T_max, want_nsp ? o->sot_index : -1);
+      if (rc) return rc;
+      if (want_nsp) HIPCHK(launch_token_prob((const float*)e->dec_logits.p + (size_t)batch * V, V, V, o->no_speech, nsp, batch, s2));
+      DecodeSelectArgs sh = sel;
+      sh.cur_len = n_initial;
+      HIPCHK(launch_decode_select(sh, batch, s2));
+      if ((rc = fork())) return rc;
+    } else {
+      ++step_positions;
+      for (int phase = -1; phase <= L; ++phase)
+        for (int h = 0; h < n_half; ++h) {
+          rc = run_decode_step(e, hs[h], h, kvbuf, tokens_dev, hb[h], hb[h + 1] - hb[h], batch, t, T_max, sample || sot_logits, phase);
+          if (rc) return rc;
+        }
+    }
+    for (int h = 0; h < n_half && !(prefill && t == n_initial - 1); ++h) {
       const int b0 = hb[h], nb = hb[h + 1] - hb[h];
       if (sot_logits) HIPCHK(launch_token_prob((const float*)e->dec_logits.p + (size_t)b0 * V, V, V, o->no_speech, nsp + b0, nb, hs[h]));
       if (!sample) continue;
@@ -2715,6 +2839,15 @@ int wca_greedy_decode(wca_engine* e, const float* mel_dev, const float* pcm_dev,
   }
   st->decoded = true;
   e->last_batch = batch;
+  e->dec_prefill_positions = prefill ? n_initial : 0;
+  e->dec_step_positions = step_positions;
+  return WCA_OK;
+}
+
+int wca_last_decode_positions(wca_engine* e, int32_t* prefill_positions, int32_t* step_positions) {
+  if (!e || !prefill_positions || !step_positions) return fail(WCA_ERR_INVALID, "null argument");
+  *prefill_positions = e->dec_prefill_positions;
+  *step_positions = e->dec_step_positions;
   return WCA_OK;
 }
 

@@ -133,6 +133,14 @@ hipError_t launch_embed_step(const int* tokens, int T_max, int t, const half_t* 
                              int n_vocab, hipStream_t s);
 // k / v columns of qkv [B][3d] -> kc / vc [B][T_max][d] at position t
 hipError_t launch_kv_append(const half_t* qkv, half_t* kc, half_t* vc, int B, int T_max, int t, int d, hipStream_t s);
+// prefill of a prompted decode (all n initial positions of every row in one forward):
+// x[b*n + i][:] = tok_emb[tokens[b*T_max + i]][:] + pos_emb[i][:] for i < n
+hipError_t launch_embed_prefix(const int* tokens, int T_max, int n, const half_t* tok_emb, const float* pos_emb, float* x, int B, int d,
+                               int n_vocab, hipStream_t s);
+// k / v columns of qkv [B*n][3d] -> kc / vc [B][T_max][d] at positions [0, n)
+hipError_t launch_kv_scatter(const half_t* qkv, half_t* kc, half_t* vc, int B, int n, int T_max, int d, hipStream_t s);
+// out [B][d] = rows (b, p0) of x [B*n][d] f32; p1 >= 0: out [B..2B) = rows (b, p1)
+hipError_t launch_gather_rows(const float* x, float* out, int B, int n, int p0, int p1, int d, hipStream_t s);
 // logit filters + greedy update of one decoding step (upstream decoding.py: SuppressBlank, SuppressTokens,
 // ApplyTimestampRules, GreedyDecoder.update at temperature 0); one workgroup per batch row
 struct DecodeSelectArgs {

@@ -3,8 +3,10 @@ probe_oracle.py:37,59-60, README.md:107-108) on the MI355X engine (C ABI wca_gre
 
 Upstream openai-whisper `decoding.py` is an absent third-party dependency; its published algorithm is restated here
 (host side: which tokens the filters suppress) and in csrc/decode.hip (the per-step filters and GreedyDecoder.update).
-Only what DecodingOptions(language="en") exercises is built: a given language (no detection), temperature 0 without
-beam search (greedy), no prompt / prefix. Anything else raises NotImplementedError instead of silently differing.
+Built: a given language (no detection), temperature 0 without beam search (greedy), and conditioning on a prompt and / or
+a prefix (DecodingOptions(prompt=...), the decoder side of transcribe(initial_prompt=...); prefix=...), whose initial tokens
+go through the decoder in one batched forward (wca_greedy_decode_ex, prefill). Anything else raises NotImplementedError
+instead of silently differing.
 """
 import zlib
 from dataclasses import dataclass, field
@@ -92,10 +94,44 @@ def _check_supported(options):
     if options.temperature != 0.0 or options.beam_size is not None or options.best_of is not None or options.patience is not None:
         raise NotImplementedError("only greedy decoding (temperature 0, no beam search / best_of) is built; the reference "
                                   "uses DecodingOptions(language='en') (infer_ali.py:40)")
-    if options.prompt is not None or options.prefix is not None:
-        raise NotImplementedError("prompt / prefix are not supported")
     if options.language is None:
         raise NotImplementedError("language detection is not built: pass DecodingOptions(language=...) as infer_ali.py:40 does")
+
+
+def _text_tokens(tokenizer, text, options, what):
+    if isinstance(text, str):
+        if options.vocab_path is None:
+            raise ValueError("a str %s is BPE-encoded and needs the vocabulary: pass DecodingOptions(vocab_path=<local *.tiktoken "
+                             "file>), or give the %s as a list of token ids" % (what, what))
+        return tokenizer.encode(" " + text.strip())
+    return [int(t) for t in text]
+
+
+def initial_tokens(tokenizer, options, n_ctx, sample_len):
+    """DecodingTask._get_initial_tokens (upstream, restated): [sot_prev, prompt[-(n_ctx // 2 - 1):]] + sot_sequence
+    [+ no_timestamps] + prefix[-(n_ctx // 2 - sample_len):] (Python slicing as upstream: a 0 bound keeps the whole prefix,
+    a negative one drops tokens from its front)."""
+    tokens = list(tokenizer.sot_sequence_including_notimestamps if options.without_timestamps else tokenizer.sot_sequence)
+    if options.prefix:
+        prefix_tokens = _text_tokens(tokenizer, options.prefix, options, "prefix")
+        if sample_len is not None:
+            max_prefix_len = n_ctx // 2 - sample_len
+            prefix_tokens = prefix_tokens[-max_prefix_len:]
+        tokens = tokens + prefix_tokens
+    if options.prompt:
+        prompt_tokens = _text_tokens(tokenizer, options.prompt, options, "prompt")
+        tokens = [tokenizer.sot_prev] + prompt_tokens[-(n_ctx // 2 - 1):] + tokens
+    return tokens
+
+
+def decode_plan(tokenizer, options, n_ctx):
+    """(initial tokens, sample_len as run, sot_index): upstream's loop stops after sample_len steps or once the sequence is
+    longer than n_ctx, so at most min(sample_len, n_ctx + 1 - len(initial)) tokens are sampled."""
+    sample_len = options.sample_len or n_ctx // 2
+    initial = initial_tokens(tokenizer, options, n_ctx, sample_len)
+    if len(initial) > n_ctx:
+        raise ValueError("the prompt and prefix give %d initial tokens, more than n_text_ctx = %d: nothing can be decoded" % (len(initial), n_ctx))
+    return initial, min(sample_len, n_ctx + 1 - len(initial)), initial.index(tokenizer.sot)
 
 
 @torch.no_grad()
@@ -111,8 +147,8 @@ def decode(model, mel, options=DecodingOptions(), pcm=None, n_samples=None, enco
     dims = model.dims
     tokenizer = get_tokenizer(model.is_multilingual, language=options.language, task=options.task, vocab_path=options.vocab_path)
     n_ctx = dims.n_text_ctx
-    sample_len = options.sample_len or n_ctx // 2
-    initial = list(tokenizer.sot_sequence_including_notimestamps if options.without_timestamps else tokenizer.sot_sequence)
+    initial, sample_len, sot_index = decode_plan(tokenizer, options, n_ctx)
+    conditioned = bool(options.prompt) or bool(options.prefix)
     sup, blank = filter_masks(tokenizer, options, dims.n_vocab)
     max_init = -1
     if not options.without_timestamps and options.max_initial_timestamp is not None:
@@ -121,7 +157,8 @@ def decode(model, mel, options=DecodingOptions(), pcm=None, n_samples=None, enco
     tokens, n_tokens, sum_logprobs = model.greedy_decode(
         mel, pcm, n_samples, initial, sup, blank, sample_len=sample_len, eot=tokenizer.eot, timestamp_begin=tokenizer.timestamp_begin,
         apply_timestamp_rules=not options.without_timestamps, max_initial_timestamp_index=max_init, batch=B,
-        no_speech=tokenizer.no_speech if tokenizer.no_speech is not None else -1)
+        no_speech=tokenizer.no_speech if tokenizer.no_speech is not None else -1, sot_index=sot_index,
+        prefill=1 if conditioned else 0)
     no_speech_probs = model.last_no_speech_prob
     results = []
     for b in range(B):

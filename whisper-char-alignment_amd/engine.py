@@ -389,11 +389,14 @@ class WhisperAMD:
         return B
 
     def greedy_decode(self, mel, pcm, n_samples, initial_tokens, suppress_mask, blank_mask, sample_len, eot, timestamp_begin,
-                      apply_timestamp_rules=True, max_initial_timestamp_index=50, batch=None, no_speech=-1):
+                      apply_timestamp_rules=True, max_initial_timestamp_index=50, batch=None, no_speech=-1, sot_index=0, prefill=0):
         """C ABI wca_greedy_decode. mel [B,n_mels,3000] f32 cuda XOR pcm [B,stride] f32 cuda (+ n_samples).
         Returns (tokens [B, n_initial+sample_len] int32, n_tokens [B] int32, sum_logprobs [B] f32) as numpy arrays; the
         encoder state stays in the engine for a following align_batch(pcm=None, ...). With no_speech >= 0 (the
-        <|nospeech|> token id) self.last_no_speech_prob [B] holds DecodingResult.no_speech_prob."""
+        <|nospeech|> token id) self.last_no_speech_prob [B] holds DecodingResult.no_speech_prob.
+        sot_index (position of <|sot|> in initial_tokens: no_speech_prob is read there) and prefill (1: one batched forward
+        over the initial tokens instead of one decode step per position) select wca_greedy_decode_ex, which also allows
+        n_initial + sample_len = n_text_ctx + 1; the defaults make today's wca_greedy_decode call."""
         self._bind_stream()
         B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(batch))  # batch=: decode a state queued by encode_batch
         n_init = len(initial_tokens)
@@ -405,12 +408,16 @@ class WhisperAMD:
         blank = np.ascontiguousarray(blank_mask, dtype=np.uint8) if blank_mask is not None else None
         if sup.shape[0] != self.dims.n_vocab or (blank is not None and blank.shape[0] != self.dims.n_vocab):
             raise ValueError("filter masks must have n_vocab entries")
-        opts = _lib.DecodeOpts(int(sample_len), int(eot), int(timestamp_begin), 1 if apply_timestamp_rules else 0,
-                               int(max_initial_timestamp_index), int(no_speech))
+        fields = (int(sample_len), int(eot), int(timestamp_begin), 1 if apply_timestamp_rules else 0, int(max_initial_timestamp_index),
+                  int(no_speech))
+        if sot_index == 0 and prefill == 0 and T <= self.dims.n_text_ctx:
+            opts, entry = _lib.DecodeOpts(*fields), self._lib.wca_greedy_decode
+        else:
+            opts, entry = _lib.DecodeOptsEx(*fields, int(sot_index), int(prefill)), self._lib.wca_greedy_decode_ex
         nsp = np.full(B, np.nan, dtype=np.float32)
         if mel is not None:
             mel = mel.contiguous().float()
-        _lib.check(self._lib.wca_greedy_decode(
+        _lib.check(entry(
             self._h, _ptr(mel) if mel is not None else None, _ptr(pcm) if pcm is not None else None,
             pcm.shape[1] if pcm is not None else 0, _lib.i32_array(n_samples) if n_samples is not None else None, B,
             _lib.i32_array(initial_tokens), n_init, sup.ctypes.data_as(C.c_void_p),
@@ -419,6 +426,12 @@ class WhisperAMD:
             nsp.ctypes.data_as(_lib._pf) if no_speech >= 0 else None))
         self.last_no_speech_prob = nsp
         return tokens, n_tok, lp
+
+    def last_decode_positions(self):
+        """(positions per row fed by the batched prefill, positions fed one decode step at a time) of the last greedy_decode."""
+        pre, step = C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.wca_last_decode_positions(self._h, C.byref(pre), C.byref(step)))
+        return pre.value, step.value
 
     def decode(self, mel, options=None):
         """whisper.decode(model, mel, options) (infer_ali.py:60)."""

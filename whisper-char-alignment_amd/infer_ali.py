@@ -140,6 +140,13 @@ def infer_dataset(args, model=None):
                              "pass --vocab <local multilingual.tiktoken>, or choose --teacher text explicitly to teacher-force the "
                              "dataset transcript (not the reference's behaviour)")
         args.teacher = "asr"
+    initial_prompt = getattr(args, "initial_prompt", None)
+    if initial_prompt is not None:
+        # openai-whisper's transcribe(initial_prompt=...): conditions the ASR pre-pass, so it only applies where that gives the text
+        if args.teacher != "asr":
+            raise SystemExit("--initial_prompt conditions the ASR pre-pass: it applies to --teacher asr only")
+        if args.vocab is None:
+            raise SystemExit("--initial_prompt is BPE-encoded: pass --vocab <local multilingual.tiktoken>")
     if rank == 0:
         print(args)
         if args.teacher == "text":
@@ -157,7 +164,7 @@ def infer_dataset(args, model=None):
         raise SystemExit("--n_mels %d does not match the checkpoint (%d); large-v3 needs --n_mels 128" % (args.n_mels, model.dims.n_mels))
     tokenizer = get_tokenizer(model.is_multilingual, language="English", vocab_path=args.vocab)
     # language="en" + task=transcribe -> ASR and alignment using whisper (infer_ali.py:40)
-    asr_options = DecodingOptions(language="en", vocab_path=args.vocab)
+    asr_options = DecodingOptions(language="en", vocab_path=args.vocab, prompt=initial_prompt)
     if args.teacher == "asr" and args.vocab is None and not args.random_init:
         raise SystemExit("--teacher asr turns token ids back into text: pass --vocab <local multilingual.tiktoken>")
     extra = {"alignment_file": args.alignment_file} if args.alignment_file else {}
@@ -358,7 +365,7 @@ def infer_dataset(args, model=None):
         if args.teacher == "text":
             notes["teacher_note"] = "ground-truth transcript teacher-forced; the reference aligns the ASR hypothesis (infer_ali.py:60-68)"
         with open(os.path.join(args.output_dir, filename + ".json"), "w") as f:
-            json.dump({**{k: v for k, v in vars(args).items() if k != "word_confidence" or v}, **results, **notes, "utterances": len(all_times), "seconds": elapsed}, f)
+            json.dump({**{k: v for k, v in vars(args).items() if k not in ("word_confidence", "initial_prompt") or v}, **results, **notes, "utterances": len(all_times), "seconds": elapsed}, f)
         if args.save_prediction:
             import joblib
             joblib.dump(all_predictions, os.path.join(args.output_dir, filename + "-predictions.pkl"))
@@ -401,6 +408,9 @@ def parse_args(argv=None):
                         "against the exact f16 weights (the reference's fp32 forward to fp32 summation noise; word times equal the CPU reference's); "
                         "f16: operands rounded to f16 once -- 1.9x faster, word times within one frame for ~98.5 %% of the boundaries")
     p.add_argument("--readers", type=int, default=4, help="reader threads (audio decode + tokenisation ahead of the GPU)")
+    p.add_argument("--initial_prompt", type=str, default=None,
+                   help="text that conditions the ASR pre-pass (openai-whisper's initial_prompt: DecodingOptions(prompt=...)), e.g. the "
+                        "spelling of names and domain words; --teacher asr only, needs --vocab; recorded in the result JSON")
     p.add_argument("--word_confidence", action="store_true",
                    help="per-word probabilities (openai-whisper's word `probability`: the mean over a word's tokens of the teacher token's "
                         "softmax probability over the text vocabulary [:eot]), computed on the GPU; with --save_prediction every record "
