@@ -97,7 +97,7 @@ typedef struct {
 } wca_align_opts;
 
 const char* wca_last_error(void);
-int wca_version(void);   /* 8: wca_greedy_decode_ex (prompt / prefix: sot_index, batched prefill); 7: exactly two precision modes */
+int wca_version(void);   /* 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: wca_greedy_decode_ex (prompt / prefix: sot_index, batched prefill); 7: exactly two precision modes */
 
 /* ---- engine lifetime ------------------------------------------------------------------------ */
 /* A new engine is in the CONTRACT precision mode (WCA_PRECISION_REFERENCE: every stage on (hi, lo) operand pairs = the fp32 forward of
@@ -377,40 +377,27 @@ int wca_test_gemm_ln(wca_engine* e, const void* a_f16_dev, const void* w_f16_dev
 int wca_test_gemm_rows(wca_engine* e, const void* a_f16_dev, const float* x_f32_dev, const float* gamma_dev, const float* beta_dev,
                        const void* w_f16_dev, const float* bias_dev, void* c_dev, int M, int N, int K, int gelu, int out_mode, int splitk,
                        int groups, void* kv_k_f16_dev, void* kv_v_f16_dev, int T_max, int kv_t);
-/* diagnostic build of the pipelined 256x256 GEMM that records s_memtime stamps per K tile into dbg_dev
- * ([4 blocks][8 waves][64 tiles][8] u64); development aid for tools/gemm_stamps.py, never used by the product.
- * out_mode: bits 0-7 as wca_test_gemm (0 / 2 / 4), bit 8 GELU, bit 9 pair operands (a = [M][hi(K) | lo(K)], plain w: the SPLITW form),
- * bits 12-15 / 16-19: when non-zero, tile coordinates are taken modulo these (m, n) -- an L2-resident operand footprint, outputs
- * collide; with the wrap set dbg_dev may be NULL (no stamps: plain timing of the wrapped launch); bits 20-21: 0 wrap operand and output
- * addresses, 1 operand addresses only, 2 output addresses only; bit 22: every LDS-DMA piece reads 1 KiB of contiguous memory (timing only) */
-int wca_test_gemm_stamped(wca_engine* e, const void* a_f16_dev, const void* w_f16_dev, void* c_dev, int M, int N, int K,
-                          int out_mode, unsigned long long* dbg_dev);
 /* diagnostic, process-wide (the product never calls it; 0 = the contract's three passes per product): leave single MFMA passes out of the
  * encoder's pair attention -- bit 0 K_lo Q_hi, bit 1 K_hi Q_lo, bit 2 V_lo P_hi, bit 3 V_hi P_lo; masks 0, 1, 2, 3, 4, 8, 9, 12, 15 exist.
  * tools/precision_ablation.py --attn-drop: the product-level ablation of timing.py:58's fp32 attention. */
 int wca_test_set_attn_split_drop(int mask);
-/* A/B and test switches of the library, process-wide (csrc/debug_switch.cpp; every default is the shipped choice and the product never calls
- * this): "attn_split_variant" (1: pair attention on the 16x16x32 kernel everywhere), "attn_variant" (f16 attention: 1 / 3), "head_stats_general"
- * (1: the general head-statistics kernel), "gemm_supertile" (m-panels per supertile), "ln_pair_v4", "fail_precision_alloc" (1: the next
- * precision switch fails its allocation: the roll-back test), "attn_split_drop", "gemm_ring" (1: the pair GEMM on round 4's two-slot rings). The environment variable of the same
- * meaning (WCA_ATTN_SPLIT_VARIANT, ...) is read ONCE, as the switch's initial value, never per launch. */
+/* test switches of the library, process-wide (csrc/debug_switch.cpp; every switch starts at 0, the shipped choice, and the product never calls
+ * this): "attn_split_variant" (1: pair attention on the 16x16x32 kernel everywhere), "head_stats_general" (1: the general head-statistics
+ * kernel), "fail_precision_alloc" (1: the next precision switch fails its allocation: the roll-back test), "attn_split_drop" (as
+ * wca_test_set_attn_split_drop), "gemm_ring" (1: the pair GEMM on round 4's two-slot rings). No environment variable sets them. */
 int wca_test_set_switch(const char* name, int value);
 /* the [batch][n_text_layer * n_text_head] head selection scores (timing.py:13-43) of the LAST fused batch, after it was fetched (no batch in
  * flight): tools/precision_ablation.py compares them with the oracle's */
 int wca_test_last_scores(wca_engine* e, int batch, float* scores_host);
 /* q,k,v [B][n][H*64] f16 device -> o [B][nq][H*64] f16; cap_dev [B][H][nq][cap_ld] f32 or NULL.
  * causal: bit 0 = causal mask; bits 8-9 = kernel variant (0 auto, 1 the 16x16x32-MFMA kernel, 2 the 32x32x16-MFMA
- * kernel that serves the encoder's un-masked self-attention = what auto picks, 3 the same with the row sums on the vector
- * ALU: an experiment that was not adopted) */
+ * kernel that serves the encoder's un-masked self-attention = what auto picks; 3 is WCA_ERR_INVALID) */
 int wca_test_attention(wca_engine* e, const void* q_dev, const void* k_dev, const void* v_dev, void* o_dev,
                        float* cap_dev, int cap_ld, int cap_cols, int B, int H, int nq, int nk, int causal);
 /* split-mode attention (attention_split.hip): q2,k2,v2 [B][n][2*H*64] f16 rows [hi(H*64) | lo(H*64)] -> o2 [B][nq][2*H*64]
  * likewise; cap_dev as above (the three-pass fp32 logits times scale). causal: bit 0 only. */
 int wca_test_attention_split(wca_engine* e, const void* q2_dev, const void* k2_dev, const void* v2_dev, void* o2_dev,
                              float* cap_dev, int cap_ld, int cap_cols, int B, int H, int nq, int nk, int causal);
-/* diagnostic build with s_memtime stamps per key tile ([4 blocks][4 waves][32 tiles][8] u64); tools/attn_stamps.py */
-int wca_test_attention_stamped(wca_engine* e, const void* q_dev, const void* k_dev, const void* v_dev, void* o_dev, int B, int H,
-                               int nq, int nk, unsigned long long* dbg_dev);
 /* one step of the greedy decoder's filters + update on caller-supplied logits (kernel parity test) */
 int wca_test_decode_select(wca_engine* e, const float* logits_dev, int batch, int n_vocab, int32_t* tokens_dev, int T_max,
                            int cur_len, int n_initial, const uint8_t* suppress_mask_dev, const uint8_t* blank_mask_dev,

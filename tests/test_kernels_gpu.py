@@ -358,9 +358,7 @@ def _attn_ref(q, k, v, H, causal):
     # ragged shapes (query / key counts not multiples of the 128-row block / 64-key tile, a single key tile, one query row)
     (2, 3, 150, 200, 1 << 8, 0), (2, 3, 150, 200, 2 << 8, 0), (2, 6, 1500, 1500, 1 << 8, 0), (1, 2, 97, 33, 2 << 8, 0),
     (1, 2, 33, 1500, 2 << 8, 0), (3, 1, 129, 64, 2 << 8, 0), (1, 5, 2, 65, 2 << 8, 0), (1, 20, 1500, 1500, 2 << 8, 0),
-    (1, 2, 300, 1500, 2 << 8, 0), (1, 3, 700, 129, 2 << 8, 0), (2, 3, 257, 200, 2 << 8, 0), (1, 2, 64, 192, 2 << 8, 0),
-    # 3 << 8 = the 32x32x16 kernel with the row sums on the vector ALU (an experiment kept for A/B; auto = 2 << 8, sums on the matrix pipe)
-    (2, 3, 150, 200, 3 << 8, 0), (1, 2, 97, 33, 3 << 8, 0), (1, 5, 2, 65, 3 << 8, 0), (1, 20, 1500, 1500, 3 << 8, 0), (2, 3, 257, 200, 3 << 8, 0)])
+    (1, 2, 300, 1500, 2 << 8, 0), (1, 3, 700, 129, 2 << 8, 0), (2, 3, 257, 200, 2 << 8, 0), (1, 2, 64, 192, 2 << 8, 0)])
 def test_attention(eng, lib, wca, B, H, nq, nk, causal, cap_cols):
     g = torch.Generator().manual_seed(nq * 13 + nk)
     d = H * 64
@@ -385,7 +383,7 @@ def test_attention(eng, lib, wca, B, H, nq, nk, causal, cap_cols):
         torch.testing.assert_close(got, qk_ref[..., :cap_cols], rtol=1e-4, atol=1e-4)
 
 
-def test_attention_rescale_branch_forced(eng, lib, wca):
+def test_attention_rescale_branch_forced_on_both_kernels(eng, lib, wca):
     """The lazy running-max scheme of both kernels takes its rescale branch only when a row's maximum grows: force it at a
     chosen LATE key tile (one key row spiked against one query row, far above everything before it) and compare the FULL
     output with an fp64 reference (a passing check on bounded random data never exercises that branch)."""
@@ -406,12 +404,24 @@ def test_attention_rescale_branch_forced(eng, lib, wca):
     vh = v.double().view(B, S, H, 64).permute(0, 2, 1, 3)
     ref = (torch.softmax(qh @ kh.transpose(-1, -2) * 0.125, -1) @ vh).permute(0, 2, 1, 3).reshape(B, S, d)
     qd, kd, vd = q.cuda(), k.cuda(), v.cuda()
-    for variant in (1, 2, 3):
+    for variant in (1, 2):
         out = torch.full((B, S, d), float("nan"), dtype=torch.float16, device="cuda")
         wca._lib.check(lib.wca_test_attention(eng._h, _vp(qd), _vp(kd), _vp(vd), _vp(out), None, 0, 0, B, H, S, S, variant << 8))
         torch.cuda.synchronize()
         err = (out.double().cpu() - ref).abs().max().item()
         assert err <= 4e-3, (variant, err)
+
+
+def test_attention_variant_3_is_rejected(eng, lib, wca):
+    """Variant bits 3 (an f16 attention form that was never adopted and has been removed) are an error, and nothing is launched."""
+    B, H, S = 1, 2, 128
+    d = H * 64
+    q = torch.randn(B, S, d, device="cuda").half()
+    out = torch.full((B, S, d), float("nan"), dtype=torch.float16, device="cuda")
+    assert lib.wca_test_attention(eng._h, _vp(q), _vp(q), _vp(q), _vp(out), None, 0, 0, B, H, S, S, 3 << 8) < 0
+    assert b"variant 3" in lib.wca_last_error()
+    torch.cuda.synchronize()
+    assert torch.isnan(out).all()
 
 
 def test_attention_bench_sized_encoder(eng, lib, wca):

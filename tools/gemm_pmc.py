@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Launches the contract mode's pair GEMMs of one encoder block (product kernels, M = 64 x 1500) a few times: the workload of the
-rocprofv3 --pmc passes in tools/session_r05_measure.sh.   python tools/gemm_pmc.py [launches=6]"""
+rocprofv3 --pmc passes (one counter set per run).   python tools/gemm_pmc.py [launches=6]"""
 import ctypes as C
 import importlib
 import os

@@ -89,14 +89,12 @@ SIGNATURES = {
     "wca_test_decode_select": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, C.POINTER(DecodeOpts), _vp, _vp]),
     "wca_test_gemm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "wca_test_gemm_ln": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
-    "wca_test_gemm_stamped": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "wca_test_set_attn_split_drop": (_i, [_i]),
     "wca_test_set_switch": (_i, [C.c_char_p, _i]),
     "wca_test_last_scores": (_i, [_vp, _i, _pf]),
     "wca_test_gemm_pairs": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "wca_test_attention": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
     "wca_test_attention_split": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
-    "wca_test_attention_stamped": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "wca_test_layernorm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i]),
     "wca_test_layernorm_split": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i]),
     "wca_test_encoder": (_i, [_vp, _vp, _i, _vp]),

@@ -75,7 +75,7 @@ __device__ __forceinline__ half4 lds_read_tr_asm(unsigned addr) {
     __builtin_amdgcn_sched_barrier(0);                                                                        \
   } while (0)
 
-template <bool CAUSAL, bool CAPTURE, bool STAMP = false>
+template <bool CAUSAL, bool CAPTURE>
 __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   half_t* lds = reinterpret_cast<half_t*>(smem);  // [buf][K tile | V tile]
@@ -164,27 +164,14 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
   stage(0, 0);
   if (nkt > 1) stage(1, 1);
   int slot = 0;
-#define WCA_STAMP(IDX)                                                                      \
-  do {                                                                                     \
-    if (STAMP) {                                                                           \
-      unsigned long long t_;                                                               \
-      __builtin_amdgcn_sched_barrier(0);                                                   \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");          \
-      __builtin_amdgcn_sched_barrier(0);                                                   \
-      if (lane == 0 && blockIdx.x < 4 && kt < 32) a.dbg[((blockIdx.x * 4 + wave) * 32 + kt) * 8 + (IDX)] = t_; \
-    }                                                                                      \
-  } while (0)
   for (int kt = 0; kt < nkt; ++kt) {
-    WCA_STAMP(0);
     if (kt + 1 < nkt) {
       asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    WCA_STAMP(1);
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    WCA_STAMP(2);
     if (kt + 2 < nkt) {
       int nslot = slot + 2;
       nslot = nslot >= 3 ? nslot - 3 : nslot;
@@ -219,7 +206,6 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) st[s][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf1[t], qf[s][1], st[s][t], 0, 0, 0);
     }
-    WCA_STAMP(3);
 
     // ---- online softmax on the RAW scores (scale > 0 commutes with max); p = exp2(s*c - m*c), c = scale*log2(e).
     // Both 16-row subtiles advance together (one combined rescale branch) so their dependency chains interleave.
@@ -339,7 +325,6 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
       rsum = __builtin_amdgcn_mfma_f32_16x16x32_f16(ones, pf[s][1], rsum, 0, 0, 0);
       l_run[s] += rsum[0];
     }
-    WCA_STAMP(4);
 
     // ---- O^T += V^T P^T. V^T fragment (A operand): lane holds V[key(k)][d = dt*16 + fr],
     // k order matches pf: j<4 -> key (2*k2)*16 + 4*fg + j, j>=4 -> key (2*k2+1)*16 + 4*fg + (j-4).
@@ -367,9 +352,7 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
         }
       }
     }
-    WCA_STAMP(5);
   }
-#undef WCA_STAMP
 
   // ---- epilogue: ot[s][dt][r] = O[q = fr][d = dt*16 + 4*fg + r]
 #pragma unroll
@@ -415,19 +398,12 @@ struct IntC {
   static constexpr int value = V;
 };
 
-__device__ __forceinline__ float xor32_sumf(float v) {
-  const unsigned u = __float_as_uint(v);
-  auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// VSUM (experiment, AttnArgs.variant 3; NOT the default): row sums as fp32 VALU adds of the lane's 32 probabilities per tile (per-lane
-// partial, the two lane halves of a row combined once at the end) instead of four `ones x P^T` MFMAs per tile -- a fifth of the tile's
-// matrix work. Interleaved A/B at 64 x 16 x 1500 x 1500 (tools/attn_ab.py 64 10 2,3): 0.708 vs 0.724 ms median on one box, 0.701 vs 0.699 on
-// another. Rejected for its numerics: the MFMA form sums exactly the f16-rounded probabilities that enter P.V, so the rounding of P cancels
-// between numerator and denominator (a row dominated by one key returns that V row exactly); summing the unrounded fp32 values adds
-// ~2^-12 relative noise per layer, and the bench's 301-utterance f16 parity leg went from 58 to 139 boundaries outside one frame with it.
-template <bool STAMP, bool VSUM = false>
+// (Measured and removed: row sums as fp32 VALU adds of the lane's 32 probabilities per tile (per-lane partial, the two lane halves of a
+// row combined once at the end) instead of four `ones x P^T` MFMAs per tile -- a fifth of the tile's matrix work. Interleaved A/B at
+// 64 x 16 x 1500 x 1500: 0.708 vs 0.724 ms median on one box, 0.701 vs 0.699 on another. Rejected for its numerics: the MFMA form sums
+// exactly the f16-rounded probabilities that enter P.V, so the rounding of P cancels between numerator and denominator (a row dominated
+// by one key returns that V row exactly); summing the unrounded fp32 values adds ~2^-12 relative noise per layer, and the bench's
+// 301-utterance f16 parity leg went from 58 to 139 boundaries outside one frame with it.)
 __global__ __launch_bounds__(256) void attn32_kernel(AttnArgs a) {
   constexpr int NW = 4;  // waves per workgroup, 32 query rows each
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -523,31 +499,18 @@ __global__ __launch_bounds__(256) void attn32_kernel(AttnArgs a) {
 
   stage(0, 0);
   if (nkt > 1) stage(1, 1);
-#define WCA_STAMP(IDX)                                                                      \
-  do {                                                                                     \
-    if (STAMP) {                                                                           \
-      unsigned long long t_;                                                               \
-      __builtin_amdgcn_sched_barrier(0);                                                   \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");          \
-      __builtin_amdgcn_sched_barrier(0);                                                   \
-      if (lane == 0 && blockIdx.x < 4 && kt < 32 && wave < 4) a.dbg[((blockIdx.x * 4 + wave) * 32 + kt) * 8 + (IDX)] = t_; \
-    }                                                                                      \
-  } while (0)
 
   // one 64-key tile in ring slot SLOT (compile time: the LDS offsets of all 24 fragment reads are immediates)
   auto tile = [&](auto slot_c, int kt) {
     constexpr int SLOT = decltype(slot_c)::value;
     constexpr int SB = SLOT * SLOT_BYTES;
-    WCA_STAMP(0);
     if (kt + 1 < nkt) {
       asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // this wave's four requests of tile kt + 1 stay in flight
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    WCA_STAMP(1);
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    WCA_STAMP(2);
     if (kt + 2 < nkt) stage((SLOT + 2) % 3, kt + 2);
 
     // ---- S^T: st[kb][r] = s'(q = l31, key = 64 kt + 32 kb + (r&3) + 8 (r>>2) + 4 hh) - m_running
@@ -583,7 +546,6 @@ __global__ __launch_bounds__(256) void attn32_kernel(AttnArgs a) {
     v0b[2] = lds_read_tr_asm<SB + 2 * 2048 + 1024>(va[0]);
     v0a[3] = lds_read_tr_asm<SB + 3 * 2048>(va[0]);
     v0b[3] = lds_read_tr_asm<SB + 3 * 2048 + 1024>(va[0]);
-    WCA_STAMP(3);
     // keys past nk (last tile only): wave-uniform branch
     if (kt * KT + KT > a.nk) {
 #pragma unroll
@@ -635,25 +597,15 @@ __global__ __launch_bounds__(256) void attn32_kernel(AttnArgs a) {
     // p = exp2(s' - m); P^T fragment of k-step s (16 keys): registers 8 (s&1) .. +7 of key block s >> 1
     half8 pf[4];
     {
-      float ps[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s4 = 0; s4 < 4; ++s4)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float p = __builtin_amdgcn_exp2f(st[s4 >> 1][8 * (s4 & 1) + j]);
-          pf[s4][j] = (half_t)p;
-          if (VSUM) ps[j & 3] += p;
-        }
-      if (VSUM) {
-        l_run += (ps[0] + ps[1]) + (ps[2] + ps[3]);
-      } else {
-        // row sums on the matrix pipe: D[i][q] = sum_k P^T[k][q] for every i (the f16-rounded probabilities that enter P.V)
-        f32x16 rs = __builtin_amdgcn_mfma_f32_32x32x16_f16(ones, pf[0], zero16, 0, 0, 0);
+        for (int j = 0; j < 8; ++j) pf[s4][j] = (half_t)__builtin_amdgcn_exp2f(st[s4 >> 1][8 * (s4 & 1) + j]);
+      // row sums on the matrix pipe: D[i][q] = sum_k P^T[k][q] for every i (the f16-rounded probabilities that enter P.V)
+      f32x16 rs = __builtin_amdgcn_mfma_f32_32x32x16_f16(ones, pf[0], zero16, 0, 0, 0);
 #pragma unroll
-        for (int s4 = 1; s4 < 4; ++s4) rs = __builtin_amdgcn_mfma_f32_32x32x16_f16(ones, pf[s4], rs, 0, 0, 0);
-        l_run += rs[0];
-      }
-      WCA_STAMP(4);
+      for (int s4 = 1; s4 < 4; ++s4) rs = __builtin_amdgcn_mfma_f32_32x32x16_f16(ones, pf[s4], rs, 0, 0, 0);
+      l_run += rs[0];
       // ---- O^T += V^T P^T: A operand element j of lane half hh = V[key 16 s + 8 (j>>2) + 4 hh + (j&3)][d = 32 db + l31]
       WCA_LGKM_WAIT8(0, v0a[0], v0b[0], v0a[1], v0b[1], v0a[2], v0b[2], v0a[3], v0b[3]);
       v1a[0] = lds_read_tr_asm<SB + 0 * 2048>(va[1]);
@@ -676,7 +628,6 @@ __global__ __launch_bounds__(256) void attn32_kernel(AttnArgs a) {
         ot[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[s4], ot[1], 0, 0, 0);
       }
     }
-    WCA_STAMP(5);
   };
   // the ring slot of tile kt is kt % 3: three tiles per trip, every slot a compile-time constant
   for (int kt = 0; kt < nkt; kt += 3) {
@@ -684,11 +635,10 @@ __global__ __launch_bounds__(256) void attn32_kernel(AttnArgs a) {
     if (kt + 1 < nkt) tile(IntC<1>{}, kt + 1);
     if (kt + 2 < nkt) tile(IntC<2>{}, kt + 2);
   }
-#undef WCA_STAMP
 
   // ---- epilogue: ot[db][r] = O[q = l31][d = 32 db + (r&3) + 8 (r>>2) + 4 hh]; the two halves of a row are swapped pairwise
   // (v_permlane32_swap) so that each lane stores 16 contiguous bytes
-  const float inv = 1.0f / (VSUM ? xor32_sumf(l_run) : l_run);
+  const float inv = 1.0f / l_run;
   half_t* op = a.O + (long)b * a.o_bs + (long)qrow * a.o_rs + h * 64;
 #pragma unroll
   for (int db = 0; db < 2; ++db)
@@ -838,7 +788,7 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
   if ((a.q_rs % 8) || (a.k_rs % 8) || (a.v_rs % 8) || (a.o_rs % 4)) return hipErrorInvalidValue;
   if (a.cap != nullptr && ((a.cap_ld % 4) != 0 || a.cap_ld < ((a.cap_cols + 3) & ~3))) return hipErrorInvalidValue;
   const bool cap = a.cap != nullptr && a.cap_cols > 0;
-  if (a.nq == 1 && !cap && !a.dbg && (!a.causal || a.nk == 1)) {  // greedy-decode steps: the KV cache holds exactly the causal prefix
+  if (a.nq == 1 && !cap && (!a.causal || a.nk == 1)) {  // greedy-decode steps: the KV cache holds exactly the causal prefix
     hipLaunchKernelGGL(attn_decode_kernel, dim3(a.H * a.B), dim3(256), 0, s, a);
     return hipGetLastError();
   }
@@ -846,17 +796,9 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
   const size_t shmem = 3 * 2 * TILE * sizeof(half_t);  // 48 KiB
   // encoder self-attention (no mask, no capture, long rows): the 32x32x16 kernel; a.variant 1 forces the 16x16x32 one, 2 the
   // 32x32x16 one (tests)
-  const int variant = a.variant ? a.variant : debug_switch(DBG_ATTN_VARIANT);  // debugging aid
-  const bool use32 = !a.causal && !cap && (a.o_rs % 8) == 0 && variant != 1 && (a.nq >= 64 || variant >= 2);
+  const bool use32 = !a.causal && !cap && (a.o_rs % 8) == 0 && a.variant != 1 && (a.nq >= 64 || a.variant == 2);
   if (use32) {
-    dim3 g32(((a.nq + 127) / 128) * a.H * a.B), b32(256);
-    if (a.dbg) hipLaunchKernelGGL((attn32_kernel<true>), g32, b32, shmem, s, a);
-    else if (variant == 3) hipLaunchKernelGGL((attn32_kernel<false, true>), g32, b32, shmem, s, a);  // row sums on the vector ALU (experiment)
-    else hipLaunchKernelGGL((attn32_kernel<false, false>), g32, b32, shmem, s, a);                  // default: row sums on the matrix pipe
-    return hipGetLastError();
-  }
-  if (a.dbg) {
-    hipLaunchKernelGGL((attn_kernel<false, false, true>), grid, block, shmem, s, a);
+    hipLaunchKernelGGL(attn32_kernel, grid, block, shmem, s, a);
     return hipGetLastError();
   }
   if (a.causal) {

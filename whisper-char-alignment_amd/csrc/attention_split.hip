@@ -803,7 +803,7 @@ hipError_t launch_attention_split(const AttnArgs& a, hipStream_t s) {
     if (e != hipSuccess) return e;                                                                                           \
     hipLaunchKernelGGL((attn_split_kernel<C, P, W>), dim3(((a.nq + (W) * 32 - 1) / ((W) * 32)) * a.H * a.B), dim3((W) * 64), shmem, s, a); \
   } while (0)
-  // the encoder form (no mask, no capture) on the 32x32x16 kernel; AttnArgs.variant 1 (tests / A-B: WCA_ATTN_SPLIT_VARIANT=1) keeps the 16x16x32 one
+  // the encoder form (no mask, no capture) on the 32x32x16 kernel; AttnArgs.variant 1 (tests; switch attn_split_variant = 1 for A/B) keeps the 16x16x32 one
   const int variant = a.variant ? a.variant : debug_switch(DBG_ATTN_SPLIT_VARIANT);
   if (!a.causal && !cap && a.nq >= 64 && variant != 1 && (a.o_rs % 8) == 0 && (a.o_lo % 8) == 0) {
 #define WCA_LAUNCH_A32(D)                                                                                                             \

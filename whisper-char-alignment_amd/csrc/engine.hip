@@ -1573,7 +1573,7 @@ int run_token_logprobs(wca_engine* e, hipStream_t s, const int64_t* tokens_dev, 
 extern "C" {
 
 const char* wca_last_error(void) { return g_err.c_str(); }
-int wca_version(void) { return 8; }   // 8: prompted greedy decode (wca_greedy_decode_ex, batched prefill); 7: two precision modes only (the per-stage precision mask, its setter / getter and the mixed
+int wca_version(void) { return 9; }   // 9: the two diagnostic stamp entry points removed, no switch read from the environment; 8: prompted greedy decode (wca_greedy_decode_ex, batched prefill); 7: two precision modes only (the per-stage precision mask, its setter / getter and the mixed
                                       // state are gone); 6: teacher-token log-probs (wca_align_batch_enqueue_ex / _fetch_ex, wca_token_logprobs);
                                       // 5: a new engine is in the contract mode; wca_engine_create_ex, W_lo slab, switch table
 
@@ -3204,41 +3204,6 @@ int wca_test_gemm_rows(wca_engine* e, const void* a_f16, const float* x_f32, con
   return WCA_OK;
 }
 
-int wca_test_gemm_stamped(wca_engine* e, const void* a, const void* w, void* c, int M, int N, int K, int out_mode, unsigned long long* dbg_dev) {
-  const int wrap_m = (out_mode >> 12) & 0xf, wrap_n = (out_mode >> 16) & 0xf;
-  if (!e || (!dbg_dev && wrap_m == 0)) return fail(WCA_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(e->device));
-  const bool pairs = (out_mode >> 9) & 1;
-  GemmArgs g{};
-  g.A = (const half_t*)a;
-  g.lda = pairs ? 2 * K : K;
-  g.a_lo = pairs ? K : 0;
-  g.W = (const half_t*)w;
-  g.ldw = K;
-  g.C = c;
-  g.ldc = N;
-  g.M = M;
-  g.N = N;
-  g.K = K;
-  g.out_mode = out_mode & 0xff;
-  g.gelu = (out_mode >> 8) & 1;
-  if (g.out_mode == 4) {
-    g.ldc = 2 * N;
-    g.c_lo = N;
-  }
-  g.site = 1;
-  g.force_tile = pairs ? 0 : 257;
-  g.dbg = dbg_dev;
-  g.dbg_wrap_m = wrap_m;
-  g.dbg_wrap_n = wrap_n;
-  g.dbg_wrap_kind = (out_mode >> 20) & 7;
-  HIPCHK(launch_gemm(g, e->stream));
-  return WCA_OK;
-}
-
-int wca_test_attention_stamped(wca_engine* e, const void* q, const void* k, const void* v, void* o, int B, int H, int nq, int nk,
-                               unsigned long long* dbg_dev);
-
 int wca_test_set_attn_split_drop(int mask) {
   if (mask != 0 && mask != 1 && mask != 2 && mask != 3 && mask != 4 && mask != 8 && mask != 9 && mask != 12 && mask != 15)
     return fail(WCA_ERR_INVALID, "attention pass mask %d is not instantiated", mask);
@@ -3264,9 +3229,11 @@ int wca_test_last_scores(wca_engine* e, int batch, float* scores_host) {
   return WCA_OK;
 }
 
-static int test_attention_impl(wca_engine* e, const void* q, const void* k, const void* v, void* o, float* cap_dev, int cap_ld, int cap_cols,
-                               int B, int H, int nq, int nk, int causal, unsigned long long* dbg) {
+int wca_test_attention(wca_engine* e, const void* q, const void* k, const void* v, void* o, float* cap_dev, int cap_ld, int cap_cols,
+                       int B, int H, int nq, int nk, int causal) {
   if (!e) return fail(WCA_ERR_INVALID, "null engine");
+  const int variant = (causal >> 8) & 3;  // 0 auto, 1 the 16x16x32 kernel, 2 the 32x32x16 kernel (attention.hip)
+  if (variant == 3) return fail(WCA_ERR_INVALID, "attention variant 3 does not exist");
   HIPCHK(hipSetDevice(e->device));
   AttnArgs a{};
   const int d = H * 64;
@@ -3293,15 +3260,9 @@ static int test_attention_impl(wca_engine* e, const void* q, const void* k, cons
   a.B = B;
   a.scale = 0.125f;
   a.causal = causal & 1;
-  a.variant = (causal >> 8) & 3;  // 0 auto, 1 the 16x16x32 kernel, 2 the 32x32x16 kernel (attention.hip)
-  a.dbg = dbg;
+  a.variant = variant;
   HIPCHK(launch_attention(a, e->stream));
   return WCA_OK;
-}
-
-int wca_test_attention(wca_engine* e, const void* q, const void* k, const void* v, void* o, float* cap_dev, int cap_ld, int cap_cols,
-                       int B, int H, int nq, int nk, int causal) {
-  return test_attention_impl(e, q, k, v, o, cap_dev, cap_ld, cap_cols, B, H, nq, nk, causal, nullptr);
 }
 
 int wca_test_attention_split(wca_engine* e, const void* q2, const void* k2, const void* v2, void* o2, float* cap_dev, int cap_ld, int cap_cols,
@@ -3337,12 +3298,6 @@ int wca_test_attention_split(wca_engine* e, const void* q2, const void* k2, cons
   a.causal = causal & 1;
   HIPCHK(launch_attention(a, e->stream));
   return WCA_OK;
-}
-
-int wca_test_attention_stamped(wca_engine* e, const void* q, const void* k, const void* v, void* o, int B, int H, int nq, int nk,
-                               unsigned long long* dbg_dev) {
-  if (!dbg_dev) return fail(WCA_ERR_INVALID, "null argument");
-  return test_attention_impl(e, q, k, v, o, nullptr, 0, 0, B, H, nq >= 0 ? nq : ((-nq) & 0xfffff), nk, nq >= 0 ? 0 : (((-nq) >> 20) << 8), dbg_dev);  // nq < 0: -(variant << 20 | nq)
 }
 
 int wca_test_decode_select(wca_engine* e, const float* logits_dev, int batch, int n_vocab, int32_t* tokens_dev, int T_max, int cur_len,

@@ -440,8 +440,7 @@ struct GemmIntC {
   static constexpr int value = V;
 };
 
-// STAMP: 0 product; 1 s_memtime stamps (+ the tile wrap below); 2 the tile wrap alone (timing of an L2-resident operand footprint)
-template <int OUT_MODE, bool GELU, int SITE, int STAMP = 0, int SPLITW_MODE = 0>
+template <int OUT_MODE, bool GELU, int SITE, int SPLITW_MODE = 0>
 __global__ __launch_bounds__(512) void gemm256p_f16_kernel(GemmArgs a) {
   // SPLITW_MODE: 0 single f16 operands; 1 pair operands, two-slot rings for A and W (round 4); 2 pair operands, THREE A slots + ONE W slot (round 5, below)
   constexpr bool SPLITW = SPLITW_MODE != 0;
@@ -492,20 +491,16 @@ __global__ __launch_bounds__(512) void gemm256p_f16_kernel(GemmArgs a) {
   const int nt_r = rho >> 4, i_r = rho & 15;
   const int wsrc_row = (OUT_MODE == 0 || OUT_MODE == 3 || OUT_MODE == 4) ? ((nt_r >> 1) * 32 + (i_r >> 2) * 8 + (nt_r & 1) * 4 + (i_r & 3)) : rho;
   // per-lane byte offsets inside a tile (tile base and K offset are wave-uniform and added per request)
-  // diagnostic builds, dbg_wrap_kind bit 2 ("packed sources", timing only -- the products are garbage): every DMA piece reads 1 KiB of CONTIGUOUS
-  // global memory (as if the operands were stored tile-packed, [panel][K step][256 rows][64]) instead of 8 rows x 128 bytes lda apart; same bytes per
-  // panel, same panels. Answers whether the row-strided source pattern costs anything in the L2 -> LDS path.
-  const bool packed_src = STAMP != 0 && (a.dbg_wrap_kind & 4) != 0;
-  const unsigned va = packed_src ? (unsigned)(rho * 64 + c0 * 8) * 2u : (unsigned)(rho * a.lda + c0 * 8) * 2u;
-  const unsigned vw = packed_src ? (unsigned)(wsrc_row * 64 + c0 * 8) * 2u : (unsigned)(wsrc_row * a.ldw + c0 * 8) * 2u;
-  const unsigned sa64 = packed_src ? 64u * 64u * 2u : 64u * a.lda * 2u, sw64 = packed_src ? 64u * 64u * 2u : 64u * a.ldw * 2u;
+  const unsigned va = (unsigned)(rho * a.lda + c0 * 8) * 2u;
+  const unsigned vw = (unsigned)(wsrc_row * a.ldw + c0 * 8) * 2u;
+  const unsigned sa64 = 64u * a.lda * 2u, sw64 = 64u * a.ldw * 2u;
 
   // request g (0..7) of a K tile: g>>1 = row block (64 rows), g&1 = operand (A / W); 1 KiB per wave each.
   // ta / tw: byte offset of (tile row 0, K offset) in A / W.
   // LDS ring. Two-slot form: slot b = [A K-tile | W K-tile] at b * 64 KiB. RING3 (pair operands): A K-tiles in THREE slots of 32 KiB at 0 / 32 / 64 KiB and
   // ONE W slot at 96 KiB: a W K-tile is read from LDS only in the even step that first uses it (the odd step re-uses the register fragments), so it is dead
   // after that step's mid barrier and the next one can land in its place; the room goes to a third A slot, so that the A tile of step s + 2 can be requested
-  // already in HALF 0 of step s (into the slot of step s - 1) and stays in flight across the step's barrier (counted vmcnt(4)): the DMA requests spread over
+  // already in HALF 0 of step s (into the slot of step s - 1) and stays in flight across the step's barrier (counted vmcnt, see below): the DMA requests spread over
   // both halves (4 + 4 instead of 0 + 8) and get 1.3 steps of latency cover instead of 0.5-1 (profiles/r05_gemm_stamps.txt: every wave spent ~360 of
   // ~3 450 cycles per step in the vmcnt wait, and half 1 with its 8 requests took 1 600-2 000 cycles against 770-960 for half 0).
   auto a_slot = [&](int buf) -> half_t* { return RING3 ? lds + buf * TILE256 : lds + buf * (2 * TILE256); };
@@ -533,6 +528,12 @@ __global__ __launch_bounds__(512) void gemm256p_f16_kernel(GemmArgs a) {
       }
     }
   };
+  // RING3: in half 0 of a K step with a successor, every wave requests the A K-tile of step s + 2, one request per 64-row block, and these requests
+  // are the ONLY ones the wait before the step's barrier leaves in flight: they are the wave's youngest, so everything issued before them has landed
+  // when the barrier opens -- the operands of step s + 1, a new tile's bias (stage_bias) and the epilogue stores of the tile before. (Two-slot rings:
+  // vmcnt(0) there.)
+  constexpr int RING3_A_REQS_IN_FLIGHT = 4;
+  static_assert(RING3_A_REQS_IN_FLIGHT * 64 == 256, "one request per 64-row block of the 256-row A tile");
 
   const int fr = lane & 15, fg = lane >> 4;
   const int pos0 = fg ^ ((fr >> 1) & 7);
@@ -549,11 +550,9 @@ __global__ __launch_bounds__(512) void gemm256p_f16_kernel(GemmArgs a) {
   const int nk = SPLITW ? 2 * (a.K / BK) : a.K / BK;   // K steps of one tile
   // byte offset of K step s inside an A row / a W row
   auto a_koff = [&](int s_) -> unsigned {
-    if (packed_src) return (unsigned)s_ * (256u * 64u * 2u);   // (K step s of a panel: its own 32 KiB)
     return SPLITW ? (unsigned)(((s_ & 1) * (int)a.a_lo + (s_ >> 1) * BK) * 2) : (unsigned)(s_ * (BK * 2));
   };
   auto w_koff = [&](int s_) -> unsigned {
-    if (packed_src) return (unsigned)(SPLITW ? (s_ >> 1) : s_) * (256u * 64u * 2u);
     return SPLITW ? (unsigned)((s_ >> 1) * (BK * 2)) : (unsigned)(s_ * (BK * 2));
   };
   // (A/B experiments that did NOT pay on MI355X and were removed: giving the two wave groups different
@@ -609,26 +608,8 @@ __global__ __launch_bounds__(512) void gemm256p_f16_kernel(GemmArgs a) {
   } else {
     tile_of(id, tm_, tn_);
   }
-  // diagnostic builds (STAMP != 0): tile coordinates taken modulo (dbg_wrap_m, dbg_wrap_n) -- for the OPERAND addresses (every workgroup then
-  // walks the same few panels: an L2-resident footprint), for the OUTPUT addresses (stores collide in a few tiles), or both (dbg_wrap_kind 1 / 2 / 0;
-  // dbg_wrap_m == 15: the diagnostic instantiation without any wrap)
-  auto wrap_opnd = [&](int& tm, int& tn) {
-    if (STAMP != 0 && a.dbg_wrap_m > 0 && a.dbg_wrap_m < 15 && (a.dbg_wrap_kind & 3) != 2) {
-      tm %= a.dbg_wrap_m;
-      tn %= a.dbg_wrap_n;
-    }
-  };
-  auto wrap_out = [&](int& tm, int& tn) {
-    if (STAMP != 0 && a.dbg_wrap_m > 0 && a.dbg_wrap_m < 15 && (a.dbg_wrap_kind & 3) != 1) {
-      tm %= a.dbg_wrap_m;
-      tn %= a.dbg_wrap_n;
-    }
-  };
-  int tma_ = tm_, tna_ = tn_;
-  wrap_opnd(tma_, tna_);
-  wrap_out(tm_, tn_);
   int m0 = tm_ * 256, n0 = tn_ * 256;
-  unsigned ta = (unsigned)(tma_ * 256) * a.lda * 2u, tw = (unsigned)(tna_ * 256) * a.ldw * 2u;
+  unsigned ta = (unsigned)m0 * a.lda * 2u, tw = (unsigned)n0 * a.ldw * 2u;
 
   // (Round-5 experiment, removed: starting the 32 workgroups of an XCD label up to 1/8 ... 1 tile period apart, so that the tile epilogues --
   //  256 KiB of stores per workgroup, issued by all 256 CUs at the same moment when they run in phase -- spread over the others' K loops:
@@ -657,16 +638,6 @@ __global__ __launch_bounds__(512) void gemm256p_f16_kernel(GemmArgs a) {
   WCA_LOAD_HALF(a_slot(0), w_slot(0), xb0, wb0, w0, x0);
   int ring_a = 0;          // RING3: A slot of the current K step (runs on across tile boundaries)
 
-#define WCA_STAMP(IDX)                                                                      \
-  do {                                                                                     \
-    if (STAMP == 1) {                                                                      \
-      unsigned long long t_;                                                               \
-      __builtin_amdgcn_sched_barrier(0);                                                   \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");          \
-      __builtin_amdgcn_sched_barrier(0);                                                   \
-      if (lane == 0 && blockIdx.x < 4 && v == (int)blockIdx.x) a.dbg[((blockIdx.x * 8 + wave) * 64 + kt) * 8 + (IDX)] = t_; \
-    }                                                                                      \
-  } while (0)
   for (;;) {
     // the tile after this one (persistent launch only: gridDim.x < nwg needs nk even and >= 2, see launch_gemm)
     const int vn = v + G;
@@ -684,11 +655,8 @@ __global__ __launch_bounds__(512) void gemm256p_f16_kernel(GemmArgs a) {
       idn = has_next ? xcd_remap(vn, nwg) : id;
       tile_of(idn, tmn_, tnn_);
     }
-    int tman_ = tmn_, tnan_ = tnn_;
-    wrap_opnd(tman_, tnan_);
-    wrap_out(tmn_, tnn_);
     const int m0n = tmn_ * 256, n0n = tnn_ * 256;
-    const unsigned tan = (unsigned)(tman_ * 256) * a.lda * 2u, twn = (unsigned)(tnan_ * 256) * a.ldw * 2u;
+    const unsigned tan = (unsigned)m0n * a.lda * 2u, twn = (unsigned)n0n * a.ldw * 2u;
     // one K step; PAR >= 0: the step's parity (= its A ring slot) is a compile-time constant (SPLITW: even = first use of a W tile)
     auto kstep = [&](auto par_c, const int kt) {
       constexpr int PAR = decltype(par_c)::value;
@@ -707,7 +675,6 @@ __global__ __launch_bounds__(512) void gemm256p_f16_kernel(GemmArgs a) {
       const unsigned ka = (in_tile2 ? ta + a_koff(kt + 2) : tan + a_koff(kt + 2 - nk));
       const unsigned kw = (in_tile2 ? tw + w_koff(kt + 2) : twn + w_koff(kt + 2 - nk));
       const int prv = RING3 ? (ring_a == 0 ? 2 : ring_a - 1) : 0;   // RING3: the A slot of step kt - 1 = of step kt + 2 (every wave is past that step's barrier)
-      WCA_STAMP(0);
       // ---- K half 0 (fragments w0/x0 were fetched under the previous step's half 1). The 12 fragment reads of
       // half 1 are issued two at a time between groups of 4 MFMAs.
 #pragma unroll
@@ -728,18 +695,15 @@ __global__ __launch_bounds__(512) void gemm256p_f16_kernel(GemmArgs a) {
         }
         // RING3: the A tile of step kt + 2 goes out HERE, in half 0 (the two-slot ring cannot: its target slot is still being read), one request in every
         // second group; half 1 keeps only the W requests of the even steps -- at most 4 DMA requests per half instead of 8 in half 1
-        if (RING3 && (g & 1) == 0 && more2) stage_one(prv, 0, ka, kw, g);
+        if (RING3 && (g & 1) == 0 && (g >> 1) < RING3_A_REQS_IN_FLIGHT && more2) stage_one(prv, 0, ka, kw, g);
         __builtin_amdgcn_sched_barrier(0);
       }
-      WCA_STAMP(1);
-      // all ds_reads of slot `cur` are retired; K step s+1 has landed. Two-slot rings: it is the only DMA in flight. RING3: the 4 youngest requests are
+      // all ds_reads of slot `cur` are retired; K step s+1 has landed. Two-slot rings: it is the only DMA in flight. RING3: the youngest requests are
       // the A tile of step s+2 just requested in half 0 (younger than the W requests of the previous step's half 1) and stay in flight across the barrier.
-      if (RING3 && more2) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+      if (RING3 && more2) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"i"(RING3_A_REQS_IN_FLIGHT) : "memory");
       else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      WCA_STAMP(2);
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      WCA_STAMP(3);
       // ---- K half 1. Slot `cur` is refilled with K step s+2 (of this tile, or of the next one) and step s+1's
       // half-0 fragments are fetched (within a tile), ONE DMA request and up to two ds_reads per group of 4 MFMAs: 64 back-to-back
       // requests per CU right after the barrier serialise in the memory pipe and delay the MFMAs of the waves that
@@ -778,15 +742,12 @@ __global__ __launch_bounds__(512) void gemm256p_f16_kernel(GemmArgs a) {
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-      WCA_STAMP(4);
       if (RING3) ring_a = nxt;
     };
     // (SPLITW with the step parity as a compile-time constant -- the loop unrolled by two -- spills 70-90 VGPRs: both steps' LDS
     //  base addresses stay live; the runtime parity costs two scalar branches per step)
     for (int kt = 0; kt < nk; ++kt) kstep(GemmIntC<-1>{}, kt);
 
-    if (STAMP == 1 && lane == 0 && blockIdx.x < 4 && (v / G) < 12)
-      a.dbg[((blockIdx.x * 8 + wave) * 64 + 48 + v / G) * 8 + 0] = __builtin_readcyclecounter();
     {
       // opaque copies: keeps the epilogue's per-lane address arithmetic from being hoisted out of the tile loop
       // (live across the K loop it cost 30 VGPRs and spilled)
@@ -803,11 +764,9 @@ __global__ __launch_bounds__(512) void gemm256p_f16_kernel(GemmArgs a) {
       else
         epilogue_wide<OUT_MODE, GELU, KernArgs>(*ap, acc, m0 + wr * 128, n0 + wc * 64, fr_e, fg_e, bias_lds + par * 256 + wc * 64);
     }
-    if (STAMP == 1 && lane == 0 && blockIdx.x < 4 && (v / G) < 12)
-      a.dbg[((blockIdx.x * 8 + wave) * 64 + 48 + v / G) * 8 + 1] = __builtin_readcyclecounter();
     if (!has_next) break;
     // next tile's bias -> the other buffer: its last readers (the epilogue two tiles back) are behind at least one
-    // barrier, and the first mid-tile barrier of the new tile (vmcnt(0) on every wave) makes it visible
+    // barrier, and the first mid-tile barrier of the new tile makes it visible (RING3: the wait before it leaves only younger requests in flight)
     par ^= 1;
     stage_bias(par, n0n);
     v = vn;
@@ -825,7 +784,6 @@ __global__ __launch_bounds__(512) void gemm256p_f16_kernel(GemmArgs a) {
     // that they are not live across the epilogue (that cost 13-18 spilled VGPRs)
     WCA_LOAD_HALF(a_slot(RING3 ? ring_a : 0), w_slot(0), xb0, wb0, w0, x0);
   }
-#undef WCA_STAMP
 #undef WCA_LOAD_HALF
 }
 
@@ -1016,10 +974,7 @@ hipError_t launch_gemm(const GemmArgs& a_in, hipStream_t s) {
       const int nk = (splitw ? 2 : 1) * (a.K / BK);
       if (a.force_tile != 258 && nk >= 2 && (nk & 1) == 0 && tiles256 > n_cu) grid = dim3((unsigned)n_cu);
       // (K <= 2048 since round 3: the K-doubled QKV / fc1 of the split mode measure -5 % / -3 % with the supertile order, same-box A/B)
-      if (a.supertile <= 0) {
-        const int sw = debug_switch(DBG_GEMM_SUPERTILE);   // (tile-order experiments)
-        a.supertile = sw > 0 ? sw : (((splitw ? 2 : 1) * a.K <= 2048 && (a.N + 255) / 256 <= 32) ? 8 : 1);
-      }
+      if (a.supertile <= 0) a.supertile = ((splitw ? 2 : 1) * a.K <= 2048 && (a.N + 255) / 256 <= 32) ? 8 : 1;
     }
   } else {
     const int ntn = (a.N + BN - 1) / BN, ntm = (a.M + BM - 1) / BM;
@@ -1041,42 +996,24 @@ hipError_t launch_gemm(const GemmArgs& a_in, hipStream_t s) {
   }
   // the dynamic-LDS limit is a per-device property of each kernel symbol: remembered per (symbol, device) so that several
   // engines (one per GPU) in one process and concurrent host threads are served correctly
-#define WCA_LAUNCH_K(KERN, OM, G, S)                                                              \
+#define WCA_LAUNCH_K(...)                                                                         \
   do {                                                                                            \
     static std::atomic<unsigned> attr_mask{0};                                                    \
     if (!(attr_mask.load(std::memory_order_acquire) & (1u << (dev & 31)))) {                      \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN<OM, G, S>),           \
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(__VA_ARGS__),              \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); \
       if (e != hipSuccess) return e;                                                              \
       attr_mask.fetch_or(1u << (dev & 31), std::memory_order_release);                            \
     }                                                                                             \
-    hipLaunchKernelGGL((KERN<OM, G, S>), grid, block, shmem, s, a);                               \
-  } while (0)
-#define WCA_LAUNCH_K4(KERN, OM, G, S, ST, SW)                                                     \
-  do {                                                                                            \
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN<OM, G, S, ST, SW>),     \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);   \
-    if (e != hipSuccess) return e;                                                                \
-    hipLaunchKernelGGL((KERN<OM, G, S, ST, SW>), grid, block, shmem, s, a);                       \
-  } while (0)
-#define WCA_LAUNCH_K5R(KERN, OM, G, S, RING)                                                        \
-  do {                                                                                              \
-    static std::atomic<unsigned> attr_mask5{0};                                                     \
-    if (!(attr_mask5.load(std::memory_order_acquire) & (1u << (dev & 31)))) {                       \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN<OM, G, S, 0, RING>), \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);   \
-      if (e != hipSuccess) return e;                                                                \
-      attr_mask5.fetch_or(1u << (dev & 31), std::memory_order_release);                             \
-    }                                                                                               \
-    hipLaunchKernelGGL((KERN<OM, G, S, 0, RING>), grid, block, shmem, s, a);                        \
+    hipLaunchKernelGGL((__VA_ARGS__), grid, block, shmem, s, a);                                  \
   } while (0)
 #define WCA_LAUNCH_S(OM, G, S)                            \
   do {                                                    \
-    if (pipelined && splitw && ring == 1) { if ((S) == 4) WCA_LAUNCH_K5R(gemm256p_f16_kernel, OM, G, 4, 1); else WCA_LAUNCH_K5R(gemm256p_f16_kernel, OM, G, 1, 1); } \
-    else if (pipelined && splitw) { if ((S) == 4) WCA_LAUNCH_K5R(gemm256p_f16_kernel, OM, G, 4, 2); else if ((S) == 3) WCA_LAUNCH_K5R(gemm256p_f16_kernel, OM, G, 3, 2); else if ((S) == 2) WCA_LAUNCH_K5R(gemm256p_f16_kernel, OM, G, 2, 2); else WCA_LAUNCH_K5R(gemm256p_f16_kernel, OM, G, 1, 2); } \
-    else if (pipelined) WCA_LAUNCH_K(gemm256p_f16_kernel, OM, G, S); \
-    else if (big) WCA_LAUNCH_K(gemm256_f16_kernel, OM, G, S);  \
-    else WCA_LAUNCH_K(gemm_f16_kernel, OM, G, S);         \
+    if (pipelined && splitw && ring == 1) { if ((S) == 4) WCA_LAUNCH_K(gemm256p_f16_kernel<OM, G, 4, 1>); else WCA_LAUNCH_K(gemm256p_f16_kernel<OM, G, 1, 1>); } \
+    else if (pipelined && splitw) { if ((S) == 4) WCA_LAUNCH_K(gemm256p_f16_kernel<OM, G, 4, 2>); else if ((S) == 3) WCA_LAUNCH_K(gemm256p_f16_kernel<OM, G, 3, 2>); else if ((S) == 2) WCA_LAUNCH_K(gemm256p_f16_kernel<OM, G, 2, 2>); else WCA_LAUNCH_K(gemm256p_f16_kernel<OM, G, 1, 2>); } \
+    else if (pipelined) WCA_LAUNCH_K(gemm256p_f16_kernel<OM, G, S>); \
+    else if (big) WCA_LAUNCH_K(gemm256_f16_kernel<OM, G, S>);  \
+    else WCA_LAUNCH_K(gemm_f16_kernel<OM, G, S>);         \
   } while (0)
 #define WCA_LAUNCH(OM, G)                     \
   do {                                        \
@@ -1088,34 +1025,6 @@ hipError_t launch_gemm(const GemmArgs& a_in, hipStream_t s) {
       default: WCA_LAUNCH_S(OM, G, 0); break; \
     }                                         \
   } while (0)
-  // diagnostic launches (tools/gemm_stamps.py; never the product path): s_memtime stamps (a.dbg) and / or the tile wrap, for the encoder's
-  // kernel forms only
-  if (a.dbg != nullptr || a.dbg_wrap_m > 0) {
-    if (!pipelined || a.dbg_wrap_n <= 0 != (a.dbg_wrap_m <= 0)) return hipErrorInvalidValue;
-#define WCA_LAUNCH_DIAG(OM, G, SW)                                                      \
-  do {                                                                                  \
-    if (a.dbg != nullptr) WCA_LAUNCH_K4(gemm256p_f16_kernel, OM, G, 1, 1, SW);          \
-    else WCA_LAUNCH_K4(gemm256p_f16_kernel, OM, G, 1, 2, SW);                           \
-  } while (0)
-    if (splitw && ring == 1) {
-      if (a.out_mode == 4 && a.gelu) WCA_LAUNCH_DIAG(4, true, 1);
-      else if (a.out_mode == 4) WCA_LAUNCH_DIAG(4, false, 1);
-      else if (a.out_mode == 2 && !a.gelu) WCA_LAUNCH_DIAG(2, false, 1);
-      else return hipErrorInvalidValue;
-    } else if (splitw) {
-      if (a.out_mode == 4 && a.gelu) WCA_LAUNCH_DIAG(4, true, 2);
-      else if (a.out_mode == 4) WCA_LAUNCH_DIAG(4, false, 2);
-      else if (a.out_mode == 2 && !a.gelu) WCA_LAUNCH_DIAG(2, false, 2);
-      else return hipErrorInvalidValue;
-    } else {
-      if (a.out_mode == 0 && a.gelu) WCA_LAUNCH_DIAG(0, true, 0);
-      else if (a.out_mode == 0) WCA_LAUNCH_DIAG(0, false, 0);
-      else if (a.out_mode == 2 && !a.gelu) WCA_LAUNCH_DIAG(2, false, 0);
-      else return hipErrorInvalidValue;
-    }
-#undef WCA_LAUNCH_DIAG
-    return hipGetLastError();
-  }
   if (a.out_mode == 3) {
     // residual + LayerNorm epilogue: persistent 256 x 256 kernel only (every workgroup of a 256-row panel must be resident:
     // one workgroup per CU, grid <= CUs), N a multiple of 256; the caller falls back to out_mode 2 + launch_layernorm_f16
@@ -1129,8 +1038,8 @@ hipError_t launch_gemm(const GemmArgs& a_in, hipStream_t s) {
     shmem += (2 * 512 + 2560) * sizeof(float);  // gamma | beta (double buffered) + the statistics exchange area
     grid = dim3((unsigned)(n_cu & ~7));          // round-based panel walk: 8 XCD labels x n_cu / 8 workgroups (idle ones exit)
     switch (a.site) {
-      case 4: WCA_LAUNCH_K(gemm256p_f16_kernel, 3, false, 4); break;
-      default: WCA_LAUNCH_K(gemm256p_f16_kernel, 3, false, 1); break;
+      case 4: WCA_LAUNCH_K(gemm256p_f16_kernel<3, false, 4>); break;
+      default: WCA_LAUNCH_K(gemm256p_f16_kernel<3, false, 1>); break;
     }
   } else if (a.out_mode == 0) {
     if (a.gelu) WCA_LAUNCH(0, true); else WCA_LAUNCH(0, false);
@@ -1147,8 +1056,6 @@ hipError_t launch_gemm(const GemmArgs& a_in, hipStream_t s) {
 #undef WCA_LAUNCH
 #undef WCA_LAUNCH_S
 #undef WCA_LAUNCH_K
-#undef WCA_LAUNCH_K4
-#undef WCA_LAUNCH_K5R
   {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -7,10 +7,9 @@ namespace wca {
 
 typedef _Float16 half_t;
 
-// ---------------------------------------------------------------- A/B and test switches (debug_switch.cpp; wca_test_set_switch)
-enum { DBG_ATTN_SPLIT_VARIANT = 0, DBG_ATTN_VARIANT, DBG_HEAD_STATS_GENERAL, DBG_GEMM_SUPERTILE, DBG_LN_PAIR_V4, DBG_FAIL_PRECISION_ALLOC,
-       DBG_ATTN_SPLIT_DROP, DBG_GEMM_RING, DBG_SWITCH_COUNT };
-int debug_switch(int id);                            // current value (its environment variable, if any, read once as the initial value)
+// ---------------------------------------------------------------- test switches (debug_switch.cpp; wca_test_set_switch)
+enum { DBG_ATTN_SPLIT_VARIANT = 0, DBG_HEAD_STATS_GENERAL, DBG_FAIL_PRECISION_ALLOC, DBG_ATTN_SPLIT_DROP, DBG_GEMM_RING, DBG_SWITCH_COUNT };
+int debug_switch(int id);                            // current value (0 until set)
 int set_debug_switch(const char* name, int value);   // 0, or -1 for an unknown name
 
 // ---------------------------------------------------------------- GEMM (gemm.hip)
@@ -46,9 +45,6 @@ struct GemmArgs {
                            // 3: f32 accumulate + LayerNorm of the updated row -> ln_out (f16); the row statistics are
                            //    exchanged between the N/256 workgroups that share a 256-row panel (gemm_epilogue.h)
   unsigned a_bytes, w_bytes; // valid bytes behind A / W (buffer-descriptor bounds); 0 => derived for flat layouts
-  unsigned long long* dbg; // diagnostic builds only: s_memtime stamps (never set by the product path)
-  int dbg_wrap_kind;       // diagnostic builds only: bits 0-1: 0 wrap operand AND output addresses, 1 operands only, 2 outputs only; bit 2: packed (contiguous) DMA sources
-  int dbg_wrap_m, dbg_wrap_n; // diagnostic builds only: tile coordinates taken modulo these (an L2-resident operand footprint; outputs collide)
   int force_tile;          // 0 auto, 128 or 256: force a tile shape (tests)
   // out_mode 3 only (the residual GEMMs of a transformer block, N = n_state <= 2048, a multiple of 256):
   const float* ln_gamma;   // [N]
@@ -103,7 +99,6 @@ struct AttnArgs {
   int nq, nk, H, B;
   float scale;                             // applied to q.k (head_dim^-0.5)
   int causal;
-  unsigned long long* dbg;                 // diagnostic builds only (s_memtime stamps)
   int variant;                             // 0 auto, 1 force the 16x16x32 kernel, 2 force the 32x32x16 kernel (tests)
   // split-f16 operands (reference-precision mode): every value x is carried as hi = f16(x), lo = f16(x - hi). The pointers above
   // address the hi halves; the lo half of an element lives `*_lo` elements further (same strides). split != 0 selects
