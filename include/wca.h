@@ -8,6 +8,9 @@
  *
  *   wca_log_mel            dataset.py:46-48, dataset.py:107-109, README.md:101-103
  *                          (whisper.pad_or_trim + whisper.log_mel_spectrogram)
+ *   wca_log_mel_long       whisper.log_mel_spectrogram(audio, n_mels, padding=N_SAMPLES) of a WHOLE recording, the first step of
+ *                          upstream whisper.transcribe (not called by the reference, whose entry points stop at 30 s)
+ *   wca_mel_window         whisper.pad_or_trim(mel[:, seek : seek + segment_size], N_FRAMES), the window cut of whisper.transcribe's loop
  *   wca_get_attentions     timing.py:45-67   get_attentions(): teacher-forced forward with every
  *                          cross-attention QK captured (timing.py:50-58), [:max_frames] slice,
  *                          median_filter, *qk_scale, softmax (timing.py:63-66); logits returned
@@ -97,7 +100,7 @@ typedef struct {
 } wca_align_opts;
 
 const char* wca_last_error(void);
-int wca_version(void);   /* 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: wca_greedy_decode_ex (prompt / prefix: sot_index, batched prefill); 7: exactly two precision modes */
+int wca_version(void);   /* 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: wca_greedy_decode_ex (prompt / prefix: sot_index, batched prefill); 7: exactly two precision modes */
 
 /* ---- engine lifetime ------------------------------------------------------------------------ */
 /* A new engine is in the CONTRACT precision mode (WCA_PRECISION_REFERENCE: every stage on (hi, lo) operand pairs = the fp32 forward of
@@ -135,6 +138,25 @@ int wca_set_allow_rounded_weights(wca_engine* e, int on);
  * mel_out_dev: [batch][n_mels][3000] f32. */
 int wca_log_mel(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, int batch,
                 float* mel_out_dev);
+
+/* Log-mel of a whole recording of any length (upstream whisper.transcribe: log_mel_spectrogram(audio, n_mels, padding=N_SAMPLES)).
+ * The signal is pcm_dev[0 .. n_samples) followed by 480000 zeros; STFT as wca_log_mel (n_fft 400, hop 160, periodic Hann, centred with
+ * reflect padding at both ends of the PADDED signal, last frame dropped): n_frames = (n_samples + 480000) / 160, written to
+ * *n_frames_out (may be NULL; it is set before ld is checked, so a call with ld = 0 asks for the size). log10(clamp 1e-10), ONE floor
+ * `max - 8` with the maximum over all frames of the recording (not per 30 s window), (x + 4) / 4.
+ * mel_out_dev: [n_mels][ld] f32 owned by the CALLER, ld >= n_frames (row m, frame t at m * ld + t; columns beyond n_frames are not
+ * touched). The raw log10 values rest in mel_out_dev between the two passes, so the engine keeps no buffer of the recording's size.
+ * Precision follows wca_set_precision like wca_log_mel: f64 DFT / filterbank accumulation in WCA_PRECISION_REFERENCE, f32 in the f16
+ * mode. n_samples in [0, 2^31 - 480001]; asynchronous on the engine's stream. */
+int wca_log_mel_long(wca_engine* e, const float* pcm_dev, int64_t n_samples, float* mel_out_dev, int64_t ld, int64_t* n_frames_out);
+
+/* pad_or_trim(mel[:, seek : seek + size], 3000) for `batch` windows of one long mel (mel_long_dev [n_mels][ld] f32 with n_frames valid
+ * frames, as wca_log_mel_long leaves it): mel_out_dev [batch][n_mels][3000] f32 with exact zeros at frames >= size -- the zero padding
+ * of the MEL domain that upstream's loop feeds its last, short window (not the log-mel of silence). The result is what
+ * wca_greedy_decode / wca_encode_batch / wca_get_attentions take as mel_dev. size outside [1, 3000], seek < 0 or seek + size > n_frames
+ * is WCA_ERR_INVALID (nothing is read); batch <= max_batch. */
+int wca_mel_window(wca_engine* e, const float* mel_long_dev, int64_t ld, int64_t n_frames, const int32_t* seek_host,
+                   const int32_t* size_host, int batch, float* mel_out_dev);
 
 /* mel_dev [batch][n_mels][3000] f32; tokens_dev [batch][n_tok] int64 (already sot..eot framed,
  * infer_ali.py:69-76; shorter utterances padded with any valid token id, true lengths in n_tok_host,

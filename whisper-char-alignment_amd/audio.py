@@ -102,6 +102,24 @@ def log_mel_spectrogram(audio, n_mels=80, padding=0, device=None, model=None):
     return eng.log_mel(audio.to(eng.device))
 
 
+def log_mel_spectrogram_long(audio, n_mels=80, device=None, model=None):
+    """whisper.log_mel_spectrogram(audio, n_mels, padding=N_SAMPLES) of a whole recording, as upstream's transcribe calls it:
+    audio f32 [n], any n -> [n_mels, (n + 480000) // 160] f32 on the GPU with ONE `max - 8` floor over the recording
+    (WhisperAMD.log_mel_long). A function of its own: log_mel_spectrogram keeps returning 3000 frames for every input it accepts."""
+    import torch
+    if model is None:
+        from .engine import default_engine
+        idx = 0
+        if isinstance(audio, torch.Tensor) and audio.is_cuda and audio.device.index is not None:
+            idx = audio.device.index
+        model = default_engine(idx)
+    if model.dims.n_mels != n_mels:
+        raise ValueError("engine was built for n_mels=%d, got %d" % (model.dims.n_mels, n_mels))
+    if not isinstance(audio, torch.Tensor):
+        audio = torch.from_numpy(np.asarray(audio, dtype=np.float32))
+    return model.log_mel_long(audio.to(model.device))
+
+
 # ------------------------------------------------------------------------------ file readers
 def _read_sphere(buf):
     if buf[:7] != b"NIST_1A":

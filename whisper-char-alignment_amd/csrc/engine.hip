@@ -1573,7 +1573,7 @@ int run_token_logprobs(wca_engine* e, hipStream_t s, const int64_t* tokens_dev, 
 extern "C" {
 
 const char* wca_last_error(void) { return g_err.c_str(); }
-int wca_version(void) { return 9; }   // 9: the two diagnostic stamp entry points removed, no switch read from the environment; 8: prompted greedy decode (wca_greedy_decode_ex, batched prefill); 7: two precision modes only (the per-stage precision mask, its setter / getter and the mixed
+int wca_version(void) { return 10; }   // 10: wca_log_mel_long / wca_mel_window (whole-recording log-mel, window cut); 9: the two diagnostic stamp entry points removed, no switch read from the environment; 8: prompted greedy decode (wca_greedy_decode_ex, batched prefill); 7: two precision modes only (the per-stage precision mask, its setter / getter and the mixed
                                       // state are gone); 6: teacher-token log-probs (wca_align_batch_enqueue_ex / _fetch_ex, wca_token_logprobs);
                                       // 5: a new engine is in the contract mode; wca_engine_create_ex, W_lo slab, switch table
 
@@ -2043,6 +2043,52 @@ int wca_log_mel(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const i
   int rc = stage_meta(e, batch, n_samples_host, nullptr, nullptr, nullptr, rows);
   if (rc) return rc;
   return run_logmel(e, pcm_dev, pcm_stride, rows[0], batch, mel_out_dev, false);
+}
+
+int wca_log_mel_long(wca_engine* e, const float* pcm_dev, int64_t n_samples, float* mel_out_dev, int64_t ld, int64_t* n_frames_out) {
+  if (!e || !mel_out_dev || (!pcm_dev && n_samples > 0)) return fail(WCA_ERR_INVALID, "null argument");
+  if (n_samples < 0 || n_samples > INT32_MAX - 480000) return fail(WCA_ERR_INVALID, "n_samples %lld outside [0, 2^31 - 480001]", (long long)n_samples);
+  const int64_t T = (n_samples + 480000) / 160;
+  if (n_frames_out) *n_frames_out = T;
+  if (ld < T) return fail(WCA_ERR_INVALID, "ld %lld < %lld frames of %lld samples + 30 s", (long long)ld, (long long)T, (long long)n_samples);
+  if (!e->have_filters) return fail(WCA_ERR_STATE, "mel_filters not loaded (wca_load_weight(\"mel_filters\"))");
+  HIPCHK(hipSetDevice(e->device));
+  if (int jr = join_phase2(e)) return jr;
+  LogMelLongArgs a{};
+  a.filters = e->mel_filters;
+  a.filt_lo = e->filt_lo;
+  a.filt_hi = e->filt_hi;
+  a.window = e->window;
+  a.twiddle = e->twiddle;
+  a.precise = e->split ? 1 : 0;
+  a.n_mels = e->dims.n_mels;
+  a.pcm = pcm_dev;
+  a.n_samples = n_samples;
+  a.mel_out = mel_out_dev;
+  a.ld = ld;
+  a.n_frames = T;
+  a.gmax = e->gmax;
+  HIPCHK(launch_logmel_long(a, e->stream));
+  return WCA_OK;
+}
+
+int wca_mel_window(wca_engine* e, const float* mel_long_dev, int64_t ld, int64_t n_frames, const int32_t* seek_host, const int32_t* size_host,
+                   int batch, float* mel_out_dev) {
+  if (!e || !mel_long_dev || !seek_host || !size_host || !mel_out_dev) return fail(WCA_ERR_INVALID, "null argument");
+  if (batch < 1 || batch > e->max_batch) return fail(WCA_ERR_INVALID, "batch %d outside [1,%d]", batch, e->max_batch);
+  if (n_frames < 1 || ld < n_frames) return fail(WCA_ERR_INVALID, "n_frames %lld / ld %lld invalid", (long long)n_frames, (long long)ld);
+  for (int b = 0; b < batch; ++b) {
+    if (size_host[b] < 1 || size_host[b] > N_FRAMES) return fail(WCA_ERR_INVALID, "size[%d]=%d outside [1,%d]", b, size_host[b], N_FRAMES);
+    if (seek_host[b] < 0 || (int64_t)seek_host[b] + size_host[b] > n_frames)
+      return fail(WCA_ERR_INVALID, "window %d: seek %d + size %d outside the %lld frames", b, seek_host[b], size_host[b], (long long)n_frames);
+  }
+  HIPCHK(hipSetDevice(e->device));
+  if (int jr = join_phase2(e)) return jr;
+  int* rows[4];
+  int rc = stage_meta(e, batch, seek_host, size_host, nullptr, nullptr, rows);
+  if (rc) return rc;
+  HIPCHK(launch_mel_window(mel_long_dev, ld, e->dims.n_mels, rows[0], rows[1], batch, mel_out_dev, e->stream));
+  return WCA_OK;
 }
 
 int wca_get_attentions(wca_engine* e, const float* mel_dev, const int64_t* tokens_dev, int batch, int n_tok, const int32_t* n_tok_host,

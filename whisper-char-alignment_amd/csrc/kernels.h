@@ -165,25 +165,45 @@ hipError_t launch_token_logprob(const float* logits, long ld, int vocab_end, int
                                 float* out, int* err, int err_bit, hipStream_t s);
 
 // ---------------------------------------------------------------- log-mel (logmel.hip)
-struct LogMelArgs {
-  const float* pcm;        // [B][pcm_stride] f32 16 kHz, already trimmed/padded by the caller or shorter
-  long pcm_stride;
-  const int* n_samples;    // [B] valid samples per utterance (<= 480000); device pointer
+struct LogMelTables {      // what pass 1 of every log-mel form reads
   const float* filters;    // [n_mels][201]
   const int* filt_lo;      // [n_mels] first non-zero bin of each filter (device)
   const int* filt_hi;      // [n_mels] one past the last non-zero bin (device)
   const float* window;     // [400] periodic hann
   const float* twiddle;    // [400][2] cos,sin(2*pi*m/400)
+  int precise;             // != 0: the DFT and the filterbank sums accumulate in f64 (reference-precision mode)
+  int n_mels;
+};
+struct LogMelArgs : LogMelTables {
+  const float* pcm;        // [B][pcm_stride] f32 16 kHz, already trimmed/padded by the caller or shorter
+  long pcm_stride;
+  const int* n_samples;    // [B] valid samples per utterance (<= 480000); device pointer
   float* mel_out;          // [B][n_mels][3000] f32 (may be nullptr)
   half_t* mel_tm;          // [B][3002][n_mels_pad] f16 time-major, rows 0 and 3001 zero (may be nullptr)
   int n_mels_pad;          // row length of mel_tm
   int tm_lo;               // != 0: mel_tm carries split values, hi at column m, lo = f16(v - hi) at column tm_lo + m
-  int precise;             // != 0: the DFT and the filterbank sums accumulate in f64 (reference-precision mode)
   float* scratch;          // [B][n_mels][3000] raw log10 values (required)
   unsigned* gmax;          // [B] ordered-int encoded running max (required)
-  int n_mels, B;
+  int B;
 };
 hipError_t launch_logmel(const LogMelArgs& a, hipStream_t s);
+
+// whisper.log_mel_spectrogram(audio, n_mels, padding=480000) of a recording of any length: n_samples of pcm followed by 480000 zeros,
+// n_frames = (n_samples + 480000) / 160 frames, ONE floor (max over the whole recording) - 8. mel_out [n_mels][ld] f32 (ld >= n_frames)
+// holds the raw log10 values between the two passes, so there is no scratch; gmax is one ordered-int word.
+struct LogMelLongArgs : LogMelTables {
+  const float* pcm;        // [n_samples] f32 16 kHz
+  long n_samples;
+  float* mel_out;          // [n_mels][ld]
+  long ld;
+  long n_frames;           // (n_samples + 480000) / 160
+  unsigned* gmax;
+};
+hipError_t launch_logmel_long(const LogMelLongArgs& a, hipStream_t s);
+
+// pad_or_trim(mel[:, seek : seek + size], 3000) for B windows of one long mel: out [B][n_mels][3000] f32, exact zeros at t >= size[b].
+// seek / size are device arrays; the caller has checked 0 <= seek, 1 <= size <= 3000, seek + size <= the long mel's frames.
+hipError_t launch_mel_window(const float* mel_long, long ld, int n_mels, const int* seek, const int* size, int B, float* out, hipStream_t s);
 
 // ---------------------------------------------------------------- post-processing (postproc.hip)
 struct HeadStatsArgs {

@@ -9,6 +9,9 @@
 //   Frames that only see zero padding are skipped: their value is exactly log10(1e-10) = -10.
 // Pass 2: floor/scale, writes the API layout [n_mels][3000] f32 and the time-major f16 image
 //   [3002][n_mels] (zero rows at both ends) that the conv-stem GEMM reads as overlapping windows.
+//
+// Whole recordings (upstream whisper.transcribe: log_mel_spectrogram(audio, n_mels, padding=N_SAMPLES)): the same pass 1 per frame on a
+//   grid sized from the recording, one device-wide maximum, pass 2 in place; then the window cut pad_or_trim(mel[:, seek:seek+size], 3000).
 #include "kernels.h"
 #include "wca_common.h"
 
@@ -38,33 +41,38 @@ __global__ void logmel_init_kernel(unsigned* gmax, int B) {
   if (i < B) gmax[i] = f2ord(-10.0f);
 }
 
-__global__ __launch_bounds__(256) void logmel_power_kernel(LogMelArgs a) {
-  __shared__ float s_e[NFFT / 2 + 1];   // even part  e[n] = s[n] + s[400-n], n = 1..199 ; e[0] = s[0], e[200] = s[200]
-  __shared__ float s_o[NFFT / 2 + 1];   // odd part   o[n] = s[n] - s[400-n]
-  __shared__ float s_raw[NFFT];
-  __shared__ f32x2 s_tw[NFFT];
-  __shared__ float s_pow[NBIN + 3];
-  __shared__ float s_max[4];
-  const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const int ns = a.n_samples[b];
-  if (t >= active_frames(ns)) return;
-  const float* pcm = a.pcm + (long)b * a.pcm_stride;
+// LDS of one frame's pass 1
+struct FrameLds {
+  float e[NFFT / 2 + 1];   // even part  e[n] = s[n] + s[400-n], n = 1..199 ; e[0] = s[0], e[200] = s[200]
+  float o[NFFT / 2 + 1];   // odd part   o[n] = s[n] - s[400-n]
+  float raw[NFFT];
+  f32x2 tw[NFFT];
+  float pow[NBIN + 3];
+  float max[4];
+};
+
+// Pass 1 of frame t by one 256-thread workgroup: `pcm` holds `ns` samples of a signal that is zero from there up to `total` samples
+// (the reflect padding mirrors at 0 and at total - 1). Thread m < n_mels writes log10(clamp(mel m)) to out[m * ld]; thread 0 folds the
+// frame's maximum into *gmax.
+__device__ __forceinline__ void frame_log_mel(const LogMelTables& a, FrameLds& s, const float* __restrict__ pcm, long ns, long total, long t,
+                                              float* __restrict__ out, long ld, unsigned* gmax) {
+  const int tid = threadIdx.x;
   for (int n = tid; n < NFFT; n += 256) {
-    int idx = t * HOP - NFFT / 2 + n;
+    long idx = t * HOP - NFFT / 2 + n;
     if (idx < 0) idx = -idx;                            // reflect (centre=True)
-    if (idx >= NSAMP) idx = 2 * (NSAMP - 1) - idx;
+    if (idx >= total) idx = 2 * (total - 1) - idx;
     const float x = (idx < ns) ? pcm[idx] : 0.f;
-    s_raw[n] = x * a.window[n];
-    s_tw[n] = reinterpret_cast<const f32x2*>(a.twiddle)[n];
+    s.raw[n] = x * a.window[n];
+    s.tw[n] = reinterpret_cast<const f32x2*>(a.twiddle)[n];
   }
   __syncthreads();
   for (int n = tid; n <= NFFT / 2; n += 256) {
     if (n == 0 || n == NFFT / 2) {
-      s_e[n] = s_raw[n];
-      s_o[n] = 0.f;
+      s.e[n] = s.raw[n];
+      s.o[n] = 0.f;
     } else {
-      s_e[n] = s_raw[n] + s_raw[NFFT - n];
-      s_o[n] = s_raw[n] - s_raw[NFFT - n];
+      s.e[n] = s.raw[n] + s.raw[NFFT - n];
+      s.o[n] = s.raw[n] - s.raw[NFFT - n];
     }
   }
   __syncthreads();
@@ -73,30 +81,30 @@ __global__ __launch_bounds__(256) void logmel_power_kernel(LogMelArgs a) {
     if (a.precise) {
       // reference-precision mode: f64 accumulation of the f32 products (the reference's FFT is accurate to ~1e-7 of the frame's
       // magnitude; a 199-term f32 sum is not). Twiddles and folded samples stay the f32 values above.
-      double re = (double)s_e[0] + ((k & 1) ? -(double)s_e[NFFT / 2] : (double)s_e[NFFT / 2]);
+      double re = (double)s.e[0] + ((k & 1) ? -(double)s.e[NFFT / 2] : (double)s.e[NFFT / 2]);
       double im = 0.0;
       int idx = 0;
       for (int n = 1; n < NFFT / 2; ++n) {
         idx += k;
         if (idx >= NFFT) idx -= NFFT;
-        const f32x2 tw = s_tw[idx];
-        re = fma((double)s_e[n], (double)tw[0], re);
-        im = fma((double)s_o[n], (double)tw[1], im);
+        const f32x2 tw = s.tw[idx];
+        re = fma((double)s.e[n], (double)tw[0], re);
+        im = fma((double)s.o[n], (double)tw[1], im);
       }
       const float ref = (float)re, imf = (float)im;  // torch.stft returns complex64; abs()**2 is then f32 arithmetic
-      s_pow[k] = ref * ref + imf * imf;
+      s.pow[k] = ref * ref + imf * imf;
     } else {
-      float re = s_e[0] + ((k & 1) ? -s_e[NFFT / 2] : s_e[NFFT / 2]);
+      float re = s.e[0] + ((k & 1) ? -s.e[NFFT / 2] : s.e[NFFT / 2]);
       float im = 0.f;
       int idx = 0;
       for (int n = 1; n < NFFT / 2; ++n) {
         idx += k;
         if (idx >= NFFT) idx -= NFFT;
-        const f32x2 tw = s_tw[idx];
-        re = fmaf(s_e[n], tw[0], re);
-        im = fmaf(s_o[n], tw[1], im);
+        const f32x2 tw = s.tw[idx];
+        re = fmaf(s.e[n], tw[0], re);
+        im = fmaf(s.o[n], tw[1], im);
       }
-      s_pow[k] = re * re + im * im;
+      s.pow[k] = re * re + im * im;
     }
   }
   __syncthreads();
@@ -108,21 +116,29 @@ __global__ __launch_bounds__(256) void logmel_power_kernel(LogMelArgs a) {
     float acc = 0.f;
     if (a.precise) {  // the reference's `filters @ magnitudes` is an f32 matmul in some blocked order: the f64 sum is within half an ulp of any
       double acc64 = 0.0;
-      for (int k = lo; k < hi; ++k) acc64 = fma((double)fr[k], (double)s_pow[k], acc64);
+      for (int k = lo; k < hi; ++k) acc64 = fma((double)fr[k], (double)s.pow[k], acc64);
       acc = (float)acc64;
     } else {
-      for (int k = lo; k < hi; ++k) acc = fmaf(fr[k], s_pow[k], acc);
+      for (int k = lo; k < hi; ++k) acc = fmaf(fr[k], s.pow[k], acc);
     }
     lv = log10f(fmaxf(acc, 1e-10f));
-    a.scratch[((long)b * a.n_mels + m) * NFRAMES + t] = lv;
+    out[(long)m * ld] = lv;
   }
   lv = wave_max(lv);
-  if ((tid & 63) == 0) s_max[tid >> 6] = lv;
+  if ((tid & 63) == 0) s.max[tid >> 6] = lv;
   __syncthreads();
   if (tid == 0) {
-    const float mx = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
-    atomicMax(a.gmax + b, f2ord(mx));
+    const float mx = fmaxf(fmaxf(s.max[0], s.max[1]), fmaxf(s.max[2], s.max[3]));
+    atomicMax(gmax, f2ord(mx));
   }
+}
+
+__global__ __launch_bounds__(256) void logmel_power_kernel(LogMelArgs a) {
+  __shared__ FrameLds s;
+  const int t = blockIdx.x, b = blockIdx.y;
+  const int ns = a.n_samples[b];
+  if (t >= active_frames(ns)) return;
+  frame_log_mel(a, s, a.pcm + (long)b * a.pcm_stride, ns, NSAMP, t, a.scratch + (long)b * a.n_mels * NFRAMES + t, NFRAMES, a.gmax + b);
 }
 
 __global__ __launch_bounds__(256) void logmel_finalize_kernel(LogMelArgs a) {
@@ -163,6 +179,38 @@ __global__ __launch_bounds__(256) void logmel_finalize_kernel(LogMelArgs a) {
   }
 }
 
+// ---- whole-recording form: the grid is sized from the recording, pass 1 leaves the raw log10 values in mel_out, pass 2 floors them
+// in place with the maximum over all frames.
+__device__ __forceinline__ long active_frames_long(long n_samples, long n_frames) {
+  const long na = (n_samples + 200 + HOP - 1) / HOP;
+  return na < n_frames ? na : n_frames;
+}
+
+__global__ void logmel_long_init_kernel(unsigned* gmax) { *gmax = f2ord(-10.0f); }
+
+__global__ __launch_bounds__(256) void logmel_long_power_kernel(LogMelLongArgs a) {
+  __shared__ FrameLds s;
+  const long t = blockIdx.x;   // the launch covers the active frames only
+  frame_log_mel(a, s, a.pcm, a.n_samples, a.n_samples + NSAMP, t, a.mel_out + t, a.ld, a.gmax);
+}
+
+__global__ __launch_bounds__(256) void logmel_long_finalize_kernel(LogMelLongArgs a) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= a.n_frames) return;
+  const float floorv = ord2f(*a.gmax) - 8.0f;
+  float* p = a.mel_out + (long)blockIdx.y * a.ld + t;
+  const float v = (t < active_frames_long(a.n_samples, a.n_frames)) ? *p : -10.0f;
+  *p = (fmaxf(v, floorv) + 4.0f) * 0.25f;
+}
+
+__global__ __launch_bounds__(256) void mel_window_kernel(const float* __restrict__ mel_long, long ld, const int* __restrict__ seek,
+                                                         const int* __restrict__ size, float* __restrict__ out) {
+  const int t = blockIdx.x * 256 + threadIdx.x, m = blockIdx.y, b = blockIdx.z;
+  if (t >= NFRAMES) return;
+  const float v = (t < size[b]) ? mel_long[(long)m * ld + seek[b] + t] : 0.f;
+  out[((long)b * gridDim.y + m) * NFRAMES + t] = v;
+}
+
 }  // namespace
 
 hipError_t launch_logmel(const LogMelArgs& a, hipStream_t s) {
@@ -171,6 +219,21 @@ hipError_t launch_logmel(const LogMelArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(logmel_init_kernel, dim3((a.B + 63) / 64), dim3(64), 0, s, a.gmax, a.B);
   hipLaunchKernelGGL(logmel_power_kernel, dim3(NFRAMES, a.B), dim3(256), 0, s, a);
   hipLaunchKernelGGL(logmel_finalize_kernel, dim3((NFRAMES + 63) / 64, a.B), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_logmel_long(const LogMelLongArgs& a, hipStream_t s) {
+  if (a.n_mels > 256 || a.n_samples < 0 || a.n_frames != (a.n_samples + NSAMP) / HOP || a.ld < a.n_frames) return hipErrorInvalidValue;
+  const long na = (a.n_samples + 200 + HOP - 1) / HOP < a.n_frames ? (a.n_samples + 200 + HOP - 1) / HOP : a.n_frames;
+  hipLaunchKernelGGL(logmel_long_init_kernel, dim3(1), dim3(1), 0, s, a.gmax);
+  if (na > 0) hipLaunchKernelGGL(logmel_long_power_kernel, dim3((unsigned)na), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(logmel_long_finalize_kernel, dim3((unsigned)((a.n_frames + 255) / 256), a.n_mels), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_mel_window(const float* mel_long, long ld, int n_mels, const int* seek, const int* size, int B, float* out, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mel_window_kernel, dim3((NFRAMES + 255) / 256, n_mels, B), dim3(256), 0, s, mel_long, ld, seek, size, out);
   return hipGetLastError();
 }
 

@@ -135,10 +135,11 @@ def decode_plan(tokenizer, options, n_ctx):
 
 
 @torch.no_grad()
-def decode(model, mel, options=DecodingOptions(), pcm=None, n_samples=None, encoded_batch=None):
+def decode(model, mel, options=DecodingOptions(), pcm=None, n_samples=None, encoded_batch=None, want_text=True):
     """whisper.decode. mel: [n_mels, 3000] or [B, n_mels, 3000] f32 cuda tensor (or None with pcm [B, stride] f32 cuda +
     n_samples, the log-mel then runs on the device; or neither with encoded_batch=B: decode the state queued by
-    model.encode_batch). Returns DecodingResult or a list of them."""
+    model.encode_batch). Returns DecodingResult or a list of them. want_text=False (transcribe without a vocabulary file) leaves
+    `text` empty instead of decoding the token ids, which only the BPE vocabulary can do."""
     _check_supported(options)
     single = mel is not None and mel.ndim == 2
     if single:
@@ -163,7 +164,7 @@ def decode(model, mel, options=DecodingOptions(), pcm=None, n_samples=None, enco
     results = []
     for b in range(B):
         toks = [int(t) for t in tokens[b, len(initial):n_tokens[b]]]
-        text = tokenizer.decode(toks).strip()
+        text = tokenizer.decode(toks).strip() if want_text else ""
         results.append(DecodingResult(language=options.language, tokens=toks, text=text,
                                       avg_logprob=float(sum_logprobs[b]) / (len(toks) + 1), no_speech_prob=float(no_speech_probs[b]),
                                       temperature=options.temperature,

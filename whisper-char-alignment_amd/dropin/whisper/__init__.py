@@ -1,6 +1,7 @@
 """`import whisper` stand-in covering exactly what the reference touches (timing.py:7-10, infer_ali.py:18-20,36-41,60,
 dataset.py:4,47-48, README.md:93-108): load_model / decode / DecodingOptions / pad_or_trim / log_mel_spectrogram and the
-`audio`, `model`, `timing`, `tokenizer` sub-modules. Nothing is downloaded: `load_model(name)` reads a LOCAL checkpoint,
+`audio`, `model`, `timing`, `tokenizer` sub-modules, plus upstream's long-form `transcribe` (`whisper.transcribe.transcribe`:
+temperature 0, word times from the character aligner; see the package's transcribe.py). Nothing is downloaded: `load_model(name)` reads a LOCAL checkpoint,
 `download_root/<name>.pt` or $WCA_WEIGHTS_DIR/<name>.pt (openai format)."""
 import contextlib as _contextlib
 import os as _os
@@ -11,6 +12,7 @@ _sys.path.insert(0, _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__)
 from _pkg import pkg as _pkg, sub as _sub  # noqa: E402
 
 _audio, _decoding, _timing, _tok = _sub("audio"), _sub("decoding"), _sub("timing"), _sub("tokenizer")
+_transcribe = _sub("transcribe")
 
 pad_or_trim = _audio.pad_or_trim
 log_mel_spectrogram = _audio.log_mel_spectrogram
@@ -32,7 +34,7 @@ def load_model(name, device="cuda:0", download_root=None, in_memory=False, max_b
 
 audio = _types.ModuleType("whisper.audio")
 for _n in ("SAMPLE_RATE", "N_FFT", "HOP_LENGTH", "CHUNK_LENGTH", "N_SAMPLES", "N_FRAMES", "N_SAMPLES_PER_TOKEN", "FRAMES_PER_SECOND",
-           "TOKENS_PER_SECOND", "pad_or_trim", "log_mel_spectrogram", "mel_filters", "load_audio"):
+           "TOKENS_PER_SECOND", "pad_or_trim", "log_mel_spectrogram", "log_mel_spectrogram_long", "mel_filters", "load_audio"):
     setattr(audio, _n, getattr(_audio, _n))
 model = _types.ModuleType("whisper.model")
 model.disable_sdpa = _contextlib.nullcontext  # the engine always materialises qk for the hooked heads
@@ -44,5 +46,15 @@ tokenizer = _types.ModuleType("whisper.tokenizer")
 tokenizer.get_tokenizer, tokenizer.Tokenizer, tokenizer.LANGUAGES = _tok.get_tokenizer, _tok.Tokenizer, _tok.LANGUAGES
 decoding = _types.ModuleType("whisper.decoding")
 decoding.DecodingOptions, decoding.DecodingResult, decoding.decode = DecodingOptions, DecodingResult, decode
+# like upstream, `whisper.transcribe` is the function (it shadows the sub-module, which stays importable as whisper.transcribe.transcribe)
+def transcribe(model, audio, **kwargs):
+    return _transcribe.transcribe(model, audio, **kwargs)
+
+
+transcribe.__doc__ = _transcribe.transcribe.__doc__
+transcribe.transcribe = transcribe
+_transcribe_module = _types.ModuleType("whisper.transcribe")
+_transcribe_module.transcribe = transcribe
+_sys.modules[_transcribe_module.__name__] = _transcribe_module
 for _m in (audio, model, timing, tokenizer, decoding):
     _sys.modules[_m.__name__] = _m

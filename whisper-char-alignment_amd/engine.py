@@ -315,6 +315,47 @@ class WhisperAMD:
         self._after_call()
         return out[0] if single else out
 
+    def log_mel_long(self, pcm):
+        """whisper.log_mel_spectrogram(pcm, n_mels, padding=N_SAMPLES) of a whole recording (C ABI wca_log_mel_long): pcm f32 [n],
+        any n -> [n_mels, (n + 480000) // 160] f32 on the GPU, one `max - 8` floor over the whole recording. The tensor is the
+        caller's: the engine keeps no buffer of the recording's size."""
+        if pcm.dim() != 1:
+            raise ValueError("log_mel_long takes one recording [n]; got shape %s" % (tuple(pcm.shape),))
+        p = pcm.to(self.device, torch.float32).contiguous()
+        n = p.shape[0]
+        T = (n + N_SAMPLES) // 160
+        out = torch.empty(self.dims.n_mels, T, device=self.device, dtype=torch.float32)
+        self._bind_stream()
+        _lib.check(self._lib.wca_log_mel_long(self._h, _ptr(p) if n else None, n, _ptr(out), T, None))
+        self._after_call()
+        return out
+
+    def mel_window(self, mel_long, seek, size):
+        """pad_or_trim(mel_long[:, seek : seek + size], 3000) (C ABI wca_mel_window). mel_long [n_mels, T] f32 cuda; seek / size ints ->
+        [n_mels, 3000], or equally long lists -> [B, n_mels, 3000]; exact zeros beyond `size`."""
+        single = not isinstance(seek, (list, tuple))
+        seeks, sizes = ([seek], [size]) if single else (list(seek), list(size))
+        if len(seeks) != len(sizes):
+            raise ValueError("seek and size must have the same length")
+        if any(not -2 ** 31 <= int(v) < 2 ** 31 for v in seeks + sizes):
+            raise ValueError("seek / size do not fit the C ABI's int32")
+        if mel_long.dim() != 2 or mel_long.shape[0] != self.dims.n_mels or mel_long.dtype != torch.float32 or mel_long.stride(1) != 1:
+            raise ValueError("mel_long must be an f32 [n_mels, T] tensor with unit frame stride")
+        mel_long = mel_long.to(self.device)
+        out = torch.empty(len(seeks), self.dims.n_mels, N_FRAMES, device=self.device, dtype=torch.float32)
+        self._bind_stream()
+        for b0 in range(0, len(seeks), self.max_batch):
+            b1 = min(len(seeks), b0 + self.max_batch)
+            _lib.check(self._lib.wca_mel_window(self._h, _ptr(mel_long), mel_long.stride(0), mel_long.shape[1], _lib.i32_array(seeks[b0:b1]),
+                                                _lib.i32_array(sizes[b0:b1]), b1 - b0, _ptr(out[b0:b1])))
+        self._after_call()
+        return out[0] if single else out
+
+    def transcribe(self, audio, **kw):
+        """whisper.transcribe(model, audio, ...) at temperature 0 with this project's word aligner (transcribe.transcribe)."""
+        from . import transcribe as _t
+        return _t.transcribe(self, audio, **kw)
+
     def get_attentions(self, mel, tokens, max_frames, medfilt_width=7, qk_scale=1.0, n_tok=None, want_logits=True):
         """mel [B,n_mels,3000] f32, tokens [B,n] int64, max_frames list[int] -> (weights [B,L,H,n,F], logits [B,n,V])."""
         mel = mel.to(self.device, torch.float32).contiguous()

@@ -1,0 +1,345 @@
+#!/usr/bin/env python3
+"""Long-form transcription: `whisper.transcribe(model, audio, ...)` at temperature 0 on the MI355X engine, with word times
+from this project's character aligner instead of upstream's alignment-heads aligner.
+
+Upstream openai-whisper `transcribe.py` is an absent third-party dependency (like `decoding.py`, see decoding.py's
+docstring); its published seek loop is restated here: PARITY UNPINNED against upstream itself. The reference
+repository has no long-form path at all (its entry points stop at 30 s, infer_ali.py:78-81).
+
+What runs where: the log-mel of the WHOLE recording once (wca_log_mel_long: one `max - 8` floor over the recording), the
+window cut pad_or_trim(mel[:, seek:seek+size], 3000) with zeros in the mel domain (wca_mel_window), greedy decode of each
+window with the previous text as the prompt (wca_greedy_decode_ex), and -- with word_timestamps=True -- the fused alignment
+on the encoder state that decode left in the engine (align_batch(pcm=None): no second encoder pass). The loop itself
+(`seek_loop`) is host Python over two callables, so it runs without a GPU against a scripted decoder.
+
+Limits (part of the contract):
+  * temperature is 0.0 (or a tuple holding only 0.0); anything else raises NotImplementedError -- the fallback ladder needs
+    sampling, which decoding._check_supported refuses. Without a ladder compression_ratio_threshold / logprob_threshold
+    cannot trigger a re-decode: the temperature-0 result is accepted, as upstream accepts the last rung of its ladder.
+    language=None (detection) is refused as in decode.
+  * one recording per call, window after window (window k+1 starts where window k ended). Several recordings in lock-step
+    would need per-row prompts in wca_greedy_decode_ex, which takes one initial-token row for the whole batch: not built.
+  * clip_timestamps, hallucination_silence_threshold, prepend_punctuations / append_punctuations are not built (they
+    belong to upstream's own word aligner).
+
+Decisions the upstream text leaves open:
+  * a window that ended inside speech (its tokens do not end in a single timestamp; seek advances to the last consecutive
+    timestamp pair) has its tail decoded again by the next window, so only the text of the segments that were KEPT is
+    aligned, against max_frames = last_timestamp_pos encoder frames: no word is reported twice. Every other window aligns
+    against max_frames = size // 2.
+  * a window whose framed text [*sot_sequence, no_timestamps, *text, eot] is longer than 448 tokens, or has at most one word,
+    or cannot be tokenised, or has max_frames < 1, gets segment times only and words = [] (the reference's skip,
+    infer_ali.py:79-81, timing.py:106-107); result["windows_without_words"] counts them.
+  * a word belongs to the segment whose [start, end) contains its start; if none does, to the last segment of its window
+    that starts at or before it (else the window's first segment).
+  * a window that ended inside speech with last_timestamp_pos == 0 would not advance at all (upstream's loop can spin there at a
+    fixed temperature), and in a short last window a timestamp beyond the window's `size` frames would carry seek past the end of the
+    recording: both advance by the window size instead, so seek strictly increases and ends at content_frames.
+  * without a vocabulary (vocab_path=None) token ids cannot be turned into text: "text" fields are "" and the "segment without text
+    is cleared" rule is not applied; tokens and times are complete. word_timestamps=True needs the vocabulary.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+if __package__ in (None, ""):
+    import importlib
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    _pkg = importlib.import_module("whisper-char-alignment_amd")
+    __package__ = _pkg.__name__
+
+from .audio import HOP_LENGTH, N_FRAMES, SAMPLE_RATE  # noqa: E402
+
+INPUT_STRIDE = 2                                         # mel frames per encoder frame (N_FRAMES // n_audio_ctx)
+TIME_PRECISION = INPUT_STRIDE * HOP_LENGTH / SAMPLE_RATE  # 0.02 s per timestamp token step / encoder frame
+FRAME_SECONDS = HOP_LENGTH / SAMPLE_RATE                  # 0.01 s per mel frame
+MAX_LENGTH = 448                                          # infer_ali.py:26
+
+
+def check_supported(temperature, language):
+    """What this transcribe refuses instead of silently differing from upstream."""
+    temps = tuple(temperature) if isinstance(temperature, (tuple, list)) else (temperature,)
+    if len(temps) != 1 or float(temps[0]) != 0.0:
+        raise NotImplementedError("transcribe runs at temperature 0.0 only: the fallback ladder %r needs sampling, which the engine's "
+                                  "greedy decode does not do (decoding._check_supported)" % (temperature,))
+    if language is None:
+        raise NotImplementedError("language detection is not built: pass language=... (as DecodingOptions(language=...) in decode)")
+    return 0.0
+
+
+def split_window(tokens, timestamp_begin, eot, seek, size, result, decode_text):
+    """One window of upstream's loop: decoded tokens -> (segments, frames to advance, max_frames for the aligner).
+    Segments split at consecutive timestamp pairs; a window that ends in a single timestamp (or has no pair) advances by `size`, one
+    that ended inside speech advances to its last pair. decode_text(tokens) -> str, or None when there is no vocabulary."""
+    tokens = [int(t) for t in tokens]
+    time_offset = seek * FRAME_SECONDS
+    is_ts = [t >= timestamp_begin for t in tokens]
+
+    def new_segment(start, end, toks):
+        text = decode_text([t for t in toks if t < eot])
+        return {"seek": seek, "start": start, "end": end, "text": text if text is not None else "", "tokens": list(toks),
+                "temperature": result.temperature, "avg_logprob": result.avg_logprob, "compression_ratio": result.compression_ratio,
+                "no_speech_prob": result.no_speech_prob, "_has_text": None if text is None else bool(text.strip())}
+
+    segments = []
+    single_timestamp_ending = is_ts[-2:] == [False, True]
+    consecutive = [i + 1 for i in range(len(tokens) - 1) if is_ts[i] and is_ts[i + 1]]
+    max_frames = size // INPUT_STRIDE
+    if consecutive:
+        slices = list(consecutive)
+        if single_timestamp_ending:
+            slices.append(len(tokens))
+        last_slice = 0
+        for current_slice in slices:
+            sliced = tokens[last_slice:current_slice]
+            segments.append(new_segment(time_offset + (sliced[0] - timestamp_begin) * TIME_PRECISION,
+                                        time_offset + (sliced[-1] - timestamp_begin) * TIME_PRECISION, sliced))
+            last_slice = current_slice
+        advance = size
+        if not single_timestamp_ending:
+            last_timestamp_pos = tokens[last_slice - 1] - timestamp_begin
+            if 0 < last_timestamp_pos * INPUT_STRIDE <= size:   # (see the module docstring for the two cases left out)
+                advance = last_timestamp_pos * INPUT_STRIDE
+                max_frames = last_timestamp_pos
+    else:
+        duration = size * FRAME_SECONDS
+        timestamps = [t for t in tokens if t >= timestamp_begin]
+        if timestamps and timestamps[-1] != timestamp_begin:
+            duration = (timestamps[-1] - timestamp_begin) * TIME_PRECISION
+        segments.append(new_segment(time_offset, time_offset + duration, tokens))
+        advance = size
+    for seg in segments:   # an instantaneous segment, or one without text, is cleared
+        has_text = seg.pop("_has_text")
+        if seg["start"] == seg["end"] or has_text is False:
+            seg["text"], seg["tokens"] = "", []
+        seg["words"] = []
+    return segments, advance, max_frames
+
+
+def seek_loop(n_frames, cut_window, decode_window, tokenizer, *, initial_prompt_tokens=(), condition_on_previous_text=True,
+              no_speech_threshold=0.6, logprob_threshold=-1.0, align_window=None, decode_text=None):
+    """whisper.transcribe's loop over a log-mel of `n_frames` frames (the recording's frames plus 3000 of padding).
+    cut_window(seek, size) -> mel window; decode_window(mel_window, prompt_tokens) -> DecodingResult (tokens, avg_logprob,
+    no_speech_prob, ...); align_window(seek, size, max_frames, segments) -> bool fills the kept segments' "words" (False: the window
+    got none). Returns {"segments", "tokens" (initial prompt included), "windows", "windows_without_words"}."""
+    if decode_text is None:
+        def decode_text(toks):
+            return tokenizer.decode(toks) if getattr(tokenizer, "has_vocab", True) else None
+    content_frames = n_frames - N_FRAMES
+    all_tokens = [int(t) for t in initial_prompt_tokens]
+    all_segments, windows = [], []
+    prompt_reset_since = 0
+    without_words = 0
+    seek = 0
+    while seek < content_frames:
+        size = min(N_FRAMES, content_frames - seek)
+        result = decode_window(cut_window(seek, size), all_tokens[prompt_reset_since:])
+        window = {"seek": seek, "size": size, "advance": size, "skipped": False, "max_frames": None, "aligned": False}
+        windows.append(window)
+        if no_speech_threshold is not None:
+            should_skip = result.no_speech_prob > no_speech_threshold
+            if logprob_threshold is not None and result.avg_logprob > logprob_threshold:
+                should_skip = False
+            if should_skip:
+                window["skipped"] = True
+                seek += size
+                continue
+        segments, advance, max_frames = split_window(result.tokens, tokenizer.timestamp_begin, tokenizer.eot, seek, size, result, decode_text)
+        window["max_frames"], window["advance"] = max_frames, advance
+        if align_window is not None:
+            window["aligned"] = bool(align_window(seek, size, max_frames, segments))
+            without_words += 0 if window["aligned"] else 1
+        seek += advance
+        all_segments.extend({"id": i, **seg} for i, seg in enumerate(segments, start=len(all_segments)))
+        all_tokens.extend(t for seg in segments for t in seg["tokens"])
+        if not condition_on_previous_text:
+            prompt_reset_since = len(all_tokens)
+    return {"segments": all_segments, "tokens": all_tokens, "windows": windows, "windows_without_words": without_words}
+
+
+def attach_words(segments, words):
+    """words: [{"word", "start", "end", "probability"}] of one window, in time order -> into the segment that contains their start."""
+    live = [s for s in segments if s["tokens"]] or list(segments)
+    for w in words:
+        home = next((s for s in live if s["start"] <= w["start"] < s["end"]), None)
+        if home is None:
+            before = [s for s in live if s["start"] <= w["start"]]
+            home = before[-1] if before else live[0]
+        home["words"].append(w)
+
+
+def make_aligner(model, tokenizer, *, aligned_unit_type="char", aggr="topk", topk=10, medfilt_width=3, w_colnorm=1.0, w_rownorm=1.0,
+                 w_coverage=0.0, word_confidence=False):
+    """align_window for seek_loop: the paper's aligner on the encoder state the window's decode left in the engine."""
+    import torch
+    from .retokenize import encode, remove_punctuation
+    from .timing import word_probabilities, words_from_jump_frames
+    sot_len = len(tokenizer.sot_sequence)
+    if aggr == "topk":
+        topk = min(int(topk), model.dims.n_text_layer * model.dims.n_text_head)   # filter_attention keeps at most every head (timing.py:13-43)
+    opts = model.make_opts(aggregation=aggr, topk=topk, w_colnorm=w_colnorm, w_rownorm=w_rownorm, w_coverage=w_coverage, sot_len=sot_len,
+                           medfilt_width=medfilt_width, qk_scale=1.0)
+    n_audio_ctx = model.dims.n_audio_ctx
+
+    def align_window(seek, size, max_frames, segments):
+        text = tokenizer.decode([t for seg in segments for t in seg["tokens"] if t < tokenizer.eot])
+        try:
+            text_tokens = encode(remove_punctuation(text), tokenizer, aligned_unit_type)
+        except Exception:   # a character the byte-level dry-run tokenizer cannot encode
+            return False
+        tokens = [*tokenizer.sot_sequence, tokenizer.no_timestamps, *text_tokens, tokenizer.eot]
+        if not text_tokens or len(tokens) > MAX_LENGTH or not 1 <= max_frames <= n_audio_ctx:
+            return False
+        toks_dev = torch.tensor([tokens], dtype=torch.int64, device=model.device)
+        res = model.align_batch(None, None, toks_dev, [len(tokens)], [max_frames], opts,
+                                token_logprobs_vocab_end=tokenizer.eot if word_confidence else None)
+        words, starts, ends = words_from_jump_frames(res[0][0], text_tokens, tokenizer, aligned_unit_type)
+        if not len(starts):
+            return False
+        probs = word_probabilities(res[2][0][:len(text_tokens)], text_tokens, tokenizer, aligned_unit_type) if word_confidence else None
+        offset = seek * FRAME_SECONDS
+        attach_words(segments, [{"word": words[i], "start": offset + float(starts[i]), "end": offset + float(ends[i]),
+                                 "probability": probs[i] if probs is not None else None} for i in range(len(starts))])
+        return True
+
+    return align_window
+
+
+def _as_pcm(audio):
+    import torch
+    if isinstance(audio, (str, os.PathLike)):
+        from .audio import load_audio
+        pcm, sr = load_audio(audio)
+        if sr != SAMPLE_RATE:
+            raise ValueError("%s is sampled at %d Hz: transcribe takes %d Hz audio (there is no resampler here)" % (audio, sr, SAMPLE_RATE))
+        if pcm.ndim > 1:
+            pcm = pcm.mean(axis=0)
+        audio = pcm
+    if not isinstance(audio, torch.Tensor):
+        audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
+    if audio.dim() != 1:
+        raise ValueError("audio must be one mono recording [n]; got shape %s" % (tuple(audio.shape),))
+    return audio.to(torch.float32)
+
+
+def transcribe(model, audio, *, language, initial_prompt=None, condition_on_previous_text=True, no_speech_threshold=0.6,
+               logprob_threshold=-1.0, word_timestamps=False, word_confidence=False, aligned_unit_type="char", aggr="topk", topk=10,
+               medfilt_width=3, vocab_path=None, temperature=0.0, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0, decode_window=None,
+               **decode_options):
+    """whisper.transcribe(model, audio, ...) -> {"text", "segments": [{"id", "seek", "start", "end", "text", "tokens", "temperature",
+    "avg_logprob", "compression_ratio", "no_speech_prob", "words": [{"word", "start", "end", "probability"}]}], "language"} plus
+    "windows" (every decoded window: seek, size, advance, skipped, max_frames, aligned) and "windows_without_words".
+    audio: a path (audio.load_audio), a numpy array or a tensor of 16 kHz mono samples, any length. word_timestamps=True: word times
+    from the character aligner per window (module docstring); word_confidence=True adds each word's probability (None otherwise).
+    decode_window(mel_window, prompt_tokens) -> DecodingResult replaces the engine's greedy decode (tests); decode_options go to
+    DecodingOptions. Limits: module docstring."""
+    from . import decoding
+    from .tokenizer import get_tokenizer
+    check_supported(temperature, language)
+    if word_confidence and not word_timestamps:
+        raise ValueError("word_confidence is a property of the aligned words: it needs word_timestamps=True")
+    if word_timestamps and vocab_path is None:
+        raise ValueError("word_timestamps aligns the decoded TEXT: pass vocab_path=<local *.tiktoken file>")
+    tokenizer = get_tokenizer(model.is_multilingual, language=language, task=decode_options.get("task", "transcribe"), vocab_path=vocab_path)
+    prompt_tokens = []
+    if initial_prompt is not None:
+        prompt_tokens = decoding._text_tokens(tokenizer, initial_prompt, decoding.DecodingOptions(vocab_path=vocab_path), "initial_prompt")
+    mel_long = model.log_mel_long(_as_pcm(audio))
+
+    if decode_window is None:
+        def decode_window(mel_window, prompt):
+            options = decoding.DecodingOptions(language=language, temperature=0.0, prompt=list(prompt) or None, vocab_path=vocab_path,
+                                               **decode_options)
+            return decoding.decode(model, mel_window, options, want_text=vocab_path is not None)
+
+    align = None
+    if word_timestamps:
+        align = make_aligner(model, tokenizer, aligned_unit_type=aligned_unit_type, aggr=aggr, topk=topk, medfilt_width=medfilt_width,
+                             w_colnorm=w_colnorm, w_rownorm=w_rownorm, w_coverage=w_coverage, word_confidence=word_confidence)
+    out = seek_loop(mel_long.shape[1], lambda seek, size: model.mel_window(mel_long, seek, size), decode_window, tokenizer,
+                    initial_prompt_tokens=prompt_tokens, condition_on_previous_text=condition_on_previous_text,
+                    no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold, align_window=align,
+                    decode_text=tokenizer.decode if vocab_path is not None else (lambda toks: None))
+    text = tokenizer.decode(out["tokens"][len(prompt_tokens):]) if vocab_path is not None else ""
+    return {"text": text, "segments": out["segments"], "language": language, "windows": out["windows"],
+            "windows_without_words": out["windows_without_words"]}
+
+
+# ------------------------------------------------------------------------------------------------ command line
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="Long-form transcription with character-aligned word times (one JSON per recording)")
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("--audio", type=str, help="one 16 kHz recording (WAV / SPHERE / FLAC)")
+    src.add_argument("--scp", type=str, help="list of recordings: `<id> <path>` or `<path>` per line")
+    p.add_argument("--output_dir", type=str, required=True)
+    p.add_argument("--model", type=str, default="medium")
+    p.add_argument("--weights", type=str, default=None, help="local openai-whisper checkpoint (.pt)")
+    p.add_argument("--random_init", action="store_true", help="seeded random weights (dry run without a checkpoint)")
+    p.add_argument("--vocab", type=str, default=None, help="local tiktoken vocabulary file (text output, word times)")
+    p.add_argument("--language", type=str, default="en")
+    p.add_argument("--initial_prompt", type=str, default=None)
+    p.add_argument("--no_condition_on_previous_text", action="store_true")
+    p.add_argument("--word_timestamps", action="store_true")
+    p.add_argument("--word_confidence", action="store_true")
+    p.add_argument("--medfilt_width", type=int, default=3)
+    p.add_argument("--aggr", type=str, default="topk", choices=["mean", "topk"])
+    p.add_argument("--topk", type=int, default=10)
+    p.add_argument("--aligned_unit_type", type=str, default="char", choices=["subword", "char"])
+    p.add_argument("--w_colnorm", type=float, default=1.0)
+    p.add_argument("--w_rownorm", type=float, default=1.0)
+    p.add_argument("--w_coverage", type=float, default=0.0)
+    p.add_argument("--forward_precision", type=str, default="reference", choices=["reference", "split", "f16"])
+    return p.parse_args(argv)
+
+
+def _recordings(args):
+    if args.audio:
+        return [(os.path.splitext(os.path.basename(args.audio))[0], args.audio)]
+    out = []
+    with open(args.scp) as f:
+        for line in f:
+            parts = line.split()
+            if parts:
+                out.append((parts[0] if len(parts) > 1 else os.path.splitext(os.path.basename(parts[0]))[0], parts[-1]))
+    return out
+
+
+def load_model(args, device="cuda:0"):
+    from .engine import WhisperAMD, dims_for
+    if args.weights:
+        return WhisperAMD.from_checkpoint(args.weights, device=device, max_batch=1, name=args.model, precision=args.forward_precision)
+    if args.random_init:
+        from .synthetic import random_state_dict
+        dims = dims_for(args.model)
+        return WhisperAMD(dims, device=device, max_batch=1, precision=args.forward_precision).load_state_dict(random_state_dict(dims, seed=0))
+    raise SystemExit("no weights: pass --weights /local/path/%s.pt (openai-whisper checkpoint; nothing is downloaded by name) "
+                     "or --random_init for a dry run" % args.model)
+
+
+def main(args, model=None):
+    """Writes <output_dir>/<id>.json per recording (transcribe()'s result plus "audio"); returns the paths."""
+    if args.word_timestamps and args.vocab is None:
+        raise SystemExit("--word_timestamps aligns the decoded text: pass --vocab <local multilingual.tiktoken>")
+    if model is None:
+        model = load_model(args)
+    os.makedirs(args.output_dir, exist_ok=True)
+    paths = []
+    for rec_id, path in _recordings(args):
+        result = transcribe(model, path, language=args.language, initial_prompt=args.initial_prompt,
+                            condition_on_previous_text=not args.no_condition_on_previous_text, word_timestamps=args.word_timestamps,
+                            word_confidence=args.word_confidence, aligned_unit_type=args.aligned_unit_type, aggr=args.aggr, topk=args.topk,
+                            medfilt_width=args.medfilt_width, vocab_path=args.vocab, w_colnorm=args.w_colnorm, w_rownorm=args.w_rownorm,
+                            w_coverage=args.w_coverage)
+        out = os.path.join(args.output_dir, rec_id + ".json")
+        with open(out, "w") as f:
+            json.dump({"audio": path, **result}, f)
+        paths.append(out)
+        print("%s: %d segments, %d windows -> %s" % (rec_id, len(result["segments"]), len(result["windows"]), out))
+    return paths
+
+
+if __name__ == "__main__":
+    main(parse_args())
