@@ -30,6 +30,9 @@
  *                          decoder, SuppressBlank / SuppressTokens / ApplyTimestampRules, GreedyDecoder)
  *   wca_greedy_decode_ex   the same with DecodingOptions(prompt=..., prefix=...) (transcribe(initial_prompt=...)): any
  *                          initial token row, <|sot|> at sot_index, and the batched prefill of upstream's first forward
+ *   wca_greedy_decode_rows the same for a batch whose rows carry initial tokens (prompts) of their own, of their own lengths, and
+ *                          their own sample budgets: the rows sit at different decoder positions (transcribe_batch: several
+ *                          recordings in lock-step, each conditioned on its own previous text)
  *   wca_align_batch        infer_ali.py:93-101 + dataset.py:47-48: the whole per-utterance pipeline
  *                          (log-mel -> forward+capture -> medfilt/softmax -> scores/top-k ->
  *                          aggregate -> DTW) for a micro-batch of utterances, results = the frame
@@ -100,7 +103,7 @@ typedef struct {
 } wca_align_opts;
 
 const char* wca_last_error(void);
-int wca_version(void);   /* 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: wca_greedy_decode_ex (prompt / prefix: sot_index, batched prefill); 7: exactly two precision modes */
+int wca_version(void);   /* 11: wca_greedy_decode_rows (per-row prompts and sample budgets); 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: wca_greedy_decode_ex (prompt / prefix: sot_index, batched prefill); 7: exactly two precision modes */
 
 /* ---- engine lifetime ------------------------------------------------------------------------ */
 /* A new engine is in the CONTRACT precision mode (WCA_PRECISION_REFERENCE: every stage on (hi, lo) operand pairs = the fp32 forward of
@@ -304,6 +307,25 @@ int wca_greedy_decode_ex(wca_engine* e, const float* mel_dev, const float* pcm_d
                          const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host, const wca_decode_opts_ex* opts,
                          int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
                          float* no_speech_prob_host);
+/* Greedy decode with per-row initial tokens. initial_tokens_host [batch][n_initial_max] (n_initial_max = max n_initial_host[b]; row b's
+ * first n_initial_host[b] entries count, the rest is ignored), sot_index_host [batch] (position of <|startoftranscript|> in row b: 0
+ * without a prompt, 1 + prompt length with one), sample_len_host [batch] (row b samples at most that many tokens; opts->sample_len is
+ * ignored). Per row the bounds of wca_greedy_decode_ex: 1 <= n_initial[b] <= n_text_ctx, sample_len[b] >= 1,
+ * n_initial[b] + sample_len[b] <= n_text_ctx + 1 (WCA_ERR_TOO_LONG), 0 <= sot_index[b] < n_initial[b], every token in the vocabulary
+ * (WCA_ERR_INVALID). T_max = max_b (n_initial[b] + sample_len[b]); tokens_out_host [batch][T_max]: row b left-aligned, its initial
+ * tokens, then its sampled tokens, eot from its first eot / its budget on; n_tokens_host[b] = index of row b's first sampled eot, at
+ * most n_initial[b] + sample_len[b]. SuppressBlank and the first-timestamp rules fire at row b's own first sampled position
+ * n_initial[b]; no_speech_prob_host[b] is read at sot_index[b]. The initial tokens always go through one batched prefill (rows padded
+ * to n_initial_max with eot; a valid position never attends to a pad). A row's tokens do not depend on the other rows' lengths except
+ * through the GEMM path the row COUNT selects (fp32 summation order, as between prefill = 0 and 1). The encoder-state queue behaves as
+ * for wca_greedy_decode_ex: the state stays for a following wca_align_batch_enqueue(pcm_dev = NULL). wca_last_decode_positions
+ * reports n_initial_max and the number of single-position steps. */
+int wca_greedy_decode_rows(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride,
+                           const int32_t* n_samples_host, int batch, const int32_t* initial_tokens_host,
+                           const int32_t* n_initial_host, const int32_t* sot_index_host, const int32_t* sample_len_host,
+                           const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host, const wca_decode_opts* opts,
+                           int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
+                           float* no_speech_prob_host);
 /* positions per row that the last wca_greedy_decode* fed through the batched prefill (n_initial, or 0) and one position at a
  * time (decode steps, the sampling steps after the first included) */
 int wca_last_decode_positions(wca_engine* e, int32_t* prefill_positions, int32_t* step_positions);
@@ -424,6 +446,18 @@ int wca_test_attention_split(wca_engine* e, const void* q2_dev, const void* k2_d
 int wca_test_decode_select(wca_engine* e, const float* logits_dev, int batch, int n_vocab, int32_t* tokens_dev, int T_max,
                            int cur_len, int n_initial, const uint8_t* suppress_mask_dev, const uint8_t* blank_mask_dev,
                            const wca_decode_opts* opts, float* sum_logprob_dev, int32_t* n_done_dev);
+/* the per-row form of that step (wca_greedy_decode_rows): cur_len_dev / n_initial_dev / cap_dev [batch] int32 device arrays; row b holds
+ * cur_len[b] tokens of which n_initial[b] are initial, and is a finished row (eot, nothing added to sum_logprob) once
+ * cur_len[b] - n_initial[b] >= cap[b]; n_done_dev [n_done_len]: entry n_done_idx counts the rows whose new token is eot */
+int wca_test_decode_select_rows(wca_engine* e, const float* logits_dev, int batch, int n_vocab, int32_t* tokens_dev, int T_max,
+                                const int32_t* cur_len_dev, const int32_t* n_initial_dev, const int32_t* cap_dev, int n_done_idx,
+                                int n_done_len, const uint8_t* suppress_mask_dev, const uint8_t* blank_mask_dev,
+                                const wca_decode_opts* opts, float* sum_logprob_dev, int32_t* n_done_dev);
+/* wca_test_attention (no capture) with per-row key counts: q [B][nq][H*64], k / v [B][nk][H*64] f16, batch row b attends to keys
+ * [0, nk_rows_dev[b]) (int32 device, clamped to [1, nk]). Only nq = 1 without a mask exists (the decode step's one-query kernel):
+ * anything else is WCA_ERR_INVALID. Row b equals a B = 1 wca_test_attention call with nk = nk_rows[b], bit for bit. */
+int wca_test_attention_rows(wca_engine* e, const void* q_dev, const void* k_dev, const void* v_dev, void* o_dev, int B, int H, int nq,
+                            int nk, const int32_t* nk_rows_dev, int causal);
 int wca_test_layernorm(wca_engine* e, const float* x_dev, const float* g_dev, const float* b_dev, void* out_f16_dev,
                        int rows, int d);
 /* split-mode LayerNorm: out2 f16 [rows][2d], hi = f16(y) at column c, lo = f16(y - hi) at column d + c */

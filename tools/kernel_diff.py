@@ -17,7 +17,10 @@ KEYS = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment
 # template parameters dropped from the product kernels: the s_memtime stamp switch and the unadopted VALU row-sum attention form
 RENAME = [(r"(gemm256p_f16_kernel<[^,]+, [^,]+, [^,]+), 0, ", r"\1, "),
           (r"attn_kernel<(true|false), (true|false), false>", r"attn_kernel<\1, \2>"),
-          (r"attn32_kernel<false, false>", "attn32_kernel")]
+          (r"attn32_kernel<false, false>", "attn32_kernel"),
+          # kernels that gained a per-row instance (wca_greedy_decode_rows): the uniform launches take the <..., false> ones
+          (r"(gemm_rows_f16_kernel<[^,]+, [^,]+, [^,>]+)>", r"\1, false>"),
+          (r"\b(attn_decode_kernel|decode_select_kernel)\(", r"\1<false>(")]
 SLOAD = re.compile(r"^(s_load_\w+|s_buffer_load_\w+)\s+(.*),\s*(0x[0-9a-fA-F]+|\d+)$")
 REG = re.compile(r"\b([vsa])(\d+|\[\d+:\d+\])")
 
@@ -53,7 +56,7 @@ def kernels(obj, tmp):
             continue
         ins = re.sub(r"\s*//.*$", "", line).strip()
         ins = re.sub(r"\s*<[^>]*>$", "", ins)   # branch target labels carry absolute addresses
-        if cur and ins:
+        if cur and ins and ins != "...":   # (a run of zero padding after s_endpgm: its presence depends on where the next kernel starts)
             code[cur].append(re.sub(r"\s+", " ", ins))
     names = demangle(sorted(res))
     return {names[k]: (res[k], code.get(k, [])) for k in res}

@@ -87,7 +87,11 @@ SIGNATURES = {
     "wca_encode_batch": (_i, [_vp, _vp, _vp, _i64, _pi32, _i]),
     "wca_greedy_decode": (_i, [_vp, _vp, _vp, _i64, _pi32, _i, _pi32, _i, _vp, _vp, C.POINTER(DecodeOpts), _pi32, _pi32, _pf, _pf]),
     "wca_greedy_decode_ex": (_i, [_vp, _vp, _vp, _i64, _pi32, _i, _pi32, _i, _vp, _vp, C.POINTER(DecodeOptsEx), _pi32, _pi32, _pf, _pf]),
+    "wca_greedy_decode_rows": (_i, [_vp, _vp, _vp, _i64, _pi32, _i, _pi32, _pi32, _pi32, _pi32, _vp, _vp, C.POINTER(DecodeOpts), _pi32, _pi32, _pf,
+                                    _pf]),
     "wca_last_decode_positions": (_i, [_vp, _pi32, _pi32]),
+    "wca_test_decode_select_rows": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(DecodeOpts), _vp, _vp]),
+    "wca_test_attention_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i]),
     "wca_test_decode_select": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, C.POINTER(DecodeOpts), _vp, _vp]),
     "wca_test_gemm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "wca_test_gemm_ln": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),

@@ -679,6 +679,10 @@ __global__ __launch_bounds__(256) void attn32_kernel(AttnArgs a) {
 // head); its four waves take a quarter of the keys each; inside a wave eight lanes share a key (8 dims of 16 bytes
 // per lane), so one wave instruction reads 8 key rows, and each 8-lane group keeps its own online-softmax state
 // (m, l, o[8 dims]). Groups and waves are merged at the end (log-sum-exp combine through shuffles, then LDS).
+// ROWS: batch row b has nk_rows[b] keys (wca_greedy_decode_rows: the rows of a step sit at different positions); everything that
+// depends on the key count (the waves' key ranges, the dead-key clamp) is derived from the row's own count, so a row's result is that
+// of a uniform launch with nk = nk_rows[b]. The uniform launches take the ROWS = false instance.
+template <bool ROWS>
 __global__ __launch_bounds__(256) void attn_decode_kernel(AttnArgs a) {
   __shared__ float part[4][66];  // per wave: m, l, o[64]
   const int tid = threadIdx.x;
@@ -695,9 +699,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnArgs a) {
   for (int j = 0; j < 8; ++j) q[j] = (float)qh[j] * c_log2;  // scores directly in the log2 domain
   const half_t* Kb = a.K + (long)b * a.k_bs + h * 64 + c * 8;
   const half_t* Vb = a.V + (long)b * a.v_bs + h * 64 + c * 8;
-  const int per_wave = ((a.nk + 3) / 4 + 7) & ~7;  // keys per wave, a multiple of the 8 keys of one step
+  const int nk = ROWS ? min(max(a.nk_rows[b], 1), a.nk) : a.nk;  // (a.nk: the rows the K / V planes hold)
+  const int per_wave = ((nk + 3) / 4 + 7) & ~7;  // keys per wave, a multiple of the 8 keys of one step
   const int k_lo = wave * per_wave;
-  const int k_hi = (k_lo + per_wave < a.nk) ? k_lo + per_wave : a.nk;
+  const int k_hi = (k_lo + per_wave < nk) ? k_lo + per_wave : nk;
   float m = -INFINITY, l = 0.f, o[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) o[j] = 0.f;
@@ -709,7 +714,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnArgs a) {
     for (int u = 0; u < U; ++u) {
       const int key = k0 + u * 8 + grp;
       live[u] = key < k_hi;
-      const int kc = live[u] ? key : a.nk - 1;
+      const int kc = live[u] ? key : nk - 1;
       kf[u] = *reinterpret_cast<const half8*>(Kb + (long)kc * a.k_rs);
       vf[u] = *reinterpret_cast<const half8*>(Vb + (long)kc * a.v_rs);
     }
@@ -782,6 +787,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnArgs a) {
 }  // namespace
 
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
+  // per-row key counts: the one-query kernel of a decode step only
+  if (a.nk_rows != nullptr && (a.split || a.nq != 1 || a.causal || (a.cap != nullptr && a.cap_cols > 0))) return hipErrorInvalidValue;
   if (a.split) return launch_attention_split(a, s);  // reference-precision mode: hi/lo operand pairs, three MFMA passes
   if (a.nq <= 0 || a.B <= 0) return hipSuccess;
   if (a.nk <= 0) return hipErrorInvalidValue;
@@ -789,7 +796,8 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
   if (a.cap != nullptr && ((a.cap_ld % 4) != 0 || a.cap_ld < ((a.cap_cols + 3) & ~3))) return hipErrorInvalidValue;
   const bool cap = a.cap != nullptr && a.cap_cols > 0;
   if (a.nq == 1 && !cap && (!a.causal || a.nk == 1)) {  // greedy-decode steps: the KV cache holds exactly the causal prefix
-    hipLaunchKernelGGL(attn_decode_kernel, dim3(a.H * a.B), dim3(256), 0, s, a);
+    if (a.nk_rows != nullptr) hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(a.H * a.B), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(attn_decode_kernel<false>, dim3(a.H * a.B), dim3(256), 0, s, a);
     return hipGetLastError();
   }
   dim3 grid(((a.nq + 127) / 128) * a.H * a.B), block(256);

@@ -42,6 +42,35 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const half_t* __restrict
   }
 }
 
+// The two kernels above with row b at its own position t_rows[b] (wca_greedy_decode_rows: the rows of a batch sit at different decoder
+// positions); the position is clamped to the row's T_max slots.
+__global__ __launch_bounds__(256) void embed_step_rows_kernel(const int* __restrict__ tokens, int T_max, const int* __restrict__ t_rows,
+                                                              const half_t* __restrict__ tok_emb, const float* __restrict__ pos_emb,
+                                                              float* __restrict__ x, int d, int n_vocab) {
+  const int b = blockIdx.x;
+  const int t = min(max(t_rows[b], 0), T_max - 1);
+  long tok = tokens[(long)b * T_max + t];
+  tok = (tok < 0 || tok >= n_vocab) ? 0 : tok;
+  const half_t* e = tok_emb + tok * d;
+  const float* p = pos_emb + (long)t * d;
+  float* o = x + (long)b * d;
+  for (int c = threadIdx.x; c < d; c += blockDim.x) o[c] = (float)e[c] + p[c];
+}
+
+__global__ __launch_bounds__(256) void kv_append_rows_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ kc, half_t* __restrict__ vc,
+                                                             int T_max, const int* __restrict__ t_rows, int d) {
+  const int b = blockIdx.x;
+  const int t = min(max(t_rows[b], 0), T_max - 1);
+  const half8* k = reinterpret_cast<const half8*>(qkv + (long)b * 3 * d + d);
+  const half8* v = reinterpret_cast<const half8*>(qkv + (long)b * 3 * d + 2 * d);
+  half8* ko = reinterpret_cast<half8*>(kc + ((long)b * T_max + t) * d);
+  half8* vo = reinterpret_cast<half8*>(vc + ((long)b * T_max + t) * d);
+  for (int c = threadIdx.x; c < d / 8; c += blockDim.x) {
+    ko[c] = k[c];
+    vo[c] = v[c];
+  }
+}
+
 // x[b * n + i] = token_embedding[tokens[b][i]] + positional_embedding[i] for i < n (the prefill's rows; n <= n_text_ctx)
 __global__ __launch_bounds__(256) void embed_prefix_kernel(const int* __restrict__ tokens, int T_max, int n, const half_t* __restrict__ tok_emb,
                                                            const float* __restrict__ pos_emb, float* __restrict__ x, int d, int n_vocab) {
@@ -78,6 +107,16 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
   for (int c = threadIdx.x; c < d; c += blockDim.x) o[c] = src[c];
 }
 
+// the same with the positions per batch row: p0_rows[b] (the row's last initial position), p1_rows[b] (its <|sot|>; nullable)
+__global__ __launch_bounds__(256) void gather_rows_per_row_kernel(const float* __restrict__ x, float* __restrict__ out, int n,
+                                                                  const int* __restrict__ p0_rows, const int* __restrict__ p1_rows, int d) {
+  const int b = blockIdx.x, j = blockIdx.y, B = gridDim.x;
+  const int p = min(max(j == 0 ? p0_rows[b] : p1_rows[b], 0), n - 1);
+  const float* src = x + ((long)b * n + p) * d;
+  float* o = out + ((long)j * B + b) * d;
+  for (int c = threadIdx.x; c < d; c += blockDim.x) o[c] = src[c];
+}
+
 __device__ __forceinline__ float block_max(float v, float* red) {
   v = wave_max(v);
   const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -100,6 +139,10 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 }
 
 // One workgroup per batch row. cur_len = number of tokens the row holds (the new token is written at index cur_len).
+// ROWS: cur_len, n_initial and the sample cap are per row (cur_len_rows / n_initial_rows / cap_rows); a row that has sampled its
+// cap (or whose lengths are not a valid state) is a finished row: EOT where the row still has room, nothing added to sum_logprob,
+// counted in n_done, which is indexed by the step (n_done_idx) because the rows' cur_len differ.
+template <bool ROWS>
 __global__ __launch_bounds__(1024) void decode_select_kernel(DecodeSelectArgs a) {
   __shared__ float red[16];
   __shared__ int red_i[16];
@@ -109,12 +152,24 @@ __global__ __launch_bounds__(1024) void decode_select_kernel(DecodeSelectArgs a)
   const float* lg = a.logits + (long)b * a.ld;
   int* tok = a.tokens + (long)b * a.T_max;
   const int V = a.n_vocab;
-  const bool first = (a.cur_len == a.n_initial);
+  const int cur_len = ROWS ? a.cur_len_rows[b] : a.cur_len;
+  const int n_initial = ROWS ? a.n_initial_rows[b] : a.n_initial;
+  if (ROWS) {
+    const bool valid = n_initial >= 1 && cur_len >= n_initial && cur_len < a.T_max;
+    if (!valid || cur_len - n_initial >= a.cap_rows[b]) {  // (uniform over the workgroup)
+      if (tid == 0) {
+        if (cur_len >= 0 && cur_len < a.T_max) tok[cur_len] = a.eot;
+        atomicAdd(a.n_done + a.n_done_idx, 1);
+      }
+      return;
+    }
+  }
+  const bool first = (cur_len == n_initial);
 
   if (tid == 0) {
     // ApplyTimestampRules bookkeeping over the sampled tokens tokens[n_initial : cur_len] (decoding.py, restated)
-    const int ns = a.cur_len - a.n_initial;
-    const int* seq = tok + a.n_initial;
+    const int ns = cur_len - n_initial;
+    const int* seq = tok + n_initial;
     const bool last = ns >= 1 && seq[ns - 1] >= a.timestamp_begin;
     const bool pen = ns < 2 || seq[ns - 2] >= a.timestamp_begin;
     int last_ts = -1;
@@ -210,17 +265,18 @@ __global__ __launch_bounds__(1024) void decode_select_kernel(DecodeSelectArgs a)
       }
   }
   if (tid == 0) {
-    const int prev = tok[a.cur_len - 1];
+    const int prev = tok[cur_len - 1];
     const float s_final = text_dead ? s_ts : s_text + s_ts;
     const float logprob = (best - m_all) - logf(s_final);  // log_softmax of the filtered logits at the argmax
     int next = best_i;
     if (best_i == 0x7fffffff) next = a.eot;  // every token filtered out (cannot happen with the stock filters)
     if (prev == a.eot) next = a.eot;         // finished rows keep emitting EOT and stop accumulating
     else a.sum_logprob[b] += logprob;
-    tok[a.cur_len] = next;
-    if (next == a.eot) atomicAdd(a.n_done + a.cur_len, 1);
+    tok[cur_len] = next;
+    if (next == a.eot) atomicAdd(a.n_done + (ROWS ? a.n_done_idx : cur_len), 1);
   }
 }
+
 
 // probs_at_sot[no_speech] of DecodingTask._main_loop (i == 0): softmax over the vocabulary of the logits at the <|sot|>
 // position, probability of the <|nospeech|> token; one workgroup per row.
@@ -257,6 +313,19 @@ hipError_t launch_kv_append(const half_t* qkv, half_t* kc, half_t* vc, int B, in
   return hipGetLastError();
 }
 
+hipError_t launch_embed_step_rows(const int* tokens, int T_max, const int* t_rows, const half_t* tok_emb, const float* pos_emb, float* x, int B,
+                                  int d, int n_vocab, hipStream_t s) {
+  if (!t_rows || T_max < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(embed_step_rows_kernel, dim3(B), dim3(256), 0, s, tokens, T_max, t_rows, tok_emb, pos_emb, x, d, n_vocab);
+  return hipGetLastError();
+}
+
+hipError_t launch_kv_append_rows(const half_t* qkv, half_t* kc, half_t* vc, int B, int T_max, const int* t_rows, int d, hipStream_t s) {
+  if ((d & 7) != 0 || !t_rows || T_max < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kv_append_rows_kernel, dim3(B), dim3(256), 0, s, qkv, kc, vc, T_max, t_rows, d);
+  return hipGetLastError();
+}
+
 hipError_t launch_embed_prefix(const int* tokens, int T_max, int n, const half_t* tok_emb, const float* pos_emb, float* x, int B, int d,
                                int n_vocab, hipStream_t s) {
   if (n < 1 || n > T_max) return hipErrorInvalidValue;
@@ -276,9 +345,21 @@ hipError_t launch_gather_rows(const float* x, float* out, int B, int n, int p0, 
   return hipGetLastError();
 }
 
+hipError_t launch_gather_rows_per_row(const float* x, float* out, int B, int n, const int* p0_rows, const int* p1_rows, int d, hipStream_t s) {
+  if (n < 1 || !p0_rows) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gather_rows_per_row_kernel, dim3(B, p1_rows ? 2 : 1), dim3(256), 0, s, x, out, n, p0_rows, p1_rows, d);
+  return hipGetLastError();
+}
+
+hipError_t launch_decode_select_rows(const DecodeSelectArgs& a, int B, hipStream_t s) {
+  if (!a.cur_len_rows || !a.n_initial_rows || !a.cap_rows || a.n_done_idx < 0 || a.T_max < 2) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(decode_select_kernel<true>, dim3(B), dim3(1024), 0, s, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_decode_select(const DecodeSelectArgs& a, int B, hipStream_t s) {
   if (a.cur_len < 1 || a.cur_len >= a.T_max || a.n_initial < 1 || a.cur_len < a.n_initial) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(decode_select_kernel, dim3(B), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(decode_select_kernel<false>, dim3(B), dim3(1024), 0, s, a);
   return hipGetLastError();
 }
 

@@ -200,6 +200,7 @@ struct wca_engine {
   int probe_LH = 0, probe_N = 0;
   // greedy ASR pre-pass (wca_greedy_decode): self-attention K/V cache [L][2][B][T_max][d], token rows, masks, logits
   GrowBuf dec_cache, dec_tokens, dec_masks, dec_logits, dec_state;
+  GrowBuf dec_rows;              // wca_greedy_decode_rows: the per-row int tables (n_initial - 1, sot_index, n_initial, sample cap; per step: fed position, key count, cur_len)
   GrowBuf dec_gather;            // prefill: the f32 residual rows whose logits are needed ([2B][d]: last initial position, <|sot|>)
   int* dec_done_host = nullptr;  // pinned: completion counter read back while the loop runs
   int dec_prefill_positions = 0, dec_step_positions = 0;  // the last decode: positions per row fed by the prefill / one at a time
@@ -561,10 +562,11 @@ hipError_t gemm(hipStream_t s, const half_t* A, int lda, const half_t* W, int ld
 // One GEMM of the decoder on few rows (a greedy-decode step: M = batch; batch-1 teacher-forced forwards: M = n tokens).
 // xln != nullptr: the A operand is LayerNorm(xln rows; ln_g, ln_b). kv_k != nullptr (QKV projection of a decode step, N = 3 d):
 // the k / v columns go to the self-attention cache at position kv_t. M <= DEC_ROWS_MAX and a shape the few-row kernel takes:
-// one launch (gemm_rows.hip); otherwise the separate LayerNorm / GEMM / kv_append launches.
+// one launch (gemm_rows.hip); otherwise the separate LayerNorm / GEMM / kv_append launches. kv_t_rows (device [M], nullable): row m
+// appends at its own position instead of kv_t (wca_greedy_decode_rows).
 int dec_gemm(wca_engine* e, hipStream_t s, int ws, const half_t* A, int lda, const float* xln, const float* ln_g, const float* ln_b,
              half_t* xn_scratch, const half_t* W, int ldw, const float* bias, void* C, int ldc, int M, int N, int K, int gelu, int out_mode,
-             int site, half_t* kv_k = nullptr, half_t* kv_v = nullptr, int T_max = 0, int kv_t = 0) {
+             int site, half_t* kv_k = nullptr, half_t* kv_v = nullptr, int T_max = 0, int kv_t = 0, const int* kv_t_rows = nullptr) {
   const bool ln = xln != nullptr;
   const int sk = gemm_rows_pick_splitk(K);
   const bool fits = sk <= 1 || (kv_k == nullptr && (size_t)((M + 63) / 64) * ((N + 15) / 16) <= e->sk_tiles &&
@@ -597,6 +599,8 @@ int dec_gemm(wca_engine* e, hipStream_t s, int ws, const half_t* A, int lda, con
     g.kv_bs = (long)T_max * K;
     g.kv_t = kv_t;
     g.kv_d = kv_k ? N / 3 : 0;
+    g.kv_t_rows = kv_k ? kv_t_rows : nullptr;
+    g.kv_tmax = T_max;
     HIPCHK(launch_gemm_rows(g, s));
     return WCA_OK;
   }
@@ -606,7 +610,8 @@ int dec_gemm(wca_engine* e, hipStream_t s, int ws, const half_t* A, int lda, con
     lda = K;
   }
   HIPCHK(gemm(s, A, lda, W, ldw, bias, C, ldc, M, N, K, gelu, out_mode, site, e->sk_big[1 + ws], e->sk_big_bytes));
-  if (kv_k) HIPCHK(launch_kv_append(reinterpret_cast<const half_t*>(C), kv_k, kv_v, M, T_max, kv_t, N / 3, s));
+  if (kv_k && kv_t_rows) HIPCHK(launch_kv_append_rows(reinterpret_cast<const half_t*>(C), kv_k, kv_v, M, T_max, kv_t_rows, N / 3, s));
+  else if (kv_k) HIPCHK(launch_kv_append(reinterpret_cast<const half_t*>(C), kv_k, kv_v, M, T_max, kv_t, N / 3, s));
   return WCA_OK;
 }
 
@@ -1137,8 +1142,10 @@ int run_decoder(wca_engine* e, const int64_t* tokens_dev, int B, int n, float* c
 // phase: -1 = embedding only, li in [0, L) = decoder layer li only, L = final LayerNorm + logits only, -2 = the whole step.
 // The two half-batches of wca_greedy_decode are enqueued layer by layer in turn (the queues are served in the order their
 // packets arrive: coarse enqueueing gives coarse alternation and no overlap).
+// pos_rows / nk_rows (device, already offset to row b0; both or neither): row b feeds the token at its OWN position pos_rows[b] and
+// attends to nk_rows[b] = pos_rows[b] + 1 cached keys (wca_greedy_decode_rows); t is then unused.
 int run_decode_step(wca_engine* e, hipStream_t s, int ws, const half_t* kvbuf, const int* tokens, int b0, int B, int B_all, int t, int T_max,
-                    bool want_logits, int phase = -2) {
+                    bool want_logits, int phase = -2, const int* pos_rows = nullptr, const int* nk_rows = nullptr) {
   const wca_model_dims& D = e->dims;
   const int dt = D.n_text_state, H = D.n_text_head, L = D.n_text_layer;
   const float scale = 1.0f / std::sqrt((float)(dt / H));
@@ -1153,14 +1160,16 @@ int run_decode_step(wca_engine* e, hipStream_t s, int ws, const half_t* kvbuf, c
   // split mode: the cross-K/V rows are [hi | lo]; the greedy pre-pass (whisper.decode runs in fp16 itself) reads the hi halves
   const int kv_ld = (e->split ? 2 : 1) * L * 2 * dt;
   const half_t* kvb = kvbuf + (size_t)b0 * N_CTX * kv_ld;
-  if (phase == -2 || phase == -1)
+  if ((phase == -2 || phase == -1) && pos_rows)
+    HIPCHK(launch_embed_step_rows(tokens + (size_t)b0 * T_max, T_max, pos_rows, e->tok_emb, e->dec_pos, xd, B, dt, D.n_vocab, s));
+  else if (phase == -2 || phase == -1)
     HIPCHK(launch_embed_step(tokens + (size_t)b0 * T_max, T_max, t, e->tok_emb, e->dec_pos, xd, B, dt, D.n_vocab, s));
   for (int li = 0; li < L; ++li) {
     if (phase != -2 && phase != li) continue;
     const LayerW& l = e->dec[li];
     half_t* kc = cache + (size_t)(2 * li) * plane + (size_t)b0 * T_max * dt;
     half_t* vc = kc + plane;
-    WCA_TRY(dec_gemm(e, s, ws, nullptr, 0, xd, l.ln1_g, l.ln1_b, xdn, l.qkv_w, dt, l.qkv_b, qkv_d, 3 * dt, B, 3 * dt, dt, 0, 0, 2, kc, vc, T_max, t));
+    WCA_TRY(dec_gemm(e, s, ws, nullptr, 0, xd, l.ln1_g, l.ln1_b, xdn, l.qkv_w, dt, l.qkv_b, qkv_d, 3 * dt, B, 3 * dt, dt, 0, 0, 2, kc, vc, T_max, t, pos_rows));
     {
       AttnArgs a{};
       a.Q = qkv_d;
@@ -1174,7 +1183,8 @@ int run_decode_step(wca_engine* e, hipStream_t s, int ws, const half_t* kvbuf, c
       a.o_bs = dt;
       a.o_rs = dt;
       a.nq = 1;
-      a.nk = t + 1;  // the cache holds exactly the causal prefix
+      a.nk = nk_rows ? T_max : t + 1;  // the cache holds exactly the causal prefix (per row: nk_rows[b] of the T_max cached rows)
+      a.nk_rows = nk_rows;
       a.H = H;
       a.B = B;
       a.scale = scale;
@@ -1220,7 +1230,10 @@ int run_decode_step(wca_engine* e, hipStream_t s, int ws, const half_t* kvbuf, c
 // the step loop continues at t = n); each layer's cross-K/V is read once for all n queries of a row. Only the rows whose logits
 // are needed get the final LayerNorm and the vocabulary projection: position n - 1 -> e->dec_logits rows [0, B), and, with
 // sot_index >= 0, position sot_index -> rows [B, 2B).
-int run_decode_prefill(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, int n, int T_max, int sot_index) {
+// last_rows (device [B], nullable): the rows of the batch hold different numbers of initial tokens, padded to n (wca_greedy_decode_rows): the
+// first choice is read at position last_rows[b] = n_initial[b] - 1 and <|sot|> at sot_rows[b] (nullable = no sot logits); sot_index is unused.
+int run_decode_prefill(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, int n, int T_max, int sot_index,
+                       const int* last_rows = nullptr, const int* sot_rows = nullptr) {
   const wca_model_dims& D = e->dims;
   const int dt = D.n_text_state, H = D.n_text_head, L = D.n_text_layer;
   const int M = B * n;
@@ -1281,9 +1294,10 @@ int run_decode_prefill(wca_engine* e, hipStream_t s, const half_t* kvbuf, const 
     WCA_TRY(dec_gemm(e, s, 0, nullptr, 0, e->xd, l.ln2_g, l.ln2_b, e->xdn, l.fc1_w, dt, l.fc1_b, e->hid_d, 4 * dt, M, 4 * dt, dt, 1, 0, 2));
     WCA_TRY(dec_gemm(e, s, 0, e->hid_d, 4 * dt, nullptr, nullptr, nullptr, nullptr, l.fc2_w, 4 * dt, l.fc2_b, e->xd, dt, M, dt, 4 * dt, 0, 2, 2));
   }
-  const int R = (sot_index >= 0 ? 2 : 1) * B;
+  const int R = ((last_rows ? sot_rows != nullptr : sot_index >= 0) ? 2 : 1) * B;
   float* xg = (float*)e->dec_gather.p;
-  HIPCHK(launch_gather_rows(e->xd, xg, B, n, n - 1, sot_index, dt, s));
+  if (last_rows) HIPCHK(launch_gather_rows_per_row(e->xd, xg, B, n, last_rows, sot_rows, dt, s));
+  else HIPCHK(launch_gather_rows(e->xd, xg, B, n, n - 1, sot_index, dt, s));
   WCA_TRY(dec_gemm(e, s, 0, nullptr, 0, xg, e->lnf_g, e->lnf_b, e->xdn, e->tok_emb, dt, nullptr, (float*)e->dec_logits.p, D.n_vocab, R, D.n_vocab,
                    dt, 0, 1, 3));
   return WCA_OK;
@@ -1573,7 +1587,7 @@ int run_token_logprobs(wca_engine* e, hipStream_t s, const int64_t* tokens_dev, 
 extern "C" {
 
 const char* wca_last_error(void) { return g_err.c_str(); }
-int wca_version(void) { return 10; }   // 10: wca_log_mel_long / wca_mel_window (whole-recording log-mel, window cut); 9: the two diagnostic stamp entry points removed, no switch read from the environment; 8: prompted greedy decode (wca_greedy_decode_ex, batched prefill); 7: two precision modes only (the per-stage precision mask, its setter / getter and the mixed
+int wca_version(void) { return 11; }   // 11: wca_greedy_decode_rows (per-row initial tokens / sample budgets: the rows of a batch at different decoder positions); 10: wca_log_mel_long / wca_mel_window (whole-recording log-mel, window cut); 9: the two diagnostic stamp entry points removed, no switch read from the environment; 8: prompted greedy decode (wca_greedy_decode_ex, batched prefill); 7: two precision modes only (the per-stage precision mask, its setter / getter and the mixed
                                       // state are gone); 6: teacher-token log-probs (wca_align_batch_enqueue_ex / _fetch_ex, wca_token_logprobs);
                                       // 5: a new engine is in the contract mode; wca_engine_create_ex, W_lo slab, switch table
 
@@ -1679,6 +1693,7 @@ void wca_engine_destroy(wca_engine* e) {
   e->dec_logits.release();
   e->dec_state.release();
   e->dec_gather.release();
+  e->dec_rows.release();
   e->probe_jump.release();
   for (int i = 0; i < 2; ++i) {
     if (e->res_host[i]) (void)hipHostFree(e->res_host[i]);
@@ -2682,6 +2697,65 @@ int wca_encode_batch(wca_engine* e, const float* mel_dev, const float* pcm_dev, 
   return WCA_OK;
 }
 
+// What wca_greedy_decode_ex and wca_greedy_decode_rows share around their loops.
+// Phase 1 on `stream` (unless an encoded state is waiting: wca_encode_batch) and the state to decode; the state stays queued for the
+// alignment (wca_align_batch_enqueue with pcm_dev = NULL). A state that was decoded but never aligned is stale once another decode
+// starts (stand-alone whisper.decode use). The autoregressive loop runs on `stream2` (it shares the decoder scratch with phase 2 of
+// the alignment, which is ordered before it on that stream; phase 1 of the NEXT batch may run beside it on `stream`): stream2 is made
+// to wait for the state's cross-K/V here.
+static int decode_take_state(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, int batch,
+                      wca_engine::EncState** out) {
+  for (auto it = e->enc_q.begin(); it != e->enc_q.end();) {
+    if (it->decoded) {
+      e->slot_busy[it->slot] = false;
+      it = e->enc_q.erase(it);
+    } else {
+      ++it;
+    }
+  }
+  if (mel_dev != nullptr || pcm_dev != nullptr) {
+    const int rc = wca_encode_batch(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch);
+    if (rc) return rc;
+  }
+  wca_engine::EncState* st = nullptr;
+  for (auto& q : e->enc_q)
+    if (!q.decoded) {
+      st = &q;
+      break;
+    }
+  if (!st || st->batch != batch) return fail(WCA_ERR_STATE, "no encoded batch of %d utterances is waiting to be decoded", batch);
+  HIPCHK(hipStreamWaitEvent(e->stream2, e->ev_kv[st->slot], 0));
+  *out = st;
+  return WCA_OK;
+}
+
+// The token rows, sum_logprob and no_speech_prob of a finished loop to the host. Row b holds n_initial[b] initial tokens and has written
+// positions [0, n_have[b]); n_tokens[b] = its first sampled EOT (or n_have[b]): tokens_out[b][n_initial[b] : n_tokens[b]] are the sampled
+// tokens, and positions never reached hold EOT. Marks the state decoded.
+static int decode_read_back(wca_engine* e, hipStream_t s2, wca_engine::EncState* st, int batch, int T_max, int eot, const int32_t* n_initial,
+                     const int32_t* n_have, int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host, float* no_speech_prob_host) {
+  std::vector<int32_t> toks((size_t)batch * T_max);
+  HIPCHK(hipMemcpyAsync(toks.data(), e->dec_tokens.p, sizeof(int) * toks.size(), hipMemcpyDeviceToHost, s2));
+  std::vector<float> lp(2 * (size_t)batch);  // sum_logprob [batch], no_speech_prob [batch] at the head of dec_state
+  HIPCHK(hipMemcpyAsync(lp.data(), e->dec_state.p, sizeof(float) * 2 * batch, hipMemcpyDeviceToHost, s2));
+  HIPCHK(hipStreamSynchronize(s2));
+  for (int b = 0; b < batch; ++b) {
+    int n = n_have[b];
+    for (int i = n_initial[b]; i < n_have[b]; ++i)
+      if (toks[(size_t)b * T_max + i] == eot) {
+        n = i;
+        break;
+      }
+    n_tokens_host[b] = n;
+    for (int i = 0; i < T_max; ++i) tokens_out_host[(size_t)b * T_max + i] = (i < n_have[b]) ? toks[(size_t)b * T_max + i] : eot;
+    if (sum_logprob_host) sum_logprob_host[b] = lp[b];
+    if (no_speech_prob_host) no_speech_prob_host[b] = lp[batch + b];
+  }
+  st->decoded = true;
+  e->last_batch = batch;
+  return WCA_OK;
+}
+
 int wca_greedy_decode(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
                       int batch, const int32_t* initial_tokens_host, int n_initial, const uint8_t* suppress_mask_host,
                       const uint8_t* blank_mask_host, const wca_decode_opts* o, int32_t* tokens_out_host, int32_t* n_tokens_host,
@@ -2710,7 +2784,6 @@ int wca_greedy_decode_ex(wca_engine* e, const float* mel_dev, const float* pcm_d
   int rc = check_ready(e);
   if (rc) return rc;
   if (mel_dev != nullptr && pcm_dev != nullptr) return fail(WCA_ERR_INVALID, "pass at most one of mel_dev / pcm_dev");
-  const bool have_input = (mel_dev != nullptr) || (pcm_dev != nullptr);
   if (!initial_tokens_host || !suppress_mask_host || !o || !tokens_out_host || !n_tokens_host) return fail(WCA_ERR_INVALID, "null argument");
   if (pcm_dev && !n_samples_host) return fail(WCA_ERR_INVALID, "null argument");
   if (batch < 1 || batch > e->max_batch) return fail(WCA_ERR_INVALID, "batch %d outside [1,%d]", batch, e->max_batch);
@@ -2727,34 +2800,10 @@ int wca_greedy_decode_ex(wca_engine* e, const float* mel_dev, const float* pcm_d
     if (initial_tokens_host[i] < 0 || initial_tokens_host[i] >= D.n_vocab) return fail(WCA_ERR_INVALID, "initial token %d outside the vocabulary", i);
   const int V = D.n_vocab, dt = D.n_text_state, L = D.n_text_layer;
   const int T_max = n_initial + o->sample_len;
-  // ---- phase 1 on `stream` (unless an encoded state is waiting: wca_encode_batch); the state stays queued for the
-  // alignment (wca_align_batch_enqueue with pcm_dev = NULL)
-  // a state that was decoded but never aligned is stale once another decode starts (stand-alone whisper.decode use)
-  for (auto it = e->enc_q.begin(); it != e->enc_q.end();) {
-    if (it->decoded) {
-      e->slot_busy[it->slot] = false;
-      it = e->enc_q.erase(it);
-    } else {
-      ++it;
-    }
-  }
-  if (have_input) {
-    rc = wca_encode_batch(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch);
-    if (rc) return rc;
-  }
   wca_engine::EncState* st = nullptr;
-  for (auto& q : e->enc_q)
-    if (!q.decoded) {
-      st = &q;
-      break;
-    }
-  if (!st || st->batch != batch) return fail(WCA_ERR_STATE, "no encoded batch of %d utterances is waiting to be decoded", batch);
-  const int bs = st->slot;
-  half_t* kvbuf = bs ? e->kv_alt : e->kv;
-  // ---- the autoregressive loop on `stream2` (it shares the decoder scratch with phase 2 of the alignment, which is
-  // ordered before it on that stream; phase 1 of the NEXT batch may run beside it on `stream`)
+  if ((rc = decode_take_state(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, &st))) return rc;
+  half_t* kvbuf = st->slot ? e->kv_alt : e->kv;
   hipStream_t s2 = e->stream2;
-  HIPCHK(hipStreamWaitEvent(s2, e->ev_kv[bs], 0));
   HIPCHK(e->dec_cache.ensure(sizeof(half_t) * (size_t)L * 2 * batch * T_max * dt));
   HIPCHK(e->dec_tokens.ensure(sizeof(int) * (size_t)batch * T_max));
   HIPCHK(e->dec_masks.ensure((size_t)2 * V));
@@ -2865,27 +2914,178 @@ int wca_greedy_decode_ex(wca_engine* e, const float* mel_dev, const float* pcm_d
     HIPCHK(hipStreamWaitEvent(s2, e->ev_join, 0));
   }
   if (dbg_host) fprintf(stderr, "[wca] greedy decode: host enqueue time %.1f us per position (%d halves)\n", host_us / (steps + n_initial - 1), n_half);
-  std::vector<int32_t> toks((size_t)batch * T_max);
-  HIPCHK(hipMemcpyAsync(toks.data(), tokens_dev, sizeof(int) * toks.size(), hipMemcpyDeviceToHost, s2));
-  std::vector<float> lp(2 * (size_t)batch);
-  HIPCHK(hipMemcpyAsync(lp.data(), sum_lp, sizeof(float) * 2 * batch, hipMemcpyDeviceToHost, s2));
-  HIPCHK(hipStreamSynchronize(s2));
-  const int n_have = n_initial + steps;  // positions written so far
-  for (int b = 0; b < batch; ++b) {
-    int n = n_have;
-    for (int i = n_initial; i < n_have; ++i)
-      if (toks[(size_t)b * T_max + i] == o->eot) {
-        n = i;
-        break;
-      }
-    n_tokens_host[b] = n;  // tokens_out[b][n_initial : n] are the sampled tokens before the first EOT
-    for (int i = 0; i < T_max; ++i) tokens_out_host[(size_t)b * T_max + i] = (i < n_have) ? toks[(size_t)b * T_max + i] : o->eot;
-    if (sum_logprob_host) sum_logprob_host[b] = lp[b];
-    if (want_nsp) no_speech_prob_host[b] = lp[batch + b];
-  }
-  st->decoded = true;
-  e->last_batch = batch;
+  std::vector<int32_t> ni_rows(batch, n_initial), have_rows(batch, n_initial + steps);  // positions written so far
+  if ((rc = decode_read_back(e, s2, st, batch, T_max, o->eot, ni_rows.data(), have_rows.data(), tokens_out_host, n_tokens_host, sum_logprob_host,
+                             want_nsp ? no_speech_prob_host : nullptr)))
+    return rc;
   e->dec_prefill_positions = prefill ? n_initial : 0;
+  e->dec_step_positions = step_positions;
+  return WCA_OK;
+}
+
+// Greedy decode of a batch whose rows carry initial tokens of their own (transcribe_batch: every recording's prompt is its own previous
+// text). Row b holds n_initial[b] tokens and samples at most sample_len[b]; at loop step s (0 = the prefill's choice) it is at
+// cur_len = n_initial[b] + s. Prefill: every row padded with eot to n_max = max n_initial (a valid query never sees a later position,
+// and the K/V that the pad positions leave in cache slots >= n_initial[b] are overwritten by the step loop before they are read);
+// steps: the per-row forms of embed_step / KV append / one-query attention / decode_select, fed from small device tables built here.
+// A row past its budget keeps going through the kernels as a finished row at a clamped position (<= T_max - 2, so no positional row
+// past n_text_ctx - 1 and no cache slot past T_max - 1 is touched); what it computes is never read.
+int wca_greedy_decode_rows(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
+                           int batch, const int32_t* initial_tokens_host, const int32_t* n_initial_host, const int32_t* sot_index_host,
+                           const int32_t* sample_len_host, const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host,
+                           const wca_decode_opts* o, int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
+                           float* no_speech_prob_host) {
+  int rc = check_ready(e);
+  if (rc) return rc;
+  if (mel_dev != nullptr && pcm_dev != nullptr) return fail(WCA_ERR_INVALID, "pass at most one of mel_dev / pcm_dev");
+  if (!initial_tokens_host || !n_initial_host || !sot_index_host || !sample_len_host || !suppress_mask_host || !o || !tokens_out_host ||
+      !n_tokens_host)
+    return fail(WCA_ERR_INVALID, "null argument");
+  if (pcm_dev && !n_samples_host) return fail(WCA_ERR_INVALID, "null argument");
+  if (batch < 1 || batch > e->max_batch) return fail(WCA_ERR_INVALID, "batch %d outside [1,%d]", batch, e->max_batch);
+  const wca_model_dims& D = e->dims;
+  if (o->eot < 0 || o->eot >= D.n_vocab || o->timestamp_begin < 0 || o->timestamp_begin > D.n_vocab)
+    return fail(WCA_ERR_INVALID, "eot / timestamp_begin outside the vocabulary");
+  int n_max = 0, T_max = 0, S = 0;
+  for (int b = 0; b < batch; ++b) {
+    const int ni = n_initial_host[b], sl = sample_len_host[b];
+    if (ni < 1 || sl < 1 || ni > D.n_text_ctx || ni + sl > D.n_text_ctx + 1)
+      return fail(WCA_ERR_TOO_LONG, "row %d: n_initial %d + sample_len %d exceeds n_text_ctx + 1 = %d (or n_initial exceeds n_text_ctx)", b, ni, sl,
+                  D.n_text_ctx + 1);
+    if (sot_index_host[b] < 0 || sot_index_host[b] >= ni) return fail(WCA_ERR_INVALID, "row %d: sot_index %d outside [0,%d)", b, sot_index_host[b], ni);
+    n_max = std::max(n_max, ni);
+    T_max = std::max(T_max, ni + sl);
+    S = std::max(S, sl);
+  }
+  for (int b = 0; b < batch; ++b)
+    for (int i = 0; i < n_initial_host[b]; ++i) {
+      const int32_t tk = initial_tokens_host[(size_t)b * n_max + i];
+      if (tk < 0 || tk >= D.n_vocab) return fail(WCA_ERR_INVALID, "row %d: initial token %d outside the vocabulary", b, i);
+    }
+  const int V = D.n_vocab, dt = D.n_text_state, L = D.n_text_layer;
+  wca_engine::EncState* st = nullptr;
+  if ((rc = decode_take_state(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, &st))) return rc;
+  half_t* kvbuf = st->slot ? e->kv_alt : e->kv;
+  hipStream_t s2 = e->stream2;
+  HIPCHK(e->dec_cache.ensure(sizeof(half_t) * (size_t)L * 2 * batch * T_max * dt));
+  HIPCHK(e->dec_tokens.ensure(sizeof(int) * (size_t)batch * T_max));
+  HIPCHK(e->dec_masks.ensure((size_t)2 * V));
+  const bool want_nsp = no_speech_prob_host != nullptr && o->no_speech >= 0 && o->no_speech < V;
+  HIPCHK(e->dec_logits.ensure(sizeof(float) * (size_t)(want_nsp ? 2 : 1) * batch * V));
+  HIPCHK(e->dec_state.ensure(sizeof(float) * 2 * batch + sizeof(int) * (size_t)S));
+  HIPCHK(e->dec_gather.ensure(sizeof(float) * 2 * (size_t)batch * dt));
+  if (!e->dec_done_host) HIPCHK(hipHostMalloc((void**)&e->dec_done_host, sizeof(int) * 4, hipHostMallocDefault));
+  std::vector<int32_t> init((size_t)batch * T_max, o->eot);
+  for (int b = 0; b < batch; ++b)
+    for (int i = 0; i < n_initial_host[b]; ++i) init[(size_t)b * T_max + i] = initial_tokens_host[(size_t)b * n_max + i];
+  // the int tables: [0] n_initial - 1, [1] sot_index, [2] n_initial, [3] sample cap; then per step s in [0, S): fed position
+  // min(n_initial + s - 1, T_max - 2), key count = fed position + 1, cur_len = n_initial + s  ([batch] each)
+  std::vector<int32_t> tab((size_t)(4 + 3 * S) * batch);
+  for (int b = 0; b < batch; ++b) {
+    const int ni = n_initial_host[b];
+    tab[0 * (size_t)batch + b] = ni - 1;
+    tab[1 * (size_t)batch + b] = sot_index_host[b];
+    tab[2 * (size_t)batch + b] = ni;
+    tab[3 * (size_t)batch + b] = sample_len_host[b];
+    for (int s = 0; s < S; ++s) {
+      const int pos = std::max(0, std::min(ni + s - 1, T_max - 2));
+      tab[(size_t)(4 + 3 * s + 0) * batch + b] = pos;
+      tab[(size_t)(4 + 3 * s + 1) * batch + b] = pos + 1;
+      tab[(size_t)(4 + 3 * s + 2) * batch + b] = ni + s;
+    }
+  }
+  HIPCHK(e->dec_rows.ensure(sizeof(int) * tab.size()));
+  int* tokens_dev = (int*)e->dec_tokens.p;
+  const int* tab_dev = (const int*)e->dec_rows.p;
+  unsigned char* masks = (unsigned char*)e->dec_masks.p;
+  float* sum_lp = (float*)e->dec_state.p;
+  float* nsp = sum_lp + batch;
+  int* n_done = (int*)((char*)e->dec_state.p + sizeof(float) * 2 * batch);
+  HIPCHK(hipMemcpyAsync(tokens_dev, init.data(), sizeof(int) * init.size(), hipMemcpyHostToDevice, s2));
+  HIPCHK(hipMemcpyAsync(e->dec_rows.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, s2));
+  HIPCHK(hipMemcpyAsync(masks, suppress_mask_host, V, hipMemcpyHostToDevice, s2));
+  if (blank_mask_host) HIPCHK(hipMemcpyAsync(masks + V, blank_mask_host, V, hipMemcpyHostToDevice, s2));
+  HIPCHK(hipMemsetAsync(e->dec_state.p, 0, sizeof(float) * 2 * batch + sizeof(int) * (size_t)S, s2));
+  HIPCHK(hipStreamSynchronize(s2));  // `init` / `tab` are pageable host memory
+  DecodeSelectArgs sel{};
+  sel.logits = (const float*)e->dec_logits.p;
+  sel.ld = V;
+  sel.n_vocab = V;
+  sel.tokens = tokens_dev;
+  sel.T_max = T_max;
+  sel.suppress_mask = masks;
+  sel.blank_mask = blank_mask_host ? masks + V : nullptr;
+  sel.eot = o->eot;
+  sel.timestamp_begin = o->timestamp_begin;
+  sel.apply_timestamp_rules = o->apply_timestamp_rules;
+  sel.max_initial_timestamp_index = o->max_initial_timestamp_index;
+  sel.sum_logprob = sum_lp;
+  sel.n_done = n_done;
+  sel.n_initial_rows = tab_dev + 2 * (size_t)batch;
+  sel.cap_rows = tab_dev + 3 * (size_t)batch;
+  const int n_half = (e->dec_streams == 2 && batch >= 16) ? 2 : 1;
+  const int hb[3] = {0, n_half == 2 ? (batch / 2 + 7) / 8 * 8 : batch, batch};
+  hipStream_t hs[2] = {s2, e->stream3};
+  auto join = [&]() -> int {
+    if (n_half == 2) {
+      HIPCHK(hipEventRecord(e->ev_join, e->stream3));
+      HIPCHK(hipStreamWaitEvent(s2, e->ev_join, 0));
+    }
+    return WCA_OK;
+  };
+  // ---- step 0: the prefill on s2 for the whole batch, and its choice
+  rc = run_decode_prefill(e, s2, kvbuf, tokens_dev, batch, n_max, T_max, -1, tab_dev, want_nsp ? tab_dev + batch : nullptr);
+  if (rc) return rc;
+  if (want_nsp) HIPCHK(launch_token_prob((const float*)e->dec_logits.p + (size_t)batch * V, V, V, o->no_speech, nsp, batch, s2));
+  {
+    DecodeSelectArgs sh = sel;
+    sh.cur_len_rows = tab_dev + (size_t)(4 + 2) * batch;
+    sh.n_done_idx = 0;
+    HIPCHK(launch_decode_select_rows(sh, batch, s2));
+  }
+  if (n_half == 2) {
+    HIPCHK(hipEventRecord(e->ev_fork, s2));
+    HIPCHK(hipStreamWaitEvent(e->stream3, e->ev_fork, 0));
+  }
+  int steps = 1, step_positions = 0;
+  bool all_done = false;
+  for (int s = 1; s < S && !all_done; ++s) {
+    const int* row = tab_dev + (size_t)(4 + 3 * s) * batch;
+    ++step_positions;
+    for (int phase = -1; phase <= L; ++phase)
+      for (int h = 0; h < n_half; ++h) {
+        rc = run_decode_step(e, hs[h], h, kvbuf, tokens_dev, hb[h], hb[h + 1] - hb[h], batch, 0, T_max, true, phase, row + hb[h],
+                             row + batch + hb[h]);
+        if (rc) return rc;
+      }
+    for (int h = 0; h < n_half; ++h) {
+      const int b0 = hb[h], nb = hb[h + 1] - hb[h];
+      DecodeSelectArgs sh = sel;
+      sh.logits = sel.logits + (size_t)b0 * V;
+      sh.tokens = sel.tokens + (size_t)b0 * T_max;
+      sh.sum_logprob = sel.sum_logprob + b0;
+      sh.n_initial_rows = sel.n_initial_rows + b0;
+      sh.cap_rows = sel.cap_rows + b0;
+      sh.cur_len_rows = row + 2 * (size_t)batch + b0;
+      sh.n_done_idx = s;
+      HIPCHK(launch_decode_select_rows(sh, nb, hs[h]));
+    }
+    ++steps;
+    // every row has produced EOT or used its budget (checked every 4 steps, as in wca_greedy_decode_ex)
+    if ((steps & 3) == 0 && steps < S) {
+      if ((rc = join())) return rc;
+      HIPCHK(hipMemcpyAsync(e->dec_done_host, n_done + s, sizeof(int), hipMemcpyDeviceToHost, s2));
+      HIPCHK(hipStreamSynchronize(s2));
+      if (e->dec_done_host[0] >= batch) all_done = true;
+    }
+  }
+  if ((rc = join())) return rc;
+  std::vector<int32_t> have_rows(batch);
+  for (int b = 0; b < batch; ++b) have_rows[b] = n_initial_host[b] + std::min(steps, (int)sample_len_host[b]);  // positions row b has written
+  if ((rc = decode_read_back(e, s2, st, batch, T_max, o->eot, n_initial_host, have_rows.data(), tokens_out_host, n_tokens_host, sum_logprob_host,
+                             want_nsp ? no_speech_prob_host : nullptr)))
+    return rc;
+  e->dec_prefill_positions = n_max;
   e->dec_step_positions = step_positions;
   return WCA_OK;
 }
@@ -3368,6 +3568,69 @@ int wca_test_decode_select(wca_engine* e, const float* logits_dev, int batch, in
   a.sum_logprob = sum_logprob_dev;
   a.n_done = n_done_dev;
   HIPCHK(launch_decode_select(a, batch, e->stream));
+  return WCA_OK;
+}
+
+int wca_test_decode_select_rows(wca_engine* e, const float* logits_dev, int batch, int n_vocab, int32_t* tokens_dev, int T_max,
+                                const int32_t* cur_len_dev, const int32_t* n_initial_dev, const int32_t* cap_dev, int n_done_idx, int n_done_len,
+                                const uint8_t* suppress_mask_dev, const uint8_t* blank_mask_dev, const wca_decode_opts* o, float* sum_logprob_dev,
+                                int32_t* n_done_dev) {
+  if (!e || !logits_dev || !tokens_dev || !cur_len_dev || !n_initial_dev || !cap_dev || !suppress_mask_dev || !o || !sum_logprob_dev || !n_done_dev)
+    return fail(WCA_ERR_INVALID, "null argument");
+  if (batch < 1 || n_vocab < 1 || T_max < 2 || n_done_idx < 0 || n_done_idx >= n_done_len) return fail(WCA_ERR_INVALID, "bad shape");
+  if (o->eot < 0 || o->eot >= n_vocab || o->timestamp_begin < 0 || o->timestamp_begin > n_vocab)
+    return fail(WCA_ERR_INVALID, "eot / timestamp_begin outside the vocabulary");
+  HIPCHK(hipSetDevice(e->device));
+  DecodeSelectArgs a{};
+  a.logits = logits_dev;
+  a.ld = n_vocab;
+  a.n_vocab = n_vocab;
+  a.tokens = tokens_dev;
+  a.T_max = T_max;
+  a.cur_len_rows = cur_len_dev;
+  a.n_initial_rows = n_initial_dev;
+  a.cap_rows = cap_dev;
+  a.n_done_idx = n_done_idx;
+  a.suppress_mask = suppress_mask_dev;
+  a.blank_mask = blank_mask_dev;
+  a.eot = o->eot;
+  a.timestamp_begin = o->timestamp_begin;
+  a.apply_timestamp_rules = o->apply_timestamp_rules;
+  a.max_initial_timestamp_index = o->max_initial_timestamp_index;
+  a.sum_logprob = sum_logprob_dev;
+  a.n_done = n_done_dev;
+  HIPCHK(launch_decode_select_rows(a, batch, e->stream));
+  return WCA_OK;
+}
+
+int wca_test_attention_rows(wca_engine* e, const void* q, const void* k, const void* v, void* o, int B, int H, int nq, int nk,
+                            const int32_t* nk_rows_dev, int causal) {
+  if (!e || !q || !k || !v || !o || !nk_rows_dev) return fail(WCA_ERR_INVALID, "null argument");
+  if (B < 1 || H < 1 || nq < 1 || nk < 1) return fail(WCA_ERR_INVALID, "bad shape");
+  HIPCHK(hipSetDevice(e->device));
+  AttnArgs a{};
+  const int d = H * 64;
+  a.Q = (const half_t*)q;
+  a.q_bs = (long)nq * d;
+  a.q_rs = d;
+  a.K = (const half_t*)k;
+  a.k_bs = (long)nk * d;
+  a.k_rs = d;
+  a.V = (const half_t*)v;
+  a.v_bs = (long)nk * d;
+  a.v_rs = d;
+  a.O = (half_t*)o;
+  a.o_bs = (long)nq * d;
+  a.o_rs = d;
+  a.nq = nq;
+  a.nk = nk;
+  a.nk_rows = nk_rows_dev;
+  a.H = H;
+  a.B = B;
+  a.scale = 0.125f;
+  a.causal = causal & 1;
+  if (launch_attention(a, e->stream) != hipSuccess)
+    return fail(WCA_ERR_INVALID, "per-row key counts are taken by the one-query f16 attention only (nq = 1, no mask)");
   return WCA_OK;
 }
 

@@ -62,7 +62,9 @@ __device__ __forceinline__ void wave_sum8(float (&v)[8]) {
 typedef unsigned long long __attribute__((address_space(1))) gu64_t;
 typedef unsigned __attribute__((address_space(1))) gu32_t;
 
-template <int A_MODE, int OUT_MODE, bool GELU>
+// KV_ROWS: the KV-cache append goes to a per-row position (a.kv_t_rows[m]) instead of a.kv_t (the QKV projection of a decode step whose
+// rows sit at different positions: out_mode 0, no GELU); the uniform launches take the KV_ROWS = false instances.
+template <int A_MODE, int OUT_MODE, bool GELU, bool KV_ROWS>
 __global__ __launch_bounds__(512) void gemm_rows_f16_kernel(GemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
@@ -292,7 +294,8 @@ __global__ __launch_bounds__(512) void gemm_rows_f16_kernel(GemmArgs a) {
       if (a.kv_k != nullptr && (unsigned)nb >= kv_d) {
         // KV-cache append: columns [d, 2d) -> K cache row, [2d, 3d) -> V cache row of batch row m at position kv_t
         const bool is_v = (unsigned)nb >= 2 * kv_d;
-        cp = (is_v ? a.kv_v : a.kv_k) + (long)m * a.kv_bs + (long)a.kv_t * a.kv_d + (nb - (is_v ? 2 : 1) * a.kv_d);
+        const int kv_t = KV_ROWS ? min(max(a.kv_t_rows[m], 0), a.kv_tmax - 1) : a.kv_t;
+        cp = (is_v ? a.kv_v : a.kv_k) + (long)m * a.kv_bs + (long)kv_t * a.kv_d + (nb - (is_v ? 2 : 1) * a.kv_d);
       }
       if (nb + 4 <= a.N && (reinterpret_cast<uintptr_t>(cp) & 7) == 0) {
         half4 o;
@@ -360,6 +363,7 @@ hipError_t launch_gemm_rows(const GemmArgs& a_in, hipStream_t s) {
   }
   if (a.kv_k != nullptr && (a.out_mode != 0 || !a.kv_v || a.kv_d <= 0 || (a.kv_d % 16) != 0 || a.N != 3 * a.kv_d || a.c_rows_per_batch != 0))
     return hipErrorInvalidValue;
+  if (a.kv_t_rows != nullptr && (a.kv_k == nullptr || a.gelu || a.kv_tmax < 1)) return hipErrorInvalidValue;
   const int NG = (a.N + 15) / 16;
   if (a.splitk > 1) {
     if (!a.sk_part || !a.sk_cnt) return hipErrorInvalidValue;
@@ -378,19 +382,32 @@ hipError_t launch_gemm_rows(const GemmArgs& a_in, hipStream_t s) {
   do {                                                                                                              \
     static std::atomic<unsigned> attr_mask{0};                                                                      \
     if (!(attr_mask.load(std::memory_order_acquire) & (1u << (dev & 31)))) {                                        \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_rows_f16_kernel<AM, OM, G>),            \
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_rows_f16_kernel<AM, OM, G, false>),     \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                   \
       if (e != hipSuccess) return e;                                                                                \
       attr_mask.fetch_or(1u << (dev & 31), std::memory_order_release);                                              \
     }                                                                                                               \
-    hipLaunchKernelGGL((gemm_rows_f16_kernel<AM, OM, G>), grid, block, shmem, s, a);                                \
+    hipLaunchKernelGGL((gemm_rows_f16_kernel<AM, OM, G, false>), grid, block, shmem, s, a);                         \
+  } while (0)
+#define WCA_ROWS_KV(AM)                                                                                             \
+  do {                                                                                                              \
+    static std::atomic<unsigned> attr_mask{0};                                                                      \
+    if (!(attr_mask.load(std::memory_order_acquire) & (1u << (dev & 31)))) {                                        \
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_rows_f16_kernel<AM, 0, false, true>),   \
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                   \
+      if (e != hipSuccess) return e;                                                                                \
+      attr_mask.fetch_or(1u << (dev & 31), std::memory_order_release);                                              \
+    }                                                                                                               \
+    hipLaunchKernelGGL((gemm_rows_f16_kernel<AM, 0, false, true>), grid, block, shmem, s, a);                       \
   } while (0)
 #define WCA_ROWS_A(OM, G)                \
   do {                                   \
     if (ln) WCA_ROWS_K(1, OM, G);        \
     else WCA_ROWS_K(0, OM, G);           \
   } while (0)
-  if (a.out_mode == 0) {
+  if (a.kv_t_rows != nullptr) {  // (out_mode 0 and no GELU: checked above)
+    if (ln) WCA_ROWS_KV(1); else WCA_ROWS_KV(0);
+  } else if (a.out_mode == 0) {
     if (a.gelu) WCA_ROWS_A(0, true); else WCA_ROWS_A(0, false);
   } else if (a.out_mode == 1 && !a.gelu) {
     WCA_ROWS_A(1, false);
@@ -400,6 +417,7 @@ hipError_t launch_gemm_rows(const GemmArgs& a_in, hipStream_t s) {
     return hipErrorInvalidValue;
   }
 #undef WCA_ROWS_A
+#undef WCA_ROWS_KV
 #undef WCA_ROWS_K
   return hipGetLastError();
 }

@@ -72,6 +72,8 @@ struct GemmArgs {
   unsigned* sk_cnt;        // one arrival counter per (64-row block, 16-column group), zero before the first launch (self-cleaning)
   int splitk;              // workgroups sharing K (0 = chosen by launch_gemm_rows: smallest with K / splitk <= 1024)
   int groups;              // 16-column groups per workgroup (0 = chosen: grid.x <= 256)
+  const int* kv_t_rows;    // few-row kernel, with kv_k: non-null = row m appends at position kv_t_rows[m] (device [M], clamped to [0, kv_tmax))
+  int kv_tmax;             // instead of kv_t: the rows of wca_greedy_decode_rows sit at different positions
 };
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s);
 // Few-row GEMM (M <= a few hundred rows: greedy-decode steps, batch-1 decoder forwards) with optional LayerNorm prologue,
@@ -105,6 +107,10 @@ struct AttnArgs {
   // attn_split_kernel: S = Qhi.Khi + Qhi.Klo + Qlo.Khi, O = Phi.Vhi + Phi.Vlo + Plo.Vhi, fp32 softmax on the exact logits.
   int split;
   long q_lo, k_lo, v_lo, o_lo;
+  // per-row key counts (device [B], nullable): batch row b attends to keys [0, min(nk_rows[b], nk)). Only the one-query f16 kernel
+  // of the decode step takes it (nq == 1, no capture, no mask, not split): anything else is hipErrorInvalidValue. Row b gets the key
+  // partition and summation order of a uniform call with nk = nk_rows[b].
+  const int* nk_rows;
 };
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 hipError_t launch_attention_split(const AttnArgs& a, hipStream_t s);  // attention_split.hip (launch_attention forwards a.split != 0 here)
@@ -128,6 +134,14 @@ hipError_t launch_embed_step(const int* tokens, int T_max, int t, const half_t* 
                              int n_vocab, hipStream_t s);
 // k / v columns of qkv [B][3d] -> kc / vc [B][T_max][d] at position t
 hipError_t launch_kv_append(const half_t* qkv, half_t* kc, half_t* vc, int B, int T_max, int t, int d, hipStream_t s);
+// the same with row b at position t_rows[b] (device [B], clamped to [0, T_max)): the rows of wca_greedy_decode_rows sit at different positions.
+// The engine reads t_rows (and AttnArgs.nk_rows, DecodeSelectArgs.cur_len_rows) from per-step tables it builds once per call on the host
+// instead of adding a scalar step to row_pos[b] in every kernel: a row past its sample budget stays in the batch at a CLAMPED position
+// (<= T_max - 2: no positional row past n_text_ctx - 1, no cache slot past T_max - 1), the attention needs a plain count array anyway, and
+// the clamp then lives in one place. 3 * steps * B ints per call.
+hipError_t launch_embed_step_rows(const int* tokens, int T_max, const int* t_rows, const half_t* tok_emb, const float* pos_emb, float* x, int B,
+                                  int d, int n_vocab, hipStream_t s);
+hipError_t launch_kv_append_rows(const half_t* qkv, half_t* kc, half_t* vc, int B, int T_max, const int* t_rows, int d, hipStream_t s);
 // prefill of a prompted decode (all n initial positions of every row in one forward):
 // x[b*n + i][:] = tok_emb[tokens[b*T_max + i]][:] + pos_emb[i][:] for i < n
 hipError_t launch_embed_prefix(const int* tokens, int T_max, int n, const half_t* tok_emb, const float* pos_emb, float* x, int B, int d,
@@ -136,6 +150,8 @@ hipError_t launch_embed_prefix(const int* tokens, int T_max, int n, const half_t
 hipError_t launch_kv_scatter(const half_t* qkv, half_t* kc, half_t* vc, int B, int n, int T_max, int d, hipStream_t s);
 // out [B][d] = rows (b, p0) of x [B*n][d] f32; p1 >= 0: out [B..2B) = rows (b, p1)
 hipError_t launch_gather_rows(const float* x, float* out, int B, int n, int p0, int p1, int d, hipStream_t s);
+// the same with the positions per batch row (device [B], clamped to [0, n)); p1_rows nullable
+hipError_t launch_gather_rows_per_row(const float* x, float* out, int B, int n, const int* p0_rows, const int* p1_rows, int d, hipStream_t s);
 // logit filters + greedy update of one decoding step (upstream decoding.py: SuppressBlank, SuppressTokens,
 // ApplyTimestampRules, GreedyDecoder.update at temperature 0); one workgroup per batch row
 struct DecodeSelectArgs {
@@ -149,8 +165,14 @@ struct DecodeSelectArgs {
   int apply_timestamp_rules, max_initial_timestamp_index;  // index < 0: no limit
   float* sum_logprob;                  // [B] accumulated log-probability of the sampled tokens
   int* n_done;                         // [T_max] n_done[cur_len] += 1 for every row whose new token is EOT
+  // launch_decode_select_rows only (device [B] each; cur_len / n_initial above are then unused):
+  const int* cur_len_rows;             // tokens row b holds; SuppressBlank / the first-timestamp rules fire at cur_len_rows[b] == n_initial_rows[b]
+  const int* n_initial_rows;           // the timestamp history is tokens[b][n_initial_rows[b] : cur_len_rows[b]]
+  const int* cap_rows;                 // sample budget: a row with cur_len - n_initial >= cap is a finished row (EOT, nothing added)
+  int n_done_idx;                      // n_done[n_done_idx] += 1 per row whose new token is EOT (the step, not cur_len)
 };
 hipError_t launch_decode_select(const DecodeSelectArgs& a, int B, hipStream_t s);
+hipError_t launch_decode_select_rows(const DecodeSelectArgs& a, int B, hipStream_t s);
 // out[b] = softmax(logits[b])[token]  (no_speech_prob: the <|nospeech|> probability at the <|sot|> position)
 hipError_t launch_token_prob(const float* logits, int ld, int n_vocab, int token, float* out, int B, hipStream_t s);
 hipError_t launch_f32_to_f16(const float* in, half_t* out, size_t n, hipStream_t s);

@@ -51,10 +51,17 @@ def transcribe(model, audio, **kwargs):
     return _transcribe.transcribe(model, audio, **kwargs)
 
 
+def transcribe_batch(model, audios, **kwargs):
+    return _transcribe.transcribe_batch(model, audios, **kwargs)
+
+
 transcribe.__doc__ = _transcribe.transcribe.__doc__
+transcribe_batch.__doc__ = _transcribe.transcribe_batch.__doc__
 transcribe.transcribe = transcribe
+transcribe.transcribe_batch = transcribe_batch
 _transcribe_module = _types.ModuleType("whisper.transcribe")
 _transcribe_module.transcribe = transcribe
+_transcribe_module.transcribe_batch = transcribe_batch
 _sys.modules[_transcribe_module.__name__] = _transcribe_module
 for _m in (audio, model, timing, tokenizer, decoding):
     _sys.modules[_m.__name__] = _m

@@ -356,6 +356,11 @@ class WhisperAMD:
         from . import transcribe as _t
         return _t.transcribe(self, audio, **kw)
 
+    def transcribe_batch(self, audios, **kw):
+        """transcribe() of several recordings in lock-step, one decode batch per round (transcribe.transcribe_batch)."""
+        from . import transcribe as _t
+        return _t.transcribe_batch(self, audios, **kw)
+
     def get_attentions(self, mel, tokens, max_frames, medfilt_width=7, qk_scale=1.0, n_tok=None, want_logits=True):
         """mel [B,n_mels,3000] f32, tokens [B,n] int64, max_frames list[int] -> (weights [B,L,H,n,F], logits [B,n,V])."""
         mel = mel.to(self.device, torch.float32).contiguous()
@@ -463,6 +468,46 @@ class WhisperAMD:
             pcm.shape[1] if pcm is not None else 0, _lib.i32_array(n_samples) if n_samples is not None else None, B,
             _lib.i32_array(initial_tokens), n_init, sup.ctypes.data_as(C.c_void_p),
             blank.ctypes.data_as(C.c_void_p) if blank is not None else None, C.byref(opts),
+            tokens.ctypes.data_as(_lib._pi32), n_tok.ctypes.data_as(_lib._pi32), lp.ctypes.data_as(_lib._pf),
+            nsp.ctypes.data_as(_lib._pf) if no_speech >= 0 else None))
+        self.last_no_speech_prob = nsp
+        return tokens, n_tok, lp
+
+    def greedy_decode_rows(self, mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask, blank_mask, eot, timestamp_begin,
+                           apply_timestamp_rules=True, max_initial_timestamp_index=50, batch=None, no_speech=-1):
+        """C ABI wca_greedy_decode_rows: greedy_decode with initial tokens, <|sot|> position and sample budget PER ROW (initial_tokens: one
+        token list per row, of any lengths; sot_index, sample_len: one int per row). Returns (tokens [B, T_max] int32 with
+        T_max = max_b(len(initial_tokens[b]) + sample_len[b]), row b left-aligned; n_tokens [B]: row b's sampled tokens are
+        tokens[b, len(initial_tokens[b]) : n_tokens[b]]; sum_logprobs [B]); self.last_no_speech_prob as greedy_decode. The initial
+        tokens always go through the batched prefill; the encoder state stays for a following align_batch(pcm=None, ...)."""
+        self._bind_stream()
+        B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(batch))
+        rows = [[int(t) for t in r] for r in initial_tokens]
+        if not (len(rows) == len(sot_index) == len(sample_len) == B):
+            raise ValueError("initial_tokens, sot_index and sample_len take one entry per batch row (%d)" % B)
+        n_init = [len(r) for r in rows]
+        n_max = max(n_init) if n_init else 0
+        init = np.full((B, max(n_max, 1)), int(eot), dtype=np.int32)
+        for b, r in enumerate(rows):
+            init[b, :len(r)] = r
+        T = max((n + int(sl) for n, sl in zip(n_init, sample_len)), default=1)
+        tokens = np.zeros((B, max(T, 1)), dtype=np.int32)
+        n_tok = np.zeros(B, dtype=np.int32)
+        lp = np.zeros(B, dtype=np.float32)
+        sup = np.ascontiguousarray(suppress_mask, dtype=np.uint8)
+        blank = np.ascontiguousarray(blank_mask, dtype=np.uint8) if blank_mask is not None else None
+        if sup.shape[0] != self.dims.n_vocab or (blank is not None and blank.shape[0] != self.dims.n_vocab):
+            raise ValueError("filter masks must have n_vocab entries")
+        opts = _lib.DecodeOpts(max(int(v) for v in sample_len) if B else 0, int(eot), int(timestamp_begin), 1 if apply_timestamp_rules else 0,
+                               int(max_initial_timestamp_index), int(no_speech))
+        nsp = np.full(B, np.nan, dtype=np.float32)
+        if mel is not None:
+            mel = mel.contiguous().float()
+        _lib.check(self._lib.wca_greedy_decode_rows(
+            self._h, _ptr(mel) if mel is not None else None, _ptr(pcm) if pcm is not None else None,
+            pcm.shape[1] if pcm is not None else 0, _lib.i32_array(n_samples) if n_samples is not None else None, B,
+            init.ctypes.data_as(_lib._pi32), _lib.i32_array(n_init), _lib.i32_array(sot_index), _lib.i32_array(sample_len),
+            sup.ctypes.data_as(C.c_void_p), blank.ctypes.data_as(C.c_void_p) if blank is not None else None, C.byref(opts),
             tokens.ctypes.data_as(_lib._pi32), n_tok.ctypes.data_as(_lib._pi32), lp.ctypes.data_as(_lib._pf),
             nsp.ctypes.data_as(_lib._pf) if no_speech >= 0 else None))
         self.last_no_speech_prob = nsp

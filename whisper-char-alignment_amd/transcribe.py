@@ -17,8 +17,12 @@ Limits (part of the contract):
     sampling, which decoding._check_supported refuses. Without a ladder compression_ratio_threshold / logprob_threshold
     cannot trigger a re-decode: the temperature-0 result is accepted, as upstream accepts the last rung of its ladder.
     language=None (detection) is refused as in decode.
-  * one recording per call, window after window (window k+1 starts where window k ended). Several recordings in lock-step
-    would need per-row prompts in wca_greedy_decode_ex, which takes one initial-token row for the whole batch: not built.
+  * transcribe() takes one recording, window after window (window k+1 starts where window k ended). transcribe_batch() takes
+    several and runs them in lock-step: every round decodes the next window of every unfinished recording in ONE batch
+    (wca_greedy_decode_rows: every row carries its own previous text as the prompt, so the rows sit at different decoder
+    positions), the batch shrinks as recordings end, and with word_timestamps one align_batch(pcm=None) per round aligns the
+    rows that have words. A recording's result is what transcribe() gives for it alone, up to argmax near-ties of the f16
+    logits (the GEMM path, and with it the fp32 summation order, depends on the number of rows in the batch).
   * clip_timestamps, hallucination_silence_threshold, prepend_punctuations / append_punctuations are not built (they
     belong to upstream's own word aligner).
 
@@ -57,6 +61,7 @@ INPUT_STRIDE = 2                                         # mel frames per encode
 TIME_PRECISION = INPUT_STRIDE * HOP_LENGTH / SAMPLE_RATE  # 0.02 s per timestamp token step / encoder frame
 FRAME_SECONDS = HOP_LENGTH / SAMPLE_RATE                  # 0.01 s per mel frame
 MAX_LENGTH = 448                                          # infer_ali.py:26
+PLACEHOLDER_FRAMES = 100                                  # max_frames of a row that rides along in a round's alignment without words
 
 
 def check_supported(temperature, language):
@@ -119,45 +124,87 @@ def split_window(tokens, timestamp_begin, eot, seek, size, result, decode_text):
     return segments, advance, max_frames
 
 
+class SeekState:
+    """One recording's side of whisper.transcribe's loop as a state machine, so that several recordings can share a decode batch:
+        while not st.done:
+            seek, size, prompt = st.request()          # the next window and the prompt tokens it is decoded with
+            pending = st.receive(decoding_result)      # None: the window was skipped (no speech) and the state has advanced
+            if pending is not None:                    # (seek, size, max_frames, segments): align the segments in place, then
+                st.commit(aligned)                     # aligned: bool, or None when no aligner runs
+    seek_loop (one recording) and transcribe_batch (several in lock-step) both drive it."""
+
+    def __init__(self, n_frames, tokenizer, *, initial_prompt_tokens=(), condition_on_previous_text=True, no_speech_threshold=0.6,
+                 logprob_threshold=-1.0, decode_text=None):
+        if decode_text is None:
+            def decode_text(toks):
+                return tokenizer.decode(toks) if getattr(tokenizer, "has_vocab", True) else None
+        self.tokenizer, self.decode_text = tokenizer, decode_text
+        self.condition_on_previous_text = condition_on_previous_text
+        self.no_speech_threshold, self.logprob_threshold = no_speech_threshold, logprob_threshold
+        self.content_frames = n_frames - N_FRAMES
+        self.all_tokens = [int(t) for t in initial_prompt_tokens]
+        self.all_segments, self.windows = [], []
+        self.prompt_reset_since = 0
+        self.without_words = 0
+        self.seek = 0
+        self._pending = None
+
+    @property
+    def done(self):
+        return self.seek >= self.content_frames
+
+    def request(self):
+        size = min(N_FRAMES, self.content_frames - self.seek)
+        return self.seek, size, self.all_tokens[self.prompt_reset_since:]
+
+    def receive(self, result):
+        seek, size, _ = self.request()
+        window = {"seek": seek, "size": size, "advance": size, "skipped": False, "max_frames": None, "aligned": False}
+        self.windows.append(window)
+        if self.no_speech_threshold is not None:
+            should_skip = result.no_speech_prob > self.no_speech_threshold
+            if self.logprob_threshold is not None and result.avg_logprob > self.logprob_threshold:
+                should_skip = False
+            if should_skip:
+                window["skipped"] = True
+                self.seek += size
+                return None
+        segments, advance, max_frames = split_window(result.tokens, self.tokenizer.timestamp_begin, self.tokenizer.eot, seek, size, result,
+                                                     self.decode_text)
+        window["max_frames"], window["advance"] = max_frames, advance
+        self._pending = (window, segments, advance)
+        return seek, size, max_frames, segments
+
+    def commit(self, aligned=None):
+        window, segments, advance = self._pending
+        self._pending = None
+        if aligned is not None:
+            window["aligned"] = bool(aligned)
+            self.without_words += 0 if window["aligned"] else 1
+        self.seek += advance
+        self.all_segments.extend({"id": i, **seg} for i, seg in enumerate(segments, start=len(self.all_segments)))
+        self.all_tokens.extend(t for seg in segments for t in seg["tokens"])
+        if not self.condition_on_previous_text:
+            self.prompt_reset_since = len(self.all_tokens)
+
+    def result(self):
+        return {"segments": self.all_segments, "tokens": self.all_tokens, "windows": self.windows, "windows_without_words": self.without_words}
+
+
 def seek_loop(n_frames, cut_window, decode_window, tokenizer, *, initial_prompt_tokens=(), condition_on_previous_text=True,
               no_speech_threshold=0.6, logprob_threshold=-1.0, align_window=None, decode_text=None):
     """whisper.transcribe's loop over a log-mel of `n_frames` frames (the recording's frames plus 3000 of padding).
     cut_window(seek, size) -> mel window; decode_window(mel_window, prompt_tokens) -> DecodingResult (tokens, avg_logprob,
     no_speech_prob, ...); align_window(seek, size, max_frames, segments) -> bool fills the kept segments' "words" (False: the window
     got none). Returns {"segments", "tokens" (initial prompt included), "windows", "windows_without_words"}."""
-    if decode_text is None:
-        def decode_text(toks):
-            return tokenizer.decode(toks) if getattr(tokenizer, "has_vocab", True) else None
-    content_frames = n_frames - N_FRAMES
-    all_tokens = [int(t) for t in initial_prompt_tokens]
-    all_segments, windows = [], []
-    prompt_reset_since = 0
-    without_words = 0
-    seek = 0
-    while seek < content_frames:
-        size = min(N_FRAMES, content_frames - seek)
-        result = decode_window(cut_window(seek, size), all_tokens[prompt_reset_since:])
-        window = {"seek": seek, "size": size, "advance": size, "skipped": False, "max_frames": None, "aligned": False}
-        windows.append(window)
-        if no_speech_threshold is not None:
-            should_skip = result.no_speech_prob > no_speech_threshold
-            if logprob_threshold is not None and result.avg_logprob > logprob_threshold:
-                should_skip = False
-            if should_skip:
-                window["skipped"] = True
-                seek += size
-                continue
-        segments, advance, max_frames = split_window(result.tokens, tokenizer.timestamp_begin, tokenizer.eot, seek, size, result, decode_text)
-        window["max_frames"], window["advance"] = max_frames, advance
-        if align_window is not None:
-            window["aligned"] = bool(align_window(seek, size, max_frames, segments))
-            without_words += 0 if window["aligned"] else 1
-        seek += advance
-        all_segments.extend({"id": i, **seg} for i, seg in enumerate(segments, start=len(all_segments)))
-        all_tokens.extend(t for seg in segments for t in seg["tokens"])
-        if not condition_on_previous_text:
-            prompt_reset_since = len(all_tokens)
-    return {"segments": all_segments, "tokens": all_tokens, "windows": windows, "windows_without_words": without_words}
+    st = SeekState(n_frames, tokenizer, initial_prompt_tokens=initial_prompt_tokens, condition_on_previous_text=condition_on_previous_text,
+                   no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold, decode_text=decode_text)
+    while not st.done:
+        seek, size, prompt = st.request()
+        pending = st.receive(decode_window(cut_window(seek, size), prompt))
+        if pending is not None:
+            st.commit(align_window(*pending) if align_window is not None else None)
+    return st.result()
 
 
 def attach_words(segments, words):
@@ -184,27 +231,65 @@ def make_aligner(model, tokenizer, *, aligned_unit_type="char", aggr="topk", top
                            medfilt_width=medfilt_width, qk_scale=1.0)
     n_audio_ctx = model.dims.n_audio_ctx
 
-    def align_window(seek, size, max_frames, segments):
+    def prepare(max_frames, segments):
+        """The framed token row the window is aligned with and its text tokens, or None where the window gets no words."""
         text = tokenizer.decode([t for seg in segments for t in seg["tokens"] if t < tokenizer.eot])
         try:
             text_tokens = encode(remove_punctuation(text), tokenizer, aligned_unit_type)
         except Exception:   # a character the byte-level dry-run tokenizer cannot encode
-            return False
+            return None
         tokens = [*tokenizer.sot_sequence, tokenizer.no_timestamps, *text_tokens, tokenizer.eot]
         if not text_tokens or len(tokens) > MAX_LENGTH or not 1 <= max_frames <= n_audio_ctx:
-            return False
-        toks_dev = torch.tensor([tokens], dtype=torch.int64, device=model.device)
-        res = model.align_batch(None, None, toks_dev, [len(tokens)], [max_frames], opts,
-                                token_logprobs_vocab_end=tokenizer.eot if word_confidence else None)
-        words, starts, ends = words_from_jump_frames(res[0][0], text_tokens, tokenizer, aligned_unit_type)
+            return None
+        return tokens, text_tokens
+
+    def attach(seek, segments, text_tokens, jump_row, logprob_row):
+        words, starts, ends = words_from_jump_frames(jump_row, text_tokens, tokenizer, aligned_unit_type)
         if not len(starts):
             return False
-        probs = word_probabilities(res[2][0][:len(text_tokens)], text_tokens, tokenizer, aligned_unit_type) if word_confidence else None
+        probs = word_probabilities(logprob_row[:len(text_tokens)], text_tokens, tokenizer, aligned_unit_type) if word_confidence else None
         offset = seek * FRAME_SECONDS
         attach_words(segments, [{"word": words[i], "start": offset + float(starts[i]), "end": offset + float(ends[i]),
                                  "probability": probs[i] if probs is not None else None} for i in range(len(starts))])
         return True
 
+    def align_window(seek, size, max_frames, segments):
+        prep = prepare(max_frames, segments)
+        if prep is None:
+            return False
+        tokens, text_tokens = prep
+        toks_dev = torch.tensor([tokens], dtype=torch.int64, device=model.device)
+        res = model.align_batch(None, None, toks_dev, [len(tokens)], [max_frames], opts,
+                                token_logprobs_vocab_end=tokenizer.eot if word_confidence else None)
+        return attach(seek, segments, text_tokens, res[0][0], res[2][0] if word_confidence else None)
+
+    def align_round(rows):
+        """rows: one entry per row of the batch the last decode left in the engine, in order: (seek, size, max_frames, segments), or
+        None for a row that was skipped. ONE align_batch(pcm=None) for the rows that have words; a row without (skipped, or refused by
+        `prepare`) rides along as a minimal placeholder row whose output is dropped. Returns one bool per row (None for a skipped row)."""
+        preps = [prepare(r[2], r[3]) if r is not None else None for r in rows]
+        if not any(p is not None for p in preps):
+            return [None if r is None else False for r in rows]   # nothing to align: the next decode drops the state
+        placeholder = [*tokenizer.sot_sequence, tokenizer.no_timestamps, tokenizer.encode(" a")[-1], tokenizer.eot]
+        token_rows = [p[0] if p is not None else placeholder for p in preps]
+        max_frames = [r[2] if p is not None else PLACEHOLDER_FRAMES for r, p in zip(rows, preps)]
+        n_max = max(len(t) for t in token_rows)
+        toks = torch.full((len(rows), n_max), tokenizer.eot, dtype=torch.int64)
+        for b, t in enumerate(token_rows):
+            toks[b, :len(t)] = torch.tensor(t, dtype=torch.int64)
+        res = model.align_batch(None, None, toks.to(model.device), [len(t) for t in token_rows], max_frames, opts,
+                                token_logprobs_vocab_end=tokenizer.eot if word_confidence else None)
+        out = []
+        for b, (r, p) in enumerate(zip(rows, preps)):
+            if r is None:
+                out.append(None)
+            elif p is None:
+                out.append(False)
+            else:
+                out.append(attach(r[0], r[3], p[1], res[0][b][:len(token_rows[b])], res[2][b] if word_confidence else None))
+        return out
+
+    align_window.align_round = align_round
     return align_window
 
 
@@ -268,6 +353,79 @@ def transcribe(model, audio, *, language, initial_prompt=None, condition_on_prev
             "windows_without_words": out["windows_without_words"]}
 
 
+def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_on_previous_text=True, no_speech_threshold=0.6,
+                     logprob_threshold=-1.0, word_timestamps=False, word_confidence=False, aligned_unit_type="char", aggr="topk", topk=10,
+                     medfilt_width=3, vocab_path=None, temperature=0.0, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0, decode_windows=None,
+                     **decode_options):
+    """transcribe() of several recordings in lock-step: a list with transcribe()'s result for every recording of `audios`, in order.
+    Each round cuts the next window of every unfinished recording, decodes them in ONE batch with every row's own previous text as its
+    prompt (decoding.decode with one DecodingOptions per row: wca_greedy_decode_rows) and, with word_timestamps, aligns the rows that
+    have words in one align_batch(pcm=None) on the state that decode left behind. The batch shrinks as recordings end; more recordings
+    than model.max_batch are processed in groups of max_batch. The keyword arguments are transcribe()'s;
+    decode_windows(mel_windows [B, n_mels, 3000], prompts: B token lists) -> B DecodingResults replaces the engine's decode (tests)."""
+    from . import decoding
+    from .tokenizer import get_tokenizer
+    import torch
+    check_supported(temperature, language)
+    if word_confidence and not word_timestamps:
+        raise ValueError("word_confidence is a property of the aligned words: it needs word_timestamps=True")
+    if word_timestamps and vocab_path is None:
+        raise ValueError("word_timestamps aligns the decoded TEXT: pass vocab_path=<local *.tiktoken file>")
+    max_batch = int(getattr(model, "max_batch", 1))
+    if max_batch < 1:
+        raise ValueError("transcribe_batch needs model.max_batch >= 1")
+    tokenizer = get_tokenizer(model.is_multilingual, language=language, task=decode_options.get("task", "transcribe"), vocab_path=vocab_path)
+    prompt_tokens = []
+    if initial_prompt is not None:
+        prompt_tokens = decoding._text_tokens(tokenizer, initial_prompt, decoding.DecodingOptions(vocab_path=vocab_path), "initial_prompt")
+
+    if decode_windows is None:
+        def decode_windows(mel_windows, prompts):
+            def options(prompt):
+                return decoding.DecodingOptions(language=language, temperature=0.0, prompt=list(prompt) or None, vocab_path=vocab_path,
+                                                **decode_options)
+            if len(prompts) == 1:   # a single row left: transcribe()'s own decode call
+                return [decoding.decode(model, mel_windows[0], options(prompts[0]), want_text=vocab_path is not None)]
+            return decoding.decode(model, mel_windows, [options(p) for p in prompts], want_text=vocab_path is not None)
+
+    align = None
+    if word_timestamps:
+        align = make_aligner(model, tokenizer, aligned_unit_type=aligned_unit_type, aggr=aggr, topk=topk, medfilt_width=medfilt_width,
+                             w_colnorm=w_colnorm, w_rownorm=w_rownorm, w_coverage=w_coverage, word_confidence=word_confidence)
+    decode_text = tokenizer.decode if vocab_path is not None else (lambda toks: None)
+    audios = list(audios)
+    results = [None] * len(audios)
+    for g0 in range(0, len(audios), max_batch):
+        group = list(range(g0, min(len(audios), g0 + max_batch)))
+        mels = {i: model.log_mel_long(_as_pcm(audios[i])) for i in group}
+        states = {i: SeekState(mels[i].shape[1], tokenizer, initial_prompt_tokens=prompt_tokens,
+                               condition_on_previous_text=condition_on_previous_text, no_speech_threshold=no_speech_threshold,
+                               logprob_threshold=logprob_threshold, decode_text=decode_text) for i in group}
+        while True:
+            live = [i for i in group if not states[i].done]   # a finished recording is never decoded again
+            if not live:
+                break
+            requests = [states[i].request() for i in live]
+            windows = torch.stack([model.mel_window(mels[i], seek, size) for i, (seek, size, _) in zip(live, requests)])
+            decoded = decode_windows(windows, [prompt for _, _, prompt in requests])
+            pending = [states[i].receive(r) for i, r in zip(live, decoded)]
+            if align is not None and len(live) == 1:
+                aligned = [align(*pending[0]) if pending[0] is not None else None]
+            elif align is not None:
+                aligned = align.align_round(pending)
+            else:
+                aligned = [None] * len(live)
+            for i, pend, al in zip(live, pending, aligned):
+                if pend is not None:
+                    states[i].commit(al)
+        for i in group:
+            out = states[i].result()
+            text = tokenizer.decode(out["tokens"][len(prompt_tokens):]) if vocab_path is not None else ""
+            results[i] = {"text": text, "segments": out["segments"], "language": language, "windows": out["windows"],
+                          "windows_without_words": out["windows_without_words"]}
+    return results
+
+
 # ------------------------------------------------------------------------------------------------ command line
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Long-form transcription with character-aligned word times (one JSON per recording)")
@@ -292,6 +450,7 @@ def parse_args(argv=None):
     p.add_argument("--w_rownorm", type=float, default=1.0)
     p.add_argument("--w_coverage", type=float, default=0.0)
     p.add_argument("--forward_precision", type=str, default="reference", choices=["reference", "split", "f16"])
+    p.add_argument("--batch", type=int, default=1, help="recordings transcribed in lock-step (transcribe_batch; the engine's max_batch)")
     return p.parse_args(argv)
 
 
@@ -310,11 +469,13 @@ def _recordings(args):
 def load_model(args, device="cuda:0"):
     from .engine import WhisperAMD, dims_for
     if args.weights:
-        return WhisperAMD.from_checkpoint(args.weights, device=device, max_batch=1, name=args.model, precision=args.forward_precision)
+        return WhisperAMD.from_checkpoint(args.weights, device=device, max_batch=max(1, args.batch), name=args.model,
+                                          precision=args.forward_precision)
     if args.random_init:
         from .synthetic import random_state_dict
         dims = dims_for(args.model)
-        return WhisperAMD(dims, device=device, max_batch=1, precision=args.forward_precision).load_state_dict(random_state_dict(dims, seed=0))
+        return WhisperAMD(dims, device=device, max_batch=max(1, args.batch),
+                          precision=args.forward_precision).load_state_dict(random_state_dict(dims, seed=0))
     raise SystemExit("no weights: pass --weights /local/path/%s.pt (openai-whisper checkpoint; nothing is downloaded by name) "
                      "or --random_init for a dry run" % args.model)
 
@@ -323,16 +484,27 @@ def main(args, model=None):
     """Writes <output_dir>/<id>.json per recording (transcribe()'s result plus "audio"); returns the paths."""
     if args.word_timestamps and args.vocab is None:
         raise SystemExit("--word_timestamps aligns the decoded text: pass --vocab <local multilingual.tiktoken>")
+    if args.batch < 1:
+        raise SystemExit("--batch must be at least 1")
     if model is None:
         model = load_model(args)
     os.makedirs(args.output_dir, exist_ok=True)
     paths = []
-    for rec_id, path in _recordings(args):
-        result = transcribe(model, path, language=args.language, initial_prompt=args.initial_prompt,
-                            condition_on_previous_text=not args.no_condition_on_previous_text, word_timestamps=args.word_timestamps,
-                            word_confidence=args.word_confidence, aligned_unit_type=args.aligned_unit_type, aggr=args.aggr, topk=args.topk,
-                            medfilt_width=args.medfilt_width, vocab_path=args.vocab, w_colnorm=args.w_colnorm, w_rownorm=args.w_rownorm,
-                            w_coverage=args.w_coverage)
+    kw = dict(language=args.language, initial_prompt=args.initial_prompt, condition_on_previous_text=not args.no_condition_on_previous_text,
+              word_timestamps=args.word_timestamps, word_confidence=args.word_confidence, aligned_unit_type=args.aligned_unit_type,
+              aggr=args.aggr, topk=args.topk, medfilt_width=args.medfilt_width, vocab_path=args.vocab, w_colnorm=args.w_colnorm,
+              w_rownorm=args.w_rownorm, w_coverage=args.w_coverage)
+    recordings = _recordings(args)
+
+    def results():   # one group of --batch recordings at a time: a group's files are written before the next group starts
+        for g0 in range(0, len(recordings), args.batch):
+            group = recordings[g0:g0 + args.batch]
+            if args.batch > 1:
+                yield from zip(group, transcribe_batch(model, [path for _, path in group], **kw))
+            else:
+                yield group[0], transcribe(model, group[0][1], **kw)
+
+    for (rec_id, path), result in results():
         out = os.path.join(args.output_dir, rec_id + ".json")
         with open(out, "w") as f:
             json.dump({"audio": path, **result}, f)
