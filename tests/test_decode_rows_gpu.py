@@ -214,6 +214,17 @@ def test_equal_lengths_give_the_uniform_result(small, tok, mel4):
     _equal_lengths(m, tok, dims, mel4)
 
 
+def test_equal_lengths_give_the_uniform_result_unfused(small, tok, mel4):
+    """The same with set_decode_mode(False, 1): the LayerNorm, the tile GEMM and the K/V append are separate launches, and the
+    per-row loop appends through kv_append_rows where the uniform loop uses kv_append. Still bit for bit."""
+    m, dims = small
+    try:
+        m.set_decode_mode(False, 1)
+        _equal_lengths(m, tok, dims, mel4)
+    finally:
+        m.set_decode_mode(True, 1)
+
+
 @pytest.mark.parametrize("lengths", [(3, 5, 9, 17), (3, 4, 37, 226)], ids=["few-row-prefill", "large-gemm-prefill"])
 def test_ragged_rows_against_each_row_alone(small, tok, mel4, lengths):
     """Rows with different numbers of initial tokens in one batch against the same utterance decoded alone through

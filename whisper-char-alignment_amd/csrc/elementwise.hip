@@ -196,7 +196,7 @@ __global__ __launch_bounds__(256) void embed_kernel(const int64_t* __restrict__ 
   const half_t* e = tok_emb + tok * d;
   const float* p = pos_emb + (long)i * d;
   float* o = x + (long)row * d;
-  if (tok_emb_lo != nullptr) {   // an embedding table that is not exact in f16: value = hi + lo (engine.hip, W_lo slab)
+  if (tok_emb_lo != nullptr) {   // an embedding table that is not exact in f16: value = hi + lo (engine_weights.hip, W_lo slab)
     const half_t* el = tok_emb_lo + tok * d;
     for (int c = threadIdx.x; c < d; c += blockDim.x) o[c] = ((float)e[c] + (float)el[c]) + p[c];
     return;

@@ -1,0 +1,421 @@
+// libwca.so engine, greedy decode: wca_greedy_decode / _ex (every row at the same position, optional batched prefill) and
+// wca_greedy_decode_rows (per-row initial tokens and sample budgets), the two loops and the plumbing they share.
+#include <chrono>
+
+#include "engine_internal.h"
+
+using namespace wca;
+
+namespace {
+
+// What wca_greedy_decode_ex and wca_greedy_decode_rows share around their loops.
+// Phase 1 on `stream` (unless an encoded state is waiting: wca_encode_batch) and the state to decode; the state stays queued for the
+// alignment (wca_align_batch_enqueue with pcm_dev = NULL). A state that was decoded but never aligned is stale once another decode
+// starts (stand-alone whisper.decode use). The autoregressive loop runs on `stream2` (it shares the decoder scratch with phase 2 of
+// the alignment, which is ordered before it on that stream; phase 1 of the NEXT batch may run beside it on `stream`): stream2 is made
+// to wait for the state's cross-K/V here.
+int decode_take_state(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, int batch,
+                      wca_engine::EncState** out) {
+  for (auto it = e->enc_q.begin(); it != e->enc_q.end();) {
+    if (it->decoded) {
+      e->slot_busy[it->slot] = false;
+      it = e->enc_q.erase(it);
+    } else {
+      ++it;
+    }
+  }
+  if (mel_dev != nullptr || pcm_dev != nullptr) {
+    const int rc = wca_encode_batch(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch);
+    if (rc) return rc;
+  }
+  wca_engine::EncState* st = nullptr;
+  for (auto& q : e->enc_q)
+    if (!q.decoded) {
+      st = &q;
+      break;
+    }
+  if (!st || st->batch != batch) return fail(WCA_ERR_STATE, "no encoded batch of %d utterances is waiting to be decoded", batch);
+  HIPCHK(hipStreamWaitEvent(e->stream2, e->ev_kv[st->slot], 0));
+  *out = st;
+  return WCA_OK;
+}
+
+// The token rows, sum_logprob and no_speech_prob of a finished loop to the host. Row b holds n_initial[b] initial tokens and has written
+// positions [0, n_have[b]); n_tokens[b] = its first sampled EOT (or n_have[b]): tokens_out[b][n_initial[b] : n_tokens[b]] are the sampled
+// tokens, and positions never reached hold EOT. Marks the state decoded.
+int decode_read_back(wca_engine* e, hipStream_t s2, wca_engine::EncState* st, int batch, int T_max, int eot, const int32_t* n_initial,
+                     const int32_t* n_have, int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host, float* no_speech_prob_host) {
+  std::vector<int32_t> toks((size_t)batch * T_max);
+  HIPCHK(hipMemcpyAsync(toks.data(), e->dec_tokens.p, sizeof(int) * toks.size(), hipMemcpyDeviceToHost, s2));
+  std::vector<float> lp(2 * (size_t)batch);  // sum_logprob [batch], no_speech_prob [batch] at the head of dec_state
+  HIPCHK(hipMemcpyAsync(lp.data(), e->dec_state.p, sizeof(float) * 2 * batch, hipMemcpyDeviceToHost, s2));
+  HIPCHK(hipStreamSynchronize(s2));
+  for (int b = 0; b < batch; ++b) {
+    int n = n_have[b];
+    for (int i = n_initial[b]; i < n_have[b]; ++i)
+      if (toks[(size_t)b * T_max + i] == eot) {
+        n = i;
+        break;
+      }
+    n_tokens_host[b] = n;
+    for (int i = 0; i < T_max; ++i) tokens_out_host[(size_t)b * T_max + i] = (i < n_have[b]) ? toks[(size_t)b * T_max + i] : eot;
+    if (sum_logprob_host) sum_logprob_host[b] = lp[b];
+    if (no_speech_prob_host) no_speech_prob_host[b] = lp[batch + b];
+  }
+  st->decoded = true;
+  e->last_batch = batch;
+  return WCA_OK;
+}
+
+// What the two loops work on, set up by decode_begin: the state to decode, the device buffers, the select arguments every step starts
+// from and the two half-batches. The batch is decoded as two half-batches on two streams (wca_set_decode_mode, batch >= 16): a step is
+// ~200 dependent launches of 5-10 us plus one HBM-bound cross-attention per layer, and the halves are independent, so one half's small
+// kernels run under the other half's cross-K/V stream. Rows never interact (per-row kernels, per-row cache planes); n_done is an atomic counter.
+struct DecodeLoop {
+  wca_engine* e = nullptr;
+  wca_engine::EncState* st = nullptr;
+  const half_t* kvbuf = nullptr;
+  hipStream_t s2 = nullptr;
+  int batch = 0, T_max = 0, V = 0;
+  bool want_nsp = false;
+  int* tokens_dev = nullptr;
+  float* nsp = nullptr;      // no_speech_prob [batch]
+  int* n_done = nullptr;     // completion counters
+  DecodeSelectArgs sel{};    // whole batch; the per-step fields (cur_len ...) are the caller's
+  int n_half = 1;
+  int hb[3] = {0, 0, 0};     // half h = rows [hb[h], hb[h + 1])
+  hipStream_t hs[2] = {nullptr, nullptr};
+
+  int fork() const {   // stream3 behind what s2 holds
+    if (n_half == 2) {
+      HIPCHK(hipEventRecord(e->ev_fork, s2));
+      HIPCHK(hipStreamWaitEvent(e->stream3, e->ev_fork, 0));
+    }
+    return WCA_OK;
+  }
+  int join() const {   // s2 behind what stream3 holds
+    if (n_half == 2) {
+      HIPCHK(hipEventRecord(e->ev_join, e->stream3));
+      HIPCHK(hipStreamWaitEvent(s2, e->ev_join, 0));
+    }
+    return WCA_OK;
+  }
+  // sel for the rows of half h
+  DecodeSelectArgs sel_half(int h) const {
+    const int b0 = hb[h];
+    DecodeSelectArgs sh = sel;
+    sh.logits = sel.logits + (size_t)b0 * V;
+    sh.tokens = sel.tokens + (size_t)b0 * T_max;
+    sh.sum_logprob = sel.sum_logprob + b0;
+    if (sel.n_initial_rows) sh.n_initial_rows = sel.n_initial_rows + b0;
+    if (sel.cap_rows) sh.cap_rows = sel.cap_rows + b0;
+    return sh;
+  }
+  // whisper's loop ends when every row has produced EOT: the counter of this step, read back (a host sync; the loops ask every 4 steps:
+  // a late stop only costs time, finished rows keep emitting EOT)
+  int all_done(const int* counter, bool* done) const {
+    WCA_TRY(join());
+    HIPCHK(hipMemcpyAsync(e->dec_done_host, counter, sizeof(int), hipMemcpyDeviceToHost, s2));
+    HIPCHK(hipStreamSynchronize(s2));
+    *done = e->dec_done_host[0] >= batch;
+    return WCA_OK;
+  }
+};
+
+// Takes the state to decode (phase 1 first where a mel / PCM is given), sizes the decode buffers, uploads the token rows `init`
+// [batch][T_max], the per-row tables `tab` (nullable -> e->dec_rows) and the masks, zeroes sum_logprob / no_speech_prob and the n_done_len
+// completion counters. logits_rows: 2 = a prefill also leaves the <|sot|> logits (rows [batch, 2 batch)); gather: the prefill's row scratch.
+template <typename Opts>
+int decode_begin(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, int batch, int T_max,
+                 int n_done_len, bool prefill, const std::vector<int32_t>& init, const std::vector<int32_t>* tab, const uint8_t* suppress_mask_host,
+                 const uint8_t* blank_mask_host, const Opts* o, bool nsp_asked, DecodeLoop* out) {
+  const wca_model_dims& D = e->dims;
+  const int V = D.n_vocab, dt = D.n_text_state, L = D.n_text_layer;
+  DecodeLoop& lp = *out;
+  lp.e = e;
+  lp.batch = batch;
+  lp.T_max = T_max;
+  lp.V = V;
+  WCA_TRY(decode_take_state(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, &lp.st));
+  lp.kvbuf = lp.st->slot ? e->kv_alt : e->kv;
+  hipStream_t s2 = lp.s2 = e->stream2;
+  HIPCHK(e->dec_cache.ensure(sizeof(half_t) * (size_t)L * 2 * batch * T_max * dt));
+  HIPCHK(e->dec_tokens.ensure(sizeof(int) * (size_t)batch * T_max));
+  HIPCHK(e->dec_masks.ensure((size_t)2 * V));
+  lp.want_nsp = nsp_asked && o->no_speech >= 0 && o->no_speech < V;
+  // the prefill's logits: rows [0, B) at the last initial position, rows [B, 2B) at <|sot|>
+  HIPCHK(e->dec_logits.ensure(sizeof(float) * (size_t)((prefill && lp.want_nsp) ? 2 : 1) * batch * V));
+  const size_t state_bytes = sizeof(float) * 2 * batch + sizeof(int) * (size_t)n_done_len;
+  HIPCHK(e->dec_state.ensure(state_bytes));
+  if (prefill) HIPCHK(e->dec_gather.ensure(sizeof(float) * 2 * (size_t)batch * dt));
+  if (tab) HIPCHK(e->dec_rows.ensure(sizeof(int) * tab->size()));
+  if (!e->dec_done_host) HIPCHK(hipHostMalloc((void**)&e->dec_done_host, sizeof(int) * 4, hipHostMallocDefault));
+  lp.tokens_dev = (int*)e->dec_tokens.p;
+  unsigned char* masks = (unsigned char*)e->dec_masks.p;
+  float* sum_lp = (float*)e->dec_state.p;
+  lp.nsp = sum_lp + batch;
+  lp.n_done = (int*)((char*)e->dec_state.p + sizeof(float) * 2 * batch);
+  HIPCHK(hipMemcpyAsync(lp.tokens_dev, init.data(), sizeof(int) * init.size(), hipMemcpyHostToDevice, s2));
+  if (tab) HIPCHK(hipMemcpyAsync(e->dec_rows.p, tab->data(), sizeof(int) * tab->size(), hipMemcpyHostToDevice, s2));
+  HIPCHK(hipMemcpyAsync(masks, suppress_mask_host, V, hipMemcpyHostToDevice, s2));
+  if (blank_mask_host) HIPCHK(hipMemcpyAsync(masks + V, blank_mask_host, V, hipMemcpyHostToDevice, s2));
+  HIPCHK(hipMemsetAsync(e->dec_state.p, 0, state_bytes, s2));
+  HIPCHK(hipStreamSynchronize(s2));  // `init` / `tab` are pageable host memory
+  DecodeSelectArgs& sel = lp.sel;
+  sel.logits = (const float*)e->dec_logits.p;
+  sel.ld = V;
+  sel.n_vocab = V;
+  sel.tokens = lp.tokens_dev;
+  sel.T_max = T_max;
+  sel.suppress_mask = masks;
+  sel.blank_mask = blank_mask_host ? masks + V : nullptr;
+  sel.eot = o->eot;
+  sel.timestamp_begin = o->timestamp_begin;
+  sel.apply_timestamp_rules = o->apply_timestamp_rules;
+  sel.max_initial_timestamp_index = o->max_initial_timestamp_index;
+  sel.sum_logprob = sum_lp;
+  sel.n_done = lp.n_done;
+  lp.n_half = (e->dec_streams == 2 && batch >= 16) ? 2 : 1;
+  lp.hb[1] = lp.n_half == 2 ? (batch / 2 + 7) / 8 * 8 : batch;
+  lp.hb[2] = batch;
+  lp.hs[0] = s2;
+  lp.hs[1] = e->stream3;
+  return WCA_OK;
+}
+
+// one position of every row through the decoder, the halves enqueued layer by layer in turn (run_decode_step)
+int decode_step(const DecodeLoop& lp, int t, bool want_logits, const int* pos_rows, const int* nk_rows) {
+  const int L = lp.e->dims.n_text_layer;
+  for (int phase = -1; phase <= L; ++phase)
+    for (int h = 0; h < lp.n_half; ++h)
+      WCA_TRY(run_decode_step(lp.e, lp.hs[h], h, lp.kvbuf, lp.tokens_dev, lp.hb[h], lp.hb[h + 1] - lp.hb[h], lp.batch, t, lp.T_max, want_logits, phase,
+                              pos_rows ? pos_rows + lp.hb[h] : nullptr, nk_rows ? nk_rows + lp.hb[h] : nullptr));
+  return WCA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wca_greedy_decode(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
+                      int batch, const int32_t* initial_tokens_host, int n_initial, const uint8_t* suppress_mask_host,
+                      const uint8_t* blank_mask_host, const wca_decode_opts* o, int32_t* tokens_out_host, int32_t* n_tokens_host,
+                      float* sum_logprob_host, float* no_speech_prob_host) {
+  if (!e) return fail(WCA_ERR_INVALID, "null engine");
+  if (!o) return fail(WCA_ERR_INVALID, "null argument");
+  if (n_initial + o->sample_len > e->dims.n_text_ctx)
+    return fail(WCA_ERR_TOO_LONG, "n_initial %d + sample_len %d exceeds n_text_ctx %d", n_initial, o->sample_len, e->dims.n_text_ctx);
+  wca_decode_opts_ex x{};
+  x.sample_len = o->sample_len;
+  x.eot = o->eot;
+  x.timestamp_begin = o->timestamp_begin;
+  x.apply_timestamp_rules = o->apply_timestamp_rules;
+  x.max_initial_timestamp_index = o->max_initial_timestamp_index;
+  x.no_speech = o->no_speech;
+  x.sot_index = 0;
+  x.prefill = 0;
+  return wca_greedy_decode_ex(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, initial_tokens_host, n_initial, suppress_mask_host,
+                              blank_mask_host, &x, tokens_out_host, n_tokens_host, sum_logprob_host, no_speech_prob_host);
+}
+
+int wca_greedy_decode_ex(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
+                         int batch, const int32_t* initial_tokens_host, int n_initial, const uint8_t* suppress_mask_host,
+                         const uint8_t* blank_mask_host, const wca_decode_opts_ex* o, int32_t* tokens_out_host, int32_t* n_tokens_host,
+                         float* sum_logprob_host, float* no_speech_prob_host) {
+  int rc = check_ready(e);
+  if (rc) return rc;
+  if (mel_dev != nullptr && pcm_dev != nullptr) return fail(WCA_ERR_INVALID, "pass at most one of mel_dev / pcm_dev");
+  if (!initial_tokens_host || !suppress_mask_host || !o || !tokens_out_host || !n_tokens_host) return fail(WCA_ERR_INVALID, "null argument");
+  if (pcm_dev && !n_samples_host) return fail(WCA_ERR_INVALID, "null argument");
+  if (batch < 1 || batch > e->max_batch) return fail(WCA_ERR_INVALID, "batch %d outside [1,%d]", batch, e->max_batch);
+  const wca_model_dims& D = e->dims;
+  // upstream samples until the sequence is longer than n_ctx: the (n_text_ctx + 1)-th token is sampled, never embedded
+  if (n_initial < 1 || o->sample_len < 1 || n_initial > D.n_text_ctx || n_initial + o->sample_len > D.n_text_ctx + 1)
+    return fail(WCA_ERR_TOO_LONG, "n_initial %d + sample_len %d exceeds n_text_ctx + 1 = %d (or n_initial exceeds n_text_ctx)", n_initial,
+                o->sample_len, D.n_text_ctx + 1);
+  if (o->sot_index < 0 || o->sot_index >= n_initial) return fail(WCA_ERR_INVALID, "sot_index %d outside [0,%d)", o->sot_index, n_initial);
+  if (o->prefill != 0 && o->prefill != 1) return fail(WCA_ERR_INVALID, "prefill must be 0 or 1");
+  if (o->eot < 0 || o->eot >= D.n_vocab || o->timestamp_begin < 0 || o->timestamp_begin > D.n_vocab)
+    return fail(WCA_ERR_INVALID, "eot / timestamp_begin outside the vocabulary");
+  for (int i = 0; i < n_initial; ++i)
+    if (initial_tokens_host[i] < 0 || initial_tokens_host[i] >= D.n_vocab) return fail(WCA_ERR_INVALID, "initial token %d outside the vocabulary", i);
+  const int V = D.n_vocab;
+  const int T_max = n_initial + o->sample_len;
+  const bool prefill = o->prefill == 1;
+  std::vector<int32_t> init((size_t)batch * T_max, o->eot);
+  for (int b = 0; b < batch; ++b)
+    for (int i = 0; i < n_initial; ++i) init[(size_t)b * T_max + i] = initial_tokens_host[i];
+  DecodeLoop lp;
+  if ((rc = decode_begin(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, T_max, T_max, prefill, init, nullptr, suppress_mask_host,
+                         blank_mask_host, o, no_speech_prob_host != nullptr, &lp)))
+    return rc;
+  lp.sel.n_initial = n_initial;
+  hipStream_t s2 = lp.s2;
+  const bool want_nsp = lp.want_nsp;
+  // prefill = 0: the initial tokens are fed one position at a time (the plain start is 3 tokens: sot, language, task);
+  // prefill = 1: one batched forward over all of them on s2 for the whole batch (run_decode_prefill), its first choice made
+  // there too, and the step loop (forked only then) continues at t = n_initial. Sampling starts after the last initial token.
+  if (!prefill && (rc = lp.fork())) return rc;
+  int steps = 0, step_positions = 0;
+  static const bool dbg_host = std::getenv("WCA_DEC_DEBUG") != nullptr;   // (read once)
+  double host_us = 0.0;
+  for (int t = prefill ? n_initial - 1 : 0; t < T_max - 1; ++t) {
+    const bool sample = (t >= n_initial - 1);
+    const bool sot_logits = (t == o->sot_index && want_nsp);  // probs_at_sot of DecodingTask._main_loop
+    const auto h0 = std::chrono::steady_clock::now();
+    if (prefill && t == n_initial - 1) {
+      rc = run_decode_prefill(e, s2, lp.kvbuf, lp.tokens_dev, batch, n_initial, T_max, want_nsp ? o->sot_index : -1);
+      if (rc) return rc;
+      if (want_nsp) HIPCHK(launch_token_prob((const float*)e->dec_logits.p + (size_t)batch * V, V, V, o->no_speech, lp.nsp, batch, s2));
+      DecodeSelectArgs sh = lp.sel;
+      sh.cur_len = n_initial;
+      HIPCHK(launch_decode_select(sh, batch, s2));
+      if ((rc = lp.fork())) return rc;
+    } else {
+      ++step_positions;
+      if ((rc = decode_step(lp, t, sample || sot_logits, nullptr, nullptr))) return rc;
+      for (int h = 0; h < lp.n_half; ++h) {
+        const int b0 = lp.hb[h], nb = lp.hb[h + 1] - lp.hb[h];
+        if (sot_logits) HIPCHK(launch_token_prob((const float*)e->dec_logits.p + (size_t)b0 * V, V, V, o->no_speech, lp.nsp + b0, nb, lp.hs[h]));
+        if (!sample) continue;
+        DecodeSelectArgs sh = lp.sel_half(h);
+        sh.cur_len = t + 1;
+        HIPCHK(launch_decode_select(sh, nb, lp.hs[h]));
+      }
+    }
+    if (dbg_host) host_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();
+    if (!sample) continue;
+    ++steps;
+    // the loop ends when every row has produced EOT (checked every 4 steps) or after sample_len steps
+    if ((steps & 3) == 0 || steps == o->sample_len) {
+      bool done = false;
+      if ((rc = lp.all_done(lp.n_done + t + 1, &done))) return rc;
+      if (done) break;
+    }
+    if (steps >= o->sample_len) break;
+  }
+  if ((rc = lp.join())) return rc;
+  if (dbg_host) fprintf(stderr, "[wca] greedy decode: host enqueue time %.1f us per position (%d halves)\n", host_us / (steps + n_initial - 1), lp.n_half);
+  std::vector<int32_t> ni_rows(batch, n_initial), have_rows(batch, n_initial + steps);  // positions written so far
+  if ((rc = decode_read_back(e, s2, lp.st, batch, T_max, o->eot, ni_rows.data(), have_rows.data(), tokens_out_host, n_tokens_host, sum_logprob_host,
+                             want_nsp ? no_speech_prob_host : nullptr)))
+    return rc;
+  e->dec_prefill_positions = prefill ? n_initial : 0;
+  e->dec_step_positions = step_positions;
+  return WCA_OK;
+}
+
+// Greedy decode of a batch whose rows carry initial tokens of their own (transcribe_batch: every recording's prompt is its own previous
+// text). Row b holds n_initial[b] tokens and samples at most sample_len[b]; at loop step s (0 = the prefill's choice) it is at
+// cur_len = n_initial[b] + s. Prefill: every row padded with eot to n_max = max n_initial (a valid query never sees a later position,
+// and the K/V that the pad positions leave in cache slots >= n_initial[b] are overwritten by the step loop before they are read);
+// steps: the per-row forms of embed_step / KV append / one-query attention / decode_select, fed from small device tables built here.
+// A row past its budget keeps going through the kernels as a finished row at a clamped position (<= T_max - 2, so no positional row
+// past n_text_ctx - 1 and no cache slot past T_max - 1 is touched); what it computes is never read.
+int wca_greedy_decode_rows(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
+                           int batch, const int32_t* initial_tokens_host, const int32_t* n_initial_host, const int32_t* sot_index_host,
+                           const int32_t* sample_len_host, const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host,
+                           const wca_decode_opts* o, int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
+                           float* no_speech_prob_host) {
+  int rc = check_ready(e);
+  if (rc) return rc;
+  if (mel_dev != nullptr && pcm_dev != nullptr) return fail(WCA_ERR_INVALID, "pass at most one of mel_dev / pcm_dev");
+  if (!initial_tokens_host || !n_initial_host || !sot_index_host || !sample_len_host || !suppress_mask_host || !o || !tokens_out_host ||
+      !n_tokens_host)
+    return fail(WCA_ERR_INVALID, "null argument");
+  if (pcm_dev && !n_samples_host) return fail(WCA_ERR_INVALID, "null argument");
+  if (batch < 1 || batch > e->max_batch) return fail(WCA_ERR_INVALID, "batch %d outside [1,%d]", batch, e->max_batch);
+  const wca_model_dims& D = e->dims;
+  if (o->eot < 0 || o->eot >= D.n_vocab || o->timestamp_begin < 0 || o->timestamp_begin > D.n_vocab)
+    return fail(WCA_ERR_INVALID, "eot / timestamp_begin outside the vocabulary");
+  int n_max = 0, T_max = 0, S = 0;
+  for (int b = 0; b < batch; ++b) {
+    const int ni = n_initial_host[b], sl = sample_len_host[b];
+    if (ni < 1 || sl < 1 || ni > D.n_text_ctx || ni + sl > D.n_text_ctx + 1)
+      return fail(WCA_ERR_TOO_LONG, "row %d: n_initial %d + sample_len %d exceeds n_text_ctx + 1 = %d (or n_initial exceeds n_text_ctx)", b, ni, sl,
+                  D.n_text_ctx + 1);
+    if (sot_index_host[b] < 0 || sot_index_host[b] >= ni) return fail(WCA_ERR_INVALID, "row %d: sot_index %d outside [0,%d)", b, sot_index_host[b], ni);
+    n_max = std::max(n_max, ni);
+    T_max = std::max(T_max, ni + sl);
+    S = std::max(S, sl);
+  }
+  for (int b = 0; b < batch; ++b)
+    for (int i = 0; i < n_initial_host[b]; ++i) {
+      const int32_t tk = initial_tokens_host[(size_t)b * n_max + i];
+      if (tk < 0 || tk >= D.n_vocab) return fail(WCA_ERR_INVALID, "row %d: initial token %d outside the vocabulary", b, i);
+    }
+  const int V = D.n_vocab;
+  std::vector<int32_t> init((size_t)batch * T_max, o->eot);
+  for (int b = 0; b < batch; ++b)
+    for (int i = 0; i < n_initial_host[b]; ++i) init[(size_t)b * T_max + i] = initial_tokens_host[(size_t)b * n_max + i];
+  // the int tables: [0] n_initial - 1, [1] sot_index, [2] n_initial, [3] sample cap; then per step s in [0, S): fed position
+  // min(n_initial + s - 1, T_max - 2), key count = fed position + 1, cur_len = n_initial + s  ([batch] each)
+  std::vector<int32_t> tab((size_t)(4 + 3 * S) * batch);
+  for (int b = 0; b < batch; ++b) {
+    const int ni = n_initial_host[b];
+    tab[0 * (size_t)batch + b] = ni - 1;
+    tab[1 * (size_t)batch + b] = sot_index_host[b];
+    tab[2 * (size_t)batch + b] = ni;
+    tab[3 * (size_t)batch + b] = sample_len_host[b];
+    for (int s = 0; s < S; ++s) {
+      const int pos = std::max(0, std::min(ni + s - 1, T_max - 2));
+      tab[(size_t)(4 + 3 * s + 0) * batch + b] = pos;
+      tab[(size_t)(4 + 3 * s + 1) * batch + b] = pos + 1;
+      tab[(size_t)(4 + 3 * s + 2) * batch + b] = ni + s;
+    }
+  }
+  DecodeLoop lp;
+  if ((rc = decode_begin(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, T_max, S, true, init, &tab, suppress_mask_host, blank_mask_host, o,
+                         no_speech_prob_host != nullptr, &lp)))
+    return rc;
+  const int* tab_dev = (const int*)e->dec_rows.p;
+  lp.sel.n_initial_rows = tab_dev + 2 * (size_t)batch;
+  lp.sel.cap_rows = tab_dev + 3 * (size_t)batch;
+  hipStream_t s2 = lp.s2;
+  const bool want_nsp = lp.want_nsp;
+  // ---- step 0: the prefill on s2 for the whole batch, and its choice
+  rc = run_decode_prefill(e, s2, lp.kvbuf, lp.tokens_dev, batch, n_max, T_max, -1, tab_dev, want_nsp ? tab_dev + batch : nullptr);
+  if (rc) return rc;
+  if (want_nsp) HIPCHK(launch_token_prob((const float*)e->dec_logits.p + (size_t)batch * V, V, V, o->no_speech, lp.nsp, batch, s2));
+  {
+    DecodeSelectArgs sh = lp.sel;
+    sh.cur_len_rows = tab_dev + (size_t)(4 + 2) * batch;
+    sh.n_done_idx = 0;
+    HIPCHK(launch_decode_select_rows(sh, batch, s2));
+  }
+  if ((rc = lp.fork())) return rc;
+  int steps = 1, step_positions = 0;
+  bool all_done = false;
+  for (int s = 1; s < S && !all_done; ++s) {
+    const int* row = tab_dev + (size_t)(4 + 3 * s) * batch;
+    ++step_positions;
+    if ((rc = decode_step(lp, 0, true, row, row + batch))) return rc;
+    for (int h = 0; h < lp.n_half; ++h) {
+      DecodeSelectArgs sh = lp.sel_half(h);
+      sh.cur_len_rows = row + 2 * (size_t)batch + lp.hb[h];
+      sh.n_done_idx = s;
+      HIPCHK(launch_decode_select_rows(sh, lp.hb[h + 1] - lp.hb[h], lp.hs[h]));
+    }
+    ++steps;
+    // every row has produced EOT or used its budget (checked every 4 steps, as in wca_greedy_decode_ex)
+    if ((steps & 3) == 0 && steps < S && (rc = lp.all_done(lp.n_done + s, &all_done))) return rc;
+  }
+  if ((rc = lp.join())) return rc;
+  std::vector<int32_t> have_rows(batch);
+  for (int b = 0; b < batch; ++b) have_rows[b] = n_initial_host[b] + std::min(steps, (int)sample_len_host[b]);  // positions row b has written
+  if ((rc = decode_read_back(e, s2, lp.st, batch, T_max, o->eot, n_initial_host, have_rows.data(), tokens_out_host, n_tokens_host, sum_logprob_host,
+                             want_nsp ? no_speech_prob_host : nullptr)))
+    return rc;
+  e->dec_prefill_positions = n_max;
+  e->dec_step_positions = step_positions;
+  return WCA_OK;
+}
+
+int wca_last_decode_positions(wca_engine* e, int32_t* prefill_positions, int32_t* step_positions) {
+  if (!e || !prefill_positions || !step_positions) return fail(WCA_ERR_INVALID, "null argument");
+  *prefill_positions = e->dec_prefill_positions;
+  *step_positions = e->dec_step_positions;
+  return WCA_OK;
+}
+
+}  // extern "C"

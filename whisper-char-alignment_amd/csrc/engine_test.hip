@@ -1,0 +1,313 @@
+// libwca.so engine, kernel-level test entry points (wca_test_*): single kernels and the encoder alone, for tests/ and tools/.
+#include "engine_internal.h"
+
+using namespace wca;
+
+namespace {
+
+// out[r][c] = hi + lo of a split row [hi(d) | lo(d)]
+__global__ void widen_split_kernel(const half_t* __restrict__ in, float* __restrict__ out, size_t rows, int d) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t st = (size_t)gridDim.x * blockDim.x;
+  for (; i < rows * d; i += st) {
+    const size_t r = i / d, c = i - r * d;
+    out[i] = (float)in[r * 2 * d + c] + (float)in[r * 2 * d + d + c];
+  }
+}
+
+__global__ void widen_kernel(const half_t* __restrict__ in, float* __restrict__ out, size_t n) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t st = (size_t)gridDim.x * blockDim.x;
+  for (; i < n; i += st) out[i] = (float)in[i];
+}
+
+// dense q / o [B][nq][w], k / v [B][nk][w] with rows of w elements (H * 64, or twice that for [hi | lo] pairs)
+AttnArgs dense_attn(const void* q, const void* k, const void* v, void* o, int w, int B, int H, int nq, int nk, int causal) {
+  AttnArgs a{};
+  a.Q = (const half_t*)q;
+  a.K = (const half_t*)k;
+  a.V = (const half_t*)v;
+  a.O = (half_t*)o;
+  a.q_bs = a.o_bs = (long)nq * w;
+  a.k_bs = a.v_bs = (long)nk * w;
+  a.q_rs = a.k_rs = a.v_rs = a.o_rs = w;
+  a.nq = nq;
+  a.nk = nk;
+  a.H = H;
+  a.B = B;
+  a.scale = 0.125f;
+  a.causal = causal & 1;
+  return a;
+}
+
+// what both forms of decode_select take
+DecodeSelectArgs select_args(const float* logits_dev, int n_vocab, int32_t* tokens_dev, int T_max, const uint8_t* suppress_mask_dev,
+                             const uint8_t* blank_mask_dev, const wca_decode_opts* o, float* sum_logprob_dev, int32_t* n_done_dev) {
+  DecodeSelectArgs a{};
+  a.logits = logits_dev;
+  a.ld = n_vocab;
+  a.n_vocab = n_vocab;
+  a.tokens = tokens_dev;
+  a.T_max = T_max;
+  a.suppress_mask = suppress_mask_dev;
+  a.blank_mask = blank_mask_dev;
+  a.eot = o->eot;
+  a.timestamp_begin = o->timestamp_begin;
+  a.apply_timestamp_rules = o->apply_timestamp_rules;
+  a.max_initial_timestamp_index = o->max_initial_timestamp_index;
+  a.sum_logprob = sum_logprob_dev;
+  a.n_done = n_done_dev;
+  return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wca_test_gemm(wca_engine* e, const void* a, const void* w, const float* bias, void* c, int M, int N, int K, int gelu, int out_mode) {
+  if (!e) return fail(WCA_ERR_INVALID, "null engine");
+  HIPCHK(hipSetDevice(e->device));
+  GemmArgs g = flat((const half_t*)a, K, (const half_t*)w, K, c, N, M, N, K);
+  g.bias = bias;
+  g.gelu = gelu;
+  g.out_mode = out_mode & 0xff;
+  if (g.out_mode == 4) {  // f16 pair output: c [M][2N], hi at column n, lo at column N + n
+    g.ldc = 2 * N;
+    g.c_lo = N;
+  }
+  g.force_tile = (out_mode >> 8) & 0xfff;  // 0 auto / 128 / 256 / 257 (persistent) / 258 (one tile per workgroup)
+  g.supertile = out_mode >> 20;             // 0 = launch_gemm's choice (tools: tile-order experiments)
+  g.sk_part = e->sk_big[0];                  // few tiles, K >= 2048, out_mode 2: split-K with the engine's workspace, as the encoder does
+  g.sk_bytes = e->sk_big_bytes;
+  HIPCHK(launch_gemm(g, e->stream));
+  return WCA_OK;
+}
+
+int wca_test_gemm_pairs(wca_engine* e, const void* a2, const void* w, const float* bias, void* c, int M, int N, int K, int gelu, int out_mode) {
+  if (!e || !a2 || !w || !c) return fail(WCA_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(e->device));
+  const int om = out_mode & 0xff;
+  if (!gemm_splitw_supported(M, N, K, 2 * K, om)) return fail(WCA_ERR_INVALID, "the pair-operand kernel does not take M=%d N=%d K=%d out_mode %d", M, N, K, om);
+  GemmArgs g = flat((const half_t*)a2, 2 * K, (const half_t*)w, K, c, N, M, N, K);
+  g.a_lo = K;
+  g.bias = bias;
+  g.gelu = gelu;
+  g.out_mode = om;
+  if (om == 4) {
+    g.ldc = 2 * N;
+    g.c_lo = N;
+  }
+  g.force_tile = (out_mode >> 8) & 0xfff;
+  g.site = 1;
+  HIPCHK(launch_gemm(g, e->stream));
+  return WCA_OK;
+}
+
+int wca_test_gemm_ln(wca_engine* e, const void* a, const void* w, const float* bias, float* x, const float* gamma, const float* beta,
+                     void* xn, int M, int N, int K, int site) {
+  if (!e || !a || !w || !x || !gamma || !beta || !xn) return fail(WCA_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(e->device));
+  if (!gemm_ln_supported(M, N, K, e->n_cu)) return fail(WCA_ERR_INVALID, "residual + LayerNorm epilogue not available for M=%d N=%d K=%d", M, N, K);
+  const size_t mpad = align_up((size_t)M, 256);
+  HIPCHK(e->tmp0.ensure(sizeof(unsigned long long) * (size_t)(N / 256) * mpad));
+  HIPCHK(e->tmp1.ensure(sizeof(unsigned) * (mpad / 256 + 16)));
+  HIPCHK(hipMemsetAsync(e->err_dev, 0, sizeof(int), e->stream));
+  GemmArgs g = flat((const half_t*)a, K, (const half_t*)w, K, x, N, M, N, K);
+  g.bias = bias;
+  g.out_mode = 3;
+  g.site = site;
+  g.ln_gamma = gamma;
+  g.ln_beta = beta;
+  g.ln_out = (half_t*)xn;
+  g.ln_ld = N;
+  g.ln_eps = 1e-5f;
+  g.ln_stats = (unsigned long long*)e->tmp0.p;
+  g.ln_cnt = (unsigned*)e->tmp1.p;
+  g.ln_err = e->err_dev;
+  HIPCHK(launch_gemm(g, e->stream));
+  HIPCHK(hipMemcpyAsync(e->err_host, e->err_dev, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  if (e->err_host[0] & 2) return fail(WCA_ERR_HIP, "LayerNorm statistics hand-off timed out");
+  return WCA_OK;
+}
+
+int wca_test_gemm_rows(wca_engine* e, const void* a_f16, const float* x_f32, const float* gamma, const float* beta, const void* w,
+                       const float* bias, void* c, int M, int N, int K, int gelu, int out_mode, int splitk, int groups, void* kv_k, void* kv_v,
+                       int T_max, int kv_t) {
+  if (!e || !w || !c || (!a_f16 && !x_f32) || (x_f32 && (!gamma || !beta))) return fail(WCA_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(e->device));
+  if (splitk <= 0) splitk = gemm_rows_pick_splitk(K);
+  if (splitk <= 0) return fail(WCA_ERR_INVALID, "no split of K=%d fits the few-row kernel", K);
+  const size_t tiles = (size_t)((M + 63) / 64) * ((N + 15) / 16);
+  if (splitk > 1) {
+    HIPCHK(e->tmp0.ensure(gemm_rows_workspace_bytes(M, N, splitk)));
+    HIPCHK(e->tmp1.ensure(sizeof(unsigned) * tiles));
+    HIPCHK(hipMemsetAsync(e->tmp1.p, 0, sizeof(unsigned) * tiles, e->stream));
+  }
+  GemmArgs g = flat((const half_t*)a_f16, K, (const half_t*)w, K, c, N, M, N, K);
+  g.A32 = x_f32;
+  g.lda32 = K;
+  g.ln_gamma = gamma;
+  g.ln_beta = beta;
+  g.ln_eps = 1e-5f;
+  g.bias = bias;
+  g.gelu = gelu;
+  g.out_mode = out_mode;
+  g.splitk = splitk;
+  g.groups = groups;
+  g.sk_part = (float*)e->tmp0.p;
+  g.sk_cnt = (unsigned*)e->tmp1.p;
+  g.kv_k = (half_t*)kv_k;
+  g.kv_v = (half_t*)kv_v;
+  g.kv_bs = (long)T_max * (N / 3);
+  g.kv_t = kv_t;
+  g.kv_d = kv_k ? N / 3 : 0;
+  HIPCHK(launch_gemm_rows(g, e->stream));
+  if (splitk > 1) {
+    // the counters must be back at zero (self-cleaning): a second launch on the same workspace has to give the same result
+    std::vector<unsigned> cnt(tiles);
+    HIPCHK(hipMemcpyAsync(cnt.data(), e->tmp1.p, sizeof(unsigned) * tiles, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (unsigned v : cnt)
+      if (v != 0) return fail(WCA_ERR_HIP, "split-K arrival counter left at %u", v);
+  }
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return WCA_OK;
+}
+
+int wca_test_set_attn_split_drop(int mask) {
+  if (mask != 0 && mask != 1 && mask != 2 && mask != 3 && mask != 4 && mask != 8 && mask != 9 && mask != 12 && mask != 15)
+    return fail(WCA_ERR_INVALID, "attention pass mask %d is not instantiated", mask);
+  set_debug_switch("attn_split_drop", mask);
+  return WCA_OK;
+}
+
+int wca_test_set_switch(const char* name, int value) {
+  if (!name) return fail(WCA_ERR_INVALID, "null argument");
+  if (set_debug_switch(name, value) != 0) return fail(WCA_ERR_INVALID, "unknown switch %s", name);
+  return WCA_OK;
+}
+
+int wca_test_last_scores(wca_engine* e, int batch, float* scores_host) {
+  if (!e || !scores_host) return fail(WCA_ERR_INVALID, "null argument");
+  if (e->enq_count != e->fetch_count) return fail(WCA_ERR_STATE, "fetch the batches in flight first");
+  HIPCHK(hipSetDevice(e->device));
+  const size_t n = (size_t)batch * e->dims.n_text_layer * e->dims.n_text_head;
+  if (batch < 1 || e->scores.bytes < n * sizeof(float)) return fail(WCA_ERR_INVALID, "no head scores of a batch of %d are held", batch);
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream2));
+  HIPCHK(hipMemcpy(scores_host, e->scores.p, n * sizeof(float), hipMemcpyDeviceToHost));
+  return WCA_OK;
+}
+
+int wca_test_attention(wca_engine* e, const void* q, const void* k, const void* v, void* o, float* cap_dev, int cap_ld, int cap_cols,
+                       int B, int H, int nq, int nk, int causal) {
+  if (!e) return fail(WCA_ERR_INVALID, "null engine");
+  const int variant = (causal >> 8) & 3;  // 0 auto, 1 the 16x16x32 kernel, 2 the 32x32x16 kernel (attention.hip)
+  if (variant == 3) return fail(WCA_ERR_INVALID, "attention variant 3 does not exist");
+  HIPCHK(hipSetDevice(e->device));
+  AttnArgs a = dense_attn(q, k, v, o, H * 64, B, H, nq, nk, causal);
+  a.cap = cap_dev;
+  a.cap_bs = (long)H * nq * cap_ld;
+  a.cap_hs = (long)nq * cap_ld;
+  a.cap_ld = cap_ld;
+  a.cap_cols = cap_cols;
+  a.variant = variant;
+  HIPCHK(launch_attention(a, e->stream));
+  return WCA_OK;
+}
+
+int wca_test_attention_split(wca_engine* e, const void* q2, const void* k2, const void* v2, void* o2, float* cap_dev, int cap_ld, int cap_cols,
+                             int B, int H, int nq, int nk, int causal) {
+  if (!e || !q2 || !k2 || !v2 || !o2) return fail(WCA_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(e->device));
+  AttnArgs a = dense_attn(q2, k2, v2, o2, 2 * H * 64, B, H, nq, nk, causal);
+  a.split = 1;
+  a.q_lo = a.k_lo = a.v_lo = a.o_lo = H * 64;
+  a.cap = cap_dev;
+  a.cap_bs = (long)H * nq * cap_ld;
+  a.cap_hs = (long)nq * cap_ld;
+  a.cap_ld = cap_ld;
+  a.cap_cols = cap_cols;
+  HIPCHK(launch_attention(a, e->stream));
+  return WCA_OK;
+}
+
+int wca_test_decode_select(wca_engine* e, const float* logits_dev, int batch, int n_vocab, int32_t* tokens_dev, int T_max, int cur_len,
+                           int n_initial, const uint8_t* suppress_mask_dev, const uint8_t* blank_mask_dev, const wca_decode_opts* o,
+                           float* sum_logprob_dev, int32_t* n_done_dev) {
+  if (!e || !logits_dev || !tokens_dev || !suppress_mask_dev || !o || !sum_logprob_dev || !n_done_dev) return fail(WCA_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(e->device));
+  DecodeSelectArgs a = select_args(logits_dev, n_vocab, tokens_dev, T_max, suppress_mask_dev, blank_mask_dev, o, sum_logprob_dev, n_done_dev);
+  a.cur_len = cur_len;
+  a.n_initial = n_initial;
+  HIPCHK(launch_decode_select(a, batch, e->stream));
+  return WCA_OK;
+}
+
+int wca_test_decode_select_rows(wca_engine* e, const float* logits_dev, int batch, int n_vocab, int32_t* tokens_dev, int T_max,
+                                const int32_t* cur_len_dev, const int32_t* n_initial_dev, const int32_t* cap_dev, int n_done_idx, int n_done_len,
+                                const uint8_t* suppress_mask_dev, const uint8_t* blank_mask_dev, const wca_decode_opts* o, float* sum_logprob_dev,
+                                int32_t* n_done_dev) {
+  if (!e || !logits_dev || !tokens_dev || !cur_len_dev || !n_initial_dev || !cap_dev || !suppress_mask_dev || !o || !sum_logprob_dev || !n_done_dev)
+    return fail(WCA_ERR_INVALID, "null argument");
+  if (batch < 1 || n_vocab < 1 || T_max < 2 || n_done_idx < 0 || n_done_idx >= n_done_len) return fail(WCA_ERR_INVALID, "bad shape");
+  if (o->eot < 0 || o->eot >= n_vocab || o->timestamp_begin < 0 || o->timestamp_begin > n_vocab)
+    return fail(WCA_ERR_INVALID, "eot / timestamp_begin outside the vocabulary");
+  HIPCHK(hipSetDevice(e->device));
+  DecodeSelectArgs a = select_args(logits_dev, n_vocab, tokens_dev, T_max, suppress_mask_dev, blank_mask_dev, o, sum_logprob_dev, n_done_dev);
+  a.cur_len_rows = cur_len_dev;
+  a.n_initial_rows = n_initial_dev;
+  a.cap_rows = cap_dev;
+  a.n_done_idx = n_done_idx;
+  HIPCHK(launch_decode_select_rows(a, batch, e->stream));
+  return WCA_OK;
+}
+
+int wca_test_attention_rows(wca_engine* e, const void* q, const void* k, const void* v, void* o, int B, int H, int nq, int nk,
+                            const int32_t* nk_rows_dev, int causal) {
+  if (!e || !q || !k || !v || !o || !nk_rows_dev) return fail(WCA_ERR_INVALID, "null argument");
+  if (B < 1 || H < 1 || nq < 1 || nk < 1) return fail(WCA_ERR_INVALID, "bad shape");
+  HIPCHK(hipSetDevice(e->device));
+  AttnArgs a = dense_attn(q, k, v, o, H * 64, B, H, nq, nk, causal);
+  a.nk_rows = nk_rows_dev;
+  if (launch_attention(a, e->stream) != hipSuccess)
+    return fail(WCA_ERR_INVALID, "per-row key counts are taken by the one-query f16 attention only (nq = 1, no mask)");
+  return WCA_OK;
+}
+
+int wca_test_layernorm(wca_engine* e, const float* x, const float* g, const float* b, void* out, int rows, int d) {
+  if (!e) return fail(WCA_ERR_INVALID, "null engine");
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(launch_layernorm_f16(x, g, b, (half_t*)out, rows, d, 1e-5f, e->stream));
+  return WCA_OK;
+}
+
+int wca_test_layernorm_split(wca_engine* e, const float* x, const float* g, const float* b, void* out2, int rows, int d) {
+  if (!e) return fail(WCA_ERR_INVALID, "null engine");
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(launch_layernorm_f16(x, g, b, (half_t*)out2, rows, d, 1e-5f, e->stream, 2 * d, d));
+  return WCA_OK;
+}
+
+int wca_test_encoder(wca_engine* e, const float* mel_dev, int batch, float* xa_out_dev) {
+  int rc = check_ready(e);
+  if (rc) return rc;
+  if ((rc = join_phase2(e))) return rc;
+  if (batch < 1 || batch > e->max_batch) return fail(WCA_ERR_INVALID, "batch %d outside [1,%d]", batch, e->max_batch);
+  const wca_model_dims& D = e->dims;
+  if ((rc = ensure_split_weights(e))) return rc;
+  if ((rc = mel_to_tm(e, mel_dev, batch))) return rc;
+  rc = run_encoder(e, batch);
+  if (rc) return rc;
+  // xn holds ln_post(x) in f16 (split mode: hi + lo pairs); widen for the caller
+  const size_t n = (size_t)batch * N_CTX * D.n_audio_state;
+  if (e->split)
+    hipLaunchKernelGGL(widen_split_kernel, dim3(2048), dim3(256), 0, e->stream, e->xn, xa_out_dev, (size_t)batch * N_CTX, D.n_audio_state);
+  else
+    hipLaunchKernelGGL(widen_kernel, dim3(2048), dim3(256), 0, e->stream, e->xn, xa_out_dev, n);
+  HIPCHK(hipGetLastError());
+  return WCA_OK;
+}
+
+}  // extern "C"

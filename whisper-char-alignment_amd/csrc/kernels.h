@@ -33,7 +33,7 @@ struct GemmArgs {
   long c_batch_stride;     // elements
   long c_lo;               // out_mode 4: elements from a value's hi half to its lo half (a multiple of 8)
   const float* addend;     // optional PRE-activation addend addend[m * ld_addend + n] (f32): added to the accumulator (with the bias) before GELU / the store --
-                           // the A_hi W_lo^T term of a weight matrix that is not exact in f16 (engine.hip, W_lo slab); out_mode 0 / 1 / 4 of the tile kernels
+                           // the A_hi W_lo^T term of a weight matrix that is not exact in f16 (engine_weights.hip, W_lo slab); out_mode 0 / 1 / 4 of the tile kernels
   int ld_addend;
   const float* pos;        // optional additive table pos[(m % pos_period)][N] (f32), or nullptr
   int pos_period;
