@@ -10,6 +10,8 @@
  *                          (whisper.pad_or_trim + whisper.log_mel_spectrogram)
  *   wca_log_mel_long       whisper.log_mel_spectrogram(audio, n_mels, padding=N_SAMPLES) of a WHOLE recording, the first step of
  *                          upstream whisper.transcribe (not called by the reference, whose entry points stop at 30 s)
+ *   wca_resample_16k       whisper.load_audio's resampling to 16 kHz (upstream pipes every file through ffmpeg; the filter here is the
+ *                          default of torchaudio.functional.resample), with wca_resample_plan / wca_resample_table on the host
  *   wca_mel_window         whisper.pad_or_trim(mel[:, seek : seek + segment_size], N_FRAMES), the window cut of whisper.transcribe's loop
  *   wca_get_attentions     timing.py:45-67   get_attentions(): teacher-forced forward with every
  *                          cross-attention QK captured (timing.py:50-58), [:max_frames] slice,
@@ -103,7 +105,7 @@ typedef struct {
 } wca_align_opts;
 
 const char* wca_last_error(void);
-int wca_version(void);   /* 11: wca_greedy_decode_rows (per-row prompts and sample budgets); 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: wca_greedy_decode_ex (prompt / prefix: sot_index, batched prefill); 7: exactly two precision modes */
+int wca_version(void);   /* 12: wca_resample_plan, wca_resample_table, wca_resample_16k (any input rate to 16 kHz); 11: wca_greedy_decode_rows (per-row prompts and sample budgets); 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: wca_greedy_decode_ex (prompt / prefix: sot_index, batched prefill); 7: exactly two precision modes */
 
 /* ---- engine lifetime ------------------------------------------------------------------------ */
 /* A new engine is in the CONTRACT precision mode (WCA_PRECISION_REFERENCE: every stage on (hi, lo) operand pairs = the fp32 forward of
@@ -152,6 +154,27 @@ int wca_log_mel(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const i
  * Precision follows wca_set_precision like wca_log_mel: f64 DFT / filterbank accumulation in WCA_PRECISION_REFERENCE, f32 in the f16
  * mode. n_samples in [0, 2^31 - 480001]; asynchronous on the engine's stream. */
 int wca_log_mel_long(wca_engine* e, const float* pcm_dev, int64_t n_samples, float* mel_out_dev, int64_t ld, int64_t* n_frames_out);
+
+/* Sample-rate conversion to 16 kHz, the step upstream whisper.load_audio leaves to ffmpeg. The filter is the default of
+ * torchaudio.functional.resample (Hann-windowed sinc, lowpass_filter_width 6, rolloff 0.99) in polyphase form. For an input rate sr_in in
+ * [2000, 384000] (anything else: WCA_ERR_INVALID), in integer arithmetic:
+ *   g = gcd(sr_in, 16000), L = 16000 / g, M = sr_in / g, W = ceil(600 M / (99 min(L, M))), n_taps = 2 W + 2, n_out = ceil(n_in L / M).
+ * Output j reads the inputs k = k0 + i - W for i in [0, n_taps), k0 = floor(j M / L) (64-bit), zero for k outside [0, n_in), against row
+ * p = (j M) mod L of the table
+ *   h[p][i] = c sinc(t) cos^2(pi t / 12),  c = 0.99 min(L, M) / M,  t = clip((i - W - p / L) c, -6, 6),  sinc(t) = sin(pi t) / (pi t):
+ *   y[j] = sum_i h[p][i] x[k], x the mean over the channels.
+ * wca_resample_plan and wca_resample_table are host only (no engine, no GPU, like wca_collate_plan): the plan quantities (any output
+ * pointer may be NULL) and the table [L][n_taps] in float64 (44101 Hz: 16000 x 36). */
+int wca_resample_plan(int sr_in, int32_t* L, int32_t* M, int32_t* W, int32_t* n_taps);
+int wca_resample_table(int sr_in, double* table_out);
+/* in_dev [channels][ld] f32 (n_in <= ld samples per channel; any 4-byte aligned address, any ld) -> out_dev [*n_out] f32 owned by the
+ * CALLER, *n_out = ceil(n_in L / M) <= out_cap (*n_out is set before out_cap is checked, so a call with out_cap = 0 asks for the size).
+ * sr_in == 16000 copies (the channel mean): the filter is no identity at equal rates, and upstream does nothing there. The engine rounds
+ * the float64 table to f32 once per rate and keeps it on the device (a second call at the same rate uploads nothing); taps accumulate in
+ * f32 in ascending order. channels in [1, 8]; *n_out <= 2^31 - 480001 so that the result always fits wca_log_mel_long; n_in = 0 gives
+ * *n_out = 0 without a launch. Asynchronous on the engine's stream; the engine keeps no buffer of the recording's size. */
+int wca_resample_16k(wca_engine* e, const float* in_dev, int channels, int64_t ld, int64_t n_in, int sr_in, float* out_dev, int64_t out_cap,
+                     int64_t* n_out);
 
 /* pad_or_trim(mel[:, seek : seek + size], 3000) for `batch` windows of one long mel (mel_long_dev [n_mels][ld] f32 with n_frames valid
  * frames, as wca_log_mel_long leaves it): mel_out_dev [batch][n_mels][3000] f32 with exact zeros at frames >= size -- the zero padding

@@ -66,6 +66,9 @@ SIGNATURES = {
     "wca_set_allow_rounded_weights": (_i, [_vp, _i]),
     "wca_log_mel": (_i, [_vp, _vp, _i64, _pi32, _i, _vp]),
     "wca_log_mel_long": (_i, [_vp, _vp, _i64, _vp, _i64, C.POINTER(_i64)]),
+    "wca_resample_plan": (_i, [_i, _pi32, _pi32, _pi32, _pi32]),
+    "wca_resample_table": (_i, [_i, C.POINTER(C.c_double)]),
+    "wca_resample_16k": (_i, [_vp, _vp, _i, _i64, _i64, _i, _vp, _i64, C.POINTER(_i64)]),
     "wca_mel_window": (_i, [_vp, _vp, _i64, _i64, _pi32, _pi32, _i, _vp]),
     "wca_get_attentions": (_i, [_vp, _vp, _vp, _i, _i, _pi32, _pi32, _i, _f, _vp, _vp]),
     "wca_median_filter": (_i, [_vp, _vp, _vp, _i64, _i, _i]),

@@ -120,6 +120,31 @@ def log_mel_spectrogram_long(audio, n_mels=80, device=None, model=None):
     return model.log_mel_long(audio.to(model.device))
 
 
+def resample_plan(sr_in):
+    """(L, M, W, n_taps) of the polyphase resampler from sr_in Hz to 16 kHz (C ABI wca_resample_plan, host only): L = 16000 / g,
+    M = sr_in / g with g = gcd(sr_in, 16000), taps k0 - W .. k0 + W + 1 around k0 = floor(j M / L). sr_in outside [2000, 384000] raises."""
+    import ctypes as C
+    from . import _lib
+    v = [C.c_int32(0) for _ in range(4)]
+    _lib.check(_lib.load().wca_resample_plan(int(sr_in), *[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def resample(audio, sr_in, model=None):
+    """What whisper.load_audio has ffmpeg do: audio f32 [n] or [channels, n] at sr_in Hz -> f32 [ceil(n * 16000 / sr_in)] at 16 kHz on the
+    GPU (WhisperAMD.resample: torchaudio.functional.resample's default filter on the mean over channels; 16 kHz input is copied)."""
+    import torch
+    if model is None:
+        from .engine import default_engine
+        idx = 0
+        if isinstance(audio, torch.Tensor) and audio.is_cuda and audio.device.index is not None:
+            idx = audio.device.index
+        model = default_engine(idx)
+    if not isinstance(audio, torch.Tensor):
+        audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
+    return model.resample(audio, sr_in)
+
+
 # ------------------------------------------------------------------------------ file readers
 def _read_sphere(buf):
     if buf[:7] != b"NIST_1A":

@@ -203,6 +203,79 @@ int wca_log_mel_long(wca_engine* e, const float* pcm_dev, int64_t n_samples, flo
   return WCA_OK;
 }
 
+int wca_resample_plan(int sr_in, int32_t* L, int32_t* M, int32_t* W, int32_t* n_taps) {
+  ResamplePlan pl;
+  if (resample_plan(sr_in, &pl)) return fail(WCA_ERR_INVALID, "sr_in %d outside [%d, %d]", sr_in, RESAMPLE_SR_MIN, RESAMPLE_SR_MAX);
+  if (L) *L = pl.L;
+  if (M) *M = pl.M;
+  if (W) *W = pl.W;
+  if (n_taps) *n_taps = pl.n_taps;
+  return WCA_OK;
+}
+
+int wca_resample_table(int sr_in, double* table_out) {
+  if (!table_out) return fail(WCA_ERR_INVALID, "null argument");
+  ResamplePlan pl;
+  if (resample_plan(sr_in, &pl)) return fail(WCA_ERR_INVALID, "sr_in %d outside [%d, %d]", sr_in, RESAMPLE_SR_MIN, RESAMPLE_SR_MAX);
+  resample_table(pl, table_out);
+  return WCA_OK;
+}
+
+int wca_resample_16k(wca_engine* e, const float* in_dev, int channels, int64_t ld, int64_t n_in, int sr_in, float* out_dev, int64_t out_cap,
+                     int64_t* n_out) {
+  constexpr size_t RS_TABLES_MAX = 8;
+  if (!e || !n_out || (n_in > 0 && (!in_dev || !out_dev))) return fail(WCA_ERR_INVALID, "null argument");
+  if (channels < 1 || channels > 8) return fail(WCA_ERR_INVALID, "channels %d outside [1, 8]", channels);
+  ResamplePlan pl;
+  if (resample_plan(sr_in, &pl)) return fail(WCA_ERR_INVALID, "sr_in %d outside [%d, %d]", sr_in, RESAMPLE_SR_MIN, RESAMPLE_SR_MAX);
+  const int64_t n_max = INT32_MAX - 480000;   // what wca_log_mel_long takes
+  if (n_in < 0 || n_in > ld || n_in > n_max * 24) return fail(WCA_ERR_INVALID, "n_in %lld outside [0, ld = %lld]", (long long)n_in, (long long)ld);
+  const int64_t n = (n_in * pl.L + pl.M - 1) / pl.M;   // (n_in L < 2^31 x 24 x 16000)
+  if (n > n_max) return fail(WCA_ERR_INVALID, "%lld samples at %d Hz give %lld at 16 kHz: more than 2^31 - 480001", (long long)n_in, sr_in, (long long)n);
+  *n_out = n;
+  if (out_cap < n) return fail(WCA_ERR_INVALID, "out_cap %lld < %lld output samples", (long long)out_cap, (long long)n);
+  if (n == 0) return WCA_OK;
+  HIPCHK(hipSetDevice(e->device));
+  if (int jr = join_phase2(e)) return jr;
+  ResampleArgs a{};
+  a.in = in_dev;
+  a.channels = channels;
+  a.ld = ld;
+  a.n_in = n_in;
+  a.out = out_dev;
+  a.n_out = n;
+  a.max_blocks = 3 * (e->n_cu > 0 ? e->n_cu : 256);
+  if (sr_in != RESAMPLE_SR_OUT) {   // the filter is no identity at equal rates, and upstream does nothing there: a copy (the channel mean)
+    auto it = std::find_if(e->rs_tables.begin(), e->rs_tables.end(), [&](const wca_engine::ResampleTable& t) { return t.sr_in == sr_in; });
+    if (it == e->rs_tables.end()) {
+      const size_t count = (size_t)pl.L * pl.n_taps;
+      std::vector<double> h(count);
+      resample_table(pl, h.data());
+      std::vector<float> hf(count);
+      for (int p = 0; p < pl.L; ++p)
+        for (int i = 0; i < pl.n_taps; ++i)
+          hf[pl.home == RESAMPLE_HOME_LDS ? (size_t)i * pl.L + p : (size_t)p * pl.n_taps + i] = (float)h[(size_t)p * pl.n_taps + i];
+      if (e->rs_tables.size() >= RS_TABLES_MAX) {   // (hipFree waits for the launches that still read it)
+        HIPCHK(hipFree(e->rs_tables.front().dev));
+        e->rs_tables.erase(e->rs_tables.begin());
+      }
+      float* dev = nullptr;
+      HIPCHK(hipMalloc(&dev, sizeof(float) * count));
+      hipError_t ce = hipMemcpy(dev, hf.data(), sizeof(float) * count, hipMemcpyHostToDevice);
+      if (ce != hipSuccess) {
+        (void)hipFree(dev);
+        HIPCHK(ce);
+      }
+      e->rs_tables.push_back({sr_in, pl, dev});
+      it = e->rs_tables.end() - 1;
+    }
+    a.plan = &it->plan;
+    a.table = it->dev;
+  }
+  HIPCHK(launch_resample(a, e->stream));
+  return WCA_OK;
+}
+
 int wca_mel_window(wca_engine* e, const float* mel_long_dev, int64_t ld, int64_t n_frames, const int32_t* seek_host, const int32_t* size_host,
                    int batch, float* mel_out_dev) {
   if (!e || !mel_long_dev || !seek_host || !size_host || !mel_out_dev) return fail(WCA_ERR_INVALID, "null argument");

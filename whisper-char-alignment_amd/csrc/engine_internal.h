@@ -179,6 +179,10 @@ struct wca_engine {
   wca::GrowBuf dec_rows;              // wca_greedy_decode_rows: the per-row int tables (n_initial - 1, sot_index, n_initial, sample cap; per step: fed position, key count, cur_len)
   wca::GrowBuf dec_gather;            // prefill: the f32 residual rows whose logits are needed ([2B][d]: last initial position, <|sot|>)
   int* dec_done_host = nullptr;  // pinned: completion counter read back while the loop runs
+  // wca_resample_16k: the polyphase tables of the input rates seen so far (f32 on the device, in the layout the plan's table home reads);
+  // at most 8, the oldest leaves
+  struct ResampleTable { int sr_in; wca::ResamplePlan plan; float* dev; };
+  std::vector<ResampleTable> rs_tables;
   int dec_prefill_positions = 0, dec_step_positions = 0;  // the last decode: positions per row fed by the prefill / one at a time
   // Encoded micro-batches (log-mel + encoder + cross-K/V done, recorded on `stream`) that no alignment has consumed
   // yet: wca_encode_batch / wca_greedy_decode push, wca_align_batch_enqueue(pcm_dev = NULL) pops the oldest. A K/V

@@ -227,6 +227,28 @@ hipError_t launch_logmel_long(const LogMelLongArgs& a, hipStream_t s);
 // seek / size are device arrays; the caller has checked 0 <= seek, 1 <= size <= 3000, seek + size <= the long mel's frames.
 hipError_t launch_mel_window(const float* mel_long, long ld, int n_mels, const int* seek, const int* size, int B, float* out, hipStream_t s);
 
+// ---------------------------------------------------------------- resampler to 16 kHz (resample.hip)
+constexpr int RESAMPLE_SR_OUT = 16000, RESAMPLE_SR_MIN = 2000, RESAMPLE_SR_MAX = 384000;
+enum { RESAMPLE_HOME_UNIFORM = 0, RESAMPLE_HOME_LDS = 1, RESAMPLE_HOME_GLOBAL = 2 };   // where the kernel reads the polyphase table from
+struct ResamplePlan {
+  int L, M, W, n_taps;     // 16000 / g, sr_in / g, half width in input samples, 2 W + 2
+  int home;                // RESAMPLE_HOME_*
+  int tile, span_max;      // outputs per tile, input samples a tile stages at most
+};
+int resample_plan(int sr_in, ResamplePlan* pl);          // host only; -1 for sr_in outside [RESAMPLE_SR_MIN, RESAMPLE_SR_MAX]
+void resample_table(const ResamplePlan& pl, double* h);  // host only: h [L][n_taps] f64
+struct ResampleArgs {
+  const float* in;         // [channels][ld] f32, n_in <= ld samples per channel, any 4-byte aligned address and any ld
+  int channels;
+  long ld, n_in;
+  float* out;              // [n_out] f32 16 kHz: the filtered mean over channels
+  long n_out;              // ceil(n_in L / M) (n_in when plan is null)
+  const ResamplePlan* plan;  // null: the input is at 16 kHz already (copy / channel mean)
+  const float* table;      // device f32: [n_taps][L] for RESAMPLE_HOME_LDS, [L][n_taps] otherwise
+  int max_blocks;          // grid cap: the workgroups stride over the tiles
+};
+hipError_t launch_resample(const ResampleArgs& a, hipStream_t s);
+
 // ---------------------------------------------------------------- post-processing (postproc.hip)
 struct HeadStatsArgs {
   const float* qk;         // captured logits: qk[b*qk_bs + head*qk_hs + t*qk_ld + f]

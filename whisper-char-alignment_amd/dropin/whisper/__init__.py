@@ -34,7 +34,8 @@ def load_model(name, device="cuda:0", download_root=None, in_memory=False, max_b
 
 audio = _types.ModuleType("whisper.audio")
 for _n in ("SAMPLE_RATE", "N_FFT", "HOP_LENGTH", "CHUNK_LENGTH", "N_SAMPLES", "N_FRAMES", "N_SAMPLES_PER_TOKEN", "FRAMES_PER_SECOND",
-           "TOKENS_PER_SECOND", "pad_or_trim", "log_mel_spectrogram", "log_mel_spectrogram_long", "mel_filters", "load_audio"):
+           "TOKENS_PER_SECOND", "pad_or_trim", "log_mel_spectrogram", "log_mel_spectrogram_long", "mel_filters", "load_audio", "resample",
+           "resample_plan"):
     setattr(audio, _n, getattr(_audio, _n))
 model = _types.ModuleType("whisper.model")
 model.disable_sdpa = _contextlib.nullcontext  # the engine always materialises qk for the hooked heads

@@ -330,6 +330,29 @@ class WhisperAMD:
         self._after_call()
         return out
 
+    def resample(self, pcm, sr_in):
+        """whisper.load_audio's resampling step on the GPU (C ABI wca_resample_16k): pcm f32 [n] or [C, n] (C <= 8 channels, averaged)
+        sampled at sr_in Hz, on the host or on the device -> cuda f32 [ceil(n * 16000 / sr_in)] at 16 kHz. The filter is
+        torchaudio.functional.resample's default (include/wca.h); sr_in == 16000 copies (the channel mean). The tensor is the caller's."""
+        if pcm.dim() not in (1, 2):
+            raise ValueError("resample takes one recording [n] or [channels, n]; got shape %s" % (tuple(pcm.shape),))
+        p = pcm.to(self.device, torch.float32)
+        p = p[None] if p.dim() == 1 else p
+        if p.stride(1) != 1 and p.shape[1] > 1:
+            p = p.contiguous()
+        channels, n = p.shape
+        ld = p.stride(0) if channels > 1 else n
+        L, M = C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.wca_resample_plan(int(sr_in), C.byref(L), C.byref(M), None, None))
+        out = torch.empty(-(-n * L.value // M.value), device=self.device, dtype=torch.float32)
+        n_out = C.c_int64(0)
+        self._bind_stream()
+        _lib.check(self._lib.wca_resample_16k(self._h, _ptr(p) if n else None, channels, ld, n, int(sr_in), _ptr(out) if n else None,
+                                              out.shape[0], C.byref(n_out)))
+        assert n_out.value == out.shape[0]
+        self._after_call()
+        return out
+
     def mel_window(self, mel_long, seek, size):
         """pad_or_trim(mel_long[:, seek : seek + size], 3000) (C ABI wca_mel_window). mel_long [n_mels, T] f32 cuda; seek / size ints ->
         [n_mels, 3000], or equally long lists -> [B, n_mels, 3000]; exact zeros beyond `size`."""

@@ -6,7 +6,9 @@ Upstream openai-whisper `transcribe.py` is an absent third-party dependency (lik
 docstring); its published seek loop is restated here: PARITY UNPINNED against upstream itself. The reference
 repository has no long-form path at all (its entry points stop at 30 s, infer_ali.py:78-81).
 
-What runs where: the log-mel of the WHOLE recording once (wca_log_mel_long: one `max - 8` floor over the recording), the
+What runs where: audio that is not at 16 kHz (a 44.1 / 48 kHz file, 8 kHz telephone audio, an array with sample_rate=...) is converted
+on the GPU first (wca_resample_16k: torchaudio.functional.resample's default filter on the mean over the channels; upstream's load_audio
+leaves this to ffmpeg), then the log-mel of the WHOLE recording once (wca_log_mel_long: one `max - 8` floor over the recording), the
 window cut pad_or_trim(mel[:, seek:seek+size], 3000) with zeros in the mel domain (wca_mel_window), greedy decode of each
 window with the previous text as the prompt (wca_greedy_decode_ex), and -- with word_timestamps=True -- the fused alignment
 on the encoder state that decode left in the engine (align_batch(pcm=None): no second encoder pass). The loop itself
@@ -293,31 +295,38 @@ def make_aligner(model, tokenizer, *, aligned_unit_type="char", aggr="topk", top
     return align_window
 
 
-def _as_pcm(audio):
+def _as_pcm(audio, model, sample_rate=SAMPLE_RATE):
+    """One recording as 16 kHz mono f32 [n]: a path is read with its own rate and channels (audio.load_audio), an array or tensor
+    ([n], or [channels, n]) is taken at `sample_rate`. Anything not at 16 kHz goes through model.resample with its channels (the kernel
+    averages them); 16 kHz audio stays on the host and is averaged there."""
     import torch
     if isinstance(audio, (str, os.PathLike)):
         from .audio import load_audio
-        pcm, sr = load_audio(audio)
-        if sr != SAMPLE_RATE:
-            raise ValueError("%s is sampled at %d Hz: transcribe takes %d Hz audio (there is no resampler here)" % (audio, sr, SAMPLE_RATE))
-        if pcm.ndim > 1:
-            pcm = pcm.mean(axis=0)
-        audio = pcm
+        audio, sample_rate = load_audio(audio)
     if not isinstance(audio, torch.Tensor):
         audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
+    audio = audio.to(torch.float32)
+    if int(sample_rate) != SAMPLE_RATE:
+        if audio.dim() not in (1, 2):
+            raise ValueError("audio must be one recording [n] or [channels, n]; got shape %s" % (tuple(audio.shape),))
+        return model.resample(audio, int(sample_rate))
+    if audio.dim() == 2:
+        audio = audio.mean(dim=0)
     if audio.dim() != 1:
         raise ValueError("audio must be one mono recording [n]; got shape %s" % (tuple(audio.shape),))
-    return audio.to(torch.float32)
+    return audio
 
 
 def transcribe(model, audio, *, language, initial_prompt=None, condition_on_previous_text=True, no_speech_threshold=0.6,
                logprob_threshold=-1.0, word_timestamps=False, word_confidence=False, aligned_unit_type="char", aggr="topk", topk=10,
                medfilt_width=3, vocab_path=None, temperature=0.0, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0, decode_window=None,
-               **decode_options):
+               sample_rate=SAMPLE_RATE, **decode_options):
     """whisper.transcribe(model, audio, ...) -> {"text", "segments": [{"id", "seek", "start", "end", "text", "tokens", "temperature",
     "avg_logprob", "compression_ratio", "no_speech_prob", "words": [{"word", "start", "end", "probability"}]}], "language"} plus
     "windows" (every decoded window: seek, size, advance, skipped, max_frames, aligned) and "windows_without_words".
-    audio: a path (audio.load_audio), a numpy array or a tensor of 16 kHz mono samples, any length. word_timestamps=True: word times
+    audio: a path (audio.load_audio: any rate from 2 to 384 kHz, up to 8 channels), or a numpy array or tensor of mono samples [n] (or
+    [channels, n]) at `sample_rate` Hz, any length. Audio that is not at 16 kHz is resampled on the GPU first (WhisperAMD.resample), as
+    upstream's load_audio has ffmpeg do. word_timestamps=True: word times
     from the character aligner per window (module docstring); word_confidence=True adds each word's probability (None otherwise).
     decode_window(mel_window, prompt_tokens) -> DecodingResult replaces the engine's greedy decode (tests); decode_options go to
     DecodingOptions. Limits: module docstring."""
@@ -332,7 +341,7 @@ def transcribe(model, audio, *, language, initial_prompt=None, condition_on_prev
     prompt_tokens = []
     if initial_prompt is not None:
         prompt_tokens = decoding._text_tokens(tokenizer, initial_prompt, decoding.DecodingOptions(vocab_path=vocab_path), "initial_prompt")
-    mel_long = model.log_mel_long(_as_pcm(audio))
+    mel_long = model.log_mel_long(_as_pcm(audio, model, sample_rate))
 
     if decode_window is None:
         def decode_window(mel_window, prompt):
@@ -356,12 +365,13 @@ def transcribe(model, audio, *, language, initial_prompt=None, condition_on_prev
 def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_on_previous_text=True, no_speech_threshold=0.6,
                      logprob_threshold=-1.0, word_timestamps=False, word_confidence=False, aligned_unit_type="char", aggr="topk", topk=10,
                      medfilt_width=3, vocab_path=None, temperature=0.0, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0, decode_windows=None,
-                     **decode_options):
+                     sample_rate=SAMPLE_RATE, **decode_options):
     """transcribe() of several recordings in lock-step: a list with transcribe()'s result for every recording of `audios`, in order.
     Each round cuts the next window of every unfinished recording, decodes them in ONE batch with every row's own previous text as its
     prompt (decoding.decode with one DecodingOptions per row: wca_greedy_decode_rows) and, with word_timestamps, aligns the rows that
     have words in one align_batch(pcm=None) on the state that decode left behind. The batch shrinks as recordings end; more recordings
-    than model.max_batch are processed in groups of max_batch. The keyword arguments are transcribe()'s;
+    than model.max_batch are processed in groups of max_batch. The keyword arguments are transcribe()'s; sample_rate is one int for
+    every array / tensor input or one per recording (a path carries its own rate);
     decode_windows(mel_windows [B, n_mels, 3000], prompts: B token lists) -> B DecodingResults replaces the engine's decode (tests)."""
     from . import decoding
     from .tokenizer import get_tokenizer
@@ -394,10 +404,13 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
                              w_colnorm=w_colnorm, w_rownorm=w_rownorm, w_coverage=w_coverage, word_confidence=word_confidence)
     decode_text = tokenizer.decode if vocab_path is not None else (lambda toks: None)
     audios = list(audios)
+    rates = [int(r) for r in sample_rate] if isinstance(sample_rate, (list, tuple)) else [int(sample_rate)] * len(audios)
+    if len(rates) != len(audios):
+        raise ValueError("sample_rate lists %d rates for %d recordings" % (len(rates), len(audios)))
     results = [None] * len(audios)
     for g0 in range(0, len(audios), max_batch):
         group = list(range(g0, min(len(audios), g0 + max_batch)))
-        mels = {i: model.log_mel_long(_as_pcm(audios[i])) for i in group}
+        mels = {i: model.log_mel_long(_as_pcm(audios[i], model, rates[i])) for i in group}
         states = {i: SeekState(mels[i].shape[1], tokenizer, initial_prompt_tokens=prompt_tokens,
                                condition_on_previous_text=condition_on_previous_text, no_speech_threshold=no_speech_threshold,
                                logprob_threshold=logprob_threshold, decode_text=decode_text) for i in group}
@@ -430,7 +443,7 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Long-form transcription with character-aligned word times (one JSON per recording)")
     src = p.add_mutually_exclusive_group(required=True)
-    src.add_argument("--audio", type=str, help="one 16 kHz recording (WAV / SPHERE / FLAC)")
+    src.add_argument("--audio", type=str, help="one recording (WAV / SPHERE / FLAC at any rate from 2 to 384 kHz, or a raw .npy array)")
     src.add_argument("--scp", type=str, help="list of recordings: `<id> <path>` or `<path>` per line")
     p.add_argument("--output_dir", type=str, required=True)
     p.add_argument("--model", type=str, default="medium")
@@ -450,6 +463,7 @@ def parse_args(argv=None):
     p.add_argument("--w_rownorm", type=float, default=1.0)
     p.add_argument("--w_coverage", type=float, default=0.0)
     p.add_argument("--forward_precision", type=str, default="reference", choices=["reference", "split", "f16"])
+    p.add_argument("--sample_rate", type=int, default=SAMPLE_RATE, help="rate of raw .npy arrays ([n] or [channels, n]); audio files carry their own")
     p.add_argument("--batch", type=int, default=1, help="recordings transcribed in lock-step (transcribe_batch; the engine's max_batch)")
     return p.parse_args(argv)
 
@@ -493,16 +507,19 @@ def main(args, model=None):
     kw = dict(language=args.language, initial_prompt=args.initial_prompt, condition_on_previous_text=not args.no_condition_on_previous_text,
               word_timestamps=args.word_timestamps, word_confidence=args.word_confidence, aligned_unit_type=args.aligned_unit_type,
               aggr=args.aggr, topk=args.topk, medfilt_width=args.medfilt_width, vocab_path=args.vocab, w_colnorm=args.w_colnorm,
-              w_rownorm=args.w_rownorm, w_coverage=args.w_coverage)
+              w_rownorm=args.w_rownorm, w_coverage=args.w_coverage, sample_rate=args.sample_rate)
     recordings = _recordings(args)
+
+    def source(path):   # a raw array is taken at --sample_rate; a file is read, with its own rate, by transcribe
+        return np.load(path) if path.endswith(".npy") else path
 
     def results():   # one group of --batch recordings at a time: a group's files are written before the next group starts
         for g0 in range(0, len(recordings), args.batch):
             group = recordings[g0:g0 + args.batch]
             if args.batch > 1:
-                yield from zip(group, transcribe_batch(model, [path for _, path in group], **kw))
+                yield from zip(group, transcribe_batch(model, [source(path) for _, path in group], **kw))
             else:
-                yield group[0], transcribe(model, group[0][1], **kw)
+                yield group[0], transcribe(model, source(group[0][1]), **kw)
 
     for (rec_id, path), result in results():
         out = os.path.join(args.output_dir, rec_id + ".json")
