@@ -43,6 +43,18 @@ def test_null_engine_is_an_error_not_a_crash(wca):
     assert lib.wca_engine_synchronize(None) < 0
     assert b"null" in lib.wca_last_error()
     assert lib.wca_finalize_weights(None) < 0
+    # every entry point of the alignment and the audio file that takes an engine checks its arguments before its first HIP call: a null
+    # engine with null / zero arguments is refused on a machine without a GPU
+    names = []
+    for f in ("engine_align.hip", "engine_audio.hip"):
+        src = open(os.path.join(ROOT, "whisper-char-alignment_amd", "csrc", f)).read()
+        names += re.findall(r"^int (wca_\w+)\(wca_engine\* e\b", src, flags=re.M)
+    assert len(names) >= 21 and {"wca_log_mel", "wca_resample_16k", "wca_align_batch_fetch_ex", "wca_probe_strict_tp"} <= set(names)
+    for name in names:
+        args = [None if issubclass(t, ctypes._Pointer) or t is ctypes.c_void_p else 0 for t in wca._lib.SIGNATURES[name][1]]
+        assert lib.wca_test_set_switch(b"no_such_switch", 1) < 0 and b"null" not in lib.wca_last_error()
+        assert getattr(lib, name)(*args) < 0, name
+        assert b"null" in lib.wca_last_error(), name
 
 
 def test_library_is_in_tree_and_has_gfx950_code(wca):

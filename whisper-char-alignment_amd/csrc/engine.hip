@@ -13,7 +13,7 @@
 //   decode    f16 self-attention K/V cache [L][2][B][T_max][d], int32 token rows, fp32 logits [B][n_vocab]
 //
 // This file: engine lifecycle, settings, profiling, the activation arena and the small helpers every entry point uses. The rest of the
-// engine is in engine_weights / engine_forward / engine_align / engine_decode / engine_comm / engine_test.hip (engine_internal.h).
+// engine is in engine_weights / engine_forward / engine_align / engine_audio / engine_decode / engine_comm / engine_test.hip (engine_internal.h).
 #include <cstdarg>
 
 #include "engine_internal.h"
@@ -91,6 +91,12 @@ void record(wca_engine* e, int i, hipStream_t s) {
 int join_phase2(wca_engine* e) {
   if (e->enq_count > e->fetch_count) HIPCHK(hipStreamWaitEvent(e->stream, e->res_ev[(e->enq_count - 1) & 1], 0));
   return WCA_OK;
+}
+
+int enter(wca_engine* e) {
+  if (!e) return fail(WCA_ERR_INVALID, "null engine");
+  HIPCHK(hipSetDevice(e->device));
+  return join_phase2(e);
 }
 
 int check_ready(wca_engine* e) {

@@ -1,6 +1,6 @@
 // libwca.so engine, forward passes: the GEMM helpers, the encoder, the cross-K/V projection, the decoder (one layer walk and the
 // four passes that drive it: teacher-forced in both precision modes, the greedy decode step, the prompted decode's prefill),
-// log-mel and phase 1 of a micro-batch.
+// the mel layout change and phase 1 of a micro-batch.
 #include "engine_internal.h"
 
 using namespace wca;
@@ -576,30 +576,6 @@ int run_decode_prefill(wca_engine* e, hipStream_t s, const half_t* kvbuf, const 
   if (last_rows) HIPCHK(launch_gather_rows_per_row(e->xd, xg, B, n, last_rows, sot_rows, dt, s));
   else HIPCHK(launch_gather_rows(e->xd, xg, B, n, n - 1, sot_index, dt, s));
   return dec_logits(e, p, xg, e->xdn, R, (float*)e->dec_logits.p);
-}
-
-int run_logmel(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int* n_samples_dev, int B, float* mel_out, bool want_tm) {
-  if (!e->have_filters) return fail(WCA_ERR_STATE, "mel_filters not loaded (wca_load_weight(\"mel_filters\"))");
-  LogMelArgs a{};
-  a.pcm = pcm_dev;
-  a.pcm_stride = pcm_stride;
-  a.n_samples = n_samples_dev;
-  a.filters = e->mel_filters;
-  a.filt_lo = e->filt_lo;
-  a.filt_hi = e->filt_hi;
-  a.window = e->window;
-  a.twiddle = e->twiddle;
-  a.mel_out = mel_out;
-  a.mel_tm = want_tm ? e->mel_tm : nullptr;
-  a.n_mels_pad = (e->split ? 2 : 1) * e->dims.n_mels;   // split mode: the conv stem reads pairs, the DFT accumulates in f64
-  a.tm_lo = e->split ? e->dims.n_mels : 0;
-  a.precise = e->split ? 1 : 0;
-  a.scratch = e->mel_scratch;
-  a.gmax = e->gmax;
-  a.n_mels = e->dims.n_mels;
-  a.B = B;
-  HIPCHK(launch_logmel(a, e->stream));
-  return WCA_OK;
 }
 
 }  // namespace wca

@@ -282,6 +282,7 @@ int check_ready(wca_engine* e);   // finalized weights, the device current, the 
 // stage per-utterance metadata into the next device slot: rows = {n_samples, n_tok, n_frames, dtwN}
 int stage_meta(wca_engine* e, int B, const int32_t* a0, const int32_t* a1, const int32_t* a2, const int32_t* a3, int** dev_rows, hipStream_t s = nullptr);
 int join_phase2(wca_engine* e);
+int enter(wca_engine* e);         // what an entry point on `stream` starts with once its arguments are checked: null engine, the device current, join_phase2
 void record(wca_engine* e, int i, hipStream_t s = nullptr);
 int take_kv_slot(wca_engine* e);
 
@@ -327,9 +328,12 @@ int run_decode_step(wca_engine* e, hipStream_t s, int ws, const half_t* kvbuf, c
                     bool want_logits, int phase = -2, const int* pos_rows = nullptr, const int* nk_rows = nullptr);
 int run_decode_prefill(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, int n, int T_max, int sot_index,
                        const int* last_rows = nullptr, const int* sot_rows = nullptr);
-int run_logmel(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int* n_samples_dev, int B, float* mel_out, bool want_tm);
 int mel_to_tm(wca_engine* e, const float* mel_dev, int batch);
 int run_phase1(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int* n_samples_dev, int batch, int slot,
                bool skip_last_v = false);
+
+// ---- engine_audio.hip
+int check_pcm_lengths(const int32_t* n_samples_host, int batch, int64_t pcm_stride);
+int run_logmel(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int* n_samples_dev, int B, float* mel_out, bool want_tm);
 
 }  // namespace wca
