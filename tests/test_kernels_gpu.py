@@ -529,6 +529,31 @@ def test_median_filter_bit_exact(eng, lib, wca, F, w):
     assert torch.equal(out.cpu(), ref)
 
 
+def test_median_filter_sizes_in_any_order(eng, lib, wca):
+    """The dynamic-LDS limit of median_filter_kernel belongs to the kernel symbol and is set once: a small row, one close to the 160 KiB of
+    a CU (4 waves x 4 bytes x (F + 2 x 16) = 141 KiB) and a small one again must each be bit-exact; a row past the limit is refused with
+    an error code and leaves the next call right."""
+    from oracle import timing_ref
+    rows, w = 8, 7
+
+    def run(F):
+        x = torch.randn(rows, F, generator=torch.Generator().manual_seed(F))
+        xd, out = x.cuda(), torch.empty_like(x).cuda()
+        rc = lib.wca_median_filter(eng._h, _vp(xd), _vp(out), rows, F, w)
+        torch.cuda.synchronize()
+        return rc, out.cpu(), x
+
+    for F in (40, 9000, 40):
+        rc, out, x = run(F)
+        wca._lib.check(rc)
+        assert torch.equal(out, timing_ref.median_filter(x.view(1, 1, rows, F), w).reshape(rows, F)), F
+    assert 4 * 4 * (10300 + 2 * 16) > 160 * 1024
+    assert run(10300)[0] != 0
+    rc, out, x = run(40)
+    wca._lib.check(rc)
+    assert torch.equal(out, timing_ref.median_filter(x.view(1, 1, rows, 40), w).reshape(rows, 40))
+
+
 # ------------------------------------------------------------------------------- filter_attention / force_align
 def _fa_gpu(eng, lib, wca, A, topk, wc, wr, wv):
     L, H, n, F = A.shape
@@ -543,9 +568,7 @@ def _fa_gpu(eng, lib, wca, A, topk, wc, wr, wv):
     return sc, idx, ss
 
 
-@pytest.mark.parametrize("shape", [(4, 6, 12, 50), (6, 8, 69, 500), (2, 3, 448, 130), (3, 2, 30, 1500)])
-@pytest.mark.parametrize("wts", [(1.0, 1.0, 0.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (1.0, 1.0, 1.0)])
-def test_filter_attention(eng, lib, wca, shape, wts):
+def _check_filter_attention(eng, lib, wca, shape, wts):
     from oracle import timing_ref
     g = torch.Generator().manual_seed(sum(shape))
     A = torch.softmax(torch.randn(*shape, generator=g) * 3, -1)
@@ -565,6 +588,28 @@ def test_filter_attention(eng, lib, wca, shape, wts):
     for pos, (rs, (l, h), _) in enumerate(ref):
         if int(idx[pos]) != l * H + h:
             assert abs(allref[int(idx[pos])] - rs) <= 4e-5 * max(1.0, abs(rs)), (pos, int(idx[pos]), l * H + h)
+
+
+@pytest.mark.parametrize("shape", [(4, 6, 12, 50), (6, 8, 69, 500), (2, 3, 448, 130), (3, 2, 30, 1500)])
+@pytest.mark.parametrize("wts", [(1.0, 1.0, 0.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (1.0, 1.0, 1.0)])
+def test_filter_attention(eng, lib, wca, shape, wts):
+    _check_filter_attention(eng, lib, wca, shape, wts)
+
+
+def test_filter_attention_sizes_in_any_order(eng, lib, wca, switch):
+    """The dynamic-LDS limit of a head_stats kernel belongs to the kernel symbol and is set once: a small launch, a large one and a small
+    one again (the same NPL instance or another) must each be right. First the general kernel on weights against the reference of
+    test_filter_attention, then the lean kernel on logits, bit for bit against the general one."""
+    for F in (50, 1500, 50):
+        _check_filter_attention(eng, lib, wca, (2, 2, 6, F), (1.0, 1.0, 1.0))
+    tm = importlib.import_module("whisper-char-alignment_amd.timing")
+    for F in (50, 1500, 50):
+        qk = (torch.randn(2, 2, 6, F, generator=torch.Generator().manual_seed(F)) * 4.0).cuda()
+        out = tm.attention_weights(qk, F, medfilt_width=3, qk_scale=0.37).cpu()
+        switch("head_stats_general", 1)
+        ref = tm.attention_weights(qk, F, medfilt_width=3, qk_scale=0.37).cpu()
+        switch("head_stats_general", 0)
+        assert torch.equal(out.view(torch.int32), ref.view(torch.int32)), F
 
 
 @pytest.mark.parametrize("aggr,topk", [("mean", -1), ("topk", 10), ("topk", 3)])

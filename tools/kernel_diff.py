@@ -20,9 +20,12 @@ RENAME = [(r"(gemm256p_f16_kernel<[^,]+, [^,]+, [^,]+), 0, ", r"\1, "),
           (r"attn32_kernel<false, false>", "attn32_kernel"),
           # kernels that gained a per-row instance (wca_greedy_decode_rows): the uniform launches take the <..., false> ones
           (r"(gemm_rows_f16_kernel<[^,]+, [^,]+, [^,>]+)>", r"\1, false>"),
-          (r"\b(attn_decode_kernel|decode_select_kernel)\(", r"\1<false>(")]
+          (r"\b(attn_decode_kernel|decode_select_kernel)\(", r"\1<false>("),
+          # the waves per workgroup of the pair attention: a constant of the body now (only 4 was ever instantiated)
+          (r"attn_split_kernel<(true|false), (true|false), 4>", r"attn_split_kernel<\1, \2>")]
 SLOAD = re.compile(r"^(s_load_\w+|s_buffer_load_\w+)\s+(.*),\s*(0x[0-9a-fA-F]+|\d+)$")
 REG = re.compile(r"\b([vsa])(\d+|\[\d+:\d+\])")
+ZERO_DWORD = "v_cndmask_b32_e32 v0, s0, v0, vcc"   # what llvm-objdump prints for 0x00000000
 
 
 def demangle(names):
@@ -58,6 +61,9 @@ def kernels(obj, tmp):
         ins = re.sub(r"\s*<[^>]*>$", "", ins)   # branch target labels carry absolute addresses
         if cur and ins and ins != "...":   # (a run of zero padding after s_endpgm: its presence depends on where the next kernel starts)
             code[cur].append(re.sub(r"\s+", " ", ins))
+    for ins in code.values():   # a single zero dword of padding behind the last s_endpgm decodes as an instruction; like the longer runs, it is layout
+        while len(ins) > 1 and ins[-1] == ZERO_DWORD and ins[-2] in (ZERO_DWORD, "s_endpgm"):
+            ins.pop()
     names = demangle(sorted(res))
     return {names[k]: (res[k], code.get(k, [])) for k in res}
 

@@ -11,69 +11,16 @@
 // (O^T = V^T P^T) straight from registers; V^T fragments come from ds_read_b64_tr_b16.
 #include <cstdlib>
 
-#include "kernels.h"
-#include "wca_common.h"
+#include "attn_common.h"
 
 namespace wca {
 
 namespace {
 
-constexpr int KT = 64;               // keys per tile
-constexpr int TILE = 64 * 64;        // f16 elements of one K or V tile
-constexpr float LOG2E = 1.4426950408889634f;
-// Deferred running-max update of the lazy online softmax: a row's running maximum m is only raised (and O, l rescaled)
-// when a tile's scores exceed it by more than RESCALE_THR in the log2 domain; until then p = exp2(s' - m) may be as large as
-// 2^THR = 256 -- exact to f16's 11 bits like any other p (f16 keeps its relative precision up to 65504), sums are fp32.
-// Without the threshold the wave-uniform rescale branch fires on almost every tile (32 rows per wave: on random data at
-// least one row's maximum grows in 75-100 % of the tiles), ~90 extra vector instructions per wave-tile.
-constexpr float RESCALE_THR = 8.0f;
-
-// max over the lanes {l, l^16} / {l, l^32} without LDS: the swap returns {own, partner} in some order
-__device__ __forceinline__ float xor16_max(float v) {
-  const unsigned u = __float_as_uint(v);
-  auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xor32_max(float v) {
-  const unsigned u = __float_as_uint(v);
-  auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-
 __device__ __forceinline__ half4 tr_read4(const half_t* p) {
   s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((WCA_LDS s16x4*)(p));
   return __builtin_bit_cast(half4, r);
 }
-
-// ---- LDS reads the compiler must not schedule or wait for itself. hipcc (ROCm 7.2) puts `s_waitcnt vmcnt(0)` in front of the
-// first ds_read_b64_tr_b16 *builtin* of the loop -- it cannot tell the transposed read from the LDS-DMA writes in flight --
-// which drains the K/V prefetch on every tile; and it issues a compiler-visible ds_read_b128 only right before its MFMA
-// (one read in flight, `lgkmcnt(0)` each). These inline-asm forms are invisible to that bookkeeping: the caller counts
-// lgkmcnt itself (LDS operations return in issue order) and names the destinations in the wait statement, so that no
-// consumer can be scheduled above the wait (cdna_hip_programming.md 5.7, form (ii)).
-__device__ __forceinline__ unsigned lds_off(const void* p) { return (unsigned)(size_t)(const WCA_LDS char*)p; }
-template <int OFF>
-__device__ __forceinline__ half8 lds_read_b128_asm(unsigned addr) {
-  half8 r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "i"(OFF));
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ half4 lds_read_tr_asm(unsigned addr) {
-  half4 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "i"(OFF));
-  return r;
-}
-#define WCA_LGKM_WAIT4(N, A, B, C, D)                                                                         \
-  do {                                                                                                        \
-    asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(A), "+v"(B), "+v"(C), "+v"(D)::"memory");              \
-    __builtin_amdgcn_sched_barrier(0);                                                                        \
-  } while (0)
-#define WCA_LGKM_WAIT8(N, A, B, C, D, E, F, G, H)                                                             \
-  do {                                                                                                        \
-    asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(A), "+v"(B), "+v"(C), "+v"(D), "+v"(E), "+v"(F), "+v"(G), "+v"(H)::"memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                                                        \
-  } while (0)
 
 template <bool CAUSAL, bool CAPTURE>
 __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
@@ -389,15 +336,6 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
 // Same staging as above: 256-thread workgroup, 32 query rows per wave, ring of three 64-key K/V tiles filled by LDS-DMA two
 // tiles ahead, counted vmcnt, one raw barrier per tile. K image: chunk ^ ((key >> 1) & 7) (conflict-free ds_read_b128 for
 // the 32-row A operand); V image: chunk ^ ((key & 2) << 1) (conflict-free transposed reads).
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-
-template <int V>
-struct IntC {
-  static constexpr int value = V;
-};
-
 // (Measured and removed: row sums as fp32 VALU adds of the lane's 32 probabilities per tile (per-lane partial, the two lane halves of a
 // row combined once at the end) instead of four `ones x P^T` MFMAs per tile -- a fifth of the tile's matrix work. Interleaved A/B at
 // 64 x 16 x 1500 x 1500: 0.708 vs 0.724 ms median on one box, 0.701 vs 0.699 on another. Rejected for its numerics: the MFMA form sums
@@ -791,9 +729,7 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
   if (a.nk_rows != nullptr && (a.split || a.nq != 1 || a.causal || (a.cap != nullptr && a.cap_cols > 0))) return hipErrorInvalidValue;
   if (a.split) return launch_attention_split(a, s);  // reference-precision mode: hi/lo operand pairs, three MFMA passes
   if (a.nq <= 0 || a.B <= 0) return hipSuccess;
-  if (a.nk <= 0) return hipErrorInvalidValue;
-  if ((a.q_rs % 8) || (a.k_rs % 8) || (a.v_rs % 8) || (a.o_rs % 4)) return hipErrorInvalidValue;
-  if (a.cap != nullptr && ((a.cap_ld % 4) != 0 || a.cap_ld < ((a.cap_cols + 3) & ~3))) return hipErrorInvalidValue;
+  if (!attn_args_ok(a)) return hipErrorInvalidValue;
   const bool cap = a.cap != nullptr && a.cap_cols > 0;
   if (a.nq == 1 && !cap && (!a.causal || a.nk == 1)) {  // greedy-decode steps: the KV cache holds exactly the causal prefix
     if (a.nk_rows != nullptr) hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(a.H * a.B), dim3(256), 0, s, a);

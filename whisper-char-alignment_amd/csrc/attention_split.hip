@@ -16,66 +16,12 @@
 // the exponential); P is split like every other operand.
 #include <cstdlib>
 
-#include "kernels.h"
-#include "wca_common.h"
+#include "attn_common.h"
+#include "launch.h"
 
 namespace wca {
 
 namespace {
-
-constexpr int KT = 64;
-constexpr int TILE = 64 * 64;  // f16 elements of one 64-key x 64-dim tile
-constexpr float LOG2E = 1.4426950408889634f;
-
-__device__ __forceinline__ float xor16_maxf(float v) {
-  const unsigned u = __float_as_uint(v);
-  auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xor32_maxf(float v) {
-  const unsigned u = __float_as_uint(v);
-  auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xor16_sumf(float v) {
-  const unsigned u = __float_as_uint(v);
-  auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float xor32_sumf(float v) {
-  const unsigned u = __float_as_uint(v);
-  auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// Transposed LDS reads as inline asm with hand-counted lgkmcnt: hipcc (ROCm 7.2) puts `s_waitcnt vmcnt(0)` in front of the first
-// ds_read_b64_tr_b16 BUILTIN of the loop (it cannot tell the transposed read from the LDS-DMA writes in flight), which drains the
-// next tile's K/V prefetch on every tile (on this kernel the prefetch has landed by then anyway: 2.13 vs 2.20 ms per encoder layer
-// at B = 64, within box variance -- kept because it removes the dependence on that timing). LDS operations return in issue order;
-// the wait names its destination registers so that no consumer can be scheduled above it.
-__device__ __forceinline__ unsigned lds_off_s(const void* p) { return (unsigned)(size_t)(const WCA_LDS char*)p; }
-template <int OFF>
-__device__ __forceinline__ half4 tr_read_asm(unsigned addr) {
-  half4 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "i"(OFF));
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ half8 b128_read_asm(unsigned addr) {
-  half8 r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "i"(OFF));
-  return r;
-}
-#define WCA_S_LGKM_WAIT4(N, A, B, C, D)                                                                       \
-  do {                                                                                                        \
-    asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(A), "+v"(B), "+v"(C), "+v"(D)::"memory");              \
-    __builtin_amdgcn_sched_barrier(0);                                                                        \
-  } while (0)
-#define WCA_S_LGKM_WAIT8(N, A, B, C, D, E, F, G, H)                                                                                  \
-  do {                                                                                                                               \
-    asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(A), "+v"(B), "+v"(C), "+v"(D), "+v"(E), "+v"(F), "+v"(G), "+v"(H)::"memory");  \
-    __builtin_amdgcn_sched_barrier(0);                                                                                               \
-  } while (0)
 
 // NW = waves per workgroup (32 query rows each): 4 everywhere (128-row blocks, two workgroups per CU = 2 waves per SIMD).
 // PMC counters of this kernel on the encoder's 64 x 16 x 1500 x 1500 shape (profiles/r04_attn_split_pmc.txt): matrix pipe busy 47 %,
@@ -87,15 +33,16 @@ __device__ __forceinline__ half8 b128_read_asm(unsigned addr) {
 //     1.853 ms -- removed;
 //   * NW = 6 (192-row blocks, 384 threads, 166 VGPRs = three waves per SIMD, a third less K / V staging per query row): 2.116 vs
 //     1.844 ms (the 8 staging pieces do not divide over 6 waves and the barrier waits for the two that stage twice) -- not
-//     instantiated any more (the NW template parameter stays).
+//     instantiated any more (NW is a constant of the body now).
 //   * one 8-wave workgroup per CU with its two wave groups in ENFORCED anti-phase (an extra barrier for waves 4-7, two barriers per tile,
 //     ring of four slots: while one group is in its S^T MFMAs its SIMD partner is in exp2 / pair split): 1.963 vs 1.860 ms -- removed.
 // What these null results say, and tools/micro/mfma_valu_coexec.hip confirms in isolation: on this chip dense vector work beside dense MFMAs
 // is nearly ADDITIVE in time whichever wave it comes from (two waves per SIMD, 16 MFMAs + 96 v_fma per pair of iterations: 578 cycles
 // against 256 of matrix pipe and 384 of vector issue), so the lever is the NUMBER of vector instructions, not where they sit.
 // What did pay: the deferred running maximum (1.869 -> 1.837 ms) and the packed-f32 softmax below.
-template <bool CAUSAL, bool CAPTURE, int NW = 4>
-__global__ __launch_bounds__(NW * 64, (2 * NW * 64) / 256) void attn_split_kernel(AttnArgs a) {
+template <bool CAUSAL, bool CAPTURE>
+__global__ __launch_bounds__(256, 2) void attn_split_kernel(AttnArgs a) {
+  constexpr int NW = 4;  // waves per workgroup, 32 query rows each
   extern __shared__ __attribute__((aligned(16))) char smem[];
   half_t* lds = reinterpret_cast<half_t*>(smem);  // [slot][K hi | K lo | V hi | V lo]
   const int tid = threadIdx.x;
@@ -193,7 +140,7 @@ __global__ __launch_bounds__(NW * 64, (2 * NW * 64) / 256) void attn_split_kerne
     const int swz = (4 * (fg & 1)) | (qd & 2);
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
-      vaddr[dt] = lds_off_s(lds) + 2u * (unsigned)((4 * fg + qd) * 64 + (((2 * dt + (pd >> 1)) ^ swz) << 3) + 4 * (pd & 1));
+      vaddr[dt] = lds_off(lds) + 2u * (unsigned)((4 * fg + qd) * 64 + (((2 * dt + (pd >> 1)) ^ swz) << 3) + 4 * (pd & 1));
   }
   // per-lane byte addresses of the K fragment reads in ring slot 0, K hi tile (the K lo tile and the slot are added at the read):
   // fragment (ks, t) = row t*16 + fr, 16-byte chunk (4 ks + fg) ^ swz128(row)
@@ -203,7 +150,7 @@ __global__ __launch_bounds__(NW * 64, (2 * NW * 64) / 256) void attn_split_kerne
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int r = t * 16 + fr;
-      kaddr[ks][t] = lds_off_s(lds) + 2u * (unsigned)(r * 64 + (((ks * 4 + fg) ^ swz128(r)) << 3));
+      kaddr[ks][t] = lds_off(lds) + 2u * (unsigned)(r * 64 + (((ks * 4 + fg) ^ swz128(r)) << 3));
     }
   float m_run[2] = {-INFINITY, -INFINITY};  // running row maximum of the scores (raw, or in the log2 domain when PRE)
   float l_part[2] = {0.f, 0.f};             // this lane's share of the row sum (its 16 keys per tile), reduced at the end
@@ -230,17 +177,17 @@ __global__ __launch_bounds__(NW * 64, (2 * NW * 64) / 256) void attn_split_kerne
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) kl[ks][t] = b128_read_asm<KLO>(kaddr[ks][t] + sbk);
+        for (int t = 0; t < 4; ++t) kl[ks][t] = lds_read_b128_asm<KLO>(kaddr[ks][t] + sbk);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) kh[ks][t] = b128_read_asm<0>(kaddr[ks][t] + sbk);
+        for (int t = 0; t < 4; ++t) kh[ks][t] = lds_read_b128_asm<0>(kaddr[ks][t] + sbk);
       }
       // the small terms first, the hi.hi product last
-      WCA_S_LGKM_WAIT4(12, kl[0][0], kl[0][1], kl[0][2], kl[0][3]);
+      WCA_LGKM_WAIT4(12, kl[0][0], kl[0][1], kl[0][2], kl[0][3]);
 #pragma unroll
       for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int t = 0; t < 4; ++t) st[s][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl[0][t], qh[s][0], st[s][t], 0, 0, 0);
-      WCA_S_LGKM_WAIT4(8, kh[0][0], kh[0][1], kh[0][2], kh[0][3]);
+      WCA_LGKM_WAIT4(8, kh[0][0], kh[0][1], kh[0][2], kh[0][3]);
 #pragma unroll
       for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -249,12 +196,12 @@ __global__ __launch_bounds__(NW * 64, (2 * NW * 64) / 256) void attn_split_kerne
       for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int t = 0; t < 4; ++t) st[s][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh[0][t], qh[s][0], st[s][t], 0, 0, 0);
-      WCA_S_LGKM_WAIT4(4, kl[1][0], kl[1][1], kl[1][2], kl[1][3]);
+      WCA_LGKM_WAIT4(4, kl[1][0], kl[1][1], kl[1][2], kl[1][3]);
 #pragma unroll
       for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int t = 0; t < 4; ++t) st[s][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl[1][t], qh[s][1], st[s][t], 0, 0, 0);
-      WCA_S_LGKM_WAIT4(0, kh[1][0], kh[1][1], kh[1][2], kh[1][3]);
+      WCA_LGKM_WAIT4(0, kh[1][0], kh[1][1], kh[1][2], kh[1][3]);
 #pragma unroll
       for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -307,7 +254,7 @@ __global__ __launch_bounds__(NW * 64, (2 * NW * 64) / 256) void attn_split_kerne
         m = fmaxf(fmaxf(m, st[s][t][0]), st[s][t][1]);   // v_max3_f32
         m = fmaxf(fmaxf(m, st[s][t][2]), st[s][t][3]);
       }
-      mx[s] = xor32_maxf(xor16_maxf(m));
+      mx[s] = xor32_max(xor16_max(m));
     }
     // DEFERRED running maximum (as in attention.hip): the reference point of a row is raised only when the tile maximum exceeds it
     // by more than 8 in the log2 domain (p <= 2^8: nowhere near the range of the f16 hi half, and p is carried as a pair anyway), or
@@ -371,23 +318,23 @@ __global__ __launch_bounds__(NW * 64, (2 * NW * 64) / 256) void attn_split_kerne
       half4 c_[8], n_[8];
 #define WCA_ISSUE_V(R, A)                                                                    \
   do {                                                                                       \
-    R[0] = tr_read_asm<VH>(A);                                                               \
-    R[1] = tr_read_asm<VH + B16>(A);                                                         \
-    R[2] = tr_read_asm<VL>(A);                                                               \
-    R[3] = tr_read_asm<VL + B16>(A);                                                         \
-    R[4] = tr_read_asm<VH + K2>(A);                                                          \
-    R[5] = tr_read_asm<VH + K2 + B16>(A);                                                    \
-    R[6] = tr_read_asm<VL + K2>(A);                                                          \
-    R[7] = tr_read_asm<VL + K2 + B16>(A);                                                    \
+    R[0] = lds_read_tr_asm<VH>(A);                                                               \
+    R[1] = lds_read_tr_asm<VH + B16>(A);                                                         \
+    R[2] = lds_read_tr_asm<VL>(A);                                                               \
+    R[3] = lds_read_tr_asm<VL + B16>(A);                                                         \
+    R[4] = lds_read_tr_asm<VH + K2>(A);                                                          \
+    R[5] = lds_read_tr_asm<VH + K2 + B16>(A);                                                    \
+    R[6] = lds_read_tr_asm<VL + K2>(A);                                                          \
+    R[7] = lds_read_tr_asm<VL + K2 + B16>(A);                                                    \
   } while (0)
       WCA_ISSUE_V(c_, vaddr[0] + sb);
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         if (dt < 3) {
           WCA_ISSUE_V(n_, vaddr[dt + 1] + sb);
-          WCA_S_LGKM_WAIT8(8, c_[0], c_[1], c_[2], c_[3], c_[4], c_[5], c_[6], c_[7]);
+          WCA_LGKM_WAIT8(8, c_[0], c_[1], c_[2], c_[3], c_[4], c_[5], c_[6], c_[7]);
         } else {
-          WCA_S_LGKM_WAIT8(0, c_[0], c_[1], c_[2], c_[3], c_[4], c_[5], c_[6], c_[7]);
+          WCA_LGKM_WAIT8(0, c_[0], c_[1], c_[2], c_[3], c_[4], c_[5], c_[6], c_[7]);
         }
 #pragma unroll
         for (int k2 = 0; k2 < 2; ++k2) {
@@ -412,7 +359,7 @@ __global__ __launch_bounds__(NW * 64, (2 * NW * 64) / 256) void attn_split_kerne
   // ---- epilogue: ot[s][dt][r] = O[q = fr][d = dt*16 + 4*fg + r]; a row's sum is spread over its four lane groups
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    const float l = xor32_sumf(xor16_sumf(l_part[s]));
+    const float l = xor32_sum(xor16_sum(l_part[s]));
     if (qrow[s] >= a.nq) continue;
     const float inv = 1.0f / l;
     half_t* op = a.O + (long)b * a.o_bs + (long)qrow[s] * a.o_rs + h * 64 + 4 * fg;
@@ -454,14 +401,6 @@ __global__ __launch_bounds__(NW * 64, (2 * NW * 64) / 256) void attn_split_kerne
 // Same arithmetic contract as attn_split_kernel (three passes per product, fp32 online softmax with the deferred maximum, P and O split
 // into pairs); the fp32 summation ORDER differs (k steps of 16 instead of 32, -m inside the accumulator), so results agree to fp32
 // noise, not bit for bit -- tests/test_split_gpu.py compares both with float64.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr float RESCALE_THR32 = 8.0f;
-
-__device__ __forceinline__ float max3f_(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-template <int V>
-struct IntC32 {
-  static constexpr int value = V;
-};
 #define WCA_S_PIN8(A, B, C, D, E, F, G, H) asm volatile("" : "+v"(A), "+v"(B), "+v"(C), "+v"(D), "+v"(E), "+v"(F), "+v"(G), "+v"(H)::"memory")
 
 // DROP (diagnostic, wca_test_set_attn_split_drop; the product runs DROP = 0): bit 0 leaves out K_lo Q_hi, bit 1 K_hi Q_lo, bit 2 V_lo P_hi,
@@ -536,7 +475,7 @@ __global__ __launch_bounds__(256, 2) void attn_split32_kernel(AttnArgs a) {
 
   // per-lane LDS byte addresses in slot 0 / the hi tiles (slot, lo tile and fragment index are immediates), as in attn32_kernel
   const int kswz = (l31 >> 1) & 7;
-  const unsigned lds_base = lds_off_s(lds);
+  const unsigned lds_base = lds_off(lds);
   unsigned ka[4];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) ka[ks] = lds_base + (unsigned)(l31 * 128 + 16 * ((hh ^ kswz) & 1) + 32 * (ks ^ (kswz >> 1)));
@@ -573,43 +512,43 @@ __global__ __launch_bounds__(256, 2) void attn_split32_kernel(AttnArgs a) {
     f32x16 st[2];
     {
       half8 kl0[4], kh0[4], kl1[4], kh1[4];
-      kl0[0] = b128_read_asm<SB + TB>(ka[0]);
-      kl0[1] = b128_read_asm<SB + TB>(ka[1]);
-      kl0[2] = b128_read_asm<SB + TB>(ka[2]);
-      kl0[3] = b128_read_asm<SB + TB>(ka[3]);
-      kh0[0] = b128_read_asm<SB>(ka[0]);
-      kh0[1] = b128_read_asm<SB>(ka[1]);
-      kh0[2] = b128_read_asm<SB>(ka[2]);
-      kh0[3] = b128_read_asm<SB>(ka[3]);
-      kl1[0] = b128_read_asm<SB + TB + 32 * 128>(ka[0]);
-      kl1[1] = b128_read_asm<SB + TB + 32 * 128>(ka[1]);
-      kl1[2] = b128_read_asm<SB + TB + 32 * 128>(ka[2]);
-      kl1[3] = b128_read_asm<SB + TB + 32 * 128>(ka[3]);
-      kh1[0] = b128_read_asm<SB + 32 * 128>(ka[0]);
-      kh1[1] = b128_read_asm<SB + 32 * 128>(ka[1]);
-      kh1[2] = b128_read_asm<SB + 32 * 128>(ka[2]);
-      kh1[3] = b128_read_asm<SB + 32 * 128>(ka[3]);
+      kl0[0] = lds_read_b128_asm<SB + TB>(ka[0]);
+      kl0[1] = lds_read_b128_asm<SB + TB>(ka[1]);
+      kl0[2] = lds_read_b128_asm<SB + TB>(ka[2]);
+      kl0[3] = lds_read_b128_asm<SB + TB>(ka[3]);
+      kh0[0] = lds_read_b128_asm<SB>(ka[0]);
+      kh0[1] = lds_read_b128_asm<SB>(ka[1]);
+      kh0[2] = lds_read_b128_asm<SB>(ka[2]);
+      kh0[3] = lds_read_b128_asm<SB>(ka[3]);
+      kl1[0] = lds_read_b128_asm<SB + TB + 32 * 128>(ka[0]);
+      kl1[1] = lds_read_b128_asm<SB + TB + 32 * 128>(ka[1]);
+      kl1[2] = lds_read_b128_asm<SB + TB + 32 * 128>(ka[2]);
+      kl1[3] = lds_read_b128_asm<SB + TB + 32 * 128>(ka[3]);
+      kh1[0] = lds_read_b128_asm<SB + 32 * 128>(ka[0]);
+      kh1[1] = lds_read_b128_asm<SB + 32 * 128>(ka[1]);
+      kh1[2] = lds_read_b128_asm<SB + 32 * 128>(ka[2]);
+      kh1[3] = lds_read_b128_asm<SB + 32 * 128>(ka[3]);
       if constexpr (DROP == 0) {
-      WCA_S_LGKM_WAIT4(12, kl0[0], kl0[1], kl0[2], kl0[3]);
+      WCA_LGKM_WAIT4(12, kl0[0], kl0[1], kl0[2], kl0[3]);
       st[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl0[0], qh[0], cinit, 0, 0, 0);
 #pragma unroll
       for (int ks = 1; ks < 4; ++ks) st[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl0[ks], qh[ks], st[0], 0, 0, 0);
-      WCA_S_LGKM_WAIT4(8, kh0[0], kh0[1], kh0[2], kh0[3]);
+      WCA_LGKM_WAIT4(8, kh0[0], kh0[1], kh0[2], kh0[3]);
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) st[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh0[ks], ql[ks], st[0], 0, 0, 0);
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) st[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh0[ks], qh[ks], st[0], 0, 0, 0);
-      WCA_S_LGKM_WAIT4(4, kl1[0], kl1[1], kl1[2], kl1[3]);
+      WCA_LGKM_WAIT4(4, kl1[0], kl1[1], kl1[2], kl1[3]);
       st[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl1[0], qh[0], cinit, 0, 0, 0);
 #pragma unroll
       for (int ks = 1; ks < 4; ++ks) st[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl1[ks], qh[ks], st[1], 0, 0, 0);
-      WCA_S_LGKM_WAIT4(0, kh1[0], kh1[1], kh1[2], kh1[3]);
+      WCA_LGKM_WAIT4(0, kh1[0], kh1[1], kh1[2], kh1[3]);
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) st[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh1[ks], ql[ks], st[1], 0, 0, 0);
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) st[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh1[ks], qh[ks], st[1], 0, 0, 0);
       } else {   // ablation forms: the same order with the dropped passes left out (the large term last)
-        WCA_S_LGKM_WAIT4(0, kh1[0], kh1[1], kh1[2], kh1[3]);
+        WCA_LGKM_WAIT4(0, kh1[0], kh1[1], kh1[2], kh1[3]);
         WCA_S_PIN8(kl0[0], kl0[1], kl0[2], kl0[3], kh0[0], kh0[1], kh0[2], kh0[3]);
         WCA_S_PIN8(kl1[0], kl1[1], kl1[2], kl1[3], kh1[0], kh1[1], kh1[2], kh1[3]);
         st[0] = cinit;
@@ -635,22 +574,22 @@ __global__ __launch_bounds__(256, 2) void attn_split32_kernel(AttnArgs a) {
     half4 v0ha[4], v0hb[4], v0la[4], v0lb[4], v1ha[4], v1hb[4], v1la[4], v1lb[4];
 #define WCA_ISSUE_V32(P, DB)                                           \
   do {                                                                 \
-    P##ha[0] = tr_read_asm<SB + 0 * 2048>(va[DB]);                     \
-    P##hb[0] = tr_read_asm<SB + 0 * 2048 + 1024>(va[DB]);              \
-    P##ha[1] = tr_read_asm<SB + 1 * 2048>(va[DB]);                     \
-    P##hb[1] = tr_read_asm<SB + 1 * 2048 + 1024>(va[DB]);              \
-    P##ha[2] = tr_read_asm<SB + 2 * 2048>(va[DB]);                     \
-    P##hb[2] = tr_read_asm<SB + 2 * 2048 + 1024>(va[DB]);              \
-    P##ha[3] = tr_read_asm<SB + 3 * 2048>(va[DB]);                     \
-    P##hb[3] = tr_read_asm<SB + 3 * 2048 + 1024>(va[DB]);              \
-    P##la[0] = tr_read_asm<SB + TB + 0 * 2048>(va[DB]);                \
-    P##lb[0] = tr_read_asm<SB + TB + 0 * 2048 + 1024>(va[DB]);         \
-    P##la[1] = tr_read_asm<SB + TB + 1 * 2048>(va[DB]);                \
-    P##lb[1] = tr_read_asm<SB + TB + 1 * 2048 + 1024>(va[DB]);         \
-    P##la[2] = tr_read_asm<SB + TB + 2 * 2048>(va[DB]);                \
-    P##lb[2] = tr_read_asm<SB + TB + 2 * 2048 + 1024>(va[DB]);         \
-    P##la[3] = tr_read_asm<SB + TB + 3 * 2048>(va[DB]);                \
-    P##lb[3] = tr_read_asm<SB + TB + 3 * 2048 + 1024>(va[DB]);         \
+    P##ha[0] = lds_read_tr_asm<SB + 0 * 2048>(va[DB]);                     \
+    P##hb[0] = lds_read_tr_asm<SB + 0 * 2048 + 1024>(va[DB]);              \
+    P##ha[1] = lds_read_tr_asm<SB + 1 * 2048>(va[DB]);                     \
+    P##hb[1] = lds_read_tr_asm<SB + 1 * 2048 + 1024>(va[DB]);              \
+    P##ha[2] = lds_read_tr_asm<SB + 2 * 2048>(va[DB]);                     \
+    P##hb[2] = lds_read_tr_asm<SB + 2 * 2048 + 1024>(va[DB]);              \
+    P##ha[3] = lds_read_tr_asm<SB + 3 * 2048>(va[DB]);                     \
+    P##hb[3] = lds_read_tr_asm<SB + 3 * 2048 + 1024>(va[DB]);              \
+    P##la[0] = lds_read_tr_asm<SB + TB + 0 * 2048>(va[DB]);                \
+    P##lb[0] = lds_read_tr_asm<SB + TB + 0 * 2048 + 1024>(va[DB]);         \
+    P##la[1] = lds_read_tr_asm<SB + TB + 1 * 2048>(va[DB]);                \
+    P##lb[1] = lds_read_tr_asm<SB + TB + 1 * 2048 + 1024>(va[DB]);         \
+    P##la[2] = lds_read_tr_asm<SB + TB + 2 * 2048>(va[DB]);                \
+    P##lb[2] = lds_read_tr_asm<SB + TB + 2 * 2048 + 1024>(va[DB]);         \
+    P##la[3] = lds_read_tr_asm<SB + TB + 3 * 2048>(va[DB]);                \
+    P##lb[3] = lds_read_tr_asm<SB + TB + 3 * 2048 + 1024>(va[DB]);         \
   } while (0)
     WCA_ISSUE_V32(v0, 0);
     if (kt * KT + KT > a.nk) {  // keys past nk (last tile only): wave-uniform
@@ -664,23 +603,23 @@ __global__ __launch_bounds__(256, 2) void attn_split32_kernel(AttnArgs a) {
     }
     float mx;
     {
-      float m0 = max3f_(st[0][0], st[0][1], st[0][2]), m1 = max3f_(st[0][3], st[0][4], st[0][5]);
-      float m2 = max3f_(st[0][6], st[0][7], st[0][8]), m3 = max3f_(st[0][9], st[0][10], st[0][11]);
-      m0 = max3f_(m0, st[0][12], st[0][13]);
-      m1 = max3f_(m1, st[0][14], st[0][15]);
-      m2 = max3f_(m2, st[1][0], st[1][1]);
-      m3 = max3f_(m3, st[1][2], st[1][3]);
-      m0 = max3f_(m0, st[1][4], st[1][5]);
-      m1 = max3f_(m1, st[1][6], st[1][7]);
-      m2 = max3f_(m2, st[1][8], st[1][9]);
-      m3 = max3f_(m3, st[1][10], st[1][11]);
-      m0 = max3f_(m0, st[1][12], st[1][13]);
-      m1 = max3f_(m1, st[1][14], st[1][15]);
-      mx = fmaxf(max3f_(m0, m1, m2), m3);
-      mx = xor32_maxf(mx);
+      float m0 = max3f(st[0][0], st[0][1], st[0][2]), m1 = max3f(st[0][3], st[0][4], st[0][5]);
+      float m2 = max3f(st[0][6], st[0][7], st[0][8]), m3 = max3f(st[0][9], st[0][10], st[0][11]);
+      m0 = max3f(m0, st[0][12], st[0][13]);
+      m1 = max3f(m1, st[0][14], st[0][15]);
+      m2 = max3f(m2, st[1][0], st[1][1]);
+      m3 = max3f(m3, st[1][2], st[1][3]);
+      m0 = max3f(m0, st[1][4], st[1][5]);
+      m1 = max3f(m1, st[1][6], st[1][7]);
+      m2 = max3f(m2, st[1][8], st[1][9]);
+      m3 = max3f(m3, st[1][10], st[1][11]);
+      m0 = max3f(m0, st[1][12], st[1][13]);
+      m1 = max3f(m1, st[1][14], st[1][15]);
+      mx = fmaxf(max3f(m0, m1, m2), m3);
+      mx = xor32_max(mx);
     }
     // deferred maximum: raised when the tile maximum of (s' - m) exceeds the threshold, or anything finite arrives while m is still -inf
-    if (__any((mx > RESCALE_THR32) || (m_run == -INFINITY && mx != -INFINITY))) {
+    if (__any((mx > RESCALE_THR) || (m_run == -INFINITY && mx != -INFINITY))) {
       const float m_eff = (m_run == -INFINITY) ? 0.f : m_run;
       const float m_new = fmaxf(m_run, mx + m_eff);
       const float delta = (m_new == -INFINITY) ? 0.f : m_new - m_eff;
@@ -724,7 +663,7 @@ __global__ __launch_bounds__(256, 2) void attn_split32_kernel(AttnArgs a) {
       l_run += psum[0] + psum[1];
     }
     // ---- O^T += V^T P^T: A operand element j of lane half hh = V[key 16 s4 + 8 (j>>2) + 4 hh + (j&3)][d = 32 db + l31]
-    WCA_S_LGKM_WAIT8(0, v0ha[0], v0hb[0], v0ha[1], v0hb[1], v0ha[2], v0hb[2], v0ha[3], v0hb[3]);
+    WCA_LGKM_WAIT8(0, v0ha[0], v0hb[0], v0ha[1], v0hb[1], v0ha[2], v0hb[2], v0ha[3], v0hb[3]);
     WCA_S_PIN8(v0la[0], v0lb[0], v0la[1], v0lb[1], v0la[2], v0lb[2], v0la[3], v0lb[3]);
     WCA_ISSUE_V32(v1, 1);
 #pragma unroll
@@ -735,7 +674,7 @@ __global__ __launch_bounds__(256, 2) void attn_split32_kernel(AttnArgs a) {
       if (!(DROP & 8)) ot[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, pl[s4], ot[0], 0, 0, 0);
       ot[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, ph[s4], ot[0], 0, 0, 0);
     }
-    WCA_S_LGKM_WAIT8(0, v1ha[0], v1hb[0], v1ha[1], v1hb[1], v1ha[2], v1hb[2], v1ha[3], v1hb[3]);
+    WCA_LGKM_WAIT8(0, v1ha[0], v1hb[0], v1ha[1], v1hb[1], v1ha[2], v1hb[2], v1ha[3], v1hb[3]);
     WCA_S_PIN8(v1la[0], v1lb[0], v1la[1], v1lb[1], v1la[2], v1lb[2], v1la[3], v1lb[3]);
 #pragma unroll
     for (int s4 = 0; s4 < 4; ++s4) {
@@ -748,13 +687,13 @@ __global__ __launch_bounds__(256, 2) void attn_split32_kernel(AttnArgs a) {
 #undef WCA_ISSUE_V32
   };
   for (int kt = 0; kt < nkt; kt += 2) {
-    tile(IntC32<0>{}, kt);
-    if (kt + 1 < nkt) tile(IntC32<1>{}, kt + 1);
+    tile(IntC<0>{}, kt);
+    if (kt + 1 < nkt) tile(IntC<1>{}, kt + 1);
   }
 
   // ---- epilogue: ot[db][r] = O[q = l31][d = 32 db + (r&3) + 8 (r>>2) + 4 hh]; the two halves of a row are swapped pairwise so that
   // each lane stores 16 contiguous bytes of the hi row and of the lo row
-  const float inv = 1.0f / xor32_sumf(l_run);
+  const float inv = 1.0f / xor32_sum(l_run);
   half_t* op = a.O + (long)b * a.o_bs + (long)qrow * a.o_rs + h * 64;
 #pragma unroll
   for (int db = 0; db < 2; ++db)
@@ -790,50 +729,34 @@ __global__ __launch_bounds__(256, 2) void attn_split32_kernel(AttnArgs a) {
 
 hipError_t launch_attention_split(const AttnArgs& a, hipStream_t s) {
   if (a.nq <= 0 || a.B <= 0) return hipSuccess;
-  if (a.nk <= 0) return hipErrorInvalidValue;
-  if ((a.q_rs % 8) || (a.k_rs % 8) || (a.v_rs % 8) || (a.o_rs % 4)) return hipErrorInvalidValue;
+  if (!attn_args_ok(a)) return hipErrorInvalidValue;
   if ((a.q_lo % 8) || (a.k_lo % 8) || (a.v_lo % 8) || (a.o_lo % 4) || a.q_lo <= 0 || a.k_lo <= 0 || a.v_lo <= 0 || a.o_lo <= 0) return hipErrorInvalidValue;
-  if (a.cap != nullptr && ((a.cap_ld % 4) != 0 || a.cap_ld < ((a.cap_cols + 3) & ~3))) return hipErrorInvalidValue;
   const bool cap = a.cap != nullptr && a.cap_cols > 0;
-  const size_t shmem = 2 * 4 * TILE * sizeof(half_t);  // 64 KiB: two slots of K hi | K lo | V hi | V lo
-#define WCA_LAUNCH_AS(C, P, W)                                                                                               \
-  do {                                                                                                                       \
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_split_kernel<C, P, W>),                            \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);                             \
-    if (e != hipSuccess) return e;                                                                                           \
-    hipLaunchKernelGGL((attn_split_kernel<C, P, W>), dim3(((a.nq + (W) * 32 - 1) / ((W) * 32)) * a.H * a.B), dim3((W) * 64), shmem, s, a); \
-  } while (0)
+  constexpr int LDS = 2 * 4 * TILE * (int)sizeof(half_t);  // 64 KiB: two slots of K hi | K lo | V hi | V lo
+  const dim3 grid(((a.nq + 127) / 128) * a.H * a.B), block(256);   // 4 waves x 32 query rows
   // the encoder form (no mask, no capture) on the 32x32x16 kernel; AttnArgs.variant 1 (tests; switch attn_split_variant = 1 for A/B) keeps the 16x16x32 one
   const int variant = a.variant ? a.variant : debug_switch(DBG_ATTN_SPLIT_VARIANT);
   if (!a.causal && !cap && a.nq >= 64 && variant != 1 && (a.o_rs % 8) == 0 && (a.o_lo % 8) == 0) {
-#define WCA_LAUNCH_A32(D)                                                                                                             \
-  do {                                                                                                                                \
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_split32_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); \
-    if (e != hipSuccess) return e;                                                                                                    \
-    hipLaunchKernelGGL(attn_split32_kernel<D>, dim3(((a.nq + 127) / 128) * a.H * a.B), dim3(256), shmem, s, a);                       \
-  } while (0)
+    auto launch32 = [&](auto drop_c) { return launch_lds<attn_split32_kernel<decltype(drop_c)::value>, LDS>(grid, block, LDS, s, a); };
     switch (debug_switch(DBG_ATTN_SPLIT_DROP)) {   // 0 in the product; the other forms are the ablation's (wca_test_set_attn_split_drop)
-      case 0: WCA_LAUNCH_A32(0); break;
-      case 1: WCA_LAUNCH_A32(1); break;
-      case 2: WCA_LAUNCH_A32(2); break;
-      case 3: WCA_LAUNCH_A32(3); break;
-      case 4: WCA_LAUNCH_A32(4); break;
-      case 8: WCA_LAUNCH_A32(8); break;
-      case 9: WCA_LAUNCH_A32(9); break;
-      case 12: WCA_LAUNCH_A32(12); break;
-      case 15: WCA_LAUNCH_A32(15); break;
+      case 0: return launch32(IntC<0>{});
+      case 1: return launch32(IntC<1>{});
+      case 2: return launch32(IntC<2>{});
+      case 3: return launch32(IntC<3>{});
+      case 4: return launch32(IntC<4>{});
+      case 8: return launch32(IntC<8>{});
+      case 9: return launch32(IntC<9>{});
+      case 12: return launch32(IntC<12>{});
+      case 15: return launch32(IntC<15>{});
       default: return hipErrorInvalidValue;
     }
-#undef WCA_LAUNCH_A32
-    return hipGetLastError();
   }
   if (a.causal) {
-    if (cap) WCA_LAUNCH_AS(true, true, 4); else WCA_LAUNCH_AS(true, false, 4);
-  } else {
-    if (cap) WCA_LAUNCH_AS(false, true, 4); else WCA_LAUNCH_AS(false, false, 4);
+    if (cap) return launch_lds<attn_split_kernel<true, true>, LDS>(grid, block, LDS, s, a);
+    return launch_lds<attn_split_kernel<true, false>, LDS>(grid, block, LDS, s, a);
   }
-#undef WCA_LAUNCH_AS
-  return hipGetLastError();
+  if (cap) return launch_lds<attn_split_kernel<false, true>, LDS>(grid, block, LDS, s, a);
+  return launch_lds<attn_split_kernel<false, false>, LDS>(grid, block, LDS, s, a);
 }
 
 }  // namespace wca

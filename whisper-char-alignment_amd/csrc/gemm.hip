@@ -21,6 +21,7 @@
 #include "gemm_epilogue.h"
 #include <cstdlib>
 #include "kernels.h"
+#include "launch.h"
 #include "wca_common.h"
 
 namespace wca {
@@ -29,6 +30,11 @@ namespace {
 
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int TILE_ELEMS = 128 * 64;  // one operand tile (f16 elements)
+// dynamic LDS of the tile kernels: what a launch asks for, and the limit its kernel symbol is given (launch.h)
+constexpr int LDS_128 = 2 * 2 * TILE_ELEMS * (int)sizeof(half_t);          // gemm_f16_kernel: two slots of A | W, 64 KiB
+constexpr int LDS_256 = 2 * 2 * 256 * 64 * (int)sizeof(half_t);            // gemm256_f16_kernel: 128 KiB
+constexpr int LDS_256P = LDS_256 + 2 * 256 * (int)sizeof(float);           // gemm256p_f16_kernel: + the tile's bias values, double buffered
+constexpr int LDS_256P_LN = LDS_256P + (2 * 512 + 2560) * (int)sizeof(float);  // ... out_mode 3: + gamma | beta (double buffered) + the statistics exchange area
 
 struct RowPtrs {
   const half_t* p[4];
@@ -435,11 +441,6 @@ __global__ __launch_bounds__(512) void gemm256_f16_kernel(GemmArgs a) {
 // (k tile 0: hi, lo), (k tile 1: hi, lo), ... -- two steps per W K-tile. The W tile is fetched ONCE (on even steps, into its own
 // ring of two slots) and its register fragments are re-used by the odd step: per algorithmic K tile 3 tiles of DMA and 40 fragment
 // reads per wave instead of the 4 tiles / 48 reads of the K-doubled call [A_hi | A_lo] [W | W]^T, and no second copy of W.
-template <int V>
-struct GemmIntC {
-  static constexpr int value = V;
-};
-
 template <int OUT_MODE, bool GELU, int SITE, int SPLITW_MODE = 0>
 __global__ __launch_bounds__(512) void gemm256p_f16_kernel(GemmArgs a) {
   // SPLITW_MODE: 0 single f16 operands; 1 pair operands, two-slot rings for A and W (round 4); 2 pair operands, THREE A slots + ONE W slot (round 5, below)
@@ -746,7 +747,7 @@ __global__ __launch_bounds__(512) void gemm256p_f16_kernel(GemmArgs a) {
     };
     // (SPLITW with the step parity as a compile-time constant -- the loop unrolled by two -- spills 70-90 VGPRs: both steps' LDS
     //  base addresses stay live; the runtime parity costs two scalar branches per step)
-    for (int kt = 0; kt < nk; ++kt) kstep(GemmIntC<-1>{}, kt);
+    for (int kt = 0; kt < nk; ++kt) kstep(IntC<-1>{}, kt);
 
     {
       // opaque copies: keeps the epilogue's per-lane address arithmetic from being hoisted out of the tile loop
@@ -917,17 +918,17 @@ hipError_t launch_gemm(const GemmArgs& a_in, hipStream_t s) {
                                                                                                                 // accumulating launch; with an addend the pair product is the K-doubled call)
   if ((a.force_tile == 64 || a.force_tile == 0) && a.M <= 64 && (a.K % 512) == 0 && a.a_rows_per_batch == 0 && a.pos == nullptr && a.addend == nullptr && a.out_mode != 4 && a.a_lo <= 0) {
     const dim3 sgrid((unsigned)((a.N + 15) / 16)), sblock(256);
-#define WCA_LAUNCH_SK(OM, G) hipLaunchKernelGGL((gemm_skinny_f16_kernel<OM, G>), sgrid, sblock, 0, s, a)
     if (a.out_mode == 0) {
-      if (a.gelu) WCA_LAUNCH_SK(0, true); else WCA_LAUNCH_SK(0, false);
+      if (a.gelu) hipLaunchKernelGGL((gemm_skinny_f16_kernel<0, true>), sgrid, sblock, 0, s, a);
+      else hipLaunchKernelGGL((gemm_skinny_f16_kernel<0, false>), sgrid, sblock, 0, s, a);
     } else if (a.out_mode == 1) {
-      if (a.gelu) WCA_LAUNCH_SK(1, true); else WCA_LAUNCH_SK(1, false);
+      if (a.gelu) hipLaunchKernelGGL((gemm_skinny_f16_kernel<1, true>), sgrid, sblock, 0, s, a);
+      else hipLaunchKernelGGL((gemm_skinny_f16_kernel<1, false>), sgrid, sblock, 0, s, a);
     } else if (a.out_mode == 2 && !a.gelu) {
-      WCA_LAUNCH_SK(2, false);
+      hipLaunchKernelGGL((gemm_skinny_f16_kernel<2, false>), sgrid, sblock, 0, s, a);
     } else {
       return hipErrorInvalidValue;
     }
-#undef WCA_LAUNCH_SK
     return hipGetLastError();
   }
   if (a.force_tile == 64) return hipErrorInvalidValue;
@@ -966,9 +967,9 @@ hipError_t launch_gemm(const GemmArgs& a_in, hipStream_t s) {
   if (big) {
     grid = dim3((unsigned)tiles256);
     block = dim3(512);
-    shmem = 2 * 2 * 256 * 64 * sizeof(half_t);  // 128 KiB
+    shmem = LDS_256;
     if (pipelined) {
-      shmem += 2 * 256 * sizeof(float);  // the tile's bias values, double buffered
+      shmem = LDS_256P;
       // persistent: one workgroup per CU walks tiles blockIdx.x, + gridDim.x, ... (the ring-slot parity carries
       // over a tile boundary only for an even number of K tiles); force_tile 258 = one tile per workgroup
       const int nk = (splitw ? 2 : 1) * (a.K / BK);
@@ -980,7 +981,7 @@ hipError_t launch_gemm(const GemmArgs& a_in, hipStream_t s) {
     const int ntn = (a.N + BN - 1) / BN, ntm = (a.M + BM - 1) / BM;
     grid = dim3(ntn * ntm);
     block = dim3(256);
-    shmem = 2 * 2 * TILE_ELEMS * sizeof(half_t);  // 64 KiB
+    shmem = LDS_128;
     // few tiles and a long K (fc2 of a one- or two-utterance batch: 96 tiles x 64 K tiles): split K over up to 4 workgroups
     // per tile; partial tiles go to the caller's workspace and a second kernel adds them in order (deterministic)
     splitk = 1;
@@ -994,37 +995,32 @@ hipError_t launch_gemm(const GemmArgs& a_in, hipStream_t s) {
     }
     grid.y = (unsigned)splitk;
   }
-  // the dynamic-LDS limit is a per-device property of each kernel symbol: remembered per (symbol, device) so that several
-  // engines (one per GPU) in one process and concurrent host threads are served correctly
-#define WCA_LAUNCH_K(...)                                                                         \
-  do {                                                                                            \
-    static std::atomic<unsigned> attr_mask{0};                                                    \
-    if (!(attr_mask.load(std::memory_order_acquire) & (1u << (dev & 31)))) {                      \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(__VA_ARGS__),              \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); \
-      if (e != hipSuccess) return e;                                                              \
-      attr_mask.fetch_or(1u << (dev & 31), std::memory_order_release);                            \
-    }                                                                                             \
-    hipLaunchKernelGGL((__VA_ARGS__), grid, block, shmem, s, a);                                  \
-  } while (0)
-#define WCA_LAUNCH_S(OM, G, S)                            \
-  do {                                                    \
-    if (pipelined && splitw && ring == 1) { if ((S) == 4) WCA_LAUNCH_K(gemm256p_f16_kernel<OM, G, 4, 1>); else WCA_LAUNCH_K(gemm256p_f16_kernel<OM, G, 1, 1>); } \
-    else if (pipelined && splitw) { if ((S) == 4) WCA_LAUNCH_K(gemm256p_f16_kernel<OM, G, 4, 2>); else if ((S) == 3) WCA_LAUNCH_K(gemm256p_f16_kernel<OM, G, 3, 2>); else if ((S) == 2) WCA_LAUNCH_K(gemm256p_f16_kernel<OM, G, 2, 2>); else WCA_LAUNCH_K(gemm256p_f16_kernel<OM, G, 1, 2>); } \
-    else if (pipelined) WCA_LAUNCH_K(gemm256p_f16_kernel<OM, G, S>); \
-    else if (big) WCA_LAUNCH_K(gemm256_f16_kernel<OM, G, S>);  \
-    else WCA_LAUNCH_K(gemm_f16_kernel<OM, G, S>);         \
-  } while (0)
-#define WCA_LAUNCH(OM, G)                     \
-  do {                                        \
-    switch (a.site) {                         \
-      case 1: WCA_LAUNCH_S(OM, G, 1); break;  \
-      case 2: WCA_LAUNCH_S(OM, G, 2); break;  \
-      case 3: WCA_LAUNCH_S(OM, G, 3); break;  \
-      case 4: WCA_LAUNCH_S(OM, G, 4); break;  \
-      default: WCA_LAUNCH_S(OM, G, 0); break; \
-    }                                         \
-  } while (0)
+  // the kernel of this launch from its compile-time out-mode, GELU and site. Pair operands: the two-slot ring forms exist for sites 1 and 4,
+  // the three-slot forms for sites 1-4; every other site takes the site-1 form
+  auto launch = [&](auto om_c, auto gelu_c, auto site_c) -> hipError_t {
+    constexpr int OM = decltype(om_c)::value, S = decltype(site_c)::value;
+    constexpr bool G = decltype(gelu_c)::value != 0;
+    if constexpr (OM == 3) {
+      return launch_lds<gemm256p_f16_kernel<3, false, S>, LDS_256P_LN>(grid, block, shmem, s, a);
+    } else {
+      if (pipelined && splitw && ring == 1) return launch_lds<gemm256p_f16_kernel<OM, G, S == 4 ? 4 : 1, 1>, LDS_256P>(grid, block, shmem, s, a);
+      if (pipelined && splitw) return launch_lds<gemm256p_f16_kernel<OM, G, S == 0 ? 1 : S, 2>, LDS_256P>(grid, block, shmem, s, a);
+      if (pipelined) return launch_lds<gemm256p_f16_kernel<OM, G, S>, LDS_256P>(grid, block, shmem, s, a);
+      if (big) return launch_lds<gemm256_f16_kernel<OM, G, S>, LDS_256>(grid, block, shmem, s, a);
+      return launch_lds<gemm_f16_kernel<OM, G, S>, LDS_128>(grid, block, shmem, s, a);
+    }
+  };
+  auto by_site = [&](auto om_c, auto gelu_c) -> hipError_t {
+    switch (a.site) {
+      case 1: return launch(om_c, gelu_c, IntC<1>{});
+      case 2: return launch(om_c, gelu_c, IntC<2>{});
+      case 3: return launch(om_c, gelu_c, IntC<3>{});
+      case 4: return launch(om_c, gelu_c, IntC<4>{});
+      default: return launch(om_c, gelu_c, IntC<0>{});
+    }
+  };
+  auto by_gelu = [&](auto om_c) -> hipError_t { return a.gelu ? by_site(om_c, IntC<1>{}) : by_site(om_c, IntC<0>{}); };
+  hipError_t e;
   if (a.out_mode == 3) {
     // residual + LayerNorm epilogue: persistent 256 x 256 kernel only (every workgroup of a 256-row panel must be resident:
     // one workgroup per CU, grid <= CUs), N a multiple of 256; the caller falls back to out_mode 2 + launch_layernorm_f16
@@ -1033,33 +1029,24 @@ hipError_t launch_gemm(const GemmArgs& a_in, hipStream_t s) {
         !a.ln_beta || !a.ln_out || !a.ln_stats || !a.ln_cnt || (a.ldc & 3) || (a.ln_ld & 7))
       return hipErrorInvalidValue;
     const size_t cnt_bytes = (((size_t)((a.M + 255) / 256) * sizeof(unsigned)) + 15) / 16 * 16;
-    hipError_t e = hipMemsetAsync(a.ln_cnt, 0, cnt_bytes, s);
+    e = hipMemsetAsync(a.ln_cnt, 0, cnt_bytes, s);
     if (e != hipSuccess) return e;
-    shmem += (2 * 512 + 2560) * sizeof(float);  // gamma | beta (double buffered) + the statistics exchange area
+    shmem = LDS_256P_LN;                         // + gamma | beta (double buffered) + the statistics exchange area
     grid = dim3((unsigned)(n_cu & ~7));          // round-based panel walk: 8 XCD labels x n_cu / 8 workgroups (idle ones exit)
-    switch (a.site) {
-      case 4: WCA_LAUNCH_K(gemm256p_f16_kernel<3, false, 4>); break;
-      default: WCA_LAUNCH_K(gemm256p_f16_kernel<3, false, 1>); break;
-    }
+    e = a.site == 4 ? launch(IntC<3>{}, IntC<0>{}, IntC<4>{}) : launch(IntC<3>{}, IntC<0>{}, IntC<1>{});
   } else if (a.out_mode == 0) {
-    if (a.gelu) WCA_LAUNCH(0, true); else WCA_LAUNCH(0, false);
+    e = by_gelu(IntC<0>{});
   } else if (a.out_mode == 1) {
-    if (a.gelu) WCA_LAUNCH(1, true); else WCA_LAUNCH(1, false);
+    e = by_gelu(IntC<1>{});
   } else if (a.out_mode == 2) {
     if (a.gelu) return hipErrorInvalidValue;
-    WCA_LAUNCH(2, false);
+    e = by_site(IntC<2>{}, IntC<0>{});
   } else if (a.out_mode == 4) {
-    if (a.gelu) WCA_LAUNCH(4, true); else WCA_LAUNCH(4, false);
+    e = by_gelu(IntC<4>{});
   } else {
     return hipErrorInvalidValue;
   }
-#undef WCA_LAUNCH
-#undef WCA_LAUNCH_S
-#undef WCA_LAUNCH_K
-  {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
+  if (e != hipSuccess) return e;
   if (splitk > 1) {
     const long n4 = (long)a.M * (a.N / 4);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a.sk_part, splitk, a.M, a.N, a.bias,

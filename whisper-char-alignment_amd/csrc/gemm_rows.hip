@@ -19,19 +19,13 @@
 // v_mfma_f32_16x16x32_f16 with W as the A operand; the four quarter accumulators of an m-tile are summed through LDS in
 // quarter order by waves 0..3 (the summation order of gemm_skinny_f16_kernel: S = 1 results are bit-identical to
 // LayerNorm kernel + that kernel).
-#include <atomic>
-
 #include "kernels.h"
+#include "launch.h"
 #include "wca_common.h"
 
 namespace wca {
 
 namespace {
-
-template <int V>
-struct IntC {
-  static constexpr int value = V;
-};
 
 constexpr int ROWS = 64;     // rows of one workgroup (grid.y walks 64-row blocks)
 constexpr int MAXU = 8;      // 32-wide k steps per wave: K / S <= 1024
@@ -373,53 +367,18 @@ hipError_t launch_gemm_rows(const GemmArgs& a_in, hipStream_t s) {
   }
   const dim3 grid((unsigned)(((NG + a.groups - 1) / a.groups) * a.splitk), (unsigned)((a.M + ROWS - 1) / ROWS)), block(512);
   const size_t shmem = (size_t)ROWS * (a.K / a.splitk + APAD) * sizeof(half_t) + 4 * 4 * 4 * 64 * sizeof(float) + 16;
-  int dev = 0;
-  {
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-  }
-#define WCA_ROWS_K(AM, OM, G)                                                                                       \
-  do {                                                                                                              \
-    static std::atomic<unsigned> attr_mask{0};                                                                      \
-    if (!(attr_mask.load(std::memory_order_acquire) & (1u << (dev & 31)))) {                                        \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_rows_f16_kernel<AM, OM, G, false>),     \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                   \
-      if (e != hipSuccess) return e;                                                                                \
-      attr_mask.fetch_or(1u << (dev & 31), std::memory_order_release);                                              \
-    }                                                                                                               \
-    hipLaunchKernelGGL((gemm_rows_f16_kernel<AM, OM, G, false>), grid, block, shmem, s, a);                         \
-  } while (0)
-#define WCA_ROWS_KV(AM)                                                                                             \
-  do {                                                                                                              \
-    static std::atomic<unsigned> attr_mask{0};                                                                      \
-    if (!(attr_mask.load(std::memory_order_acquire) & (1u << (dev & 31)))) {                                        \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_rows_f16_kernel<AM, 0, false, true>),   \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                   \
-      if (e != hipSuccess) return e;                                                                                \
-      attr_mask.fetch_or(1u << (dev & 31), std::memory_order_release);                                              \
-    }                                                                                                               \
-    hipLaunchKernelGGL((gemm_rows_f16_kernel<AM, 0, false, true>), grid, block, shmem, s, a);                       \
-  } while (0)
-#define WCA_ROWS_A(OM, G)                \
-  do {                                   \
-    if (ln) WCA_ROWS_K(1, OM, G);        \
-    else WCA_ROWS_K(0, OM, G);           \
-  } while (0)
-  if (a.kv_t_rows != nullptr) {  // (out_mode 0 and no GELU: checked above)
-    if (ln) WCA_ROWS_KV(1); else WCA_ROWS_KV(0);
-  } else if (a.out_mode == 0) {
-    if (a.gelu) WCA_ROWS_A(0, true); else WCA_ROWS_A(0, false);
-  } else if (a.out_mode == 1 && !a.gelu) {
-    WCA_ROWS_A(1, false);
-  } else if (a.out_mode == 2 && !a.gelu) {
-    WCA_ROWS_A(2, false);
-  } else {
-    return hipErrorInvalidValue;
-  }
-#undef WCA_ROWS_A
-#undef WCA_ROWS_KV
-#undef WCA_ROWS_K
-  return hipGetLastError();
+  // A_MODE 1 = LayerNorm prologue; the per-row KV append (out_mode 0 and no GELU: checked above) has its own instances
+  auto launch = [&](auto om_c, auto gelu_c, auto kv_rows_c) -> hipError_t {
+    constexpr int OM = decltype(om_c)::value;
+    constexpr bool G = decltype(gelu_c)::value != 0, KVR = decltype(kv_rows_c)::value != 0;
+    if (ln) return launch_lds<gemm_rows_f16_kernel<1, OM, G, KVR>, LDS_DEVICE_MAX>(grid, block, shmem, s, a);
+    return launch_lds<gemm_rows_f16_kernel<0, OM, G, KVR>, LDS_DEVICE_MAX>(grid, block, shmem, s, a);
+  };
+  if (a.kv_t_rows != nullptr) return launch(IntC<0>{}, IntC<0>{}, IntC<1>{});
+  if (a.out_mode == 0) return a.gelu ? launch(IntC<0>{}, IntC<1>{}, IntC<0>{}) : launch(IntC<0>{}, IntC<0>{}, IntC<0>{});
+  if (a.out_mode == 1 && !a.gelu) return launch(IntC<1>{}, IntC<0>{}, IntC<0>{});
+  if (a.out_mode == 2 && !a.gelu) return launch(IntC<2>{}, IntC<0>{}, IntC<0>{});
+  return hipErrorInvalidValue;
 }
 
 }  // namespace wca

@@ -7,6 +7,7 @@
 //   median_filter : standalone whisper.timing.median_filter
 #include <cstdlib>
 #include "kernels.h"
+#include "launch.h"
 #include "wca_common.h"
 
 namespace wca {
@@ -716,43 +717,25 @@ hipError_t launch_head_stats(const HeadStatsArgs& a, hipStream_t s) {
   dim3 grid(a.LH, a.B), block(256);
   const int w = a.medfilt_width;
   // the instruction-lean kernel (same bits) for logits input and the unrolled filter widths; the switch head_stats_general keeps the general one (A/B, tests)
-  if (!a.input_is_weights && w <= 9 && !debug_switch(DBG_HEAD_STATS_GENERAL)) {
-#define WCA_HSF(NPL, W)                                                                                   \
-  do {                                                                                                    \
-    const size_t shm = sizeof(float) * (4 * (size_t)(64 * NPL + 2 * HALO) + 8 * (size_t)Fmax + 16);      \
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(head_stats_fast_kernel<NPL, W>),     \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);             \
-    if (e != hipSuccess) return e;                                                                        \
-    hipLaunchKernelGGL((head_stats_fast_kernel<NPL, W>), grid, block, shm, s, a);                         \
-    return hipGetLastError();                                                                             \
-  } while (0)
-#define WCA_HSF_W(NPL)                     \
-  switch (w) {                             \
-    case 1: WCA_HSF(NPL, 1);               \
-    case 3: WCA_HSF(NPL, 3);               \
-    case 5: WCA_HSF(NPL, 5);               \
-    case 7: WCA_HSF(NPL, 7);               \
-    default: WCA_HSF(NPL, 9);              \
-  }
-    if (Fmax <= 64 * 8) { WCA_HSF_W(8); }
-    else if (Fmax <= 64 * 16) { WCA_HSF_W(16); }
-    else { WCA_HSF_W(24); }
-#undef WCA_HSF_W
-#undef WCA_HSF
-  }
-  const size_t shmem = sizeof(float) * (4 * (size_t)(Fmax + 2 * HALO) + 8 * (size_t)Fmax + 16);
-#define WCA_HS(NPL)                                                                                \
-  do {                                                                                             \
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(head_stats_kernel<NPL>),      \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);    \
-    if (e != hipSuccess) return e;                                                                 \
-    hipLaunchKernelGGL((head_stats_kernel<NPL>), grid, block, shmem, s, a);                        \
-  } while (0)
-  if (Fmax <= 64 * 8) WCA_HS(8);
-  else if (Fmax <= 64 * 16) WCA_HS(16);
-  else WCA_HS(24);
-#undef WCA_HS
-  return hipGetLastError();
+  const bool lean = !a.input_is_weights && w <= 9 && !debug_switch(DBG_HEAD_STATS_GENERAL);
+  // dynamic LDS: the filter's row buffers (one per wave; whole 64-value groups in the lean kernel) + the statistics area
+  auto shmem_of = [&](int row_floats) { return sizeof(float) * (4 * (size_t)(row_floats + 2 * HALO) + 8 * (size_t)Fmax + 16); };
+  auto launch = [&](auto npl_c) -> hipError_t {
+    constexpr int NPL = decltype(npl_c)::value;
+    if (!lean) return launch_lds<head_stats_kernel<NPL>, LDS_DEVICE_MAX>(grid, block, shmem_of(Fmax), s, a);
+    const size_t shm = shmem_of(64 * NPL);
+    switch (w) {
+      case 1: return launch_lds<head_stats_fast_kernel<NPL, 1>, LDS_DEVICE_MAX>(grid, block, shm, s, a);
+      case 3: return launch_lds<head_stats_fast_kernel<NPL, 3>, LDS_DEVICE_MAX>(grid, block, shm, s, a);
+      case 5: return launch_lds<head_stats_fast_kernel<NPL, 5>, LDS_DEVICE_MAX>(grid, block, shm, s, a);
+      case 7: return launch_lds<head_stats_fast_kernel<NPL, 7>, LDS_DEVICE_MAX>(grid, block, shm, s, a);
+      default: return launch_lds<head_stats_fast_kernel<NPL, 9>, LDS_DEVICE_MAX>(grid, block, shm, s, a);
+    }
+  };
+  // values per lane: the smallest of 8, 16, 24 whose 64 lanes hold the longest row
+  if (Fmax <= 64 * 8) return launch(IntC<8>{});
+  if (Fmax <= 64 * 16) return launch(IntC<16>{});
+  return launch(IntC<24>{});
 }
 
 hipError_t launch_topk(const float* scores, int LH, int B, int k, int* sel_idx, float* sel_score, hipStream_t s) {
@@ -796,14 +779,9 @@ hipError_t launch_median_filter(const float* in, float* out, long rows, int F, i
   if (rows <= 0 || F <= 0) return hipSuccess;
   if (width < 1 || (width & 1) == 0 || (width >> 1) > HALO) return hipErrorInvalidValue;
   const size_t shmem = sizeof(float) * 4 * (size_t)(F + 2 * HALO);
-  if (shmem > 160 * 1024) return hipErrorInvalidValue;
   long blocks = (rows + 3) / 4;
   if (blocks > 8192) blocks = 8192;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(median_filter_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(median_filter_kernel, dim3((unsigned)blocks), dim3(256), shmem, s, in, out, rows, F, width);
-  return hipGetLastError();
+  return launch_lds<median_filter_kernel, LDS_DEVICE_MAX>(dim3((unsigned)blocks), dim3(256), shmem, s, in, out, rows, F, width);   // (refuses rows past the CU's LDS)
 }
 
 }  // namespace wca

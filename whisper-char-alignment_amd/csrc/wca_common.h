@@ -19,6 +19,13 @@ typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
 
 constexpr int kWave = 64;
 
+// A compile-time integer as a value: the argument of a generic lambda whose body needs the number as a constant (ring slots, register
+// ring positions), and what a launcher's switch hands to the code that picks a kernel's template arguments.
+template <int V>
+struct IntC {
+  static constexpr int value = V;
+};
+
 // ---- LDS-DMA: 16 bytes per lane, LDS destination = wave-uniform base + lane*16 ----
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const WCA_GLOBAL void*)gsrc, (WCA_LDS void*)lds_wave_base, 16, 0, 0);
