@@ -277,19 +277,26 @@ def test_per_row_sample_caps(small, tok, mel4):
         np.testing.assert_allclose(lp[1], lp2[0], rtol=1e-4, atol=1e-4)
 
 
-def test_two_streams_agree_bit_for_bit(pkg, tok):
-    """The 512-wide dimensions and B = 20 of test_decode_modes_agree (16 + 4 rows on two streams), prompt lengths cycling through
-    0, 7, 30, 101: one and two streams give the same arithmetic per row."""
+@pytest.fixture(scope="module")
+def wide20(pkg):
     dims = pkg.ModelDimensions(80, 1500, 512, 8, 2, 51865, 448, 512, 8, 2)
     m = pkg.WhisperAMD(dims, device="cuda:0", max_batch=20, precision="f16")
     m.load_state_dict(_m("synthetic").random_state_dict(dims, seed=11))
+    return m, dims, _mels(m, range(40, 60), n_samples=32000)
+
+
+@pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
+def test_two_streams_agree_bit_for_bit(wide20, tok, fused):
+    """The 512-wide dimensions and B = 20 of test_decode_modes_agree (16 + 4 rows on two streams), prompt lengths cycling through
+    0, 7, 30, 101: one and two streams give the same arithmetic per row. Unfused, the second half-batch appends its K/V through
+    kv_append_rows_kernel at an offset into the position tables: the only path that reads them there."""
+    m, dims, mel = wide20
     B = 20
-    mel = _mels(m, range(40, 40 + B), n_samples=32000)
     lengths = [3 if p == 0 else 4 + p for p in [(0, 7, 30, 101)[b % 4] for b in range(B)]]
     out = {}
     try:
         for streams in (1, 2):
-            m.set_decode_mode(True, streams)
+            m.set_decode_mode(fused, streams)
             out[streams] = _rows(m, tok, dims, mel, lengths, 6)
     finally:
         m.set_decode_mode(True, 1)

@@ -239,6 +239,68 @@ def test_words_one_alignment_per_round(tr, wca, fake_vocab):
     assert all(len(seg["words"]) == 2 for res in got for seg in res["segments"])
 
 
+class _ScriptedWordModel(_WordModel):
+    """_WordModel with a scripted decoder: a window carries its seek, and script[seek] = (sampled tokens, sum_logprob, no_speech_prob).
+    Records every engine call with its argument shapes."""
+
+    def __init__(self, dims, script):
+        super().__init__(dims, [], 1)
+        self.script, self.calls = script, []
+
+    def mel_window(self, mel_long, seek, size):
+        self.calls.append(("mel_window", tuple(mel_long.shape), seek, size))
+        w = torch.zeros(self.dims.n_mels, 3000)
+        w[0, 0] = float(seek)
+        return w
+
+    def greedy_decode(self, mel, pcm, n_samples, initial, sup, blank, sample_len, eot, timestamp_begin, apply_timestamp_rules,
+                      max_initial_timestamp_index, batch, no_speech, sot_index=0, prefill=0):
+        out, sum_logprob, no_speech_prob = self.script[int(round(float(mel[0, 0, 0])))]
+        self.calls.append(("greedy_decode", tuple(mel.shape), list(initial), sample_len, batch, sot_index, prefill))
+        self.decoded.append(batch)
+        toks = np.full((1, len(initial) + sample_len), eot, np.int32)
+        toks[0, :len(initial)] = initial
+        toks[0, len(initial):len(initial) + len(out)] = out
+        self.last_no_speech_prob = np.full(1, no_speech_prob, np.float32)
+        return toks, np.array([len(initial) + len(out)], np.int32), np.full(1, sum_logprob, np.float32)
+
+    def align_batch(self, pcm, n_samples, tokens, n_tok, max_frames, opts, enqueue_only=False, token_logprobs_vocab_end=None):
+        self.calls.append(("align_batch", tuple(tokens.shape), tokens.tolist(), list(n_tok), list(max_frames), token_logprobs_vocab_end))
+        return super().align_batch(pcm, n_samples, tokens, n_tok, max_frames, opts, enqueue_only, token_logprobs_vocab_end)
+
+
+@pytest.mark.parametrize("words", [False, True], ids=["segments", "words"])
+@pytest.mark.parametrize("condition", [True, False], ids=["conditioned", "unconditioned"])
+def test_transcribe_is_transcribe_batch_of_one(tr, wca, fake_vocab, condition, words):
+    """94 s = four windows: one that ends inside speech (seek advances to its timestamp pair), one skipped as no speech, two plain
+    ones. transcribe(x) and transcribe_batch([x])[0] give the same result dict and make the same engine calls with the same shapes."""
+    tk = importlib.import_module("whisper-char-alignment_amd.tokenizer").get_tokenizer(True, language="en", task="transcribe", vocab_path=fake_vocab)
+    dims = wca.ModelDimensions(80, 1500, 256, 4, 2, 51865, 448, 256, 4, 2)
+    ts, hw = tk.timestamp_begin, tk.encode(" hello world")
+    script = {0: ([ts, *hw, ts + 200, ts + 200, *hw], -1.0, 0.05),
+              400: ([ts, *hw, ts + 100], -100.0, 0.9),
+              3400: ([ts, *hw, ts + 100], -1.0, 0.05),
+              6400: ([ts, *hw, ts + 50], -1.0, 0.05)}
+    audio = np.zeros(16000 * 94, np.float32)
+    kw = dict(language="en", vocab_path=fake_vocab, initial_prompt="abcd", condition_on_previous_text=condition, word_timestamps=words,
+              word_confidence=words)
+    one, many = _ScriptedWordModel(dims, script), _ScriptedWordModel(dims, script)
+    res = tr.transcribe(one, audio, **kw)
+    got = tr.transcribe_batch(many, [audio], **kw)
+    assert len(got) == 1 and got[0] == res
+    assert many.calls == one.calls
+    assert [(w["seek"], w["advance"], w["skipped"]) for w in res["windows"]] == [(0, 400, False), (400, 3000, True), (3400, 3000, False),
+                                                                                 (6400, 3000, False)]
+    assert [w["max_frames"] for w in res["windows"]] == [200, None, 1500, 1500]
+    assert [c[0] for c in one.calls].count("greedy_decode") == 4 and [c[0] for c in one.calls].count("align_batch") == (3 if words else 0)
+    assert all(c[1] == (1, 80, 3000) and c[4] == 1 for c in one.calls if c[0] == "greedy_decode")
+    prompts = [c[2][1:c[5]] if c[5] else [] for c in one.calls if c[0] == "greedy_decode"]
+    first = [ts, *hw, ts + 200]
+    assert prompts[0] == tk.encode(" abcd")
+    assert prompts[1] == prompts[2] == (tk.encode(" abcd") + first if condition else [])
+    assert all(len(seg["words"]) == (2 if words else 0) for seg in res["segments"]) and len(res["segments"]) == 3
+
+
 def _write_wav(path, n):
     data = np.zeros(n, dtype="<i2").tobytes()
     with open(path, "wb") as f:

@@ -1,0 +1,101 @@
+#!/usr/bin/env python3
+"""Every result of the greedy decode path on seeded small engines, one file per result, for byte-for-byte comparison (cmp) of two builds
+of this tree: a refactor of the decode path runs this in the tree before and in the tree after.
+
+  * uniform decode (wca_greedy_decode / _ex): the plain start, and a 12-token prompt with prefill 0 and 1
+  * ragged per-row decode (wca_greedy_decode_rows) with per-row budgets, in both precision modes
+    each fused and unfused, on one and on two streams, B = 20 at 512-wide dims (16 + 4 rows on two streams):
+    tokens, n_tokens, sum_logprob, no_speech_prob
+  * get_attentions weights and logits of a ragged batch of 3 in both precision modes (the teacher-forced decoder)
+  * transcribe of two synthetic recordings (45 s and 70 s) alone and as a transcribe_batch, word_timestamps=True, on a synthetic vocabulary
+
+usage: decode_dump.py OUTDIR [one-stream]     one-stream: one decode stream and set_overlap(0) only, for an ordered kernel trace"""
+import base64
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+wca = importlib.import_module("whisper-char-alignment_amd")
+syn, audio, decoding, tokenizer, tr = (importlib.import_module("whisper-char-alignment_amd." + n)
+                                       for n in ("synthetic", "audio", "decoding", "tokenizer", "transcribe"))
+out_dir, one_stream = sys.argv[1], len(sys.argv) > 2
+os.makedirs(out_dir, exist_ok=True)
+tok = tokenizer.get_tokenizer(True, language="en", task="transcribe")
+
+
+def save(name, arrays, keys=("tokens", "n_tokens", "sum_logprob", "no_speech_prob")):
+    for key, a in zip(keys, arrays):
+        np.save(os.path.join(out_dir, "%s.%s.npy" % (name, key)), a.cpu().numpy() if isinstance(a, torch.Tensor) else a)
+
+
+def initial(n):
+    """n initial tokens: the bare sot sequence (n = 3) or [sot_prev, n - 4 prompt tokens, *sot_sequence]; and the position of <|sot|>."""
+    sot = list(tok.sot_sequence)
+    if n == len(sot):
+        return sot, 0
+    prompt = [(37 * i) % 5000 + 200 for i in range(n - len(sot) - 1)]
+    return [tok.sot_prev] + prompt + sot, 1 + len(prompt)
+
+
+def fake_vocab(path):
+    """A tiktoken-format vocabulary of the right size: the 256 bytes and synthetic 4-letter tokens."""
+    ranks, i = dict(tokenizer._byte_ranks()), 0
+    while len(ranks) < 50257:
+        w = bytes([97 + (i % 26), 97 + (i // 26) % 26, 97 + (i // 676) % 26, 97 + (i // 17576) % 26])
+        i += 1
+        ranks.setdefault(w, len(ranks))
+    with open(path, "wb") as f:
+        for tokb, r in sorted(ranks.items(), key=lambda kv: kv[1]):
+            f.write(base64.b64encode(tokb) + b" " + str(r).encode() + b"\n")
+    return path
+
+
+B = 20
+dims = wca.ModelDimensions(80, 1500, 512, 8, 2, 51865, 448, 512, 8, 2)
+m = wca.WhisperAMD(dims, device="cuda:0", max_batch=B, precision="f16")
+m.load_state_dict(syn.random_state_dict(dims, seed=11))
+if one_stream:
+    m.set_overlap(0)
+mel = torch.stack([audio.log_mel_spectrogram(audio.pad_or_trim(torch.from_numpy(syn.synth_audio(s, n_samples=32000))), 80, model=m)
+                   for s in range(40, 40 + B)]).cuda()
+sup, blank = decoding.filter_masks(tok, decoding.DecodingOptions(language="en"), dims.n_vocab)
+kw = dict(eot=tok.eot, timestamp_begin=tok.timestamp_begin, apply_timestamp_rules=True, max_initial_timestamp_index=50, no_speech=tok.no_speech)
+plans = [initial(3 if p == 0 else 4 + p) for p in [(0, 7, 30, 101)[b % 4] for b in range(B)]]
+budgets = [10 - b % 4 for b in range(B)]
+att_rows = [[*tok.sot_sequence, tok.no_timestamps, *[300 + 7 * i for i in range(n)], tok.eot] for n in (9, 4, 6)]
+att_tokens = torch.full((3, max(len(r) for r in att_rows)), tok.eot, dtype=torch.int64)
+for b, r in enumerate(att_rows):
+    att_tokens[b, :len(r)] = torch.tensor(r)
+
+for precision in ("f16", "reference"):
+    m.set_precision(precision)
+    for fused in (True, False):
+        for streams in (1,) if one_stream else (1, 2):
+            m.set_decode_mode(fused, streams)
+            tag = "%s.%s.streams%d" % (precision, "fused" if fused else "unfused", streams)
+            for name, n, prefill in (("plain", 3, 0), ("prompt.prefill0", 12, 0), ("prompt.prefill1", 12, 1)) if precision == "f16" else ():
+                init, sot_index = initial(n)
+                out = m.greedy_decode(mel, None, None, init, sup, blank, sample_len=10, sot_index=sot_index, prefill=prefill, **kw)
+                save("uniform.%s.%s" % (name, tag), out + (m.last_no_speech_prob,))
+            out = m.greedy_decode_rows(mel, None, None, [p[0] for p in plans], [p[1] for p in plans], budgets, sup, blank, **kw)
+            save("rows.%s" % tag, out + (m.last_no_speech_prob,))
+    m.set_decode_mode(True, 1)
+    save("attentions.%s" % precision, m.get_attentions(mel[:3], att_tokens, [100, 80, 60], 3, 1.0, n_tok=[len(r) for r in att_rows]),
+         keys=("weights", "logits"))
+
+m.set_precision("f16")
+vocab = fake_vocab(os.path.join(out_dir, "fake.tiktoken"))
+recordings = [syn.synth_audio(30 + i, 16000 * s + 40 * i) for i, s in enumerate((45, 70))]
+tkw = dict(language="en", vocab_path=vocab, word_timestamps=True)
+results = {"alone%d" % i: tr.transcribe(m, a, **tkw) for i, a in enumerate(recordings)}
+results.update(("batch%d" % i, r) for i, r in enumerate(tr.transcribe_batch(m, recordings, **tkw)))
+for name, res in results.items():
+    with open(os.path.join(out_dir, "transcribe.%s.json" % name), "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+torch.cuda.synchronize()
+print("decode_dump: %d files in %s" % (len(os.listdir(out_dir)), out_dir))

@@ -17,8 +17,12 @@ namespace wca {
 
 namespace {
 
-__global__ __launch_bounds__(256) void embed_step_kernel(const int* __restrict__ tokens, int T_max, int t, const half_t* __restrict__ tok_emb,
-                                                         const float* __restrict__ pos_emb, float* __restrict__ x, int d, int n_vocab) {
+// a row's own position (the rows of wca_greedy_decode_rows sit at different ones), clamped to its n slots
+__device__ __forceinline__ int clamp_pos(int t, int n) { return min(max(t, 0), n - 1); }
+
+// x[b] = token_embedding[tokens[b][t]] + positional_embedding[t]
+__device__ __forceinline__ void embed_step_row(const int* tokens, int T_max, int t, const half_t* tok_emb, const float* pos_emb, float* x, int d,
+                                               int n_vocab) {
   const int b = blockIdx.x;
   long tok = tokens[(long)b * T_max + t];
   tok = (tok < 0 || tok >= n_vocab) ? 0 : tok;  // ids come from decode_select / the validated prompt; never read out of bounds
@@ -29,8 +33,7 @@ __global__ __launch_bounds__(256) void embed_step_kernel(const int* __restrict__
 }
 
 // qkv [B][3d] (q | k | v) -> kc / vc [B][T_max][d] at position t (8 halfs per thread)
-__global__ __launch_bounds__(256) void kv_append_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ kc, half_t* __restrict__ vc,
-                                                        int T_max, int t, int d) {
+__device__ __forceinline__ void kv_append_row(const half_t* qkv, half_t* kc, half_t* vc, int T_max, int t, int d) {
   const int b = blockIdx.x;
   const half8* k = reinterpret_cast<const half8*>(qkv + (long)b * 3 * d + d);
   const half8* v = reinterpret_cast<const half8*>(qkv + (long)b * 3 * d + 2 * d);
@@ -42,33 +45,30 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const half_t* __restrict
   }
 }
 
-// The two kernels above with row b at its own position t_rows[b] (wca_greedy_decode_rows: the rows of a batch sit at different decoder
-// positions); the position is clamped to the row's T_max slots.
+// Each body above has two kernels that differ only in where the position comes from: every row at t, or row b at its own t_rows[b]. They stay
+// two __global__ symbols with plain scalar / pointer arguments (a position struct as the argument, or one template over the two, changes the
+// generated code), and they read the block index as the int the bodies use: the index types decide the address arithmetic.
+__global__ __launch_bounds__(256) void embed_step_kernel(const int* __restrict__ tokens, int T_max, int t, const half_t* __restrict__ tok_emb,
+                                                         const float* __restrict__ pos_emb, float* __restrict__ x, int d, int n_vocab) {
+  embed_step_row(tokens, T_max, t, tok_emb, pos_emb, x, d, n_vocab);
+}
+
+__global__ __launch_bounds__(256) void kv_append_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ kc, half_t* __restrict__ vc,
+                                                        int T_max, int t, int d) {
+  kv_append_row(qkv, kc, vc, T_max, t, d);
+}
+
 __global__ __launch_bounds__(256) void embed_step_rows_kernel(const int* __restrict__ tokens, int T_max, const int* __restrict__ t_rows,
                                                               const half_t* __restrict__ tok_emb, const float* __restrict__ pos_emb,
                                                               float* __restrict__ x, int d, int n_vocab) {
   const int b = blockIdx.x;
-  const int t = min(max(t_rows[b], 0), T_max - 1);
-  long tok = tokens[(long)b * T_max + t];
-  tok = (tok < 0 || tok >= n_vocab) ? 0 : tok;
-  const half_t* e = tok_emb + tok * d;
-  const float* p = pos_emb + (long)t * d;
-  float* o = x + (long)b * d;
-  for (int c = threadIdx.x; c < d; c += blockDim.x) o[c] = (float)e[c] + p[c];
+  embed_step_row(tokens, T_max, clamp_pos(t_rows[b], T_max), tok_emb, pos_emb, x, d, n_vocab);
 }
 
 __global__ __launch_bounds__(256) void kv_append_rows_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ kc, half_t* __restrict__ vc,
                                                              int T_max, const int* __restrict__ t_rows, int d) {
   const int b = blockIdx.x;
-  const int t = min(max(t_rows[b], 0), T_max - 1);
-  const half8* k = reinterpret_cast<const half8*>(qkv + (long)b * 3 * d + d);
-  const half8* v = reinterpret_cast<const half8*>(qkv + (long)b * 3 * d + 2 * d);
-  half8* ko = reinterpret_cast<half8*>(kc + ((long)b * T_max + t) * d);
-  half8* vo = reinterpret_cast<half8*>(vc + ((long)b * T_max + t) * d);
-  for (int c = threadIdx.x; c < d / 8; c += blockDim.x) {
-    ko[c] = k[c];
-    vo[c] = v[c];
-  }
+  kv_append_row(qkv, kc, vc, T_max, clamp_pos(t_rows[b], T_max), d);
 }
 
 // x[b * n + i] = token_embedding[tokens[b][i]] + positional_embedding[i] for i < n (the prefill's rows; n <= n_text_ctx)
@@ -99,22 +99,25 @@ __global__ __launch_bounds__(256) void kv_scatter_kernel(const half_t* __restric
   }
 }
 
-// out[j * B + b] = x[b * n + pos_j] for the positions pos_0 = blockIdx.y == 0 ? p0 : p1 (f32 residual rows)
-__global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ x, float* __restrict__ out, int n, int p0, int p1, int d) {
-  const int b = blockIdx.x, j = blockIdx.y, B = gridDim.x;
-  const float* src = x + ((long)b * n + (j == 0 ? p0 : p1)) * d;
+// out[j * B + b] = x[r] (f32 residual rows; b, j, B as the kernels below read them)
+__device__ __forceinline__ void gather_row(const float* x, float* out, long r, int b, int j, int B, int d) {
+  const float* src = x + r * d;
   float* o = out + ((long)j * B + b) * d;
   for (int c = threadIdx.x; c < d; c += blockDim.x) o[c] = src[c];
+}
+
+// r = b * n + p with p = p0 for j == 0, p1 for j == 1
+__global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ x, float* __restrict__ out, int n, int p0, int p1, int d) {
+  const int b = blockIdx.x, j = blockIdx.y, B = gridDim.x;
+  gather_row(x, out, (long)b * n + (j == 0 ? p0 : p1), b, j, B, d);
 }
 
 // the same with the positions per batch row: p0_rows[b] (the row's last initial position), p1_rows[b] (its <|sot|>; nullable)
 __global__ __launch_bounds__(256) void gather_rows_per_row_kernel(const float* __restrict__ x, float* __restrict__ out, int n,
                                                                   const int* __restrict__ p0_rows, const int* __restrict__ p1_rows, int d) {
   const int b = blockIdx.x, j = blockIdx.y, B = gridDim.x;
-  const int p = min(max(j == 0 ? p0_rows[b] : p1_rows[b], 0), n - 1);
-  const float* src = x + ((long)b * n + p) * d;
-  float* o = out + ((long)j * B + b) * d;
-  for (int c = threadIdx.x; c < d; c += blockDim.x) o[c] = src[c];
+  const int p = clamp_pos(j == 0 ? p0_rows[b] : p1_rows[b], n);
+  gather_row(x, out, (long)b * n + p, b, j, B, d);
 }
 
 __device__ __forceinline__ float block_max(float v, float* red) {
@@ -301,28 +304,18 @@ hipError_t launch_token_prob(const float* logits, int ld, int n_vocab, int token
   return hipGetLastError();
 }
 
-hipError_t launch_embed_step(const int* tokens, int T_max, int t, const half_t* tok_emb, const float* pos_emb, float* x, int B, int d,
+hipError_t launch_embed_step(const int* tokens, int T_max, StepPos pos, const half_t* tok_emb, const float* pos_emb, float* x, int B, int d,
                              int n_vocab, hipStream_t s) {
-  hipLaunchKernelGGL(embed_step_kernel, dim3(B), dim3(256), 0, s, tokens, T_max, t, tok_emb, pos_emb, x, d, n_vocab);
+  if (pos.rows && T_max < 1) return hipErrorInvalidValue;
+  if (pos.rows) hipLaunchKernelGGL(embed_step_rows_kernel, dim3(B), dim3(256), 0, s, tokens, T_max, pos.rows, tok_emb, pos_emb, x, d, n_vocab);
+  else hipLaunchKernelGGL(embed_step_kernel, dim3(B), dim3(256), 0, s, tokens, T_max, pos.t, tok_emb, pos_emb, x, d, n_vocab);
   return hipGetLastError();
 }
 
-hipError_t launch_kv_append(const half_t* qkv, half_t* kc, half_t* vc, int B, int T_max, int t, int d, hipStream_t s) {
-  if ((d & 7) != 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kv_append_kernel, dim3(B), dim3(256), 0, s, qkv, kc, vc, T_max, t, d);
-  return hipGetLastError();
-}
-
-hipError_t launch_embed_step_rows(const int* tokens, int T_max, const int* t_rows, const half_t* tok_emb, const float* pos_emb, float* x, int B,
-                                  int d, int n_vocab, hipStream_t s) {
-  if (!t_rows || T_max < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(embed_step_rows_kernel, dim3(B), dim3(256), 0, s, tokens, T_max, t_rows, tok_emb, pos_emb, x, d, n_vocab);
-  return hipGetLastError();
-}
-
-hipError_t launch_kv_append_rows(const half_t* qkv, half_t* kc, half_t* vc, int B, int T_max, const int* t_rows, int d, hipStream_t s) {
-  if ((d & 7) != 0 || !t_rows || T_max < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kv_append_rows_kernel, dim3(B), dim3(256), 0, s, qkv, kc, vc, T_max, t_rows, d);
+hipError_t launch_kv_append(const half_t* qkv, half_t* kc, half_t* vc, int B, int T_max, StepPos pos, int d, hipStream_t s) {
+  if ((d & 7) != 0 || (pos.rows && T_max < 1)) return hipErrorInvalidValue;
+  if (pos.rows) hipLaunchKernelGGL(kv_append_rows_kernel, dim3(B), dim3(256), 0, s, qkv, kc, vc, T_max, pos.rows, d);
+  else hipLaunchKernelGGL(kv_append_kernel, dim3(B), dim3(256), 0, s, qkv, kc, vc, T_max, pos.t, d);
   return hipGetLastError();
 }
 
@@ -339,27 +332,25 @@ hipError_t launch_kv_scatter(const half_t* qkv, half_t* kc, half_t* vc, int B, i
   return hipGetLastError();
 }
 
-hipError_t launch_gather_rows(const float* x, float* out, int B, int n, int p0, int p1, int d, hipStream_t s) {
-  if (p0 < 0 || p0 >= n || p1 >= n) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(gather_rows_kernel, dim3(B, p1 >= 0 ? 2 : 1), dim3(256), 0, s, x, out, n, p0, p1, d);
-  return hipGetLastError();
-}
-
-hipError_t launch_gather_rows_per_row(const float* x, float* out, int B, int n, const int* p0_rows, const int* p1_rows, int d, hipStream_t s) {
-  if (n < 1 || !p0_rows) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(gather_rows_per_row_kernel, dim3(B, p1_rows ? 2 : 1), dim3(256), 0, s, x, out, n, p0_rows, p1_rows, d);
-  return hipGetLastError();
-}
-
-hipError_t launch_decode_select_rows(const DecodeSelectArgs& a, int B, hipStream_t s) {
-  if (!a.cur_len_rows || !a.n_initial_rows || !a.cap_rows || a.n_done_idx < 0 || a.T_max < 2) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(decode_select_kernel<true>, dim3(B), dim3(1024), 0, s, a);
+hipError_t launch_gather_rows(const float* x, float* out, int B, int n, StepPos p0, StepPos p1, int d, hipStream_t s) {
+  if (p0.rows) {
+    if (n < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_rows_per_row_kernel, dim3(B, p1.rows ? 2 : 1), dim3(256), 0, s, x, out, n, p0.rows, p1.rows, d);
+  } else {
+    if (p0.t < 0 || p0.t >= n || p1.t >= n) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(B, p1.t >= 0 ? 2 : 1), dim3(256), 0, s, x, out, n, p0.t, p1.t, d);
+  }
   return hipGetLastError();
 }
 
 hipError_t launch_decode_select(const DecodeSelectArgs& a, int B, hipStream_t s) {
-  if (a.cur_len < 1 || a.cur_len >= a.T_max || a.n_initial < 1 || a.cur_len < a.n_initial) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(decode_select_kernel<false>, dim3(B), dim3(1024), 0, s, a);
+  if (a.cur_len_rows) {
+    if (!a.n_initial_rows || !a.cap_rows || a.n_done_idx < 0 || a.T_max < 2) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(decode_select_kernel<true>, dim3(B), dim3(1024), 0, s, a);
+  } else {
+    if (a.cur_len < 1 || a.cur_len >= a.T_max || a.n_initial < 1 || a.cur_len < a.n_initial) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(decode_select_kernel<false>, dim3(B), dim3(1024), 0, s, a);
+  }
   return hipGetLastError();
 }
 

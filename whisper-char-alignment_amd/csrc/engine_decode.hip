@@ -1,5 +1,5 @@
 // libwca.so engine, greedy decode: wca_greedy_decode / _ex (every row at the same position, optional batched prefill) and
-// wca_greedy_decode_rows (per-row initial tokens and sample budgets), the two loops and the plumbing they share.
+// wca_greedy_decode_rows (per-row initial tokens and sample budgets) over one argument check, one loop and one read-back.
 #include <chrono>
 
 #include "engine_internal.h"
@@ -8,7 +8,56 @@ using namespace wca;
 
 namespace {
 
-// What wca_greedy_decode_ex and wca_greedy_decode_rows share around their loops.
+// The rows of a decode as the entry points give them. each = 1: n_initial / sot_index / sample_len are arrays of [batch] and row b's
+// initial tokens start at initial + b * n_max (wca_greedy_decode_rows); each = 0: one value, one token row, for every row -- the uniform
+// call is `batch` identical rows.
+struct DecodeRows {
+  int batch, each;
+  const int32_t *initial, *n_initial, *sot_index, *sample_len;
+  int n_max = 0, T_max = 0, S = 0;   // decode_check: the longest initial row, the longest row (initial + budget), the largest budget
+  int ni(int b) const { return n_initial[b * each]; }
+  int sl(int b) const { return sample_len[b * each]; }
+  const int32_t* init(int b) const { return initial + (size_t)b * each * n_max; }
+};
+
+// What both entry points refuse, before any work is enqueued: the engine's state, the exclusive mel / pcm inputs, null pointers (any_null:
+// the caller's own list), the batch range, each row's lengths and <|sot|> position, eot / timestamp_begin, the initial tokens. Sets r's sizes.
+template <typename Opts>
+int decode_check(wca_engine* e, const float* mel_dev, const float* pcm_dev, const int32_t* n_samples_host, bool any_null, const Opts* o,
+                 DecodeRows* r) {
+  const int rc = check_ready(e);
+  if (rc) return rc;
+  if (mel_dev != nullptr && pcm_dev != nullptr) return fail(WCA_ERR_INVALID, "pass at most one of mel_dev / pcm_dev");
+  if (any_null || (pcm_dev && !n_samples_host)) return fail(WCA_ERR_INVALID, "null argument");
+  if (r->batch < 1 || r->batch > e->max_batch) return fail(WCA_ERR_INVALID, "batch %d outside [1,%d]", r->batch, e->max_batch);
+  const wca_model_dims& D = e->dims;
+  const int n_rows = r->each ? r->batch : 1;
+  char row[24] = "";
+  auto prefix = [&](int b) {   // the row form names the row
+    if (r->each) snprintf(row, sizeof(row), "row %d: ", b);
+    return row;
+  };
+  for (int b = 0; b < n_rows; ++b) {
+    prefix(b);
+    const int ni = r->ni(b), sl = r->sl(b), sot = r->sot_index[b * r->each];
+    // upstream samples until the sequence is longer than n_ctx: the (n_text_ctx + 1)-th token is sampled, never embedded
+    if (ni < 1 || sl < 1 || ni > D.n_text_ctx || ni + sl > D.n_text_ctx + 1)
+      return fail(WCA_ERR_TOO_LONG, "%sn_initial %d + sample_len %d exceeds n_text_ctx + 1 = %d (or n_initial exceeds n_text_ctx)", row, ni, sl,
+                  D.n_text_ctx + 1);
+    if (sot < 0 || sot >= ni) return fail(WCA_ERR_INVALID, "%ssot_index %d outside [0,%d)", row, sot, ni);
+    r->n_max = std::max(r->n_max, ni);
+    r->T_max = std::max(r->T_max, ni + sl);
+    r->S = std::max(r->S, sl);
+  }
+  if (o->eot < 0 || o->eot >= D.n_vocab || o->timestamp_begin < 0 || o->timestamp_begin > D.n_vocab)
+    return fail(WCA_ERR_INVALID, "eot / timestamp_begin outside the vocabulary");
+  for (int b = 0; b < n_rows; ++b)
+    for (int i = 0; i < r->ni(b); ++i)
+      if (r->init(b)[i] < 0 || r->init(b)[i] >= D.n_vocab) return fail(WCA_ERR_INVALID, "%sinitial token %d outside the vocabulary", prefix(b), i);
+  return WCA_OK;
+}
+
+// What wca_greedy_decode_ex and wca_greedy_decode_rows share around the loop.
 // Phase 1 on `stream` (unless an encoded state is waiting: wca_encode_batch) and the state to decode; the state stays queued for the
 // alignment (wca_align_batch_enqueue with pcm_dev = NULL). A state that was decoded but never aligned is stale once another decode
 // starts (stand-alone whisper.decode use). The autoregressive loop runs on `stream2` (it shares the decoder scratch with phase 2 of
@@ -40,25 +89,27 @@ int decode_take_state(wca_engine* e, const float* mel_dev, const float* pcm_dev,
   return WCA_OK;
 }
 
-// The token rows, sum_logprob and no_speech_prob of a finished loop to the host. Row b holds n_initial[b] initial tokens and has written
-// positions [0, n_have[b]); n_tokens[b] = its first sampled EOT (or n_have[b]): tokens_out[b][n_initial[b] : n_tokens[b]] are the sampled
-// tokens, and positions never reached hold EOT. Marks the state decoded.
-int decode_read_back(wca_engine* e, hipStream_t s2, wca_engine::EncState* st, int batch, int T_max, int eot, const int32_t* n_initial,
-                     const int32_t* n_have, int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host, float* no_speech_prob_host) {
+// The token rows, sum_logprob and no_speech_prob of a loop that made `steps` choices to the host. Row b holds its initial tokens and has
+// written positions [0, n_have) with n_have = n_initial + min(steps, its budget); n_tokens[b] = its first sampled EOT (or n_have):
+// tokens_out[b][n_initial : n_tokens[b]] are the sampled tokens, and positions never reached hold EOT. Marks the state decoded.
+int decode_read_back(wca_engine* e, hipStream_t s2, wca_engine::EncState* st, const DecodeRows& r, int steps, int eot, int32_t* tokens_out_host,
+                     int32_t* n_tokens_host, float* sum_logprob_host, float* no_speech_prob_host) {
+  const int batch = r.batch, T_max = r.T_max;
   std::vector<int32_t> toks((size_t)batch * T_max);
   HIPCHK(hipMemcpyAsync(toks.data(), e->dec_tokens.p, sizeof(int) * toks.size(), hipMemcpyDeviceToHost, s2));
   std::vector<float> lp(2 * (size_t)batch);  // sum_logprob [batch], no_speech_prob [batch] at the head of dec_state
   HIPCHK(hipMemcpyAsync(lp.data(), e->dec_state.p, sizeof(float) * 2 * batch, hipMemcpyDeviceToHost, s2));
   HIPCHK(hipStreamSynchronize(s2));
   for (int b = 0; b < batch; ++b) {
-    int n = n_have[b];
-    for (int i = n_initial[b]; i < n_have[b]; ++i)
+    const int n_have = r.ni(b) + std::min(steps, r.sl(b));
+    int n = n_have;
+    for (int i = r.ni(b); i < n_have; ++i)
       if (toks[(size_t)b * T_max + i] == eot) {
         n = i;
         break;
       }
     n_tokens_host[b] = n;
-    for (int i = 0; i < T_max; ++i) tokens_out_host[(size_t)b * T_max + i] = (i < n_have[b]) ? toks[(size_t)b * T_max + i] : eot;
+    for (int i = 0; i < T_max; ++i) tokens_out_host[(size_t)b * T_max + i] = (i < n_have) ? toks[(size_t)b * T_max + i] : eot;
     if (sum_logprob_host) sum_logprob_host[b] = lp[b];
     if (no_speech_prob_host) no_speech_prob_host[b] = lp[batch + b];
   }
@@ -67,7 +118,7 @@ int decode_read_back(wca_engine* e, hipStream_t s2, wca_engine::EncState* st, in
   return WCA_OK;
 }
 
-// What the two loops work on, set up by decode_begin: the state to decode, the device buffers, the select arguments every step starts
+// What the loop works on, set up by decode_begin: the state to decode, the device buffers, the select arguments every step starts
 // from and the two half-batches. The batch is decoded as two half-batches on two streams (wca_set_decode_mode, batch >= 16): a step is
 // ~200 dependent launches of 5-10 us plus one HBM-bound cross-attention per layer, and the halves are independent, so one half's small
 // kernels run under the other half's cross-K/V stream. Rows never interact (per-row kernels, per-row cache planes); n_done is an atomic counter.
@@ -78,10 +129,11 @@ struct DecodeLoop {
   hipStream_t s2 = nullptr;
   int batch = 0, T_max = 0, V = 0;
   bool want_nsp = false;
+  int no_speech = -1;        // the <|nospeech|> token (want_nsp)
   int* tokens_dev = nullptr;
   float* nsp = nullptr;      // no_speech_prob [batch]
   int* n_done = nullptr;     // completion counters
-  DecodeSelectArgs sel{};    // whole batch; the per-step fields (cur_len ...) are the caller's
+  DecodeSelectArgs sel{};    // whole batch; the per-step fields (cur_len ...) are the loop's
   int n_half = 1;
   int hb[3] = {0, 0, 0};     // half h = rows [hb[h], hb[h + 1])
   hipStream_t hs[2] = {nullptr, nullptr};
@@ -100,9 +152,8 @@ struct DecodeLoop {
     }
     return WCA_OK;
   }
-  // sel for the rows of half h
-  DecodeSelectArgs sel_half(int h) const {
-    const int b0 = hb[h];
+  // sel for the rows from b0 on
+  DecodeSelectArgs sel_from(int b0) const {
     DecodeSelectArgs sh = sel;
     sh.logits = sel.logits + (size_t)b0 * V;
     sh.tokens = sel.tokens + (size_t)b0 * T_max;
@@ -111,7 +162,7 @@ struct DecodeLoop {
     if (sel.cap_rows) sh.cap_rows = sel.cap_rows + b0;
     return sh;
   }
-  // whisper's loop ends when every row has produced EOT: the counter of this step, read back (a host sync; the loops ask every 4 steps:
+  // whisper's loop ends when every row has produced EOT: the counter of this step, read back (a host sync; the loop asks every 4 steps:
   // a late stop only costs time, finished rows keep emitting EOT)
   int all_done(const int* counter, bool* done) const {
     WCA_TRY(join());
@@ -122,15 +173,17 @@ struct DecodeLoop {
   }
 };
 
-// Takes the state to decode (phase 1 first where a mel / PCM is given), sizes the decode buffers, uploads the token rows `init`
-// [batch][T_max], the per-row tables `tab` (nullable -> e->dec_rows) and the masks, zeroes sum_logprob / no_speech_prob and the n_done_len
-// completion counters. logits_rows: 2 = a prefill also leaves the <|sot|> logits (rows [batch, 2 batch)); gather: the prefill's row scratch.
+// Takes the state to decode (phase 1 first where a mel / PCM is given), sizes the decode buffers, uploads the token rows [batch][T_max]
+// (row b's initial tokens, then eot), the per-row tables `tab` (nullable -> e->dec_rows) and the masks, zeroes sum_logprob / no_speech_prob
+// and the n_done_len completion counters. A prefill also leaves the <|sot|> logits (rows [batch, 2 batch)) and needs the gather scratch.
 template <typename Opts>
-int decode_begin(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, int batch, int T_max,
-                 int n_done_len, bool prefill, const std::vector<int32_t>& init, const std::vector<int32_t>* tab, const uint8_t* suppress_mask_host,
-                 const uint8_t* blank_mask_host, const Opts* o, bool nsp_asked, DecodeLoop* out) {
+int decode_begin(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, const DecodeRows& r,
+                 int n_done_len, bool prefill, const std::vector<int32_t>* tab, const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host,
+                 const Opts* o, bool nsp_asked, DecodeLoop* out) {
   const wca_model_dims& D = e->dims;
-  const int V = D.n_vocab, dt = D.n_text_state, L = D.n_text_layer;
+  const int V = D.n_vocab, dt = D.n_text_state, L = D.n_text_layer, batch = r.batch, T_max = r.T_max;
+  std::vector<int32_t> init((size_t)batch * T_max, o->eot);
+  for (int b = 0; b < batch; ++b) std::copy(r.init(b), r.init(b) + r.ni(b), init.begin() + (size_t)b * T_max);
   DecodeLoop& lp = *out;
   lp.e = e;
   lp.batch = batch;
@@ -143,6 +196,7 @@ int decode_begin(wca_engine* e, const float* mel_dev, const float* pcm_dev, int6
   HIPCHK(e->dec_tokens.ensure(sizeof(int) * (size_t)batch * T_max));
   HIPCHK(e->dec_masks.ensure((size_t)2 * V));
   lp.want_nsp = nsp_asked && o->no_speech >= 0 && o->no_speech < V;
+  lp.no_speech = o->no_speech;
   // the prefill's logits: rows [0, B) at the last initial position, rows [B, 2B) at <|sot|>
   HIPCHK(e->dec_logits.ensure(sizeof(float) * (size_t)((prefill && lp.want_nsp) ? 2 : 1) * batch * V));
   const size_t state_bytes = sizeof(float) * 2 * batch + sizeof(int) * (size_t)n_done_len;
@@ -184,12 +238,88 @@ int decode_begin(wca_engine* e, const float* mel_dev, const float* pcm_dev, int6
 }
 
 // one position of every row through the decoder, the halves enqueued layer by layer in turn (run_decode_step)
-int decode_step(const DecodeLoop& lp, int t, bool want_logits, const int* pos_rows, const int* nk_rows) {
+int decode_step(const DecodeLoop& lp, StepPos pos, bool want_logits) {
   const int L = lp.e->dims.n_text_layer;
   for (int phase = -1; phase <= L; ++phase)
     for (int h = 0; h < lp.n_half; ++h)
-      WCA_TRY(run_decode_step(lp.e, lp.hs[h], h, lp.kvbuf, lp.tokens_dev, lp.hb[h], lp.hb[h + 1] - lp.hb[h], lp.batch, t, lp.T_max, want_logits, phase,
-                              pos_rows ? pos_rows + lp.hb[h] : nullptr, nk_rows ? nk_rows + lp.hb[h] : nullptr));
+      WCA_TRY(run_decode_step(lp.e, lp.hs[h], h, lp.kvbuf, lp.tokens_dev, lp.hb[h], lp.hb[h + 1] - lp.hb[h], lp.batch,
+                              StepPos{pos.t, pos.rows ? pos.rows + lp.hb[h] : nullptr}, lp.T_max, want_logits, phase));
+  return WCA_OK;
+}
+
+// What the loop does for a call. The first choice comes from one batched forward over n_prefill (padded) initial positions on s2 for the
+// whole batch (run_decode_prefill), and the step loop, forked only then, continues behind it; or (n_prefill = 0) the initial tokens are fed
+// one position at a time, n_warm of them before the first choice (the plain start is 3 tokens: sot, language, task). At most `budget`
+// choices. Uniform rows (tab == nullptr): every row holds n_initial tokens, choice c reads the forward of position n_initial - 1 + c, and
+// no_speech_prob is taken at position sot_index. Per-row (tab, device): the tables of wca_greedy_decode_rows say where each row is.
+struct DecodePlan {
+  int n_prefill, n_warm, budget;
+  int n_initial, sot_index;
+  const int* tab;
+};
+
+// The loop over forwards: forward f feeds one position of every row (or, the prefill, all initial ones) and, from f = n_warm on, makes
+// choice c = f - n_warm. Ends after `budget` choices or when every row has produced EOT (or used its own budget), asked every 4 choices.
+// The uniform form launches the scalar kernels with n_done indexed by cur_len, the per-row form the table kernels with n_done indexed by c.
+// Then the results to the host (decode_read_back) and the positions wca_last_decode_positions reports.
+int decode_run(const DecodeLoop& lp, const DecodePlan& pl, const DecodeRows& r, int eot, int32_t* tokens_out_host, int32_t* n_tokens_host,
+               float* sum_logprob_host, float* no_speech_prob_host) {
+  wca_engine* e = lp.e;
+  const int B = lp.batch, V = lp.V;
+  const float* logits = (const float*)e->dec_logits.p;
+  static const bool dbg_host = std::getenv("WCA_DEC_DEBUG") != nullptr;   // (read once)
+  double host_us = 0.0;
+  int steps = 0, step_positions = 0;
+  if (!pl.n_prefill) WCA_TRY(lp.fork());
+  for (int f = 0; f < pl.n_warm + pl.budget; ++f) {
+    const int c = f - pl.n_warm;
+    const int t = pl.n_initial - 1 - pl.n_warm + f;                                        // uniform: the position fed
+    const int* row = pl.tab ? pl.tab + (size_t)(4 + 3 * c) * B : nullptr;                  // per-row: fed position, key count, cur_len of choice c
+    const bool sot_logits = lp.want_nsp && !pl.n_prefill && t == pl.sot_index;             // probs_at_sot of DecodingTask._main_loop
+    auto select = [&](int b0, int nb, hipStream_t s) {
+      DecodeSelectArgs sh = lp.sel_from(b0);
+      if (row) {
+        sh.cur_len_rows = row + 2 * (size_t)B + b0;
+        sh.n_done_idx = c;
+      } else {
+        sh.cur_len = t + 1;
+      }
+      HIPCHK(launch_decode_select(sh, nb, s));
+      return (int)WCA_OK;
+    };
+    const auto h0 = std::chrono::steady_clock::now();
+    if (pl.n_prefill && c == 0) {
+      const StepPos last{pl.n_prefill - 1, pl.tab}, sot{lp.want_nsp ? pl.sot_index : -1, lp.want_nsp && pl.tab ? pl.tab + B : nullptr};
+      WCA_TRY(run_decode_prefill(e, lp.s2, lp.kvbuf, lp.tokens_dev, B, pl.n_prefill, lp.T_max, last, sot));
+      if (lp.want_nsp) HIPCHK(launch_token_prob(logits + (size_t)B * V, V, V, lp.no_speech, lp.nsp, B, lp.s2));
+      WCA_TRY(select(0, B, lp.s2));
+      WCA_TRY(lp.fork());
+    } else {
+      ++step_positions;
+      WCA_TRY(decode_step(lp, StepPos{t, row}, c >= 0 || sot_logits));
+      for (int h = 0; h < lp.n_half; ++h) {
+        const int b0 = lp.hb[h], nb = lp.hb[h + 1] - lp.hb[h];
+        if (sot_logits) HIPCHK(launch_token_prob(logits + (size_t)b0 * V, V, V, lp.no_speech, lp.nsp + b0, nb, lp.hs[h]));
+        if (c >= 0) WCA_TRY(select(b0, nb, lp.hs[h]));
+      }
+    }
+    if (dbg_host) host_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();
+    if (c < 0) continue;
+    steps = c + 1;
+    if ((steps & 3) == 0 && steps < pl.budget) {
+      bool done = false;
+      WCA_TRY(lp.all_done(lp.n_done + (row ? c : t + 1), &done));
+      if (done) break;
+    }
+  }
+  WCA_TRY(lp.join());
+  if (dbg_host)
+    fprintf(stderr, "[wca] greedy decode: host enqueue time %.1f us per position (%d halves)\n",
+            host_us / (steps + (pl.n_prefill ? pl.n_prefill - 1 : pl.n_warm)), lp.n_half);
+  WCA_TRY(decode_read_back(e, lp.s2, lp.st, r, steps, eot, tokens_out_host, n_tokens_host, sum_logprob_host,
+                           lp.want_nsp ? no_speech_prob_host : nullptr));
+  e->dec_prefill_positions = pl.n_prefill;
+  e->dec_step_positions = step_positions;
   return WCA_OK;
 }
 
@@ -222,87 +352,21 @@ int wca_greedy_decode_ex(wca_engine* e, const float* mel_dev, const float* pcm_d
                          int batch, const int32_t* initial_tokens_host, int n_initial, const uint8_t* suppress_mask_host,
                          const uint8_t* blank_mask_host, const wca_decode_opts_ex* o, int32_t* tokens_out_host, int32_t* n_tokens_host,
                          float* sum_logprob_host, float* no_speech_prob_host) {
-  int rc = check_ready(e);
+  const int32_t ni = n_initial;
+  DecodeRows r{batch, 0, initial_tokens_host, &ni, o ? &o->sot_index : nullptr, o ? &o->sample_len : nullptr};
+  int rc = decode_check(e, mel_dev, pcm_dev, n_samples_host, !initial_tokens_host || !suppress_mask_host || !o || !tokens_out_host || !n_tokens_host,
+                        o, &r);
   if (rc) return rc;
-  if (mel_dev != nullptr && pcm_dev != nullptr) return fail(WCA_ERR_INVALID, "pass at most one of mel_dev / pcm_dev");
-  if (!initial_tokens_host || !suppress_mask_host || !o || !tokens_out_host || !n_tokens_host) return fail(WCA_ERR_INVALID, "null argument");
-  if (pcm_dev && !n_samples_host) return fail(WCA_ERR_INVALID, "null argument");
-  if (batch < 1 || batch > e->max_batch) return fail(WCA_ERR_INVALID, "batch %d outside [1,%d]", batch, e->max_batch);
-  const wca_model_dims& D = e->dims;
-  // upstream samples until the sequence is longer than n_ctx: the (n_text_ctx + 1)-th token is sampled, never embedded
-  if (n_initial < 1 || o->sample_len < 1 || n_initial > D.n_text_ctx || n_initial + o->sample_len > D.n_text_ctx + 1)
-    return fail(WCA_ERR_TOO_LONG, "n_initial %d + sample_len %d exceeds n_text_ctx + 1 = %d (or n_initial exceeds n_text_ctx)", n_initial,
-                o->sample_len, D.n_text_ctx + 1);
-  if (o->sot_index < 0 || o->sot_index >= n_initial) return fail(WCA_ERR_INVALID, "sot_index %d outside [0,%d)", o->sot_index, n_initial);
   if (o->prefill != 0 && o->prefill != 1) return fail(WCA_ERR_INVALID, "prefill must be 0 or 1");
-  if (o->eot < 0 || o->eot >= D.n_vocab || o->timestamp_begin < 0 || o->timestamp_begin > D.n_vocab)
-    return fail(WCA_ERR_INVALID, "eot / timestamp_begin outside the vocabulary");
-  for (int i = 0; i < n_initial; ++i)
-    if (initial_tokens_host[i] < 0 || initial_tokens_host[i] >= D.n_vocab) return fail(WCA_ERR_INVALID, "initial token %d outside the vocabulary", i);
-  const int V = D.n_vocab;
-  const int T_max = n_initial + o->sample_len;
   const bool prefill = o->prefill == 1;
-  std::vector<int32_t> init((size_t)batch * T_max, o->eot);
-  for (int b = 0; b < batch; ++b)
-    for (int i = 0; i < n_initial; ++i) init[(size_t)b * T_max + i] = initial_tokens_host[i];
   DecodeLoop lp;
-  if ((rc = decode_begin(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, T_max, T_max, prefill, init, nullptr, suppress_mask_host,
-                         blank_mask_host, o, no_speech_prob_host != nullptr, &lp)))
+  if ((rc = decode_begin(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, r, r.T_max, prefill, nullptr, suppress_mask_host, blank_mask_host, o,
+                         no_speech_prob_host != nullptr, &lp)))
     return rc;
   lp.sel.n_initial = n_initial;
-  hipStream_t s2 = lp.s2;
-  const bool want_nsp = lp.want_nsp;
-  // prefill = 0: the initial tokens are fed one position at a time (the plain start is 3 tokens: sot, language, task);
-  // prefill = 1: one batched forward over all of them on s2 for the whole batch (run_decode_prefill), its first choice made
-  // there too, and the step loop (forked only then) continues at t = n_initial. Sampling starts after the last initial token.
-  if (!prefill && (rc = lp.fork())) return rc;
-  int steps = 0, step_positions = 0;
-  static const bool dbg_host = std::getenv("WCA_DEC_DEBUG") != nullptr;   // (read once)
-  double host_us = 0.0;
-  for (int t = prefill ? n_initial - 1 : 0; t < T_max - 1; ++t) {
-    const bool sample = (t >= n_initial - 1);
-    const bool sot_logits = (t == o->sot_index && want_nsp);  // probs_at_sot of DecodingTask._main_loop
-    const auto h0 = std::chrono::steady_clock::now();
-    if (prefill && t == n_initial - 1) {
-      rc = run_decode_prefill(e, s2, lp.kvbuf, lp.tokens_dev, batch, n_initial, T_max, want_nsp ? o->sot_index : -1);
-      if (rc) return rc;
-      if (want_nsp) HIPCHK(launch_token_prob((const float*)e->dec_logits.p + (size_t)batch * V, V, V, o->no_speech, lp.nsp, batch, s2));
-      DecodeSelectArgs sh = lp.sel;
-      sh.cur_len = n_initial;
-      HIPCHK(launch_decode_select(sh, batch, s2));
-      if ((rc = lp.fork())) return rc;
-    } else {
-      ++step_positions;
-      if ((rc = decode_step(lp, t, sample || sot_logits, nullptr, nullptr))) return rc;
-      for (int h = 0; h < lp.n_half; ++h) {
-        const int b0 = lp.hb[h], nb = lp.hb[h + 1] - lp.hb[h];
-        if (sot_logits) HIPCHK(launch_token_prob((const float*)e->dec_logits.p + (size_t)b0 * V, V, V, o->no_speech, lp.nsp + b0, nb, lp.hs[h]));
-        if (!sample) continue;
-        DecodeSelectArgs sh = lp.sel_half(h);
-        sh.cur_len = t + 1;
-        HIPCHK(launch_decode_select(sh, nb, lp.hs[h]));
-      }
-    }
-    if (dbg_host) host_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();
-    if (!sample) continue;
-    ++steps;
-    // the loop ends when every row has produced EOT (checked every 4 steps) or after sample_len steps
-    if ((steps & 3) == 0 || steps == o->sample_len) {
-      bool done = false;
-      if ((rc = lp.all_done(lp.n_done + t + 1, &done))) return rc;
-      if (done) break;
-    }
-    if (steps >= o->sample_len) break;
-  }
-  if ((rc = lp.join())) return rc;
-  if (dbg_host) fprintf(stderr, "[wca] greedy decode: host enqueue time %.1f us per position (%d halves)\n", host_us / (steps + n_initial - 1), lp.n_half);
-  std::vector<int32_t> ni_rows(batch, n_initial), have_rows(batch, n_initial + steps);  // positions written so far
-  if ((rc = decode_read_back(e, s2, lp.st, batch, T_max, o->eot, ni_rows.data(), have_rows.data(), tokens_out_host, n_tokens_host, sum_logprob_host,
-                             want_nsp ? no_speech_prob_host : nullptr)))
-    return rc;
-  e->dec_prefill_positions = prefill ? n_initial : 0;
-  e->dec_step_positions = step_positions;
-  return WCA_OK;
+  // sampling starts after the last initial token
+  const DecodePlan pl{prefill ? n_initial : 0, prefill ? 0 : n_initial - 1, o->sample_len, n_initial, o->sot_index, nullptr};
+  return decode_run(lp, pl, r, o->eot, tokens_out_host, n_tokens_host, sum_logprob_host, no_speech_prob_host);
 }
 
 // Greedy decode of a batch whose rows carry initial tokens of their own (transcribe_batch: every recording's prompt is its own previous
@@ -317,39 +381,15 @@ int wca_greedy_decode_rows(wca_engine* e, const float* mel_dev, const float* pcm
                            const int32_t* sample_len_host, const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host,
                            const wca_decode_opts* o, int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
                            float* no_speech_prob_host) {
-  int rc = check_ready(e);
+  DecodeRows r{batch, 1, initial_tokens_host, n_initial_host, sot_index_host, sample_len_host};
+  int rc = decode_check(e, mel_dev, pcm_dev, n_samples_host,
+                        !initial_tokens_host || !n_initial_host || !sot_index_host || !sample_len_host || !suppress_mask_host || !o ||
+                            !tokens_out_host || !n_tokens_host,
+                        o, &r);
   if (rc) return rc;
-  if (mel_dev != nullptr && pcm_dev != nullptr) return fail(WCA_ERR_INVALID, "pass at most one of mel_dev / pcm_dev");
-  if (!initial_tokens_host || !n_initial_host || !sot_index_host || !sample_len_host || !suppress_mask_host || !o || !tokens_out_host ||
-      !n_tokens_host)
-    return fail(WCA_ERR_INVALID, "null argument");
-  if (pcm_dev && !n_samples_host) return fail(WCA_ERR_INVALID, "null argument");
-  if (batch < 1 || batch > e->max_batch) return fail(WCA_ERR_INVALID, "batch %d outside [1,%d]", batch, e->max_batch);
-  const wca_model_dims& D = e->dims;
-  if (o->eot < 0 || o->eot >= D.n_vocab || o->timestamp_begin < 0 || o->timestamp_begin > D.n_vocab)
-    return fail(WCA_ERR_INVALID, "eot / timestamp_begin outside the vocabulary");
-  int n_max = 0, T_max = 0, S = 0;
-  for (int b = 0; b < batch; ++b) {
-    const int ni = n_initial_host[b], sl = sample_len_host[b];
-    if (ni < 1 || sl < 1 || ni > D.n_text_ctx || ni + sl > D.n_text_ctx + 1)
-      return fail(WCA_ERR_TOO_LONG, "row %d: n_initial %d + sample_len %d exceeds n_text_ctx + 1 = %d (or n_initial exceeds n_text_ctx)", b, ni, sl,
-                  D.n_text_ctx + 1);
-    if (sot_index_host[b] < 0 || sot_index_host[b] >= ni) return fail(WCA_ERR_INVALID, "row %d: sot_index %d outside [0,%d)", b, sot_index_host[b], ni);
-    n_max = std::max(n_max, ni);
-    T_max = std::max(T_max, ni + sl);
-    S = std::max(S, sl);
-  }
-  for (int b = 0; b < batch; ++b)
-    for (int i = 0; i < n_initial_host[b]; ++i) {
-      const int32_t tk = initial_tokens_host[(size_t)b * n_max + i];
-      if (tk < 0 || tk >= D.n_vocab) return fail(WCA_ERR_INVALID, "row %d: initial token %d outside the vocabulary", b, i);
-    }
-  const int V = D.n_vocab;
-  std::vector<int32_t> init((size_t)batch * T_max, o->eot);
-  for (int b = 0; b < batch; ++b)
-    for (int i = 0; i < n_initial_host[b]; ++i) init[(size_t)b * T_max + i] = initial_tokens_host[(size_t)b * n_max + i];
-  // the int tables: [0] n_initial - 1, [1] sot_index, [2] n_initial, [3] sample cap; then per step s in [0, S): fed position
-  // min(n_initial + s - 1, T_max - 2), key count = fed position + 1, cur_len = n_initial + s  ([batch] each)
+  const int T_max = r.T_max, S = r.S;
+  // the int tables: [0] n_initial - 1, [1] sot_index, [2] n_initial, [3] sample cap; then per choice c in [0, S): fed position
+  // min(n_initial + c - 1, T_max - 2), key count = fed position + 1, cur_len = n_initial + c  ([batch] each)
   std::vector<int32_t> tab((size_t)(4 + 3 * S) * batch);
   for (int b = 0; b < batch; ++b) {
     const int ni = n_initial_host[b];
@@ -357,58 +397,22 @@ int wca_greedy_decode_rows(wca_engine* e, const float* mel_dev, const float* pcm
     tab[1 * (size_t)batch + b] = sot_index_host[b];
     tab[2 * (size_t)batch + b] = ni;
     tab[3 * (size_t)batch + b] = sample_len_host[b];
-    for (int s = 0; s < S; ++s) {
-      const int pos = std::max(0, std::min(ni + s - 1, T_max - 2));
-      tab[(size_t)(4 + 3 * s + 0) * batch + b] = pos;
-      tab[(size_t)(4 + 3 * s + 1) * batch + b] = pos + 1;
-      tab[(size_t)(4 + 3 * s + 2) * batch + b] = ni + s;
+    for (int c = 0; c < S; ++c) {
+      const int pos = std::max(0, std::min(ni + c - 1, T_max - 2));
+      tab[(size_t)(4 + 3 * c + 0) * batch + b] = pos;
+      tab[(size_t)(4 + 3 * c + 1) * batch + b] = pos + 1;
+      tab[(size_t)(4 + 3 * c + 2) * batch + b] = ni + c;
     }
   }
   DecodeLoop lp;
-  if ((rc = decode_begin(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, T_max, S, true, init, &tab, suppress_mask_host, blank_mask_host, o,
+  if ((rc = decode_begin(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, r, S, true, &tab, suppress_mask_host, blank_mask_host, o,
                          no_speech_prob_host != nullptr, &lp)))
     return rc;
   const int* tab_dev = (const int*)e->dec_rows.p;
   lp.sel.n_initial_rows = tab_dev + 2 * (size_t)batch;
   lp.sel.cap_rows = tab_dev + 3 * (size_t)batch;
-  hipStream_t s2 = lp.s2;
-  const bool want_nsp = lp.want_nsp;
-  // ---- step 0: the prefill on s2 for the whole batch, and its choice
-  rc = run_decode_prefill(e, s2, lp.kvbuf, lp.tokens_dev, batch, n_max, T_max, -1, tab_dev, want_nsp ? tab_dev + batch : nullptr);
-  if (rc) return rc;
-  if (want_nsp) HIPCHK(launch_token_prob((const float*)e->dec_logits.p + (size_t)batch * V, V, V, o->no_speech, lp.nsp, batch, s2));
-  {
-    DecodeSelectArgs sh = lp.sel;
-    sh.cur_len_rows = tab_dev + (size_t)(4 + 2) * batch;
-    sh.n_done_idx = 0;
-    HIPCHK(launch_decode_select_rows(sh, batch, s2));
-  }
-  if ((rc = lp.fork())) return rc;
-  int steps = 1, step_positions = 0;
-  bool all_done = false;
-  for (int s = 1; s < S && !all_done; ++s) {
-    const int* row = tab_dev + (size_t)(4 + 3 * s) * batch;
-    ++step_positions;
-    if ((rc = decode_step(lp, 0, true, row, row + batch))) return rc;
-    for (int h = 0; h < lp.n_half; ++h) {
-      DecodeSelectArgs sh = lp.sel_half(h);
-      sh.cur_len_rows = row + 2 * (size_t)batch + lp.hb[h];
-      sh.n_done_idx = s;
-      HIPCHK(launch_decode_select_rows(sh, lp.hb[h + 1] - lp.hb[h], lp.hs[h]));
-    }
-    ++steps;
-    // every row has produced EOT or used its budget (checked every 4 steps, as in wca_greedy_decode_ex)
-    if ((steps & 3) == 0 && steps < S && (rc = lp.all_done(lp.n_done + s, &all_done))) return rc;
-  }
-  if ((rc = lp.join())) return rc;
-  std::vector<int32_t> have_rows(batch);
-  for (int b = 0; b < batch; ++b) have_rows[b] = n_initial_host[b] + std::min(steps, (int)sample_len_host[b]);  // positions row b has written
-  if ((rc = decode_read_back(e, s2, lp.st, batch, T_max, o->eot, n_initial_host, have_rows.data(), tokens_out_host, n_tokens_host, sum_logprob_host,
-                             want_nsp ? no_speech_prob_host : nullptr)))
-    return rc;
-  e->dec_prefill_positions = n_max;
-  e->dec_step_positions = step_positions;
-  return WCA_OK;
+  const DecodePlan pl{r.n_max, 0, S, 0, -1, tab_dev};
+  return decode_run(lp, pl, r, o->eot, tokens_out_host, n_tokens_host, sum_logprob_host, no_speech_prob_host);
 }
 
 int wca_last_decode_positions(wca_engine* e, int32_t* prefill_positions, int32_t* step_positions) {

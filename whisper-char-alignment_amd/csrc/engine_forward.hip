@@ -45,7 +45,7 @@ namespace {
 // One GEMM of the decoder on few rows (a greedy-decode step: M = batch; batch-1 teacher-forced forwards: M = n tokens), on single f16
 // operands. g.A32 != nullptr: the A operand is LayerNorm(A32 rows; ln_gamma, ln_beta), xn_scratch its f16 rows where that is a launch
 // of its own. g.kv_k != nullptr (QKV projection of a decode step, N = 3 d): the k / v columns go to the self-attention cache
-// ([.][kv_tmax][d] planes) at position kv_t, or, kv_t_rows (device [M]) given, row m at its own position (wca_greedy_decode_rows).
+// ([.][kv_tmax][d] planes) at position kv_t, or, kv_t_rows (device [M]) given, row m at its own position (StepPos{kv_t, kv_t_rows}).
 // M <= DEC_ROWS_MAX and a shape the few-row kernel takes: one launch (gemm_rows.hip); otherwise the separate LayerNorm / GEMM /
 // kv_append launches. ws = which split-K workspace (one per decode stream).
 int dec_gemm(wca_engine* e, hipStream_t s, int ws, Gemm g, half_t* xn_scratch = nullptr) {
@@ -79,8 +79,7 @@ int dec_gemm(wca_engine* e, hipStream_t s, int ws, Gemm g, half_t* xn_scratch = 
   t.sk_part = e->sk_big[1 + ws];
   t.sk_bytes = e->sk_big_bytes;
   HIPCHK(gemm(e, s, t));
-  if (g.kv_k && g.kv_t_rows) HIPCHK(launch_kv_append_rows(reinterpret_cast<const half_t*>(g.C), g.kv_k, g.kv_v, M, T_max, g.kv_t_rows, N / 3, s));
-  else if (g.kv_k) HIPCHK(launch_kv_append(reinterpret_cast<const half_t*>(g.C), g.kv_k, g.kv_v, M, T_max, g.kv_t, N / 3, s));
+  if (g.kv_k) HIPCHK(launch_kv_append(reinterpret_cast<const half_t*>(g.C), g.kv_k, g.kv_v, M, T_max, StepPos{g.kv_t, g.kv_t_rows}, N / 3, s));
   return WCA_OK;
 }
 
@@ -303,10 +302,12 @@ struct DecPass {
                          // single f16 operands on plain weights -- in split mode too (prefill and step: whisper.decode runs in fp16)
   const half_t* kv;      // cross-K/V of batch row b0 (rows [hi | lo] in split mode; single operands read the hi halves)
   // self-attention keys: the QKV buffer itself under the causal mask (cache == nullptr), or the cache planes [L][2][B_all][T_max][d], to
-  // which the QKV projection appends position t -- or row b its own pos_rows[b], attending to nk_rows[b] keys (device [B], both or neither)
+  // which the QKV projection appends position pos and whose first pos + 1 slots the one query attends to. With per-row positions the key
+  // counts are the table behind the positions: a step's tables are [B_all] fed positions, then [B_all] key counts (wca_greedy_decode_rows)
   half_t* cache;
-  int B_all, T_max, t;
-  const int *pos_rows, *nk_rows;
+  int B_all, T_max;
+  StepPos pos;
+  const int* nk_rows() const { return pos.rows ? pos.rows + B_all : nullptr; }
   half_t* scatter;       // prefill: the cache planes that take each layer's K/V at positions [0, nq) (self-attention stays in place)
   float* cap;            // capture of the cross-attention logits [B][L*H][nq][Fpad] (first Fcap keys), nullable
   int Fpad, Fcap;
@@ -386,8 +387,8 @@ AttnArgs self_attn_args(const wca_engine* e, const DecPass& p, const half_t* qkv
     a.V = vc;
     a.k_bs = a.v_bs = (long)p.T_max * dt;
     a.k_rs = a.v_rs = dt;
-    a.nk = p.nk_rows ? p.T_max : p.t + 1;  // the cache holds exactly the causal prefix (per row: nk_rows[b] of the T_max cached rows)
-    a.nk_rows = p.nk_rows;
+    a.nk = p.pos.rows ? p.T_max : p.pos.t + 1;  // the cache holds exactly the causal prefix (per row: nk_rows[b] of the T_max cached rows)
+    a.nk_rows = p.nk_rows();
     return a;
   }
   a.K = qkv + dt;
@@ -444,8 +445,8 @@ int run_decoder_layers(wca_engine* e, const DecPass& p) {
       g.kv_k = kc;
       g.kv_v = vc;
       g.kv_tmax = p.T_max;
-      g.kv_t = p.t;
-      g.kv_t_rows = p.pos_rows;
+      g.kv_t = p.pos.t;
+      g.kv_t_rows = p.pos.rows;
     }
     WCA_TRY(dec_linear(e, p, g, w2.qkv_w, xdn));
     if (p.scatter) HIPCHK(launch_kv_scatter(qkv_d, kc, vc, p.B, p.nq, p.T_max, dt, p.s));
@@ -507,16 +508,16 @@ int run_decoder(wca_engine* e, const int64_t* tokens_dev, int B, int n, float* c
   return WCA_OK;
 }
 
-// One autoregressive step of the greedy ASR pre-pass for rows [b0, b0 + B) of the batch: position t of every row (token
-// tokens[b][t]) through the decoder with the self-attention K/V cache (positions 0..t), cross-attention over this batch's
+// One autoregressive step of the greedy ASR pre-pass for rows [b0, b0 + B) of the batch: position pos of every row (token
+// tokens[b][pos]) through the decoder with the self-attention K/V cache (positions 0..pos), cross-attention over this batch's
 // cross-K/V; logits of that position -> e->dec_logits. `ws` = which split-K workspace (one per decode stream).
 // phase: -1 = embedding only, li in [0, L) = decoder layer li only, L = final LayerNorm + logits only, -2 = the whole step.
 // The two half-batches of wca_greedy_decode are enqueued layer by layer in turn (the queues are served in the order their
 // packets arrive: coarse enqueueing gives coarse alternation and no overlap).
-// pos_rows / nk_rows (device, already offset to row b0; both or neither): row b feeds the token at its OWN position pos_rows[b] and
-// attends to nk_rows[b] = pos_rows[b] + 1 cached keys (wca_greedy_decode_rows); t is then unused.
-int run_decode_step(wca_engine* e, hipStream_t s, int ws, const half_t* kvbuf, const int* tokens, int b0, int B, int B_all, int t, int T_max,
-                    bool want_logits, int phase, const int* pos_rows, const int* nk_rows) {
+// pos.rows (a step's tables of the whole batch, already offset to row b0): row b feeds the token at its OWN position and attends to the
+// cached keys up to it (DecPass::nk_rows).
+int run_decode_step(wca_engine* e, hipStream_t s, int ws, const half_t* kvbuf, const int* tokens, int b0, int B, int B_all, StepPos pos,
+                    int T_max, bool want_logits, int phase) {
   const wca_model_dims& D = e->dims;
   const int dt = D.n_text_state, L = D.n_text_layer;
   DecPass p{};
@@ -530,16 +531,12 @@ int run_decode_step(wca_engine* e, hipStream_t s, int ws, const half_t* kvbuf, c
   p.cache = (half_t*)e->dec_cache.p;
   p.B_all = B_all;
   p.T_max = T_max;
-  p.t = t;
-  p.pos_rows = pos_rows;
-  p.nk_rows = nk_rows;
+  p.pos = pos;
   p.l0 = phase == -2 ? 0 : phase;
   p.l1 = phase == -2 ? L : (phase >= 0 && phase < L ? phase + 1 : phase);   // (embedding / logits phases: no layer)
   float* xd = e->xd + (size_t)b0 * dt;
-  if ((phase == -2 || phase == -1) && pos_rows)
-    HIPCHK(launch_embed_step_rows(tokens + (size_t)b0 * T_max, T_max, pos_rows, e->tok_emb, e->dec_pos, xd, B, dt, D.n_vocab, s));
-  else if (phase == -2 || phase == -1)
-    HIPCHK(launch_embed_step(tokens + (size_t)b0 * T_max, T_max, t, e->tok_emb, e->dec_pos, xd, B, dt, D.n_vocab, s));
+  if (phase == -2 || phase == -1)
+    HIPCHK(launch_embed_step(tokens + (size_t)b0 * T_max, T_max, pos, e->tok_emb, e->dec_pos, xd, B, dt, D.n_vocab, s));
   WCA_TRY(run_decoder_layers(e, p));
   if (want_logits && (phase == -2 || phase == L))
     WCA_TRY(dec_logits(e, p, xd, e->xdn + (size_t)b0 * dt, B, (float*)e->dec_logits.p + (size_t)b0 * D.n_vocab));
@@ -551,12 +548,10 @@ int run_decode_step(wca_engine* e, hipStream_t s, int ws, const half_t* kvbuf, c
 // path's operands -- plain f16 weights and f16 activations in both precision modes (whisper.decode runs in fp16), the
 // cross-K/V hi halves in split mode. Each layer's self-attention K/V go into the cache at positions [0, n) ([L][2][B][T_max][d],
 // the step loop continues at t = n); each layer's cross-K/V is read once for all n queries of a row. Only the rows whose logits
-// are needed get the final LayerNorm and the vocabulary projection: position n - 1 -> e->dec_logits rows [0, B), and, with
-// sot_index >= 0, position sot_index -> rows [B, 2B).
-// last_rows (device [B], nullable): the rows of the batch hold different numbers of initial tokens, padded to n (wca_greedy_decode_rows): the
-// first choice is read at position last_rows[b] = n_initial[b] - 1 and <|sot|> at sot_rows[b] (nullable = no sot logits); sot_index is unused.
-int run_decode_prefill(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, int n, int T_max, int sot_index,
-                       const int* last_rows, const int* sot_rows) {
+// are needed get the final LayerNorm and the vocabulary projection: position `last` (the first choice is read there) -> e->dec_logits
+// rows [0, B), and, where given, position `sot` -> rows [B, 2B). Scalars (last.t = n - 1; sot.t < 0: no sot logits), or per row where the
+// rows hold different numbers of initial tokens, padded to n (wca_greedy_decode_rows: last.rows[b] = n_initial[b] - 1; sot.rows nullable).
+int run_decode_prefill(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, int n, int T_max, StepPos last, StepPos sot) {
   const int dt = e->dims.n_text_state;
   // the scratch is carved for max_batch x n_text_ctx rows; the GEMMs on more than DEC_ROWS_MAX rows take dec_gemm's separate
   // LayerNorm + gemm() launches, which are given no lo operands, so the products stay single f16 ones in split mode too
@@ -571,10 +566,9 @@ int run_decode_prefill(wca_engine* e, hipStream_t s, const half_t* kvbuf, const 
   p.l1 = e->dims.n_text_layer;
   HIPCHK(launch_embed_prefix(tokens, T_max, n, e->tok_emb, e->dec_pos, e->xd, B, dt, e->dims.n_vocab, s));
   WCA_TRY(run_decoder_layers(e, p));
-  const int R = ((last_rows ? sot_rows != nullptr : sot_index >= 0) ? 2 : 1) * B;
+  const int R = ((last.rows ? sot.rows != nullptr : sot.t >= 0) ? 2 : 1) * B;
   float* xg = (float*)e->dec_gather.p;
-  if (last_rows) HIPCHK(launch_gather_rows_per_row(e->xd, xg, B, n, last_rows, sot_rows, dt, s));
-  else HIPCHK(launch_gather_rows(e->xd, xg, B, n, n - 1, sot_index, dt, s));
+  HIPCHK(launch_gather_rows(e->xd, xg, B, n, last, sot, dt, s));
   return dec_logits(e, p, xg, e->xdn, R, (float*)e->dec_logits.p);
 }
 

@@ -324,10 +324,9 @@ int run_encoder(wca_engine* e, int B);
 int run_cross_kv(wca_engine* e, int B, half_t* kvbuf = nullptr, bool skip_last_v = false);
 int run_decoder(wca_engine* e, const int64_t* tokens_dev, int B, int n, float* cap, int Fpad, int Fcap, float* logits_out, hipStream_t s = nullptr,
                 const half_t* kvbuf = nullptr, bool finish_last = false);
-int run_decode_step(wca_engine* e, hipStream_t s, int ws, const half_t* kvbuf, const int* tokens, int b0, int B, int B_all, int t, int T_max,
-                    bool want_logits, int phase = -2, const int* pos_rows = nullptr, const int* nk_rows = nullptr);
-int run_decode_prefill(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, int n, int T_max, int sot_index,
-                       const int* last_rows = nullptr, const int* sot_rows = nullptr);
+int run_decode_step(wca_engine* e, hipStream_t s, int ws, const half_t* kvbuf, const int* tokens, int b0, int B, int B_all, StepPos pos,
+                    int T_max, bool want_logits, int phase = -2);
+int run_decode_prefill(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, int n, int T_max, StepPos last, StepPos sot);
 int mel_to_tm(wca_engine* e, const float* mel_dev, int batch);
 int run_phase1(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int* n_samples_dev, int batch, int slot,
                bool skip_last_v = false);

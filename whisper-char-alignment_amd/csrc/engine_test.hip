@@ -260,7 +260,7 @@ int wca_test_decode_select_rows(wca_engine* e, const float* logits_dev, int batc
   a.n_initial_rows = n_initial_dev;
   a.cap_rows = cap_dev;
   a.n_done_idx = n_done_idx;
-  HIPCHK(launch_decode_select_rows(a, batch, e->stream));
+  HIPCHK(launch_decode_select(a, batch, e->stream));
   return WCA_OK;
 }
 

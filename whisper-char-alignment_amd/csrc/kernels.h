@@ -129,29 +129,30 @@ hipError_t launch_embed(const int64_t* tokens, const half_t* tok_emb, const floa
 hipError_t launch_fill_f16(half_t* p, size_t n, float v, hipStream_t s);
 
 // ---------------------------------------------------------------- greedy ASR decode steps (decode.hip)
-// x[b][:] = tok_emb[tokens[b*T_max + t]][:] + pos_emb[t][:]
-hipError_t launch_embed_step(const int* tokens, int T_max, int t, const half_t* tok_emb, const float* pos_emb, float* x, int B, int d,
-                             int n_vocab, hipStream_t s);
-// k / v columns of qkv [B][3d] -> kc / vc [B][T_max][d] at position t
-hipError_t launch_kv_append(const half_t* qkv, half_t* kc, half_t* vc, int B, int T_max, int t, int d, hipStream_t s);
-// the same with row b at position t_rows[b] (device [B], clamped to [0, T_max)): the rows of wca_greedy_decode_rows sit at different positions.
-// The engine reads t_rows (and AttnArgs.nk_rows, DecodeSelectArgs.cur_len_rows) from per-step tables it builds once per call on the host
+// Where the rows of a decode step are: every row at position t (rows == nullptr), or row b at rows[b] (device [B], clamped to the slots the launch
+// addresses; wca_greedy_decode_rows). Host side only: each launcher picks the scalar or the table form of its kernel and runs that form's checks.
+// The engine reads rows (and AttnArgs.nk_rows, DecodeSelectArgs.cur_len_rows) from per-step tables it builds once per call on the host
 // instead of adding a scalar step to row_pos[b] in every kernel: a row past its sample budget stays in the batch at a CLAMPED position
 // (<= T_max - 2: no positional row past n_text_ctx - 1, no cache slot past T_max - 1), the attention needs a plain count array anyway, and
 // the clamp then lives in one place. 3 * steps * B ints per call.
-hipError_t launch_embed_step_rows(const int* tokens, int T_max, const int* t_rows, const half_t* tok_emb, const float* pos_emb, float* x, int B,
-                                  int d, int n_vocab, hipStream_t s);
-hipError_t launch_kv_append_rows(const half_t* qkv, half_t* kc, half_t* vc, int B, int T_max, const int* t_rows, int d, hipStream_t s);
+struct StepPos {
+  int t;
+  const int* rows;
+};
+// x[b][:] = tok_emb[tokens[b*T_max + pos_b]][:] + pos_emb[pos_b][:]
+hipError_t launch_embed_step(const int* tokens, int T_max, StepPos pos, const half_t* tok_emb, const float* pos_emb, float* x, int B, int d,
+                             int n_vocab, hipStream_t s);
+// k / v columns of qkv [B][3d] -> kc / vc [B][T_max][d] at position pos_b
+hipError_t launch_kv_append(const half_t* qkv, half_t* kc, half_t* vc, int B, int T_max, StepPos pos, int d, hipStream_t s);
 // prefill of a prompted decode (all n initial positions of every row in one forward):
 // x[b*n + i][:] = tok_emb[tokens[b*T_max + i]][:] + pos_emb[i][:] for i < n
 hipError_t launch_embed_prefix(const int* tokens, int T_max, int n, const half_t* tok_emb, const float* pos_emb, float* x, int B, int d,
                                int n_vocab, hipStream_t s);
 // k / v columns of qkv [B*n][3d] -> kc / vc [B][T_max][d] at positions [0, n)
 hipError_t launch_kv_scatter(const half_t* qkv, half_t* kc, half_t* vc, int B, int n, int T_max, int d, hipStream_t s);
-// out [B][d] = rows (b, p0) of x [B*n][d] f32; p1 >= 0: out [B..2B) = rows (b, p1)
-hipError_t launch_gather_rows(const float* x, float* out, int B, int n, int p0, int p1, int d, hipStream_t s);
-// the same with the positions per batch row (device [B], clamped to [0, n)); p1_rows nullable
-hipError_t launch_gather_rows_per_row(const float* x, float* out, int B, int n, const int* p0_rows, const int* p1_rows, int d, hipStream_t s);
+// out [B][d] = rows (b, p0) of x [B*n][d] f32, and out [B..2B) = rows (b, p1) where p1 is given (p1.t >= 0; with p0.rows: p1.rows non-null).
+// p0 decides the form; the per-row positions are clamped to [0, n)
+hipError_t launch_gather_rows(const float* x, float* out, int B, int n, StepPos p0, StepPos p1, int d, hipStream_t s);
 // logit filters + greedy update of one decoding step (upstream decoding.py: SuppressBlank, SuppressTokens,
 // ApplyTimestampRules, GreedyDecoder.update at temperature 0); one workgroup per batch row
 struct DecodeSelectArgs {
@@ -165,14 +166,13 @@ struct DecodeSelectArgs {
   int apply_timestamp_rules, max_initial_timestamp_index;  // index < 0: no limit
   float* sum_logprob;                  // [B] accumulated log-probability of the sampled tokens
   int* n_done;                         // [T_max] n_done[cur_len] += 1 for every row whose new token is EOT
-  // launch_decode_select_rows only (device [B] each; cur_len / n_initial above are then unused):
+  // the per-row form (device [B] each; cur_len_rows != nullptr selects it, cur_len / n_initial above are then unused):
   const int* cur_len_rows;             // tokens row b holds; SuppressBlank / the first-timestamp rules fire at cur_len_rows[b] == n_initial_rows[b]
   const int* n_initial_rows;           // the timestamp history is tokens[b][n_initial_rows[b] : cur_len_rows[b]]
   const int* cap_rows;                 // sample budget: a row with cur_len - n_initial >= cap is a finished row (EOT, nothing added)
   int n_done_idx;                      // n_done[n_done_idx] += 1 per row whose new token is EOT (the step, not cur_len)
 };
 hipError_t launch_decode_select(const DecodeSelectArgs& a, int B, hipStream_t s);
-hipError_t launch_decode_select_rows(const DecodeSelectArgs& a, int B, hipStream_t s);
 // out[b] = softmax(logits[b])[token]  (no_speech_prob: the <|nospeech|> probability at the <|sot|> position)
 hipError_t launch_token_prob(const float* logits, int ld, int n_vocab, int token, float* out, int B, hipStream_t s);
 hipError_t launch_f32_to_f16(const float* in, half_t* out, size_t n, hipStream_t s);

@@ -8,6 +8,7 @@ a prefix (DecodingOptions(prompt=...), the decoder side of transcribe(initial_pr
 go through the decoder in one batched forward (wca_greedy_decode_ex, prefill); a list of options gives every batch row a
 prompt / prefix of its own (wca_greedy_decode_rows). Anything else raises NotImplementedError instead of silently differing.
 """
+import dataclasses
 import zlib
 from dataclasses import dataclass, field
 from typing import List, Optional, Union
@@ -134,36 +135,48 @@ def decode_plan(tokenizer, options, n_ctx):
     return initial, min(sample_len, n_ctx + 1 - len(initial)), initial.index(tokenizer.sot)
 
 
-def _decode_rows(model, mel, options, pcm, n_samples, encoded_batch, want_text):
-    """decode() with one DecodingOptions per batch row that differ in prompt / prefix only: the rows sit at different decoder
-    positions (wca_greedy_decode_rows)."""
-    import dataclasses
-    options = list(options)
-    if not options:
+@torch.no_grad()
+def decode(model, mel, options=DecodingOptions(), pcm=None, n_samples=None, encoded_batch=None, want_text=True):
+    """whisper.decode. mel: [n_mels, 3000] or [B, n_mels, 3000] f32 cuda tensor (or None with pcm [B, stride] f32 cuda +
+    n_samples, the log-mel then runs on the device; or neither with encoded_batch=B: decode the state queued by
+    model.encode_batch). Returns DecodingResult or a list of them. want_text=False (transcribe without a vocabulary file) leaves
+    `text` empty instead of decoding the token ids, which only the BPE vocabulary can do.
+    options may also be a list with one DecodingOptions per batch row; the rows may differ in prompt / prefix only (ValueError
+    otherwise): they then sit at different decoder positions (wca_greedy_decode_rows) and the result is always a list."""
+    per_row = isinstance(options, (list, tuple))
+    rows = list(options) if per_row else [options]
+    if not rows:
         raise ValueError("an empty list of DecodingOptions")
-    for o in options:
+    for o in rows:
         _check_supported(o)
-    common = [dataclasses.replace(o, prompt=None, prefix=None) for o in options]
+    common = [dataclasses.replace(o, prompt=None, prefix=None) for o in rows]
     for b, c in enumerate(common):
         if c != common[0]:
             diff = [f.name for f in dataclasses.fields(c) if getattr(c, f.name) != getattr(common[0], f.name)]
             raise ValueError("the rows of one decode may differ in prompt / prefix only; row %d differs from row 0 in %s" % (b, ", ".join(diff)))
-    if mel is not None and mel.ndim == 2:
+    single = mel is not None and mel.ndim == 2
+    if single:
         mel = mel.unsqueeze(0)
     B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(encoded_batch))
-    if len(options) != B:
-        raise ValueError("%d DecodingOptions for a batch of %d" % (len(options), B))
-    first, dims = options[0], model.dims
+    if per_row and len(rows) != B:
+        raise ValueError("%d DecodingOptions for a batch of %d" % (len(rows), B))
+    first, dims = rows[0], model.dims
     tokenizer = get_tokenizer(model.is_multilingual, language=first.language, task=first.task, vocab_path=first.vocab_path)
-    plans = [decode_plan(tokenizer, o, dims.n_text_ctx) for o in options]
+    plans = [decode_plan(tokenizer, o, dims.n_text_ctx) for o in rows]   # (initial tokens, sample_len, sot_index) per row
     sup, blank = filter_masks(tokenizer, first, dims.n_vocab)
     max_init = -1
     if not first.without_timestamps and first.max_initial_timestamp is not None:
         max_init = round(first.max_initial_timestamp / (CHUNK_LENGTH / dims.n_audio_ctx))
-    tokens, n_tokens, sum_logprobs = model.greedy_decode_rows(
-        mel, pcm, n_samples, [p[0] for p in plans], [p[2] for p in plans], [p[1] for p in plans], sup, blank, eot=tokenizer.eot,
-        timestamp_begin=tokenizer.timestamp_begin, apply_timestamp_rules=not first.without_timestamps, max_initial_timestamp_index=max_init,
-        batch=B, no_speech=tokenizer.no_speech if tokenizer.no_speech is not None else -1)
+    kw = dict(eot=tokenizer.eot, timestamp_begin=tokenizer.timestamp_begin, apply_timestamp_rules=not first.without_timestamps,
+              max_initial_timestamp_index=max_init, batch=B, no_speech=tokenizer.no_speech if tokenizer.no_speech is not None else -1)
+    if per_row:
+        tokens, n_tokens, sum_logprobs = model.greedy_decode_rows(mel, pcm, n_samples, [p[0] for p in plans], [p[2] for p in plans],
+                                                                  [p[1] for p in plans], sup, blank, **kw)
+    else:
+        initial, sample_len, sot_index = plans[0]
+        tokens, n_tokens, sum_logprobs = model.greedy_decode(mel, pcm, n_samples, initial, sup, blank, sample_len=sample_len, sot_index=sot_index,
+                                                             prefill=1 if first.prompt or first.prefix else 0, **kw)
+        plans = plans * B
     no_speech_probs = model.last_no_speech_prob
     results = []
     for b in range(B):
@@ -172,46 +185,4 @@ def _decode_rows(model, mel, options, pcm, n_samples, encoded_batch, want_text):
         results.append(DecodingResult(language=first.language, tokens=toks, text=text, avg_logprob=float(sum_logprobs[b]) / (len(toks) + 1),
                                       no_speech_prob=float(no_speech_probs[b]), temperature=first.temperature,
                                       compression_ratio=compression_ratio(text) if text else np.nan))
-    return results
-
-
-@torch.no_grad()
-def decode(model, mel, options=DecodingOptions(), pcm=None, n_samples=None, encoded_batch=None, want_text=True):
-    """whisper.decode. mel: [n_mels, 3000] or [B, n_mels, 3000] f32 cuda tensor (or None with pcm [B, stride] f32 cuda +
-    n_samples, the log-mel then runs on the device; or neither with encoded_batch=B: decode the state queued by
-    model.encode_batch). Returns DecodingResult or a list of them. want_text=False (transcribe without a vocabulary file) leaves
-    `text` empty instead of decoding the token ids, which only the BPE vocabulary can do.
-    options may also be a list with one DecodingOptions per batch row; the rows may differ in prompt / prefix only (ValueError
-    otherwise) and the result is always a list."""
-    if isinstance(options, (list, tuple)):
-        return _decode_rows(model, mel, options, pcm, n_samples, encoded_batch, want_text)
-    _check_supported(options)
-    single = mel is not None and mel.ndim == 2
-    if single:
-        mel = mel.unsqueeze(0)
-    B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(encoded_batch))
-    dims = model.dims
-    tokenizer = get_tokenizer(model.is_multilingual, language=options.language, task=options.task, vocab_path=options.vocab_path)
-    n_ctx = dims.n_text_ctx
-    initial, sample_len, sot_index = decode_plan(tokenizer, options, n_ctx)
-    conditioned = bool(options.prompt) or bool(options.prefix)
-    sup, blank = filter_masks(tokenizer, options, dims.n_vocab)
-    max_init = -1
-    if not options.without_timestamps and options.max_initial_timestamp is not None:
-        precision = CHUNK_LENGTH / dims.n_audio_ctx
-        max_init = round(options.max_initial_timestamp / precision)
-    tokens, n_tokens, sum_logprobs = model.greedy_decode(
-        mel, pcm, n_samples, initial, sup, blank, sample_len=sample_len, eot=tokenizer.eot, timestamp_begin=tokenizer.timestamp_begin,
-        apply_timestamp_rules=not options.without_timestamps, max_initial_timestamp_index=max_init, batch=B,
-        no_speech=tokenizer.no_speech if tokenizer.no_speech is not None else -1, sot_index=sot_index,
-        prefill=1 if conditioned else 0)
-    no_speech_probs = model.last_no_speech_prob
-    results = []
-    for b in range(B):
-        toks = [int(t) for t in tokens[b, len(initial):n_tokens[b]]]
-        text = tokenizer.decode(toks).strip() if want_text else ""
-        results.append(DecodingResult(language=options.language, tokens=toks, text=text,
-                                      avg_logprob=float(sum_logprobs[b]) / (len(toks) + 1), no_speech_prob=float(no_speech_probs[b]),
-                                      temperature=options.temperature,
-                                      compression_ratio=compression_ratio(text) if text else np.nan))
-    return results[0] if single else results
+    return results[0] if single and not per_row else results

@@ -457,6 +457,28 @@ class WhisperAMD:
         self._keep.append((mel, pcm))  # the kernels read these buffers asynchronously; up to two encodes are in flight
         return B
 
+    def _greedy_call(self, entry, opts, row_args, mel, pcm, n_samples, B, T, suppress_mask, blank_mask, no_speech):
+        """What greedy_decode and greedy_decode_rows share: the masks, the output arrays, the mel / pcm / n_samples and output pointer
+        arguments around the entry point's own row arguments, and last_no_speech_prob."""
+        tokens = np.zeros((B, max(T, 1)), dtype=np.int32)
+        n_tok = np.zeros(B, dtype=np.int32)
+        lp = np.zeros(B, dtype=np.float32)
+        sup = np.ascontiguousarray(suppress_mask, dtype=np.uint8)
+        blank = np.ascontiguousarray(blank_mask, dtype=np.uint8) if blank_mask is not None else None
+        if sup.shape[0] != self.dims.n_vocab or (blank is not None and blank.shape[0] != self.dims.n_vocab):
+            raise ValueError("filter masks must have n_vocab entries")
+        nsp = np.full(B, np.nan, dtype=np.float32)
+        if mel is not None:
+            mel = mel.contiguous().float()
+        _lib.check(entry(
+            self._h, _ptr(mel) if mel is not None else None, _ptr(pcm) if pcm is not None else None,
+            pcm.shape[1] if pcm is not None else 0, _lib.i32_array(n_samples) if n_samples is not None else None, B, *row_args,
+            sup.ctypes.data_as(C.c_void_p), blank.ctypes.data_as(C.c_void_p) if blank is not None else None, C.byref(opts),
+            tokens.ctypes.data_as(_lib._pi32), n_tok.ctypes.data_as(_lib._pi32), lp.ctypes.data_as(_lib._pf),
+            nsp.ctypes.data_as(_lib._pf) if no_speech >= 0 else None))
+        self.last_no_speech_prob = nsp
+        return tokens, n_tok, lp
+
     def greedy_decode(self, mel, pcm, n_samples, initial_tokens, suppress_mask, blank_mask, sample_len, eot, timestamp_begin,
                       apply_timestamp_rules=True, max_initial_timestamp_index=50, batch=None, no_speech=-1, sot_index=0, prefill=0):
         """C ABI wca_greedy_decode. mel [B,n_mels,3000] f32 cuda XOR pcm [B,stride] f32 cuda (+ n_samples).
@@ -470,31 +492,14 @@ class WhisperAMD:
         B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(batch))  # batch=: decode a state queued by encode_batch
         n_init = len(initial_tokens)
         T = n_init + int(sample_len)
-        tokens = np.zeros((B, T), dtype=np.int32)
-        n_tok = np.zeros(B, dtype=np.int32)
-        lp = np.zeros(B, dtype=np.float32)
-        sup = np.ascontiguousarray(suppress_mask, dtype=np.uint8)
-        blank = np.ascontiguousarray(blank_mask, dtype=np.uint8) if blank_mask is not None else None
-        if sup.shape[0] != self.dims.n_vocab or (blank is not None and blank.shape[0] != self.dims.n_vocab):
-            raise ValueError("filter masks must have n_vocab entries")
         fields = (int(sample_len), int(eot), int(timestamp_begin), 1 if apply_timestamp_rules else 0, int(max_initial_timestamp_index),
                   int(no_speech))
         if sot_index == 0 and prefill == 0 and T <= self.dims.n_text_ctx:
             opts, entry = _lib.DecodeOpts(*fields), self._lib.wca_greedy_decode
         else:
             opts, entry = _lib.DecodeOptsEx(*fields, int(sot_index), int(prefill)), self._lib.wca_greedy_decode_ex
-        nsp = np.full(B, np.nan, dtype=np.float32)
-        if mel is not None:
-            mel = mel.contiguous().float()
-        _lib.check(entry(
-            self._h, _ptr(mel) if mel is not None else None, _ptr(pcm) if pcm is not None else None,
-            pcm.shape[1] if pcm is not None else 0, _lib.i32_array(n_samples) if n_samples is not None else None, B,
-            _lib.i32_array(initial_tokens), n_init, sup.ctypes.data_as(C.c_void_p),
-            blank.ctypes.data_as(C.c_void_p) if blank is not None else None, C.byref(opts),
-            tokens.ctypes.data_as(_lib._pi32), n_tok.ctypes.data_as(_lib._pi32), lp.ctypes.data_as(_lib._pf),
-            nsp.ctypes.data_as(_lib._pf) if no_speech >= 0 else None))
-        self.last_no_speech_prob = nsp
-        return tokens, n_tok, lp
+        return self._greedy_call(entry, opts, (_lib.i32_array(initial_tokens), n_init), mel, pcm, n_samples, B, T, suppress_mask, blank_mask,
+                                 no_speech)
 
     def greedy_decode_rows(self, mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask, blank_mask, eot, timestamp_begin,
                            apply_timestamp_rules=True, max_initial_timestamp_index=50, batch=None, no_speech=-1):
@@ -514,27 +519,10 @@ class WhisperAMD:
         for b, r in enumerate(rows):
             init[b, :len(r)] = r
         T = max((n + int(sl) for n, sl in zip(n_init, sample_len)), default=1)
-        tokens = np.zeros((B, max(T, 1)), dtype=np.int32)
-        n_tok = np.zeros(B, dtype=np.int32)
-        lp = np.zeros(B, dtype=np.float32)
-        sup = np.ascontiguousarray(suppress_mask, dtype=np.uint8)
-        blank = np.ascontiguousarray(blank_mask, dtype=np.uint8) if blank_mask is not None else None
-        if sup.shape[0] != self.dims.n_vocab or (blank is not None and blank.shape[0] != self.dims.n_vocab):
-            raise ValueError("filter masks must have n_vocab entries")
         opts = _lib.DecodeOpts(max(int(v) for v in sample_len) if B else 0, int(eot), int(timestamp_begin), 1 if apply_timestamp_rules else 0,
                                int(max_initial_timestamp_index), int(no_speech))
-        nsp = np.full(B, np.nan, dtype=np.float32)
-        if mel is not None:
-            mel = mel.contiguous().float()
-        _lib.check(self._lib.wca_greedy_decode_rows(
-            self._h, _ptr(mel) if mel is not None else None, _ptr(pcm) if pcm is not None else None,
-            pcm.shape[1] if pcm is not None else 0, _lib.i32_array(n_samples) if n_samples is not None else None, B,
-            init.ctypes.data_as(_lib._pi32), _lib.i32_array(n_init), _lib.i32_array(sot_index), _lib.i32_array(sample_len),
-            sup.ctypes.data_as(C.c_void_p), blank.ctypes.data_as(C.c_void_p) if blank is not None else None, C.byref(opts),
-            tokens.ctypes.data_as(_lib._pi32), n_tok.ctypes.data_as(_lib._pi32), lp.ctypes.data_as(_lib._pf),
-            nsp.ctypes.data_as(_lib._pf) if no_speech >= 0 else None))
-        self.last_no_speech_prob = nsp
-        return tokens, n_tok, lp
+        row_args = (init.ctypes.data_as(_lib._pi32), _lib.i32_array(n_init), _lib.i32_array(sot_index), _lib.i32_array(sample_len))
+        return self._greedy_call(self._lib.wca_greedy_decode_rows, opts, row_args, mel, pcm, n_samples, B, T, suppress_mask, blank_mask, no_speech)
 
     def last_decode_positions(self):
         """(positions per row fed by the batched prefill, positions fed one decode step at a time) of the last greedy_decode."""

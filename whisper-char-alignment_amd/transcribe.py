@@ -329,37 +329,16 @@ def transcribe(model, audio, *, language, initial_prompt=None, condition_on_prev
     upstream's load_audio has ffmpeg do. word_timestamps=True: word times
     from the character aligner per window (module docstring); word_confidence=True adds each word's probability (None otherwise).
     decode_window(mel_window, prompt_tokens) -> DecodingResult replaces the engine's greedy decode (tests); decode_options go to
-    DecodingOptions. Limits: module docstring."""
-    from . import decoding
-    from .tokenizer import get_tokenizer
-    check_supported(temperature, language)
-    if word_confidence and not word_timestamps:
-        raise ValueError("word_confidence is a property of the aligned words: it needs word_timestamps=True")
-    if word_timestamps and vocab_path is None:
-        raise ValueError("word_timestamps aligns the decoded TEXT: pass vocab_path=<local *.tiktoken file>")
-    tokenizer = get_tokenizer(model.is_multilingual, language=language, task=decode_options.get("task", "transcribe"), vocab_path=vocab_path)
-    prompt_tokens = []
-    if initial_prompt is not None:
-        prompt_tokens = decoding._text_tokens(tokenizer, initial_prompt, decoding.DecodingOptions(vocab_path=vocab_path), "initial_prompt")
-    mel_long = model.log_mel_long(_as_pcm(audio, model, sample_rate))
-
-    if decode_window is None:
-        def decode_window(mel_window, prompt):
-            options = decoding.DecodingOptions(language=language, temperature=0.0, prompt=list(prompt) or None, vocab_path=vocab_path,
-                                               **decode_options)
-            return decoding.decode(model, mel_window, options, want_text=vocab_path is not None)
-
-    align = None
-    if word_timestamps:
-        align = make_aligner(model, tokenizer, aligned_unit_type=aligned_unit_type, aggr=aggr, topk=topk, medfilt_width=medfilt_width,
-                             w_colnorm=w_colnorm, w_rownorm=w_rownorm, w_coverage=w_coverage, word_confidence=word_confidence)
-    out = seek_loop(mel_long.shape[1], lambda seek, size: model.mel_window(mel_long, seek, size), decode_window, tokenizer,
-                    initial_prompt_tokens=prompt_tokens, condition_on_previous_text=condition_on_previous_text,
-                    no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold, align_window=align,
-                    decode_text=tokenizer.decode if vocab_path is not None else (lambda toks: None))
-    text = tokenizer.decode(out["tokens"][len(prompt_tokens):]) if vocab_path is not None else ""
-    return {"text": text, "segments": out["segments"], "language": language, "windows": out["windows"],
-            "windows_without_words": out["windows_without_words"]}
+    DecodingOptions. Limits: module docstring. It is transcribe_batch of one recording, whose single row is decoded and aligned alone."""
+    decode_windows = None
+    if decode_window is not None:
+        def decode_windows(mel_windows, prompts):
+            return [decode_window(mel_windows[0], prompts[0])]
+    return transcribe_batch(model, [audio], language=language, initial_prompt=initial_prompt, condition_on_previous_text=condition_on_previous_text,
+                            no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold, word_timestamps=word_timestamps,
+                            word_confidence=word_confidence, aligned_unit_type=aligned_unit_type, aggr=aggr, topk=topk, medfilt_width=medfilt_width,
+                            vocab_path=vocab_path, temperature=temperature, w_colnorm=w_colnorm, w_rownorm=w_rownorm, w_coverage=w_coverage,
+                            decode_windows=decode_windows, sample_rate=sample_rate, **decode_options)[0]
 
 
 def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_on_previous_text=True, no_speech_threshold=0.6,
@@ -394,7 +373,7 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
             def options(prompt):
                 return decoding.DecodingOptions(language=language, temperature=0.0, prompt=list(prompt) or None, vocab_path=vocab_path,
                                                 **decode_options)
-            if len(prompts) == 1:   # a single row left: transcribe()'s own decode call
+            if len(prompts) == 1:   # a single row (transcribe(), or the last recording of a group): a uniform decode of one window
                 return [decoding.decode(model, mel_windows[0], options(prompts[0]), want_text=vocab_path is not None)]
             return decoding.decode(model, mel_windows, [options(p) for p in prompts], want_text=vocab_path is not None)
 
@@ -419,7 +398,8 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
             if not live:
                 break
             requests = [states[i].request() for i in live]
-            windows = torch.stack([model.mel_window(mels[i], seek, size) for i, (seek, size, _) in zip(live, requests)])
+            windows = [model.mel_window(mels[i], seek, size) for i, (seek, size, _) in zip(live, requests)]
+            windows = torch.stack(windows) if len(live) > 1 else windows[0][None]   # (one row: a view, no copy)
             decoded = decode_windows(windows, [prompt for _, _, prompt in requests])
             pending = [states[i].receive(r) for i, r in zip(live, decoded)]
             if align is not None and len(live) == 1:
