@@ -437,6 +437,15 @@ int wca_test_gemm_pairs(wca_engine* e, const void* a2_f16_dev, const void* w_f16
  * fc2's kernel symbol. WCA_ERR_INVALID where the fused form does not apply (N % 256, K % 128, fewer than 192 tiles). */
 int wca_test_gemm_ln(wca_engine* e, const void* a_f16_dev, const void* w_f16_dev, const float* bias_dev, float* x_dev,
                      const float* gamma_dev, const float* beta_dev, void* xn_f16_dev, int M, int N, int K, int site);
+/* What launch_gemm would do with a GEMM C [M][N] = A [M][K] (rows lda apart) W [N][K]^T on a device of n_cu compute units (csrc/gemm_plan.cpp,
+ * plan_gemm): no engine, no GPU, no HIP call. out_mode, gelu, site as GemmArgs; a_lo > 0 = pair operands; force_tile 0 auto / 64 / 128 / 256 /
+ * 257 / 258 (GemmForceTile); cu_limit > 0 = the CUs of a masked stream. flags: 1 an addend, 2 batch-strided A, 4 a positional table, 8 batch-strided
+ * C, 16 out_mode 3 WITHOUT its LayerNorm buffers, 32 out_mode 4 WITHOUT c_lo; sk_bytes > 0 = a split-K workspace of that size.
+ * WCA_OK and out[10] = {kernel, grid x, grid y, workgroup size, dynamic LDS, splitk, supertile, site instance, a_bytes, w_bytes} with kernel
+ * 0 nothing to launch, 1 skinny, 2 128 x 128, 3 256 x 256, 4 persistent 256 x 256, 5 / 6 its pair forms on two-slot rings / three A slots,
+ * 7 its residual + LayerNorm form; WCA_ERR_INVALID (reason in wca_last_error) where launch_gemm returns hipErrorInvalidValue. */
+int wca_test_gemm_plan(int M, int N, int K, int lda, int out_mode, int gelu, int a_lo, int force_tile, int site, int n_cu, int cu_limit, int flags,
+                       int64_t sk_bytes, int32_t* out);
 /* The few-row GEMM of the greedy-decode steps (gemm_rows.hip): C [M][N] = epilogue(A W^T + bias) with A = a_f16_dev [M][K] or,
  * when x_f32_dev != NULL, A = LayerNorm(x_f32_dev [M][K]; gamma, beta, eps 1e-5) computed in the kernel's prologue.
  * out_mode as wca_test_gemm; splitk 0 = smallest split with K / splitk <= 1024, groups 0 = chosen; kv_k / kv_v != NULL

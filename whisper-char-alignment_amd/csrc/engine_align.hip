@@ -241,8 +241,7 @@ int run_token_logprobs(wca_engine* e, hipStream_t s, const int64_t* tokens_dev, 
   float* lg = (float*)e->lp_logits.p;
   for (int r0 = 0; r0 < R; r0 += chunk) {
     const int m = std::min(chunk, R - r0);
-    const GemmOpnd o = pick_operands(sp, e->tok_emb, sp ? e->sw.tok_emb : e->tok_emb, dt, m, vocab_end, 1, e);
-    Gemm g = flat(xn + (size_t)r0 * om * dt, o, lg, ldc, m, vocab_end);
+    Gemm g = flat(xn + (size_t)r0 * om * dt, sp, e->tok_emb, e->sw.tok_emb, dt, lg, ldc, m, vocab_end);
     g.out_mode = 1;
     g.site = 3;
     HIPCHK(gemm(e, s, g));

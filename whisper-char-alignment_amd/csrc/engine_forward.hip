@@ -14,15 +14,19 @@ thread_local int g_gemm_cu_limit = 0;  // CUs owned by the stream the current ph
 namespace wca {
 
 // c_lo > 0 (split mode, f16 output): the value is stored as the pair hi at C, lo at C + c_lo (out_mode 4).
-// w_plain / k_plain (pair products only, GemmOpnd::Wp / Kp): when the engine holds a W_lo slab and this matrix has non-zero lo elements (an fp32
-// checkpoint that is not exact in f16), the product gets its third term A_hi W_lo^T -- the A_lo W_lo^T term is below 2^-22 of the result like every dropped
+// w_plain / k_plain (pair products only): when the engine holds a W_lo slab and this matrix has non-zero lo elements (an fp32 checkpoint that
+// is not exact in f16), the product gets its third term A_hi W_lo^T -- the A_lo W_lo^T term is below 2^-22 of the result like every dropped
 // lo.lo term: an accumulating launch for the read-modify-write mode, an f32 scratch added before the activation (GemmArgs.addend) for the others.
+// a_lo > 0 is a candidate: plan_gemm says whether the launch as it now stands (the addend included, which the pair kernels do not take)
+// gets a pair kernel; where not, the product is the K-doubled call on w_pair.
 hipError_t gemm(wca_engine* e, hipStream_t s, Gemm g) {
   g.cu_limit = g_gemm_cu_limit;
   if (g.c_lo > 0 && g.out_mode == 0) g.out_mode = 4;
   if (g.w_plain != nullptr && use_wlo(e) && e->wlo_bases.count(g.w_plain)) {
-    // A_hi (the hi halves of the pair rows: same row stride, k_plain columns) x W_lo^T (plain [N][k_plain])
-    GemmArgs x = flat(g.A, g.lda, wlo_of(e, g.w_plain), g.k_plain, g.C, g.ldc, g.M, g.N, g.k_plain);
+    // A_hi (the hi halves of the pair rows: same row and batch strides, k_plain columns) x W_lo^T ([N][k_plain])
+    GemmArgs x = flat(g.A, g.lda, g.w_lo ? g.w_lo : wlo_of(e, g.w_plain), g.k_plain, g.C, g.ldc, g.M, g.N, g.k_plain);
+    x.a_rows_per_batch = g.a_rows_per_batch;
+    x.a_batch_stride = g.a_batch_stride;
     x.cu_limit = g_gemm_cu_limit;
     x.site = g.site;
     x.out_mode = 2;
@@ -37,10 +41,23 @@ hipError_t gemm(wca_engine* e, hipStream_t s, Gemm g) {
     }
     if (hipError_t he = launch_gemm(x, s); he != hipSuccess) return he;
   }
+  if (g.a_lo > 0 && !plan_gemm(g, e->n_cu).pair()) {
+    g.W = g.w_pair;
+    g.K = g.ldw = 2 * g.k_plain;
+    g.a_lo = 0;
+  }
   return launch_gemm(g, s);
 }
 
 namespace {
+
+// profiling: the start (which = 0) / stop (1) event of encoder site `site` (WCA_SITE_*, < 0 = none), layer slot li
+void mark_site(wca_engine* e, hipStream_t s, int site, int li, int which) {
+  if (e->profiling && site >= 0 && li >= 0 && li < 33) {
+    (void)hipEventRecord(e->kev[site][li][which], s);
+    e->kev_set[site][li] = true;
+  }
+}
 
 // One GEMM of the decoder on few rows (a greedy-decode step: M = batch; batch-1 teacher-forced forwards: M = n tokens), on single f16
 // operands. g.A32 != nullptr: the A operand is LayerNorm(A32 rows; ln_gamma, ln_beta), xn_scratch its f16 rows where that is a launch
@@ -93,36 +110,30 @@ struct EvSlots {
   int gemm_site, gemm_li, ln_site, ln_li;
 };
 int gemm_residual_ln(wca_engine* e, hipStream_t s, Gemm g, const float* gamma, const float* beta, half_t* xn, bool allow_fused, const EvSlots& slots) {
-  auto ev = [&](int st, int li, int which) {
-    if (e->profiling && st >= 0 && li >= 0 && li < 33) {
-      (void)hipEventRecord(e->kev[st][li][which], s);
-      e->kev_set[st][li] = true;
-    }
-  };
-  ev(slots.gemm_site, slots.gemm_li, 0);
-  if (allow_fused && !e->split && gemm_ln_supported(g.M, g.N, g.K, e->n_cu)) {
-    GemmArgs f = g;
-    f.out_mode = 3;
-    f.ln_gamma = gamma;
-    f.ln_beta = beta;
-    f.ln_out = xn;
-    f.ln_ld = g.N;
-    f.ln_eps = 1e-5f;
-    f.ln_stats = e->ln_stats;
-    f.ln_cnt = e->ln_cnt;
-    f.ln_err = e->ln_err ? e->ln_err : e->err_dev;
+  mark_site(e, s, slots.gemm_site, slots.gemm_li, 0);
+  GemmArgs f = g;
+  f.out_mode = 3;
+  f.ln_gamma = gamma;
+  f.ln_beta = beta;
+  f.ln_out = xn;
+  f.ln_ld = g.N;
+  f.ln_eps = 1e-5f;
+  f.ln_stats = e->ln_stats;
+  f.ln_cnt = e->ln_cnt;
+  f.ln_err = e->ln_err ? e->ln_err : e->err_dev;
+  if (allow_fused && !e->split && plan_gemm(f, e->n_cu).kernel == GemmKernel::Persist256LN) {
     HIPCHK(launch_gemm(f, s));
-    ev(slots.gemm_site, slots.gemm_li, 1);
+    mark_site(e, s, slots.gemm_site, slots.gemm_li, 1);
     return WCA_OK;
   }
   g.out_mode = 2;
   g.sk_part = e->sk_big[0];
   g.sk_bytes = e->sk_big_bytes;
   HIPCHK(gemm(e, s, g));
-  ev(slots.gemm_site, slots.gemm_li, 1);
-  ev(slots.ln_site, slots.ln_li, 0);
+  mark_site(e, s, slots.gemm_site, slots.gemm_li, 1);
+  mark_site(e, s, slots.ln_site, slots.ln_li, 0);
   HIPCHK(launch_layernorm_f16(reinterpret_cast<const float*>(g.C), gamma, beta, xn, g.M, g.N, 1e-5f, s, (e->split ? 2 : 1) * g.N, e->split ? g.N : 0));
-  ev(slots.ln_site, slots.ln_li, 1);
+  mark_site(e, s, slots.ln_site, slots.ln_li, 1);
   return WCA_OK;
 }
 
@@ -141,7 +152,7 @@ int run_encoder(wca_engine* e, int B) {
   {
     const int k1 = sp ? e->sw.k1pad : e->k1pad;
     // output frame t lands in padded row t + 1
-    GemmArgs g = flat(e->mel_tm, om * D.n_mels, sp ? e->sw.conv1_w : e->conv1_w, k1, e->h1pad + om * d, om * d, B * N_FRAMES, d, k1);
+    Gemm g = flat(e->mel_tm, om * D.n_mels, sp ? e->sw.conv1_w : e->conv1_w, k1, e->h1pad + om * d, om * d, B * N_FRAMES, d, k1);
     g.a_rows_per_batch = N_FRAMES;
     g.a_batch_stride = (long)(N_FRAMES + 2) * om * D.n_mels;
     g.bias = e->conv1_b;
@@ -149,28 +160,17 @@ int run_encoder(wca_engine* e, int B) {
     g.c_batch_stride = (long)(N_FRAMES + 2) * om * d;
     g.c_lo = sp ? d : 0;
     g.gelu = 1;
-    g.out_mode = sp ? 4 : 0;
     g.site = 3;
-    if (sp && use_wlo(e) && e->wlo_bases.count(e->conv1_w)) {   // inexact conv1 weights: the A_hi W_lo^T term, added before the GELU
-      GemmArgs x = g;
-      x.W = e->sw.conv1_wlo;
-      x.bias = nullptr;
-      x.gelu = 0;
-      x.out_mode = 1;
-      x.c_lo = 0;
-      x.c_rows_per_batch = 0;
-      HIPCHK(e->wlo_tmp[0].ensure((size_t)g.M * g.N * sizeof(float)));
-      x.C = e->wlo_tmp[0].p;
-      x.ldc = g.N;
-      HIPCHK(launch_gemm(x, s));
-      g.addend = (const float*)e->wlo_tmp[0].p;
-      g.ld_addend = g.N;
+    if (sp) {   // inexact conv1 weights: the A_hi W_lo^T term, added before the GELU
+      g.w_plain = e->conv1_w;
+      g.k_plain = k1;
+      g.w_lo = e->sw.conv1_wlo;
     }
-    HIPCHK(launch_gemm(g, s));
+    HIPCHK(gemm(e, s, g));
   }
   {
     // stride 2: every other padded frame row
-    GemmArgs g = flat(e->h1pad, 2 * om * d, sp ? e->sw.conv2_w : e->conv2_w, 3 * om * d, e->x, d, B * N_CTX, d, 3 * om * d);
+    Gemm g = flat(e->h1pad, 2 * om * d, sp ? e->sw.conv2_w : e->conv2_w, 3 * om * d, e->x, d, B * N_CTX, d, 3 * om * d);
     g.a_rows_per_batch = N_CTX;
     g.a_batch_stride = (long)(N_FRAMES + 2) * om * d;
     g.bias = e->conv2_b;
@@ -179,31 +179,17 @@ int run_encoder(wca_engine* e, int B) {
     g.gelu = 1;
     g.out_mode = 1;
     g.site = 3;
-    if (sp && use_wlo(e) && e->wlo_bases.count(e->conv2_w)) {
-      GemmArgs x = g;
-      x.W = e->sw.conv2_wlo;
-      x.bias = nullptr;
-      x.pos = nullptr;
-      x.gelu = 0;
-      x.out_mode = 1;
-      HIPCHK(e->wlo_tmp[0].ensure((size_t)g.M * g.N * sizeof(float)));
-      x.C = e->wlo_tmp[0].p;
-      x.ldc = g.N;
-      HIPCHK(launch_gemm(x, s));
-      g.addend = (const float*)e->wlo_tmp[0].p;
-      g.ld_addend = g.N;
+    if (sp) {
+      g.w_plain = e->conv2_w;
+      g.k_plain = 3 * om * d;
+      g.w_lo = e->sw.conv2_wlo;
     }
-    HIPCHK(launch_gemm(g, s));
+    HIPCHK(gemm(e, s, g));
   }
   const int M = B * N_CTX;
   const float scale = 1.0f / std::sqrt((float)(d / H));
   memset(e->kev_set, 0, sizeof(e->kev_set));
-  auto mark = [&](int site, int li, int which) {
-    if (e->profiling && li < 33) {
-      (void)hipEventRecord(e->kev[site][li][which], s);
-      e->kev_set[site][li] = true;
-    }
-  };
+  auto mark = [&](int site, int li, int which) { mark_site(e, s, site, li, which); };
   // LayerNorms ride in the epilogue of the GEMM that produces their input (gemm_residual_ln) where wca_set_fuse_ln allows it and
   // the mode is f16: mlp_ln in the attention out-projection, the NEXT layer's attn_ln (ln_post after the last layer) in fc2;
   // only layer 0's attn_ln is always a launch
@@ -213,9 +199,8 @@ int run_encoder(wca_engine* e, int B) {
   for (int li = 0; li < D.n_audio_layer; ++li) {
     const LayerW& l = e->enc[li];
     const LayerW& w2 = sp ? e->sw.enc[li] : l;  // the K-doubled copies [N][2K] = [W | W] (present in split mode)
-    const GemmOpnd oq = pick_operands(sp, l.qkv_w, w2.qkv_w, d, M, 3 * d, sp ? 4 : 0, e);
     mark(WCA_SITE_QKV, li, 0);
-    Gemm gq = flat(e->xn, oq, e->qkv, om * 3 * d, M, 3 * d);
+    Gemm gq = flat(e->xn, sp, l.qkv_w, w2.qkv_w, d, e->qkv, om * 3 * d, M, 3 * d);
     gq.bias = l.qkv_b;
     gq.c_lo = sp ? 3 * d : 0;
     gq.site = 1;
@@ -244,14 +229,12 @@ int run_encoder(wca_engine* e, int B) {
     mark(WCA_SITE_ATTN, li, 1);
     // sites OUT / FC2 = the GEMM alone (or the fused GEMM + LayerNorm kernel); the LayerNorm launches: mlp_ln = LN2[li], the next
     // layer's attn_ln / ln_post = LN1[li + 1]
-    const GemmOpnd oo = pick_operands(sp, l.out_w, w2.out_w, d, M, d, 2, e);
-    Gemm go = flat(e->att, oo, e->x, d, M, d);
+    Gemm go = flat(e->att, sp, l.out_w, w2.out_w, d, e->x, d, M, d);
     go.bias = l.out_b;
     go.site = 1;
     WCA_TRY(gemm_residual_ln(e, s, go, l.ln2_g, l.ln2_b, e->xn, e->fuse_ln, {WCA_SITE_OUT, li, WCA_SITE_LN2, li}));
-    const GemmOpnd o1 = pick_operands(sp, l.fc1_w, w2.fc1_w, d, M, 4 * d, sp ? 4 : 0, e);
     mark(WCA_SITE_FC1, li, 0);
-    Gemm g1 = flat(e->xn, o1, e->hid, om * 4 * d, M, 4 * d);
+    Gemm g1 = flat(e->xn, sp, l.fc1_w, w2.fc1_w, d, e->hid, om * 4 * d, M, 4 * d);
     g1.bias = l.fc1_b;
     g1.gelu = 1;
     g1.c_lo = sp ? 4 * d : 0;
@@ -260,8 +243,7 @@ int run_encoder(wca_engine* e, int B) {
     mark(WCA_SITE_FC1, li, 1);
     const bool last = li + 1 == D.n_audio_layer;
     // the LayerNorm behind fc2 feeds the next layer's q / k / v projection, or (ln_post) the cross-K/V projection
-    const GemmOpnd o2 = pick_operands(sp, l.fc2_w, w2.fc2_w, 4 * d, M, d, 2, e);
-    Gemm g2 = flat(e->hid, o2, e->x, d, M, d);
+    Gemm g2 = flat(e->hid, sp, l.fc2_w, w2.fc2_w, 4 * d, e->x, d, M, d);
     g2.bias = l.fc2_b;
     g2.site = 4;
     WCA_TRY(gemm_residual_ln(e, s, g2, last ? e->lnpost_g : e->enc[li + 1].ln1_g, last ? e->lnpost_b : e->enc[li + 1].ln1_b, e->xn, e->fuse_ln,
@@ -280,8 +262,7 @@ int run_cross_kv(wca_engine* e, int B, half_t* kvbuf, bool skip_last_v) {
   const int d = D.n_audio_state, dt = D.n_text_state, L = D.n_text_layer;
   const int n_cols = L * 2 * dt - (skip_last_v ? dt : 0);
   const bool sp = e->split;
-  const GemmOpnd o = pick_operands(sp, e->kv_w, sp ? e->sw.kv_w : e->kv_w, d, B * N_CTX, n_cols, sp ? 4 : 0, e);
-  Gemm g = flat(e->xn, o, kvbuf, (sp ? 2 : 1) * L * 2 * dt, B * N_CTX, n_cols);
+  Gemm g = flat(e->xn, sp, e->kv_w, e->sw.kv_w, d, kvbuf, (sp ? 2 : 1) * L * 2 * dt, B * N_CTX, n_cols);
   g.bias = e->kv_b;
   g.c_lo = sp ? (long)L * 2 * dt : 0;
   g.site = 3;
@@ -318,7 +299,7 @@ struct DecPass {
 namespace {
 
 // C = act(A W^T + bias), or C += ... (out_mode 2), with A = LayerNorm(g.A32) where given: g describes the product on single operands
-// (dec_gemm); pair operands get the LayerNorm launch with a lo half, the operands pick_operands chooses (W2 = the [W | W] copy) and an
+// (dec_gemm); pair operands get the LayerNorm launch with a lo half, the pair form of flat() (W2 = the [W | W] copy) and an
 // f16 result as a pair
 int dec_linear(wca_engine* e, const DecPass& p, Gemm g, const half_t* W2, half_t* xn) {
   if (!p.pair) return dec_gemm(e, p.s, p.ws, g, xn);
@@ -327,8 +308,7 @@ int dec_linear(wca_engine* e, const DecPass& p, Gemm g, const half_t* W2, half_t
     HIPCHK(launch_layernorm_f16(g.A32, g.ln_gamma, g.ln_beta, xn, g.M, g.K, 1e-5f, p.s, 2 * g.K, g.K));
     g.A = xn;
   }
-  const GemmOpnd o = pick_operands(true, g.W, W2, g.K, g.M, g.N, f16_out ? 4 : g.out_mode, e);
-  Gemm m = flat(g.A, o, g.C, (f16_out ? 2 : 1) * g.ldc, g.M, g.N);
+  Gemm m = flat(g.A, true, g.W, W2, g.K, g.C, (f16_out ? 2 : 1) * g.ldc, g.M, g.N);
   m.bias = g.bias;
   m.gelu = g.gelu;
   m.out_mode = g.out_mode;

@@ -258,25 +258,6 @@ inline const half_t* wlo_of(const wca_engine* e, const half_t* w) {
   return reinterpret_cast<const half_t*>(e->wslab_lo + (reinterpret_cast<const char*>(w) - e->wslab));
 }
 
-// Operands of one GEMM. pair (split mode): the A buffer holds [hi(K) | lo(K)] rows (row stride 2 K) and the product is the
-// K-doubled [A_hi | A_lo] [W | W]^T (W2 = the [W | W] copy); otherwise the plain f16 product A W1^T.
-// Where launch_gemm takes the persistent 256 x 256 kernel (M, N given), the pair product runs in its SPLITW form: plain W, each W
-// K-tile staged once (a_lo = K); elsewhere as the K-doubled call on the [W | W] copy.
-struct GemmOpnd {
-  const half_t* W;
-  int lda, K, ldw;
-  long a_lo;
-  const half_t* Wp;   // the plain [N][K] matrix when the product is a PAIR product (null otherwise): where the W_lo term of an inexact matrix comes from
-  int Kp;
-};
-inline GemmOpnd pick_operands(bool pair, const half_t* W1, const half_t* W2, int K, int M = 0, int N = 0, int out_mode = 0, const wca_engine* wlo_e = nullptr) {
-  // (a matrix with a W_lo remainder takes the K-doubled call for its non-accumulating products: their extra term enters through the generic epilogue's addend)
-  const bool no_splitw = wlo_e != nullptr && out_mode != 2 && use_wlo(wlo_e) && wlo_e->wlo_bases.count(W1) != 0;
-  if (pair && !no_splitw && M > 0 && gemm_splitw_supported(M, N, K, 2 * K, out_mode)) return GemmOpnd{W1, 2 * K, K, K, (long)K, W1, K};
-  const int k = pair ? 2 * K : K;
-  return GemmOpnd{pair ? W2 : W1, k, k, k, 0, pair ? W1 : nullptr, K};
-}
-
 // ---- engine.hip
 int check_ready(wca_engine* e);   // finalized weights, the device current, the split mode's weight copies built
 // stage per-utterance metadata into the next device slot: rows = {n_samples, n_tok, n_frames, dtwN}
@@ -292,10 +273,13 @@ size_t layout_split_weights(wca_engine* e, char* base);
 int ensure_split_weights(wca_engine* e);
 
 // ---- engine_forward.hip
-// One GEMM call: the kernel's descriptor, filled by name, plus (pair products, GemmOpnd::Wp / Kp) the plain matrix whose W_lo term it gets.
+// One GEMM call: the kernel's descriptor, filled by name, plus what gemm() needs of a PAIR product: the plain matrix whose W_lo term it gets
+// and the [W | W] copy it falls back to.
 struct Gemm : GemmArgs {
-  const half_t* w_plain = nullptr;
+  const half_t* w_plain = nullptr;   // pair products: the plain [N][k_plain] matrix (the key of wlo_bases)
   int k_plain = 0;
+  const half_t* w_pair = nullptr;    // a_lo > 0: the [W | W] copy, [N][2 k_plain]
+  const half_t* w_lo = nullptr;      // the W_lo operand where it is not the W_lo slab's image of w_plain (the conv stem's [W_lo | 0] copies, rows of k_plain)
 };
 // C [M][N] (rows ldc apart) = A [M][K] (lda) W [N][K]^T (ldw): what every call starts from; bias, gelu, out_mode, site, c_lo ... are set by name
 inline Gemm flat(const half_t* A, int lda, const half_t* W, int ldw, void* C, int ldc, int M, int N, int K) {
@@ -311,12 +295,17 @@ inline Gemm flat(const half_t* A, int lda, const half_t* W, int ldw, void* C, in
   g.K = K;
   return g;
 }
-// the same on the operands pick_operands chose
-inline Gemm flat(const half_t* A, const GemmOpnd& o, void* C, int ldc, int M, int N) {
-  Gemm g = flat(A, o.lda, o.W, o.ldw, C, ldc, M, N, o.K);
-  g.a_lo = o.a_lo;
-  g.w_plain = o.Wp;
-  g.k_plain = o.Kp;
+// The product of a Linear in either precision mode. pair (split mode): the A buffer holds [hi(K) | lo(K)] rows (row stride 2 K) and the call is
+// the candidate with a_lo = K on the plain W1 (each W K-tile staged once), which gemm() keeps exactly where plan_gemm takes it; elsewhere
+// it becomes the K-doubled [A_hi | A_lo] [W | W]^T on W2 = the [W | W] copy. Otherwise the plain f16 product A W1^T.
+inline Gemm flat(const half_t* A, bool pair, const half_t* W1, const half_t* W2, int K, void* C, int ldc, int M, int N) {
+  Gemm g = flat(A, (pair ? 2 : 1) * K, W1, K, C, ldc, M, N, K);
+  if (pair) {
+    g.a_lo = K;
+    g.w_plain = W1;
+    g.k_plain = K;
+    g.w_pair = W2;
+  }
   return g;
 }
 hipError_t gemm(wca_engine* e, hipStream_t s, Gemm g);

@@ -87,7 +87,6 @@ int wca_test_gemm_pairs(wca_engine* e, const void* a2, const void* w, const floa
   if (!e || !a2 || !w || !c) return fail(WCA_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(e->device));
   const int om = out_mode & 0xff;
-  if (!gemm_splitw_supported(M, N, K, 2 * K, om)) return fail(WCA_ERR_INVALID, "the pair-operand kernel does not take M=%d N=%d K=%d out_mode %d", M, N, K, om);
   GemmArgs g = flat((const half_t*)a2, 2 * K, (const half_t*)w, K, c, N, M, N, K);
   g.a_lo = K;
   g.bias = bias;
@@ -99,6 +98,7 @@ int wca_test_gemm_pairs(wca_engine* e, const void* a2, const void* w, const floa
   }
   g.force_tile = (out_mode >> 8) & 0xfff;
   g.site = 1;
+  if (!plan_gemm(g, e->n_cu).pair()) return fail(WCA_ERR_INVALID, "the pair-operand kernel does not take M=%d N=%d K=%d out_mode %d", M, N, K, om);
   HIPCHK(launch_gemm(g, e->stream));
   return WCA_OK;
 }
@@ -107,7 +107,6 @@ int wca_test_gemm_ln(wca_engine* e, const void* a, const void* w, const float* b
                      void* xn, int M, int N, int K, int site) {
   if (!e || !a || !w || !x || !gamma || !beta || !xn) return fail(WCA_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(e->device));
-  if (!gemm_ln_supported(M, N, K, e->n_cu)) return fail(WCA_ERR_INVALID, "residual + LayerNorm epilogue not available for M=%d N=%d K=%d", M, N, K);
   const size_t mpad = align_up((size_t)M, 256);
   HIPCHK(e->tmp0.ensure(sizeof(unsigned long long) * (size_t)(N / 256) * mpad));
   HIPCHK(e->tmp1.ensure(sizeof(unsigned) * (mpad / 256 + 16)));
@@ -124,10 +123,46 @@ int wca_test_gemm_ln(wca_engine* e, const void* a, const void* w, const float* b
   g.ln_stats = (unsigned long long*)e->tmp0.p;
   g.ln_cnt = (unsigned*)e->tmp1.p;
   g.ln_err = e->err_dev;
+  if (plan_gemm(g, e->n_cu).kernel != GemmKernel::Persist256LN) return fail(WCA_ERR_INVALID, "residual + LayerNorm epilogue not available for M=%d N=%d K=%d", M, N, K);
   HIPCHK(launch_gemm(g, e->stream));
   HIPCHK(hipMemcpyAsync(e->err_host, e->err_dev, sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   if (e->err_host[0] & 2) return fail(WCA_ERR_HIP, "LayerNorm statistics hand-off timed out");
+  return WCA_OK;
+}
+
+int wca_test_gemm_plan(int M, int N, int K, int lda, int out_mode, int gelu, int a_lo, int force_tile, int site, int n_cu, int cu_limit, int flags,
+                       int64_t sk_bytes, int32_t* out) {
+  if (!out) return fail(WCA_ERR_INVALID, "null argument");
+  static float buf;   // what the pointers of the description point to: the plan looks at null or not
+  GemmArgs g = flat(nullptr, lda, nullptr, K, nullptr, N, M, N, K);
+  g.out_mode = out_mode;
+  g.gelu = gelu;
+  g.a_lo = a_lo;
+  g.force_tile = force_tile;
+  g.site = site;
+  g.cu_limit = cu_limit;
+  if (flags & 1) g.addend = &buf;
+  if (flags & 2) g.a_rows_per_batch = 1;
+  if (flags & 4) g.pos = &buf;
+  if (flags & 8) g.c_rows_per_batch = 1;
+  if (out_mode == 3 && !(flags & 16)) {
+    g.ln_gamma = g.ln_beta = &buf;
+    g.ln_out = (half_t*)&buf;
+    g.ln_stats = (unsigned long long*)&buf;
+    g.ln_cnt = (unsigned*)&buf;
+    g.ln_ld = N;
+  }
+  if (out_mode == 4 && !(flags & 32)) g.c_lo = N;
+  if (sk_bytes > 0) {
+    g.sk_part = &buf;
+    g.sk_bytes = (size_t)sk_bytes;
+  }
+  const GemmPlan p = plan_gemm(g, n_cu);
+  if (p.refused) return fail(WCA_ERR_INVALID, "GEMM refused: %s", p.refused);
+  const int32_t v[10] = {(int32_t)p.kernel, (int32_t)p.grid_x, (int32_t)p.grid_y, (int32_t)p.block, (int32_t)p.lds,
+                         p.splitk,          p.supertile,       p.site_used,       (int32_t)p.a_bytes, (int32_t)p.w_bytes};
+  memcpy(out, v, sizeof(v));
   return WCA_OK;
 }
 

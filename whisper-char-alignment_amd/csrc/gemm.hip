@@ -3,13 +3,15 @@
 //
 //   C[m][n] = epi( sum_k A[m][k] * W[n][k] + bias[n] )
 //
-// Four kernels, chosen by launch_gemm:
+// Four kernels, chosen by plan_gemm (gemm_plan.cpp):
 //   gemm256p_f16_kernel   persistent, software-pipelined 256 x 256 x 64 tile (8 waves): every large GEMM with a flat A
 //                         operand -- the encoder's QKV / out / fc1 / fc2, the fused cross-K/V projection, the logits
 //   gemm256_f16_kernel    same tile, two barriers per K tile, pointer DMA: the batch-strided conv-stem operands
 //   gemm_f16_kernel       128 x 128 x 64 tile per 256-thread workgroup (4 waves, 2x2, 64x64 per wave), two workgroups
 //                         per CU: GEMMs with fewer than ~192 big tiles (teacher-forced decoder, small batches)
 //   gemm_skinny_f16_kernel  M <= 64 rows, weight streaming without LDS staging: the greedy-decode steps
+// launch_gemm is plan + execute: plan_gemm, a pure host function, holds every argument check and every choice (kernel form, grid, LDS, split-K,
+// supertile, the site instance); launch_gemm picks the plan's template instance and launches it. Callers that depend on the choice ask the plan.
 // All use v_mfma_f32_16x16x32_f16 with fp32 accumulation; the tile kernels stage operands HBM -> LDS by LDS-DMA into an
 // XOR-swizzled [row][64] f16 image (swizzle applied on the per-lane SOURCE address, read back with the same XOR).
 //
@@ -19,7 +21,6 @@
 #include <atomic>
 
 #include "gemm_epilogue.h"
-#include <cstdlib>
 #include "kernels.h"
 #include "launch.h"
 #include "wca_common.h"
@@ -30,11 +31,7 @@ namespace {
 
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int TILE_ELEMS = 128 * 64;  // one operand tile (f16 elements)
-// dynamic LDS of the tile kernels: what a launch asks for, and the limit its kernel symbol is given (launch.h)
-constexpr int LDS_128 = 2 * 2 * TILE_ELEMS * (int)sizeof(half_t);          // gemm_f16_kernel: two slots of A | W, 64 KiB
-constexpr int LDS_256 = 2 * 2 * 256 * 64 * (int)sizeof(half_t);            // gemm256_f16_kernel: 128 KiB
-constexpr int LDS_256P = LDS_256 + 2 * 256 * (int)sizeof(float);           // gemm256p_f16_kernel: + the tile's bias values, double buffered
-constexpr int LDS_256P_LN = LDS_256P + (2 * 512 + 2560) * (int)sizeof(float);  // ... out_mode 3: + gamma | beta (double buffered) + the statistics exchange area
+static_assert(GEMM_LDS_128 == 2 * 2 * TILE_ELEMS * (int)sizeof(half_t), "kernels.h sizes the 128 x 128 kernel's two slots of A | W");
 
 struct RowPtrs {
   const half_t* p[4];
@@ -890,128 +887,57 @@ __global__ __launch_bounds__(256) void gemm_skinny_f16_kernel(GemmArgs a) {
 
 }  // namespace
 
-bool gemm_ln_supported(int M, int N, int K, int n_cu) {
-  if (N % 256 != 0 || N > 2048 || K % 128 != 0 || M < 1) return false;  // whole tiles across the row; an even number of K tiles
-  const long tiles = (long)((M + 255) / 256) * (N / 256);
-  if (tiles < 192) return false;       // launch_gemm sends fewer tiles to the 128 x 128 kernel
-  return (n_cu >> 3) >= N / 256;       // grid = CUs (a multiple of 8): one workgroup per CU, all resident; a round of the n_cu / 8
-                                       // workgroups of an XCD label holds at least one whole panel (N / 256 tiles)
-}
-
-bool gemm_splitw_supported(int M, int N, int K, int lda, int out_mode) {
-  if (M < 1 || N < 1 || K < 128 || (K % 128) != 0) return false;   // whole pairs of K tiles: the W ring's slot parity carries over a tile boundary
-  if (out_mode != 0 && out_mode != 1 && out_mode != 2 && out_mode != 4) return false;
-  const long tiles256 = (long)((M + 255) / 256) * ((N + 255) / 256);
-  if (tiles256 < 192) return false;                                 // launch_gemm sends fewer tiles to the 128 x 128 kernel
-  const size_t a_need = ((size_t)(M - 1) * lda + 2 * (size_t)K) * sizeof(half_t), w_need = ((size_t)(N - 1) * K + K) * sizeof(half_t);
-  return a_need < 0x7fffffffull && w_need < 0x7fffffffull;          // buffer-descriptor ranges
-}
-
 hipError_t launch_gemm(const GemmArgs& a_in, hipStream_t s) {
-  GemmArgs a = a_in;
-  if (a.M <= 0 || a.N <= 0) return hipSuccess;
-  if (a.K <= 0 || (a.K % BK) != 0) return hipErrorInvalidValue;
-  if ((a.lda % 8) != 0 || (a.ldw % 8) != 0) return hipErrorInvalidValue;  // 16-byte LDS-DMA source chunks
-  // M <= 64 (greedy-decode steps): weight-streaming skinny kernel; force_tile 64 forces it, 128 etc. bypass it
-  if (a.out_mode == 4 && (a.c_lo <= 0 || (a.c_lo & 7))) return hipErrorInvalidValue;
-  if (a.addend != nullptr && (a.out_mode == 2 || a.out_mode == 3 || a.a_lo > 0)) return hipErrorInvalidValue;   // (accumulating modes take the extra term as a second
-                                                                                                                // accumulating launch; with an addend the pair product is the K-doubled call)
-  if ((a.force_tile == 64 || a.force_tile == 0) && a.M <= 64 && (a.K % 512) == 0 && a.a_rows_per_batch == 0 && a.pos == nullptr && a.addend == nullptr && a.out_mode != 4 && a.a_lo <= 0) {
-    const dim3 sgrid((unsigned)((a.N + 15) / 16)), sblock(256);
-    if (a.out_mode == 0) {
-      if (a.gelu) hipLaunchKernelGGL((gemm_skinny_f16_kernel<0, true>), sgrid, sblock, 0, s, a);
-      else hipLaunchKernelGGL((gemm_skinny_f16_kernel<0, false>), sgrid, sblock, 0, s, a);
-    } else if (a.out_mode == 1) {
-      if (a.gelu) hipLaunchKernelGGL((gemm_skinny_f16_kernel<1, true>), sgrid, sblock, 0, s, a);
-      else hipLaunchKernelGGL((gemm_skinny_f16_kernel<1, false>), sgrid, sblock, 0, s, a);
-    } else if (a.out_mode == 2 && !a.gelu) {
-      hipLaunchKernelGGL((gemm_skinny_f16_kernel<2, false>), sgrid, sblock, 0, s, a);
-    } else {
-      return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  if (a.force_tile == 64) return hipErrorInvalidValue;
-  // tile choice: the 256^2 kernel runs one workgroup per CU, so it needs about a full wave of 256 workgroups
-  const long tiles256 = (long)((a.M + 255) / 256) * ((a.N + 255) / 256);
-  const bool splitw = a.a_lo > 0;
-  if (splitw && (a.force_tile == 64 || a.force_tile == 128 || a.force_tile == 256 || a.a_rows_per_batch != 0 ||
-                 !gemm_splitw_supported(a.M, a.N, a.K, a.lda, a.out_mode) || (a.a_lo & 7) != 0))
-    return hipErrorInvalidValue;
-  const size_t a_need = ((size_t)(a.M - 1) * a.lda + (splitw ? (size_t)a.a_lo : 0) + a.K) * sizeof(half_t), w_need = ((size_t)(a.N - 1) * a.ldw + a.K) * sizeof(half_t);
-  const bool can_buf = a.a_rows_per_batch == 0 && a_need < 0x7fffffffull && w_need < 0x7fffffffull;
-  if (a.a_bytes == 0) a.a_bytes = (unsigned)a_need;
-  if (a.w_bytes == 0) a.w_bytes = (unsigned)w_need;
   int dev = 0;
-  {
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-  }
+  if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
   static std::atomic<int> n_cu_cache[32] = {};  // CUs per device ordinal
   int n_cu = n_cu_cache[dev & 31].load(std::memory_order_relaxed);
   if (n_cu == 0) {
-    hipError_t e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return e;
+    if (hipError_t e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev); e != hipSuccess) return e;
     n_cu_cache[dev & 31].store(n_cu, std::memory_order_relaxed);
   }
-  if (a.cu_limit > 0 && a.cu_limit < n_cu) n_cu = a.cu_limit;   // a CU-masked stream: one persistent workgroup per CU it owns
-  // pair operands on the persistent kernel: three A slots + one W slot (round 5); the switch gemm_ring = 1 keeps round 4's two-slot rings (A/B, tests)
-  const int ring = splitw ? (debug_switch(DBG_GEMM_RING) == 1 ? 1 : 2) : 0;
-  const bool want_big = (a.force_tile == 256 || a.force_tile == 257 || a.force_tile == 258) || (a.force_tile == 0 && tiles256 >= 192);
-  const bool pipelined = want_big && can_buf && a.force_tile != 256 && a.addend == nullptr;   // (the pre-activation addend lives in the generic epilogue only: the
-                                                                                                 //  persistent kernel's epilogue stays as it is -- an addend launch takes the two-barrier 256 x 256 kernel)
-  const bool big = want_big;
-  dim3 grid, block;
-  size_t shmem;
-  int splitk = 1;
-  if (big) {
-    grid = dim3((unsigned)tiles256);
-    block = dim3(512);
-    shmem = LDS_256;
-    if (pipelined) {
-      shmem = LDS_256P;
-      // persistent: one workgroup per CU walks tiles blockIdx.x, + gridDim.x, ... (the ring-slot parity carries
-      // over a tile boundary only for an even number of K tiles); force_tile 258 = one tile per workgroup
-      const int nk = (splitw ? 2 : 1) * (a.K / BK);
-      if (a.force_tile != 258 && nk >= 2 && (nk & 1) == 0 && tiles256 > n_cu) grid = dim3((unsigned)n_cu);
-      // (K <= 2048 since round 3: the K-doubled QKV / fc1 of the split mode measure -5 % / -3 % with the supertile order, same-box A/B)
-      if (a.supertile <= 0) a.supertile = ((splitw ? 2 : 1) * a.K <= 2048 && (a.N + 255) / 256 <= 32) ? 8 : 1;
-    }
-  } else {
-    const int ntn = (a.N + BN - 1) / BN, ntm = (a.M + BM - 1) / BM;
-    grid = dim3(ntn * ntm);
-    block = dim3(256);
-    shmem = LDS_128;
-    // few tiles and a long K (fc2 of a one- or two-utterance batch: 96 tiles x 64 K tiles): split K over up to 4 workgroups
-    // per tile; partial tiles go to the caller's workspace and a second kernel adds them in order (deterministic)
-    splitk = 1;
-    if (a.out_mode == 2 && !a.gelu && a.sk_part != nullptr && a.pos == nullptr && a.c_rows_per_batch == 0 && (a.N % 4) == 0 && (a.ldc % 4) == 0 &&
-        ntn * ntm <= n_cu / 2 && a.K >= 2048) {
-      for (int sk = 4; sk >= 2; --sk)
-        if (a.K % (sk * BK) == 0 && (size_t)sk * a.M * a.N * sizeof(float) <= a.sk_bytes) {
-          splitk = sk;
-          break;
-        }
-    }
-    grid.y = (unsigned)splitk;
+  const GemmPlan p = plan_gemm(a_in, n_cu);
+  if (p.refused) return hipErrorInvalidValue;
+  if (p.kernel == GemmKernel::None) return hipSuccess;
+  GemmArgs a = a_in;
+  a.supertile = p.supertile;
+  a.a_bytes = p.a_bytes;
+  a.w_bytes = p.w_bytes;
+  if (p.kernel == GemmKernel::Persist256LN) {   // the panels' arrival counters
+    const size_t cnt_bytes = (((size_t)((a.M + 255) / 256) * sizeof(unsigned)) + 15) / 16 * 16;
+    if (hipError_t e = hipMemsetAsync(a.ln_cnt, 0, cnt_bytes, s); e != hipSuccess) return e;
   }
-  // the kernel of this launch from its compile-time out-mode, GELU and site. Pair operands: the two-slot ring forms exist for sites 1 and 4,
-  // the three-slot forms for sites 1-4; every other site takes the site-1 form
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+  // the instance of the planned kernel from its compile-time out-mode, GELU and site: each form exists for the sites the plan folds to
   auto launch = [&](auto om_c, auto gelu_c, auto site_c) -> hipError_t {
     constexpr int OM = decltype(om_c)::value, S = decltype(site_c)::value;
     constexpr bool G = decltype(gelu_c)::value != 0;
     if constexpr (OM == 3) {
-      return launch_lds<gemm256p_f16_kernel<3, false, S>, LDS_256P_LN>(grid, block, shmem, s, a);
+      if constexpr (S == 1 || S == 4) return launch_lds<gemm256p_f16_kernel<3, false, S>, GEMM_LDS_256P_LN>(grid, block, p.lds, s, a);
     } else {
-      if (pipelined && splitw && ring == 1) return launch_lds<gemm256p_f16_kernel<OM, G, S == 4 ? 4 : 1, 1>, LDS_256P>(grid, block, shmem, s, a);
-      if (pipelined && splitw) return launch_lds<gemm256p_f16_kernel<OM, G, S == 0 ? 1 : S, 2>, LDS_256P>(grid, block, shmem, s, a);
-      if (pipelined) return launch_lds<gemm256p_f16_kernel<OM, G, S>, LDS_256P>(grid, block, shmem, s, a);
-      if (big) return launch_lds<gemm256_f16_kernel<OM, G, S>, LDS_256>(grid, block, shmem, s, a);
-      return launch_lds<gemm_f16_kernel<OM, G, S>, LDS_128>(grid, block, shmem, s, a);
+      switch (p.kernel) {
+        case GemmKernel::Skinny:
+          if constexpr (S == 0 && OM <= 2) {
+            hipLaunchKernelGGL((gemm_skinny_f16_kernel<OM, G>), grid, block, 0, s, a);
+            return hipGetLastError();
+          }
+          break;
+        case GemmKernel::Persist256Pair2:
+          if constexpr (S == 1 || S == 4) return launch_lds<gemm256p_f16_kernel<OM, G, S, 1>, GEMM_LDS_256P>(grid, block, p.lds, s, a);
+          break;
+        case GemmKernel::Persist256Pair3:
+          if constexpr (S != 0) return launch_lds<gemm256p_f16_kernel<OM, G, S, 2>, GEMM_LDS_256P>(grid, block, p.lds, s, a);
+          break;
+        case GemmKernel::Persist256: return launch_lds<gemm256p_f16_kernel<OM, G, S>, GEMM_LDS_256P>(grid, block, p.lds, s, a);
+        case GemmKernel::Tile256: return launch_lds<gemm256_f16_kernel<OM, G, S>, GEMM_LDS_256>(grid, block, p.lds, s, a);
+        case GemmKernel::Tile128: return launch_lds<gemm_f16_kernel<OM, G, S>, GEMM_LDS_128>(grid, block, p.lds, s, a);
+        default: break;
+      }
     }
+    return hipErrorInvalidValue;   // (a form the plan never pairs with this site)
   };
   auto by_site = [&](auto om_c, auto gelu_c) -> hipError_t {
-    switch (a.site) {
+    switch (p.site_used) {
       case 1: return launch(om_c, gelu_c, IntC<1>{});
       case 2: return launch(om_c, gelu_c, IntC<2>{});
       case 3: return launch(om_c, gelu_c, IntC<3>{});
@@ -1021,35 +947,17 @@ hipError_t launch_gemm(const GemmArgs& a_in, hipStream_t s) {
   };
   auto by_gelu = [&](auto om_c) -> hipError_t { return a.gelu ? by_site(om_c, IntC<1>{}) : by_site(om_c, IntC<0>{}); };
   hipError_t e;
-  if (a.out_mode == 3) {
-    // residual + LayerNorm epilogue: persistent 256 x 256 kernel only (every workgroup of a 256-row panel must be resident:
-    // one workgroup per CU, grid <= CUs), N a multiple of 256; the caller falls back to out_mode 2 + launch_layernorm_f16
-    // where gemm_ln_supported() says no
-    if (!gemm_ln_supported(a.M, a.N, a.K, n_cu) || a.gelu || !pipelined || a.force_tile == 258 || a.pos != nullptr || a.c_rows_per_batch != 0 || !a.ln_gamma ||
-        !a.ln_beta || !a.ln_out || !a.ln_stats || !a.ln_cnt || (a.ldc & 3) || (a.ln_ld & 7))
-      return hipErrorInvalidValue;
-    const size_t cnt_bytes = (((size_t)((a.M + 255) / 256) * sizeof(unsigned)) + 15) / 16 * 16;
-    e = hipMemsetAsync(a.ln_cnt, 0, cnt_bytes, s);
-    if (e != hipSuccess) return e;
-    shmem = LDS_256P_LN;                         // + gamma | beta (double buffered) + the statistics exchange area
-    grid = dim3((unsigned)(n_cu & ~7));          // round-based panel walk: 8 XCD labels x n_cu / 8 workgroups (idle ones exit)
-    e = a.site == 4 ? launch(IntC<3>{}, IntC<0>{}, IntC<4>{}) : launch(IntC<3>{}, IntC<0>{}, IntC<1>{});
-  } else if (a.out_mode == 0) {
-    e = by_gelu(IntC<0>{});
-  } else if (a.out_mode == 1) {
-    e = by_gelu(IntC<1>{});
-  } else if (a.out_mode == 2) {
-    if (a.gelu) return hipErrorInvalidValue;
-    e = by_site(IntC<2>{}, IntC<0>{});
-  } else if (a.out_mode == 4) {
-    e = by_gelu(IntC<4>{});
-  } else {
-    return hipErrorInvalidValue;
+  switch (a.out_mode) {   // (the plan has refused every other out-mode, and GELU with 2 and 3)
+    case 0: e = by_gelu(IntC<0>{}); break;
+    case 1: e = by_gelu(IntC<1>{}); break;
+    case 2: e = by_site(IntC<2>{}, IntC<0>{}); break;
+    case 3: e = by_site(IntC<3>{}, IntC<0>{}); break;
+    default: e = by_gelu(IntC<4>{}); break;
   }
   if (e != hipSuccess) return e;
-  if (splitk > 1) {
+  if (p.splitk > 1) {
     const long n4 = (long)a.M * (a.N / 4);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a.sk_part, splitk, a.M, a.N, a.bias,
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a.sk_part, p.splitk, a.M, a.N, a.bias,
                        reinterpret_cast<float*>(a.C), a.ldc);
   }
   return hipGetLastError();

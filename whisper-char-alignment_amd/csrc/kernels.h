@@ -20,7 +20,7 @@ struct GemmArgs {
   const half_t* A;
   long a_lo;               // > 0: A rows are [hi(K) | lo(K)] pairs, lo half a_lo elements after the hi half, and W is the PLAIN [N][K]
                            // matrix: C = (A_hi + A_lo) W^T with each W K-tile staged once (gemm256p SPLITW; only where
-                           // gemm_splitw_supported() says so -- elsewhere the caller passes K-doubled operands [A_hi | A_lo], [W | W])
+                           // plan_gemm() takes it -- elsewhere the caller passes K-doubled operands [A_hi | A_lo], [W | W])
   int lda;                 // elements between consecutive A rows inside a batch
   int a_rows_per_batch;    // 0 => flat
   long a_batch_stride;     // elements
@@ -45,7 +45,7 @@ struct GemmArgs {
                            // 3: f32 accumulate + LayerNorm of the updated row -> ln_out (f16); the row statistics are
                            //    exchanged between the N/256 workgroups that share a 256-row panel (gemm_epilogue.h)
   unsigned a_bytes, w_bytes; // valid bytes behind A / W (buffer-descriptor bounds); 0 => derived for flat layouts
-  int force_tile;          // 0 auto, 128 or 256: force a tile shape (tests)
+  int force_tile;          // GemmForceTile (tests, tools)
   // out_mode 3 only (the residual GEMMs of a transformer block, N = n_state <= 2048, a multiple of 256):
   const float* ln_gamma;   // [N]
   const float* ln_beta;    // [N]
@@ -75,6 +75,38 @@ struct GemmArgs {
   const int* kv_t_rows;    // few-row kernel, with kv_k: non-null = row m appends at position kv_t_rows[m] (device [M], clamped to [0, kv_tmax))
   int kv_tmax;             // instead of kv_t: the rows of wca_greedy_decode_rows sit at different positions
 };
+// Forced kernel choices: tests and tools pack the value into bits 8-19 of the out_mode they hand to wca_test_gemm*
+enum GemmForceTile {
+  GEMM_TILE_AUTO = 0,
+  GEMM_TILE_SKINNY = 64,        // the skinny kernel, or nothing
+  GEMM_TILE_128 = 128,
+  GEMM_TILE_256 = 256,          // the two-barrier 256 x 256 kernel
+  GEMM_TILE_PERSIST = 257,      // the persistent 256 x 256 kernel
+  GEMM_TILE_PERSIST_ONE = 258,  // ... with one tile per workgroup
+};
+// dynamic LDS of the tile kernels: what a launch asks for, and the limit its kernel symbol is given (launch.h)
+constexpr int GEMM_LDS_128 = 2 * 2 * 128 * 64 * (int)sizeof(half_t);                       // gemm_f16_kernel: two slots of A | W, 64 KiB
+constexpr int GEMM_LDS_256 = 2 * 2 * 256 * 64 * (int)sizeof(half_t);                       // gemm256_f16_kernel: 128 KiB
+constexpr int GEMM_LDS_256P = GEMM_LDS_256 + 2 * 256 * (int)sizeof(float);                 // gemm256p_f16_kernel: + the tile's bias values, double buffered
+constexpr int GEMM_LDS_256P_LN = GEMM_LDS_256P + (2 * 512 + 2560) * (int)sizeof(float);    // ... out_mode 3: + gamma | beta (double buffered) + the statistics exchange area
+constexpr long GEMM_MIN_TILES_256 = 192;   // fewer 256 x 256 tiles go to the 128 x 128 kernel: the 256 x 256 kernels run one workgroup per CU
+
+// What launch_gemm does with a GemmArgs, decided on the host without a HIP call (gemm_plan.cpp): every argument check and every choice
+// of kernel, grid and LDS. Callers that must know the outcome beforehand (pair operands or K-doubled ones, the fused LayerNorm or a
+// launch of its own) plan the launch they would make and look.
+enum class GemmKernel { None /* M or N is 0: nothing to launch */, Skinny, Tile128, Tile256, Persist256, Persist256Pair2, Persist256Pair3, Persist256LN };
+struct GemmPlan {
+  GemmKernel kernel;
+  unsigned grid_x, grid_y, block;
+  unsigned lds;            // dynamic LDS of the launch
+  int splitk;              // 128 x 128 kernel only, else 1
+  int supertile;           // GemmArgs.supertile of the launch
+  unsigned a_bytes, w_bytes;
+  int site_used;           // the SITE instance that is launched: the pair forms exist for sites 1 and 4 (two-slot rings) or 1-4, out_mode 3 for 1 and 4
+  const char* refused;     // null, or why the arguments are not taken (launch_gemm: hipErrorInvalidValue)
+  bool pair() const { return kernel == GemmKernel::Persist256Pair2 || kernel == GemmKernel::Persist256Pair3; }
+};
+GemmPlan plan_gemm(const GemmArgs& a, int n_cu);
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s);
 // Few-row GEMM (M <= a few hundred rows: greedy-decode steps, batch-1 decoder forwards) with optional LayerNorm prologue,
 // KV-cache append and deterministic split-K; returns hipErrorInvalidValue for shapes it does not take (gemm_rows_supported)
@@ -82,10 +114,6 @@ hipError_t launch_gemm_rows(const GemmArgs& a, hipStream_t s);
 bool gemm_rows_supported(int M, int N, int K, bool layernorm_a);
 int gemm_rows_pick_splitk(int K);
 size_t gemm_rows_workspace_bytes(int M, int N, int splitk);
-// out_mode 3 (residual + LayerNorm epilogue) is available for this shape on a device with n_cu compute units
-bool gemm_ln_supported(int M, int N, int K, int n_cu);
-// the pair-operand form (GemmArgs.a_lo > 0, plain W) is available for this flat-A problem (launch_gemm picks the persistent 256 x 256 kernel)
-bool gemm_splitw_supported(int M, int N, int K, int lda, int out_mode);
 
 // ---------------------------------------------------------------- attention (attention.hip)
 // Flash-style multi-head attention with head_dim == 64 (every Whisper size).
