@@ -105,7 +105,7 @@ typedef struct {
 } wca_align_opts;
 
 const char* wca_last_error(void);
-int wca_version(void);   /* 12: wca_resample_plan, wca_resample_table, wca_resample_16k (any input rate to 16 kHz); 11: wca_greedy_decode_rows (per-row prompts and sample budgets); 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: wca_greedy_decode_ex (prompt / prefix: sot_index, batched prefill); 7: exactly two precision modes */
+int wca_version(void);   /* 13: wca_detect_language (the language head on the encoded state; the decode that follows re-uses the state); 12: wca_resample_plan, wca_resample_table, wca_resample_16k (any input rate to 16 kHz); 11: wca_greedy_decode_rows (per-row prompts and sample budgets); 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: wca_greedy_decode_ex (prompt / prefix: sot_index, batched prefill); 7: exactly two precision modes */
 
 /* ---- engine lifetime ------------------------------------------------------------------------ */
 /* A new engine is in the CONTRACT precision mode (WCA_PRECISION_REFERENCE: every stage on (hi, lo) operand pairs = the fp32 forward of
@@ -349,6 +349,21 @@ int wca_greedy_decode_rows(wca_engine* e, const float* mel_dev, const float* pcm
                            const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host, const wca_decode_opts* opts,
                            int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
                            float* no_speech_prob_host);
+/* Language identification, upstream's detect_language(model, mel): which of the language tokens [lang_begin, lang_begin + n_lang)
+ * (tokenizer.all_language_tokens: sot + 1 ..., 99 or 100 of them; 1 <= n_lang <= 128) follows <|startoftranscript|> (`sot`) for each row.
+ * mel_dev / pcm_dev / pcm_stride / n_samples_host / batch as for wca_greedy_decode: at most one input is non-NULL, with both NULL the oldest
+ * undecoded state of wca_encode_batch is read. One decoder position (token sot at position 0, the first step of wca_greedy_decode, f16
+ * operands in both precision modes) and the language head: the final LayerNorm and the n_lang rows of the token embedding only, which is
+ * upstream's softmax / argmax over logits whose other entries are masked to -inf.
+ * lang_token_host [batch] int32: the most probable language token (absolute id; the lowest id among equal logits);
+ * probs_host [batch][n_lang] f32: the softmax over the language tokens, entry j for token lang_begin + j.
+ * The encoded state stays queued and UNDECODED: a following wca_greedy_decode* with mel_dev = pcm_dev = NULL decodes it with no second
+ * encoder pass (upstream encodes the first window twice), and wca_align_batch_enqueue(pcm_dev = NULL) may consume it. A wca_greedy_decode* or
+ * wca_detect_language that brings an input of its own drops it, as does wca_align_batch_enqueue with a pcm_dev. Synchronous.
+ * WCA_ERR_INVALID: null engine / output pointers, both inputs given, batch outside [1, max_batch], sot or the language range outside the
+ * vocabulary; WCA_ERR_STATE: no input and no undecoded state of `batch` rows. */
+int wca_detect_language(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
+                        int batch, int sot, int lang_begin, int n_lang, int32_t* lang_token_host, float* probs_host);
 /* positions per row that the last wca_greedy_decode* fed through the batched prefill (n_initial, or 0) and one position at a
  * time (decode steps, the sampling steps after the first included) */
 int wca_last_decode_positions(wca_engine* e, int32_t* prefill_positions, int32_t* step_positions);
@@ -474,6 +489,9 @@ int wca_test_attention(wca_engine* e, const void* q_dev, const void* k_dev, cons
  * likewise; cap_dev as above (the three-pass fp32 logits times scale). causal: bit 0 only. */
 int wca_test_attention_split(wca_engine* e, const void* q2_dev, const void* k2_dev, const void* v2_dev, void* o2_dev,
                              float* cap_dev, int cap_ld, int cap_cols, int B, int H, int nq, int nk, int causal);
+/* the language head alone (kernel parity test): x_dev [B][n_text_state] f32 rows against the engine's loaded decoder.ln and
+ * token_embedding -> probs_dev [B][n_lang] f32, lang_token_dev [B] int32, on the engine's stream (asynchronous) */
+int wca_test_language_head(wca_engine* e, const float* x_dev, int B, int lang_begin, int n_lang, float* probs_dev, int32_t* lang_token_dev);
 /* one step of the greedy decoder's filters + update on caller-supplied logits (kernel parity test) */
 int wca_test_decode_select(wca_engine* e, const float* logits_dev, int batch, int n_vocab, int32_t* tokens_dev, int T_max,
                            int cur_len, int n_initial, const uint8_t* suppress_mask_dev, const uint8_t* blank_mask_dev,

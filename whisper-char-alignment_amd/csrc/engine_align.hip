@@ -507,9 +507,9 @@ int wca_align_batch_enqueue_ex(wca_engine* e, const float* pcm_dev, int64_t pcm_
     return fail(WCA_ERR_STATE, "pcm_dev == NULL re-uses the oldest state left by wca_encode_batch / wca_greedy_decode for the same batch; there is none");
   if (!reuse_enc && !n_samples_host) return fail(WCA_ERR_INVALID, "null argument");
   if (!reuse_enc && !e->enc_q.empty()) {
-    // a stand-alone decode may have left a decoded state behind; an undecoded one is still wanted by its owner
+    // a stand-alone decode (or language detection) may have left its state behind; any other undecoded one is still wanted by its owner
     for (auto& st : e->enc_q)
-      if (!st.decoded) return fail(WCA_ERR_STATE, "an encoded batch is waiting for wca_greedy_decode / wca_align_batch_enqueue(pcm_dev = NULL)");
+      if (!st.decoded && !st.detected) return fail(WCA_ERR_STATE, "an encoded batch is waiting for wca_greedy_decode / wca_align_batch_enqueue(pcm_dev = NULL)");
     for (auto& st : e->enc_q) e->slot_busy[st.slot] = false;
     e->enc_q.clear();
   }

@@ -1,5 +1,6 @@
 // libwca.so engine, greedy decode: wca_greedy_decode / _ex (every row at the same position, optional batched prefill) and
-// wca_greedy_decode_rows (per-row initial tokens and sample budgets) over one argument check, one loop and one read-back.
+// wca_greedy_decode_rows (per-row initial tokens and sample budgets) over one argument check, one loop and one read-back; and
+// wca_detect_language (one position and the language head on the state a decode then takes).
 #include <chrono>
 
 #include "engine_internal.h"
@@ -65,8 +66,10 @@ int decode_check(wca_engine* e, const float* mel_dev, const float* pcm_dev, cons
 // to wait for the state's cross-K/V here.
 int decode_take_state(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, int batch,
                       wca_engine::EncState** out) {
+  // (a state that wca_detect_language has read waits for the decode of that same state; a call that brings its own input drops it)
+  const bool fresh = mel_dev != nullptr || pcm_dev != nullptr;
   for (auto it = e->enc_q.begin(); it != e->enc_q.end();) {
-    if (it->decoded) {
+    if (it->decoded || (fresh && it->detected)) {
       e->slot_busy[it->slot] = false;
       it = e->enc_q.erase(it);
     } else {
@@ -413,6 +416,50 @@ int wca_greedy_decode_rows(wca_engine* e, const float* mel_dev, const float* pcm
   lp.sel.cap_rows = tab_dev + 3 * (size_t)batch;
   const DecodePlan pl{r.n_max, 0, S, 0, -1, tab_dev};
   return decode_run(lp, pl, r, o->eot, tokens_out_host, n_tokens_host, sum_logprob_host, no_speech_prob_host);
+}
+
+// Language identification (upstream detect_language): phase 1 as a decode takes it, ONE decoder position (t = 0, token sot) for every
+// row -- the first warm step of wca_greedy_decode up to the final residual stream, no vocabulary projection --, the language head on
+// e->xd (language_head.hip: final LayerNorm and the n_lang rows of the token embedding), one read-back. f16 operands in both precision
+// modes, like the greedy pre-pass. The state stays queued and UNDECODED: the decode that follows with mel_dev = pcm_dev = NULL runs on it
+// with no second encoder pass (decode_begin sets up dec_tokens, dec_state and the cache again; nothing of the detection is read).
+int wca_detect_language(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, int batch,
+                        int sot, int lang_begin, int n_lang, int32_t* lang_token_host, float* probs_host) {
+  const int rc = check_ready(e);
+  if (rc) return rc;
+  if (mel_dev != nullptr && pcm_dev != nullptr) return fail(WCA_ERR_INVALID, "pass at most one of mel_dev / pcm_dev");
+  if (!lang_token_host || !probs_host || (pcm_dev && !n_samples_host)) return fail(WCA_ERR_INVALID, "null argument");
+  if (batch < 1 || batch > e->max_batch) return fail(WCA_ERR_INVALID, "batch %d outside [1,%d]", batch, e->max_batch);
+  const wca_model_dims& D = e->dims;
+  const int V = D.n_vocab, dt = D.n_text_state, L = D.n_text_layer;
+  if (sot < 0 || sot >= V) return fail(WCA_ERR_INVALID, "sot %d outside the vocabulary", sot);
+  if (n_lang < 1 || n_lang > 128) return fail(WCA_ERR_INVALID, "n_lang %d outside [1,128]", n_lang);
+  if (lang_begin < 0 || lang_begin > V - n_lang) return fail(WCA_ERR_INVALID, "language tokens [%d,%d) outside the vocabulary", lang_begin, lang_begin + n_lang);
+  wca_engine::EncState* st = nullptr;
+  WCA_TRY(decode_take_state(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, &st));
+  const half_t* kvbuf = st->slot ? e->kv_alt : e->kv;
+  hipStream_t s2 = e->stream2;
+  const int T_max = 1;   // a one-slot self-attention cache: position 0 attends to itself
+  HIPCHK(e->dec_cache.ensure(sizeof(half_t) * (size_t)L * 2 * batch * T_max * dt));
+  HIPCHK(e->dec_tokens.ensure(sizeof(int) * (size_t)batch * T_max));
+  HIPCHK(e->dec_state.ensure((sizeof(float) * n_lang + sizeof(int)) * (size_t)batch));
+  int* tokens_dev = (int*)e->dec_tokens.p;
+  float* probs_dev = (float*)e->dec_state.p;
+  int* lang_dev = (int*)(probs_dev + (size_t)batch * n_lang);
+  const std::vector<int32_t> init((size_t)batch, sot);
+  HIPCHK(hipMemcpyAsync(tokens_dev, init.data(), sizeof(int) * init.size(), hipMemcpyHostToDevice, s2));
+  HIPCHK(hipStreamSynchronize(s2));  // `init` is pageable host memory
+  for (int phase = -1; phase < L; ++phase)
+    WCA_TRY(run_decode_step(e, s2, 0, kvbuf, tokens_dev, 0, batch, batch, StepPos{0, nullptr}, T_max, false, phase));
+  HIPCHK(launch_language_head(e->xd, e->lnf_g, e->lnf_b, e->tok_emb, batch, dt, V, lang_begin, n_lang, probs_dev, lang_dev, s2));
+  // probs [batch][n_lang] f32 and lang_token [batch] int32 sit back to back: one copy
+  std::vector<float> out((size_t)batch * (n_lang + 1));
+  HIPCHK(hipMemcpyAsync(out.data(), probs_dev, sizeof(float) * out.size(), hipMemcpyDeviceToHost, s2));
+  HIPCHK(hipStreamSynchronize(s2));
+  memcpy(probs_host, out.data(), sizeof(float) * (size_t)batch * n_lang);
+  memcpy(lang_token_host, out.data() + (size_t)batch * n_lang, sizeof(int32_t) * (size_t)batch);
+  st->detected = true;
+  return WCA_OK;
 }
 
 int wca_last_decode_positions(wca_engine* e, int32_t* prefill_positions, int32_t* step_positions) {

@@ -187,7 +187,9 @@ struct wca_engine {
   // Encoded micro-batches (log-mel + encoder + cross-K/V done, recorded on `stream`) that no alignment has consumed
   // yet: wca_encode_batch / wca_greedy_decode push, wca_align_batch_enqueue(pcm_dev = NULL) pops the oldest. A K/V
   // slot stays busy from its encode until the alignment that consumed it has been fetched.
-  struct EncState { int slot; int batch; bool decoded; };
+  // detected: wca_detect_language has read this (still undecoded) state; it waits for the decode that follows with mel_dev = pcm_dev = NULL
+  // and is dropped, like a decoded one, when a decode or a detection brings an input of its own
+  struct EncState { int slot; int batch; bool decoded; bool detected = false; };
   std::deque<EncState> enc_q;
   bool slot_busy[2] = {false, false};
   int res_kvslot[2] = {-1, -1};

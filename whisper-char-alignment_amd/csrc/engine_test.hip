@@ -299,6 +299,17 @@ int wca_test_decode_select_rows(wca_engine* e, const float* logits_dev, int batc
   return WCA_OK;
 }
 
+int wca_test_language_head(wca_engine* e, const float* x_dev, int B, int lang_begin, int n_lang, float* probs_dev, int32_t* lang_token_dev) {
+  if (!e || !x_dev || !probs_dev || !lang_token_dev) return fail(WCA_ERR_INVALID, "null argument");
+  if (!e->finalized) return fail(WCA_ERR_STATE, "weights not finalized (call wca_finalize_weights)");
+  HIPCHK(hipSetDevice(e->device));
+  if (launch_language_head(x_dev, e->lnf_g, e->lnf_b, e->tok_emb, B, e->dims.n_text_state, e->dims.n_vocab, lang_begin, n_lang, probs_dev,
+                           lang_token_dev, e->stream) != hipSuccess)
+    return fail(WCA_ERR_INVALID, "the language head takes B >= 1, 1 <= n_lang <= 128 and language tokens [%d,%d) inside the vocabulary", lang_begin,
+                lang_begin + n_lang);
+  return WCA_OK;
+}
+
 int wca_test_attention_rows(wca_engine* e, const void* q, const void* k, const void* v, void* o, int B, int H, int nq, int nk,
                             const int32_t* nk_rows_dev, int causal) {
   if (!e || !q || !k || !v || !o || !nk_rows_dev) return fail(WCA_ERR_INVALID, "null argument");

@@ -204,6 +204,12 @@ hipError_t launch_decode_select(const DecodeSelectArgs& a, int B, hipStream_t s)
 // out[b] = softmax(logits[b])[token]  (no_speech_prob: the <|nospeech|> probability at the <|sot|> position)
 hipError_t launch_token_prob(const float* logits, int ld, int n_vocab, int token, float* out, int B, hipStream_t s);
 hipError_t launch_f32_to_f16(const float* in, half_t* out, size_t n, hipStream_t s);
+// ---------------------------------------------------------------- language identification head (language_head.hip)
+// x [B][d] f32: the final residual stream at the <|sot|> position. Per row: xn = f16(LayerNorm(x; gamma, beta)), logit_j = xn . tok_emb[lang_begin + j]
+// (fp32 accumulation) for j < n_lang, probs [B][n_lang] = softmax(logit), lang_token [B] = lang_begin + argmax (lowest index among equals).
+// hipErrorInvalidValue: d % 8 != 0 (or d > 1280), n_lang outside [1, 128], [lang_begin, lang_begin + n_lang) not inside [0, n_vocab).
+hipError_t launch_language_head(const float* x, const float* gamma, const float* beta, const half_t* tok_emb, int B, int d, int n_vocab,
+                                int lang_begin, int n_lang, float* probs, int* lang_token, hipStream_t s);
 // ---------------------------------------------------------------- teacher-token log-probabilities (token_prob.hip)
 // the f32 rows that predict a text token: row (b, sot_len + i) of x [B * n_tok_max][d] for i < n_tok[b] - sot_len - 2 -> out [row_off[b] + i][d],
 // row_map[row_off[b] + i] = b * n_tok_max + i (n_tok, row_off: device [B]; n_text_max >= every n_text)

@@ -3,10 +3,15 @@ probe_oracle.py:37,59-60, README.md:107-108) on the MI355X engine (C ABI wca_gre
 
 Upstream openai-whisper `decoding.py` is an absent third-party dependency; its published algorithm is restated here
 (host side: which tokens the filters suppress) and in csrc/decode.hip (the per-step filters and GreedyDecoder.update).
-Built: a given language (no detection), temperature 0 without beam search (greedy), and conditioning on a prompt and / or
+Built: language identification (`detect_language`, C ABI wca_detect_language: one decoder position and the language head on the GPU;
+the encoded state stays for the decode that follows, so detecting and decoding a window costs ONE encoder pass where upstream runs two),
+decode in a given language (DecodingOptions(language=None) is refused: call detect_language first, or transcribe(language="auto")),
+temperature 0 without beam search (greedy), and conditioning on a prompt and / or
 a prefix (DecodingOptions(prompt=...), the decoder side of transcribe(initial_prompt=...); prefix=...), whose initial tokens
 go through the decoder in one batched forward (wca_greedy_decode_ex, prefill); a list of options gives every batch row a
 prompt / prefix of its own (wca_greedy_decode_rows). Anything else raises NotImplementedError instead of silently differing.
+PARITY UNPINNED against upstream itself for decode and detect_language alike (no real checkpoint is at hand): both are pinned
+against this repository's fp32 CPU oracle on synthetic weights.
 """
 import dataclasses
 import zlib
@@ -96,7 +101,8 @@ def _check_supported(options):
         raise NotImplementedError("only greedy decoding (temperature 0, no beam search / best_of) is built; the reference "
                                   "uses DecodingOptions(language='en') (infer_ali.py:40)")
     if options.language is None:
-        raise NotImplementedError("language detection is not built: pass DecodingOptions(language=...) as infer_ali.py:40 does")
+        raise NotImplementedError("decode takes a given language: pass DecodingOptions(language=...) as infer_ali.py:40 does; "
+                                  "detect_language(model, mel) names it, and transcribe(language=\"auto\") does both")
 
 
 def _text_tokens(tokenizer, text, options, what):
@@ -133,6 +139,32 @@ def decode_plan(tokenizer, options, n_ctx):
     if len(initial) > n_ctx:
         raise ValueError("the prompt and prefix give %d initial tokens, more than n_text_ctx = %d: nothing can be decoded" % (len(initial), n_ctx))
     return initial, min(sample_len, n_ctx + 1 - len(initial)), initial.index(tokenizer.sot)
+
+
+@torch.no_grad()
+def detect_language(model, mel, tokenizer=None, *, pcm=None, n_samples=None):
+    """whisper.detect_language(model, mel, tokenizer) -> (language_tokens, language_probs): the most probable language token of
+    every row ([B] int64 tensor) and one {language code: probability} dict per row; a [n_mels, 3000] mel gives a 0-dim tensor and
+    one dict. mel: f32 cuda tensor, or None with pcm [B, stride] f32 cuda + n_samples (the log-mel then runs on the device).
+    The default tokenizer numbers model.num_languages languages, as upstream. A model without language tokens (English-only)
+    raises upstream's ValueError. The encoded state stays in the engine: decode(model, None, options, encoded_batch=B) right after
+    decodes these rows with no second encoder pass."""
+    if tokenizer is None:
+        tokenizer = get_tokenizer(model.is_multilingual, num_languages=model.num_languages)
+    if tokenizer.language is None or tokenizer.language_token not in tokenizer.sot_sequence:
+        raise ValueError("This model doesn't have language tokens so it can't perform lang id")
+    single = mel is not None and mel.ndim == 2
+    if single:
+        mel = mel.unsqueeze(0)
+    lang_tokens, codes = tokenizer.all_language_tokens, tokenizer.all_language_codes
+    if list(lang_tokens) != list(range(lang_tokens[0], lang_tokens[0] + len(lang_tokens))):
+        raise ValueError("the tokenizer's language tokens are not one contiguous id range")
+    tokens, probs = model.detect_language(mel, pcm=pcm, n_samples=n_samples, sot=tokenizer.sot, lang_begin=lang_tokens[0], n_lang=len(lang_tokens))
+    language_tokens = torch.from_numpy(np.asarray(tokens, dtype=np.int64))
+    language_probs = [{c: float(p) for c, p in zip(codes, row)} for row in probs]
+    if single:
+        return language_tokens[0], language_probs[0]
+    return language_tokens, language_probs
 
 
 @torch.no_grad()

@@ -1,5 +1,5 @@
 """`import whisper` stand-in covering exactly what the reference touches (timing.py:7-10, infer_ali.py:18-20,36-41,60,
-dataset.py:4,47-48, README.md:93-108): load_model / decode / DecodingOptions / pad_or_trim / log_mel_spectrogram and the
+dataset.py:4,47-48, README.md:93-108): load_model / decode / detect_language / DecodingOptions / pad_or_trim / log_mel_spectrogram and the
 `audio`, `model`, `timing`, `tokenizer` sub-modules, plus upstream's long-form `transcribe` (`whisper.transcribe.transcribe`:
 temperature 0, word times from the character aligner; see the package's transcribe.py). Nothing is downloaded: `load_model(name)` reads a LOCAL checkpoint,
 `download_root/<name>.pt` or $WCA_WEIGHTS_DIR/<name>.pt (openai format)."""
@@ -19,6 +19,7 @@ log_mel_spectrogram = _audio.log_mel_spectrogram
 DecodingOptions = _decoding.DecodingOptions
 DecodingResult = _decoding.DecodingResult
 decode = _decoding.decode
+detect_language = _decoding.detect_language
 
 
 def load_model(name, device="cuda:0", download_root=None, in_memory=False, max_batch=8, precision=None):
@@ -47,6 +48,7 @@ tokenizer = _types.ModuleType("whisper.tokenizer")
 tokenizer.get_tokenizer, tokenizer.Tokenizer, tokenizer.LANGUAGES = _tok.get_tokenizer, _tok.Tokenizer, _tok.LANGUAGES
 decoding = _types.ModuleType("whisper.decoding")
 decoding.DecodingOptions, decoding.DecodingResult, decoding.decode = DecodingOptions, DecodingResult, decode
+decoding.detect_language = detect_language   # (model.detect_language is WhisperAMD.detect_language)
 # like upstream, `whisper.transcribe` is the function (it shadows the sub-module, which stays importable as whisper.transcribe.transcribe)
 def transcribe(model, audio, **kwargs):
     return _transcribe.transcribe(model, audio, **kwargs)

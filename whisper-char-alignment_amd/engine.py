@@ -524,6 +524,26 @@ class WhisperAMD:
         row_args = (init.ctypes.data_as(_lib._pi32), _lib.i32_array(n_init), _lib.i32_array(sot_index), _lib.i32_array(sample_len))
         return self._greedy_call(self._lib.wca_greedy_decode_rows, opts, row_args, mel, pcm, n_samples, B, T, suppress_mask, blank_mask, no_speech)
 
+    def detect_language(self, mel=None, tokenizer=None, *, pcm=None, n_samples=None, batch=None, sot=None, lang_begin=None, n_lang=None):
+        """model.detect_language(mel, tokenizer) -> (language_tokens, language_probs), upstream's schema (decoding.detect_language).
+        With sot / lang_begin / n_lang it is the thin C ABI call (wca_detect_language): mel [B,n_mels,3000] f32 cuda XOR pcm [B,stride]
+        f32 cuda (+ n_samples), or neither with batch=B (the state queued by encode_batch) -> (lang_token [B] int32, probs [B, n_lang] f32)
+        as numpy arrays. The encoded state stays in the engine for a following decode(..., encoded_batch=B)."""
+        if sot is None:
+            from . import decoding
+            return decoding.detect_language(self, mel, tokenizer, pcm=pcm, n_samples=n_samples)
+        self._bind_stream()
+        B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(batch))
+        if mel is not None:
+            mel = mel.to(self.device).contiguous().float()
+        lang = np.zeros(max(B, 1), dtype=np.int32)
+        probs = np.zeros((max(B, 1), max(int(n_lang), 1)), dtype=np.float32)
+        _lib.check(self._lib.wca_detect_language(
+            self._h, _ptr(mel) if mel is not None else None, _ptr(pcm) if pcm is not None else None, pcm.shape[1] if pcm is not None else 0,
+            _lib.i32_array(n_samples) if n_samples is not None else None, B, int(sot), int(lang_begin), int(n_lang),
+            lang.ctypes.data_as(_lib._pi32), probs.ctypes.data_as(_lib._pf)))
+        return lang[:B], probs[:B]
+
     def last_decode_positions(self):
         """(positions per row fed by the batched prefill, positions fed one decode step at a time) of the last greedy_decode."""
         pre, step = C.c_int32(0), C.c_int32(0)

@@ -1,7 +1,8 @@
 """Tokenizer handle: what callers pass as `tokenizer` (reference: whisper.tokenizer.get_tokenizer at
 infer_ali.py:41 / README.md:95). Exposes the members the reference touches: `sot_sequence`,
 `no_timestamps`, `eot`, `encode`, `decode` (plot.py:52), `split_tokens_on_unicode` (retokenize.py:24),
-`split_to_word_tokens` (retokenize.py:22), `decode_with_timestamps`.
+`split_to_word_tokens` (retokenize.py:22), `decode_with_timestamps`, and upstream's language members
+`language_token`, `all_language_tokens`, `all_language_codes` (decoding.detect_language).
 
 Character alignment over ASCII needs only the GPT-2 byte -> rank table, which is derivable offline
 (' ' -> 220, 'a' -> 64). Sub-word mode and non-ASCII text need the real merge
@@ -144,6 +145,29 @@ class Tokenizer:
         if self.task is not None:
             seq.append(self.transcribe if self.task == "transcribe" else self.translate)
         return tuple(seq)
+
+    # ---- language tokens (whisper.tokenizer.Tokenizer, upstream, restated)
+    @cached_property
+    def language_token(self):
+        """The token id of the language this tokenizer is configured with."""
+        if self.language is None:
+            raise ValueError("This tokenizer does not have language token configured")
+        return self.to_language_token(self.language)
+
+    def to_language_token(self, language):
+        token = self.special_tokens.get("<|%s|>" % language)
+        if token is not None:
+            return token
+        raise KeyError("Language %s not found in tokenizer." % language)
+
+    @cached_property
+    def all_language_tokens(self):
+        """The language tokens in LANGUAGES order: the contiguous ids sot + 1 ... sot + num_languages."""
+        return tuple(tid for text, tid in self.special_tokens.items() if text.strip("<|>") in LANGUAGES)[:self.num_languages]
+
+    @cached_property
+    def all_language_codes(self):
+        return tuple(self.decode([t]).strip("<|>") for t in self.all_language_tokens)
 
     @cached_property
     def sot_sequence_including_notimestamps(self):

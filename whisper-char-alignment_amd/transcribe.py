@@ -18,7 +18,16 @@ Limits (part of the contract):
   * temperature is 0.0 (or a tuple holding only 0.0); anything else raises NotImplementedError -- the fallback ladder needs
     sampling, which decoding._check_supported refuses. Without a ladder compression_ratio_threshold / logprob_threshold
     cannot trigger a re-decode: the temperature-0 result is accepted, as upstream accepts the last rung of its ladder.
-    language=None (detection) is refused as in decode.
+  * the language is given, or language="auto" detects it (decoding.detect_language, C ABI wca_detect_language) on each recording's
+    first window mel_window(mel, 0, size) -- the frames the first decode sees; upstream also detects on the first 30 s -- in the
+    99-language numbering of the decode tokenizer, so the detected token is the one that lands in the sot sequence. The first windows
+    of a group are detected in ONE batch; the result carries the detected "language" and its "language_probability". One decode cannot
+    mix languages, so transcribe_batch partitions a group by detected language and runs the lock-step loop once per language. Where
+    the whole group comes out in one language (transcribe() always does), the first round decodes the encoder state that detection
+    left in the engine (decode(..., encoded_batch=B)): detection then costs one decoder position, not a second encoder pass.
+    Otherwise the group is simply re-encoded language by language. An English-only model reports "en" without a detection pass
+    (probability None), and so little audio that there is no window to look at leaves "language" None. language=None stays refused
+    (NotImplementedError), as in decode: say "auto". PARITY UNPINNED against upstream, like decode.
   * transcribe() takes one recording, window after window (window k+1 starts where window k ended). transcribe_batch() takes
     several and runs them in lock-step: every round decodes the next window of every unfinished recording in ONE batch
     (wca_greedy_decode_rows: every row carries its own previous text as the prompt, so the rows sit at different decoder
@@ -73,7 +82,8 @@ def check_supported(temperature, language):
         raise NotImplementedError("transcribe runs at temperature 0.0 only: the fallback ladder %r needs sampling, which the engine's "
                                   "greedy decode does not do (decoding._check_supported)" % (temperature,))
     if language is None:
-        raise NotImplementedError("language detection is not built: pass language=... (as DecodingOptions(language=...) in decode)")
+        raise NotImplementedError("language=None is not taken: pass language=\"auto\" to detect it on the first window "
+                                  "(decoding.detect_language), or the language itself (as DecodingOptions(language=...) in decode)")
     return 0.0
 
 
@@ -320,10 +330,12 @@ def _as_pcm(audio, model, sample_rate=SAMPLE_RATE):
 def transcribe(model, audio, *, language, initial_prompt=None, condition_on_previous_text=True, no_speech_threshold=0.6,
                logprob_threshold=-1.0, word_timestamps=False, word_confidence=False, aligned_unit_type="char", aggr="topk", topk=10,
                medfilt_width=3, vocab_path=None, temperature=0.0, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0, decode_window=None,
-               sample_rate=SAMPLE_RATE, **decode_options):
+               detect_languages=None, sample_rate=SAMPLE_RATE, **decode_options):
     """whisper.transcribe(model, audio, ...) -> {"text", "segments": [{"id", "seek", "start", "end", "text", "tokens", "temperature",
     "avg_logprob", "compression_ratio", "no_speech_prob", "words": [{"word", "start", "end", "probability"}]}], "language"} plus
     "windows" (every decoded window: seek, size, advance, skipped, max_frames, aligned) and "windows_without_words".
+    language: a code or name, or "auto": the language is detected on the first window ("language" is then the detected code and
+    "language_probability", present only then, its probability) and the first decode runs on the encoder state detection left behind.
     audio: a path (audio.load_audio: any rate from 2 to 384 kHz, up to 8 channels), or a numpy array or tensor of mono samples [n] (or
     [channels, n]) at `sample_rate` Hz, any length. Audio that is not at 16 kHz is resampled on the GPU first (WhisperAMD.resample), as
     upstream's load_audio has ffmpeg do. word_timestamps=True: word times
@@ -338,24 +350,30 @@ def transcribe(model, audio, *, language, initial_prompt=None, condition_on_prev
                             no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold, word_timestamps=word_timestamps,
                             word_confidence=word_confidence, aligned_unit_type=aligned_unit_type, aggr=aggr, topk=topk, medfilt_width=medfilt_width,
                             vocab_path=vocab_path, temperature=temperature, w_colnorm=w_colnorm, w_rownorm=w_rownorm, w_coverage=w_coverage,
-                            decode_windows=decode_windows, sample_rate=sample_rate, **decode_options)[0]
+                            decode_windows=decode_windows, detect_languages=detect_languages, sample_rate=sample_rate, **decode_options)[0]
 
 
 def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_on_previous_text=True, no_speech_threshold=0.6,
                      logprob_threshold=-1.0, word_timestamps=False, word_confidence=False, aligned_unit_type="char", aggr="topk", topk=10,
                      medfilt_width=3, vocab_path=None, temperature=0.0, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0, decode_windows=None,
-                     sample_rate=SAMPLE_RATE, **decode_options):
+                     detect_languages=None, sample_rate=SAMPLE_RATE, **decode_options):
     """transcribe() of several recordings in lock-step: a list with transcribe()'s result for every recording of `audios`, in order.
     Each round cuts the next window of every unfinished recording, decodes them in ONE batch with every row's own previous text as its
     prompt (decoding.decode with one DecodingOptions per row: wca_greedy_decode_rows) and, with word_timestamps, aligns the rows that
     have words in one align_batch(pcm=None) on the state that decode left behind. The batch shrinks as recordings end; more recordings
     than model.max_batch are processed in groups of max_batch. The keyword arguments are transcribe()'s; sample_rate is one int for
     every array / tensor input or one per recording (a path carries its own rate);
-    decode_windows(mel_windows [B, n_mels, 3000], prompts: B token lists) -> B DecodingResults replaces the engine's decode (tests)."""
+    decode_windows(mel_windows [B, n_mels, 3000], prompts: B token lists) -> B DecodingResults replaces the engine's decode (tests).
+    language="auto": the first windows of a group are detected in one batch (detect_languages(mel_windows [B, n_mels, 3000]) ->
+    (B codes, B probabilities) replaces the engine's detection: tests), the group is partitioned by detected language and the
+    lock-step loop runs once per language (one decode cannot mix languages); the results still come back in input order, each with
+    its own "language" and "language_probability". A group that comes out in ONE language decodes its first round on the encoder state
+    detection left in the engine (no second encoder pass); a group with several languages is simply re-encoded, language by language."""
     from . import decoding
     from .tokenizer import get_tokenizer
     import torch
     check_supported(temperature, language)
+    auto = isinstance(language, str) and language.lower() == "auto"
     if word_confidence and not word_timestamps:
         raise ValueError("word_confidence is a property of the aligned words: it needs word_timestamps=True")
     if word_timestamps and vocab_path is None:
@@ -363,44 +381,70 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
     max_batch = int(getattr(model, "max_batch", 1))
     if max_batch < 1:
         raise ValueError("transcribe_batch needs model.max_batch >= 1")
-    tokenizer = get_tokenizer(model.is_multilingual, language=language, task=decode_options.get("task", "transcribe"), vocab_path=vocab_path)
+    task = decode_options.get("task", "transcribe")
+    tokenizers = {}
+
+    def tokenizer_for(code):   # (the special tokens but the language's own are the same in every language)
+        if code not in tokenizers:
+            tokenizers[code] = get_tokenizer(model.is_multilingual, language=code, task=task, vocab_path=vocab_path)
+        return tokenizers[code]
+
     prompt_tokens = []
     if initial_prompt is not None:
-        prompt_tokens = decoding._text_tokens(tokenizer, initial_prompt, decoding.DecodingOptions(vocab_path=vocab_path), "initial_prompt")
+        prompt_tokens = decoding._text_tokens(tokenizer_for(None if auto else language), initial_prompt,
+                                              decoding.DecodingOptions(vocab_path=vocab_path), "initial_prompt")
+    state_left = [None]   # rows of the encoded, undecoded state the engine's own detection left behind, for the decode that comes next
 
-    if decode_windows is None:
-        def decode_windows(mel_windows, prompts):
-            def options(prompt):
-                return decoding.DecodingOptions(language=language, temperature=0.0, prompt=list(prompt) or None, vocab_path=vocab_path,
-                                                **decode_options)
+    if auto and detect_languages is None and model.is_multilingual:
+        det_tok = get_tokenizer(True, num_languages=99)   # the numbering the decode tokenizer uses
+
+        def detect_languages(mel_windows):
+            tokens, probs = decoding.detect_language(model, mel_windows, det_tok)
+            state_left[0] = len(probs)
+            codes = [det_tok.all_language_codes[int(t) - det_tok.all_language_tokens[0]] for t in tokens]
+            return codes, [p[c] for c, p in zip(codes, probs)]
+
+    def engine_decode(code):
+        def options(prompt):
+            return decoding.DecodingOptions(language=code, temperature=0.0, prompt=list(prompt) or None, vocab_path=vocab_path, **decode_options)
+
+        def run(mel_windows, prompts):
+            if state_left[0] == len(prompts):   # the first round of a group that detection found in one language: its state is waiting
+                state_left[0] = None
+                rows = options(prompts[0]) if len(prompts) == 1 else [options(p) for p in prompts]   # (one row: the uniform decode, as below)
+                return decoding.decode(model, None, rows, encoded_batch=len(prompts), want_text=vocab_path is not None)
+            state_left[0] = None
             if len(prompts) == 1:   # a single row (transcribe(), or the last recording of a group): a uniform decode of one window
                 return [decoding.decode(model, mel_windows[0], options(prompts[0]), want_text=vocab_path is not None)]
             return decoding.decode(model, mel_windows, [options(p) for p in prompts], want_text=vocab_path is not None)
+        return run
 
-    align = None
-    if word_timestamps:
-        align = make_aligner(model, tokenizer, aligned_unit_type=aligned_unit_type, aggr=aggr, topk=topk, medfilt_width=medfilt_width,
-                             w_colnorm=w_colnorm, w_rownorm=w_rownorm, w_coverage=w_coverage, word_confidence=word_confidence)
-    decode_text = tokenizer.decode if vocab_path is not None else (lambda toks: None)
+    decode_text = (lambda tok: tok.decode) if vocab_path is not None else (lambda tok: (lambda toks: None))
     audios = list(audios)
     rates = [int(r) for r in sample_rate] if isinstance(sample_rate, (list, tuple)) else [int(sample_rate)] * len(audios)
     if len(rates) != len(audios):
         raise ValueError("sample_rate lists %d rates for %d recordings" % (len(rates), len(audios)))
     results = [None] * len(audios)
-    for g0 in range(0, len(audios), max_batch):
-        group = list(range(g0, min(len(audios), g0 + max_batch)))
-        mels = {i: model.log_mel_long(_as_pcm(audios[i], model, rates[i])) for i in group}
+
+    def lock_step(rows, code, mels, extra):
+        """The lock-step loop over the recordings `rows` of a group, all in language `code`; fills their results."""
+        tokenizer = tokenizer_for(code)
+        decode_rows = decode_windows if decode_windows is not None else engine_decode(code)
+        align = None
+        if word_timestamps:
+            align = make_aligner(model, tokenizer, aligned_unit_type=aligned_unit_type, aggr=aggr, topk=topk, medfilt_width=medfilt_width,
+                                 w_colnorm=w_colnorm, w_rownorm=w_rownorm, w_coverage=w_coverage, word_confidence=word_confidence)
         states = {i: SeekState(mels[i].shape[1], tokenizer, initial_prompt_tokens=prompt_tokens,
                                condition_on_previous_text=condition_on_previous_text, no_speech_threshold=no_speech_threshold,
-                               logprob_threshold=logprob_threshold, decode_text=decode_text) for i in group}
+                               logprob_threshold=logprob_threshold, decode_text=decode_text(tokenizer)) for i in rows}
         while True:
-            live = [i for i in group if not states[i].done]   # a finished recording is never decoded again
+            live = [i for i in rows if not states[i].done]   # a finished recording is never decoded again
             if not live:
                 break
             requests = [states[i].request() for i in live]
             windows = [model.mel_window(mels[i], seek, size) for i, (seek, size, _) in zip(live, requests)]
             windows = torch.stack(windows) if len(live) > 1 else windows[0][None]   # (one row: a view, no copy)
-            decoded = decode_windows(windows, [prompt for _, _, prompt in requests])
+            decoded = decode_rows(windows, [prompt for _, _, prompt in requests])
             pending = [states[i].receive(r) for i, r in zip(live, decoded)]
             if align is not None and len(live) == 1:
                 aligned = [align(*pending[0]) if pending[0] is not None else None]
@@ -411,11 +455,34 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
             for i, pend, al in zip(live, pending, aligned):
                 if pend is not None:
                     states[i].commit(al)
-        for i in group:
+        for i in rows:
             out = states[i].result()
             text = tokenizer.decode(out["tokens"][len(prompt_tokens):]) if vocab_path is not None else ""
-            results[i] = {"text": text, "segments": out["segments"], "language": language, "windows": out["windows"],
+            results[i] = {"text": text, "segments": out["segments"], "language": code, **extra.get(i, {}), "windows": out["windows"],
                           "windows_without_words": out["windows_without_words"]}
+
+    for g0 in range(0, len(audios), max_batch):
+        group = list(range(g0, min(len(audios), g0 + max_batch)))
+        mels = {i: model.log_mel_long(_as_pcm(audios[i], model, rates[i])) for i in group}
+        if not auto:
+            lock_step(group, language, mels, {})
+            continue
+        codes, extra = {i: None for i in group}, {i: {"language_probability": None} for i in group}
+        heard = [i for i in group if mels[i].shape[1] > N_FRAMES]   # recordings that have a first window
+        if detect_languages is None:   # an English-only model: "en" without a detection pass, as upstream
+            codes.update({i: "en" for i in heard})
+        elif heard:
+            first = [model.mel_window(mels[i], 0, min(N_FRAMES, mels[i].shape[1] - N_FRAMES)) for i in heard]
+            found, probs = detect_languages(torch.stack(first) if len(heard) > 1 else first[0][None])
+            for i, code, prob in zip(heard, found, probs):
+                codes[i], extra[i] = code, {"language_probability": None if prob is None else float(prob)}
+        by_language = {}
+        for i in group:
+            by_language.setdefault(codes[i], []).append(i)
+        if len(by_language) != 1 or heard != group:
+            state_left[0] = None   # the detected rows are not one decode batch: every language's first round encodes its own windows
+        for code, rows in by_language.items():
+            lock_step(rows, code, mels, extra)
     return results
 
 
@@ -430,7 +497,8 @@ def parse_args(argv=None):
     p.add_argument("--weights", type=str, default=None, help="local openai-whisper checkpoint (.pt)")
     p.add_argument("--random_init", action="store_true", help="seeded random weights (dry run without a checkpoint)")
     p.add_argument("--vocab", type=str, default=None, help="local tiktoken vocabulary file (text output, word times)")
-    p.add_argument("--language", type=str, default="en")
+    p.add_argument("--language", type=str, default="en", help="a language code or name, or `auto`: detected on each recording's first window "
+                   "(the detected code and its probability go into the output JSON)")
     p.add_argument("--initial_prompt", type=str, default=None)
     p.add_argument("--no_condition_on_previous_text", action="store_true")
     p.add_argument("--word_timestamps", action="store_true")
