@@ -461,6 +461,47 @@ int wca_test_gemm_ln(wca_engine* e, const void* a_f16_dev, const void* w_f16_dev
  * 7 its residual + LayerNorm form; WCA_ERR_INVALID (reason in wca_last_error) where launch_gemm returns hipErrorInvalidValue. */
 int wca_test_gemm_plan(int M, int N, int K, int lda, int out_mode, int gelu, int a_lo, int force_tile, int site, int n_cu, int cu_limit, int flags,
                        int64_t sk_bytes, int32_t* out);
+/* wca_test_gemm with every field of the launch description open to the caller -- the strided and batch-strided forms the engine's forward
+ * builds (csrc/engine_forward.hip: the conv stem's overlapping windows, the positional table, the pre-activation addend, pair rows,
+ * a CU-partitioned stream). Logical row m = b * rows_per_batch + t of A / C lives at base + b * batch_stride + t * ld (rows_per_batch 0: flat,
+ * m * ld); a_lo > 0: A rows are [hi | lo] pairs a_lo elements apart against the plain W; c_lo: out_mode 4's distance from hi to lo;
+ * addend [M][ld_addend] f32 is added before the GELU, pos [pos_period][N] f32 after it (row m takes pos[m % pos_period]); force_tile 0 / 64 /
+ * 128 / 256 / 257 / 258 and out_mode 0 / 1 / 2 / 4 as wca_test_gemm_plan. plan_out[2] = {kernel (numbered as in wca_test_gemm_plan), grid x} of
+ * the launch. A launch the plan refuses is WCA_ERR_INVALID with the plan's reason and writes nothing. Asynchronous on the engine's stream. */
+typedef struct wca_test_gemm_desc {
+  const void* a;
+  const void* w;
+  const float* bias;    /* nullable */
+  void* c;
+  const float* addend;  /* nullable */
+  const float* pos;     /* nullable */
+  int64_t a_batch_stride, c_batch_stride, a_lo, c_lo;
+  int32_t M, N, K;
+  int32_t lda, ldw, ldc;
+  int32_t a_rows_per_batch, c_rows_per_batch;
+  int32_t ld_addend, pos_period;
+  int32_t gelu, out_mode, force_tile, site, cu_limit, supertile;
+} wca_test_gemm_desc;
+int wca_test_gemm_ex(wca_engine* e, const wca_test_gemm_desc* desc, int32_t* plan_out);
+/* wca_test_attention / _split / _rows with every stride open to the caller (element strides; head h of a row at column h * 64; base offsets are
+ * applied by the caller to the pointers): split != 0 = pair operands, the lo half of an element *_lo elements after its hi half;
+ * cap [b * cap_bs + h * cap_hs + q * cap_ld + key] f32 for key < cap_cols, or NULL; nk_rows device [B] int32 or NULL (one-query f16 form only);
+ * causal 0 / 1; variant 0 auto / 1 / 2 as wca_test_attention. Scale 1/8. Asynchronous on the engine's stream. */
+typedef struct wca_test_attn_desc {
+  const void* q;
+  const void* k;
+  const void* v;
+  void* o;
+  float* cap;               /* nullable */
+  const int32_t* nk_rows;   /* nullable */
+  int64_t q_bs, k_bs, v_bs, o_bs;
+  int64_t q_lo, k_lo, v_lo, o_lo;
+  int64_t cap_bs, cap_hs;
+  int32_t q_rs, k_rs, v_rs, o_rs;
+  int32_t cap_ld, cap_cols;
+  int32_t split, B, H, nq, nk, causal, variant;
+} wca_test_attn_desc;
+int wca_test_attention_ex(wca_engine* e, const wca_test_attn_desc* desc);
 /* The few-row GEMM of the greedy-decode steps (gemm_rows.hip): C [M][N] = epilogue(A W^T + bias) with A = a_f16_dev [M][K] or,
  * when x_f32_dev != NULL, A = LayerNorm(x_f32_dev [M][K]; gamma, beta, eps 1e-5) computed in the kernel's prologue.
  * out_mode as wca_test_gemm; splitk 0 = smallest split with K / splitk <= 1024, groups 0 = chosen; kv_k / kv_v != NULL

@@ -86,6 +86,16 @@ def test_switch_table_reads_no_environment_and_rejects_removed_names(wca):
     assert lib.wca_test_set_switch(None, 1) < 0
     assert lib.wca_test_set_attn_split_drop(5) < 0 and lib.wca_test_set_attn_split_drop(9) == 0 and lib.wca_test_set_attn_split_drop(0) == 0
     assert lib.wca_weights_inexact(None, None, None, None, 0) < 0 and lib.wca_set_allow_rounded_weights(None, 1) < 0
+    # the strided kernel-level entry points refuse null arguments before their first HIP call: no engine, no description, no plan slot, no operands
+    gd, ad, plan = wca._lib.GemmDesc(), wca._lib.AttnDesc(), (ctypes.c_int32 * 2)(-1, -1)
+    for args in ((None, None, None), (None, ctypes.byref(gd), plan)):
+        assert lib.wca_test_set_switch(b"no_such_switch", 1) < 0 and b"null" not in lib.wca_last_error()
+        assert lib.wca_test_gemm_ex(*args) < 0 and b"null" in lib.wca_last_error() and list(plan) == [-1, -1]
+    for args in ((None, None), (None, ctypes.byref(ad))):
+        assert lib.wca_test_set_switch(b"no_such_switch", 1) < 0 and b"null" not in lib.wca_last_error()
+        assert lib.wca_test_attention_ex(*args) < 0 and b"null" in lib.wca_last_error()
+    # the descriptions mirror the header's structs: 6 pointers, then the 64-bit strides, then the 32-bit fields
+    assert ctypes.sizeof(gd) == 6 * 8 + 4 * 8 + 16 * 4 and ctypes.sizeof(ad) == 6 * 8 + 10 * 8 + 13 * 4 + 4
     # the library reads no environment variable on a launch path or in the switch table: the remaining getenv calls are one-time initialisers
     for f in ("gemm.hip", "attention.hip", "attention_split.hip", "postproc.hip", "elementwise.hip", "gemm_rows.hip", "dtw.hip", "logmel.hip", "decode.hip",
               "debug_switch.cpp"):

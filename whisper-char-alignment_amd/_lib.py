@@ -41,6 +41,21 @@ class DecodeOptsEx(C.Structure):
     _fields_ = DecodeOpts._fields_ + [("sot_index", C.c_int32), ("prefill", C.c_int32)]
 
 
+class GemmDesc(C.Structure):
+    """wca_test_gemm_desc of include/wca.h"""
+    _fields_ = ([(n, C.c_void_p) for n in ("a", "w", "bias", "c", "addend", "pos")] +
+                [(n, C.c_int64) for n in ("a_batch_stride", "c_batch_stride", "a_lo", "c_lo")] +
+                [(n, C.c_int32) for n in ("M", "N", "K", "lda", "ldw", "ldc", "a_rows_per_batch", "c_rows_per_batch", "ld_addend", "pos_period",
+                                          "gelu", "out_mode", "force_tile", "site", "cu_limit", "supertile")])
+
+
+class AttnDesc(C.Structure):
+    """wca_test_attn_desc of include/wca.h"""
+    _fields_ = ([(n, C.c_void_p) for n in ("q", "k", "v", "o", "cap", "nk_rows")] +
+                [(n, C.c_int64) for n in ("q_bs", "k_bs", "v_bs", "o_bs", "q_lo", "k_lo", "v_lo", "o_lo", "cap_bs", "cap_hs")] +
+                [(n, C.c_int32) for n in ("q_rs", "k_rs", "v_rs", "o_rs", "cap_ld", "cap_cols", "split", "B", "H", "nq", "nk", "causal", "variant")])
+
+
 ERR_TOO_LONG = -2   # WCA_ERR_TOO_LONG
 AGGR_MEAN, AGGR_TOPK = 0, 1
 PRECISION_SITES = ("logmel", "conv", "enc_gemm", "enc_attn", "cross_kv", "dec", "capture")  # the stages on (hi, lo) pairs in split mode
@@ -100,6 +115,8 @@ SIGNATURES = {
     "wca_test_decode_select": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, C.POINTER(DecodeOpts), _vp, _vp]),
     "wca_test_gemm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "wca_test_gemm_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _pi32]),
+    "wca_test_gemm_ex": (_i, [_vp, C.POINTER(GemmDesc), _pi32]),
+    "wca_test_attention_ex": (_i, [_vp, C.POINTER(AttnDesc)]),
     "wca_test_gemm_ln": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "wca_test_set_attn_split_drop": (_i, [_i]),
     "wca_test_set_switch": (_i, [C.c_char_p, _i]),

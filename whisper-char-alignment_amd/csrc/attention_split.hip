@@ -221,7 +221,14 @@ __global__ __launch_bounds__(256, 2) void attn_split_kernel(AttnArgs a) {
             const int key4 = kt * KT + t * 16 + 4 * fg;
             if (key4 < a.cap_cols) {
               float* cp = a.cap + (long)b * a.cap_bs + (long)h * a.cap_hs + (long)qrow[s] * a.cap_ld + key4;
-              *reinterpret_cast<f32x4*>(cp) = st[s][t] * a.scale;
+              const f32x4 lg = st[s][t] * a.scale;
+              if (key4 + 4 <= a.cap_cols) {
+                *reinterpret_cast<f32x4*>(cp) = lg;
+              } else {   // the group that straddles cap_cols: the row's pad columns are not this launch's to write
+#pragma unroll
+                for (int r = 0; r < 3; ++r)
+                  if (key4 + r < a.cap_cols) cp[r] = lg[r];
+              }
             }
           }
         }

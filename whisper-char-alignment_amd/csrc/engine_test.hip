@@ -166,6 +166,79 @@ int wca_test_gemm_plan(int M, int N, int K, int lda, int out_mode, int gelu, int
   return WCA_OK;
 }
 
+int wca_test_gemm_ex(wca_engine* e, const wca_test_gemm_desc* d, int32_t* plan_out) {
+  if (!e || !d || !plan_out || !d->a || !d->w || !d->c) return fail(WCA_ERR_INVALID, "null argument");
+  GemmArgs g = flat((const half_t*)d->a, d->lda, (const half_t*)d->w, d->ldw, d->c, d->ldc, d->M, d->N, d->K);
+  g.bias = d->bias;
+  g.addend = d->addend;
+  g.ld_addend = d->ld_addend;
+  g.pos = d->pos;
+  g.pos_period = d->pos_period;
+  g.a_rows_per_batch = d->a_rows_per_batch;
+  g.a_batch_stride = (long)d->a_batch_stride;
+  g.c_rows_per_batch = d->c_rows_per_batch;
+  g.c_batch_stride = (long)d->c_batch_stride;
+  g.a_lo = (long)d->a_lo;
+  g.c_lo = (long)d->c_lo;
+  g.gelu = d->gelu;
+  g.out_mode = d->out_mode;
+  g.force_tile = d->force_tile;
+  g.site = d->site;
+  g.cu_limit = d->cu_limit;
+  g.supertile = d->supertile;
+  g.sk_part = e->sk_big[0];
+  g.sk_bytes = e->sk_big_bytes;
+  if (g.pos != nullptr && g.pos_period <= 0) return fail(WCA_ERR_INVALID, "a positional table needs pos_period > 0");
+  if (g.addend != nullptr && g.ld_addend < g.N) return fail(WCA_ERR_INVALID, "ld_addend < N");
+  const GemmPlan p = plan_gemm(g, e->n_cu);
+  if (p.refused) return fail(WCA_ERR_INVALID, "GEMM refused: %s", p.refused);
+  plan_out[0] = (int32_t)p.kernel;
+  plan_out[1] = (int32_t)p.grid_x;
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(launch_gemm(g, e->stream));
+  return WCA_OK;
+}
+
+int wca_test_attention_ex(wca_engine* e, const wca_test_attn_desc* d) {
+  if (!e || !d || !d->q || !d->k || !d->v || !d->o) return fail(WCA_ERR_INVALID, "null argument");
+  if (d->B < 1 || d->H < 1 || d->nq < 1 || d->nk < 1) return fail(WCA_ERR_INVALID, "bad shape");
+  if (d->variant < 0 || d->variant > 2) return fail(WCA_ERR_INVALID, "attention variant %d does not exist", d->variant);
+  AttnArgs a{};
+  a.Q = (const half_t*)d->q;
+  a.K = (const half_t*)d->k;
+  a.V = (const half_t*)d->v;
+  a.O = (half_t*)d->o;
+  a.q_bs = (long)d->q_bs;
+  a.k_bs = (long)d->k_bs;
+  a.v_bs = (long)d->v_bs;
+  a.o_bs = (long)d->o_bs;
+  a.q_rs = d->q_rs;
+  a.k_rs = d->k_rs;
+  a.v_rs = d->v_rs;
+  a.o_rs = d->o_rs;
+  a.split = d->split;
+  a.q_lo = (long)d->q_lo;
+  a.k_lo = (long)d->k_lo;
+  a.v_lo = (long)d->v_lo;
+  a.o_lo = (long)d->o_lo;
+  a.cap = d->cap;
+  a.cap_bs = (long)d->cap_bs;
+  a.cap_hs = (long)d->cap_hs;
+  a.cap_ld = d->cap_ld;
+  a.cap_cols = d->cap_cols;
+  a.nk_rows = d->nk_rows;
+  a.B = d->B;
+  a.H = d->H;
+  a.nq = d->nq;
+  a.nk = d->nk;
+  a.scale = 0.125f;
+  a.causal = d->causal & 1;
+  a.variant = d->variant;
+  HIPCHK(hipSetDevice(e->device));
+  if (launch_attention(a, e->stream) != hipSuccess) return fail(WCA_ERR_INVALID, "the attention launcher refused these arguments");
+  return WCA_OK;
+}
+
 int wca_test_gemm_rows(wca_engine* e, const void* a_f16, const float* x_f32, const float* gamma, const float* beta, const void* w,
                        const float* bias, void* c, int M, int N, int K, int gelu, int out_mode, int splitk, int groups, void* kv_k, void* kv_v,
                        int T_max, int kv_t) {

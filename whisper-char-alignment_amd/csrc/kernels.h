@@ -125,7 +125,7 @@ struct AttnArgs {
   half_t* O; long o_bs; int o_rs;
   float* cap;                              // nullptr => no capture
   long cap_bs; long cap_hs; int cap_ld;    // cap[b*cap_bs + h*cap_hs + q*cap_ld + key]
-  int cap_cols;                            // keys [0, cap_cols) are captured (cap_ld % 4 == 0, cap_ld >= roundup4(cap_cols))
+  int cap_cols;                            // keys [0, cap_cols) are captured, and nothing past them is written (cap_ld % 4 == 0, cap_ld >= roundup4(cap_cols))
   int nq, nk, H, B;
   float scale;                             // applied to q.k (head_dim^-0.5)
   int causal;

@@ -69,9 +69,15 @@ __device__ __forceinline__ float wave_max(float v) {
 
 // Exact-erf GELU, GELU(x) = x * Phi(x), evaluated as  max(x, 0) - | 0.5 * x * erfc(|x| / sqrt(2)) |  with erfc from
 // Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7 on erf): t = 1 / (1 + p|x|/sqrt2), erfc = poly(t) * exp(-x^2/2). The 0.5
-// and the sqrt(2) are folded into the constants; one v_rcp + one v_exp + 9 plain VALU ops per element. Measured
-// against float64 erf over [-12, 12]: max abs error 3.3e-7, max relative error 1.7e-4 (below the 2^-11 rounding
-// of the f16 store that follows), i.e. this is the erf GELU of whisper.model, not the tanh approximation.
+// and the sqrt(2) are folded into the constants; one v_rcp + one v_exp + 16 plain VALU ops per element.
+// The error of 7.1.26 is absolute on erf, so RELATIVE to the GELU's negative tail it grows: uncorrected, 5e-5 at x = -3, 1.9e-4 at -3.5,
+// 1.0e-3 at -4.6, 3 % at -12, and the f16 store of a tail value then misses |out - gelu| <= (2^-11 + 1.7e-4) |gelu| + 2^-25 by up to 9 % for
+// x in [-5.1, -4.3], where the result is an f16 subnormal and the rounding leaves no room. So past |x| = 3 the erfc term is multiplied by
+// 1 + m q(m), m = min(|x|, 12.25) - 3, q the degree-3 fit of (erfc / its approximation - 1) / m on [3, 12.25] (residual 6e-5). Up to |x| = 3
+// m is exactly 0 and the result is bit for bit the uncorrected one; past 12.25 the term is below 1e-34 and the factor stays put (and finite:
+// x^2 overflows there eventually). Against float64 x Phi(x) over [-12, 12], on the MI355X point by point through every epilogue
+// (tests/test_gemm_forms_gpu.py::test_gelu_point_by_point): max abs error 3.3e-7, max relative error 6.6e-5 (below the 2^-11
+// rounding of the f16 store that follows), i.e. this is the erf GELU of whisper.model, not the tanh approximation.
 __device__ __forceinline__ float gelu_erf(float x) {
   const float ax = fabsf(x);
   const float t = __builtin_amdgcn_rcpf(fmaf(ax, 0.2316418880f, 1.0f));
@@ -81,7 +87,11 @@ __device__ __forceinline__ float gelu_erf(float x) {
   p = fmaf(p, t, 0.1274147960f);
   const float e = __builtin_amdgcn_exp2f(x * x * -0.7213475204f);
   const float h = p * t * e * x;
-  return fmaxf(x, 0.f) - fabsf(h);
+  const float m = __builtin_amdgcn_fmed3f(ax, 3.0f, 12.25f) - 3.0f;
+  float q = fmaf(2.251457545e-06f, m, -2.580338150e-05f);
+  q = fmaf(q, m, -3.094311978e-04f);
+  q = fmaf(q, m, -1.082361923e-04f);
+  return fmaxf(x, 0.f) - fabsf(fmaf(q * m, h, h));
 }
 
 // Reference-precision ("split") mode: torch's erf GELU, x * 0.5 * (1 + erf(x / sqrt 2)), to fp32 accuracy -- the polynomial above is exact
