@@ -25,6 +25,10 @@
  *                          [len(sot_sequence):-1] slice (timing.py:102), DTW + backtrace (timing.py:103)
  *   wca_default_find_alignment  timing.py:116-186 default_find_alignment (std/mean normalised alignment heads)
  *   wca_dtw                timing.py:103     whisper.timing.dtw -> dtw_cpu + backtrace
+ *   wca_dtw_open, wca_dtw_batch_dev_open, wca_align_batch_enqueue_open / wca_align_batch_fetch_open
+ *                          no counterpart in the reference or upstream (their aligners stop at one 30 s window): the OPEN-END form
+ *                          of the same DTW, for a window of a long recording that holds only a prefix of the text it is offered
+ *                          (align_long.py: a recording of any length against a given transcript)
  *   wca_probe_heads        probe_oracle.py:83-90  per-head force_align sweep (one DTW per head)
  *   wca_greedy_decode      infer_ali.py:40,60-61, probe_oracle.py:59-60, README.md:107-108:
  *                          whisper.decode(model, mels, DecodingOptions(language="en")) -- the greedy ASR pre-pass
@@ -237,6 +241,24 @@ int wca_dtw(wca_engine* e, const float* matrix_host, int N, int M, int32_t* text
  * matrix_dev [P][N][M]; jump_frame_host [P][N]: frame at which the path enters each row. */
 int wca_dtw_batch_dev(wca_engine* e, const float* matrix_dev, int P, int N, int M, int32_t* jump_frame_host);
 
+/* Open-end DTW: the recurrence, tie rule and f64-add / f32-store of wca_dtw, but the path ends in the LAST frame at whichever text row fits
+ * best instead of at row N - 1. Every cell carries L, the number of cells on its chosen path (itself included); the end row n* minimises
+ * C[i][M-1] / L[i][M-1] (every visited cell adds a non-positive cost, so the unnormalised minimum would always be the last row). The
+ * comparison is exact -- row a beats row b iff (double)C_a * L_b < (double)C_b * L_a -- and equal scores go to the lower row.
+ * The path is backtraced from (n*, M - 1); *end_row_host = n*, *score_host (nullable) = (float)((double)C / (double)L) at the end cell, for
+ * diagnostics only. Limits as wca_dtw (N <= 512, M <= 4096). */
+int wca_dtw_open(wca_engine* e, const float* matrix_host, int N, int M, int32_t* text_idx_host, int32_t* time_idx_host,
+                 int32_t* path_len_host, int32_t* end_row_host, float* score_host);
+
+/* wca_dtw_batch_dev for P problems of which open_end_host[p] != 0 marks the open-ended ones; one launch may mix open and closed problems.
+ * n_rows_host / n_cols_host [P] (each nullable: all N / all M) make the launch ragged: problem p is the n_rows[p] x n_cols[p] top-left
+ * corner of its [N][M] slice of matrix_dev. jump_frame_host [P][N]: as wca_dtw_batch_dev for rows i <= end_row[p], -1 for the rows
+ * end_row[p] < i < n_rows[p] that the path does not reach, 0 beyond n_rows[p]. end_row_host [P] (N_p - 1 for a closed problem, whose jump
+ * frames are exactly wca_dtw_batch_dev's); score_host [P] nullable. */
+int wca_dtw_batch_dev_open(wca_engine* e, const float* matrix_dev, int P, int N, int M, const int32_t* n_rows_host,
+                           const int32_t* n_cols_host, const int32_t* open_end_host, int32_t* jump_frame_host, int32_t* end_row_host,
+                           float* score_host);
+
 /* probe_oracle.py:83-90: one alignment PER HEAD (aggregation "mean" on a single head = column
  * normalisation only), all L*H DTWs in one launch. ws_dev [L][H][n][F]; scores_host [L*H] = the
  * filter_attention scores (w_col = w_row = 1); jump_frame_host [L*H][n - sot_len - 1]. */
@@ -394,6 +416,18 @@ int wca_align_batch_enqueue_ex(wca_engine* e, const float* pcm_dev, int64_t pcm_
                                const int32_t* max_frames_host, int batch, const wca_align_opts* opts, int32_t vocab_end);
 int wca_align_batch_fetch_ex(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host,
                              int32_t* sel_idx_host, float* token_logprob_host);
+/* The fused pipeline with an open-end DTW per row: wca_align_batch_enqueue_ex plus open_end_host [batch] (row b's DTW is open-ended where
+ * open_end_host[b] != 0; a row with 0 gets exactly what wca_align_batch_enqueue_ex gives it). Everything upstream of the DTW is unchanged.
+ * wca_align_batch_fetch_open: wca_align_batch_fetch_ex plus end_row_host [batch] (the last text row of row b's path, counted in DTW rows,
+ * i.e. from the first token after the sot sequence: n_tok[b] - sot_len - 2 for a closed row; -1 where no DTW ran) and score_host [batch]
+ * (both nullable). Entries (end_row, n_tok[b] - sot_len - 1) of an open row's jump frames are -1. WCA_ERR_STATE (and nothing consumed)
+ * when they are requested but the pending batch was not enqueued with _enqueue_open. */
+int wca_align_batch_enqueue_open(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
+                                 const int64_t* tokens_dev, int n_tok_max, const int32_t* n_tok_host,
+                                 const int32_t* max_frames_host, int batch, const wca_align_opts* opts, int32_t vocab_end,
+                                 const int32_t* open_end_host);
+int wca_align_batch_fetch_open(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host,
+                               int32_t* sel_idx_host, float* token_logprob_host, int32_t* end_row_host, float* score_host);
 /* The same log-sum-exp kernel on caller-supplied logits (timing.py:146-149 on the logits wca_get_attentions returns): logits_dev [rows][ld]
  * f32 (ld >= vocab_end), targets_dev [rows] int64, out_dev [rows] f32 = log_softmax(logits[r][0 : vocab_end])[targets[r]]. Synchronous
  * on the engine stream; a target outside [0, vocab_end) gives NaN there and WCA_ERR_INVALID. */

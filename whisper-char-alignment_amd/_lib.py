@@ -95,12 +95,16 @@ SIGNATURES = {
     "wca_flac_decode": (_i, [_vp, _i64, _vp, _i64, C.POINTER(_i64)]),
     "wca_dtw": (_i, [_vp, _pf, _i, _i, _pi32, _pi32, _pi32]),
     "wca_dtw_batch_dev": (_i, [_vp, _vp, _i, _i, _i, _pi32]),
+    "wca_dtw_open": (_i, [_vp, _pf, _i, _i, _pi32, _pi32, _pi32, _pi32, _pf]),
+    "wca_dtw_batch_dev_open": (_i, [_vp, _vp, _i, _i, _i, _pi32, _pi32, _pi32, _pi32, _pi32, _pf]),
     "wca_probe_heads": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _pf, _pi32]),
     "wca_align_batch": (_i, [_vp, _vp, _i64, _pi32, _vp, _i, _pi32, _pi32, _i, C.POINTER(AlignOpts), _pi32, _pi32]),
     "wca_align_batch_enqueue": (_i, [_vp, _vp, _i64, _pi32, _vp, _i, _pi32, _pi32, _i, C.POINTER(AlignOpts)]),
     "wca_align_batch_fetch": (_i, [_vp, _i, _i, _i, _pi32, _pi32]),
     "wca_align_batch_enqueue_ex": (_i, [_vp, _vp, _i64, _pi32, _vp, _i, _pi32, _pi32, _i, C.POINTER(AlignOpts), C.c_int32]),
     "wca_align_batch_fetch_ex": (_i, [_vp, _i, _i, _i, _pi32, _pi32, _pf]),
+    "wca_align_batch_enqueue_open": (_i, [_vp, _vp, _i64, _pi32, _vp, _i, _pi32, _pi32, _i, C.POINTER(AlignOpts), C.c_int32, _pi32]),
+    "wca_align_batch_fetch_open": (_i, [_vp, _i, _i, _i, _pi32, _pi32, _pf, _pi32, _pf]),
     "wca_token_logprobs": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "wca_encode_batch": (_i, [_vp, _vp, _vp, _i64, _pi32, _i]),
     "wca_greedy_decode": (_i, [_vp, _vp, _vp, _i64, _pi32, _i, _pi32, _i, _vp, _vp, C.POINTER(DecodeOpts), _pi32, _pi32, _pf, _pf]),

@@ -1,0 +1,345 @@
+#!/usr/bin/env python3
+"""Long-form forced alignment: word times of a recording of ANY length against its GIVEN transcript (a book chapter with its text, a
+talk with its subtitles, a corpus recording with its reference transcript) on the MI355X engine.
+
+Neither the reference repository (its entry points stop at one 30 s window and 448 framed tokens, infer_ali.py:78-81) nor upstream
+openai-whisper (which only times its own ASR hypothesis) has this path: PARITY IS UNPINNED. The window loop below is this project's own
+design; its mechanics and the open-end DTW kernel under it are pinned by tests, its quality on real speech is UNVALIDATED until a real
+checkpoint is at hand.
+
+What runs where: audio handling is transcribe's (`_as_pcm`, the GPU resampler, the log-mel of the whole recording once, the window cut
+`mel_window`); every window is ONE fused alignment (encode_batch of the window's mel, then align_batch(pcm=None, open_end=[...])): the
+teacher-forced forward with capture, median filter, softmax, head scores, aggregation and the DTW are the 30 s path's. The one new piece
+below the host is the OPEN-END DTW (csrc/dtw.hip, include/wca.h wca_dtw_open): an interior window holds only a PREFIX of the text it is
+offered, so its path must end in the last frame at whichever text row fits best -- the row of the smallest cost per path cell. The loop
+itself (`AlignState`) is host Python over a callable, like transcribe.SeekState: it runs without a GPU against a scripted aligner, and
+several recordings can be driven in lock-step (`force_align_long_batch`).
+
+The loop's rules
+  * units: the whole transcript is normalised and tokenised ONCE, the way `infer_ali.py --teacher text` does it: remove_punctuation, then
+    retokenize.encode in `aligned_unit_type`. Word starts come from the existing splitters (char_word_starts, else
+    split_tokens_on_spaces). A single word longer than the token limit is a ValueError before any GPU work.
+  * request() -> (seek, size, w0, w1, closed): size = min(3000, content_frames - seek) mel frames, max_frames = size // 2 encoder frames;
+    [w0, w1) is the longest run of whole words from the text cursor whose framed row [*sot_sequence, no_timestamps, *units, eot] has at
+    most 448 tokens (at least one word). `closed` iff the window reaches the end of the recording AND offers all remaining words: such a
+    window runs the closed DTW and words_from_jump_frames unchanged, and every offered word is committed.
+  * receive(jump_frames, end_row) of an open window: DTW row r is unit r of the offered run, row n_units the final eot. A word is
+    COMPLETE if the row of its last unit is <= end_row; its start is the jump frame of its first unit; its end is the jump frame of the
+    next word's first unit if that row is <= end_row, else max_frames. Every complete word EXCEPT THE LAST is committed: the window edge
+    may have cut that one, so it is offered again. With fewer than two complete words nothing is committed. The one exception: a window
+    that offers ALL remaining words and whose path reaches the eot row saw the transcript end before the window edge; its last word is
+    committed too, its end being the eot row's jump frame, and the text is used up (without this a transcript that ends before the audio
+    would drag its last word through every window of the remaining audio into the final, closed one).
+  * advance: if words were committed, seek += 2 * (jump frame of the held-back word's first unit): the next window starts where that
+    word starts, and the text cursor moves to it. If nothing was committed, or that advance is 0 (then nothing is committed either),
+    seek += size and the cursor stays: the window was silence or could not be aligned (`windows_without_words`).
+  * seek strictly increases; the loop ends at content_frames or when the text is used up. A remainder of less than one encoder frame
+    (a single mel frame) holds nothing and ends the recording.
+  * result: {"words": [{"word", "start", "end"}], "windows": [{seek, size, w0, w1, closed, end_row, score, committed}],
+    "unaligned_words": k, "windows_without_words": n}. Times are absolute seconds, seek * 0.01 + frame * 0.02. Words left over when the
+    audio ends carry start = end = None and are counted in "unaligned_words". `score` (cost per path cell at the end row) is a
+    diagnostic: no decision reads it.
+
+Limits: 448 framed tokens and 1500 encoder frames per window (the engine's), so at most 446 - len(sot_sequence) units per window; no
+per-word confidence, no silence or music detection, no fallback to ASR for a window that fails, one GPU.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+if __package__ in (None, ""):
+    import importlib
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    _pkg = importlib.import_module("whisper-char-alignment_amd")
+    __package__ = _pkg.__name__
+
+from .audio import HOP_LENGTH, N_FRAMES, SAMPLE_RATE, TOKENS_PER_SECOND  # noqa: E402
+
+INPUT_STRIDE = 2                          # mel frames per encoder frame
+FRAME_SECONDS = HOP_LENGTH / SAMPLE_RATE  # 0.01 s per mel frame
+MAX_LENGTH = 448                          # framed tokens per window (infer_ali.py:26)
+
+
+class AlignState:
+    """One recording's side of the window loop as a state machine (module docstring: the loop's rules):
+        while not st.done:
+            seek, size, w0, w1, closed = st.request()          # the next window and the run of words it is offered
+            st.receive(jump_frames, end_row, score)            # the window's DTW result: commits words, advances seek and the cursor
+    n_frames: frames of the recording's log-mel (its own plus the 3000 of padding); word_starts: index of every word's first unit in the
+    transcript's unit sequence, then the number of units (n_words + 1 entries); words: the n_words strings; sot_len = len(sot_sequence)."""
+
+    def __init__(self, n_frames, word_starts, words, sot_len, max_length=MAX_LENGTH):
+        self.content_frames = int(n_frames) - N_FRAMES
+        self.word_starts = [int(v) for v in word_starts]
+        self.word_text = list(words)
+        self.n_words = len(self.word_starts) - 1
+        if self.n_words < 0 or len(self.word_text) != self.n_words:
+            raise ValueError("word_starts needs one entry per word plus the unit count; got %d entries for %d words"
+                             % (len(self.word_starts), len(self.word_text)))
+        self.unit_limit = int(max_length) - int(sot_len) - 2   # len(sot_sequence) + 1 + n_units + 1 <= max_length
+        for k in range(self.n_words):
+            n = self.word_starts[k + 1] - self.word_starts[k]
+            if n > self.unit_limit:
+                raise ValueError("word %d (%r) has %d units: more than the %d a window's token row can hold" % (k, self.word_text[k], n, self.unit_limit))
+        self.seek, self.cursor = 0, 0
+        self.words, self.windows = [], []
+        self.without_words = 0
+        self._skip_sliver()
+
+    def _skip_sliver(self):
+        if 0 < self.content_frames - self.seek < INPUT_STRIDE:   # less than one encoder frame is left
+            self.seek = self.content_frames
+
+    @property
+    def done(self):
+        return self.seek >= self.content_frames or self.cursor >= self.n_words
+
+    def request(self):
+        size = min(N_FRAMES, self.content_frames - self.seek)
+        w0 = w1 = self.cursor
+        first = self.word_starts[w0]
+        while w1 < self.n_words and self.word_starts[w1 + 1] - first <= self.unit_limit:
+            w1 += 1
+        closed = self.seek + size >= self.content_frames and w1 == self.n_words
+        return self.seek, size, w0, w1, closed
+
+    def unit_span(self, w0, w1):
+        """The offered run [w0, w1) as a slice of the transcript's units."""
+        return self.word_starts[w0], self.word_starts[w1]
+
+    def receive(self, jump_frames, end_row, score=None, times=None):
+        """jump_frames[r]: the encoder frame at which the window's DTW path enters row r (row r = unit r of the offered run, row n_units
+        = eot); end_row: the path's last row. times (closed windows only): (starts, ends) in window seconds as words_from_jump_frames
+        gives them for the offered run, else they are formed here the same way."""
+        seek, size, w0, w1, closed = self.request()
+        max_frames = size // INPUT_STRIDE
+        base = self.word_starts[w0]
+        rows = [self.word_starts[k] - base for k in range(w0, w1 + 1)]   # first row of every offered word, then the eot row
+        jump = np.asarray(jump_frames[:rows[-1] + 1], dtype=np.int64)
+        end_row = int(end_row)
+        window = {"seek": seek, "size": size, "w0": w0, "w1": w1, "closed": closed, "end_row": end_row,
+                  "score": None if score is None else float(score), "committed": 0}
+        self.windows.append(window)
+        offset = seek * FRAME_SECONDS
+        if closed:
+            if times is None or len(times[0]) != w1 - w0:
+                t = jump / TOKENS_PER_SECOND
+                times = (t[rows[:-1]], t[rows[1:]])
+            for k in range(w0, w1):
+                self.words.append({"word": self.word_text[k], "start": offset + float(times[0][k - w0]), "end": offset + float(times[1][k - w0])})
+            window["committed"] = w1 - w0
+            self.cursor, self.seek = w1, self.content_frames
+            return window
+        complete = 0
+        while complete < w1 - w0 and rows[complete + 1] - 1 <= end_row:
+            complete += 1
+        if w1 == self.n_words and end_row >= rows[-1]:   # the path reached the eot of the transcript's last words: the text ends in this window
+            for k in range(w0, w1):
+                self.words.append({"word": self.word_text[k], "start": offset + int(jump[rows[k - w0]]) / TOKENS_PER_SECOND,
+                                   "end": offset + int(jump[rows[k - w0 + 1]]) / TOKENS_PER_SECOND})
+            window["committed"] = w1 - w0
+            self.cursor = w1
+            self.seek += INPUT_STRIDE * int(jump[rows[-1]])
+            return window
+        advance = INPUT_STRIDE * int(jump[rows[complete - 1]]) if complete >= 2 else 0
+        if advance <= 0:   # silence, or a window that could not be aligned: nothing is committed and the cursor stays
+            self.without_words += 1
+            self.seek += size
+            self._skip_sliver()
+            return window
+        for k in range(complete - 1):   # every complete word but the last, which the window edge may have cut
+            end = int(jump[rows[k + 1]]) if rows[k + 1] <= end_row else max_frames
+            self.words.append({"word": self.word_text[w0 + k], "start": offset + int(jump[rows[k]]) / TOKENS_PER_SECOND,
+                               "end": offset + end / TOKENS_PER_SECOND})
+        window["committed"] = complete - 1
+        self.cursor = w0 + complete - 1
+        self.seek += advance
+        self._skip_sliver()
+        return window
+
+    def result(self):
+        words = list(self.words)
+        left = self.n_words - self.cursor
+        words.extend({"word": self.word_text[k], "start": None, "end": None} for k in range(self.cursor, self.n_words))
+        return {"words": words, "windows": self.windows, "unaligned_words": left, "windows_without_words": self.without_words}
+
+
+def align_loop(states, align_rows):
+    """The window loop over one or several recordings in lock-step: every round asks each unfinished state for its next window and hands
+    them to align_rows(live, requests) -> one (jump_frames, end_row[, score[, times]]) per row; `live` holds the rows' indices into
+    `states`. The batch shrinks as recordings end. Returns the states' results, in order."""
+    states = list(states)
+    while True:
+        live = [i for i, st in enumerate(states) if not st.done]
+        if not live:
+            break
+        outs = align_rows(live, [states[i].request() for i in live])
+        for i, out in zip(live, outs):
+            states[i].receive(*out)
+    return [st.result() for st in states]
+
+
+def transcript_units(text, tokenizer, aligned_unit_type="char"):
+    """The whole transcript as (units, word_starts, words): remove_punctuation + retokenize.encode as `infer_ali.py --teacher text`, word
+    starts from char_word_starts, else split_tokens_on_spaces; word_starts ends with len(units)."""
+    from .retokenize import char_word_starts, encode, remove_punctuation, split_tokens_on_spaces
+    units = [int(t) for t in encode(remove_punctuation(text), tokenizer, aligned_unit_type)]
+    if not units:
+        return [], [0], []
+    toks = units + [tokenizer.eot]
+    starts = char_word_starts(toks, tokenizer) if aligned_unit_type == "char" else None
+    if starts is None:
+        _words, word_tokens = split_tokens_on_spaces(toks, tokenizer, aligned_unit_type)
+        starts = np.pad(np.cumsum([len(t) for t in word_tokens[:-1]]), (1, 0))
+    starts = [int(v) for v in starts]   # the last "word" is the eot: its start is len(units)
+    words = [tokenizer.decode_with_timestamps(units[a:b]) for a, b in zip(starts[:-1], starts[1:])]
+    return units, starts, words
+
+
+def force_align_long_batch(model, audios, texts, *, language, vocab_path, aligned_unit_type="char", aggr="topk", topk=10, medfilt_width=3,
+                           sample_rate=SAMPLE_RATE, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0):
+    """force_align_long() of several recordings in lock-step: a list with force_align_long()'s result for every (audio, text) pair, in
+    order. Every round cuts the next window of every unfinished recording and aligns them in ONE encode_batch + align_batch, whose rows
+    may mix open and closed windows; the batch shrinks as recordings end, and more recordings than model.max_batch go in groups of
+    max_batch. sample_rate is one int for every array / tensor input or one per recording (a path carries its own rate)."""
+    import torch
+    from .timing import words_from_jump_frames
+    from .tokenizer import get_tokenizer
+    from .transcribe import _as_pcm
+    audios, texts = list(audios), list(texts)
+    if len(audios) != len(texts):
+        raise ValueError("%d recordings for %d transcripts" % (len(audios), len(texts)))
+    if vocab_path is None:
+        raise ValueError("the transcript is tokenised with the model's vocabulary: pass vocab_path=<local *.tiktoken file>")
+    rates = [int(r) for r in sample_rate] if isinstance(sample_rate, (list, tuple)) else [int(sample_rate)] * len(audios)
+    if len(rates) != len(audios):
+        raise ValueError("sample_rate lists %d rates for %d recordings" % (len(rates), len(audios)))
+    max_batch = int(getattr(model, "max_batch", 1))
+    tokenizer = get_tokenizer(model.is_multilingual, language=language, vocab_path=vocab_path)
+    sot = list(tokenizer.sot_sequence)
+    if aggr == "topk":
+        topk = min(int(topk), model.dims.n_text_layer * model.dims.n_text_head)
+    opts = model.make_opts(aggregation=aggr, topk=topk, w_colnorm=w_colnorm, w_rownorm=w_rownorm, w_coverage=w_coverage, sot_len=len(sot),
+                           medfilt_width=medfilt_width, qk_scale=1.0)
+    prepared = [transcript_units(t, tokenizer, aligned_unit_type) for t in texts]
+    for units, starts, words in prepared:   # an over-long word is refused before any GPU work
+        AlignState(N_FRAMES, starts, words, len(sot))
+    results = []
+    for g0 in range(0, len(audios), max_batch):
+        group = list(range(g0, min(len(audios), g0 + max_batch)))
+        mels = [model.log_mel_long(_as_pcm(audios[i], model, rates[i])) for i in group]
+        units = [prepared[i][0] for i in group]
+        states = [AlignState(mel.shape[1], prepared[i][1], prepared[i][2], len(sot)) for i, mel in zip(group, mels)]
+
+        def align_rows(live, requests):
+            windows = [model.mel_window(mels[i], seek, size) for i, (seek, size, _w0, _w1, _c) in zip(live, requests)]
+            windows = torch.stack(windows) if len(live) > 1 else windows[0][None]
+            runs = [units[i][slice(*states[i].unit_span(w0, w1))] for i, (_s, _z, w0, w1, _c) in zip(live, requests)]
+            rows = [[*sot, tokenizer.no_timestamps, *run, tokenizer.eot] for run in runs]
+            toks = torch.full((len(rows), max(len(r) for r in rows)), tokenizer.eot, dtype=torch.int64)
+            for b, r in enumerate(rows):
+                toks[b, :len(r)] = torch.tensor(r, dtype=torch.int64)
+            model.encode_batch(mel=windows)
+            jump, _sel, end_rows, scores = model.align_batch(None, None, toks.to(model.device), [len(r) for r in rows],
+                                                             [size // INPUT_STRIDE for _s, size, _w0, _w1, _c in requests], opts,
+                                                             open_end=[not closed for _s, _z, _w0, _w1, closed in requests])
+            outs = []
+            for b, (run, req) in enumerate(zip(runs, requests)):
+                times = None
+                if req[4]:   # a closed window: today's DTW and words_from_jump_frames, unchanged
+                    _w, starts, ends = words_from_jump_frames(jump[b], run, tokenizer, aligned_unit_type, want_words=False)
+                    times = (starts, ends)
+                outs.append((jump[b], end_rows[b], scores[b], times))
+            return outs
+
+        results.extend(align_loop(states, align_rows))
+    return results
+
+
+def force_align_long(model, audio, text, *, language, vocab_path, aligned_unit_type="char", aggr="topk", topk=10, medfilt_width=3,
+                     sample_rate=SAMPLE_RATE, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0):
+    """Word times of one recording of any length against its given transcript `text` (module docstring: rules, limits, what is pinned).
+    audio: a path, or mono samples [n] (or [channels, n]) at `sample_rate` Hz, as transcribe() takes them. Returns {"words": [{"word",
+    "start", "end"}], "windows": [...], "unaligned_words", "windows_without_words"}; it is force_align_long_batch of one recording."""
+    return force_align_long_batch(model, [audio], [text], language=language, vocab_path=vocab_path, aligned_unit_type=aligned_unit_type,
+                                  aggr=aggr, topk=topk, medfilt_width=medfilt_width, sample_rate=sample_rate, w_colnorm=w_colnorm,
+                                  w_rownorm=w_rownorm, w_coverage=w_coverage)[0]
+
+
+# ------------------------------------------------------------------------------------------------ command line
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="Long-form forced alignment of a recording against its transcript (one JSON of word times per recording)")
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("--audio", type=str, help="one recording (WAV / SPHERE / FLAC at any rate, or a raw .npy array); needs --text")
+    src.add_argument("--scp", type=str, help="list of recordings: `<audio path><TAB><transcript text file>` per line")
+    p.add_argument("--text", type=str, default=None, help="the transcript of --audio: a UTF-8 text file")
+    p.add_argument("--output_dir", type=str, required=True)
+    p.add_argument("--model", type=str, default="medium")
+    p.add_argument("--weights", type=str, default=None, help="local openai-whisper checkpoint (.pt)")
+    p.add_argument("--random_init", action="store_true", help="seeded random weights (dry run without a checkpoint)")
+    p.add_argument("--vocab", type=str, required=True, help="local tiktoken vocabulary file")
+    p.add_argument("--language", type=str, default="en")
+    p.add_argument("--medfilt_width", type=int, default=3)
+    p.add_argument("--aggr", type=str, default="topk", choices=["mean", "topk"])
+    p.add_argument("--topk", type=int, default=10)
+    p.add_argument("--aligned_unit_type", type=str, default="char", choices=["subword", "char"])
+    p.add_argument("--w_colnorm", type=float, default=1.0)
+    p.add_argument("--w_rownorm", type=float, default=1.0)
+    p.add_argument("--w_coverage", type=float, default=0.0)
+    p.add_argument("--forward_precision", type=str, default="reference", choices=["reference", "split", "f16"])
+    p.add_argument("--sample_rate", type=int, default=SAMPLE_RATE, help="rate of raw .npy arrays; audio files carry their own")
+    p.add_argument("--batch", type=int, default=1, help="recordings aligned in lock-step (the engine's max_batch)")
+    return p.parse_args(argv)
+
+
+def _recordings(args):
+    if args.audio:
+        if not args.text:
+            raise SystemExit("--audio needs --text <transcript file>")
+        return [(args.audio, args.text)]
+    out = []
+    with open(args.scp) as f:
+        for line in f:
+            parts = line.rstrip("\n").split("\t")
+            if len(parts) == 2 and parts[0].strip():
+                out.append((parts[0].strip(), parts[1].strip()))
+            elif line.strip():
+                raise SystemExit("--scp lines are `<audio path><TAB><transcript text file>`; got %r" % line)
+    return out
+
+
+def main(args, model=None):
+    """Writes <output_dir>/<audio basename>.json per recording (force_align_long()'s result plus "audio" and "text"); returns the paths."""
+    from .transcribe import load_model
+    if args.batch < 1:
+        raise SystemExit("--batch must be at least 1")
+    recordings = _recordings(args)
+    if model is None:
+        model = load_model(args)
+    os.makedirs(args.output_dir, exist_ok=True)
+    kw = dict(language=args.language, vocab_path=args.vocab, aligned_unit_type=args.aligned_unit_type, aggr=args.aggr, topk=args.topk,
+              medfilt_width=args.medfilt_width, sample_rate=args.sample_rate, w_colnorm=args.w_colnorm, w_rownorm=args.w_rownorm,
+              w_coverage=args.w_coverage)
+
+    def source(path):
+        return np.load(path) if path.endswith(".npy") else path
+
+    paths = []
+    for g0 in range(0, len(recordings), args.batch):
+        group = recordings[g0:g0 + args.batch]
+        texts = [open(t, encoding="utf-8").read() for _a, t in group]
+        for (audio, text_path), result in zip(group, force_align_long_batch(model, [source(a) for a, _t in group], texts, **kw)):
+            out = os.path.join(args.output_dir, os.path.splitext(os.path.basename(audio))[0] + ".json")
+            with open(out, "w") as f:
+                json.dump({"audio": audio, "text": text_path, **result}, f)
+            paths.append(out)
+            print("%s: %d words (%d unaligned), %d windows -> %s" % (audio, len(result["words"]), result["unaligned_words"],
+                                                                     len(result["windows"]), out))
+    return paths
+
+
+if __name__ == "__main__":
+    main(parse_args())

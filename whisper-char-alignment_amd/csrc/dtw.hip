@@ -10,6 +10,14 @@
 // s - l in step s): a wavefront-parallel anti-diagonal sweep whose only cross-lane traffic is the
 // previous lane's last row (two values per step).  The 2-bit move trace is packed 16 columns per word.
 // It is neither HBM- nor MFMA-bound: N+M-1 dependent steps, reported as microseconds per utterance.
+//
+// OPEN (the open-end form, for a window of a long recording that holds only a prefix of the text it is offered): the same recurrence and
+// tie rule, but the path may end in the last frame at ANY text row. Every cell also carries L, the number of cells on its chosen path
+// (itself included), through the same hand-off as the two cost values; after the sweep the wave picks the end row n* that minimises
+// C[i][M-1] / L[i][M-1] -- every visited cell adds a non-positive cost, so the unnormalised minimum would always be the last row. The
+// comparison is exact: row a beats row b iff (double)C_a * L_b < (double)C_b * L_a (C has 24 significant bits and L < 2^13, so both
+// products are exact in f64), equal scores go to the lower row. Lane 0 then backtraces from (n*, M-1). The closed instantiations carry
+// none of this: `if constexpr` keeps their registers and shuffles what they were.
 #include "kernels.h"
 #include "wca_common.h"
 
@@ -17,7 +25,16 @@ namespace wca {
 
 namespace {
 
-template <int R, int U>
+// (Ca, La, ia) beats (Cb, Lb, ib) as the end of an open-end path: a valid row (i >= 0) beats none, then the smaller C / L decided on
+// the cross-multiplied f64 products, then the lower row
+__device__ __forceinline__ bool end_row_beats(float Ca, int La, int ia, float Cb, int Lb, int ib) {
+  if (ia < 0) return false;
+  if (ib < 0) return true;
+  const double pa = (double)Ca * (double)Lb, pb = (double)Cb * (double)La;
+  return pa < pb || (pa == pb && ia < ib);
+}
+
+template <int R, int U, bool OPEN>
 __global__ __launch_bounds__(64) void dtw_kernel(DtwArgs a) {
   const int p = blockIdx.x;
   const int lane = threadIdx.x;
@@ -27,7 +44,13 @@ __global__ __launch_bounds__(64) void dtw_kernel(DtwArgs a) {
   int* pt = a.path + (long)p * 2 * cap;
   int* pj = pt + cap;
   if (N <= 0 || M <= 0 || N > 64 * R || N > a.N_max || M > a.M_max) {
-    if (lane == 0) a.path_len[p] = 0;
+    if (lane == 0) {
+      a.path_len[p] = 0;
+      if constexpr (OPEN) {
+        if (a.end_row) a.end_row[p] = -1;
+        if (a.score) a.score[p] = 0.f;
+      }
+    }
     return;
   }
   const float* __restrict__ x = a.matrix + (long)p * a.m_bs;
@@ -43,6 +66,13 @@ __global__ __launch_bounds__(64) void dtw_kernel(DtwArgs a) {
     tw[r] = 0u;
   }
   float last_cur = INFINITY, last_prev = INFINITY;
+  // OPEN: path lengths beside the costs (0 = no path yet; such a cell's cost is INFINITY and is never chosen over a finite one)
+  int plen[OPEN ? R : 1];
+  int last_cur_len = 0, last_prev_len = 0;
+  if constexpr (OPEN) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) plen[r] = 0;
+  }
   const int lane_max = (N - 1) / R;
   const int S = M + lane_max;  // steps 0 .. S-1
 
@@ -70,9 +100,16 @@ __global__ __launch_bounds__(64) void dtw_kernel(DtwArgs a) {
         up_in = INFINITY;
         diag_in = (j == 0) ? 0.f : INFINITY;
       }
+      int up_len = 0, diag_len = 0;
+      if constexpr (OPEN) {
+        up_len = __shfl_up(last_cur_len, 1);
+        diag_len = __shfl_up(last_prev_len, 1);
+        if (lane == 0) up_len = diag_len = 0;
+      }
       const bool active = (s < S) && (j >= 0) && (j < M) && (i0 < N);
       if (active) {
         float newv[R];
+        int newl[OPEN ? R : 1];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           const int i = i0 + r;
@@ -93,6 +130,11 @@ __global__ __launch_bounds__(64) void dtw_kernel(DtwArgs a) {
           }
           const float nv = (float)((double)(-xv[u][r]) + (double)c);
           newv[r] = (i < N) ? nv : INFINITY;
+          if constexpr (OPEN) {
+            const int l1 = (r == 0) ? up_len : newl[r > 0 ? r - 1 : 0];
+            const int l0 = (r == 0) ? diag_len : plen[r > 0 ? r - 1 : 0];
+            newl[r] = (t == 0u ? l0 : (t == 1u ? l1 : plen[r])) + 1;
+          }
           if (i < N) {
             tw[r] |= t << (2 * (j & 15));
             if ((j & 15) == 15 || j == M - 1) {
@@ -105,13 +147,56 @@ __global__ __launch_bounds__(64) void dtw_kernel(DtwArgs a) {
         last_cur = newv[R - 1];
 #pragma unroll
         for (int r = 0; r < R; ++r) prev[r] = newv[r];
+        if constexpr (OPEN) {
+          last_prev_len = plen[R - 1];
+          last_cur_len = newl[R - 1];
+#pragma unroll
+          for (int r = 0; r < R; ++r) plen[r] = newl[r];
+        }
       }
     }
   }
 
+  // OPEN: every lane now holds C[i][M-1] in prev[] and L[i][M-1] in plen[] for its rows i < N: wave arg-min of C / L, per lane over
+  // its R rows and then across the lanes (a strict total order, so the butterfly leaves the same winner in every lane)
+  int end_i = N - 1;
+  if constexpr (OPEN) {
+    const bool open = a.open_end ? a.open_end[p] != 0 : a.open_all != 0;
+    float bc = 0.f;
+    int bl = 0, bi = -1;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int i = i0 + r;
+      const bool counts = open ? i < N : i == N - 1;
+      if (counts && end_row_beats(prev[r], plen[r], i, bc, bl, bi)) {
+        bc = prev[r];
+        bl = plen[r];
+        bi = i;
+      }
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const float oc = __shfl_xor(bc, d);
+      const int ol = __shfl_xor(bl, d), oi = __shfl_xor(bi, d);
+      if (end_row_beats(oc, ol, oi, bc, bl, bi)) {
+        bc = oc;
+        bl = ol;
+        bi = oi;
+      }
+    }
+    end_i = bi;
+    if (lane == 0) {
+      if (a.end_row) a.end_row[p] = bi;
+      if (a.score) a.score[p] = (float)((double)bc / (double)bl);
+    }
+    // rows past the end row are on no path
+    if (a.jump_frame)
+      for (int i = end_i + 1 + lane; i < N; i += 64) a.jump_frame[(long)p * a.jump_ld + i] = -1;
+  }
+
   __threadfence();  // trace words written by all lanes -> visible to lane 0's loads below
   if (lane == 0) {
-    int i = N - 1, j = M - 1, k = cap;
+    int i = end_i, j = M - 1, k = cap;
     int* jf = a.jump_frame ? a.jump_frame + (long)p * a.jump_ld : nullptr;
     while ((i >= 0 || j >= 0) && k > 0) {
       --k;
@@ -147,15 +232,28 @@ hipError_t launch_dtw(const DtwArgs& a, hipStream_t s) {
   if (a.N_max <= 0 || a.M_max <= 0 || a.N_max > 512) return hipErrorInvalidValue;
   const int R = (a.N_max + 63) / 64;
   dim3 grid(a.P), block(64);
+  if (a.open_end || a.open_all) {
+    switch (R) {
+      case 1: hipLaunchKernelGGL((dtw_kernel<1, 8, true>), grid, block, 0, s, a); break;
+      case 2: hipLaunchKernelGGL((dtw_kernel<2, 8, true>), grid, block, 0, s, a); break;
+      case 3: hipLaunchKernelGGL((dtw_kernel<3, 4, true>), grid, block, 0, s, a); break;
+      case 4: hipLaunchKernelGGL((dtw_kernel<4, 4, true>), grid, block, 0, s, a); break;
+      case 5: hipLaunchKernelGGL((dtw_kernel<5, 2, true>), grid, block, 0, s, a); break;
+      case 6: hipLaunchKernelGGL((dtw_kernel<6, 2, true>), grid, block, 0, s, a); break;
+      case 7: hipLaunchKernelGGL((dtw_kernel<7, 2, true>), grid, block, 0, s, a); break;
+      default: hipLaunchKernelGGL((dtw_kernel<8, 2, true>), grid, block, 0, s, a); break;
+    }
+    return hipGetLastError();
+  }
   switch (R) {
-    case 1: hipLaunchKernelGGL((dtw_kernel<1, 8>), grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((dtw_kernel<2, 8>), grid, block, 0, s, a); break;
-    case 3: hipLaunchKernelGGL((dtw_kernel<3, 4>), grid, block, 0, s, a); break;
-    case 4: hipLaunchKernelGGL((dtw_kernel<4, 4>), grid, block, 0, s, a); break;
-    case 5: hipLaunchKernelGGL((dtw_kernel<5, 2>), grid, block, 0, s, a); break;
-    case 6: hipLaunchKernelGGL((dtw_kernel<6, 2>), grid, block, 0, s, a); break;
-    case 7: hipLaunchKernelGGL((dtw_kernel<7, 2>), grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL((dtw_kernel<8, 2>), grid, block, 0, s, a); break;
+    case 1: hipLaunchKernelGGL((dtw_kernel<1, 8, false>), grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((dtw_kernel<2, 8, false>), grid, block, 0, s, a); break;
+    case 3: hipLaunchKernelGGL((dtw_kernel<3, 4, false>), grid, block, 0, s, a); break;
+    case 4: hipLaunchKernelGGL((dtw_kernel<4, 4, false>), grid, block, 0, s, a); break;
+    case 5: hipLaunchKernelGGL((dtw_kernel<5, 2, false>), grid, block, 0, s, a); break;
+    case 6: hipLaunchKernelGGL((dtw_kernel<6, 2, false>), grid, block, 0, s, a); break;
+    case 7: hipLaunchKernelGGL((dtw_kernel<7, 2, false>), grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL((dtw_kernel<8, 2, false>), grid, block, 0, s, a); break;
   }
   return hipGetLastError();
 }

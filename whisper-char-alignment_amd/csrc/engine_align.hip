@@ -82,9 +82,10 @@ int run_head_stats(wca_engine* e, hipStream_t s, HeadStatsArgs* h, const float* 
 
 // One DTW launch on s over P problems (matrix + p * m_bs, rows ld apart): N_dev[p] x M_dev[p] each, within N_max x M_max, or (both null) all
 // N_max x M_max. Trace, path and path length go to e->trace / e->path / e->pathlen; jump_ld > 0 also asks for the jump frames in e->jump, rows
-// jump_ld apart.
+// jump_ld apart. open_dev ([P] device flags, 1 = open end) or open_all asks for the open-end kernel: the end rows [P] and then the scores [P]
+// land in e->dtw_out, and a closed problem of such a launch gets what the closed kernel gives it (end row N - 1).
 int run_dtw(wca_engine* e, hipStream_t s, const float* matrix, long m_bs, int ld, int P, int N_max, int M_max, const int* N_dev, const int* M_dev,
-            int jump_ld) {
+            int jump_ld, const int* open_dev = nullptr, bool open_all = false) {
   const int wpr = (M_max + 15) / 16, cap = N_max + M_max + 2;
   HIPCHK(e->trace.ensure(sizeof(uint32_t) * (size_t)P * N_max * wpr));
   HIPCHK(e->path.ensure(sizeof(int) * (size_t)P * 2 * cap));
@@ -106,6 +107,13 @@ int run_dtw(wca_engine* e, hipStream_t s, const float* matrix, long m_bs, int ld
   dg.jump_frame = jump_ld ? (int*)e->jump.p : nullptr;
   dg.jump_ld = jump_ld;
   dg.P = P;
+  if (open_dev || open_all) {
+    HIPCHK(e->dtw_out.ensure(2 * sizeof(int) * (size_t)P));
+    dg.open_end = open_dev;
+    dg.open_all = open_all ? 1 : 0;
+    dg.end_row = (int*)e->dtw_out.p;
+    dg.score = (float*)e->dtw_out.p + P;
+  }
   HIPCHK(launch_dtw(dg, s));
   return WCA_OK;
 }
@@ -134,8 +142,10 @@ int read_path(wca_engine* e, int N, int M, int32_t* text_idx_host, int32_t* time
 }
 
 // top-k / aggregate / DTW on s behind the head statistics h of run_head_stats: on the dense maps h read (input_is_weights), or re-derived
-// from the captured logits and row statistics h kept. The jump frames land in e->jump [B][n_tok_max].
-int run_select_aggregate_dtw(wca_engine* e, hipStream_t s, const HeadStatsArgs& h, const int* dtwN_dev, const wca_align_opts* o, int L_layers) {
+// from the captured logits and row statistics h kept. The jump frames land in e->jump [B][n_tok_max]. open_dev: run_dtw's per-utterance
+// open-end flags (end rows and scores in e->dtw_out; -1 / NaN where no DTW ran).
+int run_select_aggregate_dtw(wca_engine* e, hipStream_t s, const HeadStatsArgs& h, const int* dtwN_dev, const wca_align_opts* o, int L_layers,
+                             const int* open_dev = nullptr) {
   const int B = h.B, LH = h.LH, n_max = h.n_tok_max, Fmax = h.n_frames_max;
   const int k = o->aggregation == WCA_AGGR_TOPK ? o->topk : 0;
   if (o->aggregation == WCA_AGGR_TOPK) {
@@ -183,23 +193,28 @@ int run_select_aggregate_dtw(wca_engine* e, hipStream_t s, const HeadStatsArgs& 
     // caller that compares or stores whole rows must not see what an earlier allocation left there)
     HIPCHK(e->jump.ensure(sizeof(int) * (size_t)B * n_max));
     HIPCHK(hipMemsetAsync(e->jump.p, 0, sizeof(int) * (size_t)B * n_max, s));
-    WCA_TRY(run_dtw(e, s, (const float*)e->matrix.p, (long)n_max * Fmax, Fmax, B, Nmax, Fmax, dtwN_dev, h.n_frames, n_max));
+    WCA_TRY(run_dtw(e, s, (const float*)e->matrix.p, (long)n_max * Fmax, Fmax, B, Nmax, Fmax, dtwN_dev, h.n_frames, n_max, open_dev));
+  } else if (open_dev) {
+    HIPCHK(e->dtw_out.ensure(2 * sizeof(int) * (size_t)B));
+    HIPCHK(hipMemsetAsync(e->dtw_out.p, 0xFF, 2 * sizeof(int) * (size_t)B, s));
   }
   return WCA_OK;
 }
 
 // The pinned results slot of one enqueued batch, in ints: jump frames [batch][n_tok_max], top-k heads [batch][max(k, 1)], two flag words
-// (phase 2's, and the one phase 1 raised for the batch's cross-K/V slot), then (token log-probs only) the log-probs [batch][n_tok_max] as f32.
+// (phase 2's, and the one phase 1 raised for the batch's cross-K/V slot), then (token log-probs only) the log-probs [batch][n_tok_max] as f32,
+// then (open-end batches only) the end rows [batch] and the scores [batch] as f32.
 struct ResLayout {
-  size_t jump, sel, flags, lp, ints;
+  size_t jump, sel, flags, lp, open, ints;
 };
-ResLayout res_layout(int batch, int n_tok_max, int k, bool want_lp) {
+ResLayout res_layout(int batch, int n_tok_max, int k, bool want_lp, bool want_open = false) {
   ResLayout r;
   r.jump = 0;
   r.sel = r.jump + (size_t)batch * n_tok_max;
   r.flags = r.sel + (size_t)batch * (k > 0 ? k : 1);
   r.lp = r.flags + 2;
-  r.ints = r.lp + (want_lp ? (size_t)batch * n_tok_max : 0);
+  r.open = r.lp + (want_lp ? (size_t)batch * n_tok_max : 0);
+  r.ints = r.open + (want_open ? 2 * (size_t)batch : 0);
   return r;
 }
 
@@ -253,9 +268,10 @@ int run_token_logprobs(wca_engine* e, hipStream_t s, const int64_t* tokens_dev, 
 }  // namespace
 
 // the DTW of the step-by-step entry points: P problems of N x M on `stream`
-static int dtw_dev_common(wca_engine* e, const float* matrix_dev, int P, int N, int M, bool want_jump) {
+static int dtw_dev_common(wca_engine* e, const float* matrix_dev, int P, int N, int M, bool want_jump, const int* open_dev = nullptr,
+                          bool open_all = false) {
   if (N < 1 || N > 512 || M < 1 || M > 4096) return fail(WCA_ERR_INVALID, "DTW shape N=%d M=%d unsupported (N<=512, M<=4096)", N, M);
-  return run_dtw(e, e->stream, matrix_dev, (long)N * M, M, P, N, M, nullptr, nullptr, want_jump ? N : 0);
+  return run_dtw(e, e->stream, matrix_dev, (long)N * M, M, P, N, M, nullptr, nullptr, want_jump ? N : 0, open_dev, open_all);
 }
 
 // head statistics of one utterance's given maps attns_dev [L*H][n][F] (wca_filter_attention's scores); dtwN travels as metadata row 3
@@ -267,6 +283,12 @@ static int stats_on_weights(wca_engine* e, const float* attns_dev, int LH, int n
 }
 
 extern "C" {
+
+static int align_enqueue(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, const int64_t* tokens_dev,
+                         int n_tok_max, const int32_t* n_tok_host, const int32_t* max_frames_host, int batch, const wca_align_opts* o,
+                         int32_t vocab_end, const int32_t* open_end_host);
+static int align_fetch(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host, int32_t* sel_idx_host,
+                       float* token_logprob_host, int32_t* end_row_host, float* score_host);
 
 int wca_get_attentions(wca_engine* e, const float* mel_dev, const int64_t* tokens_dev, int batch, int n_tok, const int32_t* n_tok_host,
                        const int32_t* max_frames_host, int medfilt_width, float qk_scale, float* weights_out_dev,
@@ -370,6 +392,49 @@ int wca_dtw_batch_dev(wca_engine* e, const float* matrix_dev, int P, int N, int 
   WCA_TRY(dtw_dev_common(e, matrix_dev, P, N, M, true));
   HIPCHK(hipMemcpyAsync(jump_frame_host, e->jump.p, sizeof(int) * (size_t)P * N, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
+  return WCA_OK;
+}
+
+int wca_dtw_open(wca_engine* e, const float* matrix_host, int N, int M, int32_t* text_idx_host, int32_t* time_idx_host, int32_t* path_len_host,
+                 int32_t* end_row_host, float* score_host) {
+  if (!e || !matrix_host || !text_idx_host || !time_idx_host || !path_len_host || !end_row_host) return fail(WCA_ERR_INVALID, "null argument");
+  if (N < 1 || M < 1) return fail(WCA_ERR_INVALID, "empty DTW matrix");
+  if (N > 512 || M > 4096) return fail(WCA_ERR_INVALID, "DTW shape N=%d M=%d unsupported (N<=512, M<=4096)", N, M);
+  WCA_TRY(enter(e));
+  HIPCHK(e->tmp0.ensure(sizeof(float) * (size_t)N * M));
+  HIPCHK(hipMemcpyAsync(e->tmp0.p, matrix_host, sizeof(float) * (size_t)N * M, hipMemcpyHostToDevice, e->stream));
+  WCA_TRY(dtw_dev_common(e, (const float*)e->tmp0.p, 1, N, M, false, nullptr, true));
+  HIPCHK(hipMemcpyAsync(end_row_host, e->dtw_out.p, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (score_host) HIPCHK(hipMemcpyAsync(score_host, (const float*)e->dtw_out.p + 1, sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  return read_path(e, N, M, text_idx_host, time_idx_host, path_len_host);
+}
+
+int wca_dtw_batch_dev_open(wca_engine* e, const float* matrix_dev, int P, int N, int M, const int32_t* n_rows_host, const int32_t* n_cols_host,
+                           const int32_t* open_end_host, int32_t* jump_frame_host, int32_t* end_row_host, float* score_host) {
+  if (!e || !matrix_dev || !open_end_host || !jump_frame_host || !end_row_host) return fail(WCA_ERR_INVALID, "null argument");
+  if (P < 1) return fail(WCA_ERR_INVALID, "P < 1");
+  if (N < 1 || N > 512 || M < 1 || M > 4096) return fail(WCA_ERR_INVALID, "DTW shape N=%d M=%d unsupported (N<=512, M<=4096)", N, M);
+  // the per-problem tables travel as one block: open flags, then (ragged launches) the row and column counts
+  std::vector<int32_t> meta(3 * (size_t)P);
+  for (int p = 0; p < P; ++p) {
+    const int n = n_rows_host ? n_rows_host[p] : N, m = n_cols_host ? n_cols_host[p] : M;
+    if (n < 1 || n > N || m < 1 || m > M) return fail(WCA_ERR_INVALID, "problem %d is %d x %d, outside [1,%d] x [1,%d]", p, n, m, N, M);
+    meta[p] = open_end_host[p] ? 1 : 0;
+    meta[(size_t)P + p] = n;
+    meta[2 * (size_t)P + p] = m;
+  }
+  WCA_TRY(enter(e));
+  HIPCHK(e->dtw_meta.ensure(sizeof(int) * 3 * (size_t)P));
+  const int* md = (const int*)e->dtw_meta.p;
+  HIPCHK(hipMemcpyAsync(e->dtw_meta.p, meta.data(), sizeof(int) * 3 * (size_t)P, hipMemcpyHostToDevice, e->stream));
+  // rows of a problem that the DTW does not write (beyond its own row count) are defined as 0, as on the fused path
+  HIPCHK(e->jump.ensure(sizeof(int) * (size_t)P * N));
+  HIPCHK(hipMemsetAsync(e->jump.p, 0, sizeof(int) * (size_t)P * N, e->stream));
+  WCA_TRY(run_dtw(e, e->stream, matrix_dev, (long)N * M, M, P, N, M, md + P, md + 2 * (size_t)P, N, md));
+  HIPCHK(hipMemcpyAsync(jump_frame_host, e->jump.p, sizeof(int) * (size_t)P * N, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(end_row_host, e->dtw_out.p, sizeof(int) * (size_t)P, hipMemcpyDeviceToHost, e->stream));
+  if (score_host) HIPCHK(hipMemcpyAsync(score_host, (const float*)e->dtw_out.p + P, sizeof(float) * (size_t)P, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));   // (meta is a stack-lifetime host buffer)
   return WCA_OK;
 }
 
@@ -499,7 +564,23 @@ int wca_align_batch_enqueue(wca_engine* e, const float* pcm_dev, int64_t pcm_str
 int wca_align_batch_enqueue_ex(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
                                const int64_t* tokens_dev, int n_tok_max, const int32_t* n_tok_host, const int32_t* max_frames_host,
                                int batch, const wca_align_opts* o, int32_t vocab_end) {
+  return align_enqueue(e, pcm_dev, pcm_stride, n_samples_host, tokens_dev, n_tok_max, n_tok_host, max_frames_host, batch, o, vocab_end, nullptr);
+}
+
+int wca_align_batch_enqueue_open(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
+                                 const int64_t* tokens_dev, int n_tok_max, const int32_t* n_tok_host, const int32_t* max_frames_host,
+                                 int batch, const wca_align_opts* o, int32_t vocab_end, const int32_t* open_end_host) {
+  if (!e || !open_end_host) return fail(WCA_ERR_INVALID, "null argument");
+  return align_enqueue(e, pcm_dev, pcm_stride, n_samples_host, tokens_dev, n_tok_max, n_tok_host, max_frames_host, batch, o, vocab_end,
+                       open_end_host);
+}
+
+// the body of every wca_align_batch_enqueue*: open_end_host [batch] (nullable) makes the DTW of the flagged rows open-ended
+static int align_enqueue(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, const int64_t* tokens_dev,
+                         int n_tok_max, const int32_t* n_tok_host, const int32_t* max_frames_host, int batch, const wca_align_opts* o,
+                         int32_t vocab_end, const int32_t* open_end_host) {
   if (!e || !tokens_dev || !n_tok_host || !max_frames_host || !o) return fail(WCA_ERR_INVALID, "null argument");
+  const bool want_open = open_end_host != nullptr;
   if (vocab_end < 0 || vocab_end > e->dims.n_vocab) return fail(WCA_ERR_INVALID, "vocab_end %d outside (0, %d] (0 = no token log-probs)", vocab_end, e->dims.n_vocab);
   const bool want_lp = vocab_end > 0;
   const bool reuse_enc = (pcm_dev == nullptr);  // consume the oldest encoded state (wca_encode_batch / wca_greedy_decode)
@@ -548,6 +629,12 @@ int wca_align_batch_enqueue_ex(wca_engine* e, const float* pcm_dev, int64_t pcm_
     }
     WCA_TRY(stage_meta(e, batch, off.data(), nullptr, nullptr, nullptr, lp_rows, reuse_enc ? s2 : nullptr));
   }
+  int* open_rows[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (want_open) {
+    std::vector<int32_t> flags(batch);
+    for (int b = 0; b < batch; ++b) flags[b] = open_end_host[b] ? 1 : 0;
+    WCA_TRY(stage_meta(e, batch, flags.data(), nullptr, nullptr, nullptr, open_rows, reuse_enc ? s2 : nullptr));
+  }
   // ---- phase 1 on `stream`: log-mel, encoder, cross-K/V of all decoder layers into a free K/V slot (a slot is busy
   // from its encode until the alignment that read it has been fetched; at most 2 alignments are in flight), or the
   // slot of the encoded state this call consumes.
@@ -582,7 +669,7 @@ int wca_align_batch_enqueue_ex(wca_engine* e, const float* pcm_dev, int64_t pcm_
   WCA_TRY(run_head_stats(e, s2, &h, (const float*)e->cap.p, Fpad, false, nullptr, true, rows[1], rows[2], n_tok_max, Fmax, LH, batch, o->medfilt_width,
                          o->qk_scale, o->w_colnorm, o->w_rownorm, o->w_coverage));
   record(e, 5, s2);
-  WCA_TRY(run_select_aggregate_dtw(e, s2, h, rows[3], o, D.n_text_layer));
+  WCA_TRY(run_select_aggregate_dtw(e, s2, h, rows[3], o, D.n_text_layer, open_rows[0]));
   if (want_lp) {
     HIPCHK(e->lp_out.ensure(sizeof(float) * (size_t)batch * n_tok_max));
     WCA_TRY(run_token_logprobs(e, s2, tokens_dev, batch, n_tok_max, o->sot_len, vocab_end, rows[1], lp_rows[0], lp_R, lp_nmax, (float*)e->lp_out.p));
@@ -593,7 +680,7 @@ int wca_align_batch_enqueue_ex(wca_engine* e, const float* pcm_dev, int64_t pcm_
   // behind that encoder)
   const int k = o->aggregation == WCA_AGGR_TOPK ? o->topk : 0;
   const int rs = (int)(e->enq_count & 1);
-  const ResLayout at = res_layout(batch, n_tok_max, k, want_lp);
+  const ResLayout at = res_layout(batch, n_tok_max, k, want_lp, want_open);
   WCA_TRY(ensure_res_host(e, rs, at.ints));
   int* res = e->res_host[rs];
   if (want_lp) HIPCHK(hipMemcpyAsync(res + at.lp, e->lp_out.p, sizeof(float) * (size_t)batch * n_tok_max, hipMemcpyDeviceToHost, s2));
@@ -601,12 +688,14 @@ int wca_align_batch_enqueue_ex(wca_engine* e, const float* pcm_dev, int64_t pcm_
   HIPCHK(hipMemcpyAsync(res + at.flags + 1, e->err_dev + 1 + bs, sizeof(int), hipMemcpyDeviceToHost, s2));
   if (n_tok_max - o->sot_len - 1 >= 1) HIPCHK(hipMemcpyAsync(res + at.jump, e->jump.p, sizeof(int) * (size_t)batch * n_tok_max, hipMemcpyDeviceToHost, s2));
   if (k > 0) HIPCHK(hipMemcpyAsync(res + at.sel, e->sel.p, sizeof(int) * (size_t)batch * k, hipMemcpyDeviceToHost, s2));
+  if (want_open) HIPCHK(hipMemcpyAsync(res + at.open, e->dtw_out.p, 2 * sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, s2));
   record(e, 8, s2);
   HIPCHK(hipEventRecord(e->res_ev[rs], s2));
   e->res_batch[rs] = batch;
   e->res_ntok[rs] = n_tok_max;
   e->res_topk[rs] = k;
   e->res_lp[rs] = want_lp;
+  e->res_open[rs] = want_open;
   e->res_kvslot[rs] = bs;
   e->last_batch = batch;
   e->enq_count++;
@@ -639,6 +728,17 @@ int wca_align_batch_fetch(wca_engine* e, int batch, int n_tok_max, int topk, int
 
 int wca_align_batch_fetch_ex(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host, int32_t* sel_idx_host,
                              float* token_logprob_host) {
+  return align_fetch(e, batch, n_tok_max, topk, jump_frame_host, sel_idx_host, token_logprob_host, nullptr, nullptr);
+}
+
+int wca_align_batch_fetch_open(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host, int32_t* sel_idx_host,
+                               float* token_logprob_host, int32_t* end_row_host, float* score_host) {
+  return align_fetch(e, batch, n_tok_max, topk, jump_frame_host, sel_idx_host, token_logprob_host, end_row_host, score_host);
+}
+
+// the body of every wca_align_batch_fetch*
+static int align_fetch(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host, int32_t* sel_idx_host,
+                       float* token_logprob_host, int32_t* end_row_host, float* score_host) {
   if (!e) return fail(WCA_ERR_INVALID, "null engine");
   if (e->fetch_count >= e->enq_count) return fail(WCA_ERR_STATE, "nothing to fetch");
   const int rs = (int)(e->fetch_count & 1);  // oldest un-fetched batch
@@ -646,9 +746,11 @@ int wca_align_batch_fetch_ex(wca_engine* e, int batch, int n_tok_max, int topk, 
   if (sel_idx_host && e->res_topk[rs] > 0 && topk != e->res_topk[rs]) return fail(WCA_ERR_STATE, "topk does not match the pending enqueue");
   // (checked before anything is consumed: the caller can fetch the same batch again without them)
   if (token_logprob_host && !e->res_lp[rs]) return fail(WCA_ERR_STATE, "token log-probs requested, but the pending batch was enqueued without them (vocab_end = 0)");
+  if ((end_row_host || score_host) && !e->res_open[rs])
+    return fail(WCA_ERR_STATE, "end rows requested, but the pending batch was not enqueued with wca_align_batch_enqueue_open");
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipEventSynchronize(e->res_ev[rs]));
-  const ResLayout at = res_layout(batch, n_tok_max, e->res_topk[rs], e->res_lp[rs]);
+  const ResLayout at = res_layout(batch, n_tok_max, e->res_topk[rs], e->res_lp[rs], e->res_open[rs]);
   const int* res = e->res_host[rs];
   if (jump_frame_host) memcpy(jump_frame_host, res + at.jump, sizeof(int) * (size_t)batch * n_tok_max);
   if (sel_idx_host && e->res_topk[rs] > 0) memcpy(sel_idx_host, res + at.sel, sizeof(int) * (size_t)batch * topk);
@@ -656,6 +758,8 @@ int wca_align_batch_fetch_ex(wca_engine* e, int batch, int n_tok_max, int topk, 
   e->res_kvslot[rs] = -1;
   e->fetch_count++;
   if (token_logprob_host) memcpy(token_logprob_host, res + at.lp, sizeof(float) * (size_t)batch * n_tok_max);
+  if (end_row_host) memcpy(end_row_host, res + at.open, sizeof(int) * (size_t)batch);
+  if (score_host) memcpy(score_host, res + at.open + batch, sizeof(float) * (size_t)batch);
   const int flag = res[at.flags] | (res[at.flags + 1] & 2);
   if (flag & 2) return fail(WCA_ERR_HIP, "LayerNorm statistics hand-off timed out inside a GEMM epilogue (a workgroup of a row panel never arrived)");
   if (flag == ERR_TARGET_VOCAB)

@@ -172,6 +172,7 @@ struct wca_engine {
 
   // ---- run-time sized buffers
   wca::GrowBuf cap, wws, colnorm, scores, sel, selsc, matrix, trace, path, pathlen, jump, tmp0, tmp1;
+  wca::GrowBuf dtw_out, dtw_meta;   // open-end DTW: end rows [P] then scores [P] of the last launch; wca_dtw_batch_dev_open's flags / row / column counts
   wca::GrowBuf probe_jump;          // the last wca_probe_heads' jump frames [LH][N], kept on the device for wca_probe_strict_tp
   int probe_LH = 0, probe_N = 0;
   // greedy ASR pre-pass (wca_greedy_decode): self-attention K/V cache [L][2][B][T_max][d], token rows, masks, logits
@@ -198,6 +199,7 @@ struct wca_engine {
   size_t res_host_ints[2] = {0, 0};
   hipEvent_t res_ev[2] = {};
   int res_topk[2] = {0, 0}, res_ntok[2] = {0, 0}, res_batch[2] = {0, 0};
+  bool res_open[2] = {false, false}; // the batch in that slot was enqueued open-ended (its staging slot holds end rows and scores)
   bool res_lp[2] = {false, false};   // the batch in that slot was enqueued with token log-probs (its staging slot holds them)
   // teacher-token log-probs of wca_align_batch_enqueue_ex (phase 2's stream): compact f32 rows, their final-LayerNorm output (pairs when DEC
   // is split), the row map, the chunked [rows][ldc] f32 logits scratch and the [B][n_tok_max] results

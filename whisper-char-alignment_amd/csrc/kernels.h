@@ -347,6 +347,12 @@ struct DtwArgs {
   int* jump_frame;         // [P][jump_ld] first frame of each text row (or nullptr)
   int jump_ld;             // row stride of jump_frame (>= N_max)
   int P;
+  // open-end form (either of the first two set: the launch takes the open-end kernel, which also serves its closed problems): the path
+  // of an open problem ends in the last frame at the row n* of the smallest cost per path cell; jump_frame[i] = -1 for n* < i < N
+  const int* open_end;     // [P] 1 = open, 0 = closed (device)   (or nullptr => open_all)
+  int open_all;
+  int* end_row;            // [P] n* (N - 1 for a closed problem, -1 for a refused one), or nullptr
+  float* score;            // [P] C / L at the end cell, for diagnostics (no decision reads it), or nullptr
 };
 hipError_t launch_dtw(const DtwArgs& a, hipStream_t s);
 

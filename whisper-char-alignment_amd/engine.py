@@ -379,6 +379,16 @@ class WhisperAMD:
         from . import transcribe as _t
         return _t.transcribe(self, audio, **kw)
 
+    def force_align_long(self, audio, text, **kw):
+        """Word times of a recording of any length against its given transcript (align_long.force_align_long)."""
+        from . import align_long as _a
+        return _a.force_align_long(self, audio, text, **kw)
+
+    def force_align_long_batch(self, audios, texts, **kw):
+        """force_align_long() of several recordings in lock-step, one align_batch per round (align_long.force_align_long_batch)."""
+        from . import align_long as _a
+        return _a.force_align_long_batch(self, audios, texts, **kw)
+
     def transcribe_batch(self, audios, **kw):
         """transcribe() of several recordings in lock-step, one decode batch per round (transcribe.transcribe_batch)."""
         from . import transcribe as _t
@@ -422,24 +432,32 @@ class WhisperAMD:
         return _lib.AlignOpts(_lib.AGGR_TOPK if aggregation == "topk" else _lib.AGGR_MEAN, int(topk), float(w_colnorm),
                               float(w_rownorm), float(w_coverage), int(sot_len), int(medfilt_width), float(qk_scale))
 
-    def align_batch(self, pcm, n_samples, tokens, n_tok, max_frames, opts, enqueue_only=False, token_logprobs_vocab_end=None):
+    def align_batch(self, pcm, n_samples, tokens, n_tok, max_frames, opts, enqueue_only=False, token_logprobs_vocab_end=None, open_end=None):
         """Fused pipeline. pcm [B,stride] f32 cuda, tokens [B,n_max] int64 cuda. Returns (jump_frames [B,n_max] int32, sel [B,topk]).
         token_logprobs_vocab_end (tokenizer.eot): the teacher tokens' log-probabilities are computed on the GPU as well
         (wca_align_batch_enqueue_ex) and returned as a third value [B,n_max] f32 (row b: n_tok[b] - sot_len - 2 entries, then 0);
-        after enqueue_only=True, fetch them with fetch(..., with_token_logprobs=True)."""
+        after enqueue_only=True, fetch them with fetch(..., with_token_logprobs=True).
+        open_end (B bools): row b's DTW is open-ended where open_end[b] (wca_align_batch_enqueue_open: the path ends in the last frame at
+        the text row that fits best; a row with False gets exactly the closed result). The end rows [B] int32 and the scores [B] f32 are
+        returned as two further values, after the log-probs where those are asked for; rows past a row's end row have jump frame -1.
+        After enqueue_only=True, fetch them with fetch(..., with_end_rows=True). None: nothing changes."""
         B, n_max = tokens.shape
+        if open_end is not None and len(open_end) != B:
+            raise ValueError("open_end lists %d flags for %d rows" % (len(open_end), B))
         self._bind_stream()
         # pcm=None re-uses the encoder state left by the preceding greedy_decode of the same batch
         args = (self._h, _ptr(pcm) if pcm is not None else None, pcm.shape[1] if pcm is not None else 0,
                 _lib.i32_array(n_samples) if n_samples is not None else None, _ptr(tokens), n_max, _lib.i32_array(n_tok),
                 _lib.i32_array(max_frames), B, C.byref(opts))
-        if token_logprobs_vocab_end is None:
+        if open_end is not None:
+            _lib.check(self._lib.wca_align_batch_enqueue_open(*args, int(token_logprobs_vocab_end or 0), _lib.i32_array([bool(v) for v in open_end])))
+        elif token_logprobs_vocab_end is None:
             _lib.check(self._lib.wca_align_batch_enqueue(*args))
         else:
             _lib.check(self._lib.wca_align_batch_enqueue_ex(*args, int(token_logprobs_vocab_end)))
         if enqueue_only:
             return None
-        return self.fetch(B, n_max, opts, with_token_logprobs=token_logprobs_vocab_end is not None)
+        return self.fetch(B, n_max, opts, with_token_logprobs=token_logprobs_vocab_end is not None, with_end_rows=open_end is not None)
 
     def encode_batch(self, mel=None, pcm=None, n_samples=None):
         """C ABI wca_encode_batch: enqueue log-mel/encoder/cross-K/V of a micro-batch (no host sync). The state is picked up
@@ -555,12 +573,20 @@ class WhisperAMD:
         from . import decoding
         return decoding.decode(self, mel, options if options is not None else decoding.DecodingOptions())
 
-    def fetch(self, B, n_max, opts, with_token_logprobs=False):
+    def fetch(self, B, n_max, opts, with_token_logprobs=False, with_end_rows=False):
         """Results of the oldest enqueued align_batch: (jump, sel), or (jump, sel, token_logprobs [B,n_max] f32) with
-        with_token_logprobs (the batch must have been enqueued with token_logprobs_vocab_end)."""
+        with_token_logprobs (the batch must have been enqueued with token_logprobs_vocab_end). with_end_rows (the batch must have been
+        enqueued with open_end) appends the end rows [B] int32 and the scores [B] f32."""
         k = opts.topk if opts.aggregation == _lib.AGGR_TOPK else 0
         jump = np.zeros((B, n_max), dtype=np.int32)
         sel = np.zeros((B, max(k, 1)), dtype=np.int32)
+        if with_end_rows:
+            lp = np.zeros((B, n_max), dtype=np.float32) if with_token_logprobs else None
+            end_rows, scores = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.float32)
+            _lib.check(self._lib.wca_align_batch_fetch_open(self._h, B, n_max, k, jump.ctypes.data_as(_lib._pi32), sel.ctypes.data_as(_lib._pi32),
+                                                            lp.ctypes.data_as(_lib._pf) if lp is not None else None,
+                                                            end_rows.ctypes.data_as(_lib._pi32), scores.ctypes.data_as(_lib._pf)))
+            return (jump, (sel if k > 0 else None)) + ((lp,) if lp is not None else ()) + (end_rows, scores)
         if not with_token_logprobs:
             _lib.check(self._lib.wca_align_batch_fetch(self._h, B, n_max, k, jump.ctypes.data_as(_lib._pi32),
                                                        sel.ctypes.data_as(_lib._pi32)))

@@ -86,6 +86,36 @@ def dtw(x):
     return _dtw_host(_engine_for(dev), (-x).float().cpu().numpy())
 
 
+def dtw_open(x):
+    """The open-end form of dtw(x) (C ABI wca_dtw_open; no counterpart upstream): x is the ALREADY NEGATED cost matrix. The path starts at
+    (0, 0) and ends in the last frame at the text row n* of the smallest cost per path cell, decided exactly, the lower row on ties.
+    Returns (text_indices, time_indices, end_row, score); score = cost / path length at the end cell, for diagnostics only."""
+    x = torch.as_tensor(x)
+    dev = x.device if x.is_cuda else torch.device("cuda:0")
+    eng = _engine_for(dev)
+    m = np.ascontiguousarray((-x).float().cpu().numpy(), dtype=np.float32)
+    N, M = m.shape
+    ti = np.zeros(N + M, dtype=np.int32)
+    tj = np.zeros(N + M, dtype=np.int32)
+    n, end_row, score = C.c_int32(0), C.c_int32(0), C.c_float(0)
+    eng._bind_stream()
+    _lib.check(eng._lib.wca_dtw_open(eng._h, m.ctypes.data_as(_pf), N, M, ti.ctypes.data_as(_pi), tj.ctypes.data_as(_pi), C.byref(n),
+                                     C.byref(end_row), C.byref(score)))
+    return ti[:n.value].astype(np.int64), tj[:n.value].astype(np.int64), int(end_row.value), float(score.value)
+
+
+def force_align_long(model, audio, text, **kw):
+    """Word times of a recording of any length against its given transcript: align_long.force_align_long."""
+    from . import align_long
+    return align_long.force_align_long(model, audio, text, **kw)
+
+
+def force_align_long_batch(model, audios, texts, **kw):
+    """force_align_long of several recordings in lock-step: align_long.force_align_long_batch."""
+    from . import align_long
+    return align_long.force_align_long_batch(model, audios, texts, **kw)
+
+
 def median_filter(x, filter_width):
     """whisper.timing.median_filter drop-in (reflect padding, last axis)."""
     x = _as_cuda_f32(x)
