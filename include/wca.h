@@ -13,6 +13,8 @@
  *   wca_resample_16k       whisper.load_audio's resampling to 16 kHz (upstream pipes every file through ffmpeg; the filter here is the
  *                          default of torchaudio.functional.resample), with wca_resample_plan / wca_resample_table on the host
  *   wca_mel_window         whisper.pad_or_trim(mel[:, seek : seek + segment_size], N_FRAMES), the window cut of whisper.transcribe's loop
+ *   wca_quiet_cuts         no counterpart in the reference or upstream: the quietest even frame near each equal share of a long recording,
+ *                          where transcribe(pieces=...) cuts it into pieces that are decoded side by side
  *   wca_get_attentions     timing.py:45-67   get_attentions(): teacher-forced forward with every
  *                          cross-attention QK captured (timing.py:50-58), [:max_frames] slice,
  *                          median_filter, *qk_scale, softmax (timing.py:63-66); logits returned
@@ -109,7 +111,7 @@ typedef struct {
 } wca_align_opts;
 
 const char* wca_last_error(void);
-int wca_version(void);   /* 13: wca_detect_language (the language head on the encoded state; the decode that follows re-uses the state); 12: wca_resample_plan, wca_resample_table, wca_resample_16k (any input rate to 16 kHz); 11: wca_greedy_decode_rows (per-row prompts and sample budgets); 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: wca_greedy_decode_ex (prompt / prefix: sot_index, batched prefill); 7: exactly two precision modes */
+int wca_version(void);   /* 15: wca_quiet_cuts (where to cut one long recording into pieces decoded side by side); 14: the open-end DTW entry points; 13: wca_detect_language (the language head on the encoded state; the decode that follows re-uses the state); 12: wca_resample_plan, wca_resample_table, wca_resample_16k (any input rate to 16 kHz); 11: wca_greedy_decode_rows (per-row prompts and sample budgets); 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: wca_greedy_decode_ex (prompt / prefix: sot_index, batched prefill); 7: exactly two precision modes */
 
 /* ---- engine lifetime ------------------------------------------------------------------------ */
 /* A new engine is in the CONTRACT precision mode (WCA_PRECISION_REFERENCE: every stage on (hi, lo) operand pairs = the fp32 forward of
@@ -187,6 +189,22 @@ int wca_resample_16k(wca_engine* e, const float* in_dev, int channels, int64_t l
  * is WCA_ERR_INVALID (nothing is read); batch <= max_batch. */
 int wca_mel_window(wca_engine* e, const float* mel_long_dev, int64_t ld, int64_t n_frames, const int32_t* seek_host,
                    const int32_t* size_host, int batch, float* mel_out_dev);
+
+/* Where to cut one long recording into n_pieces pieces that can be transcribed side by side: near each equal share, the quietest even
+ * frame. mel_long_dev [n_mels][ld] f32 as wca_log_mel_long leaves it, n_mels from the engine; only frames [0, content_frames) are read.
+ * Integers from the first sum on, so the summation order cannot matter and the result is exact:
+ *   q(x)  = rint(4096 clamp(x, -8, 8)), ties to even; a NaN counts as 8 (loud, never preferred)
+ *   e[t]  = sum over the mel rows m of q(mel[m][t])
+ *   s[t]  = sum over j in [-half_width, half_width] of e[clamp(t + j, 0, content_frames - 1)]     (inside int32 for n_mels <= 128)
+ *   g_k   = floor(k content_frames / n_pieces) in 64-bit, k = 1 .. n_pieces - 1
+ *   cuts_host[k] = the EVEN t in [g_k - radius, g_k + radius] with the lexicographically smallest (s[t], |t - g_k|, t): even, so that every
+ *   segment time of a piece stays on the 20 ms grid; cuts_host[0] = 0, cuts_host[n_pieces] = content_frames (n_pieces + 1 entries, strictly
+ *   increasing); level_host[k - 1] = s[cuts_host[k]] (n_pieces - 1 entries; may be NULL).
+ * WCA_ERR_INVALID, with nothing launched and cuts_host untouched, unless 2 <= n_pieces <= 4096, 1 <= radius <= 1500,
+ * 0 <= half_width <= 100, content_frames <= ld, content_frames < 2^31 and content_frames / n_pieces >= 2 radius + 2 in integer division
+ * (the search ranges are then disjoint and inside (0, content_frames)). Synchronous on the engine's stream: the host needs the cuts. */
+int wca_quiet_cuts(wca_engine* e, const float* mel_long_dev, int64_t ld, int64_t content_frames, int n_pieces, int radius, int half_width,
+                   int32_t* cuts_host, int32_t* level_host /* nullable */);
 
 /* mel_dev [batch][n_mels][3000] f32; tokens_dev [batch][n_tok] int64 (already sot..eot framed,
  * infer_ali.py:69-76; shorter utterances padded with any valid token id, true lengths in n_tok_host,

@@ -85,6 +85,7 @@ SIGNATURES = {
     "wca_resample_table": (_i, [_i, C.POINTER(C.c_double)]),
     "wca_resample_16k": (_i, [_vp, _vp, _i, _i64, _i64, _i, _vp, _i64, C.POINTER(_i64)]),
     "wca_mel_window": (_i, [_vp, _vp, _i64, _i64, _pi32, _pi32, _i, _vp]),
+    "wca_quiet_cuts": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _pi32, _pi32]),
     "wca_get_attentions": (_i, [_vp, _vp, _vp, _i, _i, _pi32, _pi32, _i, _f, _vp, _vp]),
     "wca_median_filter": (_i, [_vp, _vp, _vp, _i64, _i, _i]),
     "wca_filter_attention": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _pf, _pi32, _pf]),

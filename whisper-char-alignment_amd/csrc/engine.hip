@@ -140,7 +140,7 @@ int take_kv_slot(wca_engine* e) {
 extern "C" {
 
 const char* wca_last_error(void) { return g_err.c_str(); }
-int wca_version(void) { return 14; }   // 14: open-end DTW (wca_dtw_open, wca_dtw_batch_dev_open, wca_align_batch_enqueue_open / _fetch_open); 13: wca_detect_language (language identification on the state a decode then takes); 12: wca_resample_plan / wca_resample_table / wca_resample_16k (polyphase resampler to 16 kHz); 11: wca_greedy_decode_rows (per-row initial tokens / sample budgets: the rows of a batch at different decoder positions); 10: wca_log_mel_long / wca_mel_window (whole-recording log-mel, window cut); 9: the two diagnostic stamp entry points removed, no switch read from the environment; 8: prompted greedy decode (wca_greedy_decode_ex, batched prefill); 7: two precision modes only (the per-stage precision mask, its setter / getter and the mixed
+int wca_version(void) { return 15; }   // 15: wca_quiet_cuts (the quietest even frame near each equal share of a long recording); 14: open-end DTW (wca_dtw_open, wca_dtw_batch_dev_open, wca_align_batch_enqueue_open / _fetch_open); 13: wca_detect_language (language identification on the state a decode then takes); 12: wca_resample_plan / wca_resample_table / wca_resample_16k (polyphase resampler to 16 kHz); 11: wca_greedy_decode_rows (per-row initial tokens / sample budgets: the rows of a batch at different decoder positions); 10: wca_log_mel_long / wca_mel_window (whole-recording log-mel, window cut); 9: the two diagnostic stamp entry points removed, no switch read from the environment; 8: prompted greedy decode (wca_greedy_decode_ex, batched prefill); 7: two precision modes only (the per-stage precision mask, its setter / getter and the mixed
                                       // state are gone); 6: teacher-token log-probs (wca_align_batch_enqueue_ex / _fetch_ex, wca_token_logprobs);
                                       // 5: a new engine is in the contract mode; wca_engine_create_ex, W_lo slab, switch table
 
@@ -250,6 +250,7 @@ void wca_engine_destroy(wca_engine* e) {
   e->probe_jump.release();
   e->dtw_out.release();
   e->dtw_meta.release();
+  e->quiet_out.release();
   for (auto& t : e->rs_tables) (void)hipFree(t.dev);
   for (int i = 0; i < 2; ++i) {
     if (e->res_host[i]) (void)hipHostFree(e->res_host[i]);

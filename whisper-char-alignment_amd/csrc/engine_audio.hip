@@ -1,5 +1,5 @@
 // libwca.so engine, audio front end: the resampler to 16 kHz with its table cache (wca_resample_*), the two log-mel forms (wca_log_mel and
-// phase 1's run_logmel; wca_log_mel_long) and the window cut wca_mel_window. Host code only: the kernels live in resample.hip / logmel.hip.
+// phase 1's run_logmel; wca_log_mel_long) the window cut wca_mel_window and the quiet cuts wca_quiet_cuts. Host code only: the kernels live in resample.hip / logmel.hip / quiet_cuts.hip.
 #include "engine_internal.h"
 
 using namespace wca;
@@ -125,6 +125,33 @@ int wca_mel_window(wca_engine* e, const float* mel_long_dev, int64_t ld, int64_t
   int* rows[4];
   WCA_TRY(stage_meta(e, batch, seek_host, size_host, nullptr, nullptr, rows));
   HIPCHK(launch_mel_window(mel_long_dev, ld, e->dims.n_mels, rows[0], rows[1], batch, mel_out_dev, e->stream));
+  return WCA_OK;
+}
+
+int wca_quiet_cuts(wca_engine* e, const float* mel_long_dev, int64_t ld, int64_t content_frames, int n_pieces, int radius, int half_width,
+                   int32_t* cuts_host, int32_t* level_host) {
+  if (!e || !mel_long_dev || !cuts_host) return fail(WCA_ERR_INVALID, "null argument");
+  if (n_pieces < 2 || n_pieces > QUIET_PIECES_MAX) return fail(WCA_ERR_INVALID, "n_pieces %d outside [2,%d]", n_pieces, QUIET_PIECES_MAX);
+  if (radius < 1 || radius > QUIET_RADIUS_MAX) return fail(WCA_ERR_INVALID, "radius %d outside [1,%d]", radius, QUIET_RADIUS_MAX);
+  if (half_width < 0 || half_width > QUIET_HALF_WIDTH_MAX) return fail(WCA_ERR_INVALID, "half_width %d outside [0,%d]", half_width, QUIET_HALF_WIDTH_MAX);
+  if (content_frames > ld || content_frames > INT32_MAX)
+    return fail(WCA_ERR_INVALID, "content_frames %lld beyond ld %lld or 2^31 - 1", (long long)content_frames, (long long)ld);
+  if (content_frames / n_pieces < 2 * radius + 2)   // (also refuses content_frames < 1): the search ranges stay disjoint and inside (0, content_frames)
+    return fail(WCA_ERR_INVALID, "%lld frames in %d pieces leave %lld per piece: fewer than 2 radius + 2 = %d", (long long)content_frames, n_pieces,
+                (long long)(content_frames / n_pieces), 2 * radius + 2);
+  if (e->dims.n_mels > 128) return fail(WCA_ERR_INVALID, "n_mels %d > 128: the smoothed level would leave int32", e->dims.n_mels);
+  WCA_TRY(enter(e));
+  const int n = n_pieces - 1;
+  HIPCHK(e->quiet_out.ensure(2 * sizeof(int) * (size_t)n));
+  int* out_dev = (int*)e->quiet_out.p;
+  HIPCHK(launch_quiet_cuts(mel_long_dev, ld, e->dims.n_mels, content_frames, n_pieces, radius, half_width, out_dev, out_dev + n, e->stream));
+  std::vector<int32_t> out(2 * (size_t)n);
+  HIPCHK(hipMemcpyAsync(out.data(), out_dev, sizeof(int32_t) * out.size(), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  cuts_host[0] = 0;
+  memcpy(cuts_host + 1, out.data(), sizeof(int32_t) * (size_t)n);
+  cuts_host[n_pieces] = (int32_t)content_frames;
+  if (level_host) memcpy(level_host, out.data() + n, sizeof(int32_t) * (size_t)n);
   return WCA_OK;
 }
 

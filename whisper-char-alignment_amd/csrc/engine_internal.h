@@ -173,6 +173,7 @@ struct wca_engine {
   // ---- run-time sized buffers
   wca::GrowBuf cap, wws, colnorm, scores, sel, selsc, matrix, trace, path, pathlen, jump, tmp0, tmp1;
   wca::GrowBuf dtw_out, dtw_meta;   // open-end DTW: end rows [P] then scores [P] of the last launch; wca_dtw_batch_dev_open's flags / row / column counts
+  wca::GrowBuf quiet_out;           // wca_quiet_cuts: the interior cuts [n_pieces - 1] then their levels [n_pieces - 1], copied to the host before the call returns
   wca::GrowBuf probe_jump;          // the last wca_probe_heads' jump frames [LH][N], kept on the device for wca_probe_strict_tp
   int probe_LH = 0, probe_N = 0;
   // greedy ASR pre-pass (wca_greedy_decode): self-attention K/V cache [L][2][B][T_max][d], token rows, masks, logits

@@ -261,6 +261,14 @@ hipError_t launch_logmel_long(const LogMelLongArgs& a, hipStream_t s);
 // seek / size are device arrays; the caller has checked 0 <= seek, 1 <= size <= 3000, seek + size <= the long mel's frames.
 hipError_t launch_mel_window(const float* mel_long, long ld, int n_mels, const int* seek, const int* size, int B, float* out, hipStream_t s);
 
+// ---------------------------------------------------------------- quiet cuts of a long recording (quiet_cuts.hip)
+constexpr int QUIET_PIECES_MAX = 4096, QUIET_RADIUS_MAX = 1500, QUIET_HALF_WIDTH_MAX = 100;
+// The interior cuts of wca_quiet_cuts (include/wca.h has the definition): cuts [n_pieces - 1] and level [n_pieces - 1] are device arrays,
+// entry k - 1 for target g_k. Only frames [0, content_frames) of mel_long [n_mels][ld] are read. The caller has checked the ranges of
+// include/wca.h (the launcher refuses what would leave the kernel's LDS or let two search ranges meet).
+hipError_t launch_quiet_cuts(const float* mel_long, long ld, int n_mels, long content_frames, int n_pieces, int radius, int half_width,
+                             int* cuts, int* level, hipStream_t s);
+
 // ---------------------------------------------------------------- resampler to 16 kHz (resample.hip)
 constexpr int RESAMPLE_SR_OUT = 16000, RESAMPLE_SR_MIN = 2000, RESAMPLE_SR_MAX = 384000;
 enum { RESAMPLE_HOME_UNIFORM = 0, RESAMPLE_HOME_LDS = 1, RESAMPLE_HOME_GLOBAL = 2 };   // where the kernel reads the polyphase table from

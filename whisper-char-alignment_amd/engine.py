@@ -374,6 +374,26 @@ class WhisperAMD:
         self._after_call()
         return out[0] if single else out
 
+    def quiet_cuts(self, mel_long, n_pieces, radius=500, half_width=12, content_frames=None):
+        """Where to cut a long recording into n_pieces pieces (C ABI wca_quiet_cuts: near each equal share, the even frame with the lowest
+        level smoothed over 2 half_width + 1 frames, within `radius` frames). mel_long [n_mels, T] f32 cuda as log_mel_long leaves it;
+        content_frames defaults to T - 3000, the recording without its 30 s of padding. Returns (cuts: n_pieces + 1 frames from 0 to
+        content_frames, strictly increasing; levels: the n_pieces - 1 smoothed levels at the interior cuts) as lists of ints."""
+        if mel_long.dim() != 2 or mel_long.shape[0] != self.dims.n_mels or mel_long.dtype != torch.float32 or mel_long.stride(1) != 1:
+            raise ValueError("mel_long must be an f32 [n_mels, T] tensor with unit frame stride")
+        mel_long = mel_long.to(self.device)
+        if content_frames is None:
+            content_frames = mel_long.shape[1] - N_FRAMES
+        if int(content_frames) > mel_long.shape[1]:
+            raise ValueError("content_frames %d beyond the %d frames of mel_long" % (content_frames, mel_long.shape[1]))
+        n = int(n_pieces)
+        cuts = np.zeros(max(n, 1) + 1, dtype=np.int32)
+        levels = np.zeros(max(n - 1, 1), dtype=np.int32)
+        self._bind_stream()
+        _lib.check(self._lib.wca_quiet_cuts(self._h, _ptr(mel_long), mel_long.stride(0), int(content_frames), n, int(radius), int(half_width),
+                                            cuts.ctypes.data_as(_lib._pi32), levels.ctypes.data_as(_lib._pi32)))
+        return [int(v) for v in cuts], [int(v) for v in levels[:n - 1]]
+
     def transcribe(self, audio, **kw):
         """whisper.transcribe(model, audio, ...) at temperature 0 with this project's word aligner (transcribe.transcribe)."""
         from . import transcribe as _t

@@ -34,8 +34,14 @@ Limits (part of the contract):
     positions), the batch shrinks as recordings end, and with word_timestamps one align_batch(pcm=None) per round aligns the
     rows that have words. A recording's result is what transcribe() gives for it alone, up to argmax near-ties of the f16
     logits (the GEMM path, and with it the fp32 summation order, depends on the number of rows in the batch).
-  * clip_timestamps, hallucination_silence_threshold, prepend_punctuations / append_punctuations are not built (they
-    belong to upstream's own word aligner).
+  * clip_timestamps is upstream's (SeekState(clips=...) restates its seek_clips loop). pieces=N / "auto" has no upstream counterpart: ONE
+    recording is cut at quiet frames (wca_quiet_cuts: near each equal share the even frame with the lowest smoothed log-mel level) and its
+    pieces are decoded side by side as the rows of one batch, each conditioned on its own previous text only. What a cut does to the
+    text around it on real speech -- a word split where no quiet frame was in reach, a piece that starts without the context the
+    sequential loop would have carried over -- is UNVALIDATED: no checkpoint is at hand here, the tests run on random weights and compare
+    pieces=N with the same ranges given as clip_timestamps.
+  * hallucination_silence_threshold, prepend_punctuations / append_punctuations are not built (they belong to upstream's own word
+    aligner).
 
 Decisions the upstream text leaves open:
   * a window that ended inside speech (its tokens do not end in a single timestamp; seek advances to the last consecutive
@@ -71,6 +77,7 @@ from .audio import HOP_LENGTH, N_FRAMES, SAMPLE_RATE  # noqa: E402
 INPUT_STRIDE = 2                                         # mel frames per encoder frame (N_FRAMES // n_audio_ctx)
 TIME_PRECISION = INPUT_STRIDE * HOP_LENGTH / SAMPLE_RATE  # 0.02 s per timestamp token step / encoder frame
 FRAME_SECONDS = HOP_LENGTH / SAMPLE_RATE                  # 0.01 s per mel frame
+FRAMES_PER_SECOND = SAMPLE_RATE // HOP_LENGTH             # 100
 MAX_LENGTH = 448                                          # infer_ali.py:26
 PLACEHOLDER_FRAMES = 100                                  # max_frames of a row that rides along in a round's alignment without words
 
@@ -143,10 +150,14 @@ class SeekState:
             pending = st.receive(decoding_result)      # None: the window was skipped (no speech) and the state has advanced
             if pending is not None:                    # (seek, size, max_frames, segments): align the segments in place, then
                 st.commit(aligned)                     # aligned: bool, or None when no aligner runs
-    seek_loop (one recording) and transcribe_batch (several in lock-step) both drive it."""
+    seek_loop (one recording) and transcribe_batch (several in lock-step) both drive it.
+    clips: upstream's seek_clips, a list of (start, stop) frame pairs: the loop runs over [start, stop) of each in turn, a window never
+    reaches past its clip's stop (size = min(3000, content_frames - seek, stop - seek)) and the next clip starts when seek >= stop. A stop
+    beyond the recording is clamped to content_frames. None is the whole recording, [(0, content_frames)]. transcribe(pieces=...) gives
+    every piece of a recording a state of its own with one clip."""
 
     def __init__(self, n_frames, tokenizer, *, initial_prompt_tokens=(), condition_on_previous_text=True, no_speech_threshold=0.6,
-                 logprob_threshold=-1.0, decode_text=None):
+                 logprob_threshold=-1.0, decode_text=None, clips=None):
         if decode_text is None:
             def decode_text(toks):
                 return tokenizer.decode(toks) if getattr(tokenizer, "has_vocab", True) else None
@@ -158,15 +169,33 @@ class SeekState:
         self.all_segments, self.windows = [], []
         self.prompt_reset_since = 0
         self.without_words = 0
-        self.seek = 0
+        # upstream's seek_clips: the loop runs over these frame ranges, one after the other; None is the whole recording
+        self.clips = [(0, self.content_frames)] if clips is None else [(int(a), min(int(b), self.content_frames)) for a, b in clips]
+        if any(a < 0 for a, _ in self.clips):
+            raise ValueError("a clip starts before the recording: %r" % (clips,))
+        self.clip_idx = 0
+        self.seek = self.clips[0][0] if self.clips else 0
         self._pending = None
+        self._settle()
+
+    def _settle(self):
+        """Upstream's clip bookkeeping at the top of its loop: seek is pulled up to the clip's start, and a clip that seek has reached the end
+        of hands over to the next one, which starts at its own start."""
+        while self.clip_idx < len(self.clips):
+            start, stop = self.clips[self.clip_idx]
+            self.seek = max(self.seek, start)
+            if self.seek < stop:
+                return
+            self.clip_idx += 1
+            if self.clip_idx < len(self.clips):
+                self.seek = self.clips[self.clip_idx][0]
 
     @property
     def done(self):
-        return self.seek >= self.content_frames
+        return self.clip_idx >= len(self.clips)
 
     def request(self):
-        size = min(N_FRAMES, self.content_frames - self.seek)
+        size = min(N_FRAMES, self.content_frames - self.seek, self.clips[self.clip_idx][1] - self.seek)
         return self.seek, size, self.all_tokens[self.prompt_reset_since:]
 
     def receive(self, result):
@@ -180,6 +209,7 @@ class SeekState:
             if should_skip:
                 window["skipped"] = True
                 self.seek += size
+                self._settle()
                 return None
         segments, advance, max_frames = split_window(result.tokens, self.tokenizer.timestamp_begin, self.tokenizer.eot, seek, size, result,
                                                      self.decode_text)
@@ -194,6 +224,7 @@ class SeekState:
             window["aligned"] = bool(aligned)
             self.without_words += 0 if window["aligned"] else 1
         self.seek += advance
+        self._settle()
         self.all_segments.extend({"id": i, **seg} for i, seg in enumerate(segments, start=len(self.all_segments)))
         self.all_tokens.extend(t for seg in segments for t in seg["tokens"])
         if not self.condition_on_previous_text:
@@ -204,13 +235,13 @@ class SeekState:
 
 
 def seek_loop(n_frames, cut_window, decode_window, tokenizer, *, initial_prompt_tokens=(), condition_on_previous_text=True,
-              no_speech_threshold=0.6, logprob_threshold=-1.0, align_window=None, decode_text=None):
+              no_speech_threshold=0.6, logprob_threshold=-1.0, align_window=None, decode_text=None, clips=None):
     """whisper.transcribe's loop over a log-mel of `n_frames` frames (the recording's frames plus 3000 of padding).
     cut_window(seek, size) -> mel window; decode_window(mel_window, prompt_tokens) -> DecodingResult (tokens, avg_logprob,
     no_speech_prob, ...); align_window(seek, size, max_frames, segments) -> bool fills the kept segments' "words" (False: the window
-    got none). Returns {"segments", "tokens" (initial prompt included), "windows", "windows_without_words"}."""
+    got none); clips: SeekState's. Returns {"segments", "tokens" (initial prompt included), "windows", "windows_without_words"}."""
     st = SeekState(n_frames, tokenizer, initial_prompt_tokens=initial_prompt_tokens, condition_on_previous_text=condition_on_previous_text,
-                   no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold, decode_text=decode_text)
+                   no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold, decode_text=decode_text, clips=clips)
     while not st.done:
         seek, size, prompt = st.request()
         pending = st.receive(decode_window(cut_window(seek, size), prompt))
@@ -305,6 +336,44 @@ def make_aligner(model, tokenizer, *, aligned_unit_type="char", aggr="topk", top
     return align_window
 
 
+def clip_frames(clip_timestamps, content_frames):
+    """upstream's clip_timestamps ("a,b,..." or a list of seconds: start, end, start, end, ...) -> [(start, stop)] in frames, round(ts * 100);
+    an odd count is closed with content_frames, and none at all is the whole recording."""
+    if isinstance(clip_timestamps, str):
+        clip_timestamps = [float(ts) for ts in clip_timestamps.split(",")] if clip_timestamps else []
+    elif isinstance(clip_timestamps, (int, float)):
+        clip_timestamps = [clip_timestamps]
+    points = [round(float(ts) * FRAMES_PER_SECOND) for ts in clip_timestamps] or [0]
+    if len(points) % 2 == 1:
+        points.append(content_frames)
+    return list(zip(points[::2], points[1::2]))
+
+
+PIECE_FRAMES_AUTO = 2 * N_FRAMES   # pieces="auto": at least two windows per piece, so that conditioning on previous text keeps a meaning
+PIECE_RADIUS = 500                 # a cut may move 5 s off its equal share to find a quiet frame
+
+
+def plan_pieces(content_frames, pieces, max_batch):
+    """How many pieces a recording of content_frames frames is cut into, and how far a cut may move off its equal share: (n, radius) for
+    model.quiet_cuts. pieces: an int, capped so that a piece has at least 4 frames, or "auto": min(max_batch, content_frames // 6000).
+    radius = min(500, content_frames // n // 2 - 1), which keeps the search ranges of neighbouring cuts apart. n < 2: the recording is
+    not split, (1, 0). An int above max_batch is a ValueError: every piece is one row of the decode batch."""
+    if isinstance(pieces, str):
+        if pieces.lower() != "auto":
+            raise ValueError("pieces is an int or \"auto\", not %r" % (pieces,))
+        n = min(int(max_batch), content_frames // PIECE_FRAMES_AUTO)
+    else:
+        n = int(pieces)
+        if n < 1:
+            raise ValueError("pieces must be at least 1, not %r" % (pieces,))
+        if n > int(max_batch):
+            raise ValueError("pieces=%d needs %d decode rows: more than model.max_batch = %d" % (n, n, max_batch))
+        n = min(n, content_frames // 4)
+    if n < 2:
+        return 1, 0
+    return n, min(PIECE_RADIUS, content_frames // n // 2 - 1)
+
+
 def _as_pcm(audio, model, sample_rate=SAMPLE_RATE):
     """One recording as 16 kHz mono f32 [n]: a path is read with its own rate and channels (audio.load_audio), an array or tensor
     ([n], or [channels, n]) is taken at `sample_rate`. Anything not at 16 kHz goes through model.resample with its channels (the kernel
@@ -330,7 +399,7 @@ def _as_pcm(audio, model, sample_rate=SAMPLE_RATE):
 def transcribe(model, audio, *, language, initial_prompt=None, condition_on_previous_text=True, no_speech_threshold=0.6,
                logprob_threshold=-1.0, word_timestamps=False, word_confidence=False, aligned_unit_type="char", aggr="topk", topk=10,
                medfilt_width=3, vocab_path=None, temperature=0.0, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0, decode_window=None,
-               detect_languages=None, sample_rate=SAMPLE_RATE, **decode_options):
+               detect_languages=None, sample_rate=SAMPLE_RATE, clip_timestamps=None, pieces=None, **decode_options):
     """whisper.transcribe(model, audio, ...) -> {"text", "segments": [{"id", "seek", "start", "end", "text", "tokens", "temperature",
     "avg_logprob", "compression_ratio", "no_speech_prob", "words": [{"word", "start", "end", "probability"}]}], "language"} plus
     "windows" (every decoded window: seek, size, advance, skipped, max_frames, aligned) and "windows_without_words".
@@ -340,23 +409,30 @@ def transcribe(model, audio, *, language, initial_prompt=None, condition_on_prev
     [channels, n]) at `sample_rate` Hz, any length. Audio that is not at 16 kHz is resampled on the GPU first (WhisperAMD.resample), as
     upstream's load_audio has ffmpeg do. word_timestamps=True: word times
     from the character aligner per window (module docstring); word_confidence=True adds each word's probability (None otherwise).
-    decode_window(mel_window, prompt_tokens) -> DecodingResult replaces the engine's greedy decode (tests); decode_options go to
-    DecodingOptions. Limits: module docstring. It is transcribe_batch of one recording, whose single row is decoded and aligned alone."""
+    clip_timestamps: upstream's "start,end,start,end,..." in seconds (a str or a list; an odd count runs to the end of the recording): only
+    those ranges are transcribed, one after the other. pieces: an int or "auto" (plan_pieces): the recording is cut at quiet frames
+    (WhisperAMD.quiet_cuts) into that many pieces, which are decoded side by side as the rows of ONE batch per round; every piece starts
+    from initial_prompt only and conditions on its own previous text. The result then carries "pieces" and every window its "piece"
+    (transcribe_batch has the details). pieces and clip_timestamps together are a ValueError.
+    decode_window(mel_window, prompt_tokens) -> DecodingResult replaces the engine's greedy decode (tests; with pieces it is called row by
+    row); decode_options go to DecodingOptions. Limits: module docstring. It is transcribe_batch of one recording, whose single row is
+    decoded and aligned alone."""
     decode_windows = None
     if decode_window is not None:
         def decode_windows(mel_windows, prompts):
-            return [decode_window(mel_windows[0], prompts[0])]
+            return [decode_window(w, p) for w, p in zip(mel_windows, prompts)]
     return transcribe_batch(model, [audio], language=language, initial_prompt=initial_prompt, condition_on_previous_text=condition_on_previous_text,
                             no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold, word_timestamps=word_timestamps,
                             word_confidence=word_confidence, aligned_unit_type=aligned_unit_type, aggr=aggr, topk=topk, medfilt_width=medfilt_width,
                             vocab_path=vocab_path, temperature=temperature, w_colnorm=w_colnorm, w_rownorm=w_rownorm, w_coverage=w_coverage,
-                            decode_windows=decode_windows, detect_languages=detect_languages, sample_rate=sample_rate, **decode_options)[0]
+                            decode_windows=decode_windows, detect_languages=detect_languages, sample_rate=sample_rate,
+                            clip_timestamps=clip_timestamps, pieces=pieces, **decode_options)[0]
 
 
 def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_on_previous_text=True, no_speech_threshold=0.6,
                      logprob_threshold=-1.0, word_timestamps=False, word_confidence=False, aligned_unit_type="char", aggr="topk", topk=10,
                      medfilt_width=3, vocab_path=None, temperature=0.0, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0, decode_windows=None,
-                     detect_languages=None, sample_rate=SAMPLE_RATE, **decode_options):
+                     detect_languages=None, sample_rate=SAMPLE_RATE, clip_timestamps=None, pieces=None, **decode_options):
     """transcribe() of several recordings in lock-step: a list with transcribe()'s result for every recording of `audios`, in order.
     Each round cuts the next window of every unfinished recording, decodes them in ONE batch with every row's own previous text as its
     prompt (decoding.decode with one DecodingOptions per row: wca_greedy_decode_rows) and, with word_timestamps, aligns the rows that
@@ -368,12 +444,27 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
     (B codes, B probabilities) replaces the engine's detection: tests), the group is partitioned by detected language and the
     lock-step loop runs once per language (one decode cannot mix languages); the results still come back in input order, each with
     its own "language" and "language_probability". A group that comes out in ONE language decodes its first round on the encoder state
-    detection left in the engine (no second encoder pass); a group with several languages is simply re-encoded, language by language."""
+    detection left in the engine (no second encoder pass); a group with several languages is simply re-encoded, language by language.
+    clip_timestamps (upstream's, in seconds; the same for every recording): every recording's loop runs over those ranges only
+    (SeekState(clips=...)).
+    pieces (an int or "auto"; not together with clip_timestamps): every recording is cut into n pieces (plan_pieces; a short recording
+    into fewer, or not at all) at the quietest even frame near each equal share (model.quiet_cuts) and contributes one SeekState per
+    piece, with clips=[(cuts[k], cuts[k + 1])], to the lock-step loop: round r decodes the r-th window of every unfinished piece of every
+    recording of the group in one batch. Every piece starts from initial_prompt only and conditions on its own previous text. A group
+    holds as many recordings as their pieces fit into max_batch rows (max_batch // n for an int; for "auto" a recording's share depends on
+    its length, so its log-mel is computed before the group it ends up in is closed). A round's windows are cut with ONE mel_window call
+    per recording. The pieces are merged in order: segment ids run on, "windows" are concatenated, each with its "piece", and the result
+    carries "pieces": [{"start_frame", "stop_frame", "level"}], level being the smoothed level (wca_quiet_cuts) at the cut the piece starts
+    at, None for the first. language="auto" still detects on the recording's first window and all its pieces take that language; the first
+    round then has other rows than the detection saw, so the state detection left in the engine is simply dropped and the round encodes
+    its own windows. Without pieces and clip_timestamps the result is what it was before either existed."""
     from . import decoding
     from .tokenizer import get_tokenizer
     import torch
     check_supported(temperature, language)
     auto = isinstance(language, str) and language.lower() == "auto"
+    if pieces is not None and clip_timestamps is not None:
+        raise ValueError("pieces cuts the whole recording: it cannot be combined with clip_timestamps")
     if word_confidence and not word_timestamps:
         raise ValueError("word_confidence is a property of the aligned words: it needs word_timestamps=True")
     if word_timestamps and vocab_path is None:
@@ -381,6 +472,8 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
     max_batch = int(getattr(model, "max_batch", 1))
     if max_batch < 1:
         raise ValueError("transcribe_batch needs model.max_batch >= 1")
+    if pieces is not None:
+        plan_pieces(4 * max_batch, pieces, max_batch)   # (what does not depend on the recording is refused before any audio is read)
     task = decode_options.get("task", "transcribe")
     tokenizers = {}
 
@@ -426,24 +519,46 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
         raise ValueError("sample_rate lists %d rates for %d recordings" % (len(rates), len(audios)))
     results = [None] * len(audios)
 
-    def lock_step(rows, code, mels, extra):
-        """The lock-step loop over the recordings `rows` of a group, all in language `code`; fills their results."""
+    def plan(mel):
+        """What one recording contributes to the lock-step loop: "clips", one SeekState(clips=...) argument per decode row it takes, and
+        "pieces", the result's entry (None unless pieces were asked for)."""
+        content = mel.shape[1] - N_FRAMES
+        if clip_timestamps is not None:
+            return {"clips": [clip_frames(clip_timestamps, content)], "pieces": None}
+        if pieces is None:
+            return {"clips": [None], "pieces": None}
+        n, radius = plan_pieces(content, pieces, max_batch)
+        cuts, levels = model.quiet_cuts(mel, n, radius=radius) if n > 1 else ([0, content], [])
+        levels = [None, *levels]
+        return {"clips": [[(cuts[k], cuts[k + 1])] for k in range(n)] if n > 1 else [None],   # (not split: the plain loop, as without pieces)
+                "pieces": [{"start_frame": cuts[k], "stop_frame": cuts[k + 1], "level": levels[k]} for k in range(n)]}
+
+    def lock_step(rows, code, mels, extra, plans):
+        """The lock-step loop over the recordings `rows` of a group, all in language `code`; fills their results. A recording takes one
+        decode row per entry of its plan's "clips" (one, unless it is cut into pieces)."""
         tokenizer = tokenizer_for(code)
         decode_rows = decode_windows if decode_windows is not None else engine_decode(code)
         align = None
         if word_timestamps:
             align = make_aligner(model, tokenizer, aligned_unit_type=aligned_unit_type, aggr=aggr, topk=topk, medfilt_width=medfilt_width,
                                  w_colnorm=w_colnorm, w_rownorm=w_rownorm, w_coverage=w_coverage, word_confidence=word_confidence)
-        states = {i: SeekState(mels[i].shape[1], tokenizer, initial_prompt_tokens=prompt_tokens,
-                               condition_on_previous_text=condition_on_previous_text, no_speech_threshold=no_speech_threshold,
-                               logprob_threshold=logprob_threshold, decode_text=decode_text(tokenizer)) for i in rows}
+        states = {(i, k): SeekState(mels[i].shape[1], tokenizer, initial_prompt_tokens=prompt_tokens,
+                                    condition_on_previous_text=condition_on_previous_text, no_speech_threshold=no_speech_threshold,
+                                    logprob_threshold=logprob_threshold, decode_text=decode_text(tokenizer), clips=clips)
+                  for i in rows for k, clips in enumerate(plans[i]["clips"])}   # (in recording, then piece order)
         while True:
-            live = [i for i in rows if not states[i].done]   # a finished recording is never decoded again
+            live = [u for u in states if not states[u].done]   # a finished recording (or piece) is never decoded again
             if not live:
                 break
-            requests = [states[i].request() for i in live]
-            windows = [model.mel_window(mels[i], seek, size) for i, (seek, size, _) in zip(live, requests)]
-            windows = torch.stack(windows) if len(live) > 1 else windows[0][None]   # (one row: a view, no copy)
+            requests = [states[u].request() for u in live]
+            windows = []
+            for i in rows:   # one window cut per recording: its rows are windows of the same long mel
+                mine = [(seek, size) for u, (seek, size, _) in zip(live, requests) if u[0] == i]
+                if len(mine) == 1:
+                    windows.append(model.mel_window(mels[i], *mine[0])[None])   # (one row: a view, no copy)
+                elif mine:
+                    windows.append(model.mel_window(mels[i], [seek for seek, _ in mine], [size for _, size in mine]))
+            windows = torch.cat(windows) if len(windows) > 1 else windows[0]
             decoded = decode_rows(windows, [prompt for _, _, prompt in requests])
             pending = [states[i].receive(r) for i, r in zip(live, decoded)]
             if align is not None and len(live) == 1:
@@ -455,17 +570,50 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
             for i, pend, al in zip(live, pending, aligned):
                 if pend is not None:
                     states[i].commit(al)
-        for i in rows:
-            out = states[i].result()
-            text = tokenizer.decode(out["tokens"][len(prompt_tokens):]) if vocab_path is not None else ""
-            results[i] = {"text": text, "segments": out["segments"], "language": code, **extra.get(i, {}), "windows": out["windows"],
-                          "windows_without_words": out["windows_without_words"]}
+        for i in rows:   # a recording's pieces are merged in order (one piece: the state's own result)
+            outs = [states[(i, k)].result() for k in range(len(plans[i]["clips"]))]
+            segments, windows = [], []
+            for k, out in enumerate(outs):
+                for seg in out["segments"]:
+                    seg["id"] = len(segments)
+                    segments.append(seg)
+                for w in out["windows"]:
+                    if plans[i]["pieces"] is not None:
+                        w["piece"] = k
+                    windows.append(w)
+            tokens = [t for out in outs for t in out["tokens"][len(prompt_tokens):]]
+            results[i] = {"text": tokenizer.decode(tokens) if vocab_path is not None else "", "segments": segments, "language": code,
+                          **extra.get(i, {}), "windows": windows, "windows_without_words": sum(out["windows_without_words"] for out in outs)}
+            if plans[i]["pieces"] is not None:
+                results[i]["pieces"] = plans[i]["pieces"]
 
-    for g0 in range(0, len(audios), max_batch):
-        group = list(range(g0, min(len(audios), g0 + max_batch)))
-        mels = {i: model.log_mel_long(_as_pcm(audios[i], model, rates[i])) for i in group}
+    ready = {}   # recording -> (log-mel, plan), computed when its group is formed -- or one recording ahead, where the rows it takes
+                 # depend on its length (pieces="auto")
+
+    def prepare(i):
+        if i not in ready:
+            mel = model.log_mel_long(_as_pcm(audios[i], model, rates[i]))
+            ready[i] = (mel, plan(mel))
+        return ready[i]
+
+    def rows_of(i):   # decode rows recording i takes in a round
+        if pieces is None:
+            return 1
+        return len(prepare(i)[1]["clips"]) if isinstance(pieces, str) else int(pieces)
+
+    g0 = 0
+    while g0 < len(audios):
+        group, used = [], 0
+        while g0 < len(audios) and (not group or used + rows_of(g0) <= max_batch):   # (without pieces: max_batch recordings)
+            used += rows_of(g0)
+            group.append(g0)
+            g0 += 1
+        mels, plans = {}, {}
+        for i in group:
+            mels[i], plans[i] = prepare(i)
+            del ready[i]
         if not auto:
-            lock_step(group, language, mels, {})
+            lock_step(group, language, mels, {}, plans)
             continue
         codes, extra = {i: None for i in group}, {i: {"language_probability": None} for i in group}
         heard = [i for i in group if mels[i].shape[1] > N_FRAMES]   # recordings that have a first window
@@ -479,14 +627,18 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
         by_language = {}
         for i in group:
             by_language.setdefault(codes[i], []).append(i)
-        if len(by_language) != 1 or heard != group:
+        if len(by_language) != 1 or heard != group or any(plans[i]["clips"] != [None] for i in group):
             state_left[0] = None   # the detected rows are not one decode batch: every language's first round encodes its own windows
         for code, rows in by_language.items():
-            lock_step(rows, code, mels, extra)
+            lock_step(rows, code, mels, extra, plans)
     return results
 
 
 # ------------------------------------------------------------------------------------------------ command line
+def _pieces_arg(value):
+    return "auto" if value.lower() == "auto" else int(value)
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Long-form transcription with character-aligned word times (one JSON per recording)")
     src = p.add_mutually_exclusive_group(required=True)
@@ -513,6 +665,10 @@ def parse_args(argv=None):
     p.add_argument("--forward_precision", type=str, default="reference", choices=["reference", "split", "f16"])
     p.add_argument("--sample_rate", type=int, default=SAMPLE_RATE, help="rate of raw .npy arrays ([n] or [channels, n]); audio files carry their own")
     p.add_argument("--batch", type=int, default=1, help="recordings transcribed in lock-step (transcribe_batch; the engine's max_batch)")
+    p.add_argument("--pieces", type=_pieces_arg, default=None, metavar="N|auto", help="cut every recording at quiet frames into N pieces that are "
+                   "decoded side by side (auto: as many as --batch rows allow, at least 60 s each); needs --batch >= N")
+    p.add_argument("--clip_timestamps", type=str, default=None, metavar="a,b,...", help="transcribe only these ranges: start,end,start,end,... in "
+                   "seconds (an odd count runs to the end of the recording)")
     return p.parse_args(argv)
 
 
@@ -548,6 +704,10 @@ def main(args, model=None):
         raise SystemExit("--word_timestamps aligns the decoded text: pass --vocab <local multilingual.tiktoken>")
     if args.batch < 1:
         raise SystemExit("--batch must be at least 1")
+    if isinstance(args.pieces, int) and not 1 <= args.pieces <= args.batch:
+        raise SystemExit("--pieces %d needs --batch >= %d: every piece is one row of the decode batch" % (args.pieces, args.pieces))
+    if args.pieces is not None and args.clip_timestamps is not None:
+        raise SystemExit("--pieces cuts the whole recording: it cannot be combined with --clip_timestamps")
     if model is None:
         model = load_model(args)
     os.makedirs(args.output_dir, exist_ok=True)
@@ -556,6 +716,8 @@ def main(args, model=None):
               word_timestamps=args.word_timestamps, word_confidence=args.word_confidence, aligned_unit_type=args.aligned_unit_type,
               aggr=args.aggr, topk=args.topk, medfilt_width=args.medfilt_width, vocab_path=args.vocab, w_colnorm=args.w_colnorm,
               w_rownorm=args.w_rownorm, w_coverage=args.w_coverage, sample_rate=args.sample_rate)
+    if args.pieces is not None or args.clip_timestamps is not None:   # (otherwise the call is what it was before either existed)
+        kw.update(pieces=args.pieces, clip_timestamps=args.clip_timestamps)
     recordings = _recordings(args)
 
     def source(path):   # a raw array is taken at --sample_rate; a file is read, with its own rate, by transcribe
