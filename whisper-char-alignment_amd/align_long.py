@@ -7,7 +7,7 @@ openai-whisper (which only times its own ASR hypothesis) has this path: PARITY I
 design; its mechanics and the open-end DTW kernel under it are pinned by tests, its quality on real speech is UNVALIDATED until a real
 checkpoint is at hand.
 
-What runs where: audio handling is transcribe's (`_as_pcm`, the GPU resampler, the log-mel of the whole recording once, the window cut
+What runs where: audio handling is transcribe's (longform.py: `as_pcm`, the GPU resampler, the log-mel of the whole recording once, the window cut
 `mel_window`); every window is ONE fused alignment (encode_batch of the window's mel, then align_batch(pcm=None, open_end=[...])): the
 teacher-forced forward with capture, median filter, softmax, head scores, aggregation and the DTW are the 30 s path's. The one new piece
 below the host is the OPEN-END DTW (csrc/dtw.hip, include/wca.h wca_dtw_open): an interior window holds only a PREFIX of the text it is
@@ -44,6 +44,7 @@ Limits: 448 framed tokens and 1500 encoder frames per window (the engine's), so 
 per-word confidence, no silence or music detection, no fallback to ASR for a window that fails, one GPU.
 """
 import argparse
+import functools
 import json
 import os
 import sys
@@ -56,11 +57,9 @@ if __package__ in (None, ""):
     _pkg = importlib.import_module("whisper-char-alignment_amd")
     __package__ = _pkg.__name__
 
-from .audio import HOP_LENGTH, N_FRAMES, SAMPLE_RATE, TOKENS_PER_SECOND  # noqa: E402
-
-INPUT_STRIDE = 2                          # mel frames per encoder frame
-FRAME_SECONDS = HOP_LENGTH / SAMPLE_RATE  # 0.01 s per mel frame
-MAX_LENGTH = 448                          # framed tokens per window (infer_ali.py:26)
+from .audio import N_FRAMES, SAMPLE_RATE, TOKENS_PER_SECOND  # noqa: E402
+from .longform import (ALIGNER_KEYWORDS, FRAME_SECONDS, INPUT_STRIDE, MAX_LENGTH, add_aligner_options, add_model_options,  # noqa: E402
+                       aligner_options, as_pcm, cut_windows, groups_of, load_model, pad_token_rows, sample_rates, source)
 
 
 class AlignState:
@@ -199,74 +198,59 @@ def transcript_units(text, tokenizer, aligned_unit_type="char"):
     return units, starts, words
 
 
-def force_align_long_batch(model, audios, texts, *, language, vocab_path, aligned_unit_type="char", aggr="topk", topk=10, medfilt_width=3,
-                           sample_rate=SAMPLE_RATE, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0):
+def align_group_rows(model, tokenizer, opts, aligned_unit_type, mels, units, states, live, requests):
+    """align_loop's align_rows for one group of recordings, once all but `live` and `requests` are bound: mels, units and states are the
+    group's long log-mels, transcript units and AlignStates, by position in the group. A round is ONE encode_batch of the live rows'
+    windows and ONE align_batch, whose rows may mix open and closed windows."""
+    from .timing import words_from_jump_frames
+    windows = cut_windows(model, mels, [(i, seek, size) for i, (seek, size, _w0, _w1, _c) in zip(live, requests)])
+    runs = [units[i][slice(*states[i].unit_span(w0, w1))] for i, (_s, _z, w0, w1, _c) in zip(live, requests)]
+    rows = [[*tokenizer.sot_sequence, tokenizer.no_timestamps, *run, tokenizer.eot] for run in runs]
+    model.encode_batch(mel=windows)
+    jump, _sel, end_rows, scores = model.align_batch(None, None, pad_token_rows(rows, tokenizer.eot).to(model.device), [len(r) for r in rows],
+                                                     [size // INPUT_STRIDE for _s, size, _w0, _w1, _c in requests], opts,
+                                                     open_end=[not closed for _s, _z, _w0, _w1, closed in requests])
+    outs = []
+    for b, (run, req) in enumerate(zip(runs, requests)):
+        # a closed window: today's DTW and words_from_jump_frames, unchanged -- its (starts, ends)
+        times = words_from_jump_frames(jump[b], run, tokenizer, aligned_unit_type, want_words=False)[1:] if req[4] else None
+        outs.append((jump[b], end_rows[b], scores[b], times))
+    return outs
+
+
+def force_align_long_batch(model, audios, texts, *, language, vocab_path, aligned_unit_type="char", sample_rate=SAMPLE_RATE, **aligner):
     """force_align_long() of several recordings in lock-step: a list with force_align_long()'s result for every (audio, text) pair, in
     order. Every round cuts the next window of every unfinished recording and aligns them in ONE encode_batch + align_batch, whose rows
     may mix open and closed windows; the batch shrinks as recordings end, and more recordings than model.max_batch go in groups of
-    max_batch. sample_rate is one int for every array / tensor input or one per recording (a path carries its own rate)."""
-    import torch
-    from .timing import words_from_jump_frames
+    max_batch. sample_rate is one int for every array / tensor input or one per recording (a path carries its own rate); aligner: aggr="topk",
+    topk=10, medfilt_width=3, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0 (longform.aligner_options)."""
     from .tokenizer import get_tokenizer
-    from .transcribe import _as_pcm
     audios, texts = list(audios), list(texts)
     if len(audios) != len(texts):
         raise ValueError("%d recordings for %d transcripts" % (len(audios), len(texts)))
     if vocab_path is None:
         raise ValueError("the transcript is tokenised with the model's vocabulary: pass vocab_path=<local *.tiktoken file>")
-    rates = [int(r) for r in sample_rate] if isinstance(sample_rate, (list, tuple)) else [int(sample_rate)] * len(audios)
-    if len(rates) != len(audios):
-        raise ValueError("sample_rate lists %d rates for %d recordings" % (len(rates), len(audios)))
-    max_batch = int(getattr(model, "max_batch", 1))
+    rates = sample_rates(sample_rate, len(audios))
     tokenizer = get_tokenizer(model.is_multilingual, language=language, vocab_path=vocab_path)
-    sot = list(tokenizer.sot_sequence)
-    if aggr == "topk":
-        topk = min(int(topk), model.dims.n_text_layer * model.dims.n_text_head)
-    opts = model.make_opts(aggregation=aggr, topk=topk, w_colnorm=w_colnorm, w_rownorm=w_rownorm, w_coverage=w_coverage, sot_len=len(sot),
-                           medfilt_width=medfilt_width, qk_scale=1.0)
+    sot_len = len(tokenizer.sot_sequence)
+    opts = aligner_options(model, tokenizer, **aligner)
     prepared = [transcript_units(t, tokenizer, aligned_unit_type) for t in texts]
-    for units, starts, words in prepared:   # an over-long word is refused before any GPU work
-        AlignState(N_FRAMES, starts, words, len(sot))
+    for _units, starts, words in prepared:   # an over-long word is refused before any GPU work
+        AlignState(N_FRAMES, starts, words, sot_len)
     results = []
-    for g0 in range(0, len(audios), max_batch):
-        group = list(range(g0, min(len(audios), g0 + max_batch)))
-        mels = [model.log_mel_long(_as_pcm(audios[i], model, rates[i])) for i in group]
+    for group in groups_of(range(len(audios)), int(getattr(model, "max_batch", 1))):
+        mels = [model.log_mel_long(as_pcm(audios[i], model, rates[i])) for i in group]
+        states = [AlignState(mel.shape[1], prepared[i][1], prepared[i][2], sot_len) for i, mel in zip(group, mels)]
         units = [prepared[i][0] for i in group]
-        states = [AlignState(mel.shape[1], prepared[i][1], prepared[i][2], len(sot)) for i, mel in zip(group, mels)]
-
-        def align_rows(live, requests):
-            windows = [model.mel_window(mels[i], seek, size) for i, (seek, size, _w0, _w1, _c) in zip(live, requests)]
-            windows = torch.stack(windows) if len(live) > 1 else windows[0][None]
-            runs = [units[i][slice(*states[i].unit_span(w0, w1))] for i, (_s, _z, w0, w1, _c) in zip(live, requests)]
-            rows = [[*sot, tokenizer.no_timestamps, *run, tokenizer.eot] for run in runs]
-            toks = torch.full((len(rows), max(len(r) for r in rows)), tokenizer.eot, dtype=torch.int64)
-            for b, r in enumerate(rows):
-                toks[b, :len(r)] = torch.tensor(r, dtype=torch.int64)
-            model.encode_batch(mel=windows)
-            jump, _sel, end_rows, scores = model.align_batch(None, None, toks.to(model.device), [len(r) for r in rows],
-                                                             [size // INPUT_STRIDE for _s, size, _w0, _w1, _c in requests], opts,
-                                                             open_end=[not closed for _s, _z, _w0, _w1, closed in requests])
-            outs = []
-            for b, (run, req) in enumerate(zip(runs, requests)):
-                times = None
-                if req[4]:   # a closed window: today's DTW and words_from_jump_frames, unchanged
-                    _w, starts, ends = words_from_jump_frames(jump[b], run, tokenizer, aligned_unit_type, want_words=False)
-                    times = (starts, ends)
-                outs.append((jump[b], end_rows[b], scores[b], times))
-            return outs
-
-        results.extend(align_loop(states, align_rows))
+        results.extend(align_loop(states, functools.partial(align_group_rows, model, tokenizer, opts, aligned_unit_type, mels, units, states)))
     return results
 
 
-def force_align_long(model, audio, text, *, language, vocab_path, aligned_unit_type="char", aggr="topk", topk=10, medfilt_width=3,
-                     sample_rate=SAMPLE_RATE, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0):
+def force_align_long(model, audio, text, **options):
     """Word times of one recording of any length against its given transcript `text` (module docstring: rules, limits, what is pinned).
     audio: a path, or mono samples [n] (or [channels, n]) at `sample_rate` Hz, as transcribe() takes them. Returns {"words": [{"word",
     "start", "end"}], "windows": [...], "unaligned_words", "windows_without_words"}; it is force_align_long_batch of one recording."""
-    return force_align_long_batch(model, [audio], [text], language=language, vocab_path=vocab_path, aligned_unit_type=aligned_unit_type,
-                                  aggr=aggr, topk=topk, medfilt_width=medfilt_width, sample_rate=sample_rate, w_colnorm=w_colnorm,
-                                  w_rownorm=w_rownorm, w_coverage=w_coverage)[0]
+    return force_align_long_batch(model, [audio], [text], **options)[0]
 
 
 # ------------------------------------------------------------------------------------------------ command line
@@ -277,21 +261,10 @@ def parse_args(argv=None):
     src.add_argument("--scp", type=str, help="list of recordings: `<audio path><TAB><transcript text file>` per line")
     p.add_argument("--text", type=str, default=None, help="the transcript of --audio: a UTF-8 text file")
     p.add_argument("--output_dir", type=str, required=True)
-    p.add_argument("--model", type=str, default="medium")
-    p.add_argument("--weights", type=str, default=None, help="local openai-whisper checkpoint (.pt)")
-    p.add_argument("--random_init", action="store_true", help="seeded random weights (dry run without a checkpoint)")
+    add_model_options(p)
     p.add_argument("--vocab", type=str, required=True, help="local tiktoken vocabulary file")
     p.add_argument("--language", type=str, default="en")
-    p.add_argument("--medfilt_width", type=int, default=3)
-    p.add_argument("--aggr", type=str, default="topk", choices=["mean", "topk"])
-    p.add_argument("--topk", type=int, default=10)
-    p.add_argument("--aligned_unit_type", type=str, default="char", choices=["subword", "char"])
-    p.add_argument("--w_colnorm", type=float, default=1.0)
-    p.add_argument("--w_rownorm", type=float, default=1.0)
-    p.add_argument("--w_coverage", type=float, default=0.0)
-    p.add_argument("--forward_precision", type=str, default="reference", choices=["reference", "split", "f16"])
-    p.add_argument("--sample_rate", type=int, default=SAMPLE_RATE, help="rate of raw .npy arrays; audio files carry their own")
-    p.add_argument("--batch", type=int, default=1, help="recordings aligned in lock-step (the engine's max_batch)")
+    add_aligner_options(p)
     return p.parse_args(argv)
 
 
@@ -310,26 +283,17 @@ def _recordings(args):
                 raise SystemExit("--scp lines are `<audio path><TAB><transcript text file>`; got %r" % line)
     return out
 
-
 def main(args, model=None):
     """Writes <output_dir>/<audio basename>.json per recording (force_align_long()'s result plus "audio" and "text"); returns the paths."""
-    from .transcribe import load_model
     if args.batch < 1:
         raise SystemExit("--batch must be at least 1")
     recordings = _recordings(args)
     if model is None:
         model = load_model(args)
     os.makedirs(args.output_dir, exist_ok=True)
-    kw = dict(language=args.language, vocab_path=args.vocab, aligned_unit_type=args.aligned_unit_type, aggr=args.aggr, topk=args.topk,
-              medfilt_width=args.medfilt_width, sample_rate=args.sample_rate, w_colnorm=args.w_colnorm, w_rownorm=args.w_rownorm,
-              w_coverage=args.w_coverage)
-
-    def source(path):
-        return np.load(path) if path.endswith(".npy") else path
-
+    kw = dict(language=args.language, vocab_path=args.vocab, sample_rate=args.sample_rate, **{k: getattr(args, k) for k in ALIGNER_KEYWORDS})
     paths = []
-    for g0 in range(0, len(recordings), args.batch):
-        group = recordings[g0:g0 + args.batch]
+    for group in groups_of(recordings, args.batch):
         texts = [open(t, encoding="utf-8").read() for _a, t in group]
         for (audio, text_path), result in zip(group, force_align_long_batch(model, [source(a) for a, _t in group], texts, **kw)):
             out = os.path.join(args.output_dir, os.path.splitext(os.path.basename(audio))[0] + ".json")

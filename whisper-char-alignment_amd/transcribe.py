@@ -72,14 +72,14 @@ if __package__ in (None, ""):
     _pkg = importlib.import_module("whisper-char-alignment_amd")
     __package__ = _pkg.__name__
 
-from .audio import HOP_LENGTH, N_FRAMES, SAMPLE_RATE  # noqa: E402
+from . import decoding  # noqa: E402  (decoding.decode is looked up when it is called)
+from .audio import N_FRAMES, SAMPLE_RATE  # noqa: E402
+from .longform import (ALIGNER_KEYWORDS, FRAME_SECONDS, FRAMES_PER_SECOND, INPUT_STRIDE, MAX_LENGTH, TIME_PRECISION,  # noqa: E402,F401
+                       add_aligner_options, add_model_options, aligner_options, as_pcm, cut_windows, groups_of, load_model,
+                       pad_token_rows, sample_rates, source)
+from .tokenizer import get_tokenizer  # noqa: E402
 
-INPUT_STRIDE = 2                                         # mel frames per encoder frame (N_FRAMES // n_audio_ctx)
-TIME_PRECISION = INPUT_STRIDE * HOP_LENGTH / SAMPLE_RATE  # 0.02 s per timestamp token step / encoder frame
-FRAME_SECONDS = HOP_LENGTH / SAMPLE_RATE                  # 0.01 s per mel frame
-FRAMES_PER_SECOND = SAMPLE_RATE // HOP_LENGTH             # 100
-MAX_LENGTH = 448                                          # infer_ali.py:26
-PLACEHOLDER_FRAMES = 100                                  # max_frames of a row that rides along in a round's alignment without words
+PLACEHOLDER_FRAMES = 100   # max_frames of a row that rides along in a round's alignment without words
 
 
 def check_supported(temperature, language):
@@ -261,67 +261,50 @@ def attach_words(segments, words):
         home["words"].append(w)
 
 
-def make_aligner(model, tokenizer, *, aligned_unit_type="char", aggr="topk", topk=10, medfilt_width=3, w_colnorm=1.0, w_rownorm=1.0,
-                 w_coverage=0.0, word_confidence=False):
-    """align_window for seek_loop: the paper's aligner on the encoder state the window's decode left in the engine."""
-    import torch
-    from .retokenize import encode, remove_punctuation
-    from .timing import word_probabilities, words_from_jump_frames
-    sot_len = len(tokenizer.sot_sequence)
-    if aggr == "topk":
-        topk = min(int(topk), model.dims.n_text_layer * model.dims.n_text_head)   # filter_attention keeps at most every head (timing.py:13-43)
-    opts = model.make_opts(aggregation=aggr, topk=topk, w_colnorm=w_colnorm, w_rownorm=w_rownorm, w_coverage=w_coverage, sot_len=sot_len,
-                           medfilt_width=medfilt_width, qk_scale=1.0)
-    n_audio_ctx = model.dims.n_audio_ctx
+class WindowAligner:
+    """The paper's aligner on the encoder state a round's decode left in the engine (make_aligner's result)."""
 
-    def prepare(max_frames, segments):
+    def __init__(self, model, tokenizer, *, aligned_unit_type="char", word_confidence=False, **options):
+        self.model, self.tokenizer, self.unit, self.word_confidence = model, tokenizer, aligned_unit_type, word_confidence
+        self.opts = aligner_options(model, tokenizer, **options)
+        self.placeholder = [*tokenizer.sot_sequence, tokenizer.no_timestamps, tokenizer.encode(" a")[-1], tokenizer.eot]   # a row without words
+
+    def prepare(self, max_frames, segments):
         """The framed token row the window is aligned with and its text tokens, or None where the window gets no words."""
+        from .retokenize import encode, remove_punctuation
+        tokenizer = self.tokenizer
         text = tokenizer.decode([t for seg in segments for t in seg["tokens"] if t < tokenizer.eot])
         try:
-            text_tokens = encode(remove_punctuation(text), tokenizer, aligned_unit_type)
+            text_tokens = encode(remove_punctuation(text), tokenizer, self.unit)
         except Exception:   # a character the byte-level dry-run tokenizer cannot encode
             return None
         tokens = [*tokenizer.sot_sequence, tokenizer.no_timestamps, *text_tokens, tokenizer.eot]
-        if not text_tokens or len(tokens) > MAX_LENGTH or not 1 <= max_frames <= n_audio_ctx:
+        if not text_tokens or len(tokens) > MAX_LENGTH or not 1 <= max_frames <= self.model.dims.n_audio_ctx:
             return None
         return tokens, text_tokens
 
-    def attach(seek, segments, text_tokens, jump_row, logprob_row):
-        words, starts, ends = words_from_jump_frames(jump_row, text_tokens, tokenizer, aligned_unit_type)
+    def attach(self, seek, segments, text_tokens, jump_row, logprob_row):
+        from .timing import word_probabilities, words_from_jump_frames
+        words, starts, ends = words_from_jump_frames(jump_row, text_tokens, self.tokenizer, self.unit)
         if not len(starts):
             return False
-        probs = word_probabilities(logprob_row[:len(text_tokens)], text_tokens, tokenizer, aligned_unit_type) if word_confidence else None
+        probs = word_probabilities(logprob_row[:len(text_tokens)], text_tokens, self.tokenizer, self.unit) if self.word_confidence else None
         offset = seek * FRAME_SECONDS
         attach_words(segments, [{"word": words[i], "start": offset + float(starts[i]), "end": offset + float(ends[i]),
                                  "probability": probs[i] if probs is not None else None} for i in range(len(starts))])
         return True
 
-    def align_window(seek, size, max_frames, segments):
-        prep = prepare(max_frames, segments)
-        if prep is None:
-            return False
-        tokens, text_tokens = prep
-        toks_dev = torch.tensor([tokens], dtype=torch.int64, device=model.device)
-        res = model.align_batch(None, None, toks_dev, [len(tokens)], [max_frames], opts,
-                                token_logprobs_vocab_end=tokenizer.eot if word_confidence else None)
-        return attach(seek, segments, text_tokens, res[0][0], res[2][0] if word_confidence else None)
-
-    def align_round(rows):
+    def align_round(self, rows):
         """rows: one entry per row of the batch the last decode left in the engine, in order: (seek, size, max_frames, segments), or
         None for a row that was skipped. ONE align_batch(pcm=None) for the rows that have words; a row without (skipped, or refused by
         `prepare`) rides along as a minimal placeholder row whose output is dropped. Returns one bool per row (None for a skipped row)."""
-        preps = [prepare(r[2], r[3]) if r is not None else None for r in rows]
+        preps = [self.prepare(r[2], r[3]) if r is not None else None for r in rows]
         if not any(p is not None for p in preps):
             return [None if r is None else False for r in rows]   # nothing to align: the next decode drops the state
-        placeholder = [*tokenizer.sot_sequence, tokenizer.no_timestamps, tokenizer.encode(" a")[-1], tokenizer.eot]
-        token_rows = [p[0] if p is not None else placeholder for p in preps]
+        token_rows = [p[0] if p is not None else self.placeholder for p in preps]
         max_frames = [r[2] if p is not None else PLACEHOLDER_FRAMES for r, p in zip(rows, preps)]
-        n_max = max(len(t) for t in token_rows)
-        toks = torch.full((len(rows), n_max), tokenizer.eot, dtype=torch.int64)
-        for b, t in enumerate(token_rows):
-            toks[b, :len(t)] = torch.tensor(t, dtype=torch.int64)
-        res = model.align_batch(None, None, toks.to(model.device), [len(t) for t in token_rows], max_frames, opts,
-                                token_logprobs_vocab_end=tokenizer.eot if word_confidence else None)
+        res = self.model.align_batch(None, None, pad_token_rows(token_rows, self.tokenizer.eot).to(self.model.device), [len(t) for t in token_rows],
+                                     max_frames, self.opts, token_logprobs_vocab_end=self.tokenizer.eot if self.word_confidence else None)
         out = []
         for b, (r, p) in enumerate(zip(rows, preps)):
             if r is None:
@@ -329,11 +312,15 @@ def make_aligner(model, tokenizer, *, aligned_unit_type="char", aggr="topk", top
             elif p is None:
                 out.append(False)
             else:
-                out.append(attach(r[0], r[3], p[1], res[0][b][:len(token_rows[b])], res[2][b] if word_confidence else None))
+                out.append(self.attach(r[0], r[3], p[1], res[0][b][:len(token_rows[b])], res[2][b] if self.word_confidence else None))
         return out
 
-    align_window.align_round = align_round
-    return align_window
+    def align_window(self, seek, size, max_frames, segments):
+        """seek_loop's align_window: a round of one row."""
+        return self.align_round([(seek, size, max_frames, segments)])[0]
+
+
+make_aligner = WindowAligner   # (`.align_window` is the align_window that seek_loop takes)
 
 
 def clip_frames(clip_timestamps, content_frames):
@@ -374,32 +361,7 @@ def plan_pieces(content_frames, pieces, max_batch):
     return n, min(PIECE_RADIUS, content_frames // n // 2 - 1)
 
 
-def _as_pcm(audio, model, sample_rate=SAMPLE_RATE):
-    """One recording as 16 kHz mono f32 [n]: a path is read with its own rate and channels (audio.load_audio), an array or tensor
-    ([n], or [channels, n]) is taken at `sample_rate`. Anything not at 16 kHz goes through model.resample with its channels (the kernel
-    averages them); 16 kHz audio stays on the host and is averaged there."""
-    import torch
-    if isinstance(audio, (str, os.PathLike)):
-        from .audio import load_audio
-        audio, sample_rate = load_audio(audio)
-    if not isinstance(audio, torch.Tensor):
-        audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
-    audio = audio.to(torch.float32)
-    if int(sample_rate) != SAMPLE_RATE:
-        if audio.dim() not in (1, 2):
-            raise ValueError("audio must be one recording [n] or [channels, n]; got shape %s" % (tuple(audio.shape),))
-        return model.resample(audio, int(sample_rate))
-    if audio.dim() == 2:
-        audio = audio.mean(dim=0)
-    if audio.dim() != 1:
-        raise ValueError("audio must be one mono recording [n]; got shape %s" % (tuple(audio.shape),))
-    return audio
-
-
-def transcribe(model, audio, *, language, initial_prompt=None, condition_on_previous_text=True, no_speech_threshold=0.6,
-               logprob_threshold=-1.0, word_timestamps=False, word_confidence=False, aligned_unit_type="char", aggr="topk", topk=10,
-               medfilt_width=3, vocab_path=None, temperature=0.0, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0, decode_window=None,
-               detect_languages=None, sample_rate=SAMPLE_RATE, clip_timestamps=None, pieces=None, **decode_options):
+def transcribe(model, audio, *, language, decode_window=None, **options):
     """whisper.transcribe(model, audio, ...) -> {"text", "segments": [{"id", "seek", "start", "end", "text", "tokens", "temperature",
     "avg_logprob", "compression_ratio", "no_speech_prob", "words": [{"word", "start", "end", "probability"}]}], "language"} plus
     "windows" (every decoded window: seek, size, advance, skipped, max_frames, aligned) and "windows_without_words".
@@ -416,17 +378,155 @@ def transcribe(model, audio, *, language, initial_prompt=None, condition_on_prev
     (transcribe_batch has the details). pieces and clip_timestamps together are a ValueError.
     decode_window(mel_window, prompt_tokens) -> DecodingResult replaces the engine's greedy decode (tests; with pieces it is called row by
     row); decode_options go to DecodingOptions. Limits: module docstring. It is transcribe_batch of one recording, whose single row is
-    decoded and aligned alone."""
-    decode_windows = None
-    if decode_window is not None:
-        def decode_windows(mel_windows, prompts):
-            return [decode_window(w, p) for w, p in zip(mel_windows, prompts)]
-    return transcribe_batch(model, [audio], language=language, initial_prompt=initial_prompt, condition_on_previous_text=condition_on_previous_text,
-                            no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold, word_timestamps=word_timestamps,
-                            word_confidence=word_confidence, aligned_unit_type=aligned_unit_type, aggr=aggr, topk=topk, medfilt_width=medfilt_width,
-                            vocab_path=vocab_path, temperature=temperature, w_colnorm=w_colnorm, w_rownorm=w_rownorm, w_coverage=w_coverage,
-                            decode_windows=decode_windows, detect_languages=detect_languages, sample_rate=sample_rate,
-                            clip_timestamps=clip_timestamps, pieces=pieces, **decode_options)[0]
+    decoded and aligned alone. The other keywords and their defaults are transcribe_batch's."""
+    row_by_row = None if decode_window is None else (lambda mel_windows, prompts: [decode_window(w, p) for w, p in zip(mel_windows, prompts)])
+    return transcribe_batch(model, [audio], language=language, decode_windows=row_by_row, **options)[0]
+
+
+class _Call:
+    """What one transcribe_batch call carries from round to round: the model and options, one tokenizer per language code, the initial prompt's
+    tokens, and `state_left`: rows of encoded, undecoded state the engine's own detection left behind for the decode that comes next."""
+
+    def __init__(self, model, language, initial_prompt, vocab_path, decode_options, decode_windows, detect_languages, seek_options, aligner_options):
+        self.model, self.vocab_path, self.decode_options, self.seek_options = model, vocab_path, decode_options, seek_options
+        self.decode_windows, self.detect_languages, self.aligner_options = decode_windows, detect_languages, aligner_options   # (None: no words)
+        self.auto = isinstance(language, str) and language.lower() == "auto"
+        self.tokenizers, self.state_left, self.prompt_tokens = {}, None, []
+        if initial_prompt is not None:
+            self.prompt_tokens = decoding._text_tokens(self.tokenizer_for(None if self.auto else language), initial_prompt,
+                                                       decoding.DecodingOptions(vocab_path=vocab_path), "initial_prompt")
+        self.detect_tokenizer = None   # the engine's own detection, in the numbering the decode tokenizer uses
+        if self.auto and detect_languages is None and model.is_multilingual:
+            self.detect_tokenizer = get_tokenizer(True, num_languages=99)
+
+    def tokenizer_for(self, code):   # (the special tokens but the language's own are the same in every language)
+        if code not in self.tokenizers:
+            self.tokenizers[code] = get_tokenizer(self.model.is_multilingual, language=code, task=self.decode_options.get("task", "transcribe"),
+                                                  vocab_path=self.vocab_path)
+        return self.tokenizers[code]
+
+    def detect(self, mel_windows):
+        """(codes, probabilities) of the rows of mel_windows; the engine's own detection leaves their encoded state behind."""
+        if self.detect_languages is not None:
+            return self.detect_languages(mel_windows)
+        tok = self.detect_tokenizer
+        tokens, probs = decoding.detect_language(self.model, mel_windows, tok)
+        self.state_left = len(probs)
+        codes = [tok.all_language_codes[int(t) - tok.all_language_tokens[0]] for t in tokens]
+        return codes, [p[c] for c, p in zip(codes, probs)]
+
+    def decode(self, code, mel_windows, prompts):
+        """One round's decode: a DecodingResult per row, every row with its own previous text as the prompt."""
+        if self.decode_windows is not None:
+            return self.decode_windows(mel_windows, prompts)
+        rows = [decoding.DecodingOptions(language=code, temperature=0.0, prompt=list(p) or None, vocab_path=self.vocab_path, **self.decode_options)
+                for p in prompts]
+        want_text = self.vocab_path is not None
+        waiting, self.state_left = self.state_left == len(rows), None
+        if waiting:   # the first round of a group that detection found in one language: its state is waiting
+            return decoding.decode(self.model, None, rows[0] if len(rows) == 1 else rows, encoded_batch=len(rows), want_text=want_text)
+        if len(rows) == 1:   # a single row (transcribe(), or the last recording of a group): a uniform decode of one window
+            return [decoding.decode(self.model, mel_windows[0], rows[0], want_text=want_text)]
+        return decoding.decode(self.model, mel_windows, rows, want_text=want_text)
+
+
+def plan_recording(mel, clip_timestamps, pieces, max_batch, model):
+    """What one recording contributes to the lock-step loop: (clips, pieces). clips: one SeekState(clips=...) argument per decode row it
+    takes; pieces: the result's "pieces" entry (None unless pieces were asked for)."""
+    content = mel.shape[1] - N_FRAMES
+    if clip_timestamps is not None:
+        return [clip_frames(clip_timestamps, content)], None
+    if pieces is None:
+        return [None], None
+    n, radius = plan_pieces(content, pieces, max_batch)
+    cuts, levels = model.quiet_cuts(mel, n, radius=radius) if n > 1 else ([0, content], [])
+    levels = [None, *levels]
+    return ([[(cuts[k], cuts[k + 1])] for k in range(n)] if n > 1 else [None],   # (not split: the plain loop, as without pieces)
+            [{"start_frame": cuts[k], "stop_frame": cuts[k + 1], "level": levels[k]} for k in range(n)])
+
+
+def _prepared(model, audio, rate, clip_timestamps, pieces, max_batch):
+    mel = model.log_mel_long(as_pcm(audio, model, rate))
+    return mel, plan_recording(mel, clip_timestamps, pieces, max_batch, model)
+
+
+def form_groups(model, audios, rates, clip_timestamps, pieces, max_batch):
+    """The groups of recordings that share the decode batch: yields (indices, mels, plans), mels and plans by index. A group holds as
+    many recordings as their decode rows fit into max_batch (without pieces: max_batch recordings). A recording's log-mel is computed as
+    it joins its group -- or one recording ahead, where the rows it takes depend on its length (pieces="auto") -- and is dropped when the
+    next group is asked for: both dicts are valid until then."""
+    group, mels, plans, used = [], {}, {}, 0
+    for i, (audio, rate) in enumerate(zip(audios, rates)):
+        ahead = _prepared(model, audio, rate, clip_timestamps, pieces, max_batch) if isinstance(pieces, str) else None
+        rows = 1 if pieces is None else len(ahead[1][0]) if ahead is not None else int(pieces)   # decode rows it takes in a round
+        if group and used + rows > max_batch:
+            yield group, mels, plans
+            group, used = [], 0
+            mels.clear(), plans.clear()
+        mels[i], plans[i] = ahead or _prepared(model, audio, rate, clip_timestamps, pieces, max_batch)
+        group.append(i)
+        used += rows
+    if group:
+        yield group, mels, plans
+
+
+def detect_group(call, group, mels, plans):
+    """language="auto" for one group, its first windows detected in ONE batch: (codes, extra) by recording, the language code (None
+    where there was no window to look at) and {"language_probability": p}. The state detection left in the engine is dropped unless the
+    detected rows are the first round's rows: one language, every recording heard, none with clips or pieces."""
+    codes, extra = {i: None for i in group}, {i: {"language_probability": None} for i in group}
+    heard = [i for i in group if mels[i].shape[1] > N_FRAMES]   # recordings that have a first window
+    if call.detect_languages is None and call.detect_tokenizer is None:   # an English-only model: "en" without a detection pass, as upstream
+        codes.update({i: "en" for i in heard})
+    elif heard:
+        found, probs = call.detect(cut_windows(call.model, mels, [(i, 0, min(N_FRAMES, mels[i].shape[1] - N_FRAMES)) for i in heard]))
+        for i, code, prob in zip(heard, found, probs):
+            codes[i], extra[i] = code, {"language_probability": None if prob is None else float(prob)}
+    if len(set(codes.values())) != 1 or heard != group or any(plans[i][0] != [None] for i in group):
+        call.state_left = None   # the detected rows are not one decode batch: every language's first round encodes its own windows
+    return codes, extra
+
+
+def lock_step(call, code, rows, mels, plans):
+    """The lock-step loop over the recordings `rows` of a group, all in language `code`: returns their SeekStates, finished, by
+    (recording, piece). A recording takes one decode row per entry of its plan's clips (one, unless it is cut into pieces)."""
+    tokenizer = call.tokenizer_for(code)
+    aligner = make_aligner(call.model, tokenizer, **call.aligner_options) if call.aligner_options is not None else None
+    states = {(i, k): SeekState(mels[i].shape[1], tokenizer, initial_prompt_tokens=call.prompt_tokens, clips=clips, **call.seek_options)
+              for i in rows for k, clips in enumerate(plans[i][0])}   # (in recording, then piece order)
+    while True:
+        live = [u for u in states if not states[u].done]   # a finished recording (or piece) is never decoded again
+        if not live:
+            return states
+        requests = [states[u].request() for u in live]
+        windows = cut_windows(call.model, mels, [(u[0], seek, size) for u, (seek, size, _) in zip(live, requests)])
+        decoded = call.decode(code, windows, [prompt for _, _, prompt in requests])
+        pending = [states[u].receive(r) for u, r in zip(live, decoded)]
+        aligned = aligner.align_round(pending) if aligner is not None else [None] * len(live)
+        for u, pend, al in zip(live, pending, aligned):
+            if pend is not None:
+                states[u].commit(al)
+
+
+def merge_pieces(outs, pieces, *, tokenizer, language, extra, n_prompt):
+    """A recording's result from the SeekState results of its pieces, in order (one piece: the state's own result): segment ids run on,
+    "windows" are concatenated, each with its "piece" where pieces were asked for (pieces: the result's entry, else None), and the text
+    is all tokens but the initial prompt's n_prompt, decoded by `tokenizer` (None without a vocabulary: "")."""
+    segments, windows = [], []
+    for k, out in enumerate(outs):
+        for seg in out["segments"]:
+            seg["id"] = len(segments)
+            segments.append(seg)
+        for w in out["windows"]:
+            if pieces is not None:
+                w["piece"] = k
+            windows.append(w)
+    tokens = [t for out in outs for t in out["tokens"][n_prompt:]]
+    result = {"text": tokenizer.decode(tokens) if tokenizer is not None else "", "segments": segments, "language": language, **extra,
+              "windows": windows, "windows_without_words": sum(out["windows_without_words"] for out in outs)}
+    if pieces is not None:
+        result["pieces"] = pieces
+    return result
 
 
 def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_on_previous_text=True, no_speech_threshold=0.6,
@@ -458,11 +558,7 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
     at, None for the first. language="auto" still detects on the recording's first window and all its pieces take that language; the first
     round then has other rows than the detection saw, so the state detection left in the engine is simply dropped and the round encodes
     its own windows. Without pieces and clip_timestamps the result is what it was before either existed."""
-    from . import decoding
-    from .tokenizer import get_tokenizer
-    import torch
     check_supported(temperature, language)
-    auto = isinstance(language, str) and language.lower() == "auto"
     if pieces is not None and clip_timestamps is not None:
         raise ValueError("pieces cuts the whole recording: it cannot be combined with clip_timestamps")
     if word_confidence and not word_timestamps:
@@ -474,163 +570,21 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
         raise ValueError("transcribe_batch needs model.max_batch >= 1")
     if pieces is not None:
         plan_pieces(4 * max_batch, pieces, max_batch)   # (what does not depend on the recording is refused before any audio is read)
-    task = decode_options.get("task", "transcribe")
-    tokenizers = {}
-
-    def tokenizer_for(code):   # (the special tokens but the language's own are the same in every language)
-        if code not in tokenizers:
-            tokenizers[code] = get_tokenizer(model.is_multilingual, language=code, task=task, vocab_path=vocab_path)
-        return tokenizers[code]
-
-    prompt_tokens = []
-    if initial_prompt is not None:
-        prompt_tokens = decoding._text_tokens(tokenizer_for(None if auto else language), initial_prompt,
-                                              decoding.DecodingOptions(vocab_path=vocab_path), "initial_prompt")
-    state_left = [None]   # rows of the encoded, undecoded state the engine's own detection left behind, for the decode that comes next
-
-    if auto and detect_languages is None and model.is_multilingual:
-        det_tok = get_tokenizer(True, num_languages=99)   # the numbering the decode tokenizer uses
-
-        def detect_languages(mel_windows):
-            tokens, probs = decoding.detect_language(model, mel_windows, det_tok)
-            state_left[0] = len(probs)
-            codes = [det_tok.all_language_codes[int(t) - det_tok.all_language_tokens[0]] for t in tokens]
-            return codes, [p[c] for c, p in zip(codes, probs)]
-
-    def engine_decode(code):
-        def options(prompt):
-            return decoding.DecodingOptions(language=code, temperature=0.0, prompt=list(prompt) or None, vocab_path=vocab_path, **decode_options)
-
-        def run(mel_windows, prompts):
-            if state_left[0] == len(prompts):   # the first round of a group that detection found in one language: its state is waiting
-                state_left[0] = None
-                rows = options(prompts[0]) if len(prompts) == 1 else [options(p) for p in prompts]   # (one row: the uniform decode, as below)
-                return decoding.decode(model, None, rows, encoded_batch=len(prompts), want_text=vocab_path is not None)
-            state_left[0] = None
-            if len(prompts) == 1:   # a single row (transcribe(), or the last recording of a group): a uniform decode of one window
-                return [decoding.decode(model, mel_windows[0], options(prompts[0]), want_text=vocab_path is not None)]
-            return decoding.decode(model, mel_windows, [options(p) for p in prompts], want_text=vocab_path is not None)
-        return run
-
-    decode_text = (lambda tok: tok.decode) if vocab_path is not None else (lambda tok: (lambda toks: None))
+    seek = dict(condition_on_previous_text=condition_on_previous_text, no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold)
+    words = dict(aligned_unit_type=aligned_unit_type, aggr=aggr, topk=topk, medfilt_width=medfilt_width, w_colnorm=w_colnorm,
+                 w_rownorm=w_rownorm, w_coverage=w_coverage, word_confidence=word_confidence) if word_timestamps else None
+    call = _Call(model, language, initial_prompt, vocab_path, decode_options, decode_windows, detect_languages, seek, words)
     audios = list(audios)
-    rates = [int(r) for r in sample_rate] if isinstance(sample_rate, (list, tuple)) else [int(sample_rate)] * len(audios)
-    if len(rates) != len(audios):
-        raise ValueError("sample_rate lists %d rates for %d recordings" % (len(rates), len(audios)))
     results = [None] * len(audios)
-
-    def plan(mel):
-        """What one recording contributes to the lock-step loop: "clips", one SeekState(clips=...) argument per decode row it takes, and
-        "pieces", the result's entry (None unless pieces were asked for)."""
-        content = mel.shape[1] - N_FRAMES
-        if clip_timestamps is not None:
-            return {"clips": [clip_frames(clip_timestamps, content)], "pieces": None}
-        if pieces is None:
-            return {"clips": [None], "pieces": None}
-        n, radius = plan_pieces(content, pieces, max_batch)
-        cuts, levels = model.quiet_cuts(mel, n, radius=radius) if n > 1 else ([0, content], [])
-        levels = [None, *levels]
-        return {"clips": [[(cuts[k], cuts[k + 1])] for k in range(n)] if n > 1 else [None],   # (not split: the plain loop, as without pieces)
-                "pieces": [{"start_frame": cuts[k], "stop_frame": cuts[k + 1], "level": levels[k]} for k in range(n)]}
-
-    def lock_step(rows, code, mels, extra, plans):
-        """The lock-step loop over the recordings `rows` of a group, all in language `code`; fills their results. A recording takes one
-        decode row per entry of its plan's "clips" (one, unless it is cut into pieces)."""
-        tokenizer = tokenizer_for(code)
-        decode_rows = decode_windows if decode_windows is not None else engine_decode(code)
-        align = None
-        if word_timestamps:
-            align = make_aligner(model, tokenizer, aligned_unit_type=aligned_unit_type, aggr=aggr, topk=topk, medfilt_width=medfilt_width,
-                                 w_colnorm=w_colnorm, w_rownorm=w_rownorm, w_coverage=w_coverage, word_confidence=word_confidence)
-        states = {(i, k): SeekState(mels[i].shape[1], tokenizer, initial_prompt_tokens=prompt_tokens,
-                                    condition_on_previous_text=condition_on_previous_text, no_speech_threshold=no_speech_threshold,
-                                    logprob_threshold=logprob_threshold, decode_text=decode_text(tokenizer), clips=clips)
-                  for i in rows for k, clips in enumerate(plans[i]["clips"])}   # (in recording, then piece order)
-        while True:
-            live = [u for u in states if not states[u].done]   # a finished recording (or piece) is never decoded again
-            if not live:
-                break
-            requests = [states[u].request() for u in live]
-            windows = []
-            for i in rows:   # one window cut per recording: its rows are windows of the same long mel
-                mine = [(seek, size) for u, (seek, size, _) in zip(live, requests) if u[0] == i]
-                if len(mine) == 1:
-                    windows.append(model.mel_window(mels[i], *mine[0])[None])   # (one row: a view, no copy)
-                elif mine:
-                    windows.append(model.mel_window(mels[i], [seek for seek, _ in mine], [size for _, size in mine]))
-            windows = torch.cat(windows) if len(windows) > 1 else windows[0]
-            decoded = decode_rows(windows, [prompt for _, _, prompt in requests])
-            pending = [states[i].receive(r) for i, r in zip(live, decoded)]
-            if align is not None and len(live) == 1:
-                aligned = [align(*pending[0]) if pending[0] is not None else None]
-            elif align is not None:
-                aligned = align.align_round(pending)
-            else:
-                aligned = [None] * len(live)
-            for i, pend, al in zip(live, pending, aligned):
-                if pend is not None:
-                    states[i].commit(al)
-        for i in rows:   # a recording's pieces are merged in order (one piece: the state's own result)
-            outs = [states[(i, k)].result() for k in range(len(plans[i]["clips"]))]
-            segments, windows = [], []
-            for k, out in enumerate(outs):
-                for seg in out["segments"]:
-                    seg["id"] = len(segments)
-                    segments.append(seg)
-                for w in out["windows"]:
-                    if plans[i]["pieces"] is not None:
-                        w["piece"] = k
-                    windows.append(w)
-            tokens = [t for out in outs for t in out["tokens"][len(prompt_tokens):]]
-            results[i] = {"text": tokenizer.decode(tokens) if vocab_path is not None else "", "segments": segments, "language": code,
-                          **extra.get(i, {}), "windows": windows, "windows_without_words": sum(out["windows_without_words"] for out in outs)}
-            if plans[i]["pieces"] is not None:
-                results[i]["pieces"] = plans[i]["pieces"]
-
-    ready = {}   # recording -> (log-mel, plan), computed when its group is formed -- or one recording ahead, where the rows it takes
-                 # depend on its length (pieces="auto")
-
-    def prepare(i):
-        if i not in ready:
-            mel = model.log_mel_long(_as_pcm(audios[i], model, rates[i]))
-            ready[i] = (mel, plan(mel))
-        return ready[i]
-
-    def rows_of(i):   # decode rows recording i takes in a round
-        if pieces is None:
-            return 1
-        return len(prepare(i)[1]["clips"]) if isinstance(pieces, str) else int(pieces)
-
-    g0 = 0
-    while g0 < len(audios):
-        group, used = [], 0
-        while g0 < len(audios) and (not group or used + rows_of(g0) <= max_batch):   # (without pieces: max_batch recordings)
-            used += rows_of(g0)
-            group.append(g0)
-            g0 += 1
-        mels, plans = {}, {}
-        for i in group:
-            mels[i], plans[i] = prepare(i)
-            del ready[i]
-        if not auto:
-            lock_step(group, language, mels, {}, plans)
-            continue
-        codes, extra = {i: None for i in group}, {i: {"language_probability": None} for i in group}
-        heard = [i for i in group if mels[i].shape[1] > N_FRAMES]   # recordings that have a first window
-        if detect_languages is None:   # an English-only model: "en" without a detection pass, as upstream
-            codes.update({i: "en" for i in heard})
-        elif heard:
-            first = [model.mel_window(mels[i], 0, min(N_FRAMES, mels[i].shape[1] - N_FRAMES)) for i in heard]
-            found, probs = detect_languages(torch.stack(first) if len(heard) > 1 else first[0][None])
-            for i, code, prob in zip(heard, found, probs):
-                codes[i], extra[i] = code, {"language_probability": None if prob is None else float(prob)}
-        by_language = {}
-        for i in group:
-            by_language.setdefault(codes[i], []).append(i)
-        if len(by_language) != 1 or heard != group or any(plans[i]["clips"] != [None] for i in group):
-            state_left[0] = None   # the detected rows are not one decode batch: every language's first round encodes its own windows
-        for code, rows in by_language.items():
-            lock_step(rows, code, mels, extra, plans)
+    for group, mels, plans in form_groups(model, audios, sample_rates(sample_rate, len(audios)), clip_timestamps, pieces, max_batch):
+        codes, extra = detect_group(call, group, mels, plans) if call.auto else ({i: language for i in group}, {})
+        for code in dict.fromkeys(codes[i] for i in group):   # one decode cannot mix languages: the loop runs once per language
+            rows = [i for i in group if codes[i] == code]
+            states = lock_step(call, code, rows, mels, plans)
+            for i in rows:
+                outs = [states[(i, k)].result() for k in range(len(plans[i][0]))]
+                results[i] = merge_pieces(outs, plans[i][1], tokenizer=call.tokenizer_for(code) if vocab_path is not None else None,
+                                          language=code, extra=extra.get(i, {}), n_prompt=len(call.prompt_tokens))
     return results
 
 
@@ -645,9 +599,7 @@ def parse_args(argv=None):
     src.add_argument("--audio", type=str, help="one recording (WAV / SPHERE / FLAC at any rate from 2 to 384 kHz, or a raw .npy array)")
     src.add_argument("--scp", type=str, help="list of recordings: `<id> <path>` or `<path>` per line")
     p.add_argument("--output_dir", type=str, required=True)
-    p.add_argument("--model", type=str, default="medium")
-    p.add_argument("--weights", type=str, default=None, help="local openai-whisper checkpoint (.pt)")
-    p.add_argument("--random_init", action="store_true", help="seeded random weights (dry run without a checkpoint)")
+    add_model_options(p)
     p.add_argument("--vocab", type=str, default=None, help="local tiktoken vocabulary file (text output, word times)")
     p.add_argument("--language", type=str, default="en", help="a language code or name, or `auto`: detected on each recording's first window "
                    "(the detected code and its probability go into the output JSON)")
@@ -655,16 +607,7 @@ def parse_args(argv=None):
     p.add_argument("--no_condition_on_previous_text", action="store_true")
     p.add_argument("--word_timestamps", action="store_true")
     p.add_argument("--word_confidence", action="store_true")
-    p.add_argument("--medfilt_width", type=int, default=3)
-    p.add_argument("--aggr", type=str, default="topk", choices=["mean", "topk"])
-    p.add_argument("--topk", type=int, default=10)
-    p.add_argument("--aligned_unit_type", type=str, default="char", choices=["subword", "char"])
-    p.add_argument("--w_colnorm", type=float, default=1.0)
-    p.add_argument("--w_rownorm", type=float, default=1.0)
-    p.add_argument("--w_coverage", type=float, default=0.0)
-    p.add_argument("--forward_precision", type=str, default="reference", choices=["reference", "split", "f16"])
-    p.add_argument("--sample_rate", type=int, default=SAMPLE_RATE, help="rate of raw .npy arrays ([n] or [channels, n]); audio files carry their own")
-    p.add_argument("--batch", type=int, default=1, help="recordings transcribed in lock-step (transcribe_batch; the engine's max_batch)")
+    add_aligner_options(p)
     p.add_argument("--pieces", type=_pieces_arg, default=None, metavar="N|auto", help="cut every recording at quiet frames into N pieces that are "
                    "decoded side by side (auto: as many as --batch rows allow, at least 60 s each); needs --batch >= N")
     p.add_argument("--clip_timestamps", type=str, default=None, metavar="a,b,...", help="transcribe only these ranges: start,end,start,end,... in "
@@ -684,20 +627,6 @@ def _recordings(args):
     return out
 
 
-def load_model(args, device="cuda:0"):
-    from .engine import WhisperAMD, dims_for
-    if args.weights:
-        return WhisperAMD.from_checkpoint(args.weights, device=device, max_batch=max(1, args.batch), name=args.model,
-                                          precision=args.forward_precision)
-    if args.random_init:
-        from .synthetic import random_state_dict
-        dims = dims_for(args.model)
-        return WhisperAMD(dims, device=device, max_batch=max(1, args.batch),
-                          precision=args.forward_precision).load_state_dict(random_state_dict(dims, seed=0))
-    raise SystemExit("no weights: pass --weights /local/path/%s.pt (openai-whisper checkpoint; nothing is downloaded by name) "
-                     "or --random_init for a dry run" % args.model)
-
-
 def main(args, model=None):
     """Writes <output_dir>/<id>.json per recording (transcribe()'s result plus "audio"); returns the paths."""
     if args.word_timestamps and args.vocab is None:
@@ -713,30 +642,21 @@ def main(args, model=None):
     os.makedirs(args.output_dir, exist_ok=True)
     paths = []
     kw = dict(language=args.language, initial_prompt=args.initial_prompt, condition_on_previous_text=not args.no_condition_on_previous_text,
-              word_timestamps=args.word_timestamps, word_confidence=args.word_confidence, aligned_unit_type=args.aligned_unit_type,
-              aggr=args.aggr, topk=args.topk, medfilt_width=args.medfilt_width, vocab_path=args.vocab, w_colnorm=args.w_colnorm,
-              w_rownorm=args.w_rownorm, w_coverage=args.w_coverage, sample_rate=args.sample_rate)
+              word_timestamps=args.word_timestamps, word_confidence=args.word_confidence, vocab_path=args.vocab, sample_rate=args.sample_rate,
+              **{k: getattr(args, k) for k in ALIGNER_KEYWORDS})
     if args.pieces is not None or args.clip_timestamps is not None:   # (otherwise the call is what it was before either existed)
         kw.update(pieces=args.pieces, clip_timestamps=args.clip_timestamps)
-    recordings = _recordings(args)
-
-    def source(path):   # a raw array is taken at --sample_rate; a file is read, with its own rate, by transcribe
-        return np.load(path) if path.endswith(".npy") else path
-
-    def results():   # one group of --batch recordings at a time: a group's files are written before the next group starts
-        for g0 in range(0, len(recordings), args.batch):
-            group = recordings[g0:g0 + args.batch]
-            if args.batch > 1:
-                yield from zip(group, transcribe_batch(model, [source(path) for _, path in group], **kw))
-            else:
-                yield group[0], transcribe(model, source(group[0][1]), **kw)
-
-    for (rec_id, path), result in results():
-        out = os.path.join(args.output_dir, rec_id + ".json")
-        with open(out, "w") as f:
-            json.dump({"audio": path, **result}, f)
-        paths.append(out)
-        print("%s: %d segments, %d windows -> %s" % (rec_id, len(result["segments"]), len(result["windows"]), out))
+    for group in groups_of(_recordings(args), args.batch):   # a group's files are written before the next group starts
+        if args.batch > 1:
+            results = transcribe_batch(model, [source(path) for _, path in group], **kw)
+        else:
+            results = [transcribe(model, source(group[0][1]), **kw)]
+        for (rec_id, path), result in zip(group, results):
+            out = os.path.join(args.output_dir, rec_id + ".json")
+            with open(out, "w") as f:
+                json.dump({"audio": path, **result}, f)
+            paths.append(out)
+            print("%s: %d segments, %d windows -> %s" % (rec_id, len(result["segments"]), len(result["windows"]), out))
     return paths
 
 
