@@ -70,9 +70,6 @@ extern "C" {
 typedef struct wca_engine wca_engine;
 
 typedef enum {
-  WCA_STATUS_PARTITIONED = 1, /* wca_engine_set_stream on a CU-partitioned engine: the stream was RECORDED (it becomes the engine's stream
-                               * again when the partition is lifted) but phase 1 stays on its CU-masked stream, which is not ordered with
-                               * the caller's: synchronise before and after each entry point (the Python binding does) */
   WCA_OK = 0,
   WCA_ERR_INVALID = -1,   /* bad argument / shape                                  */
   WCA_ERR_TOO_LONG = -2,  /* n_tok > 448 or max_frames > 1500 (infer_ali.py:79)    */
@@ -506,7 +503,7 @@ int wca_test_gemm_ln(wca_engine* e, const void* a_f16_dev, const void* w_f16_dev
                      const float* gamma_dev, const float* beta_dev, void* xn_f16_dev, int M, int N, int K, int site);
 /* What launch_gemm would do with a GEMM C [M][N] = A [M][K] (rows lda apart) W [N][K]^T on a device of n_cu compute units (csrc/gemm_plan.cpp,
  * plan_gemm): no engine, no GPU, no HIP call. out_mode, gelu, site as GemmArgs; a_lo > 0 = pair operands; force_tile 0 auto / 64 / 128 / 256 /
- * 257 / 258 (GemmForceTile); cu_limit > 0 = the CUs of a masked stream. flags: 1 an addend, 2 batch-strided A, 4 a positional table, 8 batch-strided
+ * 257 / 258 (GemmForceTile); cu_limit > 0 = a cap on the persistent grid, for tests. flags: 1 an addend, 2 batch-strided A, 4 a positional table, 8 batch-strided
  * C, 16 out_mode 3 WITHOUT its LayerNorm buffers, 32 out_mode 4 WITHOUT c_lo; sk_bytes > 0 = a split-K workspace of that size.
  * WCA_OK and out[10] = {kernel, grid x, grid y, workgroup size, dynamic LDS, splitk, supertile, site instance, a_bytes, w_bytes} with kernel
  * 0 nothing to launch, 1 skinny, 2 128 x 128, 3 256 x 256, 4 persistent 256 x 256, 5 / 6 its pair forms on two-slot rings / three A slots,
@@ -515,7 +512,7 @@ int wca_test_gemm_plan(int M, int N, int K, int lda, int out_mode, int gelu, int
                        int64_t sk_bytes, int32_t* out);
 /* wca_test_gemm with every field of the launch description open to the caller -- the strided and batch-strided forms the engine's forward
  * builds (csrc/engine_forward.hip: the conv stem's overlapping windows, the positional table, the pre-activation addend, pair rows,
- * a CU-partitioned stream). Logical row m = b * rows_per_batch + t of A / C lives at base + b * batch_stride + t * ld (rows_per_batch 0: flat,
+ * a capped persistent grid). Logical row m = b * rows_per_batch + t of A / C lives at base + b * batch_stride + t * ld (rows_per_batch 0: flat,
  * m * ld); a_lo > 0: A rows are [hi | lo] pairs a_lo elements apart against the plain W; c_lo: out_mode 4's distance from hi to lo;
  * addend [M][ld_addend] f32 is added before the GELU, pos [pos_period][N] f32 after it (row m takes pos[m % pos_period]); force_tile 0 / 64 /
  * 128 / 256 / 257 / 258 and out_mode 0 / 1 / 2 / 4 as wca_test_gemm_plan. plan_out[2] = {kernel (numbered as in wca_test_gemm_plan), grid x} of
@@ -666,20 +663,12 @@ int wca_get_precision(wca_engine* e);             /* F16 or SPLIT */
  * batch's phase 1; off: everything on one stream, so that rocprofv3 per-kernel durations are not inflated by sharing
  * the CUs (profiling aid; throughput drops by the overlap's worth). No batch may be in flight when it is changed. */
 int wca_set_overlap(wca_engine* e, int on);
-/* EXPERIMENT (measured in profiles/r04_cu_partition.txt, off by default): phase2_cus > 0 (a multiple of 8) gives phase 2
- * of the alignment and the greedy decode loop CU-masked streams that own that many compute units (hipExtStreamCreateWithCUMask) and phase 1
- * (log-mel, encoder, cross-K/V) the rest, its persistent GEMM grids sized to match -- so that the HBM-bound decode kernels run BESIDE
- * the MFMA-bound encoder instead of queueing behind its persistent workgroups. 0 lifts the partition (phase 1 returns to the stream the caller
- * bound last). While it is active wca_engine_set_stream records the stream and returns WCA_STATUS_PARTITIONED (the caller's stream has no
- * mask): inputs must be complete before an entry point is called. Not together with wca_set_fuse_ln (WCA_ERR_STATE). A failure while creating
- * the masked streams leaves the previous partition (or none) in place. */
-int wca_set_cu_partition(wca_engine* e, int phase2_cus);
 /* Decoder GEMMs on few rows (a greedy-decode step of wca_greedy_decode: M = batch; batch-1 teacher-forced forwards):
  * fused != 0 (default): for up to 128 rows one few-row kernel per GEMM with the LayerNorm in its prologue, the KV-cache append in its
  * epilogue and deterministic split-K for K = 4 n_state; 0: separate LayerNorm / GEMM / append launches (the round-1 path,
- * kept for A/B tests). streams: 1 (default) or 2 = the batch as two half-batches enqueued layer by layer in turn on two streams
- * (measured on MI355X: the two hardware queues' kernels run back to back rather than concurrently, 3.86 vs 3.90 ms per step).
- * Token choices are independent of both settings up to fp32 summation order in the split-K GEMM. */
+ * kept for A/B tests). streams must be 1: the form that ran the batch as two half-batches on two streams was removed (it measured no
+ * faster, HISTORY.md) and any other value is refused with WCA_ERR_INVALID; the argument stays so that existing callers keep their arity.
+ * Token choices are independent of `fused` up to fp32 summation order in the split-K GEMM. */
 int wca_set_decode_mode(wca_engine* e, int fused, int streams);
 /* enable/disable per-stage event recording (default off: no extra events on the stream) */
 int wca_set_profiling(wca_engine* e, int on);

@@ -31,6 +31,14 @@ def test_library_exports_every_declared_symbol(wca):
     assert isinstance(lib.wca_last_error(), (bytes, type(None)))
 
 
+def test_removed_cu_partition_is_not_exported(wca):
+    """The CU-partition experiment left the library: no symbol, no declaration, no binding (an old caller fails at load, not at run time)."""
+    lib = wca._lib.load()
+    assert not hasattr(lib, "wca_set_cu_partition")
+    assert "wca_set_cu_partition" not in _declared() and "wca_set_cu_partition" not in wca._lib.SIGNATURES
+    assert not hasattr(wca.WhisperAMD, "set_cu_partition")
+
+
 def test_struct_layouts_match_header(wca):
     assert ctypes.sizeof(wca._lib.ModelDims) == 10 * 4
     assert ctypes.sizeof(wca._lib.AlignOpts) == 8 * 4

@@ -162,9 +162,8 @@ def test_greedy_decode_vs_oracle(pkg, small):
 
 def test_decode_modes_agree(pkg):
     """wca_set_decode_mode: the few-row GEMM with LayerNorm prologue / KV append / split-K (fc2: K = 2048 -> 2 workgroups per
-    column group) against the separate-launch path, and the two interleaved half-batches (16 + 4 rows on two streams) against
-    one stream. Same arithmetic except the split-K summation order: the token rows must agree (up to argmax near-ties, bounded below); one / two
-    streams bit for bit."""
+    column group) against the separate-launch path. Same arithmetic except the split-K summation order: the token rows must agree
+    (up to argmax near-ties, bounded below)."""
     syn = importlib.import_module("whisper-char-alignment_amd.synthetic")
     dims = pkg.ModelDimensions(80, 1500, 512, 8, 2, 51865, 448, 512, 8, 2)
     m = pkg.WhisperAMD(dims, device="cuda:0", max_batch=20, precision="f16")
@@ -175,15 +174,13 @@ def test_decode_modes_agree(pkg):
     ns = np.full(B, 32000, np.int32)
     initial = list(tok.sot_sequence)
     out = {}
-    for mode in ((False, 1), (True, 1), (True, 2)):
+    for mode in ((False, 1), (True, 1)):
         m.set_decode_mode(*mode)
         out[mode] = m.greedy_decode(None, pcm, ns, initial, sup, blank, sample_len=sample_len, eot=tok.eot,
                                     timestamp_begin=tok.timestamp_begin, apply_timestamp_rules=True, max_initial_timestamp_index=50,
                                     no_speech=tok.no_speech) + (m.last_no_speech_prob.copy(),)
     m.set_decode_mode(True, 1)
     t1, n1, lp1, ns1 = out[(True, 1)]
-    t2, n2, lp2, ns2 = out[(True, 2)]
-    assert np.array_equal(t1, t2) and np.array_equal(n1, n2) and np.array_equal(lp1, lp2) and np.array_equal(ns1, ns2)
     t0, n0, lp0, ns0 = out[(False, 1)]
     # separate launches vs the few-row kernel: the split-K summation order differs, so an argmax near-tie of these random-weight
     # logits may fall the other way in a row (and the row then continues differently): nearly all rows must be identical, and the
@@ -207,7 +204,7 @@ def test_decode_modes_agree(pkg):
 
 
 def test_decode_stops_when_every_row_has_ended(pkg, small):
-    """The loop's early exit (every row produced EOT; checked every 4 steps) in both stream modes: with every token but EOT
+    """The loop's early exit (every row produced EOT; checked every 4 steps): with every token but EOT
     suppressed the first sampled token of every row is EOT, the rows report zero sampled tokens and the remaining positions
     are EOT-filled."""
     m, sd, dims = small
@@ -219,14 +216,34 @@ def test_decode_stops_when_every_row_has_ended(pkg, small):
     pcm = torch.from_numpy(np.stack([syn.synth_audio(70 + b, n_samples=32000) for b in range(B)])).cuda()
     ns = np.full(B, 32000, np.int32)
     initial = list(tok.sot_sequence) + [tok.no_timestamps]
-    for streams in (1, 2):
-        m.set_decode_mode(True, streams)
-        toks, n_tok, lp = m.greedy_decode(None, pcm, ns, initial, only_eot, None, sample_len=40, eot=tok.eot,
-                                          timestamp_begin=tok.timestamp_begin, apply_timestamp_rules=False, max_initial_timestamp_index=-1)
-        assert (n_tok == len(initial)).all()
-        assert (toks[:, len(initial):] == tok.eot).all()
-        assert np.allclose(lp, 0.0, atol=1e-5)      # log-softmax over a single live token
-    m.set_decode_mode(True, 1)
+    toks, n_tok, lp = m.greedy_decode(None, pcm, ns, initial, only_eot, None, sample_len=40, eot=tok.eot,
+                                      timestamp_begin=tok.timestamp_begin, apply_timestamp_rules=False, max_initial_timestamp_index=-1)
+    assert (n_tok == len(initial)).all()
+    assert (toks[:, len(initial):] == tok.eot).all()
+    assert np.allclose(lp, 0.0, atol=1e-5)      # log-softmax over a single live token
+
+
+def test_two_stream_decode_is_refused(pkg, small):
+    """wca_set_decode_mode(e, 1, 2): the two-stream form of the loop was removed, so streams = 2 is WCA_ERR_INVALID -- and the refused
+    call changes nothing: a 4-row batch decodes to the token rows of the decode made just before it."""
+    m, sd, dims = small
+    syn = importlib.import_module("whisper-char-alignment_amd.synthetic")
+    decoding, tok, opts, sup, blank = _setup(pkg, dims)
+    B = 4
+    pcm = torch.from_numpy(np.stack([syn.synth_audio(70 + b, n_samples=32000) for b in range(B)])).cuda()
+    ns = np.full(B, 32000, np.int32)
+
+    def decode():
+        return m.greedy_decode(None, pcm, ns, list(tok.sot_sequence), sup, blank, sample_len=8, eot=tok.eot, timestamp_begin=tok.timestamp_begin,
+                               apply_timestamp_rules=True, max_initial_timestamp_index=50)
+
+    toks0, n0, lp0 = decode()
+    assert m._lib.wca_set_decode_mode(m._h, 1, 2) == -1   # WCA_ERR_INVALID
+    assert b"removed" in m._lib.wca_last_error()
+    with pytest.raises(pkg._lib.WcaError, match="removed"):
+        m.set_decode_mode(True, 2)
+    toks1, n1, lp1 = decode()
+    assert np.array_equal(toks0, toks1) and np.array_equal(n0, n1) and np.array_equal(lp0, lp1)
 
 
 def test_decode_api_and_encoder_reuse(pkg, small, fake_vocab):

@@ -154,7 +154,7 @@ def _raw_decode(m, tok, dims, mel, initial, sample_len, ex):
 
 @pytest.mark.parametrize("precision", ["f16", "reference"])
 def test_prefill_matches_stepwise(pkg, tok, precision):
-    """The same prompted batch with prefill 1 and 0, from an encode_batch state, in one- and two-stream decode mode: identical
+    """The same prompted batch with prefill 1 and 0, from an encode_batch state: identical
     rows except where the first divergence is a measured logit near-tie, log-probabilities and no_speech_prob within the
     summation noise, and the position counts show which path ran."""
     dims = pkg.ModelDimensions(80, 1500, 256, 4, 2, 51865, 448, 256, 4, 2)
@@ -166,38 +166,29 @@ def test_prefill_matches_stepwise(pkg, tok, precision):
     initial = [tok.sot_prev] + prompt + list(tok.sot_sequence)
     sot_index = initial.index(tok.sot)
     out = {}
-    for streams in (1, 2):
-        m.set_decode_mode(True, streams)
-        for prefill in (1, 0):
-            m.encode_batch(mel)
-            out[(streams, prefill)] = _decode(m, tok, dims, initial, sample_len, sot_index, prefill, batch=B)
-    m.set_decode_mode(True, 1)
-    n_init = len(initial)
-    for streams in (1, 2):
-        tp, npf, lpp, nsp_p, pos_p = out[(streams, 1)]
-        ts, nst, lps, nsp_s, pos_s = out[(streams, 0)]
-        # the prefill fed every initial position at once (its first choice included), the stepwise path one at a time
-        assert pos_p[0] == n_init and 0 <= pos_p[1] <= sample_len - 1, pos_p
-        assert pos_s[0] == 0 and pos_s[1] >= n_init, pos_s
-        same = np.array([np.array_equal(tp[b], ts[b]) and npf[b] == nst[b] for b in range(B)])
-        assert same.mean() >= 0.75, same
-        for b in np.nonzero(~same)[0]:
-            p_ = int(np.nonzero(tp[b] != ts[b])[0][0])
-            assert p_ >= n_init, (b, p_)
-            _w, logits = m.get_attentions(mel[b:b + 1], torch.from_numpy(tp[b][:p_].astype(np.int64))[None].cuda(), [100], 3, 1.0)
-            row = logits[0, p_ - 1].float().cpu().numpy()
-            gap = abs(float(row[tp[b][p_]]) - float(row[ts[b][p_]]))
-            print("prefill vs stepwise (%s, %d streams): row %d diverges at %d: %d / %d, logit gap %.2e" % (precision, streams, b, p_, tp[b][p_],
-                                                                                                     ts[b][p_], gap))
-            assert gap < 2e-2, (b, p_, gap)
-        print("prefill vs stepwise (%s, %d streams): %d/%d rows identical, max |d sum_logprob| %.2e, max |d no_speech| %.2e" % (
-            precision, streams, same.sum(), B, np.abs(lpp - lps)[same].max(), np.abs(nsp_p - nsp_s).max()))
-        np.testing.assert_allclose(lpp[same], lps[same], rtol=1e-3, atol=1e-2)
-        np.testing.assert_allclose(nsp_p, nsp_s, rtol=2e-2, atol=1e-7)
-    # one stream and two streams: the same arithmetic per row, bit for bit
     for prefill in (1, 0):
-        a, b_ = out[(1, prefill)], out[(2, prefill)]
-        assert all(np.array_equal(x, y) for x, y in zip(a[:4], b_[:4]))
+        m.encode_batch(mel)
+        out[prefill] = _decode(m, tok, dims, initial, sample_len, sot_index, prefill, batch=B)
+    n_init = len(initial)
+    tp, npf, lpp, nsp_p, pos_p = out[1]
+    ts, nst, lps, nsp_s, pos_s = out[0]
+    # the prefill fed every initial position at once (its first choice included), the stepwise path one at a time
+    assert pos_p[0] == n_init and 0 <= pos_p[1] <= sample_len - 1, pos_p
+    assert pos_s[0] == 0 and pos_s[1] >= n_init, pos_s
+    same = np.array([np.array_equal(tp[b], ts[b]) and npf[b] == nst[b] for b in range(B)])
+    assert same.mean() >= 0.75, same
+    for b in np.nonzero(~same)[0]:
+        p_ = int(np.nonzero(tp[b] != ts[b])[0][0])
+        assert p_ >= n_init, (b, p_)
+        _w, logits = m.get_attentions(mel[b:b + 1], torch.from_numpy(tp[b][:p_].astype(np.int64))[None].cuda(), [100], 3, 1.0)
+        row = logits[0, p_ - 1].float().cpu().numpy()
+        gap = abs(float(row[tp[b][p_]]) - float(row[ts[b][p_]]))
+        print("prefill vs stepwise (%s): row %d diverges at %d: %d / %d, logit gap %.2e" % (precision, b, p_, tp[b][p_], ts[b][p_], gap))
+        assert gap < 2e-2, (b, p_, gap)
+    print("prefill vs stepwise (%s): %d/%d rows identical, max |d sum_logprob| %.2e, max |d no_speech| %.2e" % (
+        precision, same.sum(), B, np.abs(lpp - lps)[same].max(), np.abs(nsp_p - nsp_s).max()))
+    np.testing.assert_allclose(lpp[same], lps[same], rtol=1e-3, atol=1e-2)
+    np.testing.assert_allclose(nsp_p, nsp_s, rtol=2e-2, atol=1e-7)
 
 
 def test_length_edge_and_bounds(pkg, small, tok):

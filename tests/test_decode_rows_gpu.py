@@ -1,7 +1,7 @@
 """Greedy decode with per-row prompts on the MI355X (wca_greedy_decode_rows): the rows of one batch sit at different decoder
 positions. The per-row kernel forms against the uniform kernels they were derived from (bit for bit), the whole loop against
 wca_greedy_decode_ex (equal lengths: bit for bit; ragged: every row against the same utterance decoded alone), per-row sample
-budgets, the two-stream mode and the refusals. Small dims, like the `small` fixture of test_decode_gpu.py."""
+budgets and the refusals. Small dims, like the `small` fixture of test_decode_gpu.py."""
 import ctypes as C
 import importlib
 
@@ -275,34 +275,6 @@ def test_per_row_sample_caps(small, tok, mel4):
     t2, n2, lp2, _ = _alone(m, tok, dims, mel4[1:2], lengths[1], 8)
     if _same_or_near_tie(m, mel4[1:2], lengths[1], toks[1], n_tok[1], t2[0], n2[0], "caps row 1"):
         np.testing.assert_allclose(lp[1], lp2[0], rtol=1e-4, atol=1e-4)
-
-
-@pytest.fixture(scope="module")
-def wide20(pkg):
-    dims = pkg.ModelDimensions(80, 1500, 512, 8, 2, 51865, 448, 512, 8, 2)
-    m = pkg.WhisperAMD(dims, device="cuda:0", max_batch=20, precision="f16")
-    m.load_state_dict(_m("synthetic").random_state_dict(dims, seed=11))
-    return m, dims, _mels(m, range(40, 60), n_samples=32000)
-
-
-@pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
-def test_two_streams_agree_bit_for_bit(wide20, tok, fused):
-    """The 512-wide dimensions and B = 20 of test_decode_modes_agree (16 + 4 rows on two streams), prompt lengths cycling through
-    0, 7, 30, 101: one and two streams give the same arithmetic per row. Unfused, the second half-batch appends its K/V through
-    kv_append_rows_kernel at an offset into the position tables: the only path that reads them there."""
-    m, dims, mel = wide20
-    B = 20
-    lengths = [3 if p == 0 else 4 + p for p in [(0, 7, 30, 101)[b % 4] for b in range(B)]]
-    out = {}
-    try:
-        for streams in (1, 2):
-            m.set_decode_mode(fused, streams)
-            out[streams] = _rows(m, tok, dims, mel, lengths, 6)
-    finally:
-        m.set_decode_mode(True, 1)
-    for a, b in zip(out[1], out[2]):
-        assert np.array_equal(a, b)
-    assert np.isfinite(out[1][2]).all() and np.isfinite(out[1][3]).all()
 
 
 def test_refusals_leave_the_engine_usable(small, tok, mel4):

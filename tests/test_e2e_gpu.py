@@ -139,68 +139,29 @@ def test_align_batch_matches_stepwise_api(wca, setup):
         assert (w1 - w).abs().max().item() < 1e-3
 
 
-def test_cu_partition_changes_nothing_but_the_streams(wca, setup):
-    """wca_set_cu_partition (the co-scheduling experiment, profiles/r04_cu_partition.txt): phase 2 on CU-masked streams owning 64 CUs,
-    phase 1 on the rest with its persistent GEMM grids sized to match -- the results must be those of the unpartitioned engine bit for
-    bit (same kernels, same arithmetic, another workgroup -> tile walk), two batches in flight included; 0 lifts it; bad sizes are refused."""
+def test_engine_runs_on_torchs_current_stream(wca, setup):
+    """The engine runs on TORCH'S CURRENT stream, not on a private non-blocking one: an entry point with device-side outputs and no
+    trailing sync (log_mel) must be ordered with torch work on a side stream -- the producer of its input is delayed by a long torch
+    kernel on that stream, the consumer follows immediately."""
     syn, tk, rt, tm, audio = _mods()
     dims, sd, model, tok = setup
-    specs = [(41, 48000, 25), (42, 80000, 40), (43, 32000, 12)]
-    utts = [_utt(syn, rt, tok, u, n, c) for u, n, c in specs]
-    n_max, smax = max(len(u[3]) for u in utts), max(len(u[0]) for u in utts)
-    pcm = np.zeros((3, smax), dtype=np.float32)
-    tarr = np.full((3, n_max), tok.eot, dtype=np.int64)
-    for i, (p, _, _, toks) in enumerate(utts):
-        pcm[i, :len(p)] = p
-        tarr[i, :len(toks)] = toks
-    args = (torch.from_numpy(pcm).cuda(), [len(u[0]) for u in utts], torch.from_numpy(tarr).cuda(), [len(u[3]) for u in utts],
-            [len(u[0]) // 320 for u in utts], model.make_opts(aggregation="topk", topk=4, sot_len=3, medfilt_width=3))
-    jump0, sel0 = model.align_batch(*args)
-    try:
-        model.set_cu_partition(64)
-        jump1, sel1 = model.align_batch(*args)
-        model.align_batch(*args, enqueue_only=True)      # two in flight on the masked streams
-        model.align_batch(*args, enqueue_only=True)
-        j2, s2 = model.fetch(3, n_max, args[5])
-        j3, s3 = model.fetch(3, n_max, args[5])
-        with pytest.raises(RuntimeError):
-            model.set_cu_partition(65)                    # a multiple of 8 below the CU count
-    finally:
-        model.set_cu_partition(0)
-    jump4, sel4 = model.align_batch(*args)
-    for j, s_ in ((jump1, sel1), (j2, s2), (j3, s3), (jump4, sel4)):
-        assert np.array_equal(j, jump0) and np.array_equal(s_, sel0)
-    # ADVICE r4 (medium): after the lift the engine runs on TORCH'S CURRENT stream again, not on its private non-blocking one -- an entry
-    # point with device-side outputs and no trailing sync (log_mel) must be ordered with torch work on a side stream: the producer of its
-    # input is delayed by a long torch kernel on that stream, the consumer follows immediately
+    p = syn.synth_audio(41, 48000)
+    smax = 80000
+    pcm = np.zeros((1, smax), dtype=np.float32)
+    pcm[0, :len(p)] = p
     side = torch.cuda.Stream()
-    ref = model.log_mel(torch.from_numpy(pcm[:1]).cuda(), [len(utts[0][0])]).clone()
+    ref = model.log_mel(torch.from_numpy(pcm).cuda(), [len(p)]).clone()
     torch.cuda.synchronize()
     with torch.cuda.stream(side):
         big = torch.randn(4096, 4096, device="cuda")
         for _ in range(20):
             big = big @ big * 1e-3                 # ~100 ms of queued work ahead of the copy below
         x = torch.zeros(1, smax, device="cuda")
-        x.copy_(torch.from_numpy(pcm[:1]).cuda(), non_blocking=True)
-        got = model.log_mel(x, [len(utts[0][0])])   # reads x on `side` (the bound stream): must see the copy
+        x.copy_(torch.from_numpy(pcm).cuda(), non_blocking=True)
+        got = model.log_mel(x, [len(p)])            # reads x on `side` (the bound stream): must see the copy
         out = got.clone()
     side.synchronize()
     assert torch.equal(out, ref)
-    # while a partition is active a foreign stream is only recorded (WCA_STATUS_PARTITIONED), and fuse_ln is refused together with it
-    model.set_cu_partition(64)
-    try:
-        with pytest.raises(wca._lib.WcaError, match="partitioned"):
-            model.set_fuse_ln(True)
-        with torch.cuda.stream(side):
-            got2 = model.log_mel(x, [len(utts[0][0])]).clone()
-        side.synchronize()
-        assert torch.equal(got2, ref)
-    finally:
-        model.set_cu_partition(0)
-    model.set_fuse_ln(True)
-    with pytest.raises(wca._lib.WcaError, match="every CU"):
-        model.set_cu_partition(64)
-    model.set_fuse_ln(False)
 
 
 def test_too_long_is_rejected(wca, setup):

@@ -350,10 +350,10 @@ def test_skinny_kernel_with_batch_strided_output(eng, lib, wca):
         assert bool((ch[mask] == sent).all())
 
 
-# ------------------------------------------------------------------------------- a CU-partitioned stream
+# ------------------------------------------------------------------------------- a capped persistent grid (cu_limit)
 @pytest.mark.parametrize("K,walks", [(128, True), (192, False)])
 def test_persistent_grid_of_a_cu_partition(eng, lib, wca, K, walks):
-    """wca_set_cu_partition gives a stream a few CUs and every GEMM on it cu_limit: the persistent grid shrinks to it and a workgroup walks
+    """cu_limit caps the persistent grid (a test knob since the CU-partition experiment left the engine): the grid shrinks to it and a workgroup walks
     several tiles (an even number of K tiles), or keeps one tile per workgroup (an odd number: the ring parity does not carry over). 8 tiles,
     ragged in M and N; cu_limit 1, 3, 5: the bits of the unrestricted launch, which is within tolerance of float64."""
     M, N = 500, 1000

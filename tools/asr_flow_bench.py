@@ -8,8 +8,7 @@ With seeded random weights the decoder never emits <|endoftext|> by itself, so t
 (EOT suppressed): a 64-character English sentence is 16-24 Whisper BPE tokens (+ 2 timestamp tokens); the teacher text that is
 aligned afterwards is the synthetic 64-character text of bench.py (the decoded ids are noise). Reports utterances/s and the
 split decode / align per batch.  usage: asr_flow_bench.py [B] [steps] [tokens,tokens,...]
-Environment: WCA_PRECISION=f16|reference (default f16: round 3's record was taken in it); WCA_PART_CUS=32,64,... repeats the whole
-measurement with the engine's CU partition (wca_set_cu_partition: phase 2 + decode loop on that many CUs, phase 1 on the rest)."""
+Environment: WCA_PRECISION=f16|reference (default f16: round 3's record was taken in it)."""
 import importlib
 import os
 import sys
@@ -117,8 +116,4 @@ def measure():
                                                t_dec * 1e3 / steps / (sample_len + len(initial) - 1), (dt - t_dec) * 1e3 / steps, B * steps / dt), flush=True)
 
 
-for part in [0] + [int(x) for x in os.environ.get("WCA_PART_CUS", "").split(",") if x]:
-    m.set_cu_partition(part)
-    print("---- CU partition: %s" % ("off (every stream may use all %d CUs)" % 256 if part == 0 else "phase 2 / decode loop on %d CUs, phase 1 on the rest" % part), flush=True)
-    measure()
-m.set_cu_partition(0)
+measure()

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Greedy ASR pre-pass (wca_greedy_decode) at the bench's model / batch: ms per autoregressive step with the encoder state
-already queued (wca_encode_batch), so that only the KV-cached loop is timed.  usage: decode_bench.py [B] [sample_len] [rounds]"""
+already queued (wca_encode_batch), so that only the KV-cached loop is timed.  usage: decode_bench.py [B] [sample_len] [rounds]
+Environment: WCA_DEC_MODES=0,1 (default): separate launches, then the fused few-row GEMMs (wca_set_decode_mode)."""
 import importlib
 import os
 import sys
@@ -30,10 +31,9 @@ pcm = torch.from_numpy(np.stack([syn.synth_audio(b, 160000) for b in range(B)]))
 ns = np.full(B, 160000, np.int32)
 kw = dict(sample_len=sample_len, eot=tok.eot, timestamp_begin=tok.timestamp_begin, apply_timestamp_rules=True,
           max_initial_timestamp_index=50)
-modes = [(bool(int(x.split(":")[0])), int(x.split(":")[1])) for x in os.environ.get("WCA_DEC_MODES", "0:1,0:2,1:1,1:2").split(",")]
-for mode in modes:
-  m.set_decode_mode(*mode)
-  print("decode mode: fused=%s streams=%d" % mode, flush=True)
+for fused in [bool(int(x)) for x in os.environ.get("WCA_DEC_MODES", "0,1").split(",")]:   # fused few-row GEMMs (1) / separate launches (0)
+  m.set_decode_mode(fused)
+  print("decode mode: fused=%s" % fused, flush=True)
   for r in range(rounds + 1):
     m.encode_batch(pcm=pcm, n_samples=ns)
     torch.cuda.synchronize()

@@ -4,12 +4,12 @@ of this tree: a refactor of the decode path runs this in the tree before and in 
 
   * uniform decode (wca_greedy_decode / _ex): the plain start, and a 12-token prompt with prefill 0 and 1
   * ragged per-row decode (wca_greedy_decode_rows) with per-row budgets, in both precision modes
-    each fused and unfused, on one and on two streams, B = 20 at 512-wide dims (16 + 4 rows on two streams):
+    each fused and unfused, B = 20 at 512-wide dims:
     tokens, n_tokens, sum_logprob, no_speech_prob
   * get_attentions weights and logits of a ragged batch of 3 in both precision modes (the teacher-forced decoder)
   * transcribe of two synthetic recordings (45 s and 70 s) alone and as a transcribe_batch, word_timestamps=True, on a synthetic vocabulary
 
-usage: decode_dump.py OUTDIR [one-stream]     one-stream: one decode stream and set_overlap(0) only, for an ordered kernel trace"""
+usage: decode_dump.py OUTDIR [one-stream]     one-stream: set_overlap(0), for an ordered kernel trace"""
 import base64
 import importlib
 import json
@@ -75,16 +75,15 @@ for b, r in enumerate(att_rows):
 for precision in ("f16", "reference"):
     m.set_precision(precision)
     for fused in (True, False):
-        for streams in (1,) if one_stream else (1, 2):
-            m.set_decode_mode(fused, streams)
-            tag = "%s.%s.streams%d" % (precision, "fused" if fused else "unfused", streams)
-            for name, n, prefill in (("plain", 3, 0), ("prompt.prefill0", 12, 0), ("prompt.prefill1", 12, 1)) if precision == "f16" else ():
-                init, sot_index = initial(n)
-                out = m.greedy_decode(mel, None, None, init, sup, blank, sample_len=10, sot_index=sot_index, prefill=prefill, **kw)
-                save("uniform.%s.%s" % (name, tag), out + (m.last_no_speech_prob,))
-            out = m.greedy_decode_rows(mel, None, None, [p[0] for p in plans], [p[1] for p in plans], budgets, sup, blank, **kw)
-            save("rows.%s" % tag, out + (m.last_no_speech_prob,))
-    m.set_decode_mode(True, 1)
+        m.set_decode_mode(fused)
+        tag = "%s.%s" % (precision, "fused" if fused else "unfused")
+        for name, n, prefill in (("plain", 3, 0), ("prompt.prefill0", 12, 0), ("prompt.prefill1", 12, 1)) if precision == "f16" else ():
+            init, sot_index = initial(n)
+            out = m.greedy_decode(mel, None, None, init, sup, blank, sample_len=10, sot_index=sot_index, prefill=prefill, **kw)
+            save("uniform.%s.%s" % (name, tag), out + (m.last_no_speech_prob,))
+        out = m.greedy_decode_rows(mel, None, None, [p[0] for p in plans], [p[1] for p in plans], budgets, sup, blank, **kw)
+        save("rows.%s" % tag, out + (m.last_no_speech_prob,))
+    m.set_decode_mode(True)
     save("attentions.%s" % precision, m.get_attentions(mel[:3], att_tokens, [100, 80, 60], 3, 1.0, n_tok=[len(r) for r in att_rows]),
          keys=("weights", "logits"))
 

@@ -71,13 +71,11 @@ static size_t layout_arena(wca_engine* e, char* base) {
     const int s_max = std::max(std::max(gemm_rows_pick_splitk((int)dt), gemm_rows_pick_splitk((int)(4 * dt))), 1);
     e->sk_tiles = (size_t)(DEC_ROWS_MAX / 64) * ((dt + 15) / 16);
     e->sk_floats = e->sk_tiles * s_max * 64 * 16;
-    for (int i = 0; i < 2; ++i) {
-      e->sk_part[i] = carve<float>(cur, e->sk_floats);
-      e->sk_cnt[i] = carve<unsigned>(cur, e->sk_tiles + 16, 256);
-    }
+    e->sk_part = carve<float>(cur, e->sk_floats);
+    e->sk_cnt = carve<unsigned>(cur, e->sk_tiles + 16, 256);
     // 128 x 128 tile GEMM with at most n_cu / 2 = 128 tiles, 4 K slices of f32 partials
     e->sk_big_bytes = (size_t)4 * 128 * 128 * 128 * sizeof(float);
-    for (int i = 0; i < 3; ++i) e->sk_big[i] = carve<float>(cur, e->sk_big_bytes / sizeof(float));
+    for (float*& p : e->sk_big) p = carve<float>(cur, e->sk_big_bytes / sizeof(float));
   }
   return (size_t)(cur - base) + 4096;
 }
@@ -140,7 +138,7 @@ int take_kv_slot(wca_engine* e) {
 extern "C" {
 
 const char* wca_last_error(void) { return g_err.c_str(); }
-int wca_version(void) { return 15; }   // 15: wca_quiet_cuts (the quietest even frame near each equal share of a long recording); 14: open-end DTW (wca_dtw_open, wca_dtw_batch_dev_open, wca_align_batch_enqueue_open / _fetch_open); 13: wca_detect_language (language identification on the state a decode then takes); 12: wca_resample_plan / wca_resample_table / wca_resample_16k (polyphase resampler to 16 kHz); 11: wca_greedy_decode_rows (per-row initial tokens / sample budgets: the rows of a batch at different decoder positions); 10: wca_log_mel_long / wca_mel_window (whole-recording log-mel, window cut); 9: the two diagnostic stamp entry points removed, no switch read from the environment; 8: prompted greedy decode (wca_greedy_decode_ex, batched prefill); 7: two precision modes only (the per-stage precision mask, its setter / getter and the mixed
+int wca_version(void) { return 16; }   // 16: the CU-partition and two-stream decode experiments removed (HISTORY.md; wca_set_decode_mode refuses streams != 1); 15: wca_quiet_cuts (the quietest even frame near each equal share of a long recording); 14: open-end DTW (wca_dtw_open, wca_dtw_batch_dev_open, wca_align_batch_enqueue_open / _fetch_open); 13: wca_detect_language (language identification on the state a decode then takes); 12: wca_resample_plan / wca_resample_table / wca_resample_16k (polyphase resampler to 16 kHz); 11: wca_greedy_decode_rows (per-row initial tokens / sample budgets: the rows of a batch at different decoder positions); 10: wca_log_mel_long / wca_mel_window (whole-recording log-mel, window cut); 9: the two diagnostic stamp entry points removed, no switch read from the environment; 8: prompted greedy decode (wca_greedy_decode_ex, batched prefill); 7: two precision modes only (the per-stage precision mask, its setter / getter and the mixed
                                       // state are gone); 6: teacher-token log-probs (wca_align_batch_enqueue_ex / _fetch_ex, wca_token_logprobs);
                                       // 5: a new engine is in the contract mode; wca_engine_create_ex, W_lo slab, switch table
 
@@ -170,9 +168,6 @@ int wca_engine_create_ex(const wca_model_dims* dims, int device_ordinal, int max
   HIPCHK(hipDeviceGetAttribute(&e->n_cu, hipDeviceAttributeMultiprocessorCount, device_ordinal));
   HIPCHK(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
   HIPCHK(hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking));
-  HIPCHK(hipStreamCreateWithFlags(&e->stream3, hipStreamNonBlocking));
-  HIPCHK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
   e->stream = e->own_stream;
   for (auto& ev : e->ev_kv) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   e->wslab_bytes = layout_weights(e, nullptr);
@@ -220,11 +215,6 @@ void wca_engine_destroy(wca_engine* e) {
   if (!e) return;
   (void)hipSetDevice(e->device);
   (void)hipDeviceSynchronize();
-  if (e->part_s1) {
-    e->enq_count = e->fetch_count;
-    e->enc_q.clear();
-    (void)wca_set_cu_partition(e, 0);
-  }
   for (GrowBuf* g : {&e->cap, &e->wws, &e->colnorm, &e->scores, &e->sel, &e->selsc, &e->matrix, &e->trace, &e->path, &e->pathlen,
                      &e->jump, &e->tmp0, &e->tmp1})
     g->release();
@@ -265,9 +255,6 @@ void wca_engine_destroy(wca_engine* e) {
   }
   for (auto& ev : e->ev_kv)
     if (ev) (void)hipEventDestroy(ev);
-  if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-  if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-  if (e->stream3) (void)hipStreamDestroy(e->stream3);
   if (e->stream2) (void)hipStreamDestroy(e->stream2);
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
   delete e;
@@ -275,12 +262,7 @@ void wca_engine_destroy(wca_engine* e) {
 
 int wca_engine_set_stream(wca_engine* e, void* hip_stream) {
   if (!e) return fail(WCA_ERR_INVALID, "null engine");
-  e->user_stream = (hipStream_t)hip_stream;  // NULL is the HIP default (null) stream, which is what torch's default stream is
-  e->user_stream_set = true;
-  // CU-partitioned engine (wca_set_cu_partition): phase 1 stays on its masked stream, which is NOT ordered with the caller's stream
-  // (WCA_STATUS_PARTITIONED tells the binding to synchronise around its calls); the stream recorded here is restored when the partition is lifted
-  if (e->part_cus > 0) return WCA_STATUS_PARTITIONED;
-  e->stream = e->user_stream;
+  e->stream = (hipStream_t)hip_stream;  // NULL is the HIP default (null) stream, which is what torch's default stream is
   return WCA_OK;
 }
 
@@ -289,15 +271,13 @@ int wca_engine_synchronize(wca_engine* e) {
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipStreamSynchronize(e->stream));
   HIPCHK(hipStreamSynchronize(e->stream2));
-  HIPCHK(hipStreamSynchronize(e->stream3));
   return WCA_OK;
 }
 
 int wca_set_decode_mode(wca_engine* e, int fused, int streams) {
   if (!e) return fail(WCA_ERR_INVALID, "null engine");
-  if (streams != 1 && streams != 2) return fail(WCA_ERR_INVALID, "streams must be 1 or 2");
+  if (streams != 1) return fail(WCA_ERR_INVALID, "streams must be 1: the two-stream form of the decode loop was removed (it measured no faster)");
   e->dec_fused = fused != 0;
-  e->dec_streams = streams;
   return WCA_OK;
 }
 
@@ -363,7 +343,6 @@ int wca_set_precision(wca_engine* e, int mode) {
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipStreamSynchronize(e->stream));
   HIPCHK(hipStreamSynchronize(e->stream2));
-  HIPCHK(hipStreamSynchronize(e->stream3));
   // The activation arena is laid out per mode (operand buffers are twice as wide in split mode) and the K-doubled weight copies
   // exist only then. Allocate the NEW arena (and copies) first; the old ones are released and the engine's state committed only
   // when both allocations succeeded, so a failed switch leaves a working engine in its previous mode.
@@ -410,58 +389,7 @@ int wca_get_precision(wca_engine* e) { return e && e->split ? WCA_PRECISION_SPLI
 
 int wca_set_fuse_ln(wca_engine* e, int on) {
   if (!e) return fail(WCA_ERR_INVALID, "null engine");
-  if (on && e->part_cus > 0)
-    return fail(WCA_ERR_STATE, "the LayerNorm epilogue fusion needs one resident workgroup per CU of the whole device: not available while the CUs are partitioned (wca_set_cu_partition)");
   e->fuse_ln = on != 0;
-  return WCA_OK;
-}
-
-int wca_set_cu_partition(wca_engine* e, int phase2_cus) {
-  if (!e) return fail(WCA_ERR_INVALID, "null engine");
-  if (phase2_cus < 0 || phase2_cus >= e->n_cu || (phase2_cus & 7)) return fail(WCA_ERR_INVALID, "phase2_cus %d: a multiple of 8 in [0, %d)", phase2_cus, e->n_cu);
-  if (e->enq_count != e->fetch_count || !e->enc_q.empty()) return fail(WCA_ERR_STATE, "fetch / consume the batches in flight before changing the CU partition");
-  if (phase2_cus > 0 && e->fuse_ln)
-    return fail(WCA_ERR_STATE, "the LayerNorm epilogue fusion (wca_set_fuse_ln) needs every CU of the device: switch it off before partitioning the CUs");
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipDeviceSynchronize());
-  // the masked streams of the NEW partition are created first and committed only when all three exist (a failure half way
-  // used to leave part_s1 set with nothing saved)
-  hipStream_t ns[3] = {nullptr, nullptr, nullptr};
-  if (phase2_cus > 0) {
-    // mask bit i = CU i of the device's enumeration; the round-robin of mask bits over the 8 XCDs gives both partitions CUs on every XCD
-    const int words = (e->n_cu + 31) / 32;
-    std::vector<uint32_t> m1(words, 0u), m2(words, 0u);
-    for (int i = 0; i < e->n_cu; ++i) (i < phase2_cus ? m2 : m1)[i >> 5] |= 1u << (i & 31);
-    for (int i = 0; i < 3; ++i) {
-      const hipError_t he = hipExtStreamCreateWithCUMask(&ns[i], (uint32_t)words, (i == 0 ? m1 : m2).data());
-      if (he != hipSuccess) {
-        for (int j = 0; j < i; ++j) (void)hipStreamDestroy(ns[j]);
-        (void)hipGetLastError();
-        return fail(WCA_ERR_HIP, "CU-masked stream %d: %s; the engine keeps its previous partition", i, hipGetErrorString(he));
-      }
-    }
-  }
-  if (e->part_s1) {   // lift the present partition: phase 1 goes back to the stream the CALLER bound (not to the engine's private one)
-    e->stream = e->user_stream_set ? e->user_stream : e->own_stream;
-    e->stream2 = e->saved_s2;
-    e->stream3 = e->saved_s3;
-    (void)hipStreamDestroy(e->part_s1);
-    (void)hipStreamDestroy(e->part_s2);
-    (void)hipStreamDestroy(e->part_s3);
-    e->part_s1 = e->part_s2 = e->part_s3 = nullptr;
-    e->saved_s2 = e->saved_s3 = nullptr;
-  }
-  e->part_cus = 0;
-  if (phase2_cus == 0) return WCA_OK;
-  e->part_s1 = ns[0];
-  e->part_s2 = ns[1];
-  e->part_s3 = ns[2];
-  e->saved_s2 = e->stream2;
-  e->saved_s3 = e->stream3;
-  e->stream = e->part_s1;   // (wca_engine_set_stream only RECORDS the caller's stream while the partition is active: that stream has no CU mask)
-  e->stream2 = e->part_s2;
-  e->stream3 = e->part_s3;
-  e->part_cus = phase2_cus;
   return WCA_OK;
 }
 

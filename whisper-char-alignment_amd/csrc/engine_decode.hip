@@ -1,8 +1,6 @@
 // libwca.so engine, greedy decode: wca_greedy_decode / _ex (every row at the same position, optional batched prefill) and
 // wca_greedy_decode_rows (per-row initial tokens and sample budgets) over one argument check, one loop and one read-back; and
 // wca_detect_language (one position and the language head on the state a decode then takes).
-#include <chrono>
-
 #include "engine_internal.h"
 
 using namespace wca;
@@ -121,10 +119,8 @@ int decode_read_back(wca_engine* e, hipStream_t s2, wca_engine::EncState* st, co
   return WCA_OK;
 }
 
-// What the loop works on, set up by decode_begin: the state to decode, the device buffers, the select arguments every step starts
-// from and the two half-batches. The batch is decoded as two half-batches on two streams (wca_set_decode_mode, batch >= 16): a step is
-// ~200 dependent launches of 5-10 us plus one HBM-bound cross-attention per layer, and the halves are independent, so one half's small
-// kernels run under the other half's cross-K/V stream. Rows never interact (per-row kernels, per-row cache planes); n_done is an atomic counter.
+// What the loop works on, set up by decode_begin: the state to decode, the device buffers and the select arguments every step starts
+// from. Rows never interact (per-row kernels, per-row cache planes); n_done is an atomic counter.
 struct DecodeLoop {
   wca_engine* e = nullptr;
   wca_engine::EncState* st = nullptr;
@@ -137,38 +133,9 @@ struct DecodeLoop {
   float* nsp = nullptr;      // no_speech_prob [batch]
   int* n_done = nullptr;     // completion counters
   DecodeSelectArgs sel{};    // whole batch; the per-step fields (cur_len ...) are the loop's
-  int n_half = 1;
-  int hb[3] = {0, 0, 0};     // half h = rows [hb[h], hb[h + 1])
-  hipStream_t hs[2] = {nullptr, nullptr};
-
-  int fork() const {   // stream3 behind what s2 holds
-    if (n_half == 2) {
-      HIPCHK(hipEventRecord(e->ev_fork, s2));
-      HIPCHK(hipStreamWaitEvent(e->stream3, e->ev_fork, 0));
-    }
-    return WCA_OK;
-  }
-  int join() const {   // s2 behind what stream3 holds
-    if (n_half == 2) {
-      HIPCHK(hipEventRecord(e->ev_join, e->stream3));
-      HIPCHK(hipStreamWaitEvent(s2, e->ev_join, 0));
-    }
-    return WCA_OK;
-  }
-  // sel for the rows from b0 on
-  DecodeSelectArgs sel_from(int b0) const {
-    DecodeSelectArgs sh = sel;
-    sh.logits = sel.logits + (size_t)b0 * V;
-    sh.tokens = sel.tokens + (size_t)b0 * T_max;
-    sh.sum_logprob = sel.sum_logprob + b0;
-    if (sel.n_initial_rows) sh.n_initial_rows = sel.n_initial_rows + b0;
-    if (sel.cap_rows) sh.cap_rows = sel.cap_rows + b0;
-    return sh;
-  }
   // whisper's loop ends when every row has produced EOT: the counter of this step, read back (a host sync; the loop asks every 4 steps:
   // a late stop only costs time, finished rows keep emitting EOT)
   int all_done(const int* counter, bool* done) const {
-    WCA_TRY(join());
     HIPCHK(hipMemcpyAsync(e->dec_done_host, counter, sizeof(int), hipMemcpyDeviceToHost, s2));
     HIPCHK(hipStreamSynchronize(s2));
     *done = e->dec_done_host[0] >= batch;
@@ -232,26 +199,11 @@ int decode_begin(wca_engine* e, const float* mel_dev, const float* pcm_dev, int6
   sel.max_initial_timestamp_index = o->max_initial_timestamp_index;
   sel.sum_logprob = sum_lp;
   sel.n_done = lp.n_done;
-  lp.n_half = (e->dec_streams == 2 && batch >= 16) ? 2 : 1;
-  lp.hb[1] = lp.n_half == 2 ? (batch / 2 + 7) / 8 * 8 : batch;
-  lp.hb[2] = batch;
-  lp.hs[0] = s2;
-  lp.hs[1] = e->stream3;
-  return WCA_OK;
-}
-
-// one position of every row through the decoder, the halves enqueued layer by layer in turn (run_decode_step)
-int decode_step(const DecodeLoop& lp, StepPos pos, bool want_logits) {
-  const int L = lp.e->dims.n_text_layer;
-  for (int phase = -1; phase <= L; ++phase)
-    for (int h = 0; h < lp.n_half; ++h)
-      WCA_TRY(run_decode_step(lp.e, lp.hs[h], h, lp.kvbuf, lp.tokens_dev, lp.hb[h], lp.hb[h + 1] - lp.hb[h], lp.batch,
-                              StepPos{pos.t, pos.rows ? pos.rows + lp.hb[h] : nullptr}, lp.T_max, want_logits, phase));
   return WCA_OK;
 }
 
 // What the loop does for a call. The first choice comes from one batched forward over n_prefill (padded) initial positions on s2 for the
-// whole batch (run_decode_prefill), and the step loop, forked only then, continues behind it; or (n_prefill = 0) the initial tokens are fed
+// whole batch (run_decode_prefill), and the step loop continues behind it; or (n_prefill = 0) the initial tokens are fed
 // one position at a time, n_warm of them before the first choice (the plain start is 3 tokens: sot, language, task). At most `budget`
 // choices. Uniform rows (tab == nullptr): every row holds n_initial tokens, choice c reads the forward of position n_initial - 1 + c, and
 // no_speech_prob is taken at position sot_index. Per-row (tab, device): the tables of wca_greedy_decode_rows say where each row is.
@@ -270,43 +222,30 @@ int decode_run(const DecodeLoop& lp, const DecodePlan& pl, const DecodeRows& r, 
   wca_engine* e = lp.e;
   const int B = lp.batch, V = lp.V;
   const float* logits = (const float*)e->dec_logits.p;
-  static const bool dbg_host = std::getenv("WCA_DEC_DEBUG") != nullptr;   // (read once)
-  double host_us = 0.0;
   int steps = 0, step_positions = 0;
-  if (!pl.n_prefill) WCA_TRY(lp.fork());
   for (int f = 0; f < pl.n_warm + pl.budget; ++f) {
     const int c = f - pl.n_warm;
     const int t = pl.n_initial - 1 - pl.n_warm + f;                                        // uniform: the position fed
     const int* row = pl.tab ? pl.tab + (size_t)(4 + 3 * c) * B : nullptr;                  // per-row: fed position, key count, cur_len of choice c
     const bool sot_logits = lp.want_nsp && !pl.n_prefill && t == pl.sot_index;             // probs_at_sot of DecodingTask._main_loop
-    auto select = [&](int b0, int nb, hipStream_t s) {
-      DecodeSelectArgs sh = lp.sel_from(b0);
-      if (row) {
-        sh.cur_len_rows = row + 2 * (size_t)B + b0;
-        sh.n_done_idx = c;
-      } else {
-        sh.cur_len = t + 1;
-      }
-      HIPCHK(launch_decode_select(sh, nb, s));
-      return (int)WCA_OK;
-    };
-    const auto h0 = std::chrono::steady_clock::now();
+    DecodeSelectArgs sel = lp.sel;
+    if (row) {
+      sel.cur_len_rows = row + 2 * (size_t)B;
+      sel.n_done_idx = c;
+    } else {
+      sel.cur_len = t + 1;
+    }
     if (pl.n_prefill && c == 0) {
       const StepPos last{pl.n_prefill - 1, pl.tab}, sot{lp.want_nsp ? pl.sot_index : -1, lp.want_nsp && pl.tab ? pl.tab + B : nullptr};
       WCA_TRY(run_decode_prefill(e, lp.s2, lp.kvbuf, lp.tokens_dev, B, pl.n_prefill, lp.T_max, last, sot));
       if (lp.want_nsp) HIPCHK(launch_token_prob(logits + (size_t)B * V, V, V, lp.no_speech, lp.nsp, B, lp.s2));
-      WCA_TRY(select(0, B, lp.s2));
-      WCA_TRY(lp.fork());
+      HIPCHK(launch_decode_select(sel, B, lp.s2));
     } else {
       ++step_positions;
-      WCA_TRY(decode_step(lp, StepPos{t, row}, c >= 0 || sot_logits));
-      for (int h = 0; h < lp.n_half; ++h) {
-        const int b0 = lp.hb[h], nb = lp.hb[h + 1] - lp.hb[h];
-        if (sot_logits) HIPCHK(launch_token_prob(logits + (size_t)b0 * V, V, V, lp.no_speech, lp.nsp + b0, nb, lp.hs[h]));
-        if (c >= 0) WCA_TRY(select(b0, nb, lp.hs[h]));
-      }
+      WCA_TRY(run_decode_step(e, lp.s2, lp.kvbuf, lp.tokens_dev, B, StepPos{t, row}, lp.T_max, c >= 0 || sot_logits));
+      if (sot_logits) HIPCHK(launch_token_prob(logits, V, V, lp.no_speech, lp.nsp, B, lp.s2));
+      if (c >= 0) HIPCHK(launch_decode_select(sel, B, lp.s2));
     }
-    if (dbg_host) host_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();
     if (c < 0) continue;
     steps = c + 1;
     if ((steps & 3) == 0 && steps < pl.budget) {
@@ -315,10 +254,6 @@ int decode_run(const DecodeLoop& lp, const DecodePlan& pl, const DecodeRows& r, 
       if (done) break;
     }
   }
-  WCA_TRY(lp.join());
-  if (dbg_host)
-    fprintf(stderr, "[wca] greedy decode: host enqueue time %.1f us per position (%d halves)\n",
-            host_us / (steps + (pl.n_prefill ? pl.n_prefill - 1 : pl.n_warm)), lp.n_half);
   WCA_TRY(decode_read_back(e, lp.s2, lp.st, r, steps, eot, tokens_out_host, n_tokens_host, sum_logprob_host,
                            lp.want_nsp ? no_speech_prob_host : nullptr));
   e->dec_prefill_positions = pl.n_prefill;
@@ -449,8 +384,7 @@ int wca_detect_language(wca_engine* e, const float* mel_dev, const float* pcm_de
   const std::vector<int32_t> init((size_t)batch, sot);
   HIPCHK(hipMemcpyAsync(tokens_dev, init.data(), sizeof(int) * init.size(), hipMemcpyHostToDevice, s2));
   HIPCHK(hipStreamSynchronize(s2));  // `init` is pageable host memory
-  for (int phase = -1; phase < L; ++phase)
-    WCA_TRY(run_decode_step(e, s2, 0, kvbuf, tokens_dev, 0, batch, batch, StepPos{0, nullptr}, T_max, false, phase));
+  WCA_TRY(run_decode_step(e, s2, kvbuf, tokens_dev, batch, StepPos{0, nullptr}, T_max, false));
   HIPCHK(launch_language_head(e->xd, e->lnf_g, e->lnf_b, e->tok_emb, batch, dt, V, lang_begin, n_lang, probs_dev, lang_dev, s2));
   // probs [batch][n_lang] f32 and lang_token [batch] int32 sit back to back: one copy
   std::vector<float> out((size_t)batch * (n_lang + 1));

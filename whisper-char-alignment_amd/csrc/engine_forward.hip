@@ -5,12 +5,6 @@
 
 using namespace wca;
 
-namespace {
-
-thread_local int g_gemm_cu_limit = 0;  // CUs owned by the stream the current phase launches on (0 = the whole device)
-
-}  // namespace
-
 namespace wca {
 
 // c_lo > 0 (split mode, f16 output): the value is stored as the pair hi at C, lo at C + c_lo (out_mode 4).
@@ -20,14 +14,12 @@ namespace wca {
 // a_lo > 0 is a candidate: plan_gemm says whether the launch as it now stands (the addend included, which the pair kernels do not take)
 // gets a pair kernel; where not, the product is the K-doubled call on w_pair.
 hipError_t gemm(wca_engine* e, hipStream_t s, Gemm g) {
-  g.cu_limit = g_gemm_cu_limit;
   if (g.c_lo > 0 && g.out_mode == 0) g.out_mode = 4;
   if (g.w_plain != nullptr && use_wlo(e) && e->wlo_bases.count(g.w_plain)) {
     // A_hi (the hi halves of the pair rows: same row and batch strides, k_plain columns) x W_lo^T ([N][k_plain])
     GemmArgs x = flat(g.A, g.lda, g.w_lo ? g.w_lo : wlo_of(e, g.w_plain), g.k_plain, g.C, g.ldc, g.M, g.N, g.k_plain);
     x.a_rows_per_batch = g.a_rows_per_batch;
     x.a_batch_stride = g.a_batch_stride;
-    x.cu_limit = g_gemm_cu_limit;
     x.site = g.site;
     x.out_mode = 2;
     if (g.out_mode != 2) {
@@ -64,8 +56,8 @@ void mark_site(wca_engine* e, hipStream_t s, int site, int li, int which) {
 // of its own. g.kv_k != nullptr (QKV projection of a decode step, N = 3 d): the k / v columns go to the self-attention cache
 // ([.][kv_tmax][d] planes) at position kv_t, or, kv_t_rows (device [M]) given, row m at its own position (StepPos{kv_t, kv_t_rows}).
 // M <= DEC_ROWS_MAX and a shape the few-row kernel takes: one launch (gemm_rows.hip); otherwise the separate LayerNorm / GEMM /
-// kv_append launches. ws = which split-K workspace (one per decode stream).
-int dec_gemm(wca_engine* e, hipStream_t s, int ws, Gemm g, half_t* xn_scratch = nullptr) {
+// kv_append launches.
+int dec_gemm(wca_engine* e, hipStream_t s, Gemm g, half_t* xn_scratch = nullptr) {
   const bool ln = g.A32 != nullptr;
   const int M = g.M, N = g.N, K = g.K, T_max = g.kv_tmax;
   const int sk = gemm_rows_pick_splitk(K);
@@ -75,8 +67,8 @@ int dec_gemm(wca_engine* e, hipStream_t s, int ws, Gemm g, half_t* xn_scratch = 
     g.lda32 = K;
     g.ln_eps = 1e-5f;
     g.splitk = sk;
-    g.sk_part = e->sk_part[ws];
-    g.sk_cnt = e->sk_cnt[ws];
+    g.sk_part = e->sk_part;
+    g.sk_cnt = e->sk_cnt;
     g.kv_bs = (long)T_max * K;
     g.kv_d = g.kv_k ? N / 3 : 0;
     if (!g.kv_k) g.kv_t_rows = nullptr;
@@ -93,7 +85,7 @@ int dec_gemm(wca_engine* e, hipStream_t s, int ws, Gemm g, half_t* xn_scratch = 
   t.gelu = g.gelu;
   t.out_mode = g.out_mode;
   t.site = g.site;
-  t.sk_part = e->sk_big[1 + ws];
+  t.sk_part = e->sk_big[1];
   t.sk_bytes = e->sk_big_bytes;
   HIPCHK(gemm(e, s, t));
   if (g.kv_k) HIPCHK(launch_kv_append(reinterpret_cast<const half_t*>(g.C), g.kv_k, g.kv_v, M, T_max, StepPos{g.kv_t, g.kv_t_rows}, N / 3, s));
@@ -277,18 +269,17 @@ int run_cross_kv(wca_engine* e, int B, half_t* kvbuf, bool skip_last_v) {
 // [fc2 + residual]. The embedding before layer 0 and the final LayerNorm + logits stay with the caller.
 struct DecPass {
   hipStream_t s;
-  int ws;                // split-K workspace (one per decode stream)
-  int B, nq, b0;         // B batch rows of nq queries each; they sit at row b0 * nq of the decoder scratch (a half-batch of the decode loop)
+  int B, nq;             // B batch rows of nq queries each
   bool pair;             // operands are [hi | lo] rows against the K-doubled weights (the teacher-forced decoder in split mode); otherwise
                          // single f16 operands on plain weights -- in split mode too (prefill and step: whisper.decode runs in fp16)
-  const half_t* kv;      // cross-K/V of batch row b0 (rows [hi | lo] in split mode; single operands read the hi halves)
-  // self-attention keys: the QKV buffer itself under the causal mask (cache == nullptr), or the cache planes [L][2][B_all][T_max][d], to
+  const half_t* kv;      // cross-K/V of the batch (rows [hi | lo] in split mode; single operands read the hi halves)
+  // self-attention keys: the QKV buffer itself under the causal mask (cache == nullptr), or the cache planes [L][2][B][T_max][d], to
   // which the QKV projection appends position pos and whose first pos + 1 slots the one query attends to. With per-row positions the key
-  // counts are the table behind the positions: a step's tables are [B_all] fed positions, then [B_all] key counts (wca_greedy_decode_rows)
+  // counts are the table behind the positions: a step's tables are [B] fed positions, then [B] key counts (wca_greedy_decode_rows)
   half_t* cache;
-  int B_all, T_max;
+  int T_max;
   StepPos pos;
-  const int* nk_rows() const { return pos.rows ? pos.rows + B_all : nullptr; }
+  const int* nk_rows() const { return pos.rows ? pos.rows + B : nullptr; }
   half_t* scatter;       // prefill: the cache planes that take each layer's K/V at positions [0, nq) (self-attention stays in place)
   float* cap;            // capture of the cross-attention logits [B][L*H][nq][Fpad] (first Fcap keys), nullable
   int Fpad, Fcap;
@@ -302,7 +293,7 @@ namespace {
 // (dec_gemm); pair operands get the LayerNorm launch with a lo half, the pair form of flat() (W2 = the [W | W] copy) and an
 // f16 result as a pair
 int dec_linear(wca_engine* e, const DecPass& p, Gemm g, const half_t* W2, half_t* xn) {
-  if (!p.pair) return dec_gemm(e, p.s, p.ws, g, xn);
+  if (!p.pair) return dec_gemm(e, p.s, g, xn);
   const bool f16_out = g.out_mode == 0;
   if (g.A32) {
     HIPCHK(launch_layernorm_f16(g.A32, g.ln_gamma, g.ln_beta, xn, g.M, g.K, 1e-5f, p.s, 2 * g.K, g.K));
@@ -314,7 +305,7 @@ int dec_linear(wca_engine* e, const DecPass& p, Gemm g, const half_t* W2, half_t
   m.out_mode = g.out_mode;
   m.site = g.site;
   m.c_lo = f16_out ? g.N : 0;
-  m.sk_part = e->sk_big[1 + p.ws];
+  m.sk_part = e->sk_big[1];
   m.sk_bytes = e->sk_big_bytes;
   HIPCHK(gemm(e, p.s, m));
   return WCA_OK;
@@ -405,20 +396,15 @@ AttnArgs cross_attn_args(const wca_engine* e, const DecPass& p, int li, const ha
 
 int run_decoder_layers(wca_engine* e, const DecPass& p) {
   const int dt = e->dims.n_text_state, L = e->dims.n_text_layer;
-  const int M = p.B * p.nq, om = p.pair ? 2 : 1;
-  const size_t r0 = (size_t)p.b0 * p.nq;   // first scratch row
-  float* xd = e->xd + r0 * dt;
-  half_t* xdn = e->xdn + r0 * om * dt;
-  half_t* qkv_d = e->qkv_d + r0 * om * 3 * dt;
-  half_t* att_d = e->att_d + r0 * om * dt;
-  half_t* q_d = e->q_d + r0 * om * dt;
-  half_t* hid_d = e->hid_d + r0 * om * 4 * dt;
+  const int M = p.B * p.nq;
+  float* xd = e->xd;
+  half_t *xdn = e->xdn, *qkv_d = e->qkv_d, *att_d = e->att_d, *q_d = e->q_d, *hid_d = e->hid_d;
   half_t* planes = p.cache ? p.cache : p.scatter;
-  const size_t plane = (size_t)p.B_all * p.T_max * dt;  // one layer's K (or V) cache
+  const size_t plane = (size_t)p.B * p.T_max * dt;  // one layer's K (or V) cache
   for (int li = p.l0; li < p.l1; ++li) {
     const LayerW& l = e->dec[li];
     const LayerW& w2 = p.pair ? e->sw.dec[li] : l;   // the [W | W] copies
-    half_t* kc = planes ? planes + (size_t)(2 * li) * plane + (size_t)p.b0 * p.T_max * dt : nullptr;
+    half_t* kc = planes ? planes + (size_t)(2 * li) * plane : nullptr;
     half_t* vc = planes ? kc + plane : nullptr;
     Gemm g = dec_flat_ln(xd, l.ln1_g, l.ln1_b, l.qkv_w, l.qkv_b, qkv_d, M, 3 * dt, dt);
     if (p.cache) {
@@ -488,38 +474,24 @@ int run_decoder(wca_engine* e, const int64_t* tokens_dev, int B, int n, float* c
   return WCA_OK;
 }
 
-// One autoregressive step of the greedy ASR pre-pass for rows [b0, b0 + B) of the batch: position pos of every row (token
-// tokens[b][pos]) through the decoder with the self-attention K/V cache (positions 0..pos), cross-attention over this batch's
-// cross-K/V; logits of that position -> e->dec_logits. `ws` = which split-K workspace (one per decode stream).
-// phase: -1 = embedding only, li in [0, L) = decoder layer li only, L = final LayerNorm + logits only, -2 = the whole step.
-// The two half-batches of wca_greedy_decode are enqueued layer by layer in turn (the queues are served in the order their
-// packets arrive: coarse enqueueing gives coarse alternation and no overlap).
-// pos.rows (a step's tables of the whole batch, already offset to row b0): row b feeds the token at its OWN position and attends to the
-// cached keys up to it (DecPass::nk_rows).
-int run_decode_step(wca_engine* e, hipStream_t s, int ws, const half_t* kvbuf, const int* tokens, int b0, int B, int B_all, StepPos pos,
-                    int T_max, bool want_logits, int phase) {
+// One autoregressive step of the greedy ASR pre-pass: position pos of every row (token tokens[b][pos]) through the decoder with the
+// self-attention K/V cache (positions 0..pos), cross-attention over this batch's cross-K/V; want_logits: the logits of that position
+// -> e->dec_logits (otherwise the step ends with the final residual stream in e->xd).
+// pos.rows (a step's tables): row b feeds the token at its OWN position and attends to the cached keys up to it (DecPass::nk_rows).
+int run_decode_step(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, StepPos pos, int T_max, bool want_logits) {
   const wca_model_dims& D = e->dims;
-  const int dt = D.n_text_state, L = D.n_text_layer;
   DecPass p{};
   p.s = s;
-  p.ws = ws;
   p.B = B;
   p.nq = 1;
-  p.b0 = b0;
-  // split mode: the cross-K/V rows are [hi | lo]; the greedy pre-pass (whisper.decode runs in fp16 itself) reads the hi halves
-  p.kv = kvbuf + (size_t)b0 * N_CTX * (e->split ? 2 : 1) * L * 2 * dt;
+  p.kv = kvbuf;   // split mode: the cross-K/V rows are [hi | lo]; the greedy pre-pass (whisper.decode runs in fp16 itself) reads the hi halves
   p.cache = (half_t*)e->dec_cache.p;
-  p.B_all = B_all;
   p.T_max = T_max;
   p.pos = pos;
-  p.l0 = phase == -2 ? 0 : phase;
-  p.l1 = phase == -2 ? L : (phase >= 0 && phase < L ? phase + 1 : phase);   // (embedding / logits phases: no layer)
-  float* xd = e->xd + (size_t)b0 * dt;
-  if (phase == -2 || phase == -1)
-    HIPCHK(launch_embed_step(tokens + (size_t)b0 * T_max, T_max, pos, e->tok_emb, e->dec_pos, xd, B, dt, D.n_vocab, s));
+  p.l1 = D.n_text_layer;
+  HIPCHK(launch_embed_step(tokens, T_max, pos, e->tok_emb, e->dec_pos, e->xd, B, D.n_text_state, D.n_vocab, s));
   WCA_TRY(run_decoder_layers(e, p));
-  if (want_logits && (phase == -2 || phase == L))
-    WCA_TRY(dec_logits(e, p, xd, e->xdn + (size_t)b0 * dt, B, (float*)e->dec_logits.p + (size_t)b0 * D.n_vocab));
+  if (want_logits) WCA_TRY(dec_logits(e, p, e->xd, e->xdn, B, (float*)e->dec_logits.p));
   return WCA_OK;
 }
 
@@ -541,7 +513,6 @@ int run_decode_prefill(wca_engine* e, hipStream_t s, const half_t* kvbuf, const 
   p.nq = n;
   p.kv = kvbuf;
   p.scatter = (half_t*)e->dec_cache.p;
-  p.B_all = B;
   p.T_max = T_max;
   p.l1 = e->dims.n_text_layer;
   HIPCHK(launch_embed_prefix(tokens, T_max, n, e->tok_emb, e->dec_pos, e->xd, B, dt, e->dims.n_vocab, s));
@@ -598,14 +569,12 @@ int run_phase1(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_
   record(e, 1);
   e->ln_err = e->err_dev + 1 + slot;
   HIPCHK(hipMemsetAsync(e->ln_err, 0, sizeof(int), e->stream));
-  g_gemm_cu_limit = e->part_cus > 0 ? e->n_cu - e->part_cus : 0;   // persistent GEMM grids = the CUs phase 1's stream owns
   int rc = run_encoder(e, batch);
   e->ln_err = e->err_dev;
   if (!rc) {
     record(e, 2);
     rc = run_cross_kv(e, batch, kvbuf, skip_last_v);
   }
-  g_gemm_cu_limit = 0;
   if (rc) return rc;
   record(e, 3);
   HIPCHK(hipEventRecord(e->ev_kv[slot], e->stream));

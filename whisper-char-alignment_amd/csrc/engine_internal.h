@@ -100,10 +100,7 @@ struct wca_engine {
   hipStream_t stream = nullptr;      // phase 1 (log-mel, encoder, cross-K/V) and every non-batched entry point
   hipStream_t own_stream = nullptr;
   hipStream_t stream2 = nullptr;     // phase 2 of wca_align_batch (decoder, post-processing, DTW, D2H): overlaps the next batch's phase 1
-  hipStream_t stream3 = nullptr;     // second half-batch of the greedy decode loop (wca_greedy_decode): its latency-bound small
-                                     // kernels run under the other half's HBM-bound cross-attention
   hipEvent_t ev_kv[2] = {};          // cross-K/V of batch slot ready (recorded on `stream`)
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // stream2 -> stream3 fork / join of the decode loop
   bool finalized = false;
   bool have_filters = false;
   bool profiling = false;
@@ -155,11 +152,11 @@ struct wca_engine {
   int meta_slot = 0;
   unsigned long long* ln_stats = nullptr;  // out_mode 3 GEMMs: per-tile row statistics [n_state/256][B*1500 padded to 256]
   unsigned* ln_cnt = nullptr;              // ... and per-panel arrival counters (zeroed by launch_gemm)
-  float* sk_part[2] = {nullptr, nullptr};  // split-K workspaces of the few-row GEMM (one per decode stream) and their
-  unsigned* sk_cnt[2] = {nullptr, nullptr};  // arrival counters (zero at creation, self-cleaning)
+  float* sk_part = nullptr;    // split-K workspace of the few-row GEMM (the decoder's stream) and its
+  unsigned* sk_cnt = nullptr;  // arrival counters (zero at creation, self-cleaning)
   size_t sk_floats = 0, sk_tiles = 0;
-  float* sk_big[3] = {nullptr, nullptr, nullptr};   // split-K partials of the 128 x 128 tile GEMM (small batches: fc2): [0] encoder stream,
-                                                     // [1 + ws] decoder / decode stream ws (the two half-batches of the decode loop may run it concurrently)
+  float* sk_big[2] = {nullptr, nullptr};   // split-K partials of the 128 x 128 tile GEMM (small batches: fc2): [0] the encoder's stream,
+                                            // [1] the decoder's (phase 2 / the decode loop run beside the next batch's encoder)
   size_t sk_big_bytes = 0;
   int n_cu = 0;
   int* err_dev = nullptr;    // device flags raised by kernels. Word 0: phase 2 / synchronous entry points (bit 0 token id outside the
@@ -234,14 +231,7 @@ struct wca_engine {
                              // the GPU to itself -- with a second process (or engine) on the device two such launches can hold each
                              // other's CUs and run into the bounded spin's time-out (measured: two bench ranks on one GPU)
   bool overlap = true;       // phase 2 on its own stream (false: everything on `stream`, for clean per-kernel profiles)
-  int part_cus = 0;          // wca_set_cu_partition: > 0 = phase 2 / the decode loop own that many CUs (CU-masked streams), phase 1 the rest
-  hipStream_t part_s1 = nullptr, part_s2 = nullptr, part_s3 = nullptr;  // the masked streams: they REPLACE stream / stream2 / stream3 while active
-  hipStream_t saved_s2 = nullptr, saved_s3 = nullptr;                   // ... and the engine's own ones come back when the partition is lifted
-  hipStream_t user_stream = nullptr;   // the stream the caller bound last (wca_engine_set_stream), also while a partition is active
-  bool user_stream_set = false;
   bool dec_fused = true;     // few-row GEMM with LayerNorm prologue / KV append / split-K for M <= DEC_ROWS_MAX = 128 rows (wca_set_decode_mode)
-  int dec_streams = 1;       // 2: the greedy decode loop as two half-batches on two streams (measured: the two queues' kernels run
-                             // back to back, not concurrently -- 3.86 vs 3.90 ms per step -- so one stream is the default)
   bool ev_valid = false;
   float stage_ms[8] = {};
 };
@@ -318,8 +308,7 @@ int run_encoder(wca_engine* e, int B);
 int run_cross_kv(wca_engine* e, int B, half_t* kvbuf = nullptr, bool skip_last_v = false);
 int run_decoder(wca_engine* e, const int64_t* tokens_dev, int B, int n, float* cap, int Fpad, int Fcap, float* logits_out, hipStream_t s = nullptr,
                 const half_t* kvbuf = nullptr, bool finish_last = false);
-int run_decode_step(wca_engine* e, hipStream_t s, int ws, const half_t* kvbuf, const int* tokens, int b0, int B, int B_all, StepPos pos,
-                    int T_max, bool want_logits, int phase = -2);
+int run_decode_step(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, StepPos pos, int T_max, bool want_logits);
 int run_decode_prefill(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, int n, int T_max, StepPos last, StepPos sot);
 int mel_to_tm(wca_engine* e, const float* mel_dev, int batch);
 int run_phase1(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int* n_samples_dev, int batch, int slot,

@@ -166,7 +166,7 @@ int ensure_split_weights(wca_engine* e) {
     WCA_TRY(dup_cols(s, l.fc1_w, dt, w.fc1_w, 2 * dt, 4 * dt, dt, dt));
     WCA_TRY(dup_cols(s, l.fc2_w, 4 * dt, w.fc2_w, 8 * dt, dt, 4 * dt, 4 * dt));
   }
-  // the copies are read by kernels on stream2 / stream3 too: make them visible before anything else is enqueued
+  // the copies are read by kernels on stream2 too: make them visible before anything else is enqueued
   HIPCHK(hipStreamSynchronize(s));
   e->sw_dirty = false;
   return WCA_OK;

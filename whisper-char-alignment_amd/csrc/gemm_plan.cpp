@@ -60,7 +60,7 @@ GemmPlan plan_gemm(const GemmArgs& a, int n_cu) {
   const bool can_buf = a.a_rows_per_batch == 0 && a_need < BUF_RANGE && w_need < BUF_RANGE;
   if (p.a_bytes == 0) p.a_bytes = (unsigned)a_need;
   if (p.w_bytes == 0) p.w_bytes = (unsigned)w_need;
-  if (a.cu_limit > 0 && a.cu_limit < n_cu) n_cu = a.cu_limit;   // a CU-masked stream: one persistent workgroup per CU it owns
+  if (a.cu_limit > 0 && a.cu_limit < n_cu) n_cu = a.cu_limit;   // the tests' cap on the persistent grid: that many workgroups walk the tiles
   // (the pre-activation addend lives in the generic epilogue only: an addend launch takes the two-barrier 256 x 256 kernel)
   const bool persistent = big && can_buf && a.force_tile != GEMM_TILE_256 && a.addend == nullptr;
   const int site = p.site_used = a.site >= 1 && a.site <= 4 ? a.site : 0;

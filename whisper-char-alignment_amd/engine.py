@@ -277,24 +277,12 @@ class WhisperAMD:
     # ---- stream handling: always run on torch's current stream so torch tensors stay ordered
     def _bind_stream(self):
         s = torch.cuda.current_stream(self.device).cuda_stream
-        if getattr(self, "_partitioned", False):
-            # CU-partitioned engine: its masked streams are not ordered with torch's stream -- complete the caller's work first (and every
-            # entry point that returns device tensors synchronises the engine afterwards: _after_call)
-            torch.cuda.current_stream(self.device).synchronize()
         if s != self._stream_bound:
-            rc = self._lib.wca_engine_set_stream(self._h, C.c_void_p(s))
-            if rc != 1:   # WCA_STATUS_PARTITIONED: recorded only
-                _lib.check(rc)
+            _lib.check(self._lib.wca_engine_set_stream(self._h, C.c_void_p(s)))
             self._stream_bound = s
 
     def synchronize(self):
         _lib.check(self._lib.wca_engine_synchronize(self._h))
-
-    def _after_call(self):
-        """Entry points that leave their results in device tensors are ordered with torch's stream by running ON it -- except on a
-        CU-partitioned engine, whose masked streams torch knows nothing about: wait for them here."""
-        if getattr(self, "_partitioned", False):
-            self.synchronize()
 
     # ---- hot path entry points (thin wrappers; shapes documented in include/wca.h)
     def log_mel(self, pcm, n_samples=None):
@@ -312,7 +300,6 @@ class WhisperAMD:
         for b0 in range(0, B, self.max_batch):
             b1 = min(B, b0 + self.max_batch)
             _lib.check(self._lib.wca_log_mel(self._h, _ptr(p[b0:b1]), n, _lib.i32_array(ns[b0:b1]), b1 - b0, _ptr(out[b0:b1])))
-        self._after_call()
         return out[0] if single else out
 
     def log_mel_long(self, pcm):
@@ -327,7 +314,6 @@ class WhisperAMD:
         out = torch.empty(self.dims.n_mels, T, device=self.device, dtype=torch.float32)
         self._bind_stream()
         _lib.check(self._lib.wca_log_mel_long(self._h, _ptr(p) if n else None, n, _ptr(out), T, None))
-        self._after_call()
         return out
 
     def resample(self, pcm, sr_in):
@@ -350,7 +336,6 @@ class WhisperAMD:
         _lib.check(self._lib.wca_resample_16k(self._h, _ptr(p) if n else None, channels, ld, n, int(sr_in), _ptr(out) if n else None,
                                               out.shape[0], C.byref(n_out)))
         assert n_out.value == out.shape[0]
-        self._after_call()
         return out
 
     def mel_window(self, mel_long, seek, size):
@@ -371,7 +356,6 @@ class WhisperAMD:
             b1 = min(len(seeks), b0 + self.max_batch)
             _lib.check(self._lib.wca_mel_window(self._h, _ptr(mel_long), mel_long.stride(0), mel_long.shape[1], _lib.i32_array(seeks[b0:b1]),
                                                 _lib.i32_array(sizes[b0:b1]), b1 - b0, _ptr(out[b0:b1])))
-        self._after_call()
         return out[0] if single else out
 
     def quiet_cuts(self, mel_long, n_pieces, radius=500, half_width=12, content_frames=None):
@@ -430,7 +414,6 @@ class WhisperAMD:
         nt = _lib.i32_array(n_tok) if n_tok is not None else None
         _lib.check(self._lib.wca_get_attentions(self._h, _ptr(mel), _ptr(tokens), B, n, nt, _lib.i32_array(mf),
                                                 int(medfilt_width), float(qk_scale), _ptr(weights), _ptr(logits)))
-        self._after_call()
         return weights, logits
 
     def encode(self, mel):
@@ -440,7 +423,6 @@ class WhisperAMD:
         out = torch.empty(B, 1500, self.dims.n_audio_state, device=self.device, dtype=torch.float32)
         self._bind_stream()
         _lib.check(self._lib.wca_test_encoder(self._h, _ptr(mel), B, _ptr(out)))
-        self._after_call()
         return out
 
     def make_opts(self, aggregation="mean", topk=-1, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0, sot_len=3,
@@ -702,17 +684,9 @@ class WhisperAMD:
         """Phase 2 on its own stream (default) or everything on one stream (clean per-kernel profiles)."""
         _lib.check(self._lib.wca_set_overlap(self._h, 1 if on else 0))
 
-    def set_cu_partition(self, phase2_cus):
-        """Experiment (wca.h: wca_set_cu_partition): phase 2 / the decode loop on CU-masked streams owning `phase2_cus` compute units,
-        phase 1 on the rest; 0 lifts it. Inputs must be complete (synchronised) before the engine is called while it is active."""
-        torch.cuda.synchronize()
-        _lib.check(self._lib.wca_set_cu_partition(self._h, int(phase2_cus)))
-        self._partitioned = int(phase2_cus) > 0
-        self._stream_bound = None   # re-bind torch's current stream at the next call (ADVICE r4: after a lift the engine must not stay on a private stream)
-
     def set_decode_mode(self, fused=True, streams=1):
-        """Few-row decoder GEMMs fused with LayerNorm / KV append / split-K (default) or separate launches; greedy decode as
-        one stream (default) or two interleaved half-batches."""
+        """Few-row decoder GEMMs fused with LayerNorm / KV append / split-K (default) or separate launches. streams must be 1 (the
+        two-stream form of the decode loop was removed; the library refuses anything else)."""
         _lib.check(self._lib.wca_set_decode_mode(self._h, 1 if fused else 0, int(streams)))
 
     def last_stage_ms(self):
