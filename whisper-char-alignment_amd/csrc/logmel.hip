@@ -121,7 +121,9 @@ __device__ __forceinline__ void frame_log_mel(const LogMelTables& a, FrameLds& s
     } else {
       for (int k = lo; k < hi; ++k) acc = fmaf(fr[k], s.pow[k], acc);
     }
-    lv = log10f(fmaxf(acc, 1e-10f));
+    // a clamped bin is exactly -10, the value the skipped frames get in pass 2 (the device's log10f(1e-10f) is one ulp below it, so
+    // silence inside the active frames came out as -1.5000002 beside the -1.5 of the frames after them)
+    lv = (acc > 1e-10f) ? log10f(acc) : -10.0f;
     out[(long)m * ld] = lv;
   }
   lv = wave_max(lv);
