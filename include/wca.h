@@ -570,6 +570,13 @@ int wca_test_set_switch(const char* name, int value);
 /* the [batch][n_text_layer * n_text_head] head selection scores (timing.py:13-43) of the LAST fused batch, after it was fetched (no batch in
  * flight): tools/precision_ablation.py compares them with the oracle's */
 int wca_test_last_scores(wca_engine* e, int batch, float* scores_host);
+/* what the LAST wca_greedy_decode* call left on the device, after a synchronisation of the decode stream (reads only, launches nothing):
+ * logits_host [logits_rows][n_vocab] f32 -- the rows of the last forward, [batch] of them, or [2 batch] after a prefill with no_speech
+ * (rows [batch, 2 batch): the <|sot|> position's, which the steps behind the prefill leave alone) -- and cache_f16_host, the self-attention
+ * cache [n_text_layer][2][batch][T_max][n_text_state] f16 with T_max = the largest n_initial + sample_len of that call. batch and T_max
+ * must be that call's (WCA_ERR_STATE otherwise, also after wca_detect_language, which overwrites the cache); more logits rows than the
+ * call left are WCA_ERR_INVALID. */
+int wca_test_decode_state(wca_engine* e, int batch, int T_max, int logits_rows, float* logits_host, void* cache_f16_host);
 /* q,k,v [B][n][H*64] f16 device -> o [B][nq][H*64] f16; cap_dev [B][H][nq][cap_ld] f32 or NULL.
  * causal: bit 0 = causal mask; bits 8-9 = kernel variant (0 auto, 1 the 16x16x32-MFMA kernel, 2 the 32x32x16-MFMA
  * kernel that serves the encoder's un-masked self-attention = what auto picks; 3 is WCA_ERR_INVALID) */

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+import decode_cache_ref as cref
+
 pytestmark = pytest.mark.gpu
 
 dref = importlib.import_module("oracle.decoding_ref")
@@ -206,6 +208,15 @@ def test_length_edge_and_bounds(pkg, small, tok):
     assert toks.shape == (1, 449) and n_tok[0] == 449 and (toks[0, 227:] < tok.eot).all()
     assert pos == (227, 221) and pos[0] + pos[1] == dims.n_text_ctx
     assert np.isfinite(lp).all() and np.isfinite(nsp).all()
+    # the 448 slots the run filled and the logits of its last forward (position 447) against float64, teacher-forced on the sampled tokens
+    logits, cache = m.decode_state(1, 449)
+    ref = cref.DecodeRef(sd, dims)
+    K, V, x, _ = ref.forward(torch.from_numpy(toks[:, :448].astype(np.int64)), ref.cross_kv(ref.encoder(mel.cpu())))
+    diff = (torch.from_numpy(cache.astype(np.float64))[:, :, :, :448] - torch.stack([K, V], 1)).abs()
+    dl = float((torch.from_numpy(logits.astype(np.float64)) - ref.logits(x[:, 447])).abs().max())
+    print("decode-cache measure length edge: plane0 %.3e plane_deep %.3e logits %.3e" % (float(diff[0].max()), float(diff[1:].max()), dl))
+    assert float(diff[0].max()) <= cref.TOL["small_plane0"] and float(diff[1:].max()) <= cref.TOL["small_plane_deep"]
+    assert dl <= cref.TOL["small_logits"], dl
     # the bounds of wca_greedy_decode_ex and of the old entry point
     with pytest.raises(_m("_lib").TooLongError):
         _decode(m, tok, dims, initial, sample_len + 1, sot_index, 1, mel=mel)

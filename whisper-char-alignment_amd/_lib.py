@@ -126,6 +126,7 @@ SIGNATURES = {
     "wca_test_set_attn_split_drop": (_i, [_i]),
     "wca_test_set_switch": (_i, [C.c_char_p, _i]),
     "wca_test_last_scores": (_i, [_vp, _i, _pf]),
+    "wca_test_decode_state": (_i, [_vp, _i, _i, _i, _pf, _vp]),
     "wca_test_gemm_pairs": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "wca_test_attention": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
     "wca_test_attention_split": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),

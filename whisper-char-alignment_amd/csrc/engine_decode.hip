@@ -258,6 +258,9 @@ int decode_run(const DecodeLoop& lp, const DecodePlan& pl, const DecodeRows& r, 
                            lp.want_nsp ? no_speech_prob_host : nullptr));
   e->dec_prefill_positions = pl.n_prefill;
   e->dec_step_positions = step_positions;
+  e->dec_batch = B;
+  e->dec_T_max = lp.T_max;
+  e->dec_logits_rows = (pl.n_prefill && lp.want_nsp ? 2 : 1) * B;   // a prefill leaves the <|sot|> rows behind the last position's
   return WCA_OK;
 }
 
@@ -375,6 +378,7 @@ int wca_detect_language(wca_engine* e, const float* mel_dev, const float* pcm_de
   const half_t* kvbuf = st->slot ? e->kv_alt : e->kv;
   hipStream_t s2 = e->stream2;
   const int T_max = 1;   // a one-slot self-attention cache: position 0 attends to itself
+  e->dec_batch = e->dec_T_max = e->dec_logits_rows = 0;   // the last decode's cache is overwritten
   HIPCHK(e->dec_cache.ensure(sizeof(half_t) * (size_t)L * 2 * batch * T_max * dt));
   HIPCHK(e->dec_tokens.ensure(sizeof(int) * (size_t)batch * T_max));
   HIPCHK(e->dec_state.ensure((sizeof(float) * n_lang + sizeof(int)) * (size_t)batch));

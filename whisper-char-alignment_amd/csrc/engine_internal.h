@@ -183,6 +183,7 @@ struct wca_engine {
   struct ResampleTable { int sr_in; wca::ResamplePlan plan; float* dev; };
   std::vector<ResampleTable> rs_tables;
   int dec_prefill_positions = 0, dec_step_positions = 0;  // the last decode: positions per row fed by the prefill / one at a time
+  int dec_batch = 0, dec_T_max = 0, dec_logits_rows = 0;  // the last decode's cache shape and the rows its forwards left in dec_logits (wca_test_decode_state)
   // Encoded micro-batches (log-mel + encoder + cross-K/V done, recorded on `stream`) that no alignment has consumed
   // yet: wca_encode_batch / wca_greedy_decode push, wca_align_batch_enqueue(pcm_dev = NULL) pops the oldest. A K/V
   // slot stays busy from its encode until the alignment that consumed it has been fetched.

@@ -308,6 +308,23 @@ int wca_test_last_scores(wca_engine* e, int batch, float* scores_host) {
   return WCA_OK;
 }
 
+int wca_test_decode_state(wca_engine* e, int batch, int T_max, int logits_rows, float* logits_host, void* cache_f16_host) {
+  if (!e || !logits_host || !cache_f16_host) return fail(WCA_ERR_INVALID, "null argument");
+  const wca_model_dims& D = e->dims;
+  if (batch < 1 || batch != e->dec_batch || T_max != e->dec_T_max)
+    return fail(WCA_ERR_STATE, "the last decode ran batch %d with T_max %d, not batch %d with T_max %d", e->dec_batch, e->dec_T_max, batch, T_max);
+  if (logits_rows < 1 || logits_rows > e->dec_logits_rows)
+    return fail(WCA_ERR_INVALID, "the last decode left %d logits rows, not %d", e->dec_logits_rows, logits_rows);
+  const size_t logits_bytes = sizeof(float) * (size_t)logits_rows * D.n_vocab;
+  const size_t cache_bytes = sizeof(half_t) * (size_t)D.n_text_layer * 2 * batch * T_max * D.n_text_state;
+  if (logits_bytes > e->dec_logits.bytes || cache_bytes > e->dec_cache.bytes) return fail(WCA_ERR_INVALID, "the decode buffers hold less than was asked for");
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipStreamSynchronize(e->stream2));
+  HIPCHK(hipMemcpy(logits_host, e->dec_logits.p, logits_bytes, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(cache_f16_host, e->dec_cache.p, cache_bytes, hipMemcpyDeviceToHost));
+  return WCA_OK;
+}
+
 int wca_test_attention(wca_engine* e, const void* q, const void* k, const void* v, void* o, float* cap_dev, int cap_ld, int cap_cols,
                        int B, int H, int nq, int nk, int causal) {
   if (!e) return fail(WCA_ERR_INVALID, "null engine");

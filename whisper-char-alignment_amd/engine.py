@@ -570,6 +570,17 @@ class WhisperAMD:
         _lib.check(self._lib.wca_last_decode_positions(self._h, C.byref(pre), C.byref(step)))
         return pre.value, step.value
 
+    def decode_state(self, batch, T_max, logits_rows=None):
+        """Test accessor (C ABI wca_test_decode_state): what the last greedy_decode / greedy_decode_rows left on the device ->
+        (logits [logits_rows, n_vocab] f32, cache [n_text_layer, 2, batch, T_max, n_text_state] f16) as numpy arrays. T_max is that call's
+        largest n_initial + sample_len; logits_rows defaults to batch (2 * batch: with the <|sot|> rows of a prefill with no_speech)."""
+        rows = int(batch if logits_rows is None else logits_rows)
+        logits = np.zeros((max(rows, 1), self.dims.n_vocab), dtype=np.float32)
+        cache = np.zeros((self.dims.n_text_layer, 2, max(int(batch), 1), max(int(T_max), 1), self.dims.n_text_state), dtype=np.float16)
+        _lib.check(self._lib.wca_test_decode_state(self._h, int(batch), int(T_max), rows, logits.ctypes.data_as(_lib._pf),
+                                                   cache.ctypes.data_as(C.c_void_p)))
+        return logits, cache
+
     def decode(self, mel, options=None):
         """whisper.decode(model, mel, options) (infer_ali.py:60)."""
         from . import decoding
