@@ -41,7 +41,9 @@
  *   wca_greedy_decode_rows the same for a batch whose rows carry initial tokens (prompts) of their own, of their own lengths, and
  *                          their own sample budgets: the rows sit at different decoder positions (transcribe_batch: several
  *                          recordings in lock-step, each conditioned on its own previous text)
- *   wca_align_batch        infer_ali.py:93-101 + dataset.py:47-48: the whole per-utterance pipeline
+ *   wca_decode_rows_sampled the same with a temperature and a seed per row (upstream GreedyDecoder at temperature > 0), and optionally on
+ *                          the encoder state the previous decode left (the rungs of transcribe's temperature fallback ladder)
+ *   wca_align_batch       infer_ali.py:93-101 + dataset.py:47-48: the whole per-utterance pipeline
  *                          (log-mel -> forward+capture -> medfilt/softmax -> scores/top-k ->
  *                          aggregate -> DTW) for a micro-batch of utterances, results = the frame
  *                          at which the DTW path enters every token row (timing.py:110-111 `jumps`)
@@ -386,6 +388,26 @@ int wca_greedy_decode_rows(wca_engine* e, const float* mel_dev, const float* pcm
                            const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host, const wca_decode_opts* opts,
                            int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
                            float* no_speech_prob_host);
+/* wca_greedy_decode_rows with temperature sampling (upstream GreedyDecoder.update at temperature > 0: a draw from
+ * Categorical(logits = filtered logits / T), sum_logprob accumulating the UNTEMPERED log-softmax of the filtered logits at the drawn token).
+ * temperature_host [batch] f32 (negative or not finite: WCA_ERR_INVALID) and seed_host [batch] uint64; the other arguments, checks and
+ * results are those of wca_greedy_decode_rows. A row at temperature 0 is decoded greedily, bit for bit as wca_greedy_decode_rows decodes it.
+ * A row at T > 0 draws by Gumbel-max: next = argmax_v (logit[v] * (1.0f / T) + G(v)) over the tokens its filters leave (the lowest index
+ * among equals; the "timestamp mass beats every text token" rule is decided on the untempered logits), G(v) = -logf(-logf(u)),
+ * u = ((x >> 9) + 0.5) * 2^-23 in fp32, x = word v & 3 of Philox4x32-10 with key (seed low word, seed high word) and counter
+ * (v >> 2, c, 0, 0), c = the number of tokens the row has sampled so far. A row's draws therefore follow (seed, c, v, its logits) alone:
+ * not the batch row it sits in, not the other rows. The law is upstream's; the draws are not torch's (another generator).
+ * redecode = 1 (requires mel_dev = pcm_dev = NULL, else WCA_ERR_INVALID): decodes AGAIN the newest state of `batch` rows that is already
+ * decoded and not yet aligned -- the one the previous decode left for wca_align_batch_enqueue(pcm_dev = NULL) --, with no encoder pass;
+ * WCA_ERR_STATE if there is none. Nothing is dropped from the queue and the state is still there for the alignment afterwards.
+ * redecode = 0: the state queue behaves as for wca_greedy_decode_rows. */
+int wca_decode_rows_sampled(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride,
+                            const int32_t* n_samples_host, int batch, const int32_t* initial_tokens_host,
+                            const int32_t* n_initial_host, const int32_t* sot_index_host, const int32_t* sample_len_host,
+                            const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host, const wca_decode_opts* opts,
+                            int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
+                            float* no_speech_prob_host, const float* temperature_host, const uint64_t* seed_host,
+                            int redecode);
 /* Language identification, upstream's detect_language(model, mel): which of the language tokens [lang_begin, lang_begin + n_lang)
  * (tokenizer.all_language_tokens: sot + 1 ..., 99 or 100 of them; 1 <= n_lang <= 128) follows <|startoftranscript|> (`sot`) for each row.
  * mel_dev / pcm_dev / pcm_stride / n_samples_host / batch as for wca_greedy_decode: at most one input is non-NULL, with both NULL the oldest
@@ -600,6 +622,13 @@ int wca_test_decode_select_rows(wca_engine* e, const float* logits_dev, int batc
                                 const int32_t* cur_len_dev, const int32_t* n_initial_dev, const int32_t* cap_dev, int n_done_idx,
                                 int n_done_len, const uint8_t* suppress_mask_dev, const uint8_t* blank_mask_dev,
                                 const wca_decode_opts* opts, float* sum_logprob_dev, int32_t* n_done_dev);
+/* that step in its sampling form (wca_decode_rows_sampled): temperature_dev [batch] f32 and seed_dev [batch] uint64 device arrays; row b
+ * draws with the counter cur_len[b] - n_initial[b] and, at temperature 0, takes the argmax exactly as wca_test_decode_select_rows does */
+int wca_test_decode_sample_rows(wca_engine* e, const float* logits_dev, int batch, int n_vocab, int32_t* tokens_dev, int T_max,
+                                const int32_t* cur_len_dev, const int32_t* n_initial_dev, const int32_t* cap_dev, int n_done_idx,
+                                int n_done_len, const uint8_t* suppress_mask_dev, const uint8_t* blank_mask_dev,
+                                const wca_decode_opts* opts, float* sum_logprob_dev, int32_t* n_done_dev,
+                                const float* temperature_dev, const uint64_t* seed_dev);
 /* wca_test_attention (no capture) with per-row key counts: q [B][nq][H*64], k / v [B][nk][H*64] f16, batch row b attends to keys
  * [0, nk_rows_dev[b]) (int32 device, clamped to [1, nk]). Only nq = 1 without a mask exists (the decode step's one-query kernel):
  * anything else is WCA_ERR_INVALID. Row b equals a B = 1 wca_test_attention call with nk = nk_rows[b], bit for bit. */

@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Greedy ASR pre-pass (wca_greedy_decode) at the bench's model / batch: ms per autoregressive step with the encoder state
-already queued (wca_encode_batch), so that only the KV-cached loop is timed.  usage: decode_bench.py [B] [sample_len] [rounds]
+already queued (wca_encode_batch), so that only the KV-cached loop is timed.
+usage: decode_bench.py [B] [sample_len] [rounds] [--temperature T] [--seed S]
+--temperature T (with --seed S, default 0): the same rows through wca_decode_rows_sampled at temperature T, row b with seed S + b. That is the
+per-row form (the prompt goes through one batched prefill, not position by position), so its base line is --temperature 0, which runs the
+same entry point greedily; without --temperature the loop is wca_greedy_decode as before.
 Environment: WCA_DEC_MODES=0,1 (default): separate launches, then the fused few-row GEMMs (wca_set_decode_mode)."""
 import importlib
 import os
@@ -15,9 +19,16 @@ wca = importlib.import_module("whisper-char-alignment_amd")
 syn = importlib.import_module("whisper-char-alignment_amd.synthetic")
 tok_mod = importlib.import_module("whisper-char-alignment_amd.tokenizer")
 
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-sample_len = int(sys.argv[2]) if len(sys.argv) > 2 else 64
-rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+argv, named = [], {"--temperature": None, "--seed": 0}
+for a in sys.argv[1:]:
+    if argv and argv[-1] in named:
+        named[argv.pop()] = float(a)
+    else:
+        argv.append(a)
+temperature, seed = named["--temperature"], int(named["--seed"])
+B = int(argv[0]) if len(argv) > 0 else 64
+sample_len = int(argv[1]) if len(argv) > 1 else 64
+rounds = int(argv[2]) if len(argv) > 2 else 3
 model_name = os.environ.get("WCA_MODEL", "medium")
 dims = wca.dims_for(model_name)
 m = wca.WhisperAMD(dims, max_batch=B, precision="f16")
@@ -38,10 +49,17 @@ for fused in [bool(int(x)) for x in os.environ.get("WCA_DEC_MODES", "0,1").split
     m.encode_batch(pcm=pcm, n_samples=ns)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    toks, n_tok, lp = m.greedy_decode(None, None, None, initial, sup, None, batch=B, **kw)
+    if temperature is None:
+      toks, n_tok, lp = m.greedy_decode(None, None, None, initial, sup, None, batch=B, **kw)
+    else:
+      toks, n_tok, lp = m.decode_rows_sampled(None, None, None, [initial] * B, [0] * B, [sample_len] * B, sup, None, batch=B,
+                                              temperature=[temperature] * B, seed=[seed + b for b in range(B)],
+                                              **{k: v for k, v in kw.items() if k != "sample_len"})
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     steps = len(initial) - 1 + sample_len  # the prompt is fed position by position through the same step
-    print("  round %d: B=%d %s  %.1f ms for %d sampled tokens (+%d prompt positions)  -> %.3f ms per position, %.0f utt/s decode-only"
-          % (r, B, model_name, dt * 1e3, sample_len, len(initial), dt * 1e3 / steps, B / dt), flush=True)
+    if temperature is not None:
+      steps = sample_len                   # one prefill forward over the prompt, then sample_len - 1 steps
+    print("  round %d: B=%d %s%s  %.1f ms for %d sampled tokens (+%d prompt positions)  -> %.3f ms per position, %.0f utt/s decode-only"
+          % (r, B, model_name, "" if temperature is None else " T=%g (rows form)" % temperature, dt * 1e3, sample_len, len(initial), dt * 1e3 / steps, B / dt), flush=True)
   print("  tokens[0][:12] =", toks[0][:12].tolist(), " n_tok[0] =", int(n_tok[0]))

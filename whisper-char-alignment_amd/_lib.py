@@ -112,6 +112,9 @@ SIGNATURES = {
     "wca_greedy_decode_ex": (_i, [_vp, _vp, _vp, _i64, _pi32, _i, _pi32, _i, _vp, _vp, C.POINTER(DecodeOptsEx), _pi32, _pi32, _pf, _pf]),
     "wca_greedy_decode_rows": (_i, [_vp, _vp, _vp, _i64, _pi32, _i, _pi32, _pi32, _pi32, _pi32, _vp, _vp, C.POINTER(DecodeOpts), _pi32, _pi32, _pf,
                                     _pf]),
+    "wca_decode_rows_sampled": (_i, [_vp, _vp, _vp, _i64, _pi32, _i, _pi32, _pi32, _pi32, _pi32, _vp, _vp, C.POINTER(DecodeOpts), _pi32, _pi32, _pf,
+                                     _pf, _pf, C.POINTER(C.c_uint64), _i]),
+    "wca_test_decode_sample_rows": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(DecodeOpts), _vp, _vp, _vp, _vp]),
     "wca_detect_language": (_i, [_vp, _vp, _vp, _i64, _pi32, _i, _i, _i, _i, _pi32, _pf]),
     "wca_test_language_head": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "wca_last_decode_positions": (_i, [_vp, _pi32, _pi32]),

@@ -9,7 +9,9 @@
 //   * decode_select:  the logit filters (SuppressBlank, SuppressTokens, ApplyTimestampRules), GreedyDecoder.update
 //                     (argmax at temperature 0, log-softmax of the FILTERED logits for sum_logprobs, EOT latching)
 //                     for one batch row per workgroup; integer / index work, bit-exact against the oracle on the same
-//                     fp32 logits (tests/test_decode_gpu.py).
+//                     fp32 logits (tests/test_decode_gpu.py). Its sampling form (GreedyDecoder.update at temperature > 0:
+//                     Gumbel-max over Philox4x32-10 noise, per-row temperature and seed) is tested token for token against a
+//                     float64 restatement (tests/test_decode_sample_gpu.py).
 #include "kernels.h"
 #include "wca_common.h"
 
@@ -141,11 +143,38 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   return r;
 }
 
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3"; the Random123 known answers are pinned in
+// tests/test_decode_sample_ref.py through the float64 restatement this kernel is tested against): counter c[4], key (k0, k1) -> c[4].
+__device__ __forceinline__ void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1) {
+  for (int r = 0; r < 10; ++r) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+    c[0] = hi1 ^ c[1] ^ k0;
+    c[1] = lo1;
+    c[2] = hi0 ^ c[3] ^ k1;
+    c[3] = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+
+// Standard Gumbel noise of a 32-bit word: u = ((x >> 9) + 0.5) 2^-23 is exact in fp32 and strictly inside (0, 1) (23 bits, not 24: k + 0.5
+// with a 24-bit k rounds up to u = 1 and G = +inf), so G = -log(-log(u)) is finite, in about [-2.82, 16.64]. Full-precision logf.
+__device__ __forceinline__ float gumbel_of(unsigned x) {
+  const float u = ((float)(x >> 9) + 0.5f) * 1.1920928955078125e-07f;
+  return -logf(-logf(u));
+}
+
 // One workgroup per batch row. cur_len = number of tokens the row holds (the new token is written at index cur_len).
 // ROWS: cur_len, n_initial and the sample cap are per row (cur_len_rows / n_initial_rows / cap_rows); a row that has sampled its
 // cap (or whose lengths are not a valid state) is a finished row: EOT where the row still has room, nothing added to sum_logprob,
 // counted in n_done, which is indexed by the step (n_done_idx) because the rows' cur_len differ.
-template <bool ROWS>
+// SAMPLE (with ROWS): a row whose temperature_rows[b] is T > 0 draws its token from softmax(filtered logits / T) by Gumbel-max in pass 3:
+// argmax_v (lg[v] * (1 / T) + G(v)) with G from Philox keyed by the row's seed and counted by (v >> 2, cur_len - n_initial), one Philox call
+// per four consecutive tokens. The draw depends on (seed, sampled count, v, the row's logits) only: not on the batch row, nor on a summation
+// order. The filters, text_dead and sum_logprob (the UNTEMPERED log-softmax at the drawn token) are the greedy form's; a row at T == 0 runs
+// the greedy pass 3 itself. The instances without SAMPLE hold none of this.
+template <bool ROWS, bool SAMPLE = false>
 __global__ __launch_bounds__(1024) void decode_select_kernel(DecodeSelectArgs a) {
   __shared__ float red[16];
   __shared__ int red_i[16];
@@ -234,12 +263,35 @@ __global__ __launch_bounds__(1024) void decode_select_kernel(DecodeSelectArgs a)
   // pass 3: argmax (lowest index among equals) of the final filtered logits
   float best = -INFINITY;
   int best_i = 0x7fffffff;
-  for (int v = tid; v < V; v += blockDim.x) {
-    if (dead(v) || (text_dead && v < a.timestamp_begin)) continue;
-    const float x = lg[v];
-    if (x > best) {
-      best = x;
-      best_i = v;
+  const float temperature = SAMPLE ? a.temperature_rows[b] : 0.f;  // (uniform over the workgroup)
+  if (SAMPLE && temperature > 0.f) {
+    // ... of the perturbed scores: a thread takes groups of four consecutive tokens, one Philox call each (the rows are not 16-byte
+    // aligned: scalar loads)
+    const float inv_T = 1.0f / temperature;
+    const unsigned long long seed = a.seed_rows[b];
+    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+    for (int g = tid; g * 4 < V; g += blockDim.x) {
+      unsigned c[4] = {(unsigned)g, (unsigned)(cur_len - n_initial), 0u, 0u};
+      philox4x32_10(c, k0, k1);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int v = g * 4 + j;
+        if (v >= V || dead(v) || (text_dead && v < a.timestamp_begin)) continue;
+        const float x = lg[v] * inv_T + gumbel_of(c[j]);
+        if (x > best) {
+          best = x;
+          best_i = v;
+        }
+      }
+    }
+  } else {
+    for (int v = tid; v < V; v += blockDim.x) {
+      if (dead(v) || (text_dead && v < a.timestamp_begin)) continue;
+      const float x = lg[v];
+      if (x > best) {
+        best = x;
+        best_i = v;
+      }
     }
   }
   {
@@ -270,7 +322,9 @@ __global__ __launch_bounds__(1024) void decode_select_kernel(DecodeSelectArgs a)
   if (tid == 0) {
     const int prev = tok[cur_len - 1];
     const float s_final = text_dead ? s_ts : s_text + s_ts;
-    const float logprob = (best - m_all) - logf(s_final);  // log_softmax of the filtered logits at the argmax
+    // a draw reduced on the perturbed score: the token's own logit (nothing survived the filters: -inf, as the greedy `best`)
+    if (SAMPLE && temperature > 0.f) best = best_i == 0x7fffffff ? -INFINITY : lg[best_i];
+    const float logprob = (best - m_all) - logf(s_final);  // log_softmax of the filtered logits at the chosen token
     int next = best_i;
     if (best_i == 0x7fffffff) next = a.eot;  // every token filtered out (cannot happen with the stock filters)
     if (prev == a.eot) next = a.eot;         // finished rows keep emitting EOT and stop accumulating
@@ -346,9 +400,14 @@ hipError_t launch_gather_rows(const float* x, float* out, int B, int n, StepPos 
 hipError_t launch_decode_select(const DecodeSelectArgs& a, int B, hipStream_t s) {
   if (a.cur_len_rows) {
     if (!a.n_initial_rows || !a.cap_rows || a.n_done_idx < 0 || a.T_max < 2) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(decode_select_kernel<true>, dim3(B), dim3(1024), 0, s, a);
+    if (a.temperature_rows) {
+      if (!a.seed_rows) return hipErrorInvalidValue;
+      hipLaunchKernelGGL((decode_select_kernel<true, true>), dim3(B), dim3(1024), 0, s, a);
+    } else {
+      hipLaunchKernelGGL(decode_select_kernel<true>, dim3(B), dim3(1024), 0, s, a);
+    }
   } else {
-    if (a.cur_len < 1 || a.cur_len >= a.T_max || a.n_initial < 1 || a.cur_len < a.n_initial) return hipErrorInvalidValue;
+    if (a.temperature_rows || a.cur_len < 1 || a.cur_len >= a.T_max || a.n_initial < 1 || a.cur_len < a.n_initial) return hipErrorInvalidValue;
     hipLaunchKernelGGL(decode_select_kernel<false>, dim3(B), dim3(1024), 0, s, a);
   }
   return hipGetLastError();

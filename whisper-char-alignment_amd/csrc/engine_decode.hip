@@ -1,5 +1,6 @@
 // libwca.so engine, greedy decode: wca_greedy_decode / _ex (every row at the same position, optional batched prefill) and
-// wca_greedy_decode_rows (per-row initial tokens and sample budgets) over one argument check, one loop and one read-back; and
+// wca_greedy_decode_rows (per-row initial tokens and sample budgets) over one argument check, one loop and one read-back;
+// wca_decode_rows_sampled (the per-row call with a temperature and a seed per row, optionally on the state the last decode left); and
 // wca_detect_language (one position and the language head on the state a decode then takes).
 #include "engine_internal.h"
 
@@ -62,8 +63,19 @@ int decode_check(wca_engine* e, const float* mel_dev, const float* pcm_dev, cons
 // starts (stand-alone whisper.decode use). The autoregressive loop runs on `stream2` (it shares the decoder scratch with phase 2 of
 // the alignment, which is ordered before it on that stream; phase 1 of the NEXT batch may run beside it on `stream`): stream2 is made
 // to wait for the state's cross-K/V here.
+// redecode (wca_decode_rows_sampled; no input of its own): the state is the NEWEST one that is already decoded and not yet aligned -- what
+// the previous decode left for the alignment -- and nothing is dropped: it stays queued, decoded, for that alignment.
 int decode_take_state(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, int batch,
-                      wca_engine::EncState** out) {
+                      wca_engine::EncState** out, bool redecode = false) {
+  if (redecode) {
+    wca_engine::EncState* st = nullptr;
+    for (auto it = e->enc_q.rbegin(); it != e->enc_q.rend() && !st; ++it)
+      if (it->decoded) st = &*it;
+    if (!st || st->batch != batch) return fail(WCA_ERR_STATE, "no decoded batch of %d utterances is waiting to be decoded again", batch);
+    HIPCHK(hipStreamWaitEvent(e->stream2, e->ev_kv[st->slot], 0));
+    *out = st;
+    return WCA_OK;
+  }
   // (a state that wca_detect_language has read waits for the decode of that same state; a call that brings its own input drops it)
   const bool fresh = mel_dev != nullptr || pcm_dev != nullptr;
   for (auto it = e->enc_q.begin(); it != e->enc_q.end();) {
@@ -149,7 +161,7 @@ struct DecodeLoop {
 template <typename Opts>
 int decode_begin(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, const DecodeRows& r,
                  int n_done_len, bool prefill, const std::vector<int32_t>* tab, const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host,
-                 const Opts* o, bool nsp_asked, DecodeLoop* out) {
+                 const Opts* o, bool nsp_asked, DecodeLoop* out, bool redecode = false) {
   const wca_model_dims& D = e->dims;
   const int V = D.n_vocab, dt = D.n_text_state, L = D.n_text_layer, batch = r.batch, T_max = r.T_max;
   std::vector<int32_t> init((size_t)batch * T_max, o->eot);
@@ -159,7 +171,7 @@ int decode_begin(wca_engine* e, const float* mel_dev, const float* pcm_dev, int6
   lp.batch = batch;
   lp.T_max = T_max;
   lp.V = V;
-  WCA_TRY(decode_take_state(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, &lp.st));
+  WCA_TRY(decode_take_state(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, &lp.st, redecode));
   lp.kvbuf = lp.st->slot ? e->kv_alt : e->kv;
   hipStream_t s2 = lp.s2 = e->stream2;
   HIPCHK(e->dec_cache.ensure(sizeof(half_t) * (size_t)L * 2 * batch * T_max * dt));
@@ -317,21 +329,34 @@ int wca_greedy_decode_ex(wca_engine* e, const float* mel_dev, const float* pcm_d
 // steps: the per-row forms of embed_step / KV append / one-query attention / decode_select, fed from small device tables built here.
 // A row past its budget keeps going through the kernels as a finished row at a clamped position (<= T_max - 2, so no positional row
 // past n_text_ctx - 1 and no cache slot past T_max - 1 is touched); what it computes is never read.
-int wca_greedy_decode_rows(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
-                           int batch, const int32_t* initial_tokens_host, const int32_t* n_initial_host, const int32_t* sot_index_host,
-                           const int32_t* sample_len_host, const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host,
-                           const wca_decode_opts* o, int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
-                           float* no_speech_prob_host) {
+//
+// Sampling (wca_decode_rows_sampled: temperature_host / seed_host [batch], else both null): the tables gain the rows' Philox seeds and
+// temperatures, and the select step takes its sampling form; everything else is the greedy call. redecode: see decode_take_state.
+static int decode_rows(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, int batch,
+                       const int32_t* initial_tokens_host, const int32_t* n_initial_host, const int32_t* sot_index_host,
+                       const int32_t* sample_len_host, const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host,
+                       const wca_decode_opts* o, int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
+                       float* no_speech_prob_host, const float* temperature_host, const uint64_t* seed_host, bool redecode) {
   DecodeRows r{batch, 1, initial_tokens_host, n_initial_host, sot_index_host, sample_len_host};
   int rc = decode_check(e, mel_dev, pcm_dev, n_samples_host,
                         !initial_tokens_host || !n_initial_host || !sot_index_host || !sample_len_host || !suppress_mask_host || !o ||
                             !tokens_out_host || !n_tokens_host,
                         o, &r);
   if (rc) return rc;
+  if (redecode && (mel_dev || pcm_dev)) return fail(WCA_ERR_INVALID, "redecode takes no input: pass mel_dev = pcm_dev = NULL");
+  for (int b = 0; temperature_host && b < batch; ++b)
+    if (!(temperature_host[b] >= 0.f) || !std::isfinite(temperature_host[b]))
+      return fail(WCA_ERR_INVALID, "row %d: temperature %g is negative or not finite", b, (double)temperature_host[b]);
   const int T_max = r.T_max, S = r.S;
   // the int tables: [0] n_initial - 1, [1] sot_index, [2] n_initial, [3] sample cap; then per choice c in [0, S): fed position
   // min(n_initial + c - 1, T_max - 2), key count = fed position + 1, cur_len = n_initial + c  ([batch] each)
-  std::vector<int32_t> tab((size_t)(4 + 3 * S) * batch);
+  // sampling: behind them (at an even index: 8-byte aligned) the seeds [batch] uint64, then the temperatures [batch] f32
+  const size_t n_int = (size_t)(4 + 3 * S) * batch, seed_at = (n_int + 1) & ~(size_t)1, temp_at = seed_at + 2 * (size_t)batch;
+  std::vector<int32_t> tab(temperature_host ? temp_at + batch : n_int);
+  if (temperature_host) {
+    memcpy(tab.data() + seed_at, seed_host, sizeof(uint64_t) * batch);
+    memcpy(tab.data() + temp_at, temperature_host, sizeof(float) * batch);
+  }
   for (int b = 0; b < batch; ++b) {
     const int ni = n_initial_host[b];
     tab[0 * (size_t)batch + b] = ni - 1;
@@ -347,13 +372,42 @@ int wca_greedy_decode_rows(wca_engine* e, const float* mel_dev, const float* pcm
   }
   DecodeLoop lp;
   if ((rc = decode_begin(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, r, S, true, &tab, suppress_mask_host, blank_mask_host, o,
-                         no_speech_prob_host != nullptr, &lp)))
+                         no_speech_prob_host != nullptr, &lp, redecode)))
     return rc;
   const int* tab_dev = (const int*)e->dec_rows.p;
   lp.sel.n_initial_rows = tab_dev + 2 * (size_t)batch;
   lp.sel.cap_rows = tab_dev + 3 * (size_t)batch;
+  if (temperature_host) {
+    lp.sel.seed_rows = (const unsigned long long*)(tab_dev + seed_at);
+    lp.sel.temperature_rows = (const float*)(tab_dev + temp_at);
+  }
   const DecodePlan pl{r.n_max, 0, S, 0, -1, tab_dev};
   return decode_run(lp, pl, r, o->eot, tokens_out_host, n_tokens_host, sum_logprob_host, no_speech_prob_host);
+}
+
+int wca_greedy_decode_rows(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
+                           int batch, const int32_t* initial_tokens_host, const int32_t* n_initial_host, const int32_t* sot_index_host,
+                           const int32_t* sample_len_host, const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host,
+                           const wca_decode_opts* o, int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
+                           float* no_speech_prob_host) {
+  return decode_rows(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, initial_tokens_host, n_initial_host, sot_index_host, sample_len_host,
+                     suppress_mask_host, blank_mask_host, o, tokens_out_host, n_tokens_host, sum_logprob_host, no_speech_prob_host, nullptr, nullptr,
+                     false);
+}
+
+// wca_greedy_decode_rows with a temperature and a Philox seed per row (upstream GreedyDecoder.update at temperature > 0; decode.hip), and
+// optionally on the state the previous decode left (redecode: the rungs of transcribe's temperature fallback cost no encoder pass).
+int wca_decode_rows_sampled(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
+                            int batch, const int32_t* initial_tokens_host, const int32_t* n_initial_host, const int32_t* sot_index_host,
+                            const int32_t* sample_len_host, const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host,
+                            const wca_decode_opts* o, int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
+                            float* no_speech_prob_host, const float* temperature_host, const uint64_t* seed_host, int redecode) {
+  if (!e) return fail(WCA_ERR_INVALID, "null engine");
+  if (!temperature_host || !seed_host) return fail(WCA_ERR_INVALID, "null argument");
+  if (redecode != 0 && redecode != 1) return fail(WCA_ERR_INVALID, "redecode must be 0 or 1");
+  return decode_rows(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, initial_tokens_host, n_initial_host, sot_index_host, sample_len_host,
+                     suppress_mask_host, blank_mask_host, o, tokens_out_host, n_tokens_host, sum_logprob_host, no_speech_prob_host,
+                     temperature_host, seed_host, redecode == 1);
 }
 
 // Language identification (upstream detect_language): phase 1 as a decode takes it, ONE decoder position (t = 0, token sot) for every

@@ -389,6 +389,28 @@ int wca_test_decode_select_rows(wca_engine* e, const float* logits_dev, int batc
   return WCA_OK;
 }
 
+int wca_test_decode_sample_rows(wca_engine* e, const float* logits_dev, int batch, int n_vocab, int32_t* tokens_dev, int T_max,
+                                const int32_t* cur_len_dev, const int32_t* n_initial_dev, const int32_t* cap_dev, int n_done_idx, int n_done_len,
+                                const uint8_t* suppress_mask_dev, const uint8_t* blank_mask_dev, const wca_decode_opts* o, float* sum_logprob_dev,
+                                int32_t* n_done_dev, const float* temperature_dev, const uint64_t* seed_dev) {
+  if (!e || !logits_dev || !tokens_dev || !cur_len_dev || !n_initial_dev || !cap_dev || !suppress_mask_dev || !o || !sum_logprob_dev ||
+      !n_done_dev || !temperature_dev || !seed_dev)
+    return fail(WCA_ERR_INVALID, "null argument");
+  if (batch < 1 || n_vocab < 1 || T_max < 2 || n_done_idx < 0 || n_done_idx >= n_done_len) return fail(WCA_ERR_INVALID, "bad shape");
+  if (o->eot < 0 || o->eot >= n_vocab || o->timestamp_begin < 0 || o->timestamp_begin > n_vocab)
+    return fail(WCA_ERR_INVALID, "eot / timestamp_begin outside the vocabulary");
+  HIPCHK(hipSetDevice(e->device));
+  DecodeSelectArgs a = select_args(logits_dev, n_vocab, tokens_dev, T_max, suppress_mask_dev, blank_mask_dev, o, sum_logprob_dev, n_done_dev);
+  a.cur_len_rows = cur_len_dev;
+  a.n_initial_rows = n_initial_dev;
+  a.cap_rows = cap_dev;
+  a.n_done_idx = n_done_idx;
+  a.temperature_rows = temperature_dev;
+  a.seed_rows = (const unsigned long long*)seed_dev;
+  HIPCHK(launch_decode_select(a, batch, e->stream));
+  return WCA_OK;
+}
+
 int wca_test_language_head(wca_engine* e, const float* x_dev, int B, int lang_begin, int n_lang, float* probs_dev, int32_t* lang_token_dev) {
   if (!e || !x_dev || !probs_dev || !lang_token_dev) return fail(WCA_ERR_INVALID, "null argument");
   if (!e->finalized) return fail(WCA_ERR_STATE, "weights not finalized (call wca_finalize_weights)");

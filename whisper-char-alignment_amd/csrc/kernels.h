@@ -182,7 +182,8 @@ hipError_t launch_kv_scatter(const half_t* qkv, half_t* kc, half_t* vc, int B, i
 // p0 decides the form; the per-row positions are clamped to [0, n)
 hipError_t launch_gather_rows(const float* x, float* out, int B, int n, StepPos p0, StepPos p1, int d, hipStream_t s);
 // logit filters + greedy update of one decoding step (upstream decoding.py: SuppressBlank, SuppressTokens,
-// ApplyTimestampRules, GreedyDecoder.update at temperature 0); one workgroup per batch row
+// ApplyTimestampRules, GreedyDecoder.update at temperature 0, or -- per-row form, temperature_rows -- at a temperature per row); one
+// workgroup per batch row
 struct DecodeSelectArgs {
   const float* logits;                 // [B] rows, ld apart: the last position's fp32 logits
   int ld, n_vocab;
@@ -199,6 +200,10 @@ struct DecodeSelectArgs {
   const int* n_initial_rows;           // the timestamp history is tokens[b][n_initial_rows[b] : cur_len_rows[b]]
   const int* cap_rows;                 // sample budget: a row with cur_len - n_initial >= cap is a finished row (EOT, nothing added)
   int n_done_idx;                      // n_done[n_done_idx] += 1 per row whose new token is EOT (the step, not cur_len)
+  // the sampling form (per-row form only; temperature_rows != nullptr selects it; device [B] each): GreedyDecoder.update at temperature > 0,
+  // drawn by Gumbel-max over the filtered logits. A row at temperature 0 takes the argmax as the greedy form does, bit for bit.
+  const float* temperature_rows;            // T: next = argmax_v (lg[v] * (1 / T) + G(v)); sum_logprob still adds the UNTEMPERED log-softmax
+  const unsigned long long* seed_rows;      // Philox4x32-10 key (low word, high word); counter (v >> 2, cur_len - n_initial, 0, 0), word v & 3
 };
 hipError_t launch_decode_select(const DecodeSelectArgs& a, int B, hipStream_t s);
 // out[b] = softmax(logits[b])[token]  (no_speech_prob: the <|nospeech|> probability at the <|sot|> position)

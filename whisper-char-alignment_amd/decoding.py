@@ -9,7 +9,13 @@ decode in a given language (DecodingOptions(language=None) is refused: call dete
 temperature 0 without beam search (greedy), and conditioning on a prompt and / or
 a prefix (DecodingOptions(prompt=...), the decoder side of transcribe(initial_prompt=...); prefix=...), whose initial tokens
 go through the decoder in one batched forward (wca_greedy_decode_ex, prefill); a list of options gives every batch row a
-prompt / prefix of its own (wca_greedy_decode_rows). Anything else raises NotImplementedError instead of silently differing.
+prompt / prefix of its own (wca_greedy_decode_rows). Temperature sampling is opt-in through the engine-specific
+DecodingOptions(seed=<int>): with a seed, temperature > 0 draws every token from softmax(filtered logits / temperature), as
+upstream's GreedyDecoder.update does, and avg_logprob sums the untempered log-probabilities (wca_decode_rows_sampled; the rows of
+a list may differ in temperature and seed as well). The draw is Gumbel-max over Philox4x32-10 noise in the decode step's kernel
+(csrc/decode.hip): the law is upstream's, the draws are not torch's, because the generator differs; it is pinned token for token
+against a float64 restatement (tests/decode_sample_ref.py). With seed=None a temperature other than 0 raises as it always did,
+and beam_size / best_of / patience are refused either way. Anything else raises NotImplementedError instead of silently differing.
 PARITY UNPINNED against upstream itself for decode and detect_language alike (no real checkpoint is at hand): both are pinned
 against this repository's fp32 CPU oracle on synthetic weights.
 """
@@ -45,6 +51,8 @@ class DecodingOptions:
     max_initial_timestamp: Optional[float] = 1.0
     fp16: bool = True
     vocab_path: Optional[str] = None  # engine-specific: local tiktoken file for the tokenizer
+    seed: Optional[int] = None        # engine-specific: an int allows temperature > 0 (the engine's sampling is reproducible by
+                                      # construction and picks no seed for the caller); over a batch, row b draws with seed + b
 
 
 @dataclass(frozen=True)
@@ -97,7 +105,12 @@ def filter_masks(tokenizer, options, n_vocab):
 
 
 def _check_supported(options):
-    if options.temperature != 0.0 or options.beam_size is not None or options.best_of is not None or options.patience is not None:
+    sampling = options.temperature != 0.0 and options.seed is not None   # opt-in: without a seed every refusal is what it was
+    if sampling and not (isinstance(options.temperature, (int, float)) and 0.0 <= options.temperature < float("inf")):
+        raise ValueError("temperature must be a finite number >= 0, not %r" % (options.temperature,))
+    if options.seed is not None and (isinstance(options.seed, bool) or not isinstance(options.seed, (int, np.integer))):
+        raise ValueError("seed must be an int (or None: greedy decoding only), not %r" % (options.seed,))
+    if (options.temperature != 0.0 and not sampling) or options.beam_size is not None or options.best_of is not None or options.patience is not None:
         raise NotImplementedError("only greedy decoding (temperature 0, no beam search / best_of) is built; the reference "
                                   "uses DecodingOptions(language='en') (infer_ali.py:40)")
     if options.language is None:
@@ -168,24 +181,37 @@ def detect_language(model, mel, tokenizer=None, *, pcm=None, n_samples=None):
 
 
 @torch.no_grad()
-def decode(model, mel, options=DecodingOptions(), pcm=None, n_samples=None, encoded_batch=None, want_text=True):
+def decode(model, mel, options=DecodingOptions(), pcm=None, n_samples=None, encoded_batch=None, want_text=True, redecode=False,
+           row_sample_len=None):
     """whisper.decode. mel: [n_mels, 3000] or [B, n_mels, 3000] f32 cuda tensor (or None with pcm [B, stride] f32 cuda +
     n_samples, the log-mel then runs on the device; or neither with encoded_batch=B: decode the state queued by
     model.encode_batch). Returns DecodingResult or a list of them. want_text=False (transcribe without a vocabulary file) leaves
     `text` empty instead of decoding the token ids, which only the BPE vocabulary can do.
-    options may also be a list with one DecodingOptions per batch row; the rows may differ in prompt / prefix only (ValueError
-    otherwise): they then sit at different decoder positions (wca_greedy_decode_rows) and the result is always a list."""
+    options may also be a list with one DecodingOptions per batch row; the rows may differ in prompt / prefix / temperature / seed only
+    (ValueError otherwise): they then sit at different decoder positions (wca_greedy_decode_rows) and the result is always a list.
+    Sampling is opt-in through DecodingOptions(seed=<int>): temperature > 0 then draws every token from softmax(filtered logits /
+    temperature) as upstream's GreedyDecoder does, avg_logprob from the untempered log-probabilities (wca_decode_rows_sampled: Gumbel-max
+    over Philox noise -- upstream's law, not torch's draws). One DecodingOptions over B rows gives row b the seed (seed + b) mod 2^64; a
+    list gives every row its own. A row at temperature 0 is decoded greedily whatever its seed, and a call whose rows are all at
+    temperature 0 is exactly the greedy engine call.
+    redecode=True (mel = pcm = None, encoded_batch=B): decode AGAIN the state that the previous decode of these B rows left for the
+    alignment, with no encoder pass (the rungs of transcribe's temperature fallback); the state stays for align_batch(pcm=None).
+    row_sample_len (with a list of options; one int or None per row) caps a row's sampled tokens below its options' sample_len: the rows
+    of a re-decode whose first result was kept ride along for one token."""
     per_row = isinstance(options, (list, tuple))
     rows = list(options) if per_row else [options]
     if not rows:
         raise ValueError("an empty list of DecodingOptions")
     for o in rows:
         _check_supported(o)
-    common = [dataclasses.replace(o, prompt=None, prefix=None) for o in rows]
+    common = [dataclasses.replace(o, prompt=None, prefix=None, temperature=0.0, seed=None) for o in rows]
     for b, c in enumerate(common):
         if c != common[0]:
             diff = [f.name for f in dataclasses.fields(c) if getattr(c, f.name) != getattr(common[0], f.name)]
-            raise ValueError("the rows of one decode may differ in prompt / prefix only; row %d differs from row 0 in %s" % (b, ", ".join(diff)))
+            raise ValueError("the rows of one decode may differ in prompt / prefix / temperature / seed only; row %d differs from row 0 in %s"
+                             % (b, ", ".join(diff)))
+    if redecode and (mel is not None or pcm is not None or encoded_batch is None):
+        raise ValueError("redecode=True decodes the state of the previous decode again: pass mel = pcm = None and encoded_batch=B")
     single = mel is not None and mel.ndim == 2
     if single:
         mel = mel.unsqueeze(0)
@@ -195,13 +221,24 @@ def decode(model, mel, options=DecodingOptions(), pcm=None, n_samples=None, enco
     first, dims = rows[0], model.dims
     tokenizer = get_tokenizer(model.is_multilingual, language=first.language, task=first.task, vocab_path=first.vocab_path)
     plans = [decode_plan(tokenizer, o, dims.n_text_ctx) for o in rows]   # (initial tokens, sample_len, sot_index) per row
+    if row_sample_len is not None:
+        if not per_row or len(row_sample_len) != B:
+            raise ValueError("row_sample_len takes one entry per row of a list of DecodingOptions")
+        plans = [(p[0], p[1] if cap is None else max(1, min(p[1], int(cap))), p[2]) for p, cap in zip(plans, row_sample_len)]
     sup, blank = filter_masks(tokenizer, first, dims.n_vocab)
     max_init = -1
     if not first.without_timestamps and first.max_initial_timestamp is not None:
         max_init = round(first.max_initial_timestamp / (CHUNK_LENGTH / dims.n_audio_ctx))
     kw = dict(eot=tokenizer.eot, timestamp_begin=tokenizer.timestamp_begin, apply_timestamp_rules=not first.without_timestamps,
               max_initial_timestamp_index=max_init, batch=B, no_speech=tokenizer.no_speech if tokenizer.no_speech is not None else -1)
-    if per_row:
+    if redecode or any(o.temperature != 0.0 for o in rows):
+        if not per_row:   # one DecodingOptions over the batch: row b draws with seed + b
+            rows, plans = [dataclasses.replace(first, seed=None if first.seed is None else int(first.seed) + b) for b in range(B)], plans * B
+        tokens, n_tokens, sum_logprobs = model.decode_rows_sampled(mel, pcm, n_samples, [p[0] for p in plans], [p[2] for p in plans],
+                                                                   [p[1] for p in plans], sup, blank, redecode=redecode,
+                                                                   temperature=[float(o.temperature) for o in rows],
+                                                                   seed=[int(o.seed or 0) % (1 << 64) for o in rows], **kw)
+    elif per_row:
         tokens, n_tokens, sum_logprobs = model.greedy_decode_rows(mel, pcm, n_samples, [p[0] for p in plans], [p[2] for p in plans],
                                                                   [p[1] for p in plans], sup, blank, **kw)
     else:
@@ -209,12 +246,13 @@ def decode(model, mel, options=DecodingOptions(), pcm=None, n_samples=None, enco
         tokens, n_tokens, sum_logprobs = model.greedy_decode(mel, pcm, n_samples, initial, sup, blank, sample_len=sample_len, sot_index=sot_index,
                                                              prefill=1 if first.prompt or first.prefix else 0, **kw)
         plans = plans * B
+    rows = rows if len(rows) == B else rows * B
     no_speech_probs = model.last_no_speech_prob
     results = []
     for b in range(B):
         toks = [int(t) for t in tokens[b, len(plans[b][0]):n_tokens[b]]]
         text = tokenizer.decode(toks).strip() if want_text else ""
         results.append(DecodingResult(language=first.language, tokens=toks, text=text, avg_logprob=float(sum_logprobs[b]) / (len(toks) + 1),
-                                      no_speech_prob=float(no_speech_probs[b]), temperature=first.temperature,
+                                      no_speech_prob=float(no_speech_probs[b]), temperature=rows[b].temperature,
                                       compression_ratio=compression_ratio(text) if text else np.nan))
     return results[0] if single and not per_row else results

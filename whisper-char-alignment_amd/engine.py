@@ -477,9 +477,9 @@ class WhisperAMD:
         self._keep.append((mel, pcm))  # the kernels read these buffers asynchronously; up to two encodes are in flight
         return B
 
-    def _greedy_call(self, entry, opts, row_args, mel, pcm, n_samples, B, T, suppress_mask, blank_mask, no_speech):
-        """What greedy_decode and greedy_decode_rows share: the masks, the output arrays, the mel / pcm / n_samples and output pointer
-        arguments around the entry point's own row arguments, and last_no_speech_prob."""
+    def _greedy_call(self, entry, opts, row_args, mel, pcm, n_samples, B, T, suppress_mask, blank_mask, no_speech, tail=()):
+        """What greedy_decode, greedy_decode_rows and decode_rows_sampled share: the masks, the output arrays, the mel / pcm / n_samples and
+        output pointer arguments around the entry point's own row arguments (and, behind them, its `tail`), and last_no_speech_prob."""
         tokens = np.zeros((B, max(T, 1)), dtype=np.int32)
         n_tok = np.zeros(B, dtype=np.int32)
         lp = np.zeros(B, dtype=np.float32)
@@ -495,7 +495,7 @@ class WhisperAMD:
             pcm.shape[1] if pcm is not None else 0, _lib.i32_array(n_samples) if n_samples is not None else None, B, *row_args,
             sup.ctypes.data_as(C.c_void_p), blank.ctypes.data_as(C.c_void_p) if blank is not None else None, C.byref(opts),
             tokens.ctypes.data_as(_lib._pi32), n_tok.ctypes.data_as(_lib._pi32), lp.ctypes.data_as(_lib._pf),
-            nsp.ctypes.data_as(_lib._pf) if no_speech >= 0 else None))
+            nsp.ctypes.data_as(_lib._pf) if no_speech >= 0 else None, *tail))
         self.last_no_speech_prob = nsp
         return tokens, n_tok, lp
 
@@ -528,6 +528,31 @@ class WhisperAMD:
         T_max = max_b(len(initial_tokens[b]) + sample_len[b]), row b left-aligned; n_tokens [B]: row b's sampled tokens are
         tokens[b, len(initial_tokens[b]) : n_tokens[b]]; sum_logprobs [B]); self.last_no_speech_prob as greedy_decode. The initial
         tokens always go through the batched prefill; the encoder state stays for a following align_batch(pcm=None, ...)."""
+        return self._decode_rows(self._lib.wca_greedy_decode_rows, (), mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask,
+                                 blank_mask, eot, timestamp_begin, apply_timestamp_rules, max_initial_timestamp_index, batch, no_speech)
+
+    def decode_rows_sampled(self, mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask, blank_mask, eot, timestamp_begin,
+                            apply_timestamp_rules=True, max_initial_timestamp_index=50, batch=None, no_speech=-1, temperature=None, seed=None,
+                            redecode=False):
+        """C ABI wca_decode_rows_sampled: greedy_decode_rows with a temperature (float >= 0) and a seed (int, taken mod 2^64) PER ROW. A row
+        at temperature 0 is decoded greedily, bit for bit as greedy_decode_rows decodes it; a row at T > 0 draws each token from
+        softmax(filtered logits / T) by Gumbel-max with Philox noise keyed by its seed and counted by its sampled tokens, so a row's draws
+        do not depend on where in the batch it sits. sum_logprobs accumulates the untempered log-probability, as upstream does.
+        redecode=True (mel = pcm = None, batch=B): decode again the state the previous decode of these B rows left for
+        align_batch(pcm=None), with no encoder pass; the state is still there for the alignment afterwards."""
+        B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(batch))
+        if temperature is None or seed is None or len(temperature) != B or len(seed) != B:
+            raise ValueError("temperature and seed take one entry per batch row (%d)" % B)
+        temps = np.ascontiguousarray([float(t) for t in temperature], dtype=np.float32)
+        seeds = np.ascontiguousarray([int(v) % (1 << 64) for v in seed], dtype=np.uint64)
+        tail = (temps.ctypes.data_as(_lib._pf), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), 1 if redecode else 0)
+        return self._decode_rows(self._lib.wca_decode_rows_sampled, tail, mel, pcm, n_samples, initial_tokens, sot_index, sample_len,
+                                 suppress_mask, blank_mask, eot, timestamp_begin, apply_timestamp_rules, max_initial_timestamp_index, batch,
+                                 no_speech)
+
+    def _decode_rows(self, entry, tail, mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask, blank_mask, eot,
+                     timestamp_begin, apply_timestamp_rules, max_initial_timestamp_index, batch, no_speech):
+        """The per-row tables that greedy_decode_rows and decode_rows_sampled pass."""
         self._bind_stream()
         B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(batch))
         rows = [[int(t) for t in r] for r in initial_tokens]
@@ -542,7 +567,7 @@ class WhisperAMD:
         opts = _lib.DecodeOpts(max(int(v) for v in sample_len) if B else 0, int(eot), int(timestamp_begin), 1 if apply_timestamp_rules else 0,
                                int(max_initial_timestamp_index), int(no_speech))
         row_args = (init.ctypes.data_as(_lib._pi32), _lib.i32_array(n_init), _lib.i32_array(sot_index), _lib.i32_array(sample_len))
-        return self._greedy_call(self._lib.wca_greedy_decode_rows, opts, row_args, mel, pcm, n_samples, B, T, suppress_mask, blank_mask, no_speech)
+        return self._greedy_call(entry, opts, row_args, mel, pcm, n_samples, B, T, suppress_mask, blank_mask, no_speech, tail)
 
     def detect_language(self, mel=None, tokenizer=None, *, pcm=None, n_samples=None, batch=None, sot=None, lang_begin=None, n_lang=None):
         """model.detect_language(mel, tokenizer) -> (language_tokens, language_probs), upstream's schema (decoding.detect_language).

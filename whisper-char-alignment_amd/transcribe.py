@@ -15,9 +15,18 @@ on the encoder state that decode left in the engine (align_batch(pcm=None): no s
 (`seek_loop`) is host Python over two callables, so it runs without a GPU against a scripted decoder.
 
 Limits (part of the contract):
-  * temperature is 0.0 (or a tuple holding only 0.0); anything else raises NotImplementedError -- the fallback ladder needs
-    sampling, which decoding._check_supported refuses. Without a ladder compression_ratio_threshold / logprob_threshold
-    cannot trigger a re-decode: the temperature-0 result is accepted, as upstream accepts the last rung of its ladder.
+  * the temperature fallback ladder is opt-in through seed=<int>. Without a seed (the default) temperature is 0.0 (or a tuple holding
+    only 0.0) and anything else raises NotImplementedError, as before the sampler existed: the engine's sampling is reproducible by
+    construction and picks no seed for the caller. With a seed, temperature may be upstream's (0.0, 0.2, 0.4, 0.6, 0.8, 1.0) or any
+    number or non-empty tuple: a window whose result has compression_ratio > compression_ratio_threshold (2.4) or avg_logprob <
+    logprob_threshold (-1), and is not taken for silence, is decoded again at the next temperature, on the encoder state its first
+    decode left in the engine (wca_decode_rows_sampled, redecode: a rung costs decoder positions only, where upstream encodes the window
+    again); the last rung is accepted whatever it gives, and a window accepted above 0.5 does not condition the next one. Without a
+    vocabulary the compression ratio is NaN and only the log-probability test can fire. What is pinned: the sampler against a float64
+    restatement, token for token (tests/test_decode_sample_gpu.py), and the ladder's mechanics (tests/test_transcribe_ladder.py). What is
+    not: the law of the draws is upstream's (Categorical(logits / T), untempered log-probabilities), the draws themselves are not
+    torch's -- another generator --, and what the ladder does to repetition loops on real speech is UNVALIDATED: no checkpoint is at
+    hand, and random weights fall through every rung.
   * the language is given, or language="auto" detects it (decoding.detect_language, C ABI wca_detect_language) on each recording's
     first window mel_window(mel, 0, size) -- the frames the first decode sees; upstream also detects on the first 30 s -- in the
     99-language numbering of the decode tokenizer, so the detected token is the one that lands in the sot sequence. The first windows
@@ -82,16 +91,48 @@ from .tokenizer import get_tokenizer  # noqa: E402
 PLACEHOLDER_FRAMES = 100   # max_frames of a row that rides along in a round's alignment without words
 
 
-def check_supported(temperature, language):
-    """What this transcribe refuses instead of silently differing from upstream."""
+SEEK_MIX, RUNG_MIX = 0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9
+
+
+def window_seed(seed, seek, rung):
+    """The Philox seed a window is sampled with: the call's seed mixed with the window's first frame and the index of the temperature in
+    the ladder, so that a recording's draws do not depend on the batch row or the group it rides in."""
+    return (int(seed) ^ (int(seek) * SEEK_MIX) ^ (int(rung) * RUNG_MIX)) % (1 << 64)
+
+
+def check_supported(temperature, language, seed=None):
+    """What this transcribe refuses instead of silently differing from upstream. Returns the temperature ladder: 0.0 without a seed (any
+    other temperature is refused then, as it always was), with an int seed the tuple of temperatures (a number or a non-empty sequence of
+    finite numbers >= 0, as upstream takes them)."""
     temps = tuple(temperature) if isinstance(temperature, (tuple, list)) else (temperature,)
-    if len(temps) != 1 or float(temps[0]) != 0.0:
+    if seed is not None:
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+            raise ValueError("seed must be an int (or None: temperature 0.0 only), not %r" % (seed,))
+        if not temps or not all(isinstance(t, (int, float, np.integer, np.floating)) and 0.0 <= float(t) < float("inf") for t in temps):
+            raise ValueError("temperature must be a finite number >= 0 or a non-empty tuple of them, not %r" % (temperature,))
+    elif len(temps) != 1 or float(temps[0]) != 0.0:
         raise NotImplementedError("transcribe runs at temperature 0.0 only: the fallback ladder %r needs sampling, which the engine's "
                                   "greedy decode does not do (decoding._check_supported)" % (temperature,))
     if language is None:
         raise NotImplementedError("language=None is not taken: pass language=\"auto\" to detect it on the first window "
                                   "(decoding.detect_language), or the language itself (as DecodingOptions(language=...) in decode)")
-    return 0.0
+    return 0.0 if seed is None else tuple(float(t) for t in temps)
+
+
+def needs_fallback(result, compression_ratio_threshold, logprob_threshold, no_speech_threshold):
+    """Upstream's decode_with_fallback rule for one window: too repetitive (compression ratio above its threshold) or too improbable
+    (average log-probability below its threshold) -- unless the window is taken for silence (no_speech_prob above its threshold and the
+    average log-probability below its own), which the seek loop skips anyway. A threshold of None switches its test off; a NaN
+    compression ratio (no vocabulary: no text to compress) never fires."""
+    fallback = False
+    if compression_ratio_threshold is not None and result.compression_ratio > compression_ratio_threshold:
+        fallback = True
+    if logprob_threshold is not None and result.avg_logprob < logprob_threshold:
+        fallback = True
+    if (no_speech_threshold is not None and result.no_speech_prob > no_speech_threshold and logprob_threshold is not None and
+            result.avg_logprob < logprob_threshold):
+        fallback = False
+    return fallback
 
 
 def split_window(tokens, timestamp_begin, eot, seek, size, result, decode_text):
@@ -214,11 +255,11 @@ class SeekState:
         segments, advance, max_frames = split_window(result.tokens, self.tokenizer.timestamp_begin, self.tokenizer.eot, seek, size, result,
                                                      self.decode_text)
         window["max_frames"], window["advance"] = max_frames, advance
-        self._pending = (window, segments, advance)
+        self._pending = (window, segments, advance, result.temperature)
         return seek, size, max_frames, segments
 
     def commit(self, aligned=None):
-        window, segments, advance = self._pending
+        window, segments, advance, temperature = self._pending
         self._pending = None
         if aligned is not None:
             window["aligned"] = bool(aligned)
@@ -227,7 +268,8 @@ class SeekState:
         self._settle()
         self.all_segments.extend({"id": i, **seg} for i, seg in enumerate(segments, start=len(self.all_segments)))
         self.all_tokens.extend(t for seg in segments for t in seg["tokens"])
-        if not self.condition_on_previous_text:
+        # (as upstream: a window rescued at a high temperature does not condition the next one; a greedy result never gets here)
+        if not self.condition_on_previous_text or (temperature is not None and temperature > 0.5):
             self.prompt_reset_since = len(self.all_tokens)
 
     def result(self):
@@ -377,9 +419,15 @@ def transcribe(model, audio, *, language, decode_window=None, **options):
     from initial_prompt only and conditions on its own previous text. The result then carries "pieces" and every window its "piece"
     (transcribe_batch has the details). pieces and clip_timestamps together are a ValueError.
     decode_window(mel_window, prompt_tokens) -> DecodingResult replaces the engine's greedy decode (tests; with pieces it is called row by
-    row); decode_options go to DecodingOptions. Limits: module docstring. It is transcribe_batch of one recording, whose single row is
+    row; with seed= it is also given temperature= and seed=, transcribe_batch's temperatures= / seeds= for its row); decode_options go to DecodingOptions. Limits: module docstring. It is transcribe_batch of one recording, whose single row is
     decoded and aligned alone. The other keywords and their defaults are transcribe_batch's."""
-    row_by_row = None if decode_window is None else (lambda mel_windows, prompts: [decode_window(w, p) for w, p in zip(mel_windows, prompts)])
+    def row_by_row(mel_windows, prompts, temperatures=None, seeds=None):
+        if temperatures is None:
+            return [decode_window(w, p) for w, p in zip(mel_windows, prompts)]
+        return [decode_window(w, p, temperature=t, seed=s) for w, p, t, s in zip(mel_windows, prompts, temperatures, seeds)]   # (with seed=)
+
+    if decode_window is None:
+        row_by_row = None
     return transcribe_batch(model, [audio], language=language, decode_windows=row_by_row, **options)[0]
 
 
@@ -387,8 +435,10 @@ class _Call:
     """What one transcribe_batch call carries from round to round: the model and options, one tokenizer per language code, the initial prompt's
     tokens, and `state_left`: rows of encoded, undecoded state the engine's own detection left behind for the decode that comes next."""
 
-    def __init__(self, model, language, initial_prompt, vocab_path, decode_options, decode_windows, detect_languages, seek_options, aligner_options):
+    def __init__(self, model, language, initial_prompt, vocab_path, decode_options, decode_windows, detect_languages, seek_options, aligner_options,
+                 temperatures=(0.0,), seed=None, compression_ratio_threshold=2.4):
         self.model, self.vocab_path, self.decode_options, self.seek_options = model, vocab_path, decode_options, seek_options
+        self.temperatures, self.seed, self.compression_ratio_threshold = temperatures, seed, compression_ratio_threshold   # seed None: no ladder
         self.decode_windows, self.detect_languages, self.aligner_options = decode_windows, detect_languages, aligner_options   # (None: no words)
         self.auto = isinstance(language, str) and language.lower() == "auto"
         self.tokenizers, self.state_left, self.prompt_tokens = {}, None, []
@@ -415,13 +465,46 @@ class _Call:
         codes = [tok.all_language_codes[int(t) - tok.all_language_tokens[0]] for t in tokens]
         return codes, [p[c] for c, p in zip(codes, probs)]
 
-    def decode(self, code, mel_windows, prompts):
-        """One round's decode: a DecodingResult per row, every row with its own previous text as the prompt."""
-        if self.decode_windows is not None:
-            return self.decode_windows(mel_windows, prompts)
+    def decode(self, code, mel_windows, prompts, seeks=None):
+        """One round's decode: a DecodingResult per row, every row with its own previous text as the prompt. With a seed (seeks: the
+        windows' first frames) the round walks upstream's temperature ladder: every row at temperatures[0]; then, while a row needs a
+        fallback (needs_fallback) and rungs remain, the SAME encoded state is decoded again (decoding.decode(redecode=True): decoder
+        positions only, where upstream encodes the window again) with the failed rows at the next temperature and the accepted rows
+        riding along on a sample budget of 1, their output ignored: a decoded position costs about the same for 16 rows as for one. The
+        last rung is accepted whatever it gives. Row b of rung r draws with window_seed(seed, seeks[b], r). The state is left decoded,
+        for the round's one alignment."""
+        if self.seed is None:
+            return self.decode_windows(mel_windows, prompts) if self.decode_windows is not None else self.decode_rung(code, mel_windows, prompts)
+        n, ladder = len(prompts), self.temperatures
+        results, failed = [None] * n, [True] * n
+        for rung, t in enumerate(ladder):
+            seeds = [window_seed(self.seed, seek, rung) for seek in seeks]
+            temps = [t if f else None for f in failed]   # None: the row is accepted; whatever it gives now is ignored
+            if self.decode_windows is not None:
+                got = self.decode_windows(mel_windows, prompts, temperatures=temps, seeds=seeds)
+            else:
+                got = self.decode_rung(code, mel_windows, prompts, temps, seeds, redecode=rung > 0)
+            for b in range(n):
+                if failed[b]:
+                    results[b] = got[b]
+                    failed[b] = rung + 1 < len(ladder) and needs_fallback(got[b], self.compression_ratio_threshold, self.seek_options["logprob_threshold"],
+                                                                          self.seek_options["no_speech_threshold"])
+            if not any(failed):
+                break
+        return results
+
+    def decode_rung(self, code, mel_windows, prompts, temperatures=None, seeds=None, redecode=False):
+        """The engine's decode of a round's rows. temperatures None: at temperature 0, the call it always was."""
+        greedy = temperatures is None or all(t == 0.0 for t in temperatures)
+        temperatures, seeds = temperatures or [0.0] * len(prompts), seeds or [None] * len(prompts)
         rows = [decoding.DecodingOptions(language=code, temperature=0.0, prompt=list(p) or None, vocab_path=self.vocab_path, **self.decode_options)
-                for p in prompts]
+                if greedy or not t else
+                decoding.DecodingOptions(language=code, temperature=t, seed=s, prompt=list(p) or None, vocab_path=self.vocab_path, **self.decode_options)
+                for p, t, s in zip(prompts, temperatures, seeds)]
         want_text = self.vocab_path is not None
+        if redecode:   # a later rung: the state of this round's first decode again, the accepted rows (None) for one token
+            return decoding.decode(self.model, None, rows, encoded_batch=len(rows), want_text=want_text, redecode=True,
+                                   row_sample_len=[None if t is not None else 1 for t in temperatures])
         waiting, self.state_left = self.state_left == len(rows), None
         if waiting:   # the first round of a group that detection found in one language: its state is waiting
             return decoding.decode(self.model, None, rows[0] if len(rows) == 1 else rows, encoded_batch=len(rows), want_text=want_text)
@@ -500,7 +583,7 @@ def lock_step(call, code, rows, mels, plans):
             return states
         requests = [states[u].request() for u in live]
         windows = cut_windows(call.model, mels, [(u[0], seek, size) for u, (seek, size, _) in zip(live, requests)])
-        decoded = call.decode(code, windows, [prompt for _, _, prompt in requests])
+        decoded = call.decode(code, windows, [prompt for _, _, prompt in requests], [seek for seek, _, _ in requests])
         pending = [states[u].receive(r) for u, r in zip(live, decoded)]
         aligned = aligner.align_round(pending) if aligner is not None else [None] * len(live)
         for u, pend, al in zip(live, pending, aligned):
@@ -532,7 +615,8 @@ def merge_pieces(outs, pieces, *, tokenizer, language, extra, n_prompt):
 def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_on_previous_text=True, no_speech_threshold=0.6,
                      logprob_threshold=-1.0, word_timestamps=False, word_confidence=False, aligned_unit_type="char", aggr="topk", topk=10,
                      medfilt_width=3, vocab_path=None, temperature=0.0, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0, decode_windows=None,
-                     detect_languages=None, sample_rate=SAMPLE_RATE, clip_timestamps=None, pieces=None, **decode_options):
+                     detect_languages=None, sample_rate=SAMPLE_RATE, clip_timestamps=None, pieces=None, seed=None,
+                     compression_ratio_threshold=2.4, **decode_options):
     """transcribe() of several recordings in lock-step: a list with transcribe()'s result for every recording of `audios`, in order.
     Each round cuts the next window of every unfinished recording, decodes them in ONE batch with every row's own previous text as its
     prompt (decoding.decode with one DecodingOptions per row: wca_greedy_decode_rows) and, with word_timestamps, aligns the rows that
@@ -557,8 +641,17 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
     carries "pieces": [{"start_frame", "stop_frame", "level"}], level being the smoothed level (wca_quiet_cuts) at the cut the piece starts
     at, None for the first. language="auto" still detects on the recording's first window and all its pieces take that language; the first
     round then has other rows than the detection saw, so the state detection left in the engine is simply dropped and the round encodes
-    its own windows. Without pieces and clip_timestamps the result is what it was before either existed."""
-    check_supported(temperature, language)
+    its own windows. Without pieces and clip_timestamps the result is what it was before either existed.
+    seed (an int; None: temperature 0.0 only, every call as it always was) switches on upstream's temperature fallback: temperature may
+    then be a number or a tuple such as upstream's default (0.0, 0.2, 0.4, 0.6, 0.8, 1.0), and a window whose result is too repetitive
+    (compression_ratio > compression_ratio_threshold) or too improbable (avg_logprob < logprob_threshold), and not taken for silence, is
+    decoded again at the next temperature (_Call.decode; needs_fallback) with the seed window_seed(seed, seek, rung). A threshold of None
+    switches its test off; without a vocabulary there is no text, the compression ratio is NaN and that test never fires. A segment's
+    "temperature" is the rung its window was accepted at, and a window accepted above 0.5 does not condition the next one. With a seed
+    decode_windows is also given temperatures= (one per row; None for a row whose earlier result was kept and whose new one is ignored)
+    and seeds= (one per row). The law of the draws is upstream's, the draws are not (decoding.decode); what the ladder does to real
+    speech is UNVALIDATED here (module docstring)."""
+    temperatures = check_supported(temperature, language, seed)
     if pieces is not None and clip_timestamps is not None:
         raise ValueError("pieces cuts the whole recording: it cannot be combined with clip_timestamps")
     if word_confidence and not word_timestamps:
@@ -573,7 +666,8 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
     seek = dict(condition_on_previous_text=condition_on_previous_text, no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold)
     words = dict(aligned_unit_type=aligned_unit_type, aggr=aggr, topk=topk, medfilt_width=medfilt_width, w_colnorm=w_colnorm,
                  w_rownorm=w_rownorm, w_coverage=w_coverage, word_confidence=word_confidence) if word_timestamps else None
-    call = _Call(model, language, initial_prompt, vocab_path, decode_options, decode_windows, detect_languages, seek, words)
+    call = _Call(model, language, initial_prompt, vocab_path, decode_options, decode_windows, detect_languages, seek, words,
+                 *(() if seed is None else (temperatures, int(seed), compression_ratio_threshold)))
     audios = list(audios)
     results = [None] * len(audios)
     for group, mels, plans in form_groups(model, audios, sample_rates(sample_rate, len(audios)), clip_timestamps, pieces, max_batch):
@@ -612,7 +706,23 @@ def parse_args(argv=None):
                    "decoded side by side (auto: as many as --batch rows allow, at least 60 s each); needs --batch >= N")
     p.add_argument("--clip_timestamps", type=str, default=None, metavar="a,b,...", help="transcribe only these ranges: start,end,start,end,... in "
                    "seconds (an odd count runs to the end of the recording)")
+    # the temperature fallback (needs --seed). An option that is not given is absent from the namespace (main reads the defaults named here):
+    # without --seed the parsed arguments and the call they make are what they were before the ladder existed
+    ladder = dict(default=argparse.SUPPRESS)
+    p.add_argument("--seed", type=int, help="switches on the temperature fallback: windows that loop or are improbable are decoded again with "
+                   "sampling, reproducibly for this seed (default: none, temperature 0 only)", **ladder)
+    p.add_argument("--temperature", type=float, help="the first temperature (default 0; anything else needs --seed)", **ladder)
+    p.add_argument("--temperature_increment_on_fallback", type=float, help="the ladder's step up to 1.0 (upstream's default is 0.2; default: "
+                   "none, --temperature alone)", **ladder)
+    p.add_argument("--compression_ratio_threshold", type=float, help="default 2.4", **ladder)
     return p.parse_args(argv)
+
+
+def temperature_ladder(temperature, increment):
+    """upstream's cli: np.arange(temperature, 1.0 + 1e-6, increment) as a tuple, or the one temperature without an increment."""
+    if increment is None:
+        return (float(temperature),)
+    return tuple(float(t) for t in np.arange(temperature, 1.0 + 1e-6, increment))
 
 
 def _recordings(args):
@@ -646,6 +756,11 @@ def main(args, model=None):
               **{k: getattr(args, k) for k in ALIGNER_KEYWORDS})
     if args.pieces is not None or args.clip_timestamps is not None:   # (otherwise the call is what it was before either existed)
         kw.update(pieces=args.pieces, clip_timestamps=args.clip_timestamps)
+    if getattr(args, "seed", None) is not None:   # (likewise: without --seed the call is what it was)
+        kw.update(seed=args.seed, compression_ratio_threshold=getattr(args, "compression_ratio_threshold", 2.4),
+                  temperature=temperature_ladder(getattr(args, "temperature", 0.0), getattr(args, "temperature_increment_on_fallback", None)))
+    elif getattr(args, "temperature", 0.0) != 0.0 or getattr(args, "temperature_increment_on_fallback", None) is not None:
+        raise SystemExit("--temperature / --temperature_increment_on_fallback sample: pass --seed <int>")
     for group in groups_of(_recordings(args), args.batch):   # a group's files are written before the next group starts
         if args.batch > 1:
             results = transcribe_batch(model, [source(path) for _, path in group], **kw)
