@@ -27,27 +27,23 @@
  *                          [len(sot_sequence):-1] slice (timing.py:102), DTW + backtrace (timing.py:103)
  *   wca_default_find_alignment  timing.py:116-186 default_find_alignment (std/mean normalised alignment heads)
  *   wca_dtw                timing.py:103     whisper.timing.dtw -> dtw_cpu + backtrace
- *   wca_dtw_open, wca_dtw_batch_dev_open, wca_align_batch_enqueue_open / wca_align_batch_fetch_open
+ *   wca_dtw_open, wca_dtw_batch_dev_open, wca_align_desc.open_end_host
  *                          no counterpart in the reference or upstream (their aligners stop at one 30 s window): the OPEN-END form
  *                          of the same DTW, for a window of a long recording that holds only a prefix of the text it is offered
  *                          (align_long.py: a recording of any length against a given transcript)
  *   wca_probe_heads        probe_oracle.py:83-90  per-head force_align sweep (one DTW per head)
- *   wca_greedy_decode      infer_ali.py:40,60-61, probe_oracle.py:59-60, README.md:107-108:
+ *   wca_decode             infer_ali.py:40,60-61, probe_oracle.py:59-60, README.md:107-108:
  *                          whisper.decode(model, mels, DecodingOptions(language="en")) -- the greedy ASR pre-pass
  *                          that produces the teacher text (upstream decoding.py: KV-cached autoregressive
- *                          decoder, SuppressBlank / SuppressTokens / ApplyTimestampRules, GreedyDecoder)
- *   wca_greedy_decode_ex   the same with DecodingOptions(prompt=..., prefix=...) (transcribe(initial_prompt=...)): any
- *                          initial token row, <|sot|> at sot_index, and the batched prefill of upstream's first forward
- *   wca_greedy_decode_rows the same for a batch whose rows carry initial tokens (prompts) of their own, of their own lengths, and
- *                          their own sample budgets: the rows sit at different decoder positions (transcribe_batch: several
- *                          recordings in lock-step, each conditioned on its own previous text)
- *   wca_decode_rows_sampled the same with a temperature and a seed per row (upstream GreedyDecoder at temperature > 0), and optionally on
- *                          the encoder state the previous decode left (the rungs of transcribe's temperature fallback ladder)
+ *                          decoder, SuppressBlank / SuppressTokens / ApplyTimestampRules, GreedyDecoder); through the fields of
+ *                          wca_decode_desc also DecodingOptions(prompt=..., prefix=...) (transcribe(initial_prompt=...)), rows with
+ *                          prompts and sample budgets of their own (transcribe_batch), and upstream's GreedyDecoder at temperature > 0
+ *                          (the rungs of transcribe's temperature fallback ladder)
  *   wca_align_batch       infer_ali.py:93-101 + dataset.py:47-48: the whole per-utterance pipeline
  *                          (log-mel -> forward+capture -> medfilt/softmax -> scores/top-k ->
  *                          aggregate -> DTW) for a micro-batch of utterances, results = the frame
  *                          at which the DTW path enters every token row (timing.py:110-111 `jumps`)
- *   wca_align_batch_enqueue_ex / wca_align_batch_fetch_ex, wca_token_logprobs
+ *   wca_align_desc.vocab_end / wca_align_result.token_logprob_host, wca_token_logprobs
  *                          timing.py:146-150 (`text_token_probs`: softmax of logits[len(sot_sequence):, :eot] at the
  *                          teacher token) and timing.py:181-184 (`word_probabilities`, the per-word mean the host forms):
  *                          the teacher-token log-probabilities, computed and kept on the GPU
@@ -110,7 +106,7 @@ typedef struct {
 } wca_align_opts;
 
 const char* wca_last_error(void);
-int wca_version(void);   /* 15: wca_quiet_cuts (where to cut one long recording into pieces decoded side by side); 14: the open-end DTW entry points; 13: wca_detect_language (the language head on the encoded state; the decode that follows re-uses the state); 12: wca_resample_plan, wca_resample_table, wca_resample_16k (any input rate to 16 kHz); 11: wca_greedy_decode_rows (per-row prompts and sample budgets); 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: wca_greedy_decode_ex (prompt / prefix: sot_index, batched prefill); 7: exactly two precision modes */
+int wca_version(void);   /* 17: one descriptor call each for decode (wca_decode, wca_decode_desc) and the fused alignment (wca_align_desc, wca_align_result) in place of the eleven entry points that had grown feature by feature; 16: the CU-partition and two-stream decode experiments are gone; 15: wca_quiet_cuts (where to cut one long recording into pieces decoded side by side); 14: the open-end DTW entry points; 13: wca_detect_language (the language head on the encoded state; the decode that follows re-uses the state); 12: wca_resample_plan, wca_resample_table, wca_resample_16k (any input rate to 16 kHz); 11: per-row prompts and sample budgets in the decode; 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: prompt / prefix in the decode (sot_index, batched prefill); 7: exactly two precision modes */
 
 /* ---- engine lifetime ------------------------------------------------------------------------ */
 /* A new engine is in the CONTRACT precision mode (WCA_PRECISION_REFERENCE: every stage on (hi, lo) operand pairs = the fp32 forward of
@@ -184,7 +180,7 @@ int wca_resample_16k(wca_engine* e, const float* in_dev, int channels, int64_t l
 /* pad_or_trim(mel[:, seek : seek + size], 3000) for `batch` windows of one long mel (mel_long_dev [n_mels][ld] f32 with n_frames valid
  * frames, as wca_log_mel_long leaves it): mel_out_dev [batch][n_mels][3000] f32 with exact zeros at frames >= size -- the zero padding
  * of the MEL domain that upstream's loop feeds its last, short window (not the log-mel of silence). The result is what
- * wca_greedy_decode / wca_encode_batch / wca_get_attentions take as mel_dev. size outside [1, 3000], seek < 0 or seek + size > n_frames
+ * wca_decode / wca_encode_batch / wca_get_attentions take as mel_dev. size outside [1, 3000], seek < 0 or seek + size > n_frames
  * is WCA_ERR_INVALID (nothing is read); batch <= max_batch. */
 int wca_mel_window(wca_engine* e, const float* mel_long_dev, int64_t ld, int64_t n_frames, const int32_t* seek_host,
                    const int32_t* size_host, int batch, float* mel_out_dev);
@@ -289,22 +285,57 @@ int wca_probe_heads(wca_engine* e, const float* ws_dev, int L, int H, int n, int
 int wca_probe_strict_tp(wca_engine* e, int n_heads, const int32_t* word_end_row_host, int n_hyp, const double* ref_times_host, int n_ref,
                         const uint8_t* same_word_host, double tolerance, int32_t* tp_host);
 
-/* Fused per-utterance pipeline for a micro-batch (the north-star hot path).
- * pcm_dev [batch][pcm_stride] f32 (NULL: re-use the encoder state of the preceding wca_greedy_decode of this
- * batch); tokens_dev [batch][n_tok_max] int64; n_tok_host, n_samples_host, max_frames_host [batch].
- * jump_frame_host [batch][n_tok_max]: for utterance b, entries [0, n_tok[b] - sot_len - 1) are the frame
- * index at which the DTW path enters that text row (jump_times * 50, timing.py:110-111); the remaining entries of a row are 0.
- * sel_idx_host [batch][topk] may be NULL. */
-int wca_align_batch(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
-                    const int64_t* tokens_dev, int n_tok_max, const int32_t* n_tok_host,
-                    const int32_t* max_frames_host, int batch, const wca_align_opts* opts, int32_t* jump_frame_host,
-                    int32_t* sel_idx_host);
-
-/* whisper.DecodingOptions as the reference uses it (infer_ali.py:40: language="en", everything else default:
- * task transcribe, temperature 0 -> greedy, no beam, sample_len n_text_ctx // 2, suppress_blank, suppress_tokens "-1",
- * without_timestamps False, max_initial_timestamp 1.0, no prompt / prefix: those take wca_decode_opts_ex). */
+/* Fused per-utterance pipeline for a micro-batch (the north-star hot path), and the teacher-token log-probabilities
+ * (timing.py:146-150 of the reference: text_token_probs = softmax(logits[len(sot_sequence):, :eot]) at the teacher token, here in log
+ * space; the per-word mean of timing.py:181-184 is the caller's). A zero in an optional field means "off". */
 typedef struct {
-  int32_t sample_len;                  /* maximum number of sampled tokens (224)                              */
+  const float* pcm_dev;             /* [batch][pcm_stride] f32; NULL: consume the oldest encoded state of this batch (wca_encode_batch, or
+                                       the one the preceding wca_decode left) instead of running phase 1                                  */
+  const int32_t* n_samples_host;    /* [batch]; required with pcm_dev                                                                   */
+  const int64_t* tokens_dev;        /* [batch][n_tok_max] int64, each row [*sot_sequence, no_timestamps, *text, eot]                      */
+  const int32_t* n_tok_host;        /* [batch]: row b's true length                                                                     */
+  const int32_t* max_frames_host;   /* [batch]                                                                                          */
+  const wca_align_opts* opts;
+  const int32_t* open_end_host;     /* [batch], nullable: row b's DTW is open-ended (wca_dtw_open) where open_end_host[b] != 0; a row with 0
+                                       gets exactly the closed result. Everything upstream of the DTW is unchanged.                       */
+  int64_t pcm_stride;
+  int32_t n_tok_max;
+  int32_t batch;
+  int32_t vocab_end;                /* in (0, n_vocab] (= tokenizer.eot): also compute the teacher-token log-probs; 0: none. With them the
+                                       decoder finishes its last layer and the n_text_b = n_tok[b] - sot_len - 2 text rows of every utterance
+                                       go through the final LayerNorm, the vocabulary projection (tok_emb rows [0, vocab_end)) and a
+                                       log-sum-exp kernel on the engine's second stream; the [rows][vocab] logits never reach the host. The
+                                       jump frames and top-k heads are the same with and without them.                                   */
+} wca_align_desc;
+
+typedef struct {
+  int32_t* jump_frame_host;   /* [batch][n_tok_max]: for utterance b, entries [0, n_tok[b] - sot_len - 1) are the frame index at which the
+                                 DTW path enters that text row (jump_times * 50, timing.py:110-111); the remaining entries of a row are 0.
+                                 Entries (end_row, n_tok[b] - sot_len - 1) of an open row are -1.                                        */
+  int32_t* sel_idx_host;      /* [batch][topk], nullable: the selected heads                                                             */
+  float* token_logprob_host;  /* [batch][n_tok_max] f32, nullable: entry i < n_text_b of row b is
+                                 log_softmax(logits[b][sot_len + i][0 : vocab_end])[tokens[b][sot_len + 1 + i]], the rest 0; the prediction of
+                                 eot is not scored, as in the reference. A teacher token >= vocab_end has no value: NaN, and the fetch returns
+                                 WCA_ERR_INVALID.                                                                                        */
+  int32_t* end_row_host;      /* [batch], nullable: the last text row of row b's path, counted in DTW rows, i.e. from the first token after
+                                 the sot sequence: n_tok[b] - sot_len - 2 for a closed row; -1 where no DTW ran                           */
+  float* score_host;          /* [batch], nullable: wca_dtw_open's score of the end cell                                                 */
+} wca_align_result;
+
+/* wca_align_batch_enqueue only enqueues the work on the engine stream (no host sync; results stay in the engine's pinned staging ring until
+ * wca_align_batch_fetch). Up to TWO batches may be in flight: wca_align_batch_fetch returns the OLDEST pending one (waiting on its HIP event
+ * only), so the host can post-process batch i while batch i+1 runs; batch, n_tok_max and topk must be those of that enqueue.
+ * WCA_ERR_STATE (and nothing consumed) when token_logprob_host is given but the pending batch was enqueued with vocab_end = 0, or when
+ * end_row_host / score_host are given but it was enqueued without open_end_host. wca_align_batch is the enqueue, then the fetch. */
+int wca_align_batch_enqueue(wca_engine* e, const wca_align_desc* d);
+int wca_align_batch_fetch(wca_engine* e, int batch, int n_tok_max, int topk, const wca_align_result* r);
+int wca_align_batch(wca_engine* e, const wca_align_desc* d, const wca_align_result* r);
+
+/* The filter fields of whisper.DecodingOptions as the reference uses it (infer_ali.py:40: language="en", everything else default:
+ * task transcribe, suppress_blank, suppress_tokens "-1", without_timestamps False, max_initial_timestamp 1.0). */
+typedef struct {
+  int32_t sample_len;                  /* upstream's sample_len (224 = n_text_ctx // 2), kept for the callers' bookkeeping: wca_decode takes
+                                          every budget, the shared one of a per_row 0 call too, from sample_len_host and does not read it */
   int32_t eot;                         /* tokenizer.eot                                                       */
   int32_t timestamp_begin;             /* tokenizer.timestamp_begin (<|0.00|>)                                */
   int32_t apply_timestamp_rules;       /* 1 = ApplyTimestampRules (without_timestamps False)                  */
@@ -312,160 +343,104 @@ typedef struct {
   int32_t no_speech;                   /* tokenizer.no_speech (<|nospeech|>) for no_speech_prob; < 0 = skip   */
 } wca_decode_opts;
 
-/* wca_decode_opts plus what a prompted decode (DecodingOptions(prompt=..., prefix=...)) needs. */
-typedef struct {
-  int32_t sample_len;                  /* maximum number of sampled tokens                                    */
-  int32_t eot;
-  int32_t timestamp_begin;
-  int32_t apply_timestamp_rules;
-  int32_t max_initial_timestamp_index;
-  int32_t no_speech;
-  int32_t sot_index;                   /* position of <|startoftranscript|> in the initial tokens: no_speech_prob is read
-                                          from its logits (after a prompt: [sot_prev, prompt..., sot, ...])   */
-  int32_t prefill;                     /* 0: the initial tokens go through the decoder one position at a time (one decode
-                                          step each, as wca_greedy_decode does); 1: one batched forward over all of them
-                                          (causal self-attention, each layer's cross-K/V read once), upstream's first
-                                          forward. The two agree up to f16 / fp32 summation order. */
-} wca_decode_opts_ex;
-
-/* Greedy ASR pre-pass for a micro-batch. At most one of mel_dev ([batch][n_mels][3000] f32, what whisper.decode
- * takes) and pcm_dev ([batch][pcm_stride] f32 + n_samples_host, log-mel computed on the device) is non-NULL; with
- * both NULL the oldest undecoded state of wca_encode_batch is decoded.
- * initial_tokens_host [n_initial]: tokenizer.sot_sequence (every row starts with it).
- * suppress_mask_host [n_vocab] bytes: 1 = logit forced to -inf at every step (SuppressTokens list and, when the
- *   timestamp rules are on, <|notimestamps|>); blank_mask_host [n_vocab] (nullable): 1 = -inf at the first sampled
- *   position (SuppressBlank: tokenizer.encode(" ") + [eot]).
- * tokens_out_host [batch][n_initial + sample_len] int32 (positions never reached hold eot);
- * n_tokens_host [batch]: row b's sampled tokens before its first EOT are tokens_out[b][n_initial : n_tokens[b]];
- * sum_logprob_host [batch] (nullable): GreedyDecoder's sum of log-probabilities of the sampled tokens.
- * no_speech_prob_host [batch] (nullable; needs opts->no_speech >= 0): softmax probability of <|nospeech|> at the
- *   <|startoftranscript|> position (DecodingResult.no_speech_prob).
- * The encoder output and cross-attention K/V of this batch stay in the engine: the next wca_align_batch_enqueue
- * for the same batch may pass pcm_dev = NULL to re-use them (the reference runs the encoder twice,
- * infer_ali.py:60 and timing.py:58). Synchronous (returns with the tokens). A state that was decoded but not aligned
- * is dropped when the next wca_greedy_decode starts. */
 /* Phase 1 alone (log-mel or a given mel -> encoder -> cross-attention K/V of every decoder layer), enqueued on the
- * engine stream without a host sync. The encoded state is queued: wca_greedy_decode(mel_dev = pcm_dev = NULL) decodes
+ * engine stream without a host sync. The encoded state is queued: wca_decode without an input decodes
  * the oldest undecoded one, wca_align_batch_enqueue(pcm_dev = NULL) consumes the oldest one. Two K/V slots exist, so
  * the NEXT batch can be encoded while the current one is decoded and aligned (the decode loop and the alignment's
  * phase 2 run on the engine's second stream). */
 int wca_encode_batch(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride,
                      const int32_t* n_samples_host, int batch);
 
-int wca_greedy_decode(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride,
-                      const int32_t* n_samples_host, int batch, const int32_t* initial_tokens_host, int n_initial,
-                      const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host, const wca_decode_opts* opts,
-                      int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
-                      float* no_speech_prob_host);
-/* Prompted greedy decode: wca_greedy_decode with opts->sot_index and opts->prefill (wca_greedy_decode is this call with
- * sot_index = 0, prefill = 0, and the tighter bound n_initial + sample_len <= n_text_ctx). initial_tokens_host [n_initial] is
- * upstream's _get_initial_tokens: [sot_prev, prompt..., ] sot_sequence [, no_timestamps] [, prefix...]; the first sampled
- * position (SuppressBlank, the first-timestamp rules) is n_initial. Upstream samples until the sequence is longer than
- * n_text_ctx, so n_initial + sample_len <= n_text_ctx + 1 is allowed (the last token is sampled, never embedded: no positional
- * row past n_text_ctx - 1 is read); n_initial > n_text_ctx is refused (WCA_ERR_TOO_LONG). tokens_out_host is
- * [batch][n_initial + sample_len]; no_speech_prob_host is the <|nospeech|> probability at sot_index. */
-int wca_greedy_decode_ex(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride,
-                         const int32_t* n_samples_host, int batch, const int32_t* initial_tokens_host, int n_initial,
-                         const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host, const wca_decode_opts_ex* opts,
-                         int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
-                         float* no_speech_prob_host);
-/* Greedy decode with per-row initial tokens. initial_tokens_host [batch][n_initial_max] (n_initial_max = max n_initial_host[b]; row b's
- * first n_initial_host[b] entries count, the rest is ignored), sot_index_host [batch] (position of <|startoftranscript|> in row b: 0
- * without a prompt, 1 + prompt length with one), sample_len_host [batch] (row b samples at most that many tokens; opts->sample_len is
- * ignored). Per row the bounds of wca_greedy_decode_ex: 1 <= n_initial[b] <= n_text_ctx, sample_len[b] >= 1,
- * n_initial[b] + sample_len[b] <= n_text_ctx + 1 (WCA_ERR_TOO_LONG), 0 <= sot_index[b] < n_initial[b], every token in the vocabulary
- * (WCA_ERR_INVALID). T_max = max_b (n_initial[b] + sample_len[b]); tokens_out_host [batch][T_max]: row b left-aligned, its initial
- * tokens, then its sampled tokens, eot from its first eot / its budget on; n_tokens_host[b] = index of row b's first sampled eot, at
- * most n_initial[b] + sample_len[b]. SuppressBlank and the first-timestamp rules fire at row b's own first sampled position
- * n_initial[b]; no_speech_prob_host[b] is read at sot_index[b]. The initial tokens always go through one batched prefill (rows padded
- * to n_initial_max with eot; a valid position never attends to a pad). A row's tokens do not depend on the other rows' lengths except
- * through the GEMM path the row COUNT selects (fp32 summation order, as between prefill = 0 and 1). The encoder-state queue behaves as
- * for wca_greedy_decode_ex: the state stays for a following wca_align_batch_enqueue(pcm_dev = NULL). wca_last_decode_positions
- * reports n_initial_max and the number of single-position steps. */
-int wca_greedy_decode_rows(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride,
-                           const int32_t* n_samples_host, int batch, const int32_t* initial_tokens_host,
-                           const int32_t* n_initial_host, const int32_t* sot_index_host, const int32_t* sample_len_host,
-                           const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host, const wca_decode_opts* opts,
-                           int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
-                           float* no_speech_prob_host);
-/* wca_greedy_decode_rows with temperature sampling (upstream GreedyDecoder.update at temperature > 0: a draw from
- * Categorical(logits = filtered logits / T), sum_logprob accumulating the UNTEMPERED log-softmax of the filtered logits at the drawn token).
- * temperature_host [batch] f32 (negative or not finite: WCA_ERR_INVALID) and seed_host [batch] uint64; the other arguments, checks and
- * results are those of wca_greedy_decode_rows. A row at temperature 0 is decoded greedily, bit for bit as wca_greedy_decode_rows decodes it.
- * A row at T > 0 draws by Gumbel-max: next = argmax_v (logit[v] * (1.0f / T) + G(v)) over the tokens its filters leave (the lowest index
- * among equals; the "timestamp mass beats every text token" rule is decided on the untempered logits), G(v) = -logf(-logf(u)),
- * u = ((x >> 9) + 0.5) * 2^-23 in fp32, x = word v & 3 of Philox4x32-10 with key (seed low word, seed high word) and counter
- * (v >> 2, c, 0, 0), c = the number of tokens the row has sampled so far. A row's draws therefore follow (seed, c, v, its logits) alone:
- * not the batch row it sits in, not the other rows. The law is upstream's; the draws are not torch's (another generator).
- * redecode = 1 (requires mel_dev = pcm_dev = NULL, else WCA_ERR_INVALID): decodes AGAIN the newest state of `batch` rows that is already
- * decoded and not yet aligned -- the one the previous decode left for wca_align_batch_enqueue(pcm_dev = NULL) --, with no encoder pass;
- * WCA_ERR_STATE if there is none. Nothing is dropped from the queue and the state is still there for the alignment afterwards.
- * redecode = 0: the state queue behaves as for wca_greedy_decode_rows. */
-int wca_decode_rows_sampled(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride,
-                            const int32_t* n_samples_host, int batch, const int32_t* initial_tokens_host,
-                            const int32_t* n_initial_host, const int32_t* sot_index_host, const int32_t* sample_len_host,
-                            const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host, const wca_decode_opts* opts,
-                            int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
-                            float* no_speech_prob_host, const float* temperature_host, const uint64_t* seed_host,
-                            int redecode);
+/* The ASR pre-pass for a micro-batch: whisper.decode at temperature 0 (greedy) or, per row, at a temperature. Pointers first, then 64-bit
+ * fields, then 32-bit fields; a zero in an optional field means "off".
+ *
+ * Input and state. With mel_dev or pcm_dev the batch is encoded first; with neither, the oldest undecoded state of wca_encode_batch (or the
+ * one wca_detect_language has read) is decoded. The encoder output and cross-attention K/V stay in the engine: the next
+ * wca_align_batch_enqueue for the same batch may pass pcm_dev = NULL to re-use them (the reference runs the encoder twice, infer_ali.py:60
+ * and timing.py:58). A state that was decoded but not aligned is dropped when the next wca_decode that is no redecode starts.
+ *
+ * Rows. Row b holds n_initial[b] initial tokens -- upstream's _get_initial_tokens: [sot_prev, prompt..., ] sot_sequence [, no_timestamps]
+ * [, prefix...] -- with <|startoftranscript|> at sot_index[b] (0 without a prompt, 1 + prompt length with one), and samples at most
+ * sample_len[b] tokens. The first sampled position, where SuppressBlank and the first-timestamp rules fire, is n_initial[b]. Bounds per row:
+ * 1 <= n_initial <= n_text_ctx, sample_len >= 1 and n_initial + sample_len <= n_text_ctx + 1, else WCA_ERR_TOO_LONG (upstream samples until
+ * the sequence is longer than n_text_ctx: the last token is sampled, never embedded, so no positional row past n_text_ctx - 1 is read; this
+ * is the one length bound of every decode -- the tighter n_initial + sample_len <= n_text_ctx of ABI versions up to 16 belonged to one
+ * entry point alone and left with it); 0 <= sot_index < n_initial and every initial token inside the vocabulary, else WCA_ERR_INVALID.
+ *
+ * Sampling (temperature_host and seed_host, given together; per_row 1 only). A row at temperature 0 is decoded greedily, bit for bit as
+ * without the two arrays. A row at T > 0 is upstream's GreedyDecoder.update at temperature > 0: a draw from Categorical(logits = filtered
+ * logits / T), sum_logprob accumulating the UNTEMPERED log-softmax of the filtered logits at the drawn token. It draws by Gumbel-max:
+ * next = argmax_v (logit[v] * (1.0f / T) + G(v)) over the tokens its filters leave (the lowest index among equals; the "timestamp mass beats
+ * every text token" rule is decided on the untempered logits), G(v) = -logf(-logf(u)), u = ((x >> 9) + 0.5) * 2^-23 in fp32, x = word v & 3 of
+ * Philox4x32-10 with key (seed low word, seed high word) and counter (v >> 2, c, 0, 0), c = the number of tokens the row has sampled so far.
+ * A row's draws therefore follow (seed, c, v, its logits) alone: not the batch row it sits in, not the other rows. The law is upstream's;
+ * the draws are not torch's (another generator).
+ *
+ * Refused with WCA_ERR_INVALID before any work is enqueued: a null engine, descriptor or required field; both inputs given; batch outside
+ * [1, max_batch]; per_row, prefill or redecode other than 0 or 1; per_row 0 with a temperature, a seed or redecode; per_row 1 with
+ * prefill 0; only one of temperature_host and seed_host; redecode together with an input; a temperature that is negative or not finite.
+ * Synchronous (returns with the tokens). wca_last_decode_positions reports the prefill's positions (n_initial, the largest with per_row 1,
+ * or 0) and the number of single-position steps. */
+typedef struct {
+  const float* mel_dev;                /* [batch][n_mels][3000] f32, what whisper.decode takes; at most one of mel_dev / pcm_dev            */
+  const float* pcm_dev;                /* [batch][pcm_stride] f32, log-mel computed on the device; needs n_samples_host [batch]             */
+  const int32_t* n_samples_host;
+  const int32_t* initial_tokens_host;  /* per_row 0: [n_initial]; per_row 1: [batch][n_initial_max], n_initial_max = max_b n_initial[b] (row
+                                          b's first n_initial[b] entries count, the rest is ignored)                                       */
+  const int32_t* n_initial_host;       /* these three: one entry (per_row 0) or [batch] (per_row 1)                                        */
+  const int32_t* sot_index_host;
+  const int32_t* sample_len_host;
+  const float* temperature_host;       /* [batch] f32, nullable                                                                            */
+  const uint64_t* seed_host;           /* [batch], nullable                                                                                */
+  const uint8_t* suppress_mask_host;   /* [n_vocab] bytes: 1 = logit forced to -inf at every step (SuppressTokens list and, when the
+                                          timestamp rules are on, <|notimestamps|>)                                                        */
+  const uint8_t* blank_mask_host;      /* [n_vocab], nullable: 1 = -inf at the first sampled position (SuppressBlank: tokenizer.encode(" ")
+                                          + [eot])                                                                                         */
+  const wca_decode_opts* opts;
+  int32_t* tokens_out_host;            /* [batch][T_max], T_max = max_b (n_initial[b] + sample_len[b]): row b left-aligned, its initial
+                                          tokens, then its sampled tokens, eot from its first eot / its budget on                          */
+  int32_t* n_tokens_host;              /* [batch]: index of row b's first sampled eot, at most n_initial[b] + sample_len[b]; its sampled
+                                          tokens are tokens_out[b][n_initial[b] : n_tokens[b]]                                             */
+  float* sum_logprob_host;             /* [batch], nullable: GreedyDecoder's sum of log-probabilities of the sampled tokens                */
+  float* no_speech_prob_host;          /* [batch], nullable (needs opts->no_speech >= 0): softmax probability of <|nospeech|> at row b's
+                                          sot_index (DecodingResult.no_speech_prob)                                                        */
+  int64_t pcm_stride;
+  int32_t batch;
+  int32_t per_row;                     /* 0: one row description shared by every batch row (the row arrays have one entry), the scalar
+                                          kernels run and `prefill` is honoured. 1: the row arrays have `batch` entries, the rows sit at
+                                          different decoder positions, the table kernels run, always behind a prefill (rows padded to
+                                          n_initial_max with eot; a valid position never attends to a pad), and opts->sample_len is ignored.
+                                          A row's tokens do not depend on the other rows' lengths except through the GEMM path the row
+                                          COUNT selects (fp32 summation order, as between prefill 0 and 1).                                */
+  int32_t prefill;                     /* 0: the initial tokens go through the decoder one position at a time (one decode step each);
+                                          1: one batched forward over all of them (causal self-attention, each layer's cross-K/V read
+                                          once), upstream's first forward. The two agree up to f16 / fp32 summation order.                 */
+  int32_t redecode;                    /* 1 (no input): decode AGAIN the newest state of `batch` rows that is already decoded and not yet
+                                          aligned -- the one the previous decode left for wca_align_batch_enqueue(pcm_dev = NULL) --, with
+                                          no encoder pass (the rungs of transcribe's temperature fallback ladder); WCA_ERR_STATE if there is
+                                          none. Nothing is dropped from the queue and the state is still there for the alignment.          */
+} wca_decode_desc;
+int wca_decode(wca_engine* e, const wca_decode_desc* d);
 /* Language identification, upstream's detect_language(model, mel): which of the language tokens [lang_begin, lang_begin + n_lang)
  * (tokenizer.all_language_tokens: sot + 1 ..., 99 or 100 of them; 1 <= n_lang <= 128) follows <|startoftranscript|> (`sot`) for each row.
- * mel_dev / pcm_dev / pcm_stride / n_samples_host / batch as for wca_greedy_decode: at most one input is non-NULL, with both NULL the oldest
- * undecoded state of wca_encode_batch is read. One decoder position (token sot at position 0, the first step of wca_greedy_decode, f16
+ * mel_dev / pcm_dev / pcm_stride / n_samples_host / batch as for wca_decode: at most one input is non-NULL, with both NULL the oldest
+ * undecoded state of wca_encode_batch is read. One decoder position (token sot at position 0, the first step of a wca_decode without prefill, f16
  * operands in both precision modes) and the language head: the final LayerNorm and the n_lang rows of the token embedding only, which is
  * upstream's softmax / argmax over logits whose other entries are masked to -inf.
  * lang_token_host [batch] int32: the most probable language token (absolute id; the lowest id among equal logits);
  * probs_host [batch][n_lang] f32: the softmax over the language tokens, entry j for token lang_begin + j.
- * The encoded state stays queued and UNDECODED: a following wca_greedy_decode* with mel_dev = pcm_dev = NULL decodes it with no second
- * encoder pass (upstream encodes the first window twice), and wca_align_batch_enqueue(pcm_dev = NULL) may consume it. A wca_greedy_decode* or
+ * The encoded state stays queued and UNDECODED: a following wca_decode with mel_dev = pcm_dev = NULL decodes it with no second
+ * encoder pass (upstream encodes the first window twice), and wca_align_batch_enqueue(pcm_dev = NULL) may consume it. A wca_decode or
  * wca_detect_language that brings an input of its own drops it, as does wca_align_batch_enqueue with a pcm_dev. Synchronous.
  * WCA_ERR_INVALID: null engine / output pointers, both inputs given, batch outside [1, max_batch], sot or the language range outside the
  * vocabulary; WCA_ERR_STATE: no input and no undecoded state of `batch` rows. */
 int wca_detect_language(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
                         int batch, int sot, int lang_begin, int n_lang, int32_t* lang_token_host, float* probs_host);
-/* positions per row that the last wca_greedy_decode* fed through the batched prefill (n_initial, or 0) and one position at a
+/* positions per row that the last wca_decode fed through the batched prefill (n_initial, or 0) and one position at a
  * time (decode steps, the sampling steps after the first included) */
 int wca_last_decode_positions(wca_engine* e, int32_t* prefill_positions, int32_t* step_positions);
 
-/* Same pipeline, but only enqueues the work on the engine stream (no host sync; results stay in the engine's
- * pinned staging ring until wca_align_batch_fetch). Up to TWO batches may be in flight: _fetch returns the
- * OLDEST pending one (waiting on its HIP event only), so the host can post-process batch i while batch i+1 runs. */
-int wca_align_batch_enqueue(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
-                            const int64_t* tokens_dev, int n_tok_max, const int32_t* n_tok_host,
-                            const int32_t* max_frames_host, int batch, const wca_align_opts* opts);
-int wca_align_batch_fetch(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host,
-                          int32_t* sel_idx_host);
-
-/* Teacher-token log-probabilities (timing.py:146-150 of the reference: text_token_probs = softmax(logits[len(sot_sequence):, :eot]) at
- * the teacher token, here in log space; the per-word mean of timing.py:181-184 is the caller's). For utterance b with
- * tokens = [*sot_sequence, no_timestamps, *text, eot] and n_text = n_tok[b] - sot_len - 2, entry i < n_text is
- *   log_softmax(logits[b][sot_len + i][0 : vocab_end])[tokens[b][sot_len + 1 + i]];
- * the prediction of eot is not scored, as in the reference.
- * _enqueue_ex: wca_align_batch_enqueue with vocab_end (= tokenizer.eot) in (0, n_vocab]; 0 = no log-probs, exactly the path of
- *   wca_align_batch_enqueue. With log-probs the decoder finishes its last layer and the n_text rows of every utterance go through the final
- *   LayerNorm, the vocabulary projection (tok_emb rows [0, vocab_end)) and a log-sum-exp kernel on the engine's second stream; the
- *   [rows][vocab] logits never reach the host. A teacher token >= vocab_end has no value: NaN, and _fetch_ex returns WCA_ERR_INVALID.
- *   The jump frames and top-k heads are the same with and without log-probs.
- * _fetch_ex: wca_align_batch_fetch plus token_logprob_host [batch][n_tok_max] f32 (nullable): entries [0, n_text_b) of row b, the rest 0.
- *   WCA_ERR_STATE (and nothing consumed) when token_logprob_host is given but the pending batch was enqueued with vocab_end = 0. */
-int wca_align_batch_enqueue_ex(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
-                               const int64_t* tokens_dev, int n_tok_max, const int32_t* n_tok_host,
-                               const int32_t* max_frames_host, int batch, const wca_align_opts* opts, int32_t vocab_end);
-int wca_align_batch_fetch_ex(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host,
-                             int32_t* sel_idx_host, float* token_logprob_host);
-/* The fused pipeline with an open-end DTW per row: wca_align_batch_enqueue_ex plus open_end_host [batch] (row b's DTW is open-ended where
- * open_end_host[b] != 0; a row with 0 gets exactly what wca_align_batch_enqueue_ex gives it). Everything upstream of the DTW is unchanged.
- * wca_align_batch_fetch_open: wca_align_batch_fetch_ex plus end_row_host [batch] (the last text row of row b's path, counted in DTW rows,
- * i.e. from the first token after the sot sequence: n_tok[b] - sot_len - 2 for a closed row; -1 where no DTW ran) and score_host [batch]
- * (both nullable). Entries (end_row, n_tok[b] - sot_len - 1) of an open row's jump frames are -1. WCA_ERR_STATE (and nothing consumed)
- * when they are requested but the pending batch was not enqueued with _enqueue_open. */
-int wca_align_batch_enqueue_open(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
-                                 const int64_t* tokens_dev, int n_tok_max, const int32_t* n_tok_host,
-                                 const int32_t* max_frames_host, int batch, const wca_align_opts* opts, int32_t vocab_end,
-                                 const int32_t* open_end_host);
-int wca_align_batch_fetch_open(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host,
-                               int32_t* sel_idx_host, float* token_logprob_host, int32_t* end_row_host, float* score_host);
-/* The same log-sum-exp kernel on caller-supplied logits (timing.py:146-149 on the logits wca_get_attentions returns): logits_dev [rows][ld]
+/* The log-sum-exp kernel of the alignment's token log-probs on caller-supplied logits (timing.py:146-149 on the logits wca_get_attentions returns): logits_dev [rows][ld]
  * f32 (ld >= vocab_end), targets_dev [rows] int64, out_dev [rows] f32 = log_softmax(logits[r][0 : vocab_end])[targets[r]]. Synchronous
  * on the engine stream; a target outside [0, vocab_end) gives NaN there and WCA_ERR_INVALID. */
 int wca_token_logprobs(wca_engine* e, const float* logits_dev, int rows, int ld, int vocab_end, const int64_t* targets_dev,
@@ -592,7 +567,7 @@ int wca_test_set_switch(const char* name, int value);
 /* the [batch][n_text_layer * n_text_head] head selection scores (timing.py:13-43) of the LAST fused batch, after it was fetched (no batch in
  * flight): tools/precision_ablation.py compares them with the oracle's */
 int wca_test_last_scores(wca_engine* e, int batch, float* scores_host);
-/* what the LAST wca_greedy_decode* call left on the device, after a synchronisation of the decode stream (reads only, launches nothing):
+/* what the LAST wca_decode call left on the device, after a synchronisation of the decode stream (reads only, launches nothing):
  * logits_host [logits_rows][n_vocab] f32 -- the rows of the last forward, [batch] of them, or [2 batch] after a prefill with no_speech
  * (rows [batch, 2 batch): the <|sot|> position's, which the steps behind the prefill leave alone) -- and cache_f16_host, the self-attention
  * cache [n_text_layer][2][batch][T_max][n_text_state] f16 with T_max = the largest n_initial + sample_len of that call. batch and T_max
@@ -615,14 +590,14 @@ int wca_test_language_head(wca_engine* e, const float* x_dev, int B, int lang_be
 int wca_test_decode_select(wca_engine* e, const float* logits_dev, int batch, int n_vocab, int32_t* tokens_dev, int T_max,
                            int cur_len, int n_initial, const uint8_t* suppress_mask_dev, const uint8_t* blank_mask_dev,
                            const wca_decode_opts* opts, float* sum_logprob_dev, int32_t* n_done_dev);
-/* the per-row form of that step (wca_greedy_decode_rows): cur_len_dev / n_initial_dev / cap_dev [batch] int32 device arrays; row b holds
+/* the per-row form of that step (wca_decode with per_row 1): cur_len_dev / n_initial_dev / cap_dev [batch] int32 device arrays; row b holds
  * cur_len[b] tokens of which n_initial[b] are initial, and is a finished row (eot, nothing added to sum_logprob) once
  * cur_len[b] - n_initial[b] >= cap[b]; n_done_dev [n_done_len]: entry n_done_idx counts the rows whose new token is eot */
 int wca_test_decode_select_rows(wca_engine* e, const float* logits_dev, int batch, int n_vocab, int32_t* tokens_dev, int T_max,
                                 const int32_t* cur_len_dev, const int32_t* n_initial_dev, const int32_t* cap_dev, int n_done_idx,
                                 int n_done_len, const uint8_t* suppress_mask_dev, const uint8_t* blank_mask_dev,
                                 const wca_decode_opts* opts, float* sum_logprob_dev, int32_t* n_done_dev);
-/* that step in its sampling form (wca_decode_rows_sampled): temperature_dev [batch] f32 and seed_dev [batch] uint64 device arrays; row b
+/* that step in its sampling form (wca_decode with temperature_host / seed_host): temperature_dev [batch] f32 and seed_dev [batch] uint64 device arrays; row b
  * draws with the counter cur_len[b] - n_initial[b] and, at temperature 0, takes the argmax exactly as wca_test_decode_select_rows does */
 int wca_test_decode_sample_rows(wca_engine* e, const float* logits_dev, int batch, int n_vocab, int32_t* tokens_dev, int T_max,
                                 const int32_t* cur_len_dev, const int32_t* n_initial_dev, const int32_t* cap_dev, int n_done_idx,
@@ -690,7 +665,7 @@ int wca_set_fuse_ln(wca_engine* e, int on);
  *     blocks on can be left on single f16 operands, and that leaving only the log-mel and the conv stem on them moves the head
  *     selection scores by 1e-4 relative (all stages split: 4e-6) and misses two near-tied utterances of a 700-utterance leg
  *     (profiles/r04_parity_leg_700utt.txt).
- * The greedy ASR pre-pass (wca_greedy_decode) computes in f16 in both modes, like whisper.decode's fp16 default.
+ * The greedy ASR pre-pass (wca_decode) computes in f16 in both modes, like whisper.decode's fp16 default.
  * Switching re-creates the activation arena: no batch may be in flight, encoded-but-unconsumed states are dropped. */
 enum { WCA_PRECISION_F16 = 0, WCA_PRECISION_SPLIT = 1, WCA_PRECISION_REFERENCE = 1 };
 int wca_set_precision(wca_engine* e, int mode);   /* F16 or SPLIT (= REFERENCE) */
@@ -699,7 +674,7 @@ int wca_get_precision(wca_engine* e);             /* F16 or SPLIT */
  * batch's phase 1; off: everything on one stream, so that rocprofv3 per-kernel durations are not inflated by sharing
  * the CUs (profiling aid; throughput drops by the overlap's worth). No batch may be in flight when it is changed. */
 int wca_set_overlap(wca_engine* e, int on);
-/* Decoder GEMMs on few rows (a greedy-decode step of wca_greedy_decode: M = batch; batch-1 teacher-forced forwards):
+/* Decoder GEMMs on few rows (a decode step of wca_decode: M = batch; batch-1 teacher-forced forwards):
  * fused != 0 (default): for up to 128 rows one few-row kernel per GEMM with the LayerNorm in its prologue, the KV-cache append in its
  * epilogue and deterministic split-K for K = 4 n_state; 0: separate LayerNorm / GEMM / append launches (the round-1 path,
  * kept for A/B tests). streams must be 1: the form that ran the batch as two half-batches on two streams was removed (it measured no

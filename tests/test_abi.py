@@ -39,6 +39,41 @@ def test_removed_cu_partition_is_not_exported(wca):
     assert not hasattr(wca.WhisperAMD, "set_cu_partition")
 
 
+def test_removed_decode_and_alignment_names_are_not_exported(wca):
+    """One descriptor call each replaced the four decode and the seven fused-alignment entry points: the ten names that left are in no
+    symbol table, declaration or binding."""
+    lib = wca._lib.load()
+    header = open(os.path.join(ROOT, "include", "wca.h")).read()
+    for name in ("wca_greedy_decode", "wca_greedy_decode_ex", "wca_greedy_decode_rows", "wca_decode_rows_sampled", "wca_decode_opts_ex",
+                 "wca_align_batch_enqueue_ex", "wca_align_batch_enqueue_open", "wca_align_batch_fetch_ex", "wca_align_batch_fetch_open"):
+        assert not hasattr(lib, name), name
+        assert name not in header and name not in wca._lib.SIGNATURES, name
+    assert not hasattr(wca._lib, "DecodeOptsEx")
+    assert {"wca_decode", "wca_align_batch", "wca_align_batch_enqueue", "wca_align_batch_fetch"} <= set(_declared())
+
+
+def test_descriptor_calls_refuse_null_arguments_without_a_gpu(wca):
+    """wca_decode and the three fused-alignment calls: no engine and no descriptor, and no engine with an empty descriptor, are refused with
+    a message that says `null` before any HIP call; the ctypes descriptors have the header's layout."""
+    lib, L = wca._lib.load(), wca._lib
+    dd, ad, ar = L.DecodeDesc(), L.AlignDesc(), L.AlignResult()
+    calls = [(lib.wca_decode, (None, None)), (lib.wca_decode, (None, ctypes.byref(dd))),
+             (lib.wca_align_batch_enqueue, (None, None)), (lib.wca_align_batch_enqueue, (None, ctypes.byref(ad))),
+             (lib.wca_align_batch_fetch, (None, 0, 0, 0, None)), (lib.wca_align_batch_fetch, (None, 0, 0, 0, ctypes.byref(ar))),
+             (lib.wca_align_batch, (None, None, None)), (lib.wca_align_batch, (None, ctypes.byref(ad), ctypes.byref(ar)))]
+    for fn, args in calls:
+        assert lib.wca_test_set_switch(b"no_such_switch", 1) < 0 and b"null" not in lib.wca_last_error()
+        assert fn(*args) < 0 and b"null" in lib.wca_last_error(), (fn.__name__, args)
+    # pointers, then 64-bit fields, then 32-bit fields, padded to the 8-byte alignment of the pointers
+    assert ctypes.sizeof(dd) == 16 * 8 + 1 * 8 + 4 * 4
+    assert ctypes.sizeof(ad) == 7 * 8 + 1 * 8 + 3 * 4 + 4
+    assert ctypes.sizeof(ar) == 5 * 8
+    header = open(os.path.join(ROOT, "include", "wca.h")).read()
+    for name, struct in (("wca_decode_desc", L.DecodeDesc), ("wca_align_desc", L.AlignDesc), ("wca_align_result", L.AlignResult)):
+        body = re.search(r"typedef struct \{([^{}]*)\} %s;" % name, header, flags=re.S).group(1)
+        assert re.findall(r"(\w+);", re.sub(r"/\*.*?\*/", "", body, flags=re.S)) == [f[0] for f in struct._fields_], name
+
+
 def test_struct_layouts_match_header(wca):
     assert ctypes.sizeof(wca._lib.ModelDims) == 10 * 4
     assert ctypes.sizeof(wca._lib.AlignOpts) == 8 * 4
@@ -57,7 +92,7 @@ def test_null_engine_is_an_error_not_a_crash(wca):
     for f in ("engine_align.hip", "engine_audio.hip"):
         src = open(os.path.join(ROOT, "whisper-char-alignment_amd", "csrc", f)).read()
         names += re.findall(r"^int (wca_\w+)\(wca_engine\* e\b", src, flags=re.M)
-    assert len(names) >= 21 and {"wca_log_mel", "wca_resample_16k", "wca_align_batch_fetch_ex", "wca_probe_strict_tp"} <= set(names)
+    assert len(names) >= 22 and {"wca_log_mel", "wca_resample_16k", "wca_align_batch_fetch", "wca_probe_strict_tp"} <= set(names)
     for name in names:
         args = [None if issubclass(t, ctypes._Pointer) or t is ctypes.c_void_p else 0 for t in wca._lib.SIGNATURES[name][1]]
         assert lib.wca_test_set_switch(b"no_such_switch", 1) < 0 and b"null" not in lib.wca_last_error()

@@ -141,7 +141,7 @@ def test_prefill_then_steps(sc, engines, mel_dev, tok, precision, fused, n):
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "separate"])
 def test_ragged_rows_hold_their_own_positions(sc, engines, mel_dev, tok, fused):
-    """wca_greedy_decode_rows: rows of 3 / 64 / 65 / 226 initial tokens of their own, padded to 226 in the prefill, then ROWS_STEPS steps at per-row
+    """wca_decode with per_row 1: rows of 3 / 64 / 65 / 226 initial tokens of their own, padded to 226 in the prefill, then ROWS_STEPS steps at per-row
     positions. Row b's slots [0, n_initial[b] + steps - 1) hold ITS positions -- the pad left-overs of the short rows are overwritten where the
     steps went --, its last logits are its own last position's, and the <|sot|> rows are read at each row's own index."""
     m = engines("f16")

@@ -1,6 +1,6 @@
 """CPU tests of prompt / prefix conditioning in decode (DecodingOptions(prompt=..., prefix=...), upstream
 DecodingTask._get_initial_tokens, restated): the initial-token construction, the sample_len cap, sot_index, which engine
-call decode() makes, and the C ABI mirror of wca_decode_opts_ex. The decode itself runs on the GPU
+call decode() makes, and the C ABI mirror of wca_decode_opts and of the descriptor's prompt fields. The decode itself runs on the GPU
 (tests/test_decode_prompt_gpu.py)."""
 import ctypes
 import importlib
@@ -143,19 +143,23 @@ def test_decode_passes_the_plan_to_the_engine(decoding, tok, wca):
     assert m.calls[-1]["prefill"] == 1 and m.calls[-1]["sot_index"] == 0
 
 
-def test_decode_opts_ex_mirrors_the_header(wca):
+def test_decode_opts_and_desc_mirror_the_header(wca):
     src = open(os.path.join(ROOT, "include", "wca.h")).read()
-    body = re.search(r"typedef struct \{([^{}]*)\} wca_decode_opts_ex;", src, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = re.findall(r"int32_t\s+(\w+);", body)
-    assert fields == [f[0] for f in wca._lib.DecodeOptsEx._fields_]
-    assert fields[:6] == [f[0] for f in wca._lib.DecodeOpts._fields_] and fields[6:] == ["sot_index", "prefill"]
-    assert ctypes.sizeof(wca._lib.DecodeOptsEx) == 8 * 4
+
+    def fields(name):
+        body = re.search(r"typedef struct \{([^{}]*)\} %s;" % name, src, flags=re.S).group(1)
+        return re.findall(r"(\w+);", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+
+    assert fields("wca_decode_opts") == [f[0] for f in wca._lib.DecodeOpts._fields_] and ctypes.sizeof(wca._lib.DecodeOpts) == 6 * 4
+    # what a prompted decode needs sits in the descriptor: <|sot|>'s position per row, and the batched prefill
+    desc = fields("wca_decode_desc")
+    assert desc == [f[0] for f in wca._lib.DecodeDesc._fields_]
+    assert "sot_index_host" in desc and desc[-4:] == ["batch", "per_row", "prefill", "redecode"]
     lib = wca._lib.load()
     assert lib.wca_version() >= 8
     a, b = ctypes.c_int32(0), ctypes.c_int32(0)
     assert lib.wca_last_decode_positions(None, ctypes.byref(a), ctypes.byref(b)) < 0
-    assert lib.wca_greedy_decode_ex(None, None, None, 0, None, 1, None, 0, None, None, None, None, None, None, None) < 0
+    assert lib.wca_decode(None, ctypes.byref(wca._lib.DecodeDesc())) < 0
 
 
 def test_cli_accepts_initial_prompt():

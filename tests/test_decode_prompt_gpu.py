@@ -1,6 +1,6 @@
-"""Prompted greedy decode on the MI355X (DecodingOptions(prompt=..., prefix=...), wca_greedy_decode_ex): the result against
+"""Prompted greedy decode on the MI355X (DecodingOptions(prompt=..., prefix=...), wca_decode's sot_index and prefill): the result against
 the CPU oracle (oracle/decoding_ref.py) with the prompted initial tokens, the batched prefill against the one-position-at-a-time
-path, the n_text_ctx + 1 length edge and the old entry point. Small dims, like the `small` fixture of test_decode_gpu.py."""
+path, the n_text_ctx + 1 length edge and a raw zero-default descriptor. Small dims, like the `small` fixture of test_decode_gpu.py."""
 import ctypes as C
 import glob
 import importlib
@@ -138,19 +138,20 @@ def _decode(m, tok, dims, initial, sample_len, sot_index, prefill, mel=None, bat
     return out + (m.last_no_speech_prob.copy(), m.last_decode_positions())
 
 
-def _raw_decode(m, tok, dims, mel, initial, sample_len, ex):
-    """One call of wca_greedy_decode (ex False) or wca_greedy_decode_ex(sot_index = 0, prefill = 0) (ex True) through ctypes."""
+def _raw_decode(m, tok, dims, mel, initial, sample_len):
+    """One call of wca_decode through ctypes with every optional field of the descriptor left at zero: per_row 0, prefill 0, sot_index 0."""
     _lib = _m("_lib")
     sup, blank = _masks(tok, dims)
     B, T = mel.shape[0], len(initial) + sample_len
     toks, n_tok, lp, nsp = np.zeros((B, T), np.int32), np.zeros(B, np.int32), np.zeros(B, np.float32), np.zeros(B, np.float32)
-    fields = (sample_len, tok.eot, tok.timestamp_begin, 1, 50, tok.no_speech)
-    o = _lib.DecodeOptsEx(*fields, 0, 0) if ex else _lib.DecodeOpts(*fields)
+    o = _lib.DecodeOpts(sample_len, tok.eot, tok.timestamp_begin, 1, 50, tok.no_speech)
+    init, n_init, sot, sl = (_lib.i32_array(v) for v in (initial, [len(initial)], [0], [sample_len]))
+    d = _lib.DecodeDesc(mel_dev=mel.data_ptr(), initial_tokens_host=C.addressof(init), n_initial_host=C.addressof(n_init),
+                        sot_index_host=C.addressof(sot), sample_len_host=C.addressof(sl), suppress_mask_host=sup.ctypes.data,
+                        blank_mask_host=blank.ctypes.data, opts=C.pointer(o), tokens_out_host=toks.ctypes.data, n_tokens_host=n_tok.ctypes.data,
+                        sum_logprob_host=lp.ctypes.data, no_speech_prob_host=nsp.ctypes.data, batch=B)
     m._bind_stream()
-    entry = m._lib.wca_greedy_decode_ex if ex else m._lib.wca_greedy_decode
-    _lib.check(entry(m._h, C.c_void_p(mel.data_ptr()), None, 0, None, B, _lib.i32_array(initial), len(initial), sup.ctypes.data_as(C.c_void_p),
-                     blank.ctypes.data_as(C.c_void_p), C.byref(o), toks.ctypes.data_as(_lib._pi32), n_tok.ctypes.data_as(_lib._pi32),
-                     lp.ctypes.data_as(_lib._pf), nsp.ctypes.data_as(_lib._pf)))
+    _lib.check(m._lib.wca_decode(m._h, C.byref(d)))
     return toks, n_tok, lp, nsp
 
 
@@ -217,27 +218,32 @@ def test_length_edge_and_bounds(pkg, small, tok):
     print("decode-cache measure length edge: plane0 %.3e plane_deep %.3e logits %.3e" % (float(diff[0].max()), float(diff[1:].max()), dl))
     assert float(diff[0].max()) <= cref.TOL["small_plane0"] and float(diff[1:].max()) <= cref.TOL["small_plane_deep"]
     assert dl <= cref.TOL["small_logits"], dl
-    # the bounds of wca_greedy_decode_ex and of the old entry point
+    # the one length bound of every decode, n_initial + sample_len <= n_text_ctx + 1, through the Python method and the raw call
     with pytest.raises(_m("_lib").TooLongError):
         _decode(m, tok, dims, initial, sample_len + 1, sot_index, 1, mel=mel)
     with pytest.raises(_m("_lib").TooLongError):
         _decode(m, tok, dims, [tok.sot] * 449, 1, 0, 1, mel=mel)
     with pytest.raises(_m("_lib").TooLongError):
-        _raw_decode(m, tok, dims, mel, list(tok.sot_sequence), 446, ex=False)   # the old entry point keeps its bound
+        _raw_decode(m, tok, dims, mel, list(tok.sot_sequence), 447)   # 3 + 447 = n_text_ctx + 2
+    toks, n_tok, lp, nsp = _raw_decode(m, tok, dims, mel, list(tok.sot_sequence), 446)   # 3 + 446 = n_text_ctx + 1: not refused, and it runs
+    assert toks.shape == (1, 449) and 3 <= n_tok[0] <= 449 and (toks[0, n_tok[0]:] == tok.eot).all() and np.isfinite(lp).all()
     with pytest.raises(_m("_lib").WcaError):
         _decode(m, tok, dims, initial, 8, len(initial), 1, mel=mel)   # sot_index outside the initial tokens
 
 
-def test_old_entry_point_is_ex_without_prefill(pkg, small, tok):
-    """wca_greedy_decode and wca_greedy_decode_ex(prefill = 0, sot_index = 0) give bit-identical results."""
+def test_raw_descriptor_matches_greedy_decode(pkg, small, tok):
+    """A raw wca_decode_desc with every optional field zero and greedy_decode with its default sot_index and prefill give bit-identical
+    results in all four outputs."""
     m, sd, dims = small
     mel = _mel(m, [50, 51, 52])
     initial = list(tok.sot_sequence)
-    old = _raw_decode(m, tok, dims, mel, initial, 12, ex=False)
+    raw = _raw_decode(m, tok, dims, mel, initial, 12)
     pos = m.last_decode_positions()
-    ex = _raw_decode(m, tok, dims, mel, initial, 12, ex=True)
-    assert all(np.array_equal(a, b) for a, b in zip(old, ex))
-    assert np.isfinite(old[3]).all() and pos == m.last_decode_positions() and pos[0] == 0 and pos[1] >= len(initial)
+    sup, blank = _masks(tok, dims)
+    py = m.greedy_decode(mel, None, None, initial, sup, blank, sample_len=12, eot=tok.eot, timestamp_begin=tok.timestamp_begin,
+                         apply_timestamp_rules=True, max_initial_timestamp_index=50, no_speech=tok.no_speech) + (m.last_no_speech_prob,)
+    assert all(np.array_equal(a, b) for a, b in zip(raw, py))
+    assert np.isfinite(raw[3]).all() and pos == m.last_decode_positions() and pos[0] == 0 and pos[1] >= len(initial)
 
 
 def test_infer_ali_initial_prompt(tmp_path, fake_vocab):

@@ -1,6 +1,6 @@
-"""Greedy decode with per-row prompts on the MI355X (wca_greedy_decode_rows): the rows of one batch sit at different decoder
+"""Greedy decode with per-row prompts on the MI355X (wca_decode with per_row 1): the rows of one batch sit at different decoder
 positions. The per-row kernel forms against the uniform kernels they were derived from (bit for bit), the whole loop against
-wca_greedy_decode_ex (equal lengths: bit for bit; ragged: every row against the same utterance decoded alone), per-row sample
+wca_decode (equal lengths: bit for bit; ragged: every row against the same utterance decoded alone), per-row sample
 budgets and the refusals. Small dims, like the `small` fixture of test_decode_gpu.py."""
 import ctypes as C
 import importlib
@@ -209,7 +209,7 @@ def _equal_lengths(m, tok, dims, mel4):
 
 
 def test_equal_lengths_give_the_uniform_result(small, tok, mel4):
-    """Four rows that share one prompt of 20 tokens: bit for bit what wca_greedy_decode_ex(prefill = 1) gives for the batch."""
+    """Four rows that share one prompt of 20 tokens: bit for bit what greedy_decode(prefill=1) gives for the batch."""
     m, dims = small
     _equal_lengths(m, tok, dims, mel4)
 
@@ -228,7 +228,7 @@ def test_equal_lengths_give_the_uniform_result_unfused(small, tok, mel4):
 @pytest.mark.parametrize("lengths", [(3, 5, 9, 17), (3, 4, 37, 226)], ids=["few-row-prefill", "large-gemm-prefill"])
 def test_ragged_rows_against_each_row_alone(small, tok, mel4, lengths):
     """Rows with different numbers of initial tokens in one batch against the same utterance decoded alone through
-    wca_greedy_decode_ex(prefill = 1). The GEMM path (and the fp32 summation order) depends on the row count, so: no_speech_prob
+    greedy_decode(prefill=1). The GEMM path (and the fp32 summation order) depends on the row count, so: no_speech_prob
     at rtol 1e-4, identical rows' sum_logprob at rtol = atol = 1e-4, a differing row excused only by a teacher-forced logit gap
     below 1e-3 at its first divergent position, at least three of the four rows identical."""
     m, dims = small
@@ -297,4 +297,18 @@ def test_refusals_leave_the_engine_usable(small, tok, mel4):
         call([sot, sot[:2] + [dims.n_vocab], sot, sot], [0] * 4, [8] * 4)               # a token outside the vocabulary
     with pytest.raises(_lib.WcaError):
         call([sot] * 5, [0] * 5, [8] * 5, mel=torch.cat([mel4, mel4[:1]]))              # batch > max_batch
+    # the combinations of descriptor fields that no decode runs: WCA_ERR_INVALID, through the engine's one descriptor call
+    opts = _lib.DecodeOpts(8, tok.eot, tok.timestamp_begin, 1, 50, tok.no_speech)
+    temps, seeds = np.zeros(4, np.float32), np.arange(4, dtype=np.uint64)
+    uniform = (_lib.i32_array(sot), [len(sot)], [0], [8], opts, sup, blank, 0)
+    rows = (np.array([sot] * 4, np.int32), [len(sot)] * 4, [0] * 4, [8] * 4, opts, sup, blank, 1)
+    for args in ((mel4, None, None, None) + uniform + (0, temps, seeds),               # per_row 0 with a temperature and a seed
+                 (None, None, None, 4) + uniform + (0, None, None, True),              # per_row 0 with redecode
+                 (mel4, None, None, None) + rows + (0,),                               # per_row 1 with prefill 0
+                 (mel4, None, None, None) + rows + (1, temps, None),                   # a temperature without a seed
+                 (mel4, None, None, None) + rows + (1, None, seeds),                   # a seed without a temperature
+                 (mel4, None, None, None) + rows + (1, temps, seeds, True)):           # redecode together with an input
+        with pytest.raises(_lib.WcaError) as err:
+            m._decode(*args)
+        assert err.value.code == -1, err.value                                          # WCA_ERR_INVALID
     _equal_lengths(m, tok, dims, mel4)

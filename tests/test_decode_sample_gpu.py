@@ -1,5 +1,5 @@
 """Temperature sampling on the MI355X: the sampling form of the decode step (csrc/decode.hip, wca_test_decode_sample_rows) token for token
-against the float64 restatement tests/decode_sample_ref.py; wca_decode_rows_sampled at temperature 0 against wca_greedy_decode_rows, bit
+against the float64 restatement tests/decode_sample_ref.py; wca_decode with temperature_host / seed_host at temperature 0 against wca_decode with per_row 1, bit
 for bit; draws that follow their seed and not their batch row; the sampled loop against the reference sampler fed the teacher-forced
 logits; the re-decode of a resident encoder state; and transcribe's fallback ladder end to end on random weights. Small dims (the
 `small` fixture of tests/test_decode_rows_gpu.py)."""

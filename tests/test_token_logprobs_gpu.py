@@ -1,6 +1,6 @@
 """Teacher-token log-probabilities on the MI355X (`-m gpu`): openai-whisper's word `probability` (timing.py:146-150 and 181-184 of
 the reference: softmax of logits[len(sot_sequence):, :eot] at the teacher token, averaged per word), computed in the batched pipeline
-(wca_align_batch_enqueue_ex / _fetch_ex) and by wca_token_logprobs on given logits:
+(wca_align_desc.vocab_end / wca_align_result.token_logprob_host) and by wca_token_logprobs on given logits:
   * the log-sum-exp kernel against float64 log_softmax;
   * the batched path against the fp32 CPU oracle (contract mode) and against the same engine's materialised logits (both modes);
   * with log-probs on, the alignment (jump frames, selected heads) is bit-identical to the path without them;

@@ -2,6 +2,7 @@
 decoders. Every recording's result must be what transcribe() gives for it alone; the decode batch shrinks as recordings end, every
 row carries its own previous text as the prompt, and more recordings than max_batch go in groups. The GPU side is
 tests/test_transcribe_batch_gpu.py."""
+import ctypes
 import importlib
 import json
 import struct
@@ -349,7 +350,7 @@ def test_dropin_whisper_exports_transcribe_batch(tr):
 def test_abi_mirror_of_the_rows_entry_points(wca):
     lib = wca._lib.load()
     assert lib.wca_version() >= 11
-    assert lib.wca_greedy_decode_rows(None, None, None, 0, None, 1, None, None, None, None, None, None, None, None, None, None, None) < 0
+    assert lib.wca_decode(None, ctypes.byref(wca._lib.DecodeDesc())) < 0
     assert lib.wca_test_decode_select_rows(None, None, 1, 1, None, 2, None, None, None, 0, 1, None, None, None, None, None) < 0
     assert b"null" in lib.wca_last_error()
     assert lib.wca_test_attention_rows(None, None, None, None, None, 1, 1, 1, 1, None, 0) < 0 and b"null" in lib.wca_last_error()

@@ -1,5 +1,5 @@
 """transcribe_batch on the MI355X: three synthetic recordings of 20 s, 47 s and 75 s in lock-step on the tiny seeded model of
-tests/test_decode_gpu.py, through the engine's own decode (wca_greedy_decode_rows), against transcribe() of each recording alone.
+tests/test_decode_gpu.py, through the engine's own decode (wca_decode with per_row 1), against transcribe() of each recording alone.
 The windows (seek, size, advance, skipped) and the tokens must be equal; where they are not, the first differing window is excused
 only by a measured argmax near-tie of that window's decode (the rule of tests/test_decode_rows_gpu.py: a teacher-forced logit gap
 below 1e-3 at the first divergent position), for at most one recording of the three. Where the tokens agree, the segment times are

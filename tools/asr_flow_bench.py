@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the reference's REAL per-utterance flow (infer_ali.py:57-101: whisper.decode pre-pass -> teacher text ->
 get_attentions / force_align) at the bench configuration, through the product's pipeline: the encoder and the cross-K/V run ONCE
-per micro-batch (wca_encode_batch), the greedy decode (wca_greedy_decode) and the alignment (wca_align_batch_enqueue with
+per micro-batch (wca_encode_batch), the greedy decode (wca_decode) and the alignment (wca_align_batch_enqueue with
 pcm = NULL) both re-use them; the next batch's phase 1 is enqueued before the current batch is decoded, like the CLI does.
 
 With seeded random weights the decoder never emits <|endoftext|> by itself, so the number of sampled tokens is FIXED per run

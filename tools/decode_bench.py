@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Greedy ASR pre-pass (wca_greedy_decode) at the bench's model / batch: ms per autoregressive step with the encoder state
+"""Greedy ASR pre-pass (wca_decode) at the bench's model / batch: ms per autoregressive step with the encoder state
 already queued (wca_encode_batch), so that only the KV-cached loop is timed.
 usage: decode_bench.py [B] [sample_len] [rounds] [--temperature T] [--seed S]
---temperature T (with --seed S, default 0): the same rows through wca_decode_rows_sampled at temperature T, row b with seed S + b. That is the
+--temperature T (with --seed S, default 0): the same rows through wca_decode with temperature_host / seed_host at temperature T, row b with seed S + b. That is the
 per-row form (the prompt goes through one batched prefill, not position by position), so its base line is --temperature 0, which runs the
-same entry point greedily; without --temperature the loop is wca_greedy_decode as before.
+same per-row form greedily; without --temperature the loop is the uniform form (per_row 0) as before.
 Environment: WCA_DEC_MODES=0,1 (default): separate launches, then the fused few-row GEMMs (wca_set_decode_mode)."""
 import importlib
 import os

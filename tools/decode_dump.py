@@ -2,10 +2,14 @@
 """Every result of the greedy decode path on seeded small engines, one file per result, for byte-for-byte comparison (cmp) of two builds
 of this tree: a refactor of the decode path runs this in the tree before and in the tree after.
 
-  * uniform decode (wca_greedy_decode / _ex): the plain start, and a 12-token prompt with prefill 0 and 1
-  * ragged per-row decode (wca_greedy_decode_rows) with per-row budgets, in both precision modes
+  * uniform decode (greedy_decode: wca_decode with per_row 0): the plain start, and a 12-token prompt with prefill 0 and 1
+  * ragged per-row decode (wca_decode with per_row 1) with per-row budgets, in both precision modes
     each fused and unfused, B = 20 at 512-wide dims:
     tokens, n_tokens, sum_logprob, no_speech_prob
+  * the same ragged rows with a temperature (0 / 0.4 / 1.0 cycling) and a seed (100 + b) per row, from the input and again with
+    redecode=True on the state that decode left
+  * align_batch of a ragged batch of 3 in both precision modes: plain, with teacher-token log-probs, and with open-end rows
+    (True, False, True) plus log-probs; each in one call and as enqueue_only=True then fetch
   * get_attentions weights and logits of a ragged batch of 3 in both precision modes (the teacher-forced decoder)
   * transcribe of two synthetic recordings (45 s and 70 s) alone and as a transcribe_batch, word_timestamps=True, on a synthetic vocabulary
 
@@ -71,6 +75,9 @@ att_rows = [[*tok.sot_sequence, tok.no_timestamps, *[300 + 7 * i for i in range(
 att_tokens = torch.full((3, max(len(r) for r in att_rows)), tok.eot, dtype=torch.int64)
 for b, r in enumerate(att_rows):
     att_tokens[b, :len(r)] = torch.tensor(r)
+align_pcm = torch.from_numpy(np.stack([syn.synth_audio(s, n_samples=32000) for s in range(40, 43)])).cuda()
+align_ns = [32000, 25600, 19200]
+align_opts = m.make_opts("topk", topk=4, sot_len=len(tok.sot_sequence), medfilt_width=3)
 
 for precision in ("f16", "reference"):
     m.set_precision(precision)
@@ -83,7 +90,23 @@ for precision in ("f16", "reference"):
             save("uniform.%s.%s" % (name, tag), out + (m.last_no_speech_prob,))
         out = m.greedy_decode_rows(mel, None, None, [p[0] for p in plans], [p[1] for p in plans], budgets, sup, blank, **kw)
         save("rows.%s" % tag, out + (m.last_no_speech_prob,))
+        # temperature sampling on the same ragged rows, then once more on the state that decode left (no encoder pass)
+        skw = dict(temperature=[(0.0, 0.4, 1.0)[b % 3] for b in range(B)], seed=[100 + b for b in range(B)], **kw)
+        out = m.decode_rows_sampled(mel, None, None, [p[0] for p in plans], [p[1] for p in plans], budgets, sup, blank, **skw)
+        save("sampled.%s" % tag, out + (m.last_no_speech_prob,))
+        out = m.decode_rows_sampled(None, None, None, [p[0] for p in plans], [p[1] for p in plans], budgets, sup, blank, batch=B, redecode=True,
+                                    **skw)
+        save("sampled.redecode.%s" % tag, out + (m.last_no_speech_prob,))
     m.set_decode_mode(True)
+    # the fused alignment at B = 3: plain, with teacher-token log-probs, with open-end rows; each in one call and as enqueue then fetch
+    for name, akw, fkw in (("plain", {}, {}), ("logprobs", dict(token_logprobs_vocab_end=tok.eot), dict(with_token_logprobs=True)),
+                           ("open", dict(token_logprobs_vocab_end=tok.eot, open_end=[True, False, True]),
+                            dict(with_token_logprobs=True, with_end_rows=True))):
+        keys = ("jump", "sel") + (("token_logprobs",) if "with_token_logprobs" in fkw else ()) + (("end_rows", "scores") if "open_end" in akw else ())
+        args = (align_pcm, align_ns, att_tokens.cuda(), [len(r) for r in att_rows], [100, 80, 60], align_opts)
+        save("align.%s.%s" % (name, precision), m.align_batch(*args, **akw), keys=keys)
+        m.align_batch(*args, enqueue_only=True, **akw)
+        save("align.%s.fetch.%s" % (name, precision), m.fetch(3, att_tokens.shape[1], align_opts, **fkw), keys=keys)
     save("attentions.%s" % precision, m.get_attentions(mel[:3], att_tokens, [100, 80, 60], 3, 1.0, n_tok=[len(r) for r in att_rows]),
          keys=("weights", "logits"))
 

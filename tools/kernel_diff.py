@@ -18,7 +18,7 @@ KEYS = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment
 RENAME = [(r"(gemm256p_f16_kernel<[^,]+, [^,]+, [^,]+), 0, ", r"\1, "),
           (r"attn_kernel<(true|false), (true|false), false>", r"attn_kernel<\1, \2>"),
           (r"attn32_kernel<false, false>", "attn32_kernel"),
-          # kernels that gained a per-row instance (wca_greedy_decode_rows): the uniform launches take the <..., false> ones
+          # kernels that gained a per-row instance (wca_decode with per_row 1): the uniform launches take the <..., false> ones
           (r"(gemm_rows_f16_kernel<[^,]+, [^,]+, [^,>]+)>", r"\1, false>"),
           (r"\b(attn_decode_kernel|decode_select_kernel)\(", r"\1<false>("),
           # the waves per workgroup of the pair attention: a constant of the body now (only 4 was ever instantiated)

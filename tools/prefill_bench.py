@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Prompted greedy decode (wca_greedy_decode_ex) at the bench's model / batch: time from the start of the decode to the first
+"""Prompted greedy decode (wca_decode) at the bench's model / batch: time from the start of the decode to the first
 sampled token, initial tokens fed one position at a time (prefill 0) against the batched prefill (prefill 1), for several
 initial-token counts, in both precision modes; then a full prompted decode both ways. The encoder state is queued and
 finished before each timed call (wca_encode_batch), so only the decoder is timed.

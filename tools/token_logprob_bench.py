@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of the teacher-token log-probabilities (wca_align_batch_enqueue_ex, vocab_end = eot) on the fused batch path: the bench
+"""Cost of the teacher-token log-probabilities (wca_align_batch_enqueue, vocab_end = eot) on the fused batch path: the bench
 workload (whisper-medium dims, seeded random weights, contract mode, B = 64 utterances of 10 s with 64 characters, top-10,
 medfilt 3 -- BASELINE.json configs[1]) in ONE process, with and without log-probs in alternating rounds, each round a two-deep
 enqueue / fetch pipeline like bench.py's. Prints one JSON line: utt/s of each variant (median over rounds) and the relative cost.

@@ -3,7 +3,7 @@
 
 Seeded random weights at whisper-medium dimensions, synthetic recordings of 2-5 minutes, condition_on_previous_text=True (every
 window is decoded with the recording's own previous text as its prompt, so the rows of a batch sit at different decoder positions:
-wca_greedy_decode_rows). For every --batch value the same recordings are transcribed; batch 1 is N sequential transcribe() calls,
+wca_decode with per_row 1). For every --batch value the same recordings are transcribed; batch 1 is N sequential transcribe() calls,
 the path a `--scp` list took before transcribe_batch existed. Every batch size is warmed once untimed, then timed over --rounds
 passes whose order rotates; the median is reported as recordings/s and decoded windows/s per batch size.
 With random weights the decoder emits noise, so the number of windows per recording is whatever the seek rules make of it; it is

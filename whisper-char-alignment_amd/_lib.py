@@ -37,8 +37,25 @@ class DecodeOpts(C.Structure):
                 ("apply_timestamp_rules", C.c_int32), ("max_initial_timestamp_index", C.c_int32), ("no_speech", C.c_int32)]
 
 
-class DecodeOptsEx(C.Structure):
-    _fields_ = DecodeOpts._fields_ + [("sot_index", C.c_int32), ("prefill", C.c_int32)]
+class DecodeDesc(C.Structure):
+    """wca_decode_desc of include/wca.h"""
+    _fields_ = ([(n, C.c_void_p) for n in ("mel_dev", "pcm_dev", "n_samples_host", "initial_tokens_host", "n_initial_host", "sot_index_host",
+                                           "sample_len_host", "temperature_host", "seed_host", "suppress_mask_host", "blank_mask_host")] +
+                [("opts", C.POINTER(DecodeOpts))] +
+                [(n, C.c_void_p) for n in ("tokens_out_host", "n_tokens_host", "sum_logprob_host", "no_speech_prob_host")] +
+                [("pcm_stride", C.c_int64)] + [(n, C.c_int32) for n in ("batch", "per_row", "prefill", "redecode")])
+
+
+class AlignDesc(C.Structure):
+    """wca_align_desc of include/wca.h"""
+    _fields_ = ([(n, C.c_void_p) for n in ("pcm_dev", "n_samples_host", "tokens_dev", "n_tok_host", "max_frames_host")] +
+                [("opts", C.POINTER(AlignOpts)), ("open_end_host", C.c_void_p), ("pcm_stride", C.c_int64)] +
+                [(n, C.c_int32) for n in ("n_tok_max", "batch", "vocab_end")])
+
+
+class AlignResult(C.Structure):
+    """wca_align_result of include/wca.h"""
+    _fields_ = [(n, C.c_void_p) for n in ("jump_frame_host", "sel_idx_host", "token_logprob_host", "end_row_host", "score_host")]
 
 
 class GemmDesc(C.Structure):
@@ -99,21 +116,12 @@ SIGNATURES = {
     "wca_dtw_open": (_i, [_vp, _pf, _i, _i, _pi32, _pi32, _pi32, _pi32, _pf]),
     "wca_dtw_batch_dev_open": (_i, [_vp, _vp, _i, _i, _i, _pi32, _pi32, _pi32, _pi32, _pi32, _pf]),
     "wca_probe_heads": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _pf, _pi32]),
-    "wca_align_batch": (_i, [_vp, _vp, _i64, _pi32, _vp, _i, _pi32, _pi32, _i, C.POINTER(AlignOpts), _pi32, _pi32]),
-    "wca_align_batch_enqueue": (_i, [_vp, _vp, _i64, _pi32, _vp, _i, _pi32, _pi32, _i, C.POINTER(AlignOpts)]),
-    "wca_align_batch_fetch": (_i, [_vp, _i, _i, _i, _pi32, _pi32]),
-    "wca_align_batch_enqueue_ex": (_i, [_vp, _vp, _i64, _pi32, _vp, _i, _pi32, _pi32, _i, C.POINTER(AlignOpts), C.c_int32]),
-    "wca_align_batch_fetch_ex": (_i, [_vp, _i, _i, _i, _pi32, _pi32, _pf]),
-    "wca_align_batch_enqueue_open": (_i, [_vp, _vp, _i64, _pi32, _vp, _i, _pi32, _pi32, _i, C.POINTER(AlignOpts), C.c_int32, _pi32]),
-    "wca_align_batch_fetch_open": (_i, [_vp, _i, _i, _i, _pi32, _pi32, _pf, _pi32, _pf]),
+    "wca_align_batch": (_i, [_vp, C.POINTER(AlignDesc), C.POINTER(AlignResult)]),
+    "wca_align_batch_enqueue": (_i, [_vp, C.POINTER(AlignDesc)]),
+    "wca_align_batch_fetch": (_i, [_vp, _i, _i, _i, C.POINTER(AlignResult)]),
     "wca_token_logprobs": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "wca_encode_batch": (_i, [_vp, _vp, _vp, _i64, _pi32, _i]),
-    "wca_greedy_decode": (_i, [_vp, _vp, _vp, _i64, _pi32, _i, _pi32, _i, _vp, _vp, C.POINTER(DecodeOpts), _pi32, _pi32, _pf, _pf]),
-    "wca_greedy_decode_ex": (_i, [_vp, _vp, _vp, _i64, _pi32, _i, _pi32, _i, _vp, _vp, C.POINTER(DecodeOptsEx), _pi32, _pi32, _pf, _pf]),
-    "wca_greedy_decode_rows": (_i, [_vp, _vp, _vp, _i64, _pi32, _i, _pi32, _pi32, _pi32, _pi32, _vp, _vp, C.POINTER(DecodeOpts), _pi32, _pi32, _pf,
-                                    _pf]),
-    "wca_decode_rows_sampled": (_i, [_vp, _vp, _vp, _i64, _pi32, _i, _pi32, _pi32, _pi32, _pi32, _vp, _vp, C.POINTER(DecodeOpts), _pi32, _pi32, _pf,
-                                     _pf, _pf, C.POINTER(C.c_uint64), _i]),
+    "wca_decode": (_i, [_vp, C.POINTER(DecodeDesc)]),
     "wca_test_decode_sample_rows": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(DecodeOpts), _vp, _vp, _vp, _vp]),
     "wca_detect_language": (_i, [_vp, _vp, _vp, _i64, _pi32, _i, _i, _i, _i, _pi32, _pf]),
     "wca_test_language_head": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -624,7 +624,7 @@ __global__ __launch_bounds__(256) void attn32_kernel(AttnArgs a) {
 // head); its four waves take a quarter of the keys each; inside a wave eight lanes share a key (8 dims of 16 bytes
 // per lane), so one wave instruction reads 8 key rows, and each 8-lane group keeps its own online-softmax state
 // (m, l, o[8 dims]). Groups and waves are merged at the end (log-sum-exp combine through shuffles, then LDS).
-// ROWS: batch row b has nk_rows[b] keys (wca_greedy_decode_rows: the rows of a step sit at different positions); everything that
+// ROWS: batch row b has nk_rows[b] keys (the per-row wca_decode: the rows of a step sit at different positions); everything that
 // depends on the key count (the waves' key ranges, the dead-key clamp) is derived from the row's own count, so a row's result is that
 // of a uniform launch with nk = nk_rows[b]. The uniform launches take the ROWS = false instance.
 template <bool ROWS>

@@ -19,7 +19,7 @@ namespace wca {
 
 namespace {
 
-// a row's own position (the rows of wca_greedy_decode_rows sit at different ones), clamped to its n slots
+// a row's own position (the rows of the per-row wca_decode sit at different ones), clamped to its n slots
 __device__ __forceinline__ int clamp_pos(int t, int n) { return min(max(t, 0), n - 1); }
 
 // x[b] = token_embedding[tokens[b][t]] + positional_embedding[t]

@@ -39,7 +39,7 @@ int validate_lengths(int B, int n_tok_max, const int32_t* n_tok, const int32_t* 
   return WCA_OK;
 }
 
-// a cross-K/V slot no queued batch (wca_encode_batch / wca_greedy_decode / an un-fetched alignment) still needs
+// a cross-K/V slot no queued batch (wca_encode_batch / wca_decode / an un-fetched alignment) still needs
 int kv_slot_or_fail(wca_engine* e, int* slot) {
   *slot = take_kv_slot(e);
   return *slot < 0 ? fail(WCA_ERR_STATE, "both cross-K/V slots hold live batches: fetch or consume one first") : WCA_OK;
@@ -283,12 +283,6 @@ static int stats_on_weights(wca_engine* e, const float* attns_dev, int LH, int n
 }
 
 extern "C" {
-
-static int align_enqueue(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, const int64_t* tokens_dev,
-                         int n_tok_max, const int32_t* n_tok_host, const int32_t* max_frames_host, int batch, const wca_align_opts* o,
-                         int32_t vocab_end, const int32_t* open_end_host);
-static int align_fetch(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host, int32_t* sel_idx_host,
-                       float* token_logprob_host, int32_t* end_row_host, float* score_host);
 
 int wca_get_attentions(wca_engine* e, const float* mel_dev, const int64_t* tokens_dev, int batch, int n_tok, const int32_t* n_tok_host,
                        const int32_t* max_frames_host, int medfilt_width, float qk_scale, float* weights_out_dev,
@@ -555,42 +549,27 @@ int wca_default_find_alignment(wca_engine* e, const float* ws_dev, int L, int H,
   return read_path(e, N, F, text_idx_host, time_idx_host, path_len_host, matrix_host);
 }
 
-int wca_align_batch_enqueue(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
-                            const int64_t* tokens_dev, int n_tok_max, const int32_t* n_tok_host, const int32_t* max_frames_host,
-                            int batch, const wca_align_opts* o) {
-  return wca_align_batch_enqueue_ex(e, pcm_dev, pcm_stride, n_samples_host, tokens_dev, n_tok_max, n_tok_host, max_frames_host, batch, o, 0);
-}
-
-int wca_align_batch_enqueue_ex(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
-                               const int64_t* tokens_dev, int n_tok_max, const int32_t* n_tok_host, const int32_t* max_frames_host,
-                               int batch, const wca_align_opts* o, int32_t vocab_end) {
-  return align_enqueue(e, pcm_dev, pcm_stride, n_samples_host, tokens_dev, n_tok_max, n_tok_host, max_frames_host, batch, o, vocab_end, nullptr);
-}
-
-int wca_align_batch_enqueue_open(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
-                                 const int64_t* tokens_dev, int n_tok_max, const int32_t* n_tok_host, const int32_t* max_frames_host,
-                                 int batch, const wca_align_opts* o, int32_t vocab_end, const int32_t* open_end_host) {
-  if (!e || !open_end_host) return fail(WCA_ERR_INVALID, "null argument");
-  return align_enqueue(e, pcm_dev, pcm_stride, n_samples_host, tokens_dev, n_tok_max, n_tok_host, max_frames_host, batch, o, vocab_end,
-                       open_end_host);
-}
-
-// the body of every wca_align_batch_enqueue*: open_end_host [batch] (nullable) makes the DTW of the flagged rows open-ended
-static int align_enqueue(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, const int64_t* tokens_dev,
-                         int n_tok_max, const int32_t* n_tok_host, const int32_t* max_frames_host, int batch, const wca_align_opts* o,
-                         int32_t vocab_end, const int32_t* open_end_host) {
-  if (!e || !tokens_dev || !n_tok_host || !max_frames_host || !o) return fail(WCA_ERR_INVALID, "null argument");
+// the fused pipeline, enqueued: d->open_end_host [batch] (nullable) makes the DTW of the flagged rows open-ended
+int wca_align_batch_enqueue(wca_engine* e, const wca_align_desc* d) {
+  if (!e || !d || !d->tokens_dev || !d->n_tok_host || !d->max_frames_host || !d->opts) return fail(WCA_ERR_INVALID, "null argument");
+  const float* pcm_dev = d->pcm_dev;
+  const int64_t pcm_stride = d->pcm_stride;
+  const int64_t* tokens_dev = d->tokens_dev;
+  const int32_t *n_samples_host = d->n_samples_host, *n_tok_host = d->n_tok_host, *max_frames_host = d->max_frames_host,
+                *open_end_host = d->open_end_host;
+  const int n_tok_max = d->n_tok_max, batch = d->batch, vocab_end = d->vocab_end;
+  const wca_align_opts* o = d->opts;
   const bool want_open = open_end_host != nullptr;
   if (vocab_end < 0 || vocab_end > e->dims.n_vocab) return fail(WCA_ERR_INVALID, "vocab_end %d outside (0, %d] (0 = no token log-probs)", vocab_end, e->dims.n_vocab);
   const bool want_lp = vocab_end > 0;
-  const bool reuse_enc = (pcm_dev == nullptr);  // consume the oldest encoded state (wca_encode_batch / wca_greedy_decode)
+  const bool reuse_enc = (pcm_dev == nullptr);  // consume the oldest encoded state (wca_encode_batch / wca_decode)
   if (reuse_enc && (e->enc_q.empty() || e->enc_q.front().batch != batch))
-    return fail(WCA_ERR_STATE, "pcm_dev == NULL re-uses the oldest state left by wca_encode_batch / wca_greedy_decode for the same batch; there is none");
+    return fail(WCA_ERR_STATE, "pcm_dev == NULL re-uses the oldest state left by wca_encode_batch / wca_decode for the same batch; there is none");
   if (!reuse_enc && !n_samples_host) return fail(WCA_ERR_INVALID, "null argument");
   if (!reuse_enc && !e->enc_q.empty()) {
     // a stand-alone decode (or language detection) may have left its state behind; any other undecoded one is still wanted by its owner
     for (auto& st : e->enc_q)
-      if (!st.decoded && !st.detected) return fail(WCA_ERR_STATE, "an encoded batch is waiting for wca_greedy_decode / wca_align_batch_enqueue(pcm_dev = NULL)");
+      if (!st.decoded && !st.detected) return fail(WCA_ERR_STATE, "an encoded batch is waiting for wca_decode / wca_align_batch_enqueue(pcm_dev = NULL)");
     for (auto& st : e->enc_q) e->slot_busy[st.slot] = false;
     e->enc_q.clear();
   }
@@ -722,24 +701,11 @@ int wca_encode_batch(wca_engine* e, const float* mel_dev, const float* pcm_dev, 
   return WCA_OK;
 }
 
-int wca_align_batch_fetch(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host, int32_t* sel_idx_host) {
-  return wca_align_batch_fetch_ex(e, batch, n_tok_max, topk, jump_frame_host, sel_idx_host, nullptr);
-}
-
-int wca_align_batch_fetch_ex(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host, int32_t* sel_idx_host,
-                             float* token_logprob_host) {
-  return align_fetch(e, batch, n_tok_max, topk, jump_frame_host, sel_idx_host, token_logprob_host, nullptr, nullptr);
-}
-
-int wca_align_batch_fetch_open(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host, int32_t* sel_idx_host,
-                               float* token_logprob_host, int32_t* end_row_host, float* score_host) {
-  return align_fetch(e, batch, n_tok_max, topk, jump_frame_host, sel_idx_host, token_logprob_host, end_row_host, score_host);
-}
-
-// the body of every wca_align_batch_fetch*
-static int align_fetch(wca_engine* e, int batch, int n_tok_max, int topk, int32_t* jump_frame_host, int32_t* sel_idx_host,
-                       float* token_logprob_host, int32_t* end_row_host, float* score_host) {
+int wca_align_batch_fetch(wca_engine* e, int batch, int n_tok_max, int topk, const wca_align_result* r) {
   if (!e) return fail(WCA_ERR_INVALID, "null engine");
+  if (!r) return fail(WCA_ERR_INVALID, "null argument");
+  int32_t *jump_frame_host = r->jump_frame_host, *sel_idx_host = r->sel_idx_host, *end_row_host = r->end_row_host;
+  float *token_logprob_host = r->token_logprob_host, *score_host = r->score_host;
   if (e->fetch_count >= e->enq_count) return fail(WCA_ERR_STATE, "nothing to fetch");
   const int rs = (int)(e->fetch_count & 1);  // oldest un-fetched batch
   if (batch != e->res_batch[rs] || n_tok_max != e->res_ntok[rs]) return fail(WCA_ERR_STATE, "fetch does not match the oldest pending enqueue");
@@ -747,7 +713,7 @@ static int align_fetch(wca_engine* e, int batch, int n_tok_max, int topk, int32_
   // (checked before anything is consumed: the caller can fetch the same batch again without them)
   if (token_logprob_host && !e->res_lp[rs]) return fail(WCA_ERR_STATE, "token log-probs requested, but the pending batch was enqueued without them (vocab_end = 0)");
   if ((end_row_host || score_host) && !e->res_open[rs])
-    return fail(WCA_ERR_STATE, "end rows requested, but the pending batch was not enqueued with wca_align_batch_enqueue_open");
+    return fail(WCA_ERR_STATE, "end rows requested, but the pending batch was enqueued without open_end_host");
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipEventSynchronize(e->res_ev[rs]));
   const ResLayout at = res_layout(batch, n_tok_max, e->res_topk[rs], e->res_lp[rs], e->res_open[rs]);
@@ -769,11 +735,10 @@ static int align_fetch(wca_engine* e, int batch, int n_tok_max, int topk, int32_
   return WCA_OK;
 }
 
-int wca_align_batch(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, const int64_t* tokens_dev,
-                    int n_tok_max, const int32_t* n_tok_host, const int32_t* max_frames_host, int batch, const wca_align_opts* o,
-                    int32_t* jump_frame_host, int32_t* sel_idx_host) {
-  WCA_TRY(wca_align_batch_enqueue(e, pcm_dev, pcm_stride, n_samples_host, tokens_dev, n_tok_max, n_tok_host, max_frames_host, batch, o));
-  return wca_align_batch_fetch(e, batch, n_tok_max, o->aggregation == WCA_AGGR_TOPK ? o->topk : 0, jump_frame_host, sel_idx_host);
+int wca_align_batch(wca_engine* e, const wca_align_desc* d, const wca_align_result* r) {
+  if (!e || !d || !r) return fail(WCA_ERR_INVALID, "null argument");
+  WCA_TRY(wca_align_batch_enqueue(e, d));
+  return wca_align_batch_fetch(e, d->batch, d->n_tok_max, d->opts->aggregation == WCA_AGGR_TOPK ? d->opts->topk : 0, r);
 }
 
 int wca_token_logprobs(wca_engine* e, const float* logits_dev, int rows, int ld, int vocab_end, const int64_t* targets_dev, float* out_dev) {

@@ -1,16 +1,15 @@
-// libwca.so engine, greedy decode: wca_greedy_decode / _ex (every row at the same position, optional batched prefill) and
-// wca_greedy_decode_rows (per-row initial tokens and sample budgets) over one argument check, one loop and one read-back;
-// wca_decode_rows_sampled (the per-row call with a temperature and a seed per row, optionally on the state the last decode left); and
-// wca_detect_language (one position and the language head on the state a decode then takes).
+// libwca.so engine, decode: wca_decode -- every row at the same position with an optional batched prefill, or per-row initial tokens,
+// sample budgets, temperatures and seeds, optionally on the state the last decode left -- over one argument check, one loop and one
+// read-back; and wca_detect_language (one position and the language head on the state a decode then takes).
 #include "engine_internal.h"
 
 using namespace wca;
 
 namespace {
 
-// The rows of a decode as the entry points give them. each = 1: n_initial / sot_index / sample_len are arrays of [batch] and row b's
-// initial tokens start at initial + b * n_max (wca_greedy_decode_rows); each = 0: one value, one token row, for every row -- the uniform
-// call is `batch` identical rows.
+// The rows of a decode as the descriptor gives them. each = per_row = 1: n_initial / sot_index / sample_len are arrays of [batch] and row b's
+// initial tokens start at initial + b * n_max; each = 0: one value, one token row, for every row -- the uniform call is `batch` identical
+// rows.
 struct DecodeRows {
   int batch, each;
   const int32_t *initial, *n_initial, *sot_index, *sample_len;
@@ -20,11 +19,14 @@ struct DecodeRows {
   const int32_t* init(int b) const { return initial + (size_t)b * each * n_max; }
 };
 
-// What both entry points refuse, before any work is enqueued: the engine's state, the exclusive mel / pcm inputs, null pointers (any_null:
-// the caller's own list), the batch range, each row's lengths and <|sot|> position, eot / timestamp_begin, the initial tokens. Sets r's sizes.
-template <typename Opts>
-int decode_check(wca_engine* e, const float* mel_dev, const float* pcm_dev, const int32_t* n_samples_host, bool any_null, const Opts* o,
-                 DecodeRows* r) {
+// What every decode is refused for, before any work is enqueued: the engine's state, the exclusive mel / pcm inputs, null pointers, the batch
+// range, each row's lengths and <|sot|> position, eot / timestamp_begin, the initial tokens. Sets r's sizes.
+int decode_check(wca_engine* e, const wca_decode_desc* d, DecodeRows* r) {
+  const float *mel_dev = d->mel_dev, *pcm_dev = d->pcm_dev;
+  const int32_t* n_samples_host = d->n_samples_host;
+  const wca_decode_opts* o = d->opts;
+  const bool any_null = !d->initial_tokens_host || !d->n_initial_host || !d->sot_index_host || !d->sample_len_host || !d->suppress_mask_host ||
+                        !o || !d->tokens_out_host || !d->n_tokens_host;
   const int rc = check_ready(e);
   if (rc) return rc;
   if (mel_dev != nullptr && pcm_dev != nullptr) return fail(WCA_ERR_INVALID, "pass at most one of mel_dev / pcm_dev");
@@ -57,13 +59,13 @@ int decode_check(wca_engine* e, const float* mel_dev, const float* pcm_dev, cons
   return WCA_OK;
 }
 
-// What wca_greedy_decode_ex and wca_greedy_decode_rows share around the loop.
+// What the uniform and the per-row decode share around the loop.
 // Phase 1 on `stream` (unless an encoded state is waiting: wca_encode_batch) and the state to decode; the state stays queued for the
 // alignment (wca_align_batch_enqueue with pcm_dev = NULL). A state that was decoded but never aligned is stale once another decode
 // starts (stand-alone whisper.decode use). The autoregressive loop runs on `stream2` (it shares the decoder scratch with phase 2 of
 // the alignment, which is ordered before it on that stream; phase 1 of the NEXT batch may run beside it on `stream`): stream2 is made
 // to wait for the state's cross-K/V here.
-// redecode (wca_decode_rows_sampled; no input of its own): the state is the NEWEST one that is already decoded and not yet aligned -- what
+// redecode (no input of its own): the state is the NEWEST one that is already decoded and not yet aligned -- what
 // the previous decode left for the alignment -- and nothing is dropped: it stays queued, decoded, for that alignment.
 int decode_take_state(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, int batch,
                       wca_engine::EncState** out, bool redecode = false) {
@@ -105,9 +107,11 @@ int decode_take_state(wca_engine* e, const float* mel_dev, const float* pcm_dev,
 // The token rows, sum_logprob and no_speech_prob of a loop that made `steps` choices to the host. Row b holds its initial tokens and has
 // written positions [0, n_have) with n_have = n_initial + min(steps, its budget); n_tokens[b] = its first sampled EOT (or n_have):
 // tokens_out[b][n_initial : n_tokens[b]] are the sampled tokens, and positions never reached hold EOT. Marks the state decoded.
-int decode_read_back(wca_engine* e, hipStream_t s2, wca_engine::EncState* st, const DecodeRows& r, int steps, int eot, int32_t* tokens_out_host,
-                     int32_t* n_tokens_host, float* sum_logprob_host, float* no_speech_prob_host) {
-  const int batch = r.batch, T_max = r.T_max;
+int decode_read_back(wca_engine* e, hipStream_t s2, wca_engine::EncState* st, const DecodeRows& r, int steps, const wca_decode_desc* d,
+                     bool want_nsp) {
+  const int batch = r.batch, T_max = r.T_max, eot = d->opts->eot;
+  int32_t *tokens_out_host = d->tokens_out_host, *n_tokens_host = d->n_tokens_host;
+  float *sum_logprob_host = d->sum_logprob_host, *no_speech_prob_host = want_nsp ? d->no_speech_prob_host : nullptr;
   std::vector<int32_t> toks((size_t)batch * T_max);
   HIPCHK(hipMemcpyAsync(toks.data(), e->dec_tokens.p, sizeof(int) * toks.size(), hipMemcpyDeviceToHost, s2));
   std::vector<float> lp(2 * (size_t)batch);  // sum_logprob [batch], no_speech_prob [batch] at the head of dec_state
@@ -158,10 +162,10 @@ struct DecodeLoop {
 // Takes the state to decode (phase 1 first where a mel / PCM is given), sizes the decode buffers, uploads the token rows [batch][T_max]
 // (row b's initial tokens, then eot), the per-row tables `tab` (nullable -> e->dec_rows) and the masks, zeroes sum_logprob / no_speech_prob
 // and the n_done_len completion counters. A prefill also leaves the <|sot|> logits (rows [batch, 2 batch)) and needs the gather scratch.
-template <typename Opts>
-int decode_begin(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, const DecodeRows& r,
-                 int n_done_len, bool prefill, const std::vector<int32_t>* tab, const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host,
-                 const Opts* o, bool nsp_asked, DecodeLoop* out, bool redecode = false) {
+int decode_begin(wca_engine* e, const wca_decode_desc* d, const DecodeRows& r, int n_done_len, const std::vector<int32_t>* tab, DecodeLoop* out) {
+  const wca_decode_opts* o = d->opts;
+  const uint8_t *suppress_mask_host = d->suppress_mask_host, *blank_mask_host = d->blank_mask_host;
+  const bool prefill = d->prefill == 1;
   const wca_model_dims& D = e->dims;
   const int V = D.n_vocab, dt = D.n_text_state, L = D.n_text_layer, batch = r.batch, T_max = r.T_max;
   std::vector<int32_t> init((size_t)batch * T_max, o->eot);
@@ -171,13 +175,13 @@ int decode_begin(wca_engine* e, const float* mel_dev, const float* pcm_dev, int6
   lp.batch = batch;
   lp.T_max = T_max;
   lp.V = V;
-  WCA_TRY(decode_take_state(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, &lp.st, redecode));
+  WCA_TRY(decode_take_state(e, d->mel_dev, d->pcm_dev, d->pcm_stride, d->n_samples_host, batch, &lp.st, d->redecode == 1));
   lp.kvbuf = lp.st->slot ? e->kv_alt : e->kv;
   hipStream_t s2 = lp.s2 = e->stream2;
   HIPCHK(e->dec_cache.ensure(sizeof(half_t) * (size_t)L * 2 * batch * T_max * dt));
   HIPCHK(e->dec_tokens.ensure(sizeof(int) * (size_t)batch * T_max));
   HIPCHK(e->dec_masks.ensure((size_t)2 * V));
-  lp.want_nsp = nsp_asked && o->no_speech >= 0 && o->no_speech < V;
+  lp.want_nsp = d->no_speech_prob_host && o->no_speech >= 0 && o->no_speech < V;
   lp.no_speech = o->no_speech;
   // the prefill's logits: rows [0, B) at the last initial position, rows [B, 2B) at <|sot|>
   HIPCHK(e->dec_logits.ensure(sizeof(float) * (size_t)((prefill && lp.want_nsp) ? 2 : 1) * batch * V));
@@ -218,7 +222,7 @@ int decode_begin(wca_engine* e, const float* mel_dev, const float* pcm_dev, int6
 // whole batch (run_decode_prefill), and the step loop continues behind it; or (n_prefill = 0) the initial tokens are fed
 // one position at a time, n_warm of them before the first choice (the plain start is 3 tokens: sot, language, task). At most `budget`
 // choices. Uniform rows (tab == nullptr): every row holds n_initial tokens, choice c reads the forward of position n_initial - 1 + c, and
-// no_speech_prob is taken at position sot_index. Per-row (tab, device): the tables of wca_greedy_decode_rows say where each row is.
+// no_speech_prob is taken at position sot_index. Per-row (tab, device): the tables of decode_per_row say where each row is.
 struct DecodePlan {
   int n_prefill, n_warm, budget;
   int n_initial, sot_index;
@@ -229,8 +233,7 @@ struct DecodePlan {
 // choice c = f - n_warm. Ends after `budget` choices or when every row has produced EOT (or used its own budget), asked every 4 choices.
 // The uniform form launches the scalar kernels with n_done indexed by cur_len, the per-row form the table kernels with n_done indexed by c.
 // Then the results to the host (decode_read_back) and the positions wca_last_decode_positions reports.
-int decode_run(const DecodeLoop& lp, const DecodePlan& pl, const DecodeRows& r, int eot, int32_t* tokens_out_host, int32_t* n_tokens_host,
-               float* sum_logprob_host, float* no_speech_prob_host) {
+int decode_run(const DecodeLoop& lp, const DecodePlan& pl, const DecodeRows& r, const wca_decode_desc* d) {
   wca_engine* e = lp.e;
   const int B = lp.batch, V = lp.V;
   const float* logits = (const float*)e->dec_logits.p;
@@ -266,8 +269,7 @@ int decode_run(const DecodeLoop& lp, const DecodePlan& pl, const DecodeRows& r, 
       if (done) break;
     }
   }
-  WCA_TRY(decode_read_back(e, lp.s2, lp.st, r, steps, eot, tokens_out_host, n_tokens_host, sum_logprob_host,
-                           lp.want_nsp ? no_speech_prob_host : nullptr));
+  WCA_TRY(decode_read_back(e, lp.s2, lp.st, r, steps, d, lp.want_nsp));
   e->dec_prefill_positions = pl.n_prefill;
   e->dec_step_positions = step_positions;
   e->dec_batch = B;
@@ -276,93 +278,47 @@ int decode_run(const DecodeLoop& lp, const DecodePlan& pl, const DecodeRows& r, 
   return WCA_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int wca_greedy_decode(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
-                      int batch, const int32_t* initial_tokens_host, int n_initial, const uint8_t* suppress_mask_host,
-                      const uint8_t* blank_mask_host, const wca_decode_opts* o, int32_t* tokens_out_host, int32_t* n_tokens_host,
-                      float* sum_logprob_host, float* no_speech_prob_host) {
-  if (!e) return fail(WCA_ERR_INVALID, "null engine");
-  if (!o) return fail(WCA_ERR_INVALID, "null argument");
-  if (n_initial + o->sample_len > e->dims.n_text_ctx)
-    return fail(WCA_ERR_TOO_LONG, "n_initial %d + sample_len %d exceeds n_text_ctx %d", n_initial, o->sample_len, e->dims.n_text_ctx);
-  wca_decode_opts_ex x{};
-  x.sample_len = o->sample_len;
-  x.eot = o->eot;
-  x.timestamp_begin = o->timestamp_begin;
-  x.apply_timestamp_rules = o->apply_timestamp_rules;
-  x.max_initial_timestamp_index = o->max_initial_timestamp_index;
-  x.no_speech = o->no_speech;
-  x.sot_index = 0;
-  x.prefill = 0;
-  return wca_greedy_decode_ex(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, initial_tokens_host, n_initial, suppress_mask_host,
-                              blank_mask_host, &x, tokens_out_host, n_tokens_host, sum_logprob_host, no_speech_prob_host);
-}
-
-int wca_greedy_decode_ex(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
-                         int batch, const int32_t* initial_tokens_host, int n_initial, const uint8_t* suppress_mask_host,
-                         const uint8_t* blank_mask_host, const wca_decode_opts_ex* o, int32_t* tokens_out_host, int32_t* n_tokens_host,
-                         float* sum_logprob_host, float* no_speech_prob_host) {
-  const int32_t ni = n_initial;
-  DecodeRows r{batch, 0, initial_tokens_host, &ni, o ? &o->sot_index : nullptr, o ? &o->sample_len : nullptr};
-  int rc = decode_check(e, mel_dev, pcm_dev, n_samples_host, !initial_tokens_host || !suppress_mask_host || !o || !tokens_out_host || !n_tokens_host,
-                        o, &r);
-  if (rc) return rc;
-  if (o->prefill != 0 && o->prefill != 1) return fail(WCA_ERR_INVALID, "prefill must be 0 or 1");
-  const bool prefill = o->prefill == 1;
+// The uniform decode (per_row 0): every row holds the same n_initial tokens; the scalar kernels, with or without a prefill.
+int decode_uniform(wca_engine* e, const wca_decode_desc* d, const DecodeRows& r) {
+  const int n_initial = r.ni(0);
+  const bool prefill = d->prefill == 1;
   DecodeLoop lp;
-  if ((rc = decode_begin(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, r, r.T_max, prefill, nullptr, suppress_mask_host, blank_mask_host, o,
-                         no_speech_prob_host != nullptr, &lp)))
-    return rc;
+  WCA_TRY(decode_begin(e, d, r, r.T_max, nullptr, &lp));
   lp.sel.n_initial = n_initial;
   // sampling starts after the last initial token
-  const DecodePlan pl{prefill ? n_initial : 0, prefill ? 0 : n_initial - 1, o->sample_len, n_initial, o->sot_index, nullptr};
-  return decode_run(lp, pl, r, o->eot, tokens_out_host, n_tokens_host, sum_logprob_host, no_speech_prob_host);
+  const DecodePlan pl{prefill ? n_initial : 0, prefill ? 0 : n_initial - 1, r.S, n_initial, r.sot_index[0], nullptr};
+  return decode_run(lp, pl, r, d);
 }
 
-// Greedy decode of a batch whose rows carry initial tokens of their own (transcribe_batch: every recording's prompt is its own previous
-// text). Row b holds n_initial[b] tokens and samples at most sample_len[b]; at loop step s (0 = the prefill's choice) it is at
+// The decode of a batch whose rows carry initial tokens of their own (per_row 1; transcribe_batch: every recording's prompt is its own
+// previous text). Row b holds n_initial[b] tokens and samples at most sample_len[b]; at loop step s (0 = the prefill's choice) it is at
 // cur_len = n_initial[b] + s. Prefill: every row padded with eot to n_max = max n_initial (a valid query never sees a later position,
 // and the K/V that the pad positions leave in cache slots >= n_initial[b] are overwritten by the step loop before they are read);
 // steps: the per-row forms of embed_step / KV append / one-query attention / decode_select, fed from small device tables built here.
 // A row past its budget keeps going through the kernels as a finished row at a clamped position (<= T_max - 2, so no positional row
 // past n_text_ctx - 1 and no cache slot past T_max - 1 is touched); what it computes is never read.
 //
-// Sampling (wca_decode_rows_sampled: temperature_host / seed_host [batch], else both null): the tables gain the rows' Philox seeds and
-// temperatures, and the select step takes its sampling form; everything else is the greedy call. redecode: see decode_take_state.
-static int decode_rows(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host, int batch,
-                       const int32_t* initial_tokens_host, const int32_t* n_initial_host, const int32_t* sot_index_host,
-                       const int32_t* sample_len_host, const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host,
-                       const wca_decode_opts* o, int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
-                       float* no_speech_prob_host, const float* temperature_host, const uint64_t* seed_host, bool redecode) {
-  DecodeRows r{batch, 1, initial_tokens_host, n_initial_host, sot_index_host, sample_len_host};
-  int rc = decode_check(e, mel_dev, pcm_dev, n_samples_host,
-                        !initial_tokens_host || !n_initial_host || !sot_index_host || !sample_len_host || !suppress_mask_host || !o ||
-                            !tokens_out_host || !n_tokens_host,
-                        o, &r);
-  if (rc) return rc;
-  if (redecode && (mel_dev || pcm_dev)) return fail(WCA_ERR_INVALID, "redecode takes no input: pass mel_dev = pcm_dev = NULL");
-  for (int b = 0; temperature_host && b < batch; ++b)
-    if (!(temperature_host[b] >= 0.f) || !std::isfinite(temperature_host[b]))
-      return fail(WCA_ERR_INVALID, "row %d: temperature %g is negative or not finite", b, (double)temperature_host[b]);
-  const int T_max = r.T_max, S = r.S;
+// Sampling (temperature_host / seed_host [batch], else both null): the tables gain the rows' Philox seeds and temperatures, and the select
+// step takes its sampling form (upstream GreedyDecoder.update at temperature > 0; decode.hip); everything else is the greedy call.
+// redecode: see decode_take_state.
+int decode_per_row(wca_engine* e, const wca_decode_desc* d, const DecodeRows& r) {
+  const int batch = r.batch, T_max = r.T_max, S = r.S;
+  const float* temperature_host = d->temperature_host;
   // the int tables: [0] n_initial - 1, [1] sot_index, [2] n_initial, [3] sample cap; then per choice c in [0, S): fed position
   // min(n_initial + c - 1, T_max - 2), key count = fed position + 1, cur_len = n_initial + c  ([batch] each)
   // sampling: behind them (at an even index: 8-byte aligned) the seeds [batch] uint64, then the temperatures [batch] f32
   const size_t n_int = (size_t)(4 + 3 * S) * batch, seed_at = (n_int + 1) & ~(size_t)1, temp_at = seed_at + 2 * (size_t)batch;
   std::vector<int32_t> tab(temperature_host ? temp_at + batch : n_int);
   if (temperature_host) {
-    memcpy(tab.data() + seed_at, seed_host, sizeof(uint64_t) * batch);
+    memcpy(tab.data() + seed_at, d->seed_host, sizeof(uint64_t) * batch);
     memcpy(tab.data() + temp_at, temperature_host, sizeof(float) * batch);
   }
   for (int b = 0; b < batch; ++b) {
-    const int ni = n_initial_host[b];
+    const int ni = r.ni(b);
     tab[0 * (size_t)batch + b] = ni - 1;
-    tab[1 * (size_t)batch + b] = sot_index_host[b];
+    tab[1 * (size_t)batch + b] = r.sot_index[b];
     tab[2 * (size_t)batch + b] = ni;
-    tab[3 * (size_t)batch + b] = sample_len_host[b];
+    tab[3 * (size_t)batch + b] = r.sl(b);
     for (int c = 0; c < S; ++c) {
       const int pos = std::max(0, std::min(ni + c - 1, T_max - 2));
       tab[(size_t)(4 + 3 * c + 0) * batch + b] = pos;
@@ -371,9 +327,7 @@ static int decode_rows(wca_engine* e, const float* mel_dev, const float* pcm_dev
     }
   }
   DecodeLoop lp;
-  if ((rc = decode_begin(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, r, S, true, &tab, suppress_mask_host, blank_mask_host, o,
-                         no_speech_prob_host != nullptr, &lp, redecode)))
-    return rc;
+  WCA_TRY(decode_begin(e, d, r, S, &tab, &lp));
   const int* tab_dev = (const int*)e->dec_rows.p;
   lp.sel.n_initial_rows = tab_dev + 2 * (size_t)batch;
   lp.sel.cap_rows = tab_dev + 3 * (size_t)batch;
@@ -382,36 +336,31 @@ static int decode_rows(wca_engine* e, const float* mel_dev, const float* pcm_dev
     lp.sel.temperature_rows = (const float*)(tab_dev + temp_at);
   }
   const DecodePlan pl{r.n_max, 0, S, 0, -1, tab_dev};
-  return decode_run(lp, pl, r, o->eot, tokens_out_host, n_tokens_host, sum_logprob_host, no_speech_prob_host);
+  return decode_run(lp, pl, r, d);
 }
 
-int wca_greedy_decode_rows(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
-                           int batch, const int32_t* initial_tokens_host, const int32_t* n_initial_host, const int32_t* sot_index_host,
-                           const int32_t* sample_len_host, const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host,
-                           const wca_decode_opts* o, int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
-                           float* no_speech_prob_host) {
-  return decode_rows(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, initial_tokens_host, n_initial_host, sot_index_host, sample_len_host,
-                     suppress_mask_host, blank_mask_host, o, tokens_out_host, n_tokens_host, sum_logprob_host, no_speech_prob_host, nullptr, nullptr,
-                     false);
-}
+}  // namespace
 
-// wca_greedy_decode_rows with a temperature and a Philox seed per row (upstream GreedyDecoder.update at temperature > 0; decode.hip), and
-// optionally on the state the previous decode left (redecode: the rungs of transcribe's temperature fallback cost no encoder pass).
-int wca_decode_rows_sampled(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int32_t* n_samples_host,
-                            int batch, const int32_t* initial_tokens_host, const int32_t* n_initial_host, const int32_t* sot_index_host,
-                            const int32_t* sample_len_host, const uint8_t* suppress_mask_host, const uint8_t* blank_mask_host,
-                            const wca_decode_opts* o, int32_t* tokens_out_host, int32_t* n_tokens_host, float* sum_logprob_host,
-                            float* no_speech_prob_host, const float* temperature_host, const uint64_t* seed_host, int redecode) {
+extern "C" {
+
+int wca_decode(wca_engine* e, const wca_decode_desc* d) {
   if (!e) return fail(WCA_ERR_INVALID, "null engine");
-  if (!temperature_host || !seed_host) return fail(WCA_ERR_INVALID, "null argument");
-  if (redecode != 0 && redecode != 1) return fail(WCA_ERR_INVALID, "redecode must be 0 or 1");
-  return decode_rows(e, mel_dev, pcm_dev, pcm_stride, n_samples_host, batch, initial_tokens_host, n_initial_host, sot_index_host, sample_len_host,
-                     suppress_mask_host, blank_mask_host, o, tokens_out_host, n_tokens_host, sum_logprob_host, no_speech_prob_host,
-                     temperature_host, seed_host, redecode == 1);
+  if (!d) return fail(WCA_ERR_INVALID, "null descriptor");
+  if ((d->per_row | d->prefill | d->redecode) & ~1) return fail(WCA_ERR_INVALID, "per_row, prefill and redecode must each be 0 or 1");
+  if (!d->temperature_host != !d->seed_host) return fail(WCA_ERR_INVALID, "temperature_host and seed_host are given together or not at all");
+  if (!d->per_row && (d->temperature_host || d->redecode)) return fail(WCA_ERR_INVALID, "temperatures, seeds and redecode need per_row = 1");
+  if (d->per_row && !d->prefill) return fail(WCA_ERR_INVALID, "per_row = 1 always runs the batched prefill: pass prefill = 1");
+  if (d->redecode && (d->mel_dev || d->pcm_dev)) return fail(WCA_ERR_INVALID, "redecode takes no input: pass mel_dev = pcm_dev = NULL");
+  DecodeRows r{d->batch, d->per_row, d->initial_tokens_host, d->n_initial_host, d->sot_index_host, d->sample_len_host};
+  WCA_TRY(decode_check(e, d, &r));
+  for (int b = 0; d->temperature_host && b < d->batch; ++b)
+    if (!(d->temperature_host[b] >= 0.f) || !std::isfinite(d->temperature_host[b]))
+      return fail(WCA_ERR_INVALID, "row %d: temperature %g is negative or not finite", b, (double)d->temperature_host[b]);
+  return d->per_row ? decode_per_row(e, d, r) : decode_uniform(e, d, r);
 }
 
 // Language identification (upstream detect_language): phase 1 as a decode takes it, ONE decoder position (t = 0, token sot) for every
-// row -- the first warm step of wca_greedy_decode up to the final residual stream, no vocabulary projection --, the language head on
+// row -- the first warm step of a wca_decode without prefill up to the final residual stream, no vocabulary projection --, the language head on
 // e->xd (language_head.hip: final LayerNorm and the n_lang rows of the token embedding), one read-back. f16 operands in both precision
 // modes, like the greedy pre-pass. The state stays queued and UNDECODED: the decode that follows with mel_dev = pcm_dev = NULL runs on it
 // with no second encoder pass (decode_begin sets up dec_tokens, dec_state and the cache again; nothing of the detection is read).

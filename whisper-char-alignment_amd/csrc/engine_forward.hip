@@ -275,7 +275,7 @@ struct DecPass {
   const half_t* kv;      // cross-K/V of the batch (rows [hi | lo] in split mode; single operands read the hi halves)
   // self-attention keys: the QKV buffer itself under the causal mask (cache == nullptr), or the cache planes [L][2][B][T_max][d], to
   // which the QKV projection appends position pos and whose first pos + 1 slots the one query attends to. With per-row positions the key
-  // counts are the table behind the positions: a step's tables are [B] fed positions, then [B] key counts (wca_greedy_decode_rows)
+  // counts are the table behind the positions: a step's tables are [B] fed positions, then [B] key counts (the per-row wca_decode)
   half_t* cache;
   int T_max;
   StepPos pos;
@@ -452,7 +452,7 @@ int dec_logits(wca_engine* e, const DecPass& p, const float* x, half_t* xn, int 
 // GEMMs (the few-row kernel of gemm_rows.hip has no pair output), attn_split_kernel; the captured logits are the three-pass fp32 sums and
 // every f16 operand row is [hi | lo], twice as wide as in the f16 mode.
 // finish_last: the last layer runs to its end (cross-out, ln2, MLP) also without logits_out: e->xd then holds the final residual stream
-// (the token log-probs of wca_align_batch_enqueue_ex take it from there)
+// (the token log-probs of wca_align_batch_enqueue with vocab_end take it from there)
 int run_decoder(wca_engine* e, const int64_t* tokens_dev, int B, int n, float* cap, int Fpad, int Fcap, float* logits_out, hipStream_t s,
                 const half_t* kvbuf, bool finish_last) {
   const wca_model_dims& D = e->dims;
@@ -502,7 +502,7 @@ int run_decode_step(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int
 // the step loop continues at t = n); each layer's cross-K/V is read once for all n queries of a row. Only the rows whose logits
 // are needed get the final LayerNorm and the vocabulary projection: position `last` (the first choice is read there) -> e->dec_logits
 // rows [0, B), and, where given, position `sot` -> rows [B, 2B). Scalars (last.t = n - 1; sot.t < 0: no sot logits), or per row where the
-// rows hold different numbers of initial tokens, padded to n (wca_greedy_decode_rows: last.rows[b] = n_initial[b] - 1; sot.rows nullable).
+// rows hold different numbers of initial tokens, padded to n (the per-row wca_decode: last.rows[b] = n_initial[b] - 1; sot.rows nullable).
 int run_decode_prefill(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, int n, int T_max, StepPos last, StepPos sot) {
   const int dt = e->dims.n_text_state;
   // the scratch is carved for max_batch x n_text_ctx rows; the GEMMs on more than DEC_ROWS_MAX rows take dec_gemm's separate

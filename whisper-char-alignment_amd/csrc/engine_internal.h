@@ -173,9 +173,9 @@ struct wca_engine {
   wca::GrowBuf quiet_out;           // wca_quiet_cuts: the interior cuts [n_pieces - 1] then their levels [n_pieces - 1], copied to the host before the call returns
   wca::GrowBuf probe_jump;          // the last wca_probe_heads' jump frames [LH][N], kept on the device for wca_probe_strict_tp
   int probe_LH = 0, probe_N = 0;
-  // greedy ASR pre-pass (wca_greedy_decode): self-attention K/V cache [L][2][B][T_max][d], token rows, masks, logits
+  // greedy ASR pre-pass (wca_decode): self-attention K/V cache [L][2][B][T_max][d], token rows, masks, logits
   wca::GrowBuf dec_cache, dec_tokens, dec_masks, dec_logits, dec_state;
-  wca::GrowBuf dec_rows;              // wca_greedy_decode_rows: the per-row int tables (n_initial - 1, sot_index, n_initial, sample cap; per step: fed position, key count, cur_len)
+  wca::GrowBuf dec_rows;              // the per-row wca_decode: the per-row int tables (n_initial - 1, sot_index, n_initial, sample cap; per step: fed position, key count, cur_len)
   wca::GrowBuf dec_gather;            // prefill: the f32 residual rows whose logits are needed ([2B][d]: last initial position, <|sot|>)
   int* dec_done_host = nullptr;  // pinned: completion counter read back while the loop runs
   // wca_resample_16k: the polyphase tables of the input rates seen so far (f32 on the device, in the layout the plan's table home reads);
@@ -185,7 +185,7 @@ struct wca_engine {
   int dec_prefill_positions = 0, dec_step_positions = 0;  // the last decode: positions per row fed by the prefill / one at a time
   int dec_batch = 0, dec_T_max = 0, dec_logits_rows = 0;  // the last decode's cache shape and the rows its forwards left in dec_logits (wca_test_decode_state)
   // Encoded micro-batches (log-mel + encoder + cross-K/V done, recorded on `stream`) that no alignment has consumed
-  // yet: wca_encode_batch / wca_greedy_decode push, wca_align_batch_enqueue(pcm_dev = NULL) pops the oldest. A K/V
+  // yet: wca_encode_batch / wca_decode push, wca_align_batch_enqueue(pcm_dev = NULL) pops the oldest. A K/V
   // slot stays busy from its encode until the alignment that consumed it has been fetched.
   // detected: wca_detect_language has read this (still undecoded) state; it waits for the decode that follows with mel_dev = pcm_dev = NULL
   // and is dropped, like a decoded one, when a decode or a detection brings an input of its own
@@ -200,7 +200,7 @@ struct wca_engine {
   int res_topk[2] = {0, 0}, res_ntok[2] = {0, 0}, res_batch[2] = {0, 0};
   bool res_open[2] = {false, false}; // the batch in that slot was enqueued open-ended (its staging slot holds end rows and scores)
   bool res_lp[2] = {false, false};   // the batch in that slot was enqueued with token log-probs (its staging slot holds them)
-  // teacher-token log-probs of wca_align_batch_enqueue_ex (phase 2's stream): compact f32 rows, their final-LayerNorm output (pairs when DEC
+  // teacher-token log-probs of wca_align_batch_enqueue with vocab_end (phase 2's stream): compact f32 rows, their final-LayerNorm output (pairs when DEC
   // is split), the row map, the chunked [rows][ldc] f32 logits scratch and the [B][n_tok_max] results
   wca::GrowBuf lp_x, lp_xn, lp_map, lp_logits, lp_out;
   unsigned long enq_count = 0, fetch_count = 0;

@@ -73,7 +73,7 @@ struct GemmArgs {
   int splitk;              // workgroups sharing K (0 = chosen by launch_gemm_rows: smallest with K / splitk <= 1024)
   int groups;              // 16-column groups per workgroup (0 = chosen: grid.x <= 256)
   const int* kv_t_rows;    // few-row kernel, with kv_k: non-null = row m appends at position kv_t_rows[m] (device [M], clamped to [0, kv_tmax))
-  int kv_tmax;             // instead of kv_t: the rows of wca_greedy_decode_rows sit at different positions
+  int kv_tmax;             // instead of kv_t: the rows of the per-row wca_decode sit at different positions
 };
 // Forced kernel choices: tests and tools pack the value into bits 8-19 of the out_mode they hand to wca_test_gemm*
 enum GemmForceTile {
@@ -158,7 +158,7 @@ hipError_t launch_fill_f16(half_t* p, size_t n, float v, hipStream_t s);
 
 // ---------------------------------------------------------------- greedy ASR decode steps (decode.hip)
 // Where the rows of a decode step are: every row at position t (rows == nullptr), or row b at rows[b] (device [B], clamped to the slots the launch
-// addresses; wca_greedy_decode_rows). Host side only: each launcher picks the scalar or the table form of its kernel and runs that form's checks.
+// addresses; the per-row wca_decode). Host side only: each launcher picks the scalar or the table form of its kernel and runs that form's checks.
 // The engine reads rows (and AttnArgs.nk_rows, DecodeSelectArgs.cur_len_rows) from per-step tables it builds once per call on the host
 // instead of adding a scalar step to row_pos[b] in every kernel: a row past its sample budget stays in the batch at a CLAMPED position
 // (<= T_max - 2: no positional row past n_text_ctx - 1, no cache slot past T_max - 1), the attention needs a plain count array anyway, and

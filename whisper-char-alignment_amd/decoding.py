@@ -1,5 +1,5 @@
 """Greedy ASR pre-pass: `whisper.decode(model, mel, options)` as the reference calls it (infer_ali.py:40,60-61,
-probe_oracle.py:37,59-60, README.md:107-108) on the MI355X engine (C ABI wca_greedy_decode).
+probe_oracle.py:37,59-60, README.md:107-108) on the MI355X engine (C ABI wca_decode).
 
 Upstream openai-whisper `decoding.py` is an absent third-party dependency; its published algorithm is restated here
 (host side: which tokens the filters suppress) and in csrc/decode.hip (the per-step filters and GreedyDecoder.update).
@@ -8,10 +8,10 @@ the encoded state stays for the decode that follows, so detecting and decoding a
 decode in a given language (DecodingOptions(language=None) is refused: call detect_language first, or transcribe(language="auto")),
 temperature 0 without beam search (greedy), and conditioning on a prompt and / or
 a prefix (DecodingOptions(prompt=...), the decoder side of transcribe(initial_prompt=...); prefix=...), whose initial tokens
-go through the decoder in one batched forward (wca_greedy_decode_ex, prefill); a list of options gives every batch row a
-prompt / prefix of its own (wca_greedy_decode_rows). Temperature sampling is opt-in through the engine-specific
+go through the decoder in one batched forward (wca_decode, prefill); a list of options gives every batch row a
+prompt / prefix of its own (wca_decode with per_row 1). Temperature sampling is opt-in through the engine-specific
 DecodingOptions(seed=<int>): with a seed, temperature > 0 draws every token from softmax(filtered logits / temperature), as
-upstream's GreedyDecoder.update does, and avg_logprob sums the untempered log-probabilities (wca_decode_rows_sampled; the rows of
+upstream's GreedyDecoder.update does, and avg_logprob sums the untempered log-probabilities (wca_decode with temperature_host / seed_host; the rows of
 a list may differ in temperature and seed as well). The draw is Gumbel-max over Philox4x32-10 noise in the decode step's kernel
 (csrc/decode.hip): the law is upstream's, the draws are not torch's, because the generator differs; it is pinned token for token
 against a float64 restatement (tests/decode_sample_ref.py). With seed=None a temperature other than 0 raises as it always did,
@@ -90,7 +90,7 @@ def suppress_token_ids(tokenizer, options):
 
 
 def filter_masks(tokenizer, options, n_vocab):
-    """(suppress_mask, blank_mask) byte arrays [n_vocab] for wca_greedy_decode."""
+    """(suppress_mask, blank_mask) byte arrays [n_vocab] for wca_decode."""
     sup = np.zeros(n_vocab, dtype=np.uint8)
     if options.suppress_tokens:
         ids = [t for t in suppress_token_ids(tokenizer, options) if t < n_vocab]
@@ -188,9 +188,9 @@ def decode(model, mel, options=DecodingOptions(), pcm=None, n_samples=None, enco
     model.encode_batch). Returns DecodingResult or a list of them. want_text=False (transcribe without a vocabulary file) leaves
     `text` empty instead of decoding the token ids, which only the BPE vocabulary can do.
     options may also be a list with one DecodingOptions per batch row; the rows may differ in prompt / prefix / temperature / seed only
-    (ValueError otherwise): they then sit at different decoder positions (wca_greedy_decode_rows) and the result is always a list.
+    (ValueError otherwise): they then sit at different decoder positions (wca_decode with per_row 1) and the result is always a list.
     Sampling is opt-in through DecodingOptions(seed=<int>): temperature > 0 then draws every token from softmax(filtered logits /
-    temperature) as upstream's GreedyDecoder does, avg_logprob from the untempered log-probabilities (wca_decode_rows_sampled: Gumbel-max
+    temperature) as upstream's GreedyDecoder does, avg_logprob from the untempered log-probabilities (wca_decode with temperature_host / seed_host: Gumbel-max
     over Philox noise -- upstream's law, not torch's draws). One DecodingOptions over B rows gives row b the seed (seed + b) mod 2^64; a
     list gives every row its own. A row at temperature 0 is decoded greedily whatever its seed, and a call whose rows are all at
     temperature 0 is exactly the greedy engine call.

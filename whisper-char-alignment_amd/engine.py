@@ -136,7 +136,12 @@ def default_engine(device_index=0, need_weights=False):
 
 
 def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    """The address of a torch tensor, a numpy array or a ctypes array as a c_void_p; None is the null pointer."""
+    if t is None:
+        return C.c_void_p(0)
+    if hasattr(t, "data_ptr"):
+        return C.c_void_p(t.data_ptr())
+    return C.c_void_p(t.ctypes.data if hasattr(t, "ctypes") else C.addressof(t))
 
 
 class WhisperAMD:
@@ -437,9 +442,9 @@ class WhisperAMD:
     def align_batch(self, pcm, n_samples, tokens, n_tok, max_frames, opts, enqueue_only=False, token_logprobs_vocab_end=None, open_end=None):
         """Fused pipeline. pcm [B,stride] f32 cuda, tokens [B,n_max] int64 cuda. Returns (jump_frames [B,n_max] int32, sel [B,topk]).
         token_logprobs_vocab_end (tokenizer.eot): the teacher tokens' log-probabilities are computed on the GPU as well
-        (wca_align_batch_enqueue_ex) and returned as a third value [B,n_max] f32 (row b: n_tok[b] - sot_len - 2 entries, then 0);
+        (wca_align_desc.vocab_end) and returned as a third value [B,n_max] f32 (row b: n_tok[b] - sot_len - 2 entries, then 0);
         after enqueue_only=True, fetch them with fetch(..., with_token_logprobs=True).
-        open_end (B bools): row b's DTW is open-ended where open_end[b] (wca_align_batch_enqueue_open: the path ends in the last frame at
+        open_end (B bools): row b's DTW is open-ended where open_end[b] (wca_align_desc.open_end_host: the path ends in the last frame at
         the text row that fits best; a row with False gets exactly the closed result). The end rows [B] int32 and the scores [B] f32 are
         returned as two further values, after the log-probs where those are asked for; rows past a row's end row have jump frame -1.
         After enqueue_only=True, fetch them with fetch(..., with_end_rows=True). None: nothing changes."""
@@ -448,15 +453,13 @@ class WhisperAMD:
             raise ValueError("open_end lists %d flags for %d rows" % (len(open_end), B))
         self._bind_stream()
         # pcm=None re-uses the encoder state left by the preceding greedy_decode of the same batch
-        args = (self._h, _ptr(pcm) if pcm is not None else None, pcm.shape[1] if pcm is not None else 0,
-                _lib.i32_array(n_samples) if n_samples is not None else None, _ptr(tokens), n_max, _lib.i32_array(n_tok),
-                _lib.i32_array(max_frames), B, C.byref(opts))
-        if open_end is not None:
-            _lib.check(self._lib.wca_align_batch_enqueue_open(*args, int(token_logprobs_vocab_end or 0), _lib.i32_array([bool(v) for v in open_end])))
-        elif token_logprobs_vocab_end is None:
-            _lib.check(self._lib.wca_align_batch_enqueue(*args))
-        else:
-            _lib.check(self._lib.wca_align_batch_enqueue_ex(*args, int(token_logprobs_vocab_end)))
+        ns = _lib.i32_array(n_samples) if n_samples is not None else None
+        nt, mf = _lib.i32_array(n_tok), _lib.i32_array(max_frames)
+        oe = _lib.i32_array([bool(v) for v in open_end]) if open_end is not None else None
+        d = _lib.AlignDesc(pcm_dev=_ptr(pcm), n_samples_host=_ptr(ns), tokens_dev=_ptr(tokens), n_tok_host=_ptr(nt), max_frames_host=_ptr(mf),
+                           opts=C.pointer(opts), open_end_host=_ptr(oe), pcm_stride=pcm.shape[1] if pcm is not None else 0, n_tok_max=n_max,
+                           batch=B, vocab_end=int(token_logprobs_vocab_end or 0))
+        _lib.check(self._lib.wca_align_batch_enqueue(self._h, C.byref(d)))
         if enqueue_only:
             return None
         return self.fetch(B, n_max, opts, with_token_logprobs=token_logprobs_vocab_end is not None, with_end_rows=open_end is not None)
@@ -477,9 +480,14 @@ class WhisperAMD:
         self._keep.append((mel, pcm))  # the kernels read these buffers asynchronously; up to two encodes are in flight
         return B
 
-    def _greedy_call(self, entry, opts, row_args, mel, pcm, n_samples, B, T, suppress_mask, blank_mask, no_speech, tail=()):
-        """What greedy_decode, greedy_decode_rows and decode_rows_sampled share: the masks, the output arrays, the mel / pcm / n_samples and
-        output pointer arguments around the entry point's own row arguments (and, behind them, its `tail`), and last_no_speech_prob."""
+    def _decode(self, mel, pcm, n_samples, batch, init, n_init, sot_index, sample_len, opts, suppress_mask, blank_mask, per_row, prefill,
+                temps=None, seeds=None, redecode=False):
+        """What greedy_decode, greedy_decode_rows and decode_rows_sampled share: the masks, the output arrays, the wca_decode_desc around
+        the caller's row arrays (init [n] or [B, n_max], n_init / sot_index / sample_len: one int or one per row), the call, and
+        last_no_speech_prob. Every array the descriptor points to is a local of this frame until the call has returned."""
+        self._bind_stream()
+        B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(batch))  # batch=: decode a state queued by encode_batch
+        T = max((int(n) + int(sl) for n, sl in zip(n_init, sample_len)), default=1)
         tokens = np.zeros((B, max(T, 1)), dtype=np.int32)
         n_tok = np.zeros(B, dtype=np.int32)
         lp = np.zeros(B, dtype=np.float32)
@@ -490,52 +498,46 @@ class WhisperAMD:
         nsp = np.full(B, np.nan, dtype=np.float32)
         if mel is not None:
             mel = mel.contiguous().float()
-        _lib.check(entry(
-            self._h, _ptr(mel) if mel is not None else None, _ptr(pcm) if pcm is not None else None,
-            pcm.shape[1] if pcm is not None else 0, _lib.i32_array(n_samples) if n_samples is not None else None, B, *row_args,
-            sup.ctypes.data_as(C.c_void_p), blank.ctypes.data_as(C.c_void_p) if blank is not None else None, C.byref(opts),
-            tokens.ctypes.data_as(_lib._pi32), n_tok.ctypes.data_as(_lib._pi32), lp.ctypes.data_as(_lib._pf),
-            nsp.ctypes.data_as(_lib._pf) if no_speech >= 0 else None, *tail))
+        ns = _lib.i32_array(n_samples) if n_samples is not None else None
+        ni, si, sl = _lib.i32_array(n_init), _lib.i32_array(sot_index), _lib.i32_array(sample_len)
+        d = _lib.DecodeDesc(mel_dev=_ptr(mel), pcm_dev=_ptr(pcm), n_samples_host=_ptr(ns), initial_tokens_host=_ptr(init), n_initial_host=_ptr(ni),
+                            sot_index_host=_ptr(si), sample_len_host=_ptr(sl), temperature_host=_ptr(temps), seed_host=_ptr(seeds),
+                            suppress_mask_host=_ptr(sup), blank_mask_host=_ptr(blank), opts=C.pointer(opts), tokens_out_host=_ptr(tokens),
+                            n_tokens_host=_ptr(n_tok), sum_logprob_host=_ptr(lp), no_speech_prob_host=_ptr(nsp if opts.no_speech >= 0 else None),
+                            pcm_stride=pcm.shape[1] if pcm is not None else 0, batch=B, per_row=per_row, prefill=int(prefill),
+                            redecode=1 if redecode else 0)
+        _lib.check(self._lib.wca_decode(self._h, C.byref(d)))
         self.last_no_speech_prob = nsp
         return tokens, n_tok, lp
 
     def greedy_decode(self, mel, pcm, n_samples, initial_tokens, suppress_mask, blank_mask, sample_len, eot, timestamp_begin,
                       apply_timestamp_rules=True, max_initial_timestamp_index=50, batch=None, no_speech=-1, sot_index=0, prefill=0):
-        """C ABI wca_greedy_decode. mel [B,n_mels,3000] f32 cuda XOR pcm [B,stride] f32 cuda (+ n_samples).
+        """C ABI wca_decode with one row description for every row. mel [B,n_mels,3000] f32 cuda XOR pcm [B,stride] f32 cuda (+ n_samples).
         Returns (tokens [B, n_initial+sample_len] int32, n_tokens [B] int32, sum_logprobs [B] f32) as numpy arrays; the
         encoder state stays in the engine for a following align_batch(pcm=None, ...). With no_speech >= 0 (the
         <|nospeech|> token id) self.last_no_speech_prob [B] holds DecodingResult.no_speech_prob.
-        sot_index (position of <|sot|> in initial_tokens: no_speech_prob is read there) and prefill (1: one batched forward
-        over the initial tokens instead of one decode step per position) select wca_greedy_decode_ex, which also allows
-        n_initial + sample_len = n_text_ctx + 1; the defaults make today's wca_greedy_decode call."""
-        self._bind_stream()
-        B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(batch))  # batch=: decode a state queued by encode_batch
-        n_init = len(initial_tokens)
-        T = n_init + int(sample_len)
-        fields = (int(sample_len), int(eot), int(timestamp_begin), 1 if apply_timestamp_rules else 0, int(max_initial_timestamp_index),
-                  int(no_speech))
-        if sot_index == 0 and prefill == 0 and T <= self.dims.n_text_ctx:
-            opts, entry = _lib.DecodeOpts(*fields), self._lib.wca_greedy_decode
-        else:
-            opts, entry = _lib.DecodeOptsEx(*fields, int(sot_index), int(prefill)), self._lib.wca_greedy_decode_ex
-        return self._greedy_call(entry, opts, (_lib.i32_array(initial_tokens), n_init), mel, pcm, n_samples, B, T, suppress_mask, blank_mask,
-                                 no_speech)
+        sot_index: position of <|sot|> in initial_tokens (no_speech_prob is read there); prefill=1: one batched forward
+        over the initial tokens instead of one decode step per position. n_initial + sample_len may reach n_text_ctx + 1."""
+        opts = _lib.DecodeOpts(int(sample_len), int(eot), int(timestamp_begin), 1 if apply_timestamp_rules else 0, int(max_initial_timestamp_index),
+                               int(no_speech))
+        return self._decode(mel, pcm, n_samples, batch, _lib.i32_array(initial_tokens), [len(initial_tokens)], [sot_index], [sample_len], opts,
+                            suppress_mask, blank_mask, 0, prefill)
 
     def greedy_decode_rows(self, mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask, blank_mask, eot, timestamp_begin,
                            apply_timestamp_rules=True, max_initial_timestamp_index=50, batch=None, no_speech=-1):
-        """C ABI wca_greedy_decode_rows: greedy_decode with initial tokens, <|sot|> position and sample budget PER ROW (initial_tokens: one
+        """C ABI wca_decode with per_row = 1: greedy_decode with initial tokens, <|sot|> position and sample budget PER ROW (initial_tokens: one
         token list per row, of any lengths; sot_index, sample_len: one int per row). Returns (tokens [B, T_max] int32 with
         T_max = max_b(len(initial_tokens[b]) + sample_len[b]), row b left-aligned; n_tokens [B]: row b's sampled tokens are
         tokens[b, len(initial_tokens[b]) : n_tokens[b]]; sum_logprobs [B]); self.last_no_speech_prob as greedy_decode. The initial
         tokens always go through the batched prefill; the encoder state stays for a following align_batch(pcm=None, ...)."""
-        return self._decode_rows(self._lib.wca_greedy_decode_rows, (), mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask,
-                                 blank_mask, eot, timestamp_begin, apply_timestamp_rules, max_initial_timestamp_index, batch, no_speech)
+        return self._decode_rows(mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask, blank_mask, eot, timestamp_begin,
+                                 apply_timestamp_rules, max_initial_timestamp_index, batch, no_speech)
 
     def decode_rows_sampled(self, mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask, blank_mask, eot, timestamp_begin,
                             apply_timestamp_rules=True, max_initial_timestamp_index=50, batch=None, no_speech=-1, temperature=None, seed=None,
                             redecode=False):
-        """C ABI wca_decode_rows_sampled: greedy_decode_rows with a temperature (float >= 0) and a seed (int, taken mod 2^64) PER ROW. A row
-        at temperature 0 is decoded greedily, bit for bit as greedy_decode_rows decodes it; a row at T > 0 draws each token from
+        """greedy_decode_rows with a temperature (float >= 0) and a seed (int, taken mod 2^64) PER ROW (wca_decode_desc.temperature_host /
+        seed_host). A row at temperature 0 is decoded greedily, bit for bit as greedy_decode_rows decodes it; a row at T > 0 draws each token from
         softmax(filtered logits / T) by Gumbel-max with Philox noise keyed by its seed and counted by its sampled tokens, so a row's draws
         do not depend on where in the batch it sits. sum_logprobs accumulates the untempered log-probability, as upstream does.
         redecode=True (mel = pcm = None, batch=B): decode again the state the previous decode of these B rows left for
@@ -545,15 +547,12 @@ class WhisperAMD:
             raise ValueError("temperature and seed take one entry per batch row (%d)" % B)
         temps = np.ascontiguousarray([float(t) for t in temperature], dtype=np.float32)
         seeds = np.ascontiguousarray([int(v) % (1 << 64) for v in seed], dtype=np.uint64)
-        tail = (temps.ctypes.data_as(_lib._pf), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), 1 if redecode else 0)
-        return self._decode_rows(self._lib.wca_decode_rows_sampled, tail, mel, pcm, n_samples, initial_tokens, sot_index, sample_len,
-                                 suppress_mask, blank_mask, eot, timestamp_begin, apply_timestamp_rules, max_initial_timestamp_index, batch,
-                                 no_speech)
+        return self._decode_rows(mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask, blank_mask, eot, timestamp_begin,
+                                 apply_timestamp_rules, max_initial_timestamp_index, batch, no_speech, temps, seeds, redecode)
 
-    def _decode_rows(self, entry, tail, mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask, blank_mask, eot,
-                     timestamp_begin, apply_timestamp_rules, max_initial_timestamp_index, batch, no_speech):
-        """The per-row tables that greedy_decode_rows and decode_rows_sampled pass."""
-        self._bind_stream()
+    def _decode_rows(self, mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask, blank_mask, eot, timestamp_begin,
+                     apply_timestamp_rules, max_initial_timestamp_index, batch, no_speech, temps=None, seeds=None, redecode=False):
+        """The per-row arrays that greedy_decode_rows and decode_rows_sampled pass."""
         B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(batch))
         rows = [[int(t) for t in r] for r in initial_tokens]
         if not (len(rows) == len(sot_index) == len(sample_len) == B):
@@ -563,11 +562,10 @@ class WhisperAMD:
         init = np.full((B, max(n_max, 1)), int(eot), dtype=np.int32)
         for b, r in enumerate(rows):
             init[b, :len(r)] = r
-        T = max((n + int(sl) for n, sl in zip(n_init, sample_len)), default=1)
         opts = _lib.DecodeOpts(max(int(v) for v in sample_len) if B else 0, int(eot), int(timestamp_begin), 1 if apply_timestamp_rules else 0,
                                int(max_initial_timestamp_index), int(no_speech))
-        row_args = (init.ctypes.data_as(_lib._pi32), _lib.i32_array(n_init), _lib.i32_array(sot_index), _lib.i32_array(sample_len))
-        return self._greedy_call(entry, opts, row_args, mel, pcm, n_samples, B, T, suppress_mask, blank_mask, no_speech, tail)
+        return self._decode(mel, pcm, n_samples, batch, init, n_init, sot_index, sample_len, opts, suppress_mask, blank_mask, 1, 1, temps, seeds,
+                            redecode)
 
     def detect_language(self, mel=None, tokenizer=None, *, pcm=None, n_samples=None, batch=None, sot=None, lang_begin=None, n_lang=None):
         """model.detect_language(mel, tokenizer) -> (language_tokens, language_probs), upstream's schema (decoding.detect_language).
@@ -618,21 +616,11 @@ class WhisperAMD:
         k = opts.topk if opts.aggregation == _lib.AGGR_TOPK else 0
         jump = np.zeros((B, n_max), dtype=np.int32)
         sel = np.zeros((B, max(k, 1)), dtype=np.int32)
-        if with_end_rows:
-            lp = np.zeros((B, n_max), dtype=np.float32) if with_token_logprobs else None
-            end_rows, scores = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.float32)
-            _lib.check(self._lib.wca_align_batch_fetch_open(self._h, B, n_max, k, jump.ctypes.data_as(_lib._pi32), sel.ctypes.data_as(_lib._pi32),
-                                                            lp.ctypes.data_as(_lib._pf) if lp is not None else None,
-                                                            end_rows.ctypes.data_as(_lib._pi32), scores.ctypes.data_as(_lib._pf)))
-            return (jump, (sel if k > 0 else None)) + ((lp,) if lp is not None else ()) + (end_rows, scores)
-        if not with_token_logprobs:
-            _lib.check(self._lib.wca_align_batch_fetch(self._h, B, n_max, k, jump.ctypes.data_as(_lib._pi32),
-                                                       sel.ctypes.data_as(_lib._pi32)))
-            return jump, (sel if k > 0 else None)
-        lp = np.zeros((B, n_max), dtype=np.float32)
-        _lib.check(self._lib.wca_align_batch_fetch_ex(self._h, B, n_max, k, jump.ctypes.data_as(_lib._pi32),
-                                                      sel.ctypes.data_as(_lib._pi32), lp.ctypes.data_as(_lib._pf)))
-        return jump, (sel if k > 0 else None), lp
+        lp = np.zeros((B, n_max), dtype=np.float32) if with_token_logprobs else None
+        end_rows, scores = (np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.float32)) if with_end_rows else (None, None)
+        r = _lib.AlignResult(_ptr(jump), _ptr(sel), _ptr(lp), _ptr(end_rows), _ptr(scores))
+        _lib.check(self._lib.wca_align_batch_fetch(self._h, B, n_max, k, C.byref(r)))
+        return (jump, (sel if k > 0 else None)) + ((lp,) if with_token_logprobs else ()) + ((end_rows, scores) if with_end_rows else ())
 
     def set_profiling(self, on):
         _lib.check(self._lib.wca_set_profiling(self._h, 1 if on else 0))

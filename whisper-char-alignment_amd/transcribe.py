@@ -10,7 +10,7 @@ What runs where: audio that is not at 16 kHz (a 44.1 / 48 kHz file, 8 kHz teleph
 on the GPU first (wca_resample_16k: torchaudio.functional.resample's default filter on the mean over the channels; upstream's load_audio
 leaves this to ffmpeg), then the log-mel of the WHOLE recording once (wca_log_mel_long: one `max - 8` floor over the recording), the
 window cut pad_or_trim(mel[:, seek:seek+size], 3000) with zeros in the mel domain (wca_mel_window), greedy decode of each
-window with the previous text as the prompt (wca_greedy_decode_ex), and -- with word_timestamps=True -- the fused alignment
+window with the previous text as the prompt (wca_decode), and -- with word_timestamps=True -- the fused alignment
 on the encoder state that decode left in the engine (align_batch(pcm=None): no second encoder pass). The loop itself
 (`seek_loop`) is host Python over two callables, so it runs without a GPU against a scripted decoder.
 
@@ -20,7 +20,7 @@ Limits (part of the contract):
     construction and picks no seed for the caller. With a seed, temperature may be upstream's (0.0, 0.2, 0.4, 0.6, 0.8, 1.0) or any
     number or non-empty tuple: a window whose result has compression_ratio > compression_ratio_threshold (2.4) or avg_logprob <
     logprob_threshold (-1), and is not taken for silence, is decoded again at the next temperature, on the encoder state its first
-    decode left in the engine (wca_decode_rows_sampled, redecode: a rung costs decoder positions only, where upstream encodes the window
+    decode left in the engine (wca_decode with temperature_host / seed_host, redecode: a rung costs decoder positions only, where upstream encodes the window
     again); the last rung is accepted whatever it gives, and a window accepted above 0.5 does not condition the next one. Without a
     vocabulary the compression ratio is NaN and only the log-probability test can fire. What is pinned: the sampler against a float64
     restatement, token for token (tests/test_decode_sample_gpu.py), and the ladder's mechanics (tests/test_transcribe_ladder.py). What is
@@ -39,7 +39,7 @@ Limits (part of the contract):
     (NotImplementedError), as in decode: say "auto". PARITY UNPINNED against upstream, like decode.
   * transcribe() takes one recording, window after window (window k+1 starts where window k ended). transcribe_batch() takes
     several and runs them in lock-step: every round decodes the next window of every unfinished recording in ONE batch
-    (wca_greedy_decode_rows: every row carries its own previous text as the prompt, so the rows sit at different decoder
+    (wca_decode with per_row 1: every row carries its own previous text as the prompt, so the rows sit at different decoder
     positions), the batch shrinks as recordings end, and with word_timestamps one align_batch(pcm=None) per round aligns the
     rows that have words. A recording's result is what transcribe() gives for it alone, up to argmax near-ties of the f16
     logits (the GEMM path, and with it the fp32 summation order, depends on the number of rows in the batch).
@@ -619,7 +619,7 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
                      compression_ratio_threshold=2.4, **decode_options):
     """transcribe() of several recordings in lock-step: a list with transcribe()'s result for every recording of `audios`, in order.
     Each round cuts the next window of every unfinished recording, decodes them in ONE batch with every row's own previous text as its
-    prompt (decoding.decode with one DecodingOptions per row: wca_greedy_decode_rows) and, with word_timestamps, aligns the rows that
+    prompt (decoding.decode with one DecodingOptions per row: wca_decode with per_row 1) and, with word_timestamps, aligns the rows that
     have words in one align_batch(pcm=None) on the state that decode left behind. The batch shrinks as recordings end; more recordings
     than model.max_batch are processed in groups of max_batch. The keyword arguments are transcribe()'s; sample_rate is one int for
     every array / tensor input or one per recording (a path carries its own rate);
