@@ -39,6 +39,9 @@
  *                          wca_decode_desc also DecodingOptions(prompt=..., prefix=...) (transcribe(initial_prompt=...)), rows with
  *                          prompts and sample budgets of their own (transcribe_batch), and upstream's GreedyDecoder at temperature > 0
  *                          (the rungs of transcribe's temperature fallback ladder)
+ *   wca_decode_group       upstream decoding.py BeamSearchDecoder / best_of + MaximumLikelihoodRanker (DecodingOptions(beam_size=..., patience=...,
+ *                          best_of=...), what upstream's command line decodes with by default; not called by the reference): wca_decode on
+ *                          n_group decoder rows per audio that share its cross-K/V, with the beam step and the cache reorder on the GPU
  *   wca_align_batch       infer_ali.py:93-101 + dataset.py:47-48: the whole per-utterance pipeline
  *                          (log-mel -> forward+capture -> medfilt/softmax -> scores/top-k ->
  *                          aggregate -> DTW) for a micro-batch of utterances, results = the frame
@@ -106,7 +109,7 @@ typedef struct {
 } wca_align_opts;
 
 const char* wca_last_error(void);
-int wca_version(void);   /* 17: one descriptor call each for decode (wca_decode, wca_decode_desc) and the fused alignment (wca_align_desc, wca_align_result) in place of the eleven entry points that had grown feature by feature; 16: the CU-partition and two-stream decode experiments are gone; 15: wca_quiet_cuts (where to cut one long recording into pieces decoded side by side); 14: the open-end DTW entry points; 13: wca_detect_language (the language head on the encoded state; the decode that follows re-uses the state); 12: wca_resample_plan, wca_resample_table, wca_resample_16k (any input rate to 16 kHz); 11: per-row prompts and sample budgets in the decode; 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: prompt / prefix in the decode (sot_index, batched prefill); 7: exactly two precision modes */
+int wca_version(void);   /* 18: wca_decode_group (beam search and best_of: G decoder rows per audio, a beam step and a cache reorder on the GPU); 17: one descriptor call each for decode (wca_decode, wca_decode_desc) and the fused alignment (wca_align_desc, wca_align_result) in place of the eleven entry points that had grown feature by feature; 16: the CU-partition and two-stream decode experiments are gone; 15: wca_quiet_cuts (where to cut one long recording into pieces decoded side by side); 14: the open-end DTW entry points; 13: wca_detect_language (the language head on the encoded state; the decode that follows re-uses the state); 12: wca_resample_plan, wca_resample_table, wca_resample_16k (any input rate to 16 kHz); 11: per-row prompts and sample budgets in the decode; 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: prompt / prefix in the decode (sot_index, batched prefill); 7: exactly two precision modes */
 
 /* ---- engine lifetime ------------------------------------------------------------------------ */
 /* A new engine is in the CONTRACT precision mode (WCA_PRECISION_REFERENCE: every stage on (hi, lo) operand pairs = the fp32 forward of
@@ -421,6 +424,43 @@ typedef struct {
                                           none. Nothing is dropped from the queue and the state is still there for the alignment.          */
 } wca_decode_desc;
 int wca_decode(wca_engine* e, const wca_decode_desc* d);
+
+/* Beam search and best_of: whisper.decode with DecodingOptions(beam_size=G [, patience]) at temperature 0, or with best_of=G at a
+ * temperature. `rows` describes the `batch` audios exactly as for wca_decode (always with prefill = 1; per_row and redecode as there); its
+ * four output pointers are not read and may be NULL. Every audio gets n_group decoder rows that share its cross-K/V, decoder row
+ * r = b * n_group + g being beam / sample g of audio b, so batch * n_group <= max_batch. The audios go through one prefill; each audio's
+ * cache rows and logits are then handed to its rows.
+ *
+ * mode 0, beam (upstream BeamSearchDecoder, restated; no temperatures): at every choice each live row offers the n_group + 1 most probable
+ * tokens of the log-softmax of its FILTERED logits (the filters of wca_decode; the lowest token first among equal logits). The candidates
+ * of an audio score sum_logprob[source] + logprob and are walked in the order (score descending, source beam ascending, token
+ * ascending): a candidate that ends in eot is newly finished, the others become the next beams, and the walk stops at the n_group-th of
+ * those. The newly finished ones join the audio's finished list, best first, while it holds fewer than max_candidates =
+ * round(beam_size * patience) (computed by the caller). At the first choice only beam 0 offers candidates (the rows are still identical:
+ * upstream's dedup of equal sequences, made deterministic). The self-attention cache rows follow the beams that continue them. The loop
+ * stops when every audio's list is full or its budget is used (asked every 4 choices). Then upstream's finalize: a list with fewer than
+ * n_group sequences is topped up from the live beams in descending order of sum_logprob (the lower beam among equals).
+ * Slots per audio: n_slot = max(n_group, max_candidates) -- with patience > 1 the list may hold more than n_group sequences, and the
+ * ranker sees all of them, as upstream's does.
+ *
+ * mode 1, independent samples (upstream's best_of; temperatures and seeds required): row (b, g) is wca_decode's sampling row at
+ * temperature[b] with the seed group_seed(seed[b], g) = seed[b] ^ (g * 0x94D049BB133111EB) mod 2^64, so sample 0 is the plain sampled
+ * decode of that seed. n_slot = n_group, slot g = sample g. Nothing selects across rows on the device: the ranking is the caller's.
+ *
+ * Refused with WCA_ERR_INVALID before any work is enqueued: what wca_decode refuses; a null engine, descriptor or required field;
+ * prefill 0; batch * n_group > max_batch; n_group outside [1, 16]; mode 0 with temperatures or max_candidates outside [1, 4096]; mode 1
+ * without temperatures. Synchronous. The encoded state stays for the alignment as after wca_decode. */
+typedef struct {
+  int32_t* tokens_out_host;    /* [batch][n_slot][T_max], T_max as wca_decode: a sequence's initial tokens, its sampled tokens, then eot */
+  int32_t* n_tokens_host;      /* [batch][n_slot]: index of the sequence's closing eot (its sampled tokens are [n_initial[b], n_tokens)) */
+  float* sum_logprob_host;     /* [batch][n_slot]                                                                                     */
+  int32_t* n_out_host;         /* [batch]: how many of the n_slot slots hold a sequence (the first n_out; the others hold eot and 0)    */
+  float* no_speech_prob_host;  /* [batch], nullable: as wca_decode, from the audios' <|sot|> rows                                       */
+  int32_t n_group;             /* G >= 1                                                                                              */
+  int32_t mode;                /* 0 = beam, 1 = independent samples                                                                   */
+  int32_t max_candidates;      /* mode 0: round(beam_size * patience) >= 1                                                            */
+} wca_group_desc;
+int wca_decode_group(wca_engine* e, const wca_decode_desc* rows, const wca_group_desc* g);
 /* Language identification, upstream's detect_language(model, mel): which of the language tokens [lang_begin, lang_begin + n_lang)
  * (tokenizer.all_language_tokens: sot + 1 ..., 99 or 100 of them; 1 <= n_lang <= 128) follows <|startoftranscript|> (`sot`) for each row.
  * mel_dev / pcm_dev / pcm_stride / n_samples_host / batch as for wca_decode: at most one input is non-NULL, with both NULL the oldest
@@ -574,6 +614,53 @@ int wca_test_last_scores(wca_engine* e, int batch, float* scores_host);
  * must be that call's (WCA_ERR_STATE otherwise, also after wca_detect_language, which overwrites the cache); more logits rows than the
  * call left are WCA_ERR_INVALID. */
 int wca_test_decode_state(wca_engine* e, int batch, int T_max, int logits_rows, float* logits_host, void* cache_f16_host);
+/* One beam step of wca_decode_group (mode 0) on caller-supplied logits and token rows: the per-row candidates, then the per-audio merge
+ * (kernel parity test, tests/beam_ref.py). R = batch * n_group decoder rows, all arrays on the device: logits [R][n_vocab] f32;
+ * tokens_in / tokens_out [R][T_max] int32, two buffers; cur_len / n_initial / cap [R] int32 (the rows of a group hold equal values; an
+ * audio with cur_len - n_initial >= cap is past its budget and copied through); sum_logprob [R] f32, updated in place; src [R] int32;
+ * cand_tok [R][n_group + 1] int32 and cand_lp likewise f32 (the candidates, token -1 at -inf where the filters leave fewer); the finished
+ * lists fin_n [batch], fin_len / fin_sum [batch][max_candidates], fin_tok [batch][max_candidates][T_max], appended to; trace [R][2] int32 =
+ * (source row, token); n_done [1] int32, incremented once per audio whose list is full after the step or that is past its budget.
+ * first != 0: only beam 0 of a group offers candidates. Asynchronous on the engine's stream. */
+typedef struct {
+  const float* logits_dev;
+  const int32_t* tokens_in_dev;
+  int32_t* tokens_out_dev;
+  const int32_t* cur_len_dev;
+  const int32_t* n_initial_dev;
+  const int32_t* cap_dev;
+  const uint8_t* suppress_mask_dev;
+  const uint8_t* blank_mask_dev;   /* nullable */
+  const wca_decode_opts* opts;
+  float* sum_logprob_dev;
+  int32_t* src_dev;
+  int32_t* cand_tok_dev;
+  float* cand_lp_dev;
+  int32_t* fin_n_dev;
+  int32_t* fin_len_dev;
+  float* fin_sum_dev;
+  int32_t* fin_tok_dev;
+  int32_t* trace_dev;
+  int32_t* n_done_dev;
+  int32_t batch;
+  int32_t n_group;
+  int32_t n_vocab;
+  int32_t T_max;
+  int32_t first;
+  int32_t max_candidates;
+} wca_test_beam_desc;
+int wca_test_beam_step(wca_engine* e, const wca_test_beam_desc* desc);
+/* The cache reorder of wca_decode_group alone: for every plane p < n_planes and row r < rows_dst,
+ * dst[p][r][0 : n_keep[r]] = src[p][s][0 : n_keep[r]] with s = src_idx_dev[r], or r / div where src_idx_dev is NULL (the broadcast of an
+ * audio's prefill to its group). src_dev [n_planes][rows_src][T_max][d] f16, dst_dev [n_planes][rows_dst][T_max][d] f16, two buffers;
+ * n_keep_dev [rows_dst] int32 (clamped to [0, T_max]); s is clamped to [0, rows_src); d % 8 == 0. Asynchronous on the engine's stream. */
+int wca_test_kv_reorder(wca_engine* e, const void* src_dev, void* dst_dev, int n_planes, int rows_src, int rows_dst, int T_max, int d,
+                        const int32_t* src_idx_dev, int div, const int32_t* n_keep_dev);
+/* What the LAST wca_decode_group in beam mode chose (reads only): trace_host [steps][rows][2] int32, entry (c, r) = (the row whose beam
+ * row r continues after choice c, the token it appended; -1 for a row past its budget). *steps_out / *rows_out (set first, so a call with
+ * trace_host = NULL asks for the sizes) = the choices made and batch * n_group; WCA_ERR_STATE if there was no such call, WCA_ERR_INVALID if
+ * cap_entries < steps * rows * 2. */
+int wca_test_beam_trace(wca_engine* e, int32_t* steps_out, int32_t* rows_out, int32_t* trace_host, int64_t cap_entries);
 /* q,k,v [B][n][H*64] f16 device -> o [B][nq][H*64] f16; cap_dev [B][H][nq][cap_ld] f32 or NULL.
  * causal: bit 0 = causal mask; bits 8-9 = kernel variant (0 auto, 1 the 16x16x32-MFMA kernel, 2 the 32x32x16-MFMA
  * kernel that serves the encoder's un-masked self-attention = what auto picks; 3 is WCA_ERR_INVALID) */

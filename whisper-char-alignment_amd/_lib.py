@@ -46,6 +46,21 @@ class DecodeDesc(C.Structure):
                 [("pcm_stride", C.c_int64)] + [(n, C.c_int32) for n in ("batch", "per_row", "prefill", "redecode")])
 
 
+class GroupDesc(C.Structure):
+    """wca_group_desc of include/wca.h"""
+    _fields_ = ([(n, C.c_void_p) for n in ("tokens_out_host", "n_tokens_host", "sum_logprob_host", "n_out_host", "no_speech_prob_host")] +
+                [(n, C.c_int32) for n in ("n_group", "mode", "max_candidates")])
+
+
+class BeamDesc(C.Structure):
+    """wca_test_beam_desc of include/wca.h"""
+    _fields_ = ([(n, C.c_void_p) for n in ("logits_dev", "tokens_in_dev", "tokens_out_dev", "cur_len_dev", "n_initial_dev", "cap_dev",
+                                           "suppress_mask_dev", "blank_mask_dev")] + [("opts", C.POINTER(DecodeOpts))] +
+                [(n, C.c_void_p) for n in ("sum_logprob_dev", "src_dev", "cand_tok_dev", "cand_lp_dev", "fin_n_dev", "fin_len_dev", "fin_sum_dev",
+                                           "fin_tok_dev", "trace_dev", "n_done_dev")] +
+                [(n, C.c_int32) for n in ("batch", "n_group", "n_vocab", "T_max", "first", "max_candidates")])
+
+
 class AlignDesc(C.Structure):
     """wca_align_desc of include/wca.h"""
     _fields_ = ([(n, C.c_void_p) for n in ("pcm_dev", "n_samples_host", "tokens_dev", "n_tok_host", "max_frames_host")] +
@@ -122,6 +137,10 @@ SIGNATURES = {
     "wca_token_logprobs": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "wca_encode_batch": (_i, [_vp, _vp, _vp, _i64, _pi32, _i]),
     "wca_decode": (_i, [_vp, C.POINTER(DecodeDesc)]),
+    "wca_decode_group": (_i, [_vp, C.POINTER(DecodeDesc), C.POINTER(GroupDesc)]),
+    "wca_test_beam_step": (_i, [_vp, C.POINTER(BeamDesc)]),
+    "wca_test_kv_reorder": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "wca_test_beam_trace": (_i, [_vp, _pi32, _pi32, _pi32, _i64]),
     "wca_test_decode_sample_rows": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(DecodeOpts), _vp, _vp, _vp, _vp]),
     "wca_detect_language": (_i, [_vp, _vp, _vp, _i64, _pi32, _i, _i, _i, _i, _pi32, _pf]),
     "wca_test_language_head": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -627,7 +627,10 @@ __global__ __launch_bounds__(256) void attn32_kernel(AttnArgs a) {
 // ROWS: batch row b has nk_rows[b] keys (the per-row wca_decode: the rows of a step sit at different positions); everything that
 // depends on the key count (the waves' key ranges, the dead-key clamp) is derived from the row's own count, so a row's result is that
 // of a uniform launch with nk = nk_rows[b]. The uniform launches take the ROWS = false instance.
-template <bool ROWS>
+// GROUP: K and V are indexed by b / kv_group (the beams of an audio share its cross-K/V); everything else, the key partition and the
+// summation order included, is the plain instance's, so a grouped row equals a plain row on the same K / V bit for bit. It is an instance
+// of its own so that the plain ones keep their code.
+template <bool ROWS, bool GROUP = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(AttnArgs a) {
   __shared__ float part[4][66];  // per wave: m, l, o[64]
   const int tid = threadIdx.x;
@@ -642,8 +645,9 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnArgs a) {
   float q[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) q[j] = (float)qh[j] * c_log2;  // scores directly in the log2 domain
-  const half_t* Kb = a.K + (long)b * a.k_bs + h * 64 + c * 8;
-  const half_t* Vb = a.V + (long)b * a.v_bs + h * 64 + c * 8;
+  const int bk = GROUP ? b / a.kv_group : b;
+  const half_t* Kb = a.K + (long)bk * a.k_bs + h * 64 + c * 8;
+  const half_t* Vb = a.V + (long)bk * a.v_bs + h * 64 + c * 8;
   const int nk = ROWS ? min(max(a.nk_rows[b], 1), a.nk) : a.nk;  // (a.nk: the rows the K / V planes hold)
   const int per_wave = ((nk + 3) / 4 + 7) & ~7;  // keys per wave, a multiple of the 8 keys of one step
   const int k_lo = wave * per_wave;
@@ -734,12 +738,15 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnArgs a) {
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
   // per-row key counts: the one-query kernel of a decode step only
   if (a.nk_rows != nullptr && (a.split || a.nq != 1 || a.causal || (a.cap != nullptr && a.cap_cols > 0))) return hipErrorInvalidValue;
+  // grouped K / V: the one-query kernel with uniform key counts only
+  if (a.kv_group > 1 && (a.split || a.nq != 1 || a.causal || a.nk_rows != nullptr || (a.cap != nullptr && a.cap_cols > 0))) return hipErrorInvalidValue;
   if (a.split) return launch_attention_split(a, s);  // reference-precision mode: hi/lo operand pairs, three MFMA passes
   if (a.nq <= 0 || a.B <= 0) return hipSuccess;
   if (!attn_args_ok(a)) return hipErrorInvalidValue;
   const bool cap = a.cap != nullptr && a.cap_cols > 0;
   if (a.nq == 1 && !cap && (!a.causal || a.nk == 1)) {  // greedy-decode steps: the KV cache holds exactly the causal prefix
-    if (a.nk_rows != nullptr) hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(a.H * a.B), dim3(256), 0, s, a);
+    if (a.kv_group > 1) hipLaunchKernelGGL((attn_decode_kernel<false, true>), dim3(a.H * a.B), dim3(256), 0, s, a);
+    else if (a.nk_rows != nullptr) hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(a.H * a.B), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(attn_decode_kernel<false>, dim3(a.H * a.B), dim3(256), 0, s, a);
     return hipGetLastError();
   }

@@ -12,8 +12,7 @@
 //                     fp32 logits (tests/test_decode_gpu.py). Its sampling form (GreedyDecoder.update at temperature > 0:
 //                     Gumbel-max over Philox4x32-10 noise, per-row temperature and seed) is tested token for token against a
 //                     float64 restatement (tests/test_decode_sample_gpu.py).
-#include "kernels.h"
-#include "wca_common.h"
+#include "decode_filter.h"
 
 namespace wca {
 
@@ -122,27 +121,6 @@ __global__ __launch_bounds__(256) void gather_rows_per_row_kernel(const float* _
   gather_row(x, out, (long)b * n + p, b, j, B, d);
 }
 
-__device__ __forceinline__ float block_max(float v, float* red) {
-  v = wave_max(v);
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int i = 1; i < nw; ++i) r = fmaxf(r, red[i]);
-  return r;
-}
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int i = 1; i < nw; ++i) r += red[i];
-  return r;
-}
-
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3"; the Random123 known answers are pinned in
 // tests/test_decode_sample_ref.py through the float64 restatement this kernel is tested against): counter c[4], key (k0, k1) -> c[4].
 __device__ __forceinline__ void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1) {
@@ -198,68 +176,13 @@ __global__ __launch_bounds__(1024) void decode_select_kernel(DecodeSelectArgs a)
   }
   const bool first = (cur_len == n_initial);
 
-  if (tid == 0) {
-    // ApplyTimestampRules bookkeeping over the sampled tokens tokens[n_initial : cur_len] (decoding.py, restated)
-    const int ns = cur_len - n_initial;
-    const int* seq = tok + n_initial;
-    const bool last = ns >= 1 && seq[ns - 1] >= a.timestamp_begin;
-    const bool pen = ns < 2 || seq[ns - 2] >= a.timestamp_begin;
-    int last_ts = -1;
-    for (int i = 0; i < ns; ++i)
-      if (seq[i] >= a.timestamp_begin) last_ts = seq[i];
-    hist[0] = last;
-    hist[1] = pen;
-    hist[2] = last_ts >= 0;
-    // timestamps must not decrease; they may repeat only when closing a segment
-    hist[3] = (last_ts >= 0) ? ((last && !pen) ? last_ts : last_ts + 1) : 0;
-  }
+  if (tid == 0) timestamp_history(tok + n_initial, cur_len - n_initial, a.timestamp_begin, hist);
   __syncthreads();
-  const bool last_ts = hist[0], pen_ts = hist[1], have_ts = hist[2];
-  const int ts_bound = hist[3];
-
-  auto dead = [&](int v) -> bool {
-    if (a.suppress_mask[v]) return true;  // SuppressTokens (+ <|notimestamps|> under the timestamp rules)
-    if (first && a.blank_mask != nullptr && a.blank_mask[v]) return true;  // SuppressBlank
-    if (a.apply_timestamp_rules) {
-      if (last_ts) {
-        if (pen_ts) {
-          if (v >= a.timestamp_begin) return true;  // has to be non-timestamp
-        } else {
-          if (v < a.eot) return true;  // cannot be normal text tokens
-        }
-      }
-      if (have_ts && v >= a.timestamp_begin && v < ts_bound) return true;
-      if (first) {
-        if (v < a.timestamp_begin) return true;  // must start with a timestamp
-        if (a.max_initial_timestamp_index >= 0 && v > a.timestamp_begin + a.max_initial_timestamp_index) return true;
-      }
-    }
-    return false;
-  };
-
-  // pass 1: maxima over the filtered logits (all / text part)
-  float m_all = -INFINITY, m_text = -INFINITY;
-  for (int v = tid; v < V; v += blockDim.x) {
-    if (dead(v)) continue;
-    const float x = lg[v];
-    m_all = fmaxf(m_all, x);
-    if (v < a.timestamp_begin) m_text = fmaxf(m_text, x);
-  }
-  m_all = block_max(m_all, red);
-  m_text = block_max(m_text, red);
-  // pass 2: partition sums relative to m_all
-  float s_text = 0.f, s_ts = 0.f;
-  for (int v = tid; v < V; v += blockDim.x) {
-    if (dead(v)) continue;
-    const float e = __expf(lg[v] - m_all);
-    if (v < a.timestamp_begin) s_text += e; else s_ts += e;
-  }
-  s_text = block_sum(s_text, red);
-  s_ts = block_sum(s_ts, red);
-  // "if sum of probability over timestamps is above any other token, sample timestamp":
-  // logsumexp(logprobs[ts:]) > max(logprobs[:ts])  <=>  log(s_ts) > m_text - m_all
-  bool text_dead = false;
-  if (a.apply_timestamp_rules && s_ts > 0.f && logf(s_ts) > m_text - m_all) text_dead = true;
+  const RowFilter filt(a, first, hist);
+  auto dead = [&](int v) -> bool { return filt.dead(v); };
+  float m_all, s_final;
+  bool text_dead;
+  filtered_softmax_stats(lg, V, filt, red, &m_all, &s_final, &text_dead);
   // pass 3: argmax (lowest index among equals) of the final filtered logits
   float best = -INFINITY;
   int best_i = 0x7fffffff;
@@ -321,7 +244,6 @@ __global__ __launch_bounds__(1024) void decode_select_kernel(DecodeSelectArgs a)
   }
   if (tid == 0) {
     const int prev = tok[cur_len - 1];
-    const float s_final = text_dead ? s_ts : s_text + s_ts;
     // a draw reduced on the perturbed score: the token's own logit (nothing survived the filters: -inf, as the greedy `best`)
     if (SAMPLE && temperature > 0.f) best = best_i == 0x7fffffff ? -INFINITY : lg[best_i];
     const float logprob = (best - m_all) - logf(s_final);  // log_softmax of the filtered logits at the chosen token

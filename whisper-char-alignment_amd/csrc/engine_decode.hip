@@ -21,12 +21,13 @@ struct DecodeRows {
 
 // What every decode is refused for, before any work is enqueued: the engine's state, the exclusive mel / pcm inputs, null pointers, the batch
 // range, each row's lengths and <|sot|> position, eot / timestamp_begin, the initial tokens. Sets r's sizes.
-int decode_check(wca_engine* e, const wca_decode_desc* d, DecodeRows* r) {
+// need_out: the descriptor's own output arrays are required (wca_decode_group writes its group descriptor's instead).
+int decode_check(wca_engine* e, const wca_decode_desc* d, DecodeRows* r, bool need_out = true) {
   const float *mel_dev = d->mel_dev, *pcm_dev = d->pcm_dev;
   const int32_t* n_samples_host = d->n_samples_host;
   const wca_decode_opts* o = d->opts;
   const bool any_null = !d->initial_tokens_host || !d->n_initial_host || !d->sot_index_host || !d->sample_len_host || !d->suppress_mask_host ||
-                        !o || !d->tokens_out_host || !d->n_tokens_host;
+                        !o || (need_out && (!d->tokens_out_host || !d->n_tokens_host));
   const int rc = check_ready(e);
   if (rc) return rc;
   if (mel_dev != nullptr && pcm_dev != nullptr) return fail(WCA_ERR_INVALID, "pass at most one of mel_dev / pcm_dev");
@@ -178,6 +179,7 @@ int decode_begin(wca_engine* e, const wca_decode_desc* d, const DecodeRows& r, i
   WCA_TRY(decode_take_state(e, d->mel_dev, d->pcm_dev, d->pcm_stride, d->n_samples_host, batch, &lp.st, d->redecode == 1));
   lp.kvbuf = lp.st->slot ? e->kv_alt : e->kv;
   hipStream_t s2 = lp.s2 = e->stream2;
+  e->dec_cache_off = 0;
   HIPCHK(e->dec_cache.ensure(sizeof(half_t) * (size_t)L * 2 * batch * T_max * dt));
   HIPCHK(e->dec_tokens.ensure(sizeof(int) * (size_t)batch * T_max));
   HIPCHK(e->dec_masks.ensure((size_t)2 * V));
@@ -339,6 +341,246 @@ int decode_per_row(wca_engine* e, const wca_decode_desc* d, const DecodeRows& r)
   return decode_run(lp, pl, r, d);
 }
 
+// The Philox seed of sample g of a row whose seed is s (include/wca.h): g = 0 keeps s.
+inline uint64_t group_seed(uint64_t s, int g) { return s ^ ((uint64_t)g * 0x94D049BB133111EBull); }
+
+// wca_decode_group: G decoder rows per audio, row b * G + g = beam or sample g of audio b. The B audios go through today's prefill; each
+// audio's cache rows and logits are then handed to its G rows, and the step loop is decode_per_row's on R = B G rows whose cross-attention
+// reads the audio's K/V (run_decode_step, kv_group). The rows of a group hold their audio's initial tokens, positions and budget.
+//   mode 0 (beam): each choice is beam_topk + beam_merge between two token buffers, and from the second choice on the cache rows follow
+//     their beams into the other half of dec_cache (kv_reorder; at the first choice every beam continues beam 0, whose cache all G rows
+//     already hold). The loop stops when every audio's finished list holds max_candidates sequences or is past its budget. Upstream's
+//     finalize runs on the host: a list shorter than G is topped up from the live beams, which the merge leaves in descending order of
+//     sum_logprob.
+//   mode 1 (samples): decode_select's sampling form on the R rows, row (b, g) drawing with group_seed(seed[b], g); nothing is reordered.
+int decode_group(wca_engine* e, const wca_decode_desc* d, const wca_group_desc* gd, const DecodeRows& r) {
+  const wca_decode_opts* o = d->opts;
+  const wca_model_dims& D = e->dims;
+  const int B = r.batch, G = gd->n_group, R = B * G, T_max = r.T_max, S = r.S, K = G + 1;
+  const int V = D.n_vocab, dt = D.n_text_state, L = D.n_text_layer;
+  const bool beam = gd->mode == 0;
+  const int MC = beam ? gd->max_candidates : 1, n_slot = beam ? std::max(G, MC) : G;
+  // the int tables of decode_per_row on R rows; behind them the prefill's [B] last initial positions and [B] <|sot|> positions; sampling:
+  // behind those (8-byte aligned) the rows' seeds [R] uint64 and temperatures [R] f32
+  const size_t n_int = (size_t)(4 + 3 * S) * R, pre_at = n_int, seed_at = (pre_at + 2 * (size_t)B + 1) & ~(size_t)1, temp_at = seed_at + 2 * (size_t)R;
+  std::vector<int32_t> tab(beam ? pre_at + 2 * (size_t)B : temp_at + R);
+  for (int row = 0; row < R; ++row) {
+    const int b = row / G, ni = r.ni(b);
+    tab[0 * (size_t)R + row] = ni - 1;
+    tab[1 * (size_t)R + row] = r.sot_index[b * r.each];
+    tab[2 * (size_t)R + row] = ni;
+    tab[3 * (size_t)R + row] = r.sl(b);
+    for (int c = 0; c < S; ++c) {
+      const int pos = std::max(0, std::min(ni + c - 1, T_max - 2));
+      tab[(size_t)(4 + 3 * c + 0) * R + row] = pos;
+      tab[(size_t)(4 + 3 * c + 1) * R + row] = pos + 1;
+      tab[(size_t)(4 + 3 * c + 2) * R + row] = ni + c;
+    }
+    if (!beam) {
+      const uint64_t seed = group_seed(d->seed_host[b], row - b * G);
+      memcpy(tab.data() + seed_at + 2 * (size_t)row, &seed, sizeof(seed));
+      memcpy(tab.data() + temp_at + row, d->temperature_host + b, sizeof(float));
+    }
+  }
+  for (int b = 0; b < B; ++b) {
+    tab[pre_at + b] = r.ni(b) - 1;
+    tab[pre_at + B + b] = r.sot_index[b * r.each];
+  }
+  // token rows: two buffers [R][T_max] (the beam step gathers from one into the other), then the prefill's [B][T_max]
+  std::vector<int32_t> init((size_t)(2 * R + B) * T_max, o->eot);
+  for (int row = 0; row < 2 * R + B; ++row) {
+    const int b = row < 2 * R ? (row % R) / G : row - 2 * R;
+    std::copy(r.init(b), r.init(b) + r.ni(b), init.begin() + (size_t)row * T_max);
+  }
+
+  wca_engine::EncState* st = nullptr;
+  WCA_TRY(decode_take_state(e, d->mel_dev, d->pcm_dev, d->pcm_stride, d->n_samples_host, B, &st, d->redecode == 1));
+  const half_t* kvbuf = st->slot ? e->kv_alt : e->kv;
+  hipStream_t s2 = e->stream2;
+  const size_t half_elems = (size_t)L * 2 * R * T_max * dt;   // one of the two caches
+  const bool want_nsp = gd->no_speech_prob_host && o->no_speech >= 0 && o->no_speech < V;
+  e->dec_cache_off = 0;
+  e->dec_batch = e->dec_T_max = e->dec_logits_rows = 0;
+  e->grp_steps = e->grp_rows = 0;
+  HIPCHK(e->dec_cache.ensure(sizeof(half_t) * 2 * half_elems));
+  HIPCHK(e->dec_tokens.ensure(sizeof(int) * init.size()));
+  HIPCHK(e->dec_masks.ensure((size_t)2 * V));
+  HIPCHK(e->dec_logits.ensure(sizeof(float) * (size_t)std::max(R, 2 * B) * V));
+  const size_t state_bytes = sizeof(float) * (R + B) + sizeof(int) * (size_t)S;
+  HIPCHK(e->dec_state.ensure(state_bytes));
+  HIPCHK(e->dec_gather.ensure(sizeof(float) * 2 * (size_t)B * dt));
+  HIPCHK(e->dec_rows.ensure(sizeof(int) * tab.size()));
+  // the beam step's arrays, 4-byte entries: candidates [R][K] tokens and log-probabilities, sources [R], the finished lists (counts [B],
+  // lengths and sums [B][MC], token rows [B][MC][T_max]), the trace [S][R][2]
+  const size_t cand_at = 0, lp_at = cand_at + (size_t)R * K, src_at = lp_at + (size_t)R * K, finn_at = src_at + R, finlen_at = finn_at + B,
+               finsum_at = finlen_at + (size_t)B * MC, fintok_at = finsum_at + (size_t)B * MC, trace_at = fintok_at + (size_t)B * MC * T_max,
+               beam_words = trace_at + (size_t)S * R * 2;
+  if (beam) {
+    HIPCHK(e->dec_beam.ensure(sizeof(int) * beam_words));
+    HIPCHK(hipMemsetAsync(e->dec_beam.p, 0, sizeof(int) * beam_words, s2));
+  }
+  if (!e->dec_done_host) HIPCHK(hipHostMalloc((void**)&e->dec_done_host, sizeof(int) * 4, hipHostMallocDefault));
+  int* tok_buf[2] = {(int*)e->dec_tokens.p, (int*)e->dec_tokens.p + (size_t)R * T_max};
+  int* tok_pre = (int*)e->dec_tokens.p + 2 * (size_t)R * T_max;
+  unsigned char* masks = (unsigned char*)e->dec_masks.p;
+  float* sum_lp = (float*)e->dec_state.p;
+  float* nsp = sum_lp + R;
+  int* n_done = (int*)(nsp + B);
+  int* bw = (int*)e->dec_beam.p;
+  float* logits = (float*)e->dec_logits.p;
+  half_t* cache = (half_t*)e->dec_cache.p;
+  const int* tab_dev = (const int*)e->dec_rows.p;
+  HIPCHK(hipMemcpyAsync(tok_buf[0], init.data(), sizeof(int) * init.size(), hipMemcpyHostToDevice, s2));
+  HIPCHK(hipMemcpyAsync(e->dec_rows.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, s2));
+  HIPCHK(hipMemcpyAsync(masks, d->suppress_mask_host, V, hipMemcpyHostToDevice, s2));
+  if (d->blank_mask_host) HIPCHK(hipMemcpyAsync(masks + V, d->blank_mask_host, V, hipMemcpyHostToDevice, s2));
+  HIPCHK(hipMemsetAsync(e->dec_state.p, 0, state_bytes, s2));
+  HIPCHK(hipStreamSynchronize(s2));  // `init` / `tab` are pageable host memory
+
+  DecodeSelectArgs sel{};
+  sel.logits = logits;
+  sel.ld = V;
+  sel.n_vocab = V;
+  sel.T_max = T_max;
+  sel.suppress_mask = masks;
+  sel.blank_mask = d->blank_mask_host ? masks + V : nullptr;
+  sel.eot = o->eot;
+  sel.timestamp_begin = o->timestamp_begin;
+  sel.apply_timestamp_rules = o->apply_timestamp_rules;
+  sel.max_initial_timestamp_index = o->max_initial_timestamp_index;
+  sel.sum_logprob = sum_lp;
+  sel.n_done = n_done;
+  sel.n_initial_rows = tab_dev + 2 * (size_t)R;
+  sel.cap_rows = tab_dev + 3 * (size_t)R;
+  if (!beam) {
+    sel.seed_rows = (const unsigned long long*)(tab_dev + seed_at);
+    sel.temperature_rows = (const float*)(tab_dev + temp_at);
+  }
+
+  int cur_tok = 0, cur_cache = 0, steps = 0, step_positions = 0;
+  for (int c = 0; c < S; ++c) {
+    const int* row = tab_dev + (size_t)(4 + 3 * c) * R;   // fed position, key count, cur_len of choice c
+    if (c == 0) {
+      const StepPos last{r.n_max - 1, tab_dev + pre_at}, sot{-1, want_nsp ? tab_dev + pre_at + B : nullptr};
+      WCA_TRY(run_decode_prefill(e, s2, kvbuf, tok_pre, B, r.n_max, T_max, last, sot));   // into the first half, as planes of B rows
+      if (want_nsp) HIPCHK(launch_token_prob(logits + (size_t)B * V, V, V, o->no_speech, nsp, B, s2));
+      // every row of a group starts from its audio's logits and cache: logits row b to rows [b G, (b + 1) G), from the back so that no
+      // source row is overwritten before it is read; the cache rows [0, n_initial) into the second half, as planes of R rows
+      for (int dst = R - 1; dst > 0; --dst)
+        if (dst != dst / G)
+          HIPCHK(hipMemcpyAsync(logits + (size_t)dst * V, logits + (size_t)(dst / G) * V, sizeof(float) * V, hipMemcpyDeviceToDevice, s2));
+      HIPCHK(launch_kv_reorder(cache, cache + half_elems, 2 * L, B, R, T_max, dt, nullptr, G, tab_dev + 2 * (size_t)R, s2));
+      cur_cache = 1;
+    } else {
+      ++step_positions;
+      e->dec_cache_off = cur_cache * half_elems;
+      WCA_TRY(run_decode_step(e, s2, kvbuf, tok_buf[cur_tok], R, StepPos{0, row}, T_max, true, G));
+    }
+    sel.tokens = tok_buf[cur_tok];
+    sel.cur_len_rows = row + 2 * (size_t)R;
+    sel.n_done_idx = c;
+    if (beam) {
+      BeamTopkArgs tk{sel, K, bw + cand_at, (float*)(bw + lp_at)};
+      HIPCHK(launch_beam_topk(tk, R, s2));
+      BeamMergeArgs m{};
+      m.cand_tok = bw + cand_at;
+      m.cand_lp = (const float*)(bw + lp_at);
+      m.K = K;
+      m.G = G;
+      m.tok_in = tok_buf[cur_tok];
+      m.tok_out = tok_buf[cur_tok ^ 1];
+      m.T_max = T_max;
+      m.sum_logprob = sum_lp;
+      m.src = bw + src_at;
+      m.cur_len_rows = sel.cur_len_rows;
+      m.n_initial_rows = sel.n_initial_rows;
+      m.cap_rows = sel.cap_rows;
+      m.first = c == 0;
+      m.eot = o->eot;
+      m.max_candidates = MC;
+      m.fin_n = bw + finn_at;
+      m.fin_len = bw + finlen_at;
+      m.fin_sum = (float*)(bw + finsum_at);
+      m.fin_tok = bw + fintok_at;
+      m.trace = bw + trace_at + (size_t)c * R * 2;
+      m.n_done = n_done + c;
+      HIPCHK(launch_beam_merge(m, B, s2));
+      cur_tok ^= 1;
+      if (c > 0) {   // the cache rows follow their beams: key count of this step's forward
+        HIPCHK(launch_kv_reorder(cache + cur_cache * half_elems, cache + (cur_cache ^ 1) * half_elems, 2 * L, R, R, T_max, dt, bw + src_at, 1,
+                                 row + R, s2));
+        cur_cache ^= 1;
+      }
+    } else {
+      HIPCHK(launch_decode_select(sel, R, s2));
+    }
+    steps = c + 1;
+    if ((steps & 3) == 0 && steps < S) {
+      HIPCHK(hipMemcpyAsync(e->dec_done_host, n_done + c, sizeof(int), hipMemcpyDeviceToHost, s2));
+      HIPCHK(hipStreamSynchronize(s2));
+      if (e->dec_done_host[0] >= (beam ? B : R)) break;
+    }
+  }
+  e->dec_cache_off = cur_cache * half_elems;
+
+  // read-back and, for the beams, upstream's finalize
+  std::vector<int32_t> toks((size_t)R * T_max), fin(beam ? trace_at - finn_at : 0);
+  std::vector<float> lp((size_t)R + B);
+  HIPCHK(hipMemcpyAsync(toks.data(), tok_buf[cur_tok], sizeof(int) * toks.size(), hipMemcpyDeviceToHost, s2));
+  HIPCHK(hipMemcpyAsync(lp.data(), sum_lp, sizeof(float) * lp.size(), hipMemcpyDeviceToHost, s2));
+  if (beam) HIPCHK(hipMemcpyAsync(fin.data(), bw + finn_at, sizeof(int) * fin.size(), hipMemcpyDeviceToHost, s2));
+  HIPCHK(hipStreamSynchronize(s2));
+  const int32_t *fin_n = fin.data(), *fin_len = fin_n + B, *fin_tok = fin_len + 2 * (size_t)B * MC;
+  const float* fin_sum = (const float*)(fin_len + (size_t)B * MC);
+  const int eot = o->eot;
+  std::fill(gd->tokens_out_host, gd->tokens_out_host + (size_t)B * n_slot * T_max, eot);
+  for (int b = 0; b < B; ++b) {
+    const int ni = r.ni(b), n_have = ni + std::min(steps, r.sl(b));
+    int n_out = 0;
+    auto put = [&](const int32_t* row, int n_tok, float sum) {
+      const size_t slot = (size_t)b * n_slot + n_out++;
+      std::copy(row, row + n_tok, gd->tokens_out_host + slot * T_max);
+      gd->n_tokens_host[slot] = n_tok;
+      gd->sum_logprob_host[slot] = sum;
+    };
+    if (beam) {
+      for (int q = 0; q < fin_n[b]; ++q) put(fin_tok + ((size_t)b * MC + q) * T_max, fin_len[(size_t)b * MC + q], fin_sum[(size_t)b * MC + q]);
+      for (int g = 0; g < G && n_out < G; ++g)   // the live beams, best first; a dead beam (-inf) is no sequence
+        if (std::isfinite(lp[(size_t)b * G + g])) put(toks.data() + ((size_t)b * G + g) * T_max, n_have, lp[(size_t)b * G + g]);
+    } else {
+      for (int g = 0; g < G; ++g) {
+        const int32_t* row = toks.data() + ((size_t)b * G + g) * T_max;
+        int n = n_have;
+        for (int i = ni; i < n_have; ++i)
+          if (row[i] == eot) {
+            n = i;
+            break;
+          }
+        put(row, n, lp[(size_t)b * G + g]);
+      }
+    }
+    for (int q = n_out; q < n_slot; ++q) {
+      gd->n_tokens_host[(size_t)b * n_slot + q] = 0;
+      gd->sum_logprob_host[(size_t)b * n_slot + q] = 0.f;
+    }
+    gd->n_out_host[b] = n_out;
+    if (want_nsp) gd->no_speech_prob_host[b] = lp[(size_t)R + b];
+  }
+  st->decoded = true;
+  e->last_batch = B;
+  e->dec_prefill_positions = r.n_max;
+  e->dec_step_positions = step_positions;
+  e->dec_batch = R;
+  e->dec_T_max = T_max;
+  e->dec_logits_rows = R;
+  if (beam) {
+    e->grp_steps = steps;
+    e->grp_rows = R;
+    e->grp_trace_off = sizeof(int) * trace_at;
+  }
+  return WCA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -357,6 +599,30 @@ int wca_decode(wca_engine* e, const wca_decode_desc* d) {
     if (!(d->temperature_host[b] >= 0.f) || !std::isfinite(d->temperature_host[b]))
       return fail(WCA_ERR_INVALID, "row %d: temperature %g is negative or not finite", b, (double)d->temperature_host[b]);
   return d->per_row ? decode_per_row(e, d, r) : decode_uniform(e, d, r);
+}
+
+int wca_decode_group(wca_engine* e, const wca_decode_desc* d, const wca_group_desc* g) {
+  if (!e) return fail(WCA_ERR_INVALID, "null engine");
+  if (!d || !g) return fail(WCA_ERR_INVALID, "null descriptor");
+  if (!g->tokens_out_host || !g->n_tokens_host || !g->sum_logprob_host || !g->n_out_host) return fail(WCA_ERR_INVALID, "null argument");
+  if ((d->per_row | d->prefill | d->redecode) & ~1) return fail(WCA_ERR_INVALID, "per_row, prefill and redecode must each be 0 or 1");
+  if (!d->prefill) return fail(WCA_ERR_INVALID, "a group decode always runs the batched prefill: pass prefill = 1");
+  if (!d->temperature_host != !d->seed_host) return fail(WCA_ERR_INVALID, "temperature_host and seed_host are given together or not at all");
+  if (!d->per_row && (d->temperature_host || d->redecode)) return fail(WCA_ERR_INVALID, "temperatures, seeds and redecode need per_row = 1");
+  if (d->redecode && (d->mel_dev || d->pcm_dev)) return fail(WCA_ERR_INVALID, "redecode takes no input: pass mel_dev = pcm_dev = NULL");
+  if (g->mode != 0 && g->mode != 1) return fail(WCA_ERR_INVALID, "mode %d is neither 0 (beam) nor 1 (samples)", g->mode);
+  if (g->n_group < 1 || g->n_group > BEAM_GROUP_MAX) return fail(WCA_ERR_INVALID, "n_group %d outside [1,%d]", g->n_group, BEAM_GROUP_MAX);
+  if (g->mode == 0 && d->temperature_host) return fail(WCA_ERR_INVALID, "beam search runs at temperature 0: pass no temperatures");
+  if (g->mode == 1 && !d->temperature_host) return fail(WCA_ERR_INVALID, "independent samples need temperature_host and seed_host");
+  if (g->mode == 0 && (g->max_candidates < 1 || g->max_candidates > 4096)) return fail(WCA_ERR_INVALID, "max_candidates %d outside [1,4096]", g->max_candidates);
+  if (d->batch < 1 || (long)d->batch * g->n_group > e->max_batch)
+    return fail(WCA_ERR_INVALID, "batch %d x n_group %d outside [1, max_batch = %d] decoder rows", d->batch, g->n_group, e->max_batch);
+  DecodeRows r{d->batch, d->per_row, d->initial_tokens_host, d->n_initial_host, d->sot_index_host, d->sample_len_host};
+  WCA_TRY(decode_check(e, d, &r, false));
+  for (int b = 0; d->temperature_host && b < d->batch; ++b)
+    if (!(d->temperature_host[b] >= 0.f) || !std::isfinite(d->temperature_host[b]))
+      return fail(WCA_ERR_INVALID, "row %d: temperature %g is negative or not finite", b, (double)d->temperature_host[b]);
+  return decode_group(e, d, g, r);
 }
 
 // Language identification (upstream detect_language): phase 1 as a decode takes it, ONE decoder position (t = 0, token sot) for every
@@ -382,6 +648,7 @@ int wca_detect_language(wca_engine* e, const float* mel_dev, const float* pcm_de
   hipStream_t s2 = e->stream2;
   const int T_max = 1;   // a one-slot self-attention cache: position 0 attends to itself
   e->dec_batch = e->dec_T_max = e->dec_logits_rows = 0;   // the last decode's cache is overwritten
+  e->dec_cache_off = 0;
   HIPCHK(e->dec_cache.ensure(sizeof(half_t) * (size_t)L * 2 * batch * T_max * dt));
   HIPCHK(e->dec_tokens.ensure(sizeof(int) * (size_t)batch * T_max));
   HIPCHK(e->dec_state.ensure((sizeof(float) * n_lang + sizeof(int)) * (size_t)batch));

@@ -273,6 +273,7 @@ struct DecPass {
   bool pair;             // operands are [hi | lo] rows against the K-doubled weights (the teacher-forced decoder in split mode); otherwise
                          // single f16 operands on plain weights -- in split mode too (prefill and step: whisper.decode runs in fp16)
   const half_t* kv;      // cross-K/V of the batch (rows [hi | lo] in split mode; single operands read the hi halves)
+  int kv_group;          // > 1: row b reads the cross-K/V of audio b / kv_group (the beams of wca_decode_group; one-query steps only)
   // self-attention keys: the QKV buffer itself under the causal mask (cache == nullptr), or the cache planes [L][2][B][T_max][d], to
   // which the QKV projection appends position pos and whose first pos + 1 slots the one query attends to. With per-row positions the key
   // counts are the table behind the positions: a step's tables are [B] fed positions, then [B] key counts (the per-row wca_decode)
@@ -391,6 +392,7 @@ AttnArgs cross_attn_args(const wca_engine* e, const DecPass& p, int li, const ha
   a.cap_ld = p.Fpad;
   a.cap_cols = p.Fcap;
   a.nk = N_CTX;
+  a.kv_group = p.kv_group;
   return a;
 }
 
@@ -478,14 +480,16 @@ int run_decoder(wca_engine* e, const int64_t* tokens_dev, int B, int n, float* c
 // self-attention K/V cache (positions 0..pos), cross-attention over this batch's cross-K/V; want_logits: the logits of that position
 // -> e->dec_logits (otherwise the step ends with the final residual stream in e->xd).
 // pos.rows (a step's tables): row b feeds the token at its OWN position and attends to the cached keys up to it (DecPass::nk_rows).
-int run_decode_step(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, StepPos pos, int T_max, bool want_logits) {
+int run_decode_step(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, StepPos pos, int T_max, bool want_logits,
+                    int kv_group) {
   const wca_model_dims& D = e->dims;
   DecPass p{};
   p.s = s;
   p.B = B;
   p.nq = 1;
   p.kv = kvbuf;   // split mode: the cross-K/V rows are [hi | lo]; the greedy pre-pass (whisper.decode runs in fp16 itself) reads the hi halves
-  p.cache = (half_t*)e->dec_cache.p;
+  p.kv_group = kv_group;
+  p.cache = (half_t*)e->dec_cache.p + e->dec_cache_off;
   p.T_max = T_max;
   p.pos = pos;
   p.l1 = D.n_text_layer;
@@ -512,7 +516,7 @@ int run_decode_prefill(wca_engine* e, hipStream_t s, const half_t* kvbuf, const 
   p.B = B;
   p.nq = n;
   p.kv = kvbuf;
-  p.scatter = (half_t*)e->dec_cache.p;
+  p.scatter = (half_t*)e->dec_cache.p + e->dec_cache_off;
   p.T_max = T_max;
   p.l1 = e->dims.n_text_layer;
   HIPCHK(launch_embed_prefix(tokens, T_max, n, e->tok_emb, e->dec_pos, e->xd, B, dt, e->dims.n_vocab, s));

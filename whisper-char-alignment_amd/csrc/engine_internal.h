@@ -177,6 +177,11 @@ struct wca_engine {
   wca::GrowBuf dec_cache, dec_tokens, dec_masks, dec_logits, dec_state;
   wca::GrowBuf dec_rows;              // the per-row wca_decode: the per-row int tables (n_initial - 1, sot_index, n_initial, sample cap; per step: fed position, key count, cur_len)
   wca::GrowBuf dec_gather;            // prefill: the f32 residual rows whose logits are needed ([2B][d]: last initial position, <|sot|>)
+  wca::GrowBuf dec_beam;              // wca_decode_group: the beam step's candidates, sources, finished lists and trace
+  size_t dec_cache_off = 0;           // halfs from dec_cache.p to the cache the decoder reads and appends to: 0, or the second half while a
+                                      // group decode ping-pongs between the two (kv_reorder); wca_test_decode_state reads from there
+  int grp_steps = 0, grp_rows = 0;    // the last wca_decode_group in beam mode: choices made and decoder rows (wca_test_beam_trace)
+  size_t grp_trace_off = 0;           // bytes from dec_beam.p to its trace [steps][rows][2]
   int* dec_done_host = nullptr;  // pinned: completion counter read back while the loop runs
   // wca_resample_16k: the polyphase tables of the input rates seen so far (f32 on the device, in the layout the plan's table home reads);
   // at most 8, the oldest leaves
@@ -309,7 +314,9 @@ int run_encoder(wca_engine* e, int B);
 int run_cross_kv(wca_engine* e, int B, half_t* kvbuf = nullptr, bool skip_last_v = false);
 int run_decoder(wca_engine* e, const int64_t* tokens_dev, int B, int n, float* cap, int Fpad, int Fcap, float* logits_out, hipStream_t s = nullptr,
                 const half_t* kvbuf = nullptr, bool finish_last = false);
-int run_decode_step(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, StepPos pos, int T_max, bool want_logits);
+// kv_group > 1: row b attends to the cross-K/V of audio b / kv_group (wca_decode_group)
+int run_decode_step(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, StepPos pos, int T_max, bool want_logits,
+                    int kv_group = 1);
 int run_decode_prefill(wca_engine* e, hipStream_t s, const half_t* kvbuf, const int* tokens, int B, int n, int T_max, StepPos last, StepPos sot);
 int mel_to_tm(wca_engine* e, const float* mel_dev, int batch);
 int run_phase1(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int* n_samples_dev, int batch, int slot,

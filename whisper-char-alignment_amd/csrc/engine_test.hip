@@ -317,11 +317,87 @@ int wca_test_decode_state(wca_engine* e, int batch, int T_max, int logits_rows, 
     return fail(WCA_ERR_INVALID, "the last decode left %d logits rows, not %d", e->dec_logits_rows, logits_rows);
   const size_t logits_bytes = sizeof(float) * (size_t)logits_rows * D.n_vocab;
   const size_t cache_bytes = sizeof(half_t) * (size_t)D.n_text_layer * 2 * batch * T_max * D.n_text_state;
-  if (logits_bytes > e->dec_logits.bytes || cache_bytes > e->dec_cache.bytes) return fail(WCA_ERR_INVALID, "the decode buffers hold less than was asked for");
+  const size_t cache_off = sizeof(half_t) * e->dec_cache_off;   // a group decode: the half its last step wrote
+  if (logits_bytes > e->dec_logits.bytes || cache_off + cache_bytes > e->dec_cache.bytes) return fail(WCA_ERR_INVALID, "the decode buffers hold less than was asked for");
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipStreamSynchronize(e->stream2));
   HIPCHK(hipMemcpy(logits_host, e->dec_logits.p, logits_bytes, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(cache_f16_host, e->dec_cache.p, cache_bytes, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(cache_f16_host, (const char*)e->dec_cache.p + cache_off, cache_bytes, hipMemcpyDeviceToHost));
+  return WCA_OK;
+}
+
+int wca_test_beam_step(wca_engine* e, const wca_test_beam_desc* d) {
+  if (!e || !d) return fail(WCA_ERR_INVALID, "null argument");
+  if (!d->logits_dev || !d->tokens_in_dev || !d->tokens_out_dev || !d->cur_len_dev || !d->n_initial_dev || !d->cap_dev || !d->suppress_mask_dev ||
+      !d->opts || !d->sum_logprob_dev || !d->src_dev || !d->cand_tok_dev || !d->cand_lp_dev || !d->fin_n_dev || !d->fin_len_dev || !d->fin_sum_dev ||
+      !d->fin_tok_dev || !d->trace_dev || !d->n_done_dev)
+    return fail(WCA_ERR_INVALID, "null argument");
+  const wca_decode_opts* o = d->opts;
+  if (d->batch < 1 || d->n_group < 1 || d->n_group > BEAM_GROUP_MAX || d->n_vocab < 1 || d->T_max < 2 || d->max_candidates < 1)
+    return fail(WCA_ERR_INVALID, "bad shape");
+  if (d->tokens_in_dev == d->tokens_out_dev) return fail(WCA_ERR_INVALID, "tokens_in_dev and tokens_out_dev are two buffers");
+  if (o->eot < 0 || o->eot >= d->n_vocab || o->timestamp_begin < 0 || o->timestamp_begin > d->n_vocab)
+    return fail(WCA_ERR_INVALID, "eot / timestamp_begin outside the vocabulary");
+  HIPCHK(hipSetDevice(e->device));
+  const int R = d->batch * d->n_group;
+  BeamTopkArgs tk{};
+  tk.sel = select_args(d->logits_dev, d->n_vocab, const_cast<int32_t*>(d->tokens_in_dev), d->T_max, d->suppress_mask_dev, d->blank_mask_dev, o,
+                       d->sum_logprob_dev, d->n_done_dev);
+  tk.sel.cur_len_rows = d->cur_len_dev;
+  tk.sel.n_initial_rows = d->n_initial_dev;
+  tk.sel.cap_rows = d->cap_dev;
+  tk.K = d->n_group + 1;
+  tk.cand_tok = d->cand_tok_dev;
+  tk.cand_lp = d->cand_lp_dev;
+  HIPCHK(launch_beam_topk(tk, R, e->stream));
+  BeamMergeArgs m{};
+  m.cand_tok = d->cand_tok_dev;
+  m.cand_lp = d->cand_lp_dev;
+  m.K = tk.K;
+  m.G = d->n_group;
+  m.tok_in = d->tokens_in_dev;
+  m.tok_out = d->tokens_out_dev;
+  m.T_max = d->T_max;
+  m.sum_logprob = d->sum_logprob_dev;
+  m.src = d->src_dev;
+  m.cur_len_rows = d->cur_len_dev;
+  m.n_initial_rows = d->n_initial_dev;
+  m.cap_rows = d->cap_dev;
+  m.first = d->first != 0;
+  m.eot = o->eot;
+  m.max_candidates = d->max_candidates;
+  m.fin_n = d->fin_n_dev;
+  m.fin_len = d->fin_len_dev;
+  m.fin_sum = d->fin_sum_dev;
+  m.fin_tok = d->fin_tok_dev;
+  m.trace = d->trace_dev;
+  m.n_done = d->n_done_dev;
+  HIPCHK(launch_beam_merge(m, d->batch, e->stream));
+  return WCA_OK;
+}
+
+int wca_test_kv_reorder(wca_engine* e, const void* src_dev, void* dst_dev, int n_planes, int rows_src, int rows_dst, int T_max, int d,
+                        const int32_t* src_idx_dev, int div, const int32_t* n_keep_dev) {
+  if (!e || !src_dev || !dst_dev || !n_keep_dev) return fail(WCA_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(e->device));
+  if (launch_kv_reorder((const half_t*)src_dev, (half_t*)dst_dev, n_planes, rows_src, rows_dst, T_max, d, src_idx_dev, div, n_keep_dev, e->stream) !=
+      hipSuccess)
+    return fail(WCA_ERR_INVALID, "the cache reorder refused these arguments");
+  return WCA_OK;
+}
+
+int wca_test_beam_trace(wca_engine* e, int32_t* steps_out, int32_t* rows_out, int32_t* trace_host, int64_t cap_entries) {
+  if (!e || !steps_out || !rows_out) return fail(WCA_ERR_INVALID, "null argument");
+  if (e->grp_rows < 1) return fail(WCA_ERR_STATE, "the last decode was no beam search");
+  *steps_out = e->grp_steps;
+  *rows_out = e->grp_rows;
+  if (!trace_host) return WCA_OK;
+  const size_t n = (size_t)e->grp_steps * e->grp_rows * 2;
+  if (cap_entries < 0 || (size_t)cap_entries < n) return fail(WCA_ERR_INVALID, "the trace holds %zu entries, more than the %lld offered", n, (long long)cap_entries);
+  if (e->grp_trace_off + sizeof(int) * n > e->dec_beam.bytes) return fail(WCA_ERR_STATE, "the beam buffers hold less than the trace");
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipStreamSynchronize(e->stream2));
+  HIPCHK(hipMemcpy(trace_host, (const char*)e->dec_beam.p + e->grp_trace_off, sizeof(int) * n, hipMemcpyDeviceToHost));
   return WCA_OK;
 }
 

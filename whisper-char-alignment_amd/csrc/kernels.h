@@ -139,6 +139,10 @@ struct AttnArgs {
   // of the decode step takes it (nq == 1, no capture, no mask, not split): anything else is hipErrorInvalidValue. Row b gets the key
   // partition and summation order of a uniform call with nk = nk_rows[b].
   const int* nk_rows;
+  // rows of a group share one K / V (wca_decode_group: decoder row b is a beam of audio b / kv_group and attends to that audio's
+  // cross-K/V): kv_group > 1 indexes K and V by b / kv_group. Only the one-query f16 kernel with uniform key counts takes it, as its own
+  // instance; 0 and 1 mean the plain form, whose instances hold none of this.
+  int kv_group;
 };
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 hipError_t launch_attention_split(const AttnArgs& a, hipStream_t s);  // attention_split.hip (launch_attention forwards a.split != 0 here)
@@ -209,6 +213,50 @@ hipError_t launch_decode_select(const DecodeSelectArgs& a, int B, hipStream_t s)
 // out[b] = softmax(logits[b])[token]  (no_speech_prob: the <|nospeech|> probability at the <|sot|> position)
 hipError_t launch_token_prob(const float* logits, int ld, int n_vocab, int token, float* out, int B, hipStream_t s);
 hipError_t launch_f32_to_f16(const float* in, half_t* out, size_t n, hipStream_t s);
+// ---------------------------------------------------------------- beam step and cache reorder (beam.hip)
+// Decoder row r = b * G + g is beam g of audio b (wca_decode_group). A step is two launches: the per-row candidates, then the per-audio merge.
+constexpr int BEAM_GROUP_MAX = 16;
+// (a) one workgroup per row: the filters of decode_select (the per-row form of `sel`: cur_len_rows / n_initial_rows / cap_rows), the fp32
+// log-softmax of the filtered logits, the top K = G + 1 entries -- the lowest token first among equal logits -- into cand_tok / cand_lp
+// [R][K]. Entries past the tokens the filters leave, and every entry of a row that is past its budget, are token -1 at -inf.
+struct BeamTopkArgs {
+  DecodeSelectArgs sel;   // logits, masks, options and the CURRENT token rows; sum_logprob / n_done are not used
+  int K;
+  int* cand_tok;
+  float* cand_lp;
+};
+hipError_t launch_beam_topk(const BeamTopkArgs& a, int R, hipStream_t s);
+// (b) one wave per audio, upstream's BeamSearchDecoder.update: the G K candidates score sum_logprob[source] + logprob and are walked in the
+// order (score descending, source beam ascending, token ascending); a candidate ending in eot is newly finished, the others become the G
+// next beams and the walk stops at the G-th. The newly finished ones join the audio's finished list, best first, while it holds fewer than
+// max_candidates. tok_out row b * G + g = tok_in row src, its first cur_len tokens, then the new token (tok_in and tok_out are two
+// buffers); sum_logprob is updated in place, src[r] is the ABSOLUTE source row, trace[r] = (src[r], token). first != 0: only beam 0 of a
+// group offers candidates (the beams are still identical). An audio past its budget is copied through (src[r] = r, trace token -1). *n_done
+// counts the audios whose finished list is full after this step or that are past their budget.
+struct BeamMergeArgs {
+  const int* cand_tok;
+  const float* cand_lp;
+  int K, G;
+  const int* tok_in;
+  int* tok_out;
+  int T_max;
+  float* sum_logprob;                                  // [R]
+  int* src;                                            // [R]
+  const int *cur_len_rows, *n_initial_rows, *cap_rows;  // [R]: the rows of a group hold their audio's values
+  int first, eot, max_candidates;
+  int* fin_n;      // [B] sequences in the audio's finished list
+  int* fin_len;    // [B][max_candidates] tokens before the closing eot
+  float* fin_sum;  // [B][max_candidates]
+  int* fin_tok;    // [B][max_candidates][T_max]
+  int* trace;      // [R][2] of this step
+  int* n_done;
+};
+hipError_t launch_beam_merge(const BeamMergeArgs& a, int B, hipStream_t s);
+// For every plane p < n_planes (a decoder layer's K or V cache) and row r < rows_dst: dst[p][r][0 : n_keep[r]] = src[p][s][0 : n_keep[r]]
+// with s = src_idx[r], or r / div where src_idx is null (the broadcast of an audio's prefill to its group); planes are [rows][T_max][d] f16,
+// copied 8 halfs at a time (d % 8 == 0). s is clamped to [0, rows_src) and n_keep[r] to [0, T_max]; src and dst must not overlap.
+hipError_t launch_kv_reorder(const half_t* src, half_t* dst, int n_planes, int rows_src, int rows_dst, int T_max, int d, const int* src_idx,
+                             int div, const int* n_keep, hipStream_t s);
 // ---------------------------------------------------------------- language identification head (language_head.hip)
 // x [B][d] f32: the final residual stream at the <|sot|> position. Per row: xn = f16(LayerNorm(x; gamma, beta)), logit_j = xn . tok_emb[lang_begin + j]
 // (fp32 accumulation) for j < n_lang, probs [B][n_lang] = softmax(logit), lang_token [B] = lang_begin + argmax (lowest index among equals).

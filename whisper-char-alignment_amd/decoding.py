@@ -6,7 +6,7 @@ Upstream openai-whisper `decoding.py` is an absent third-party dependency; its p
 Built: language identification (`detect_language`, C ABI wca_detect_language: one decoder position and the language head on the GPU;
 the encoded state stays for the decode that follows, so detecting and decoding a window costs ONE encoder pass where upstream runs two),
 decode in a given language (DecodingOptions(language=None) is refused: call detect_language first, or transcribe(language="auto")),
-temperature 0 without beam search (greedy), and conditioning on a prompt and / or
+temperature 0 greedily or with beam search, and conditioning on a prompt and / or
 a prefix (DecodingOptions(prompt=...), the decoder side of transcribe(initial_prompt=...); prefix=...), whose initial tokens
 go through the decoder in one batched forward (wca_decode, prefill); a list of options gives every batch row a
 prompt / prefix of its own (wca_decode with per_row 1). Temperature sampling is opt-in through the engine-specific
@@ -14,8 +14,14 @@ DecodingOptions(seed=<int>): with a seed, temperature > 0 draws every token from
 upstream's GreedyDecoder.update does, and avg_logprob sums the untempered log-probabilities (wca_decode with temperature_host / seed_host; the rows of
 a list may differ in temperature and seed as well). The draw is Gumbel-max over Philox4x32-10 noise in the decode step's kernel
 (csrc/decode.hip): the law is upstream's, the draws are not torch's, because the generator differs; it is pinned token for token
-against a float64 restatement (tests/decode_sample_ref.py). With seed=None a temperature other than 0 raises as it always did,
-and beam_size / best_of / patience are refused either way. Anything else raises NotImplementedError instead of silently differing.
+against a float64 restatement (tests/decode_sample_ref.py). With seed=None a temperature other than 0 raises as it always did.
+Beam search and best_of (C ABI wca_decode_group; csrc/beam.hip): DecodingOptions(beam_size=G [, patience]) at temperature 0 is upstream's
+BeamSearchDecoder on G decoder rows per audio that share the audio's cross-K/V, DecodingOptions(best_of=G, temperature > 0, seed) is G
+independent samples per audio (sample g drawing with group_seed(seed, g)), and MaximumLikelihoodRanker (length_penalty) picks the result on
+the host; rows x G must fit the engine's max_batch. Pinned against a float64 restatement of upstream's update / finalize / ranker
+(tests/beam_ref.py) and against the fp32 oracle replayed along the engine's beams; where upstream leaves an order open (equal logits in
+topk, equal scores) the order is fixed here: lower source beam, then lower token. Upstream's own option checks raise its ValueErrors.
+Anything else raises NotImplementedError instead of silently differing.
 PARITY UNPINNED against upstream itself for decode and detect_language alike (no real checkpoint is at hand): both are pinned
 against this repository's fp32 CPU oracle on synthetic weights.
 """
@@ -104,15 +110,60 @@ def filter_masks(tokenizer, options, n_vocab):
     return sup, blank
 
 
-def _check_supported(options):
+GROUP_MAX = 16                   # decoder rows per audio (BEAM_GROUP_MAX of the library)
+GROUP_MIX = 0x94D049BB133111EB   # odd: distinct g give distinct seeds
+
+
+def group_seed(seed, g):
+    """The Philox seed of sample g of a row whose seed is `seed` (best_of; include/wca.h, wca_decode_group): the row's seed mixed with the
+    sample's index, so that sample 0 is the plain sampled decode of that seed and a row's samples do not depend on the batch it rides in."""
+    return (int(seed) ^ (int(g) * GROUP_MIX)) % (1 << 64)
+
+
+def sequence_score(sum_logprob, length, length_penalty=None):
+    """MaximumLikelihoodRanker's score of one sequence (upstream, restated): sum_logprob / length, or with a length penalty
+    sum_logprob / ((5 + length) / 6) ** length_penalty (Google NMT). A sequence without sampled tokens scores -inf: it ranks last."""
+    if length <= 0:
+        return -np.inf
+    penalty = float(length) if length_penalty is None else ((5 + length) / 6) ** length_penalty
+    return float(sum_logprob) / penalty
+
+
+def rank_sequences(sum_logprobs, lengths, length_penalty=None):
+    """MaximumLikelihoodRanker.rank for one audio: the index of the best sequence, the first among equal scores."""
+    scores = [sequence_score(s, n, length_penalty) for s, n in zip(sum_logprobs, lengths)]
+    return int(np.argmax(scores))
+
+
+def _check_supported(options, grouped=False):
+    """What is refused instead of silently differing from upstream. grouped: the caller can give every audio several decoder rows (decode()
+    does, through wca_decode_group); only then are beam_size / patience / best_of taken, under upstream's own checks
+    (DecodingTask._verify_options). A check on behalf of a plain one-row-per-audio decode refuses them as it always did."""
     sampling = options.temperature != 0.0 and options.seed is not None   # opt-in: without a seed every refusal is what it was
     if sampling and not (isinstance(options.temperature, (int, float)) and 0.0 <= options.temperature < float("inf")):
         raise ValueError("temperature must be a finite number >= 0, not %r" % (options.temperature,))
     if options.seed is not None and (isinstance(options.seed, bool) or not isinstance(options.seed, (int, np.integer))):
-        raise ValueError("seed must be an int (or None: greedy decoding only), not %r" % (options.seed,))
-    if (options.temperature != 0.0 and not sampling) or options.beam_size is not None or options.best_of is not None or options.patience is not None:
-        raise NotImplementedError("only greedy decoding (temperature 0, no beam search / best_of) is built; the reference "
-                                  "uses DecodingOptions(language='en') (infer_ali.py:40)")
+        raise ValueError("seed must be an int (or None: temperature 0 only), not %r" % (options.seed,))
+    if options.temperature != 0.0 and not sampling:
+        raise NotImplementedError("temperature %r needs DecodingOptions(seed=<int>): the engine's sampling (and with it best_of) is reproducible "
+                                  "by construction and picks no seed for the caller; without one only temperature 0 is decoded" % (options.temperature,))
+    if not grouped and (options.beam_size is not None or options.best_of is not None or options.patience is not None):
+        raise NotImplementedError("beam_size / patience / best_of take several decoder rows per audio: decode() runs them (C ABI "
+                                  "wca_decode_group); a decode of one row per audio does not")
+    for name in ("beam_size", "best_of"):
+        v = getattr(options, name)
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= GROUP_MAX):
+            raise ValueError("%s must be an int in [1, %d], not %r" % (name, GROUP_MAX, v))
+    if options.beam_size is not None and options.best_of is not None:
+        raise ValueError("beam_size and best_of can't be given together")
+    if options.patience is not None and (options.beam_size is None or not options.patience > 0):
+        raise ValueError("patience requires beam_size to be given, and must be positive")
+    if options.length_penalty is not None and not 0 <= options.length_penalty <= 1:
+        raise ValueError("length_penalty (alpha) should be a value between 0 and 1")
+    if options.temperature == 0.0 and options.best_of is not None:
+        raise ValueError("best_of with greedy sampling (T=0) is not compatible")
+    if options.temperature != 0.0 and options.beam_size is not None:
+        raise ValueError("beam_size needs temperature 0 (upstream's fallback drops it on the rungs above 0: pass best_of there)")
     if options.language is None:
         raise NotImplementedError("decode takes a given language: pass DecodingOptions(language=...) as infer_ali.py:40 does; "
                                   "detect_language(model, mel) names it, and transcribe(language=\"auto\") does both")
@@ -203,13 +254,20 @@ def decode(model, mel, options=DecodingOptions(), pcm=None, n_samples=None, enco
     if not rows:
         raise ValueError("an empty list of DecodingOptions")
     for o in rows:
-        _check_supported(o)
-    common = [dataclasses.replace(o, prompt=None, prefix=None, temperature=0.0, seed=None) for o in rows]
+        _check_supported(o, grouped=True)
+    if any((o.beam_size, o.patience) != (rows[0].beam_size, rows[0].patience) for o in rows):
+        raise NotImplementedError("the rows of one decode share beam_size and patience: a decode whose audios take different numbers of "
+                                  "decoder rows is not built")
+    common = [dataclasses.replace(o, prompt=None, prefix=None, temperature=0.0, seed=None, best_of=None) for o in rows]
     for b, c in enumerate(common):
         if c != common[0]:
             diff = [f.name for f in dataclasses.fields(c) if getattr(c, f.name) != getattr(common[0], f.name)]
             raise ValueError("the rows of one decode may differ in prompt / prefix / temperature / seed only; row %d differs from row 0 in %s"
                              % (b, ", ".join(diff)))
+    best_of = {o.best_of for o in rows if o.temperature != 0.0}   # (a row at temperature 0 carries none: it rides along greedily)
+    if len(best_of) > 1:
+        raise ValueError("the rows of one decode that sit at a temperature above 0 must share best_of")
+    best_of, beam_size = (best_of.pop() if best_of else None), rows[0].beam_size
     if redecode and (mel is not None or pcm is not None or encoded_batch is None):
         raise ValueError("redecode=True decodes the state of the previous decode again: pass mel = pcm = None and encoded_batch=B")
     single = mel is not None and mel.ndim == 2
@@ -231,7 +289,23 @@ def decode(model, mel, options=DecodingOptions(), pcm=None, n_samples=None, enco
         max_init = round(first.max_initial_timestamp / (CHUNK_LENGTH / dims.n_audio_ctx))
     kw = dict(eot=tokenizer.eot, timestamp_begin=tokenizer.timestamp_begin, apply_timestamp_rules=not first.without_timestamps,
               max_initial_timestamp_index=max_init, batch=B, no_speech=tokenizer.no_speech if tokenizer.no_speech is not None else -1)
-    if redecode or any(o.temperature != 0.0 for o in rows):
+    if beam_size is not None or best_of is not None:
+        # G decoder rows per audio (wca_decode_group): the beams, or best_of independent samples; then upstream's MaximumLikelihoodRanker
+        G = beam_size if beam_size is not None else best_of
+        if B * G > getattr(model, "max_batch", B * G):
+            raise NotImplementedError("%d audios x %d decoder rows each exceed the engine's max_batch = %d, and a group is not split over "
+                                      "several calls: create the engine with more rows" % (B, G, model.max_batch))
+        if not per_row:   # one DecodingOptions over the batch: row b draws with seed + b
+            rows, plans = [dataclasses.replace(first, seed=None if first.seed is None else int(first.seed) + b) for b in range(B)], plans * B
+        sampled = dict(temperature=[float(o.temperature) for o in rows], seed=[int(o.seed or 0) % (1 << 64) for o in rows]) if beam_size is None else {}
+        slots, n_slots, sums, n_out = model.decode_group(mel, pcm, n_samples, [p[0] for p in plans], [p[2] for p in plans], [p[1] for p in plans],
+                                                         sup, blank, redecode=redecode, n_group=G, mode=0 if beam_size is not None else 1,
+                                                         max_candidates=max(1, round(G * (first.patience or 1.0))) if beam_size is not None else None,
+                                                         **sampled, **kw)
+        best = [rank_sequences(sums[b, :n_out[b]], n_slots[b, :n_out[b]] - len(plans[b][0]), first.length_penalty) for b in range(B)]
+        tokens = np.stack([slots[b, i] for b, i in enumerate(best)])
+        n_tokens, sum_logprobs = [n_slots[b, i] for b, i in enumerate(best)], [sums[b, i] for b, i in enumerate(best)]
+    elif redecode or any(o.temperature != 0.0 for o in rows):
         if not per_row:   # one DecodingOptions over the batch: row b draws with seed + b
             rows, plans = [dataclasses.replace(first, seed=None if first.seed is None else int(first.seed) + b) for b in range(B)], plans * B
         tokens, n_tokens, sum_logprobs = model.decode_rows_sampled(mel, pcm, n_samples, [p[0] for p in plans], [p[2] for p in plans],

@@ -567,6 +567,74 @@ class WhisperAMD:
         return self._decode(mel, pcm, n_samples, batch, init, n_init, sot_index, sample_len, opts, suppress_mask, blank_mask, 1, 1, temps, seeds,
                             redecode)
 
+    def decode_group(self, mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask, blank_mask, eot, timestamp_begin,
+                     apply_timestamp_rules=True, max_initial_timestamp_index=50, batch=None, no_speech=-1, n_group=1, mode=0, max_candidates=None,
+                     temperature=None, seed=None, redecode=False):
+        """C ABI wca_decode_group: greedy_decode_rows' per-row arrays for the B audios, n_group decoder rows per audio that share its
+        cross-K/V. mode 0: beam search with beam_size = n_group and max_candidates = round(beam_size * patience) (default n_group); mode 1:
+        n_group independent samples per audio at temperature[b], sample g drawing with decoding.group_seed(seed[b], g).
+        Returns (tokens [B, n_slot, T_max] int32, n_tokens [B, n_slot] int32, sum_logprobs [B, n_slot] f32, n_out [B] int32) with
+        n_slot = max(n_group, max_candidates) for the beam and n_group for samples: the first n_out[b] slots of audio b hold a sequence
+        (beam: the finished list in the order it filled, then the live beams that top it up; samples: sample g in slot g), whose sampled
+        tokens are tokens[b, i, len(initial_tokens[b]) : n_tokens[b, i]]. The ranking is the caller's (decoding.rank_sequences).
+        self.last_no_speech_prob [B] as greedy_decode; the encoder state stays for a following align_batch(pcm=None, ...)."""
+        self._bind_stream()
+        B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(batch))
+        rows = [[int(t) for t in r] for r in initial_tokens]
+        if not (len(rows) == len(sot_index) == len(sample_len) == B):
+            raise ValueError("initial_tokens, sot_index and sample_len take one entry per batch row (%d)" % B)
+        G, mode = int(n_group), int(mode)
+        if mode not in (0, 1):
+            raise ValueError("mode is 0 (beam) or 1 (independent samples)")
+        max_candidates = G if max_candidates is None else int(max_candidates)
+        n_slot = max(G, max_candidates) if mode == 0 else G
+        if G < 1 or n_slot < 1:
+            raise ValueError("n_group and max_candidates must be at least 1")
+        temps = seeds = None
+        if temperature is not None or seed is not None:
+            if temperature is None or seed is None or len(temperature) != B or len(seed) != B:
+                raise ValueError("temperature and seed take one entry per batch row (%d)" % B)
+            temps = np.ascontiguousarray([float(t) for t in temperature], dtype=np.float32)
+            seeds = np.ascontiguousarray([int(v) % (1 << 64) for v in seed], dtype=np.uint64)
+        n_init = [len(r) for r in rows]
+        init = np.full((B, max(max(n_init, default=0), 1)), int(eot), dtype=np.int32)
+        for b, r in enumerate(rows):
+            init[b, :len(r)] = r
+        T = max((n + int(sl) for n, sl in zip(n_init, sample_len)), default=1)
+        tokens = np.zeros((B, n_slot, max(T, 1)), dtype=np.int32)
+        n_tok = np.zeros((B, n_slot), dtype=np.int32)
+        lp = np.zeros((B, n_slot), dtype=np.float32)
+        n_out = np.zeros(B, dtype=np.int32)
+        nsp = np.full(B, np.nan, dtype=np.float32)
+        sup = np.ascontiguousarray(suppress_mask, dtype=np.uint8)
+        blank = np.ascontiguousarray(blank_mask, dtype=np.uint8) if blank_mask is not None else None
+        if sup.shape[0] != self.dims.n_vocab or (blank is not None and blank.shape[0] != self.dims.n_vocab):
+            raise ValueError("filter masks must have n_vocab entries")
+        if mel is not None:
+            mel = mel.contiguous().float()
+        opts = _lib.DecodeOpts(max(int(v) for v in sample_len) if B else 0, int(eot), int(timestamp_begin), 1 if apply_timestamp_rules else 0,
+                               int(max_initial_timestamp_index), int(no_speech))
+        ns = _lib.i32_array(n_samples) if n_samples is not None else None
+        ni, si, sl = _lib.i32_array(n_init), _lib.i32_array(sot_index), _lib.i32_array(sample_len)
+        d = _lib.DecodeDesc(mel_dev=_ptr(mel), pcm_dev=_ptr(pcm), n_samples_host=_ptr(ns), initial_tokens_host=_ptr(init), n_initial_host=_ptr(ni),
+                            sot_index_host=_ptr(si), sample_len_host=_ptr(sl), temperature_host=_ptr(temps), seed_host=_ptr(seeds),
+                            suppress_mask_host=_ptr(sup), blank_mask_host=_ptr(blank), opts=C.pointer(opts),
+                            pcm_stride=pcm.shape[1] if pcm is not None else 0, batch=B, per_row=1, prefill=1, redecode=1 if redecode else 0)
+        g = _lib.GroupDesc(tokens_out_host=_ptr(tokens), n_tokens_host=_ptr(n_tok), sum_logprob_host=_ptr(lp), n_out_host=_ptr(n_out),
+                           no_speech_prob_host=_ptr(nsp if opts.no_speech >= 0 else None), n_group=G, mode=mode, max_candidates=max_candidates)
+        _lib.check(self._lib.wca_decode_group(self._h, C.byref(d), C.byref(g)))
+        self.last_no_speech_prob = nsp
+        return tokens, n_tok, lp, n_out
+
+    def beam_trace(self):
+        """Test accessor (C ABI wca_test_beam_trace): what the last beam search chose -> [steps, rows, 2] int32, entry (c, r) = (the row
+        whose beam row r continues after choice c, the token it appended; -1 for a row past its budget)."""
+        steps, rows = C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.wca_test_beam_trace(self._h, C.byref(steps), C.byref(rows), None, 0))
+        trace = np.zeros((max(steps.value, 1), max(rows.value, 1), 2), dtype=np.int32)
+        _lib.check(self._lib.wca_test_beam_trace(self._h, C.byref(steps), C.byref(rows), trace.ctypes.data_as(_lib._pi32), trace.size))
+        return trace[:steps.value, :rows.value]
+
     def detect_language(self, mel=None, tokenizer=None, *, pcm=None, n_samples=None, batch=None, sot=None, lang_begin=None, n_lang=None):
         """model.detect_language(mel, tokenizer) -> (language_tokens, language_probs), upstream's schema (decoding.detect_language).
         With sot / lang_begin / n_lang it is the thin C ABI call (wca_detect_language): mel [B,n_mels,3000] f32 cuda XOR pcm [B,stride]

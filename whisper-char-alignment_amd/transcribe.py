@@ -27,6 +27,10 @@ Limits (part of the contract):
     not: the law of the draws is upstream's (Categorical(logits / T), untempered log-probabilities), the draws themselves are not
     torch's -- another generator --, and what the ladder does to repetition loops on real speech is UNVALIDATED: no checkpoint is at
     hand, and random weights fall through every rung.
+  * beam_size, patience, length_penalty and best_of are upstream's and default to None (a call without them is what it was): the beam at
+    temperature 0, best_of on the rungs above it (so best_of needs a seed), each window on max(beam_size, best_of) decoder rows of the
+    engine's max_batch (C ABI wca_decode_group; transcribe_batch's docstring). What is pinned: the beam step, the cache reorder and the
+    loop (tests/test_beam_step_gpu.py, tests/test_kv_reorder_gpu.py, tests/test_decode_beam_gpu.py); parity with upstream itself is not.
   * the language is given, or language="auto" detects it (decoding.detect_language, C ABI wca_detect_language) on each recording's
     first window mel_window(mel, 0, size) -- the frames the first decode sees; upstream also detects on the first 30 s -- in the
     99-language numbering of the decode tokenizer, so the detected token is the one that lands in the sot sequence. The first windows
@@ -436,8 +440,9 @@ class _Call:
     tokens, and `state_left`: rows of encoded, undecoded state the engine's own detection left behind for the decode that comes next."""
 
     def __init__(self, model, language, initial_prompt, vocab_path, decode_options, decode_windows, detect_languages, seek_options, aligner_options,
-                 temperatures=(0.0,), seed=None, compression_ratio_threshold=2.4):
+                 temperatures=(0.0,), seed=None, compression_ratio_threshold=2.4, group_options=None):
         self.model, self.vocab_path, self.decode_options, self.seek_options = model, vocab_path, decode_options, seek_options
+        self.group_options = group_options or {}   # beam_size / patience / best_of: which of them a row carries depends on its temperature
         self.temperatures, self.seed, self.compression_ratio_threshold = temperatures, seed, compression_ratio_threshold   # seed None: no ladder
         self.decode_windows, self.detect_languages, self.aligner_options = decode_windows, detect_languages, aligner_options   # (None: no words)
         self.auto = isinstance(language, str) and language.lower() == "auto"
@@ -497,9 +502,15 @@ class _Call:
         """The engine's decode of a round's rows. temperatures None: at temperature 0, the call it always was."""
         greedy = temperatures is None or all(t == 0.0 for t in temperatures)
         temperatures, seeds = temperatures or [0.0] * len(prompts), seeds or [None] * len(prompts)
-        rows = [decoding.DecodingOptions(language=code, temperature=0.0, prompt=list(p) or None, vocab_path=self.vocab_path, **self.decode_options)
+        # upstream's decode_with_fallback: the beam (beam_size, patience) at temperature 0, best_of above it; a row that only rides along
+        # (None) on a rung of sampled rows carries neither
+        beam = {k: v for k, v in self.group_options.items() if k in ("beam_size", "patience") and v is not None}
+        best = {k: v for k, v in self.group_options.items() if k == "best_of" and v is not None}
+        rows = [decoding.DecodingOptions(language=code, temperature=0.0, prompt=list(p) or None, vocab_path=self.vocab_path,
+                                         **(beam if greedy else {}), **self.decode_options)
                 if greedy or not t else
-                decoding.DecodingOptions(language=code, temperature=t, seed=s, prompt=list(p) or None, vocab_path=self.vocab_path, **self.decode_options)
+                decoding.DecodingOptions(language=code, temperature=t, seed=s, prompt=list(p) or None, vocab_path=self.vocab_path, **best,
+                                         **self.decode_options)
                 for p, t, s in zip(prompts, temperatures, seeds)]
         want_text = self.vocab_path is not None
         if redecode:   # a later rung: the state of this round's first decode again, the accepted rows (None) for one token
@@ -616,7 +627,7 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
                      logprob_threshold=-1.0, word_timestamps=False, word_confidence=False, aligned_unit_type="char", aggr="topk", topk=10,
                      medfilt_width=3, vocab_path=None, temperature=0.0, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0, decode_windows=None,
                      detect_languages=None, sample_rate=SAMPLE_RATE, clip_timestamps=None, pieces=None, seed=None,
-                     compression_ratio_threshold=2.4, **decode_options):
+                     compression_ratio_threshold=2.4, beam_size=None, patience=None, length_penalty=None, best_of=None, **decode_options):
     """transcribe() of several recordings in lock-step: a list with transcribe()'s result for every recording of `audios`, in order.
     Each round cuts the next window of every unfinished recording, decodes them in ONE batch with every row's own previous text as its
     prompt (decoding.decode with one DecodingOptions per row: wca_decode with per_row 1) and, with word_timestamps, aligns the rows that
@@ -650,8 +661,29 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
     "temperature" is the rung its window was accepted at, and a window accepted above 0.5 does not condition the next one. With a seed
     decode_windows is also given temperatures= (one per row; None for a row whose earlier result was kept and whose new one is ignored)
     and seeds= (one per row). The law of the draws is upstream's, the draws are not (decoding.decode); what the ladder does to real
-    speech is UNVALIDATED here (module docstring)."""
+    speech is UNVALIDATED here (module docstring).
+    beam_size, patience, length_penalty, best_of (upstream's; all None: every call as it always was): as upstream's decode_with_fallback, a
+    window at temperature 0 is decoded by beam search (beam_size beams, a finished list of round(beam_size * patience) sequences) and a
+    window on a rung above 0 as the best of best_of independent samples (which therefore needs a seed); the winner is
+    MaximumLikelihoodRanker's, with length_penalty. Every window then takes G = max(beam_size, best_of) decoder rows (C ABI
+    wca_decode_group), so a round holds at most max_batch // G windows and G above max_batch is a ValueError. What is pinned: the beam
+    step and the cache reorder against a float64 restatement of upstream's BeamSearchDecoder, the loop against the fp32 oracle
+    (tests/test_beam_step_gpu.py, tests/test_decode_beam_gpu.py). PARITY with upstream itself stays UNPINNED, as for decode."""
     temperatures = check_supported(temperature, language, seed)
+    group_options = dict(beam_size=beam_size, patience=patience, best_of=best_of)
+    if length_penalty is not None:
+        decode_options = dict(decode_options, length_penalty=length_penalty)
+    if beam_size is not None or best_of is not None or patience is not None:
+        # (the checks of decoding._check_supported, before any audio is read; a probe per kind of row the ladder will build)
+        if beam_size is not None and best_of is not None and seed is None:
+            raise ValueError("best_of is for the rungs above temperature 0: it needs seed=<int> and a temperature ladder that reaches them")
+        if beam_size is not None or patience is not None:
+            decoding._check_supported(decoding.DecodingOptions(language="en", beam_size=beam_size, patience=patience, length_penalty=length_penalty), grouped=True)
+        if best_of is not None:
+            if seed is None:
+                raise ValueError("best_of draws samples: it needs seed=<int>, as all sampling here does")
+            decoding._check_supported(decoding.DecodingOptions(language="en", temperature=1.0, seed=0, best_of=best_of, length_penalty=length_penalty),
+                                       grouped=True)
     if pieces is not None and clip_timestamps is not None:
         raise ValueError("pieces cuts the whole recording: it cannot be combined with clip_timestamps")
     if word_confidence and not word_timestamps:
@@ -661,13 +693,17 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
     max_batch = int(getattr(model, "max_batch", 1))
     if max_batch < 1:
         raise ValueError("transcribe_batch needs model.max_batch >= 1")
+    n_group = max(beam_size or 1, best_of or 1)
+    if n_group > max_batch:
+        raise ValueError("beam_size / best_of = %d needs %d decoder rows per window: more than model.max_batch = %d" % (n_group, n_group, max_batch))
+    max_batch //= n_group   # windows per round: each takes n_group decoder rows
     if pieces is not None:
         plan_pieces(4 * max_batch, pieces, max_batch)   # (what does not depend on the recording is refused before any audio is read)
     seek = dict(condition_on_previous_text=condition_on_previous_text, no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold)
     words = dict(aligned_unit_type=aligned_unit_type, aggr=aggr, topk=topk, medfilt_width=medfilt_width, w_colnorm=w_colnorm,
                  w_rownorm=w_rownorm, w_coverage=w_coverage, word_confidence=word_confidence) if word_timestamps else None
     call = _Call(model, language, initial_prompt, vocab_path, decode_options, decode_windows, detect_languages, seek, words,
-                 *(() if seed is None else (temperatures, int(seed), compression_ratio_threshold)))
+                 *(() if seed is None else (temperatures, int(seed), compression_ratio_threshold)), group_options=group_options)
     audios = list(audios)
     results = [None] * len(audios)
     for group, mels, plans in form_groups(model, audios, sample_rates(sample_rate, len(audios)), clip_timestamps, pieces, max_batch):
@@ -715,6 +751,11 @@ def parse_args(argv=None):
     p.add_argument("--temperature_increment_on_fallback", type=float, help="the ladder's step up to 1.0 (upstream's default is 0.2; default: "
                    "none, --temperature alone)", **ladder)
     p.add_argument("--compression_ratio_threshold", type=float, help="default 2.4", **ladder)
+    # beam search and best_of (upstream's options; likewise absent unless given). Each window takes max(beam_size, best_of) of the --batch rows
+    p.add_argument("--beam_size", type=int, help="beams of the search at temperature 0 (upstream's command line runs 5; default: none, greedy)", **ladder)
+    p.add_argument("--patience", type=float, help="the search ends after round(beam_size * patience) finished sequences (default 1.0)", **ladder)
+    p.add_argument("--length_penalty", type=float, help="alpha of the ranker's length normalisation (default: none, sum / length)", **ladder)
+    p.add_argument("--best_of", type=int, help="independent samples per window on the rungs above temperature 0 (needs --seed)", **ladder)
     return p.parse_args(argv)
 
 
@@ -761,6 +802,9 @@ def main(args, model=None):
                   temperature=temperature_ladder(getattr(args, "temperature", 0.0), getattr(args, "temperature_increment_on_fallback", None)))
     elif getattr(args, "temperature", 0.0) != 0.0 or getattr(args, "temperature_increment_on_fallback", None) is not None:
         raise SystemExit("--temperature / --temperature_increment_on_fallback sample: pass --seed <int>")
+    for name in ("beam_size", "patience", "length_penalty", "best_of"):   # (likewise: given options only)
+        if getattr(args, name, None) is not None:
+            kw[name] = getattr(args, name)
     for group in groups_of(_recordings(args), args.batch):   # a group's files are written before the next group starts
         if args.batch > 1:
             results = transcribe_batch(model, [source(path) for _, path in group], **kw)
