@@ -607,6 +607,34 @@ int wca_test_set_switch(const char* name, int value);
 /* the [batch][n_text_layer * n_text_head] head selection scores (timing.py:13-43) of the LAST fused batch, after it was fetched (no batch in
  * flight): tools/precision_ablation.py compares them with the oracle's */
 int wca_test_last_scores(wca_engine* e, int batch, float* scores_host);
+/* Phase 2's post-processing of wca_align_batch_enqueue on caller-supplied logits (kernel parity test, tests/postproc_ref.py): the metadata
+ * staging, the head statistics on logits with the per-row (max, sum) kept, the top-k, the aggregation that re-materialises the selected
+ * heads, and the ragged DTW -- the very functions the fused path calls, on the engine's stream, then the copies and one synchronisation.
+ * No weights are needed. qk_dev [B][L*H][n_tok_max][ld] f32 with ld >= the largest n_frames[b]; utterance b's n_tok[b] x n_frames[b]
+ * corner counts. B in [1, max_batch], lengths as wca_align_desc's (n_tok[b] in [0, n_tok_max], n_frames[b] in [1, 1500]), options as
+ * wca_align_batch_enqueue checks them; anything else is WCA_ERR_INVALID / WCA_ERR_TOO_LONG. Every host output is nullable; F = n_frames_max,
+ * k = opts->topk: scores [B][L*H], colnorm [B][L*H][F], rowstats [B][L*H][n_tok_max][2] = (max, sum) -- rows [n_tok[b],
+ * n_tok_max) of an utterance are not written by this call --, sel_idx [B][k] (top-k only), matrix [B][n_tok_max][F] (rows
+ * [0, n_tok[b] - sot_len - 1) x columns [0, n_frames[b]) of utterance b are written by this call), jump [B][n_tok_max] as
+ * wca_align_result.jump_frame_host. */
+typedef struct {
+  const float* qk_dev;
+  const int32_t* n_tok_host;
+  const int32_t* n_frames_host;
+  const int32_t* open_end_host;     /* [B], nullable: as wca_align_desc.open_end_host */
+  const wca_align_opts* opts;
+  float* scores_host;
+  float* colnorm_host;
+  float* rowstats_host;
+  int32_t* sel_idx_host;
+  float* matrix_host;
+  int32_t* jump_host;
+  int32_t B, L, H, n_tok_max, ld, n_frames_max;   /* n_frames_max: F of the output layouts, largest n_frames[b] <= F <= min(ld, 1500) */
+} wca_test_postproc_desc;
+int wca_test_align_postproc(wca_engine* e, const wca_test_postproc_desc* desc);
+/* the first `count` floats of the column norms [B][L*H][F] that the LAST head-statistics launch on the engine's stream left (after
+ * wca_force_align on one utterance: [L*H][F]); reads only, launches nothing */
+int wca_test_last_colnorm(wca_engine* e, int64_t count, float* colnorm_host);
 /* what the LAST wca_decode call left on the device, after a synchronisation of the decode stream (reads only, launches nothing):
  * logits_host [logits_rows][n_vocab] f32 -- the rows of the last forward, [batch] of them, or [2 batch] after a prefill with no_speech
  * (rows [batch, 2 batch): the <|sot|> position's, which the steps behind the prefill leave alone) -- and cache_f16_host, the self-attention

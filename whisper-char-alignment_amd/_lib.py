@@ -73,6 +73,13 @@ class AlignResult(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("jump_frame_host", "sel_idx_host", "token_logprob_host", "end_row_host", "score_host")]
 
 
+class PostprocDesc(C.Structure):
+    """wca_test_postproc_desc of include/wca.h"""
+    _fields_ = ([(n, C.c_void_p) for n in ("qk_dev", "n_tok_host", "n_frames_host", "open_end_host")] + [("opts", C.POINTER(AlignOpts))] +
+                [(n, C.c_void_p) for n in ("scores_host", "colnorm_host", "rowstats_host", "sel_idx_host", "matrix_host", "jump_host")] +
+                [(n, C.c_int32) for n in ("B", "L", "H", "n_tok_max", "ld", "n_frames_max")])
+
+
 class GemmDesc(C.Structure):
     """wca_test_gemm_desc of include/wca.h"""
     _fields_ = ([(n, C.c_void_p) for n in ("a", "w", "bias", "c", "addend", "pos")] +
@@ -156,6 +163,8 @@ SIGNATURES = {
     "wca_test_set_attn_split_drop": (_i, [_i]),
     "wca_test_set_switch": (_i, [C.c_char_p, _i]),
     "wca_test_last_scores": (_i, [_vp, _i, _pf]),
+    "wca_test_align_postproc": (_i, [_vp, C.POINTER(PostprocDesc)]),
+    "wca_test_last_colnorm": (_i, [_vp, _i64, _pf]),
     "wca_test_decode_state": (_i, [_vp, _i, _i, _i, _pf, _vp]),
     "wca_test_gemm_pairs": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "wca_test_attention": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),

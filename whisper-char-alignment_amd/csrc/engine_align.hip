@@ -5,27 +5,18 @@
 
 using namespace wca;
 
-namespace {
-
-int check_medfilt(int width) {
+int wca::check_medfilt(int width) {
   if (width < 1 || !(width & 1) || width > 33) return fail(WCA_ERR_INVALID, "median filter width %d must be odd and in [1, 33]", width);
   return WCA_OK;
 }
 
-// attention maps [L][H][n][F] handed in by the caller
-int check_maps(int L, int H, int n, int F) {
-  if (L < 1 || H < 1 || n < 1 || n > MAX_TOK) return fail(WCA_ERR_INVALID, "bad shape L=%d H=%d n=%d", L, H, n);
-  if (F < 1 || F > N_CTX) return fail(WCA_ERR_TOO_LONG, "F=%d outside [1,%d]", F, N_CTX);
-  return WCA_OK;
-}
-
-int check_aggregation(const wca_align_opts* o) {
+int wca::check_aggregation(const wca_align_opts* o) {
   if (o->aggregation != WCA_AGGR_MEAN && o->aggregation != WCA_AGGR_TOPK) return fail(WCA_ERR_INVALID, "aggregation %d", o->aggregation);
   if (o->aggregation == WCA_AGGR_TOPK && o->topk < 1) return fail(WCA_ERR_INVALID, "topk must be > 0 (timing.py:92)");
   return WCA_OK;
 }
 
-int validate_lengths(int B, int n_tok_max, const int32_t* n_tok, const int32_t* max_frames, int* Fmax_out) {
+int wca::validate_lengths(int B, int n_tok_max, const int32_t* n_tok, const int32_t* max_frames, int* Fmax_out) {
   if (n_tok_max > MAX_TOK) return fail(WCA_ERR_TOO_LONG, "n_tok %d > %d", n_tok_max, MAX_TOK);
   if (n_tok_max < 1) return fail(WCA_ERR_INVALID, "n_tok %d < 1", n_tok_max);
   int Fmax = 0;
@@ -39,18 +30,29 @@ int validate_lengths(int B, int n_tok_max, const int32_t* n_tok, const int32_t* 
   return WCA_OK;
 }
 
+namespace {
+
+// attention maps [L][H][n][F] handed in by the caller
+int check_maps(int L, int H, int n, int F) {
+  if (L < 1 || H < 1 || n < 1 || n > MAX_TOK) return fail(WCA_ERR_INVALID, "bad shape L=%d H=%d n=%d", L, H, n);
+  if (F < 1 || F > N_CTX) return fail(WCA_ERR_TOO_LONG, "F=%d outside [1,%d]", F, N_CTX);
+  return WCA_OK;
+}
+
 // a cross-K/V slot no queued batch (wca_encode_batch / wca_decode / an un-fetched alignment) still needs
 int kv_slot_or_fail(wca_engine* e, int* slot) {
   *slot = take_kv_slot(e);
   return *slot < 0 ? fail(WCA_ERR_STATE, "both cross-K/V slots hold live batches: fetch or consume one first") : WCA_OK;
 }
 
+}  // namespace
+
 // One head_stats launch on s over qk [B][LH][n_max][ld]: captured logits, or (input_is_weights) softmaxed maps, of which utterance b's
 // n_tok[b] x n_frames[b] corner counts. Column norms go to e->colnorm and scores to e->scores; want_rowstats keeps the per-row (max, sum)
 // in e->wws for a later re-materialisation, weights_out takes the dense maps [B][LH][n_max][Fmax]. *h: what was launched.
-int run_head_stats(wca_engine* e, hipStream_t s, HeadStatsArgs* h, const float* qk, int ld, bool input_is_weights, float* weights_out,
-                   bool want_rowstats, const int* n_tok_dev, const int* n_frames_dev, int n_max, int Fmax, int LH, int B, int medfilt_width,
-                   float qk_scale, float w_col, float w_row, float w_cov) {
+int wca::run_head_stats(wca_engine* e, hipStream_t s, HeadStatsArgs* h, const float* qk, int ld, bool input_is_weights, float* weights_out,
+                        bool want_rowstats, const int* n_tok_dev, const int* n_frames_dev, int n_max, int Fmax, int LH, int B, int medfilt_width,
+                        float qk_scale, float w_col, float w_row, float w_cov) {
   HIPCHK(e->colnorm.ensure(sizeof(float) * (size_t)B * LH * Fmax));
   HIPCHK(e->scores.ensure(sizeof(float) * (size_t)B * LH));
   if (want_rowstats) HIPCHK(e->wws.ensure(sizeof(float) * (size_t)B * LH * n_max * 2));
@@ -79,6 +81,8 @@ int run_head_stats(wca_engine* e, hipStream_t s, HeadStatsArgs* h, const float* 
   HIPCHK(launch_head_stats(*h, s));
   return WCA_OK;
 }
+
+namespace {
 
 // One DTW launch on s over P problems (matrix + p * m_bs, rows ld apart): N_dev[p] x M_dev[p] each, within N_max x M_max, or (both null) all
 // N_max x M_max. Trace, path and path length go to e->trace / e->path / e->pathlen; jump_ld > 0 also asks for the jump frames in e->jump, rows
@@ -141,11 +145,13 @@ int read_path(wca_engine* e, int N, int M, int32_t* text_idx_host, int32_t* time
   return WCA_OK;
 }
 
+}  // namespace
+
 // top-k / aggregate / DTW on s behind the head statistics h of run_head_stats: on the dense maps h read (input_is_weights), or re-derived
 // from the captured logits and row statistics h kept. The jump frames land in e->jump [B][n_tok_max]. open_dev: run_dtw's per-utterance
 // open-end flags (end rows and scores in e->dtw_out; -1 / NaN where no DTW ran).
-int run_select_aggregate_dtw(wca_engine* e, hipStream_t s, const HeadStatsArgs& h, const int* dtwN_dev, const wca_align_opts* o, int L_layers,
-                             const int* open_dev = nullptr) {
+int wca::run_select_aggregate_dtw(wca_engine* e, hipStream_t s, const HeadStatsArgs& h, const int* dtwN_dev, const wca_align_opts* o,
+                                  int L_layers, const int* open_dev) {
   const int B = h.B, LH = h.LH, n_max = h.n_tok_max, Fmax = h.n_frames_max;
   const int k = o->aggregation == WCA_AGGR_TOPK ? o->topk : 0;
   if (o->aggregation == WCA_AGGR_TOPK) {
@@ -200,6 +206,8 @@ int run_select_aggregate_dtw(wca_engine* e, hipStream_t s, const HeadStatsArgs& 
   }
   return WCA_OK;
 }
+
+namespace {
 
 // The pinned results slot of one enqueued batch, in ints: jump frames [batch][n_tok_max], top-k heads [batch][max(k, 1)], two flag words
 // (phase 2's, and the one phase 1 raised for the batch's cross-K/V slot), then (token log-probs only) the log-probs [batch][n_tok_max] as f32,

@@ -322,6 +322,17 @@ int mel_to_tm(wca_engine* e, const float* mel_dev, int batch);
 int run_phase1(wca_engine* e, const float* mel_dev, const float* pcm_dev, int64_t pcm_stride, const int* n_samples_dev, int batch, int slot,
                bool skip_last_v = false);
 
+// ---- engine_align.hip: the argument checks and the two halves of phase 2's post-processing that wca_align_batch_enqueue, the step-by-step
+// entry points and the test hook wca_test_align_postproc (engine_test.hip) share
+int check_medfilt(int width);
+int check_aggregation(const wca_align_opts* o);
+int validate_lengths(int B, int n_tok_max, const int32_t* n_tok, const int32_t* max_frames, int* Fmax_out);
+int run_head_stats(wca_engine* e, hipStream_t s, HeadStatsArgs* h, const float* qk, int ld, bool input_is_weights, float* weights_out,
+                   bool want_rowstats, const int* n_tok_dev, const int* n_frames_dev, int n_max, int Fmax, int LH, int B, int medfilt_width,
+                   float qk_scale, float w_col, float w_row, float w_cov);
+int run_select_aggregate_dtw(wca_engine* e, hipStream_t s, const HeadStatsArgs& h, const int* dtwN_dev, const wca_align_opts* o, int L_layers,
+                             const int* open_dev = nullptr);
+
 // ---- engine_audio.hip
 int check_pcm_lengths(const int32_t* n_samples_host, int batch, int64_t pcm_stride);
 int run_logmel(wca_engine* e, const float* pcm_dev, int64_t pcm_stride, const int* n_samples_dev, int B, float* mel_out, bool want_tm);

@@ -308,6 +308,60 @@ int wca_test_last_scores(wca_engine* e, int batch, float* scores_host) {
   return WCA_OK;
 }
 
+int wca_test_align_postproc(wca_engine* e, const wca_test_postproc_desc* d) {
+  if (!e || !d || !d->qk_dev || !d->n_tok_host || !d->n_frames_host || !d->opts) return fail(WCA_ERR_INVALID, "null argument");
+  const wca_align_opts* o = d->opts;
+  const int B = d->B, LH = d->L * d->H, n_max = d->n_tok_max, F = d->n_frames_max;
+  if (B < 1 || B > e->max_batch) return fail(WCA_ERR_INVALID, "batch %d outside [1,%d]", B, e->max_batch);
+  if (d->L < 1 || d->H < 1 || LH > 8192) return fail(WCA_ERR_INVALID, "bad shape L=%d H=%d", d->L, d->H);
+  if (o->sot_len < 0) return fail(WCA_ERR_INVALID, "sot_len %d < 0", o->sot_len);
+  WCA_TRY(check_aggregation(o));
+  WCA_TRY(check_medfilt(o->medfilt_width));
+  int Fmax = 0;
+  WCA_TRY(validate_lengths(B, n_max, d->n_tok_host, d->n_frames_host, &Fmax));
+  if (F > N_CTX) return fail(WCA_ERR_TOO_LONG, "n_frames_max=%d > %d", F, N_CTX);
+  if (F < Fmax || d->ld < F) return fail(WCA_ERR_INVALID, "need the largest n_frames %d <= n_frames_max %d <= ld %d", Fmax, F, d->ld);
+  WCA_TRY(enter(e));
+  std::vector<int32_t> dn(B), flags(B);
+  for (int b = 0; b < B; ++b) {
+    dn[b] = std::max(0, d->n_tok_host[b] - o->sot_len - 1);
+    flags[b] = d->open_end_host && d->open_end_host[b] ? 1 : 0;
+  }
+  int* rows[4];
+  int* open_rows[4] = {nullptr, nullptr, nullptr, nullptr};
+  WCA_TRY(stage_meta(e, B, nullptr, d->n_tok_host, d->n_frames_host, dn.data(), rows));
+  if (d->open_end_host) WCA_TRY(stage_meta(e, B, flags.data(), nullptr, nullptr, nullptr, open_rows));
+  hipStream_t s = e->stream;
+  HeadStatsArgs h;
+  WCA_TRY(run_head_stats(e, s, &h, d->qk_dev, d->ld, false, nullptr, true, rows[1], rows[2], n_max, F, LH, B, o->medfilt_width, o->qk_scale,
+                         o->w_colnorm, o->w_rownorm, o->w_coverage));
+  WCA_TRY(run_select_aggregate_dtw(e, s, h, rows[3], o, d->L, open_rows[0]));
+  const bool topk = o->aggregation == WCA_AGGR_TOPK;
+  const size_t BLH = (size_t)B * LH;
+  if (d->scores_host) HIPCHK(hipMemcpyAsync(d->scores_host, e->scores.p, sizeof(float) * BLH, hipMemcpyDeviceToHost, s));
+  if (d->colnorm_host) HIPCHK(hipMemcpyAsync(d->colnorm_host, e->colnorm.p, sizeof(float) * BLH * F, hipMemcpyDeviceToHost, s));
+  if (d->rowstats_host) HIPCHK(hipMemcpyAsync(d->rowstats_host, e->wws.p, sizeof(float) * BLH * n_max * 2, hipMemcpyDeviceToHost, s));
+  if (d->sel_idx_host && topk) HIPCHK(hipMemcpyAsync(d->sel_idx_host, e->sel.p, sizeof(int) * (size_t)B * o->topk, hipMemcpyDeviceToHost, s));
+  if (d->matrix_host) HIPCHK(hipMemcpyAsync(d->matrix_host, e->matrix.p, sizeof(float) * (size_t)B * n_max * F, hipMemcpyDeviceToHost, s));
+  if (d->jump_host) {
+    if (n_max - o->sot_len - 1 >= 1)   // (otherwise no DTW ran and nothing wrote e->jump: the rows are 0 by definition)
+      HIPCHK(hipMemcpyAsync(d->jump_host, e->jump.p, sizeof(int) * (size_t)B * n_max, hipMemcpyDeviceToHost, s));
+    else
+      memset(d->jump_host, 0, sizeof(int) * (size_t)B * n_max);
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  return WCA_OK;
+}
+
+int wca_test_last_colnorm(wca_engine* e, int64_t count, float* colnorm_host) {
+  if (!e || !colnorm_host) return fail(WCA_ERR_INVALID, "null argument");
+  if (count < 1 || (size_t)count * sizeof(float) > e->colnorm.bytes) return fail(WCA_ERR_INVALID, "%lld column norms are not held", (long long)count);
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipMemcpy(colnorm_host, e->colnorm.p, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost));
+  return WCA_OK;
+}
+
 int wca_test_decode_state(wca_engine* e, int batch, int T_max, int logits_rows, float* logits_host, void* cache_f16_host) {
   if (!e || !logits_host || !cache_f16_host) return fail(WCA_ERR_INVALID, "null argument");
   const wca_model_dims& D = e->dims;

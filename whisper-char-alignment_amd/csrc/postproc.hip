@@ -162,7 +162,9 @@ __global__ __launch_bounds__(256) void head_stats_kernel(HeadStatsArgs a) {
         v[i] = (f < F) ? expf(v[i] - mx) : 0.f;
         sum += v[i];
       }
-      sum = wave_sum(sum);
+      // the rotating adds of wave_sum pair the 16 lanes of a row differently in every lane: the lanes hold sums that differ in the last bits.
+      // The row has ONE sum, lane 0's: the one stored below, which the aggregation's re-materialisation divides by
+      sum = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(wave_sum(sum))));
       if (a.rowstats && lane == 0) {
         float* rsp = a.rowstats + (((long)b * a.LH + head) * a.n_tok_max + t) * 2;
         rsp[0] = mx;
@@ -459,7 +461,7 @@ __global__ __launch_bounds__(256) void head_stats_fast_kernel(HeadStatsArgs a) {
       sum += s2[j].x;
       sum += s2[j].y;
     }
-    sum = wave_sum_folded(sum);
+    sum = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(wave_sum_folded(sum))));   // lane 0's, as in head_stats_kernel
     if (rsp && lane == 0) {
       rsp[2 * t] = mx;
       rsp[2 * t + 1] = sum;
@@ -576,8 +578,11 @@ __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ sco
   }
 }
 
-// value of the filtered + softmaxed map of head `hd` at (t, f), recomputed from the captured logits exactly as
-// head_stats_kernel computed it (same median, same expf(v - max) / sum), so both paths give identical bits
+// value of the filtered + softmaxed map of head `hd` at (t, f), recomputed from the captured logits exactly as both head-statistics
+// kernels computed it: the same median (a median is one of its inputs), the product with the scale ROUNDED to fp32 before the row maximum
+// is subtracted (the kernels take the maximum of the rounded products; a fused multiply-subtract would feed expf the unrounded product,
+// off by up to half an ulp of it -- 1.2e-4 in the exponent at a product of 3700), libm's expf and the IEEE division by the row's one
+// sum. Identical bits: tests/test_postproc_gpu.py holds the aggregated matrix to the step-by-step API's, which reads the dense maps.
 __device__ __forceinline__ float remat_weight(const AggregateArgs& a, int b, int hd, int t, int f, int F) {
   const float* row = a.qk + (long)b * a.qk_bs + (long)hd * a.qk_hs + (long)t * a.qk_ld;
   const float* rs = a.rowstats + (((long)b * a.LH + hd) * a.n_tok_max + t) * 2;
@@ -595,7 +600,9 @@ __device__ __forceinline__ float remat_weight(const AggregateArgs& a, int b, int
     }
     med = (w == 3) ? median_w<3>(win) : (w == 5) ? median_w<5>(win) : (w == 7) ? median_w<7>(win) : median_generic(win, w);
   }
-  return expf(med * a.qk_scale - rs[0]) / rs[1];
+  float prod = med * a.qk_scale;
+  asm("" : "+v"(prod));  // no contraction of this product into the subtraction below
+  return expf(prod - rs[0]) / rs[1];
 }
 
 __global__ __launch_bounds__(256) void aggregate_kernel(AggregateArgs a) {

@@ -677,6 +677,30 @@ class WhisperAMD:
         from . import decoding
         return decoding.decode(self, mel, options if options is not None else decoding.DecodingOptions())
 
+    def align_postproc(self, qk, n_tok, n_frames, opts, L, H, n_frames_max=None, open_end=None):
+        """C ABI wca_test_align_postproc (tests): phase 2's post-processing of align_batch on given logits qk [B, L*H, n_tok_max, ld] f32
+        cuda. Returns a dict of numpy arrays: scores [B,LH], colnorm [B,LH,F], rowstats [B,LH,n_tok_max,2], sel [B,topk] (None for
+        'mean'), matrix [B,n_tok_max,F], jump [B,n_tok_max]; F = n_frames_max (default: the largest n_frames). Only utterance b's own
+        corner of an array is defined."""
+        qk = qk.to(self.device, torch.float32).contiguous()
+        B, LH, n_max, ld = qk.shape
+        if LH != L * H:
+            raise ValueError("qk holds %d heads, not %d x %d" % (LH, L, H))
+        F = int(n_frames_max) if n_frames_max is not None else max(int(v) for v in n_frames)
+        k = opts.topk if opts.aggregation == _lib.AGGR_TOPK else 0
+        out = {"scores": np.zeros((B, LH), np.float32), "colnorm": np.zeros((B, LH, max(F, 1)), np.float32),
+               "rowstats": np.zeros((B, LH, n_max, 2), np.float32), "sel": np.zeros((B, k), np.int32) if k > 0 else None,
+               "matrix": np.zeros((B, n_max, max(F, 1)), np.float32), "jump": np.zeros((B, n_max), np.int32)}
+        nt, nf = _lib.i32_array(n_tok), _lib.i32_array(n_frames)
+        oe = _lib.i32_array([bool(v) for v in open_end]) if open_end is not None else None
+        self._bind_stream()
+        d = _lib.PostprocDesc(qk_dev=_ptr(qk), n_tok_host=_ptr(nt), n_frames_host=_ptr(nf), open_end_host=_ptr(oe), opts=C.pointer(opts),
+                              scores_host=_ptr(out["scores"]), colnorm_host=_ptr(out["colnorm"]), rowstats_host=_ptr(out["rowstats"]),
+                              sel_idx_host=_ptr(out["sel"]), matrix_host=_ptr(out["matrix"]), jump_host=_ptr(out["jump"]),
+                              B=B, L=L, H=H, n_tok_max=n_max, ld=ld, n_frames_max=F)
+        _lib.check(self._lib.wca_test_align_postproc(self._h, C.byref(d)))
+        return out
+
     def fetch(self, B, n_max, opts, with_token_logprobs=False, with_end_rows=False):
         """Results of the oldest enqueued align_batch: (jump, sel), or (jump, sel, token_logprobs [B,n_max] f32) with
         with_token_logprobs (the batch must have been enqueued with token_logprobs_vocab_end). with_end_rows (the batch must have been
