@@ -8,6 +8,10 @@ of this tree: a refactor of the decode path runs this in the tree before and in 
     tokens, n_tokens, sum_logprob, no_speech_prob
   * the same ragged rows with a temperature (0 / 0.4 / 1.0 cycling) and a seed (100 + b) per row, from the input and again with
     redecode=True on the state that decode left
+  * grouped decodes (decode_group: wca_decode_group) of the first four of those rows, beside each of the above: beam search with 1, 3 and 5
+    beams (20 rows, the engine's limit) and with 3 beams and max_candidates 6; 1 and 4 independent samples per audio, and the 4 again
+    with redecode=True; a beam decode of three audios and the align_batch(pcm=None) that takes the state it left. Per case the results,
+    n_out, the beam trace, and from decode_state the logits rows and the cache slots the call defines
   * align_batch of a ragged batch of 3 in both precision modes: plain, with teacher-token log-probs, and with open-end rows
     (True, False, True) plus log-probs; each in one call and as enqueue_only=True then fetch
   * get_attentions weights and logits of a ragged batch of 3 in both precision modes (the teacher-forced decoder)
@@ -35,6 +39,20 @@ tok = tokenizer.get_tokenizer(True, language="en", task="transcribe")
 def save(name, arrays, keys=("tokens", "n_tokens", "sum_logprob", "no_speech_prob")):
     for key, a in zip(keys, arrays):
         np.save(os.path.join(out_dir, "%s.%s.npy" % (name, key)), a.cpu().numpy() if isinstance(a, torch.Tensor) else a)
+
+
+def save_group(name, out, rows, G, beam=False):
+    """The results of a decode_group, the beam's trace, and what it left on the device: the logits rows and, of the cache, the slots the call
+    defines. Row (b, g) has fed its n_initial tokens and one position per choice after the first, so slots [0, n_initial + choices - 1),
+    clamped where a row past its budget stays at slot T_max - 2; the rest of the cache is uninitialised memory."""
+    save(name, out + (m.last_no_speech_prob,), keys=("tokens", "n_tokens", "sum_logprob", "n_out", "no_speech_prob"))
+    if beam:
+        save(name, (m.beam_trace(),), keys=("trace",))
+    n_init, T_max, steps = [len(r) for r in rows[0]], out[0].shape[2], m.last_decode_positions()[1] + 1
+    logits, cache = m.decode_state(len(n_init) * G, T_max)
+    for r in range(len(n_init) * G):
+        cache[:, :, r, min(n_init[r // G] + steps - 1, T_max - 1):] = 0
+    save(name, (logits, cache), keys=("logits", "cache"))
 
 
 def initial(n):
@@ -97,6 +115,21 @@ for precision in ("f16", "reference"):
         out = m.decode_rows_sampled(None, None, None, [p[0] for p in plans], [p[1] for p in plans], budgets, sup, blank, batch=B, redecode=True,
                                     **skw)
         save("sampled.redecode.%s" % tag, out + (m.last_no_speech_prob,))
+        # grouped decodes of the first four audios (3, 11, 34 and 105 initial tokens, budgets 10, 9, 8, 7: the stop test runs at choices 4, 8)
+        grows = ([p[0] for p in plans[:4]], [p[1] for p in plans[:4]], budgets[:4], sup, blank)
+        for G, MC in ((1, None), (3, None), (5, None), (3, 6)):
+            out = m.decode_group(mel[:4], None, None, *grows, n_group=G, mode=0, max_candidates=MC, **kw)
+            save_group("beam.g%d%s.%s" % (G, ".mc%d" % MC if MC else "", tag), out, grows, G, beam=True)
+        gkw = dict(mode=1, temperature=[0.0, 0.4, 1.0, 0.4], seed=[100 + b for b in range(4)], **kw)
+        for G in (1, 4):
+            save_group("samples.g%d.%s" % (G, tag), m.decode_group(mel[:4], None, None, *grows, n_group=G, **gkw), grows, G)
+        out = m.decode_group(None, None, None, *grows, n_group=4, batch=4, redecode=True, **gkw)
+        save_group("samples.g4.redecode.%s" % tag, out, grows, 4)
+        # the state a beam decode leaves is the one the alignment takes (transcribe)
+        arows = ([p[0] for p in plans[:3]], [p[1] for p in plans[:3]], budgets[:3], sup, blank)
+        save_group("beam.b3.%s" % tag, m.decode_group(mel[:3], None, None, *arows, n_group=3, mode=0, **kw), arows, 3, beam=True)
+        save("beam.b3.align.%s" % tag, m.align_batch(None, None, att_tokens.cuda(), [len(r) for r in att_rows], [100, 80, 60], align_opts),
+             keys=("jump", "sel"))
     m.set_decode_mode(True)
     # the fused alignment at B = 3: plain, with teacher-token log-probs, with open-end rows; each in one call and as enqueue then fetch
     for name, akw, fkw in (("plain", {}, {}), ("logprobs", dict(token_logprobs_vocab_end=tok.eot), dict(with_token_logprobs=True)),

@@ -289,32 +289,28 @@ def decode(model, mel, options=DecodingOptions(), pcm=None, n_samples=None, enco
         max_init = round(first.max_initial_timestamp / (CHUNK_LENGTH / dims.n_audio_ctx))
     kw = dict(eot=tokenizer.eot, timestamp_begin=tokenizer.timestamp_begin, apply_timestamp_rules=not first.without_timestamps,
               max_initial_timestamp_index=max_init, batch=B, no_speech=tokenizer.no_speech if tokenizer.no_speech is not None else -1)
-    if beam_size is not None or best_of is not None:
+    grouped, sampling = beam_size is not None or best_of is not None, redecode or any(o.temperature != 0.0 for o in rows)
+    if not per_row and (grouped or sampling):   # one DecodingOptions over the batch: row b draws with seed + b
+        rows, plans = [dataclasses.replace(first, seed=None if first.seed is None else int(first.seed) + b) for b in range(B)], plans * B
+    row_arrays = ([p[0] for p in plans], [p[2] for p in plans], [p[1] for p in plans])   # initial tokens, sot_index, sample_len per row
+    sampled = dict(temperature=[float(o.temperature) for o in rows], seed=[int(o.seed or 0) % (1 << 64) for o in rows])
+    if grouped:
         # G decoder rows per audio (wca_decode_group): the beams, or best_of independent samples; then upstream's MaximumLikelihoodRanker
         G = beam_size if beam_size is not None else best_of
         if B * G > getattr(model, "max_batch", B * G):
             raise NotImplementedError("%d audios x %d decoder rows each exceed the engine's max_batch = %d, and a group is not split over "
                                       "several calls: create the engine with more rows" % (B, G, model.max_batch))
-        if not per_row:   # one DecodingOptions over the batch: row b draws with seed + b
-            rows, plans = [dataclasses.replace(first, seed=None if first.seed is None else int(first.seed) + b) for b in range(B)], plans * B
-        sampled = dict(temperature=[float(o.temperature) for o in rows], seed=[int(o.seed or 0) % (1 << 64) for o in rows]) if beam_size is None else {}
-        slots, n_slots, sums, n_out = model.decode_group(mel, pcm, n_samples, [p[0] for p in plans], [p[2] for p in plans], [p[1] for p in plans],
-                                                         sup, blank, redecode=redecode, n_group=G, mode=0 if beam_size is not None else 1,
+        slots, n_slots, sums, n_out = model.decode_group(mel, pcm, n_samples, *row_arrays, sup, blank, redecode=redecode, n_group=G,
+                                                         mode=0 if beam_size is not None else 1,
                                                          max_candidates=max(1, round(G * (first.patience or 1.0))) if beam_size is not None else None,
-                                                         **sampled, **kw)
+                                                         **(sampled if beam_size is None else {}), **kw)
         best = [rank_sequences(sums[b, :n_out[b]], n_slots[b, :n_out[b]] - len(plans[b][0]), first.length_penalty) for b in range(B)]
         tokens = np.stack([slots[b, i] for b, i in enumerate(best)])
         n_tokens, sum_logprobs = [n_slots[b, i] for b, i in enumerate(best)], [sums[b, i] for b, i in enumerate(best)]
-    elif redecode or any(o.temperature != 0.0 for o in rows):
-        if not per_row:   # one DecodingOptions over the batch: row b draws with seed + b
-            rows, plans = [dataclasses.replace(first, seed=None if first.seed is None else int(first.seed) + b) for b in range(B)], plans * B
-        tokens, n_tokens, sum_logprobs = model.decode_rows_sampled(mel, pcm, n_samples, [p[0] for p in plans], [p[2] for p in plans],
-                                                                   [p[1] for p in plans], sup, blank, redecode=redecode,
-                                                                   temperature=[float(o.temperature) for o in rows],
-                                                                   seed=[int(o.seed or 0) % (1 << 64) for o in rows], **kw)
+    elif sampling:
+        tokens, n_tokens, sum_logprobs = model.decode_rows_sampled(mel, pcm, n_samples, *row_arrays, sup, blank, redecode=redecode, **sampled, **kw)
     elif per_row:
-        tokens, n_tokens, sum_logprobs = model.greedy_decode_rows(mel, pcm, n_samples, [p[0] for p in plans], [p[2] for p in plans],
-                                                                  [p[1] for p in plans], sup, blank, **kw)
+        tokens, n_tokens, sum_logprobs = model.greedy_decode_rows(mel, pcm, n_samples, *row_arrays, sup, blank, **kw)
     else:
         initial, sample_len, sot_index = plans[0]
         tokens, n_tokens, sum_logprobs = model.greedy_decode(mel, pcm, n_samples, initial, sup, blank, sample_len=sample_len, sot_index=sot_index,

@@ -144,6 +144,19 @@ def _ptr(t):
     return C.c_void_p(t.ctypes.data if hasattr(t, "ctypes") else C.addressof(t))
 
 
+def _batch_size(mel, pcm, batch):
+    """The rows of a call that takes mel XOR pcm, or neither with batch=B (a state queued by encode_batch or left by the last decode)."""
+    return mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(batch))
+
+
+def _temps_seeds(B, temperature, seed):
+    """One temperature (float >= 0) and one seed (int, taken mod 2^64) per row, as the arrays wca_decode_desc points to."""
+    if temperature is None or seed is None or len(temperature) != B or len(seed) != B:
+        raise ValueError("temperature and seed take one entry per batch row (%d)" % B)
+    return (np.ascontiguousarray([float(t) for t in temperature], dtype=np.float32),
+            np.ascontiguousarray([int(v) % (1 << 64) for v in seed], dtype=np.uint64))
+
+
 class WhisperAMD:
     def __init__(self, dims, device="cuda:0", max_batch=8, _register=True, precision="reference"):
         """precision: 'reference' (default since round 5, like wca_engine_create): the CONTRACT mode -- the reference's fp32 forward
@@ -481,16 +494,18 @@ class WhisperAMD:
         return B
 
     def _decode(self, mel, pcm, n_samples, batch, init, n_init, sot_index, sample_len, opts, suppress_mask, blank_mask, per_row, prefill,
-                temps=None, seeds=None, redecode=False):
-        """What greedy_decode, greedy_decode_rows and decode_rows_sampled share: the masks, the output arrays, the wca_decode_desc around
-        the caller's row arrays (init [n] or [B, n_max], n_init / sot_index / sample_len: one int or one per row), the call, and
-        last_no_speech_prob. Every array the descriptor points to is a local of this frame until the call has returned."""
+                temps=None, seeds=None, redecode=False, group=None):
+        """What the four decode methods share: the masks, the output arrays, the wca_decode_desc around the caller's row arrays (init [n] or
+        [B, n_max], n_init / sot_index / sample_len: one int or one per row), the call, and last_no_speech_prob. group = (n_group, mode,
+        max_candidates, n_slot): wca_decode_group, whose outputs hold n_slot sequences per audio and the [B] counts n_out behind them.
+        Every array a descriptor points to is a local of this frame until the call has returned."""
         self._bind_stream()
-        B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(batch))  # batch=: decode a state queued by encode_batch
+        B = _batch_size(mel, pcm, batch)
         T = max((int(n) + int(sl) for n, sl in zip(n_init, sample_len)), default=1)
-        tokens = np.zeros((B, max(T, 1)), dtype=np.int32)
-        n_tok = np.zeros(B, dtype=np.int32)
-        lp = np.zeros(B, dtype=np.float32)
+        slots = (B,) if group is None else (B, group[3])
+        tokens = np.zeros(slots + (max(T, 1),), dtype=np.int32)
+        n_tok = np.zeros(slots, dtype=np.int32)
+        lp = np.zeros(slots, dtype=np.float32)
         sup = np.ascontiguousarray(suppress_mask, dtype=np.uint8)
         blank = np.ascontiguousarray(blank_mask, dtype=np.uint8) if blank_mask is not None else None
         if sup.shape[0] != self.dims.n_vocab or (blank is not None and blank.shape[0] != self.dims.n_vocab):
@@ -500,15 +515,22 @@ class WhisperAMD:
             mel = mel.contiguous().float()
         ns = _lib.i32_array(n_samples) if n_samples is not None else None
         ni, si, sl = _lib.i32_array(n_init), _lib.i32_array(sot_index), _lib.i32_array(sample_len)
+        out = dict(tokens_out_host=_ptr(tokens), n_tokens_host=_ptr(n_tok), sum_logprob_host=_ptr(lp),
+                   no_speech_prob_host=_ptr(nsp if opts.no_speech >= 0 else None))   # the group descriptor's where there is one
         d = _lib.DecodeDesc(mel_dev=_ptr(mel), pcm_dev=_ptr(pcm), n_samples_host=_ptr(ns), initial_tokens_host=_ptr(init), n_initial_host=_ptr(ni),
                             sot_index_host=_ptr(si), sample_len_host=_ptr(sl), temperature_host=_ptr(temps), seed_host=_ptr(seeds),
-                            suppress_mask_host=_ptr(sup), blank_mask_host=_ptr(blank), opts=C.pointer(opts), tokens_out_host=_ptr(tokens),
-                            n_tokens_host=_ptr(n_tok), sum_logprob_host=_ptr(lp), no_speech_prob_host=_ptr(nsp if opts.no_speech >= 0 else None),
+                            suppress_mask_host=_ptr(sup), blank_mask_host=_ptr(blank), opts=C.pointer(opts),
                             pcm_stride=pcm.shape[1] if pcm is not None else 0, batch=B, per_row=per_row, prefill=int(prefill),
-                            redecode=1 if redecode else 0)
-        _lib.check(self._lib.wca_decode(self._h, C.byref(d)))
+                            redecode=1 if redecode else 0, **({} if group else out))
+        if group is None:
+            _lib.check(self._lib.wca_decode(self._h, C.byref(d)))
+            self.last_no_speech_prob = nsp
+            return tokens, n_tok, lp
+        n_out = np.zeros(B, dtype=np.int32)
+        g = _lib.GroupDesc(n_out_host=_ptr(n_out), n_group=group[0], mode=group[1], max_candidates=group[2], **out)
+        _lib.check(self._lib.wca_decode_group(self._h, C.byref(d), C.byref(g)))
         self.last_no_speech_prob = nsp
-        return tokens, n_tok, lp
+        return tokens, n_tok, lp, n_out
 
     def greedy_decode(self, mel, pcm, n_samples, initial_tokens, suppress_mask, blank_mask, sample_len, eot, timestamp_begin,
                       apply_timestamp_rules=True, max_initial_timestamp_index=50, batch=None, no_speech=-1, sot_index=0, prefill=0):
@@ -542,18 +564,14 @@ class WhisperAMD:
         do not depend on where in the batch it sits. sum_logprobs accumulates the untempered log-probability, as upstream does.
         redecode=True (mel = pcm = None, batch=B): decode again the state the previous decode of these B rows left for
         align_batch(pcm=None), with no encoder pass; the state is still there for the alignment afterwards."""
-        B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(batch))
-        if temperature is None or seed is None or len(temperature) != B or len(seed) != B:
-            raise ValueError("temperature and seed take one entry per batch row (%d)" % B)
-        temps = np.ascontiguousarray([float(t) for t in temperature], dtype=np.float32)
-        seeds = np.ascontiguousarray([int(v) % (1 << 64) for v in seed], dtype=np.uint64)
+        temps, seeds = _temps_seeds(_batch_size(mel, pcm, batch), temperature, seed)
         return self._decode_rows(mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask, blank_mask, eot, timestamp_begin,
                                  apply_timestamp_rules, max_initial_timestamp_index, batch, no_speech, temps, seeds, redecode)
 
     def _decode_rows(self, mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask, blank_mask, eot, timestamp_begin,
-                     apply_timestamp_rules, max_initial_timestamp_index, batch, no_speech, temps=None, seeds=None, redecode=False):
-        """The per-row arrays that greedy_decode_rows and decode_rows_sampled pass."""
-        B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(batch))
+                     apply_timestamp_rules, max_initial_timestamp_index, batch, no_speech, temps=None, seeds=None, redecode=False, group=None):
+        """The per-row arrays that greedy_decode_rows, decode_rows_sampled and decode_group pass."""
+        B = _batch_size(mel, pcm, batch)
         rows = [[int(t) for t in r] for r in initial_tokens]
         if not (len(rows) == len(sot_index) == len(sample_len) == B):
             raise ValueError("initial_tokens, sot_index and sample_len take one entry per batch row (%d)" % B)
@@ -565,7 +583,7 @@ class WhisperAMD:
         opts = _lib.DecodeOpts(max(int(v) for v in sample_len) if B else 0, int(eot), int(timestamp_begin), 1 if apply_timestamp_rules else 0,
                                int(max_initial_timestamp_index), int(no_speech))
         return self._decode(mel, pcm, n_samples, batch, init, n_init, sot_index, sample_len, opts, suppress_mask, blank_mask, 1, 1, temps, seeds,
-                            redecode)
+                            redecode, group)
 
     def decode_group(self, mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask, blank_mask, eot, timestamp_begin,
                      apply_timestamp_rules=True, max_initial_timestamp_index=50, batch=None, no_speech=-1, n_group=1, mode=0, max_candidates=None,
@@ -578,11 +596,6 @@ class WhisperAMD:
         (beam: the finished list in the order it filled, then the live beams that top it up; samples: sample g in slot g), whose sampled
         tokens are tokens[b, i, len(initial_tokens[b]) : n_tokens[b, i]]. The ranking is the caller's (decoding.rank_sequences).
         self.last_no_speech_prob [B] as greedy_decode; the encoder state stays for a following align_batch(pcm=None, ...)."""
-        self._bind_stream()
-        B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(batch))
-        rows = [[int(t) for t in r] for r in initial_tokens]
-        if not (len(rows) == len(sot_index) == len(sample_len) == B):
-            raise ValueError("initial_tokens, sot_index and sample_len take one entry per batch row (%d)" % B)
         G, mode = int(n_group), int(mode)
         if mode not in (0, 1):
             raise ValueError("mode is 0 (beam) or 1 (independent samples)")
@@ -592,39 +605,10 @@ class WhisperAMD:
             raise ValueError("n_group and max_candidates must be at least 1")
         temps = seeds = None
         if temperature is not None or seed is not None:
-            if temperature is None or seed is None or len(temperature) != B or len(seed) != B:
-                raise ValueError("temperature and seed take one entry per batch row (%d)" % B)
-            temps = np.ascontiguousarray([float(t) for t in temperature], dtype=np.float32)
-            seeds = np.ascontiguousarray([int(v) % (1 << 64) for v in seed], dtype=np.uint64)
-        n_init = [len(r) for r in rows]
-        init = np.full((B, max(max(n_init, default=0), 1)), int(eot), dtype=np.int32)
-        for b, r in enumerate(rows):
-            init[b, :len(r)] = r
-        T = max((n + int(sl) for n, sl in zip(n_init, sample_len)), default=1)
-        tokens = np.zeros((B, n_slot, max(T, 1)), dtype=np.int32)
-        n_tok = np.zeros((B, n_slot), dtype=np.int32)
-        lp = np.zeros((B, n_slot), dtype=np.float32)
-        n_out = np.zeros(B, dtype=np.int32)
-        nsp = np.full(B, np.nan, dtype=np.float32)
-        sup = np.ascontiguousarray(suppress_mask, dtype=np.uint8)
-        blank = np.ascontiguousarray(blank_mask, dtype=np.uint8) if blank_mask is not None else None
-        if sup.shape[0] != self.dims.n_vocab or (blank is not None and blank.shape[0] != self.dims.n_vocab):
-            raise ValueError("filter masks must have n_vocab entries")
-        if mel is not None:
-            mel = mel.contiguous().float()
-        opts = _lib.DecodeOpts(max(int(v) for v in sample_len) if B else 0, int(eot), int(timestamp_begin), 1 if apply_timestamp_rules else 0,
-                               int(max_initial_timestamp_index), int(no_speech))
-        ns = _lib.i32_array(n_samples) if n_samples is not None else None
-        ni, si, sl = _lib.i32_array(n_init), _lib.i32_array(sot_index), _lib.i32_array(sample_len)
-        d = _lib.DecodeDesc(mel_dev=_ptr(mel), pcm_dev=_ptr(pcm), n_samples_host=_ptr(ns), initial_tokens_host=_ptr(init), n_initial_host=_ptr(ni),
-                            sot_index_host=_ptr(si), sample_len_host=_ptr(sl), temperature_host=_ptr(temps), seed_host=_ptr(seeds),
-                            suppress_mask_host=_ptr(sup), blank_mask_host=_ptr(blank), opts=C.pointer(opts),
-                            pcm_stride=pcm.shape[1] if pcm is not None else 0, batch=B, per_row=1, prefill=1, redecode=1 if redecode else 0)
-        g = _lib.GroupDesc(tokens_out_host=_ptr(tokens), n_tokens_host=_ptr(n_tok), sum_logprob_host=_ptr(lp), n_out_host=_ptr(n_out),
-                           no_speech_prob_host=_ptr(nsp if opts.no_speech >= 0 else None), n_group=G, mode=mode, max_candidates=max_candidates)
-        _lib.check(self._lib.wca_decode_group(self._h, C.byref(d), C.byref(g)))
-        self.last_no_speech_prob = nsp
-        return tokens, n_tok, lp, n_out
+            temps, seeds = _temps_seeds(_batch_size(mel, pcm, batch), temperature, seed)
+        return self._decode_rows(mel, pcm, n_samples, initial_tokens, sot_index, sample_len, suppress_mask, blank_mask, eot, timestamp_begin,
+                                 apply_timestamp_rules, max_initial_timestamp_index, batch, no_speech, temps, seeds, redecode,
+                                 (G, mode, max_candidates, n_slot))
 
     def beam_trace(self):
         """Test accessor (C ABI wca_test_beam_trace): what the last beam search chose -> [steps, rows, 2] int32, entry (c, r) = (the row
@@ -644,7 +628,7 @@ class WhisperAMD:
             from . import decoding
             return decoding.detect_language(self, mel, tokenizer, pcm=pcm, n_samples=n_samples)
         self._bind_stream()
-        B = mel.shape[0] if mel is not None else (pcm.shape[0] if pcm is not None else int(batch))
+        B = _batch_size(mel, pcm, batch)
         if mel is not None:
             mel = mel.to(self.device).contiguous().float()
         lang = np.zeros(max(B, 1), dtype=np.int32)
