@@ -646,9 +646,13 @@ class WhisperAMD:
         return pre.value, step.value
 
     def decode_state(self, batch, T_max, logits_rows=None):
-        """Test accessor (C ABI wca_test_decode_state): what the last greedy_decode / greedy_decode_rows left on the device ->
-        (logits [logits_rows, n_vocab] f32, cache [n_text_layer, 2, batch, T_max, n_text_state] f16) as numpy arrays. T_max is that call's
-        largest n_initial + sample_len; logits_rows defaults to batch (2 * batch: with the <|sot|> rows of a prefill with no_speech)."""
+        """Test accessor (C ABI wca_test_decode_state): what the last decode (greedy_decode, greedy_decode_rows, decode_rows_sampled or
+        decode_group) left on the device -> (logits [logits_rows, n_vocab] f32, cache [n_text_layer, 2, batch, T_max, n_text_state] f16) as
+        numpy arrays. T_max is that call's largest n_initial + sample_len; logits_rows defaults to batch (2 * batch: with the <|sot|> rows of
+        a prefill with no_speech). After decode_group batch is its B * n_group decoder rows, row b * n_group + g = beam or sample g of audio
+        b: the cache is the half of the two that the last reorder wrote (beam: the rows of the beams after the last choice, slots
+        [0, n_initial + choices - 1); samples: each row's own), the logits are the last step's B * n_group rows (beam: the beams before the
+        last choice), and the rows of an audio past its budget hold, past what they had fed at their last choice, what is never read."""
         rows = int(batch if logits_rows is None else logits_rows)
         logits = np.zeros((max(rows, 1), self.dims.n_vocab), dtype=np.float32)
         cache = np.zeros((self.dims.n_text_layer, 2, max(int(batch), 1), max(int(T_max), 1), self.dims.n_text_state), dtype=np.float16)
