@@ -595,6 +595,38 @@ int wca_test_attention_ex(wca_engine* e, const wca_test_attn_desc* desc);
 int wca_test_gemm_rows(wca_engine* e, const void* a_f16_dev, const float* x_f32_dev, const float* gamma_dev, const float* beta_dev,
                        const void* w_f16_dev, const float* bias_dev, void* c_dev, int M, int N, int K, int gelu, int out_mode, int splitk,
                        int groups, void* kv_k_f16_dev, void* kv_v_f16_dev, int T_max, int kv_t);
+/* wca_test_gemm_rows with every field launch_gemm_rows accepts open to the caller (element strides; base offsets are applied by the caller to
+ * the pointers). a [M] f16 rows lda apart, or, x != NULL, A = LayerNorm(x rows lda32 floats apart; gamma, beta, eps 1e-5); w [N] rows ldw apart;
+ * logical row m of C at c + m * ldc, or, c_rows_per_batch > 0, at c + (m / rows_per_batch) * c_batch_stride + (m % rows_per_batch) * ldc;
+ * out_mode 0 f16 / 1 f32 / 2 f32 accumulate; splitk 0 = chosen, groups 0 = chosen; kv_k / kv_v != NULL (out_mode 0, N = 3 d): columns [d, 3d)
+ * of row m go to the caches [M][kv_tmax][d] at position kv_t, or, kv_t_rows != NULL (device [M] int32), at kv_t_rows[m] clamped to
+ * [0, kv_tmax). The split-K workspace is the engine's scratch; after a split launch the arrival counters must be back at zero
+ * (WCA_ERR_HIP otherwise). A launch the launcher refuses is WCA_ERR_INVALID and writes nothing. Returns after the launch has finished. */
+typedef struct wca_test_gemm_rows_desc {
+  const void* a;              /* nullable when x is given */
+  const float* x;             /* nullable */
+  const float* gamma;
+  const float* beta;
+  const void* w;
+  const float* bias;          /* nullable */
+  void* c;
+  void* kv_k;                 /* nullable */
+  void* kv_v;
+  const int32_t* kv_t_rows;   /* nullable */
+  int64_t c_batch_stride;
+  int32_t M, N, K;
+  int32_t lda, lda32, ldw, ldc;
+  int32_t c_rows_per_batch;
+  int32_t gelu, out_mode, splitk, groups;
+  int32_t kv_tmax, kv_t;
+} wca_test_gemm_rows_desc;
+int wca_test_gemm_rows_ex(wca_engine* e, const wca_test_gemm_rows_desc* desc);
+/* Which path the engine of a model n_text_state wide gives a decoder GEMM C [M][N] = A [M][K] W^T (csrc/gemm_plan.cpp, plan_dec_gemm, the
+ * decision of dec_gemm with the few-row kernel enabled): no engine, no GPU, no HIP call. layernorm != 0: A is LayerNorm of the f32 rows;
+ * kv_append != 0: the QKV projection of a decode step. out[8] = {few_row (0: the separate LayerNorm / GEMM / kv_append launches, and zeros
+ * up to the capacity), splitk, column groups per workgroup, grid x, grid y, dynamic LDS bytes, split-K workspace bytes of the launch,
+ * bytes of the engine's split-K workspace}. */
+int wca_test_dec_gemm_plan(int n_text_state, int M, int N, int K, int layernorm, int kv_append, int64_t* out);
 /* diagnostic, process-wide (the product never calls it; 0 = the contract's three passes per product): leave single MFMA passes out of the
  * encoder's pair attention -- bit 0 K_lo Q_hi, bit 1 K_hi Q_lo, bit 2 V_lo P_hi, bit 3 V_hi P_lo; masks 0, 1, 2, 3, 4, 8, 9, 12, 15 exist.
  * tools/precision_ablation.py --attn-drop: the product-level ablation of timing.py:58's fp32 attention. */

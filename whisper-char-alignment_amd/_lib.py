@@ -88,6 +88,14 @@ class GemmDesc(C.Structure):
                                           "gelu", "out_mode", "force_tile", "site", "cu_limit", "supertile")])
 
 
+class GemmRowsDesc(C.Structure):
+    """wca_test_gemm_rows_desc of include/wca.h"""
+    _fields_ = ([(n, C.c_void_p) for n in ("a", "x", "gamma", "beta", "w", "bias", "c", "kv_k", "kv_v", "kv_t_rows")] +
+                [("c_batch_stride", C.c_int64)] +
+                [(n, C.c_int32) for n in ("M", "N", "K", "lda", "lda32", "ldw", "ldc", "c_rows_per_batch", "gelu", "out_mode", "splitk", "groups",
+                                          "kv_tmax", "kv_t")])
+
+
 class AttnDesc(C.Structure):
     """wca_test_attn_desc of include/wca.h"""
     _fields_ = ([(n, C.c_void_p) for n in ("q", "k", "v", "o", "cap", "nk_rows")] +
@@ -188,6 +196,8 @@ SIGNATURES = {
     "wca_collate_plan": (_i, [C.POINTER(_i64), C.POINTER(_i64), _i, C.POINTER(_i64)]),
     "wca_probe_strict_tp": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, C.c_double, _vp]),
     "wca_test_gemm_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i]),
+    "wca_test_gemm_rows_ex": (_i, [_vp, C.POINTER(GemmRowsDesc)]),
+    "wca_test_dec_gemm_plan": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_i64)]),
 }
 
 _lib = None

@@ -67,10 +67,10 @@ static size_t layout_arena(wca_engine* e, char* base) {
     e->ln_cnt = carve<unsigned>(cur, mpad / 256 + 16, 256);
   }
   {
-    // few-row GEMM, split-K (K > 1024: fc2; every K of the 1280-wide model): up to ROWS_MAX rows, N = n_text_state columns
-    const int s_max = std::max(std::max(gemm_rows_pick_splitk((int)dt), gemm_rows_pick_splitk((int)(4 * dt))), 1);
-    e->sk_tiles = (size_t)(DEC_ROWS_MAX / 64) * ((dt + 15) / 16);
-    e->sk_floats = e->sk_tiles * s_max * 64 * 16;
+    // few-row GEMM, split-K workspace (dec_sk_capacity, gemm_plan.cpp)
+    const DecSkCapacity sk = dec_sk_capacity((int)dt);
+    e->sk_tiles = sk.tiles;
+    e->sk_floats = sk.floats;
     e->sk_part = carve<float>(cur, e->sk_floats);
     e->sk_cnt = carve<unsigned>(cur, e->sk_tiles + 16, 256);
     // 128 x 128 tile GEMM with at most n_cu / 2 = 128 tiles, 4 K slices of f32 partials

@@ -60,13 +60,11 @@ void mark_site(wca_engine* e, hipStream_t s, int site, int li, int which) {
 int dec_gemm(wca_engine* e, hipStream_t s, Gemm g, half_t* xn_scratch = nullptr) {
   const bool ln = g.A32 != nullptr;
   const int M = g.M, N = g.N, K = g.K, T_max = g.kv_tmax;
-  const int sk = gemm_rows_pick_splitk(K);
-  const bool fits = sk <= 1 || (g.kv_k == nullptr && (size_t)((M + 63) / 64) * ((N + 15) / 16) <= e->sk_tiles &&
-                                gemm_rows_workspace_bytes(M, N, sk) <= e->sk_floats * sizeof(float));
-  if (e->dec_fused && M <= DEC_ROWS_MAX && gemm_rows_supported(M, N, K, ln) && fits) {
+  const DecGemmPlan plan = plan_dec_gemm(M, N, K, ln, g.kv_k != nullptr, DecSkCapacity{e->sk_tiles, e->sk_floats});
+  if (e->dec_fused && plan.few_row) {
     g.lda32 = K;
     g.ln_eps = 1e-5f;
-    g.splitk = sk;
+    g.splitk = plan.splitk;
     g.sk_part = e->sk_part;
     g.sk_cnt = e->sk_cnt;
     g.kv_bs = (long)T_max * K;

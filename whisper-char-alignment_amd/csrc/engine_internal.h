@@ -30,7 +30,6 @@ int fail(int code, const char* fmt, ...);   // records the message of wca_last_e
 
 constexpr int N_FRAMES = 3000, N_CTX = 1500, MAX_TOK = 448, N_BIN = 201, N_FFT = 400;
 constexpr int META_SLOTS = 16;
-constexpr int DEC_ROWS_MAX = 128;  // decoder GEMMs on at most this many rows take the few-row kernel (gemm_rows.hip)
 
 #define WCA_TRY(expr)          \
   do {                         \

@@ -166,6 +166,17 @@ int wca_test_gemm_plan(int M, int N, int K, int lda, int out_mode, int gelu, int
   return WCA_OK;
 }
 
+int wca_test_dec_gemm_plan(int n_text_state, int M, int N, int K, int layernorm, int kv_append, int64_t* out) {
+  if (!out) return fail(WCA_ERR_INVALID, "null argument");
+  if (n_text_state < 1 || M < 1 || N < 1 || K < 1) return fail(WCA_ERR_INVALID, "bad shape n_text_state=%d M=%d N=%d K=%d", n_text_state, M, N, K);
+  const DecSkCapacity cap = dec_sk_capacity(n_text_state);
+  const DecGemmPlan p = plan_dec_gemm(M, N, K, layernorm != 0, kv_append != 0, cap);
+  const int64_t v[8] = {p.few_row ? 1 : 0,    p.splitk,          p.groups, (int64_t)p.grid_x, (int64_t)p.grid_y, (int64_t)p.lds,
+                        (int64_t)p.ws_bytes, (int64_t)(cap.floats * sizeof(float))};
+  memcpy(out, v, sizeof(v));
+  return WCA_OK;
+}
+
 int wca_test_gemm_ex(wca_engine* e, const wca_test_gemm_desc* d, int32_t* plan_out) {
   if (!e || !d || !plan_out || !d->a || !d->w || !d->c) return fail(WCA_ERR_INVALID, "null argument");
   GemmArgs g = flat((const half_t*)d->a, d->lda, (const half_t*)d->w, d->ldw, d->c, d->ldc, d->M, d->N, d->K);
@@ -242,8 +253,36 @@ int wca_test_attention_ex(wca_engine* e, const wca_test_attn_desc* d) {
 int wca_test_gemm_rows(wca_engine* e, const void* a_f16, const float* x_f32, const float* gamma, const float* beta, const void* w,
                        const float* bias, void* c, int M, int N, int K, int gelu, int out_mode, int splitk, int groups, void* kv_k, void* kv_v,
                        int T_max, int kv_t) {
-  if (!e || !w || !c || (!a_f16 && !x_f32) || (x_f32 && (!gamma || !beta))) return fail(WCA_ERR_INVALID, "null argument");
+  wca_test_gemm_rows_desc d{};
+  d.a = a_f16;
+  d.x = x_f32;
+  d.gamma = gamma;
+  d.beta = beta;
+  d.w = w;
+  d.bias = bias;
+  d.c = c;
+  d.kv_k = kv_k;
+  d.kv_v = kv_v;
+  d.M = M;
+  d.N = N;
+  d.K = K;
+  d.lda = d.lda32 = d.ldw = K;
+  d.ldc = N;
+  d.gelu = gelu;
+  d.out_mode = out_mode;
+  d.splitk = splitk;
+  d.groups = groups;
+  d.kv_tmax = T_max;
+  d.kv_t = kv_t;
+  return wca_test_gemm_rows_ex(e, &d);
+}
+
+int wca_test_gemm_rows_ex(wca_engine* e, const wca_test_gemm_rows_desc* d) {
+  if (!e || !d || !d->w || !d->c || (!d->a && !d->x) || (d->x && (!d->gamma || !d->beta))) return fail(WCA_ERR_INVALID, "null argument");
+  const int M = d->M, N = d->N, K = d->K;
+  if (M < 1 || N < 1 || K < 1) return fail(WCA_ERR_INVALID, "bad shape M=%d N=%d K=%d", M, N, K);
   HIPCHK(hipSetDevice(e->device));
+  int splitk = d->splitk;
   if (splitk <= 0) splitk = gemm_rows_pick_splitk(K);
   if (splitk <= 0) return fail(WCA_ERR_INVALID, "no split of K=%d fits the few-row kernel", K);
   const size_t tiles = (size_t)((M + 63) / 64) * ((N + 15) / 16);
@@ -252,25 +291,38 @@ int wca_test_gemm_rows(wca_engine* e, const void* a_f16, const float* x_f32, con
     HIPCHK(e->tmp1.ensure(sizeof(unsigned) * tiles));
     HIPCHK(hipMemsetAsync(e->tmp1.p, 0, sizeof(unsigned) * tiles, e->stream));
   }
-  GemmArgs g = flat((const half_t*)a_f16, K, (const half_t*)w, K, c, N, M, N, K);
-  g.A32 = x_f32;
-  g.lda32 = K;
-  g.ln_gamma = gamma;
-  g.ln_beta = beta;
+  GemmArgs g = flat((const half_t*)d->a, d->lda, (const half_t*)d->w, d->ldw, d->c, d->ldc, M, N, K);
+  g.c_rows_per_batch = d->c_rows_per_batch;
+  g.c_batch_stride = (long)d->c_batch_stride;
+  g.A32 = d->x;
+  g.lda32 = d->lda32;
+  g.ln_gamma = d->gamma;
+  g.ln_beta = d->beta;
   g.ln_eps = 1e-5f;
-  g.bias = bias;
-  g.gelu = gelu;
-  g.out_mode = out_mode;
+  g.bias = d->bias;
+  g.gelu = d->gelu;
+  g.out_mode = d->out_mode;
   g.splitk = splitk;
-  g.groups = groups;
+  g.groups = d->groups;
   g.sk_part = (float*)e->tmp0.p;
   g.sk_cnt = (unsigned*)e->tmp1.p;
-  g.kv_k = (half_t*)kv_k;
-  g.kv_v = (half_t*)kv_v;
-  g.kv_bs = (long)T_max * (N / 3);
-  g.kv_t = kv_t;
-  g.kv_d = kv_k ? N / 3 : 0;
-  HIPCHK(launch_gemm_rows(g, e->stream));
+  g.kv_k = (half_t*)d->kv_k;
+  g.kv_v = (half_t*)d->kv_v;
+  g.kv_bs = (long)d->kv_tmax * (N / 3);
+  g.kv_t = d->kv_t;
+  g.kv_d = d->kv_k ? N / 3 : 0;
+  g.kv_t_rows = d->kv_t_rows;
+  g.kv_tmax = d->kv_tmax;
+  // the launcher trusts kv_t and the strides of C (the engine derives them): an entry point for tests checks what would leave the buffers
+  if (d->kv_k && !d->kv_t_rows && (d->kv_t < 0 || d->kv_t >= d->kv_tmax)) return fail(WCA_ERR_INVALID, "kv_t %d outside [0,%d)", d->kv_t, d->kv_tmax);
+  if (d->ldc < (d->kv_k ? N / 3 : N) || (d->c_rows_per_batch > 0 && d->c_batch_stride < (int64_t)d->c_rows_per_batch * d->ldc))
+    return fail(WCA_ERR_INVALID, "rows of C overlap (ldc %d, c_batch_stride %lld)", d->ldc, (long long)d->c_batch_stride);
+  const hipError_t he = launch_gemm_rows(g, e->stream);
+  if (he == hipErrorInvalidValue) {
+    (void)hipGetLastError();
+    return fail(WCA_ERR_INVALID, "the few-row GEMM's launcher refused M=%d N=%d K=%d splitk %d out_mode %d", M, N, K, splitk, d->out_mode);
+  }
+  HIPCHK(he);
   if (splitk > 1) {
     // the counters must be back at zero (self-cleaning): a second launch on the same workspace has to give the same result
     std::vector<unsigned> cnt(tiles);

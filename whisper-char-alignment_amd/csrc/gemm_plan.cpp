@@ -1,5 +1,8 @@
 // Which kernel a GEMM gets, and with what grid: plan_gemm, the host arithmetic of launch_gemm (gemm.hip) without a HIP call, so that the
-// callers that depend on the outcome ask instead of predicting it, and a CPU test can pin it (wca_test_gemm_plan).
+// callers that depend on the outcome ask instead of predicting it, and a CPU test can pin it (wca_test_gemm_plan). plan_dec_gemm is the same for
+// the decoder's choice between the few-row kernel and the separate launches (dec_gemm; wca_test_dec_gemm_plan).
+#include <algorithm>
+
 #include "kernels.h"
 
 namespace wca {
@@ -116,6 +119,34 @@ GemmPlan plan_gemm(const GemmArgs& a, int n_cu) {
   } else if (!gelu_ok && !(a.out_mode == 2 && !a.gelu)) {
     return refuse("out_mode is not 0 - 4, or out_mode 2 with GELU");
   }
+  return p;
+}
+
+// few-row GEMM, split-K (K > 1024: fc2; every K of the 1280-wide model): up to DEC_ROWS_MAX rows, N = n_text_state columns
+DecSkCapacity dec_sk_capacity(int n_text_state) {
+  const int s_max = std::max(std::max(gemm_rows_pick_splitk(n_text_state), gemm_rows_pick_splitk(4 * n_text_state)), 1);
+  DecSkCapacity c{};
+  c.tiles = (size_t)(DEC_ROWS_MAX / 64) * (((size_t)n_text_state + 15) / 16);
+  c.floats = c.tiles * s_max * 64 * 16;
+  return c;
+}
+
+DecGemmPlan plan_dec_gemm(int M, int N, int K, bool layernorm_a, bool kv_append, const DecSkCapacity& cap) {
+  DecGemmPlan p{};
+  const int sk = gemm_rows_pick_splitk(K);
+  const bool fits = sk <= 1 || (!kv_append && (size_t)((M + 63) / 64) * ((N + 15) / 16) <= cap.tiles &&
+                                gemm_rows_workspace_bytes(M, N, sk) <= cap.floats * sizeof(float));
+  if (!(M <= DEC_ROWS_MAX && gemm_rows_supported(M, N, K, layernorm_a) && fits)) return p;
+  p.few_row = true;
+  p.splitk = sk;
+  // the grid and the LDS that launch_gemm_rows (gemm_rows.hip) gives this split with groups = 0: 64-row blocks, 16-column groups, an f16 image
+  // of 64 rows of K / splitk + 8 halfs, the four quarter accumulators of four m-tiles, one flag word
+  const int NG = (N + 15) / 16;
+  p.groups = sk > 1 ? 1 : (NG + 255) / 256;
+  p.grid_x = (unsigned)(((NG + p.groups - 1) / p.groups) * sk);
+  p.grid_y = (unsigned)((M + 63) / 64);
+  p.lds = (size_t)64 * (K / sk + 8) * sizeof(half_t) + 4 * 4 * 4 * 64 * sizeof(float) + 16;
+  p.ws_bytes = gemm_rows_workspace_bytes(M, N, sk);
   return p;
 }
 

@@ -114,6 +114,22 @@ hipError_t launch_gemm_rows(const GemmArgs& a, hipStream_t s);
 bool gemm_rows_supported(int M, int N, int K, bool layernorm_a);
 int gemm_rows_pick_splitk(int K);
 size_t gemm_rows_workspace_bytes(int M, int N, int splitk);
+// Which path a decoder GEMM on M rows takes (engine_forward.hip dec_gemm), decided on the host without a HIP call (gemm_plan.cpp;
+// wca_test_dec_gemm_plan pins it on the CPU): the few-row kernel for M <= DEC_ROWS_MAX rows of a shape it takes whose split-K workspace
+// fits the engine's (a split-K launch takes no KV append), otherwise the separate LayerNorm / GEMM / kv_append launches.
+constexpr int DEC_ROWS_MAX = 128;
+struct DecSkCapacity {
+  size_t tiles, floats;    // arrival counters and f32 partials of the engine's few-row split-K workspace
+};
+DecSkCapacity dec_sk_capacity(int n_text_state);
+struct DecGemmPlan {
+  bool few_row;
+  int splitk, groups;      // what launch_gemm_rows runs with (groups as it chooses them); 0 where few_row is false, as everything below
+  unsigned grid_x, grid_y;
+  size_t lds;              // dynamic LDS of the launch
+  size_t ws_bytes;         // split-K partials of the launch
+};
+DecGemmPlan plan_dec_gemm(int M, int N, int K, bool layernorm_a, bool kv_append, const DecSkCapacity& cap);
 
 // ---------------------------------------------------------------- attention (attention.hip)
 // Flash-style multi-head attention with head_dim == 64 (every Whisper size).
