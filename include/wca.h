@@ -552,8 +552,9 @@ int wca_test_gemm_plan(int M, int N, int K, int lda, int out_mode, int gelu, int
  * a capped persistent grid). Logical row m = b * rows_per_batch + t of A / C lives at base + b * batch_stride + t * ld (rows_per_batch 0: flat,
  * m * ld); a_lo > 0: A rows are [hi | lo] pairs a_lo elements apart against the plain W; c_lo: out_mode 4's distance from hi to lo;
  * addend [M][ld_addend] f32 is added before the GELU, pos [pos_period][N] f32 after it (row m takes pos[m % pos_period]); force_tile 0 / 64 /
- * 128 / 256 / 257 / 258 and out_mode 0 / 1 / 2 / 4 as wca_test_gemm_plan. plan_out[2] = {kernel (numbered as in wca_test_gemm_plan), grid x} of
- * the launch. A launch the plan refuses is WCA_ERR_INVALID with the plan's reason and writes nothing. Asynchronous on the engine's stream. */
+ * 128 / 256 / 257 / 258 and out_mode 0 / 1 / 2 / 3 / 4 as wca_test_gemm_plan. plan_out[2] = {kernel (numbered as in wca_test_gemm_plan), grid x} of
+ * the launch. A launch the plan refuses is WCA_ERR_INVALID with the plan's reason and writes nothing. Asynchronous on the engine's stream
+ * (out_mode 3 waits for the launch). */
 typedef struct wca_test_gemm_desc {
   const void* a;
   const void* w;
@@ -567,6 +568,12 @@ typedef struct wca_test_gemm_desc {
   int32_t a_rows_per_batch, c_rows_per_batch;
   int32_t ld_addend, pos_period;
   int32_t gelu, out_mode, force_tile, site, cu_limit, supertile;
+  /* out_mode 3 (c is then x, f32 [M][ldc], read-modify-write): ln_out f16 rows ln_ld apart = LayerNorm(x; ln_gamma, ln_beta, eps 1e-5). The call
+   * supplies the statistics workspace and the zeroed error word, waits for the launch and reports a statistics hand-off that timed out. */
+  const float* ln_gamma;
+  const float* ln_beta;
+  void* ln_out;
+  int32_t ln_ld;
 } wca_test_gemm_desc;
 int wca_test_gemm_ex(wca_engine* e, const wca_test_gemm_desc* desc, int32_t* plan_out);
 /* wca_test_attention / _split / _rows with every stride open to the caller (element strides; head h of a row at column h * 64; base offsets are

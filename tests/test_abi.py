@@ -137,6 +137,10 @@ def test_switch_table_reads_no_environment_and_rejects_removed_names(wca):
     for args in ((None, None), (None, ctypes.byref(ad))):
         assert lib.wca_test_set_switch(b"no_such_switch", 1) < 0 and b"null" not in lib.wca_last_error()
         assert lib.wca_test_attention_ex(*args) < 0 and b"null" in lib.wca_last_error()
+    header = open(os.path.join(ROOT, "include", "wca.h")).read()
+    body = re.search(r"typedef struct wca_test_gemm_desc \{([^{}]*)\} wca_test_gemm_desc;", header, flags=re.S).group(1)
+    names = [n for decl in re.findall(r"([\w ,*]+);", re.sub(r"/\*.*?\*/", "", body, flags=re.S)) for n in re.findall(r"(\w+)\s*(?:,|$)", decl)]
+    assert names == [f[0] for f in wca._lib.GemmDesc._fields_] and names[-4:] == ["ln_gamma", "ln_beta", "ln_out", "ln_ld"]
     rd = wca._lib.GemmRowsDesc()
     for args in ((None, None), (None, ctypes.byref(rd))):
         assert lib.wca_test_set_switch(b"no_such_switch", 1) < 0 and b"null" not in lib.wca_last_error()
@@ -145,8 +149,9 @@ def test_switch_table_reads_no_environment_and_rejects_removed_names(wca):
     slots = (ctypes.c_int64 * 8)(*([-1] * 8))
     assert lib.wca_test_dec_gemm_plan(1024, 1, 1024, 1024, 0, 0, None) < 0 and b"null" in lib.wca_last_error()
     assert lib.wca_test_dec_gemm_plan(1024, 0, 1024, 1024, 0, 0, slots) < 0 and b"bad shape" in lib.wca_last_error() and list(slots) == [-1] * 8
-    # the descriptions mirror the header's structs: 6 pointers, then the 64-bit strides, then the 32-bit fields
-    assert ctypes.sizeof(gd) == 6 * 8 + 4 * 8 + 16 * 4 and ctypes.sizeof(ad) == 6 * 8 + 10 * 8 + 13 * 4 + 4
+    # the descriptions mirror the header's structs: 6 pointers, then the 64-bit strides, then the 32-bit fields (the GEMM's: then the three
+    # LayerNorm pointers of out_mode 3 and ln_ld, padded to the pointers' alignment)
+    assert ctypes.sizeof(gd) == 6 * 8 + 4 * 8 + 16 * 4 + 3 * 8 + 4 + 4 and ctypes.sizeof(ad) == 6 * 8 + 10 * 8 + 13 * 4 + 4
     assert ctypes.sizeof(rd) == 10 * 8 + 8 + 14 * 4
     # the library reads no environment variable on a launch path or in the switch table: the remaining getenv calls are one-time initialisers
     for f in ("gemm.hip", "attention.hip", "attention_split.hip", "postproc.hip", "elementwise.hip", "gemm_rows.hip", "dtw.hip", "logmel.hip", "decode.hip",

@@ -85,7 +85,8 @@ class GemmDesc(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("a", "w", "bias", "c", "addend", "pos")] +
                 [(n, C.c_int64) for n in ("a_batch_stride", "c_batch_stride", "a_lo", "c_lo")] +
                 [(n, C.c_int32) for n in ("M", "N", "K", "lda", "ldw", "ldc", "a_rows_per_batch", "c_rows_per_batch", "ld_addend", "pos_period",
-                                          "gelu", "out_mode", "force_tile", "site", "cu_limit", "supertile")])
+                                          "gelu", "out_mode", "force_tile", "site", "cu_limit", "supertile")] +
+                [(n, C.c_void_p) for n in ("ln_gamma", "ln_beta", "ln_out")] + [("ln_ld", C.c_int32)])
 
 
 class GemmRowsDesc(C.Structure):

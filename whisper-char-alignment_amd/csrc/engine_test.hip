@@ -106,29 +106,23 @@ int wca_test_gemm_pairs(wca_engine* e, const void* a2, const void* w, const floa
 int wca_test_gemm_ln(wca_engine* e, const void* a, const void* w, const float* bias, float* x, const float* gamma, const float* beta,
                      void* xn, int M, int N, int K, int site) {
   if (!e || !a || !w || !x || !gamma || !beta || !xn) return fail(WCA_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(e->device));
-  const size_t mpad = align_up((size_t)M, 256);
-  HIPCHK(e->tmp0.ensure(sizeof(unsigned long long) * (size_t)(N / 256) * mpad));
-  HIPCHK(e->tmp1.ensure(sizeof(unsigned) * (mpad / 256 + 16)));
-  HIPCHK(hipMemsetAsync(e->err_dev, 0, sizeof(int), e->stream));
-  GemmArgs g = flat((const half_t*)a, K, (const half_t*)w, K, x, N, M, N, K);
-  g.bias = bias;
-  g.out_mode = 3;
-  g.site = site;
-  g.ln_gamma = gamma;
-  g.ln_beta = beta;
-  g.ln_out = (half_t*)xn;
-  g.ln_ld = N;
-  g.ln_eps = 1e-5f;
-  g.ln_stats = (unsigned long long*)e->tmp0.p;
-  g.ln_cnt = (unsigned*)e->tmp1.p;
-  g.ln_err = e->err_dev;
-  if (plan_gemm(g, e->n_cu).kernel != GemmKernel::Persist256LN) return fail(WCA_ERR_INVALID, "residual + LayerNorm epilogue not available for M=%d N=%d K=%d", M, N, K);
-  HIPCHK(launch_gemm(g, e->stream));
-  HIPCHK(hipMemcpyAsync(e->err_host, e->err_dev, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  if (e->err_host[0] & 2) return fail(WCA_ERR_HIP, "LayerNorm statistics hand-off timed out");
-  return WCA_OK;
+  wca_test_gemm_desc d{};
+  d.a = a;
+  d.w = w;
+  d.bias = bias;
+  d.c = x;
+  d.M = M;
+  d.N = N;
+  d.K = K;
+  d.lda = d.ldw = K;
+  d.ldc = d.ln_ld = N;
+  d.out_mode = 3;
+  d.site = site;
+  d.ln_gamma = gamma;
+  d.ln_beta = beta;
+  d.ln_out = xn;
+  int32_t plan[2];
+  return wca_test_gemm_ex(e, &d, plan);
 }
 
 int wca_test_gemm_plan(int M, int N, int K, int lda, int out_mode, int gelu, int a_lo, int force_tile, int site, int n_cu, int cu_limit, int flags,
@@ -201,12 +195,37 @@ int wca_test_gemm_ex(wca_engine* e, const wca_test_gemm_desc* d, int32_t* plan_o
   g.sk_bytes = e->sk_big_bytes;
   if (g.pos != nullptr && g.pos_period <= 0) return fail(WCA_ERR_INVALID, "a positional table needs pos_period > 0");
   if (g.addend != nullptr && g.ld_addend < g.N) return fail(WCA_ERR_INVALID, "ld_addend < N");
+  const bool ln = g.out_mode == 3;
+  if (ln) {
+    // residual + LayerNorm epilogue: the statistics workspace of the engine's scratch buffers and its error word
+    if (!d->ln_gamma || !d->ln_beta || !d->ln_out) return fail(WCA_ERR_INVALID, "null argument");
+    if (g.M <= 0 || g.N <= 0) return fail(WCA_ERR_INVALID, "residual + LayerNorm epilogue not available for M=%d N=%d K=%d", g.M, g.N, g.K);
+    HIPCHK(hipSetDevice(e->device));
+    const size_t mpad = align_up((size_t)g.M, 256);
+    HIPCHK(e->tmp0.ensure(sizeof(unsigned long long) * (size_t)((g.N + 255) / 256) * mpad));
+    HIPCHK(e->tmp1.ensure(sizeof(unsigned) * (mpad / 256 + 16)));
+    g.ln_gamma = d->ln_gamma;
+    g.ln_beta = d->ln_beta;
+    g.ln_out = (half_t*)d->ln_out;
+    g.ln_ld = d->ln_ld;
+    g.ln_eps = 1e-5f;
+    g.ln_stats = (unsigned long long*)e->tmp0.p;
+    g.ln_cnt = (unsigned*)e->tmp1.p;
+    g.ln_err = e->err_dev;
+  }
   const GemmPlan p = plan_gemm(g, e->n_cu);
   if (p.refused) return fail(WCA_ERR_INVALID, "GEMM refused: %s", p.refused);
+  if (ln && p.kernel != GemmKernel::Persist256LN) return fail(WCA_ERR_INVALID, "residual + LayerNorm epilogue not available for M=%d N=%d K=%d", g.M, g.N, g.K);
   plan_out[0] = (int32_t)p.kernel;
   plan_out[1] = (int32_t)p.grid_x;
   HIPCHK(hipSetDevice(e->device));
+  if (ln) HIPCHK(hipMemsetAsync(e->err_dev, 0, sizeof(int), e->stream));
   HIPCHK(launch_gemm(g, e->stream));
+  if (ln) {
+    HIPCHK(hipMemcpyAsync(e->err_host, e->err_dev, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->err_host[0] & 2) return fail(WCA_ERR_HIP, "LayerNorm statistics hand-off timed out");
+  }
   return WCA_OK;
 }
 
