@@ -489,6 +489,12 @@ def _dtw_cases():
     for i in range(50):
         diag[i, i * 8:(i + 1) * 8] = 0.5
     cases.append(("diagonal", diag))
+    # the closed instantiations R = 5, 6, 8 (N in 257 .. 384 and 449 .. 512), each at its first and last N, on the column counts around a
+    # 16-column block and a long one: random costs, and small integers where most cells tie
+    for N in (257, 320, 321, 384, 449, 512):
+        for M in (15, 16, 17, 100):
+            cases.append(("rand%dx%d" % (N, M), rng.random((N, M), dtype=np.float32)))
+            cases.append(("ints%dx%d" % (N, M), rng.integers(0, 3, size=(N, M)).astype(np.float32)))
     return cases
 
 
