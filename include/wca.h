@@ -275,6 +275,19 @@ int wca_dtw_batch_dev_open(wca_engine* e, const float* matrix_dev, int P, int N,
                            const int32_t* n_cols_host, const int32_t* open_end_host, int32_t* jump_frame_host, int32_t* end_row_host,
                            float* score_host);
 
+/* wca_dtw_batch_dev_open plus the per-row score of each path (a null open_end_host: every problem is closed). For text row i of problem p,
+ * path_cells_host[p][i] is the number of cells of the backtraced path in that row and path_mean_host[p][i] the mean of matrix[p][i][j]
+ * (NOT negated) over them, added in f64 and rounded once to f32. Within a row the path only moves along the frame axis, so the cells are
+ * the frames jump[i] .. last[i]: last = n_cols[p] - 1 for the end row, otherwise jump[i+1] where the path enters row i + 1 vertically (that
+ * frame then counts in both rows) and jump[i+1] - 1 where it enters diagonally. Rows the path does not reach (past an open end row, or
+ * beyond n_rows[p]) are (0, 0.0). Both outputs are [P][N] like jump_frame_host; the jump frames and end rows are wca_dtw_batch_dev_open's.
+ * The score is computed by a kernel of its own behind the DTW; the bits do not depend on P or on a problem's position. Limits as wca_dtw;
+ * unlike wca_dtw_batch_dev_open this call also takes an EMPTY problem (n_rows[p] or n_cols[p] = 0): no DTW runs for it, its end row is -1,
+ * its jump frames, cells and means are 0. */
+int wca_dtw_path_scores(wca_engine* e, const float* matrix_dev, int P, int N, int M, const int32_t* n_rows_host, const int32_t* n_cols_host,
+                        const int32_t* open_end_host, int32_t* jump_frame_host, int32_t* end_row_host, float* path_mean_host,
+                        int32_t* path_cells_host);
+
 /* probe_oracle.py:83-90: one alignment PER HEAD (aggregation "mean" on a single head = column
  * normalisation only), all L*H DTWs in one launch. ws_dev [L][H][n][F]; scores_host [L*H] = the
  * filter_attention scores (w_col = w_row = 1); jump_frame_host [L*H][n - sot_len - 1]. */
@@ -309,6 +322,8 @@ typedef struct {
                                        go through the final LayerNorm, the vocabulary projection (tok_emb rows [0, vocab_end)) and a
                                        log-sum-exp kernel on the engine's second stream; the [rows][vocab] logits never reach the host. The
                                        jump frames and top-k heads are the same with and without them.                                   */
+  int32_t path_scores;              /* != 0: also run the path-score kernel (wca_dtw_path_scores) behind the DTW, on the aggregated matrix
+                                       the DTW was given; read with wca_align_batch_path_scores before the fetch. 0: nothing changes.     */
 } wca_align_desc;
 
 typedef struct {
@@ -333,6 +348,11 @@ typedef struct {
 int wca_align_batch_enqueue(wca_engine* e, const wca_align_desc* d);
 int wca_align_batch_fetch(wca_engine* e, int batch, int n_tok_max, int topk, const wca_align_result* r);
 int wca_align_batch(wca_engine* e, const wca_align_desc* d, const wca_align_result* r);
+/* The path scores of the OLDEST pending batch, which must have been enqueued with path_scores != 0 (WCA_ERR_STATE otherwise, or when nothing
+ * is pending): waits for that batch like the fetch, copies path_mean_host / path_cells_host [batch][n_tok_max] -- laid out like
+ * jump_frame_host: entry i of row b belongs to DTW row i, 0 beyond the DTW's rows -- and does NOT consume the batch: the
+ * wca_align_batch_fetch that follows does. */
+int wca_align_batch_path_scores(wca_engine* e, int batch, int n_tok_max, float* path_mean_host, int32_t* path_cells_host);
 
 /* The filter fields of whisper.DecodingOptions as the reference uses it (infer_ali.py:40: language="en", everything else default:
  * task transcribe, suppress_blank, suppress_tokens "-1", without_timestamps False, max_initial_timestamp 1.0). */
@@ -671,6 +691,9 @@ typedef struct {
   int32_t B, L, H, n_tok_max, ld, n_frames_max;   /* n_frames_max: F of the output layouts, largest n_frames[b] <= F <= min(ld, 1500) */
 } wca_test_postproc_desc;
 int wca_test_align_postproc(wca_engine* e, const wca_test_postproc_desc* desc);
+/* wca_test_align_postproc with the path-score kernel behind the DTW, as wca_align_desc.path_scores asks for it (the same function of the
+ * fused path): path_mean_host / path_cells_host [B][n_tok_max], laid out like jump_host, both required. */
+int wca_test_align_postproc_scores(wca_engine* e, const wca_test_postproc_desc* desc, float* path_mean_host, int32_t* path_cells_host);
 /* the first `count` floats of the column norms [B][L*H][F] that the LAST head-statistics launch on the engine's stream left (after
  * wca_force_align on one utterance: [L*H][F]); reads only, launches nothing */
 int wca_test_last_colnorm(wca_engine* e, int64_t count, float* colnorm_host);

@@ -65,7 +65,7 @@ class AlignDesc(C.Structure):
     """wca_align_desc of include/wca.h"""
     _fields_ = ([(n, C.c_void_p) for n in ("pcm_dev", "n_samples_host", "tokens_dev", "n_tok_host", "max_frames_host")] +
                 [("opts", C.POINTER(AlignOpts)), ("open_end_host", C.c_void_p), ("pcm_stride", C.c_int64)] +
-                [(n, C.c_int32) for n in ("n_tok_max", "batch", "vocab_end")])
+                [(n, C.c_int32) for n in ("n_tok_max", "batch", "vocab_end", "path_scores")])
 
 
 class AlignResult(C.Structure):
@@ -146,10 +146,12 @@ SIGNATURES = {
     "wca_dtw_batch_dev": (_i, [_vp, _vp, _i, _i, _i, _pi32]),
     "wca_dtw_open": (_i, [_vp, _pf, _i, _i, _pi32, _pi32, _pi32, _pi32, _pf]),
     "wca_dtw_batch_dev_open": (_i, [_vp, _vp, _i, _i, _i, _pi32, _pi32, _pi32, _pi32, _pi32, _pf]),
+    "wca_dtw_path_scores": (_i, [_vp, _vp, _i, _i, _i, _pi32, _pi32, _pi32, _pi32, _pi32, _pf, _pi32]),
     "wca_probe_heads": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _pf, _pi32]),
     "wca_align_batch": (_i, [_vp, C.POINTER(AlignDesc), C.POINTER(AlignResult)]),
     "wca_align_batch_enqueue": (_i, [_vp, C.POINTER(AlignDesc)]),
     "wca_align_batch_fetch": (_i, [_vp, _i, _i, _i, C.POINTER(AlignResult)]),
+    "wca_align_batch_path_scores": (_i, [_vp, _i, _i, _pf, _pi32]),
     "wca_token_logprobs": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "wca_encode_batch": (_i, [_vp, _vp, _vp, _i64, _pi32, _i]),
     "wca_decode": (_i, [_vp, C.POINTER(DecodeDesc)]),
@@ -173,6 +175,7 @@ SIGNATURES = {
     "wca_test_set_switch": (_i, [C.c_char_p, _i]),
     "wca_test_last_scores": (_i, [_vp, _i, _pf]),
     "wca_test_align_postproc": (_i, [_vp, C.POINTER(PostprocDesc)]),
+    "wca_test_align_postproc_scores": (_i, [_vp, C.POINTER(PostprocDesc), _pf, _pi32]),
     "wca_test_last_colnorm": (_i, [_vp, _i64, _pf]),
     "wca_test_decode_state": (_i, [_vp, _i, _i, _i, _pf, _vp]),
     "wca_test_gemm_pairs": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),

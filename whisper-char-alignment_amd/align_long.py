@@ -39,6 +39,11 @@ The loop's rules
     "unaligned_words": k, "windows_without_words": n}. Times are absolute seconds, seek * 0.01 + frame * 0.02. Words left over when the
     audio ends carry start = end = None and are counted in "unaligned_words". `score` (cost per path cell at the end row) is a
     diagnostic: no decision reads it.
+  * word_scores=True (off by default; without it no result gains a key): every window's align_batch also runs the path-score kernel, and
+    every word carries "score": the mean of the aggregated attention matrix over the cells of the window's DTW path in the word's unit
+    rows (timing.word_alignment_scores on the window that committed it; in [0, 1], uncalibrated; None for an unaligned word). Every window
+    entry carries "mean_word_score": the mean of the scores of the words it committed, None where it committed none. No decision reads
+    either.
 
 Limits: 448 framed tokens and 1500 encoder frames per window (the engine's), so at most 446 - len(sot_sequence) units per window; no
 per-word confidence, no silence or music detection, no fallback to ASR for a window that fails, one GPU.
@@ -70,7 +75,8 @@ class AlignState:
     n_frames: frames of the recording's log-mel (its own plus the 3000 of padding); word_starts: index of every word's first unit in the
     transcript's unit sequence, then the number of units (n_words + 1 entries); words: the n_words strings; sot_len = len(sot_sequence)."""
 
-    def __init__(self, n_frames, word_starts, words, sot_len, max_length=MAX_LENGTH):
+    def __init__(self, n_frames, word_starts, words, sot_len, max_length=MAX_LENGTH, word_scores=False):
+        self.word_scores = bool(word_scores)   # receive() is given the window's path scores: words carry "score", windows "mean_word_score"
         self.content_frames = int(n_frames) - N_FRAMES
         self.word_starts = [int(v) for v in word_starts]
         self.word_text = list(words)
@@ -109,10 +115,30 @@ class AlignState:
         """The offered run [w0, w1) as a slice of the transcript's units."""
         return self.word_starts[w0], self.word_starts[w1]
 
-    def receive(self, jump_frames, end_row, score=None, times=None):
+    def _attach_scores(self, window, n_before, rows, path):
+        """The words receive() just committed (self.words[n_before:], the first offered words of the window, in order) get their "score":
+        the cell-weighted mean of path = (path_mean, path_cells) over the word's rows, as timing.word_alignment_scores forms it."""
+        if not self.word_scores:
+            return window
+        if path is None:
+            raise ValueError("an AlignState with word_scores=True needs every window's path scores")
+        mean = np.asarray(path[0][:rows[-1] + 1], dtype=np.float64)
+        cells = np.asarray(path[1][:rows[-1] + 1], dtype=np.float64)
+        got = []
+        for k, w in enumerate(self.words[n_before:]):
+            c = cells[rows[k]:rows[k + 1]].sum()
+            w["score"] = float((mean[rows[k]:rows[k + 1]] * cells[rows[k]:rows[k + 1]]).sum() / c) if c > 0 else float("nan")
+            got.append(w["score"])
+        live = [s for s in got if s == s]
+        window["mean_word_score"] = float(np.mean(live)) if live else None
+        return window
+
+    def receive(self, jump_frames, end_row, score=None, times=None, path=None):
         """jump_frames[r]: the encoder frame at which the window's DTW path enters row r (row r = unit r of the offered run, row n_units
         = eot); end_row: the path's last row. times (closed windows only): (starts, ends) in window seconds as words_from_jump_frames
-        gives them for the offered run, else they are formed here the same way."""
+        gives them for the offered run, else they are formed here the same way. path (word_scores only): the window's (path_mean,
+        path_cells) rows."""
+        n_before = len(self.words)
         seek, size, w0, w1, closed = self.request()
         max_frames = size // INPUT_STRIDE
         base = self.word_starts[w0]
@@ -131,7 +157,7 @@ class AlignState:
                 self.words.append({"word": self.word_text[k], "start": offset + float(times[0][k - w0]), "end": offset + float(times[1][k - w0])})
             window["committed"] = w1 - w0
             self.cursor, self.seek = w1, self.content_frames
-            return window
+            return self._attach_scores(window, n_before, rows, path)
         complete = 0
         while complete < w1 - w0 and rows[complete + 1] - 1 <= end_row:
             complete += 1
@@ -142,13 +168,13 @@ class AlignState:
             window["committed"] = w1 - w0
             self.cursor = w1
             self.seek += INPUT_STRIDE * int(jump[rows[-1]])
-            return window
+            return self._attach_scores(window, n_before, rows, path)
         advance = INPUT_STRIDE * int(jump[rows[complete - 1]]) if complete >= 2 else 0
         if advance <= 0:   # silence, or a window that could not be aligned: nothing is committed and the cursor stays
             self.without_words += 1
             self.seek += size
             self._skip_sliver()
-            return window
+            return self._attach_scores(window, n_before, rows, path)
         for k in range(complete - 1):   # every complete word but the last, which the window edge may have cut
             end = int(jump[rows[k + 1]]) if rows[k + 1] <= end_row else max_frames
             self.words.append({"word": self.word_text[w0 + k], "start": offset + int(jump[rows[k]]) / TOKENS_PER_SECOND,
@@ -157,12 +183,13 @@ class AlignState:
         self.cursor = w0 + complete - 1
         self.seek += advance
         self._skip_sliver()
-        return window
+        return self._attach_scores(window, n_before, rows, path)
 
     def result(self):
         words = list(self.words)
         left = self.n_words - self.cursor
-        words.extend({"word": self.word_text[k], "start": None, "end": None} for k in range(self.cursor, self.n_words))
+        extra = {"score": None} if self.word_scores else {}
+        words.extend({"word": self.word_text[k], "start": None, "end": None, **extra} for k in range(self.cursor, self.n_words))
         return {"words": words, "windows": self.windows, "unaligned_words": left, "windows_without_words": self.without_words}
 
 
@@ -201,29 +228,33 @@ def transcript_units(text, tokenizer, aligned_unit_type="char"):
 def align_group_rows(model, tokenizer, opts, aligned_unit_type, mels, units, states, live, requests):
     """align_loop's align_rows for one group of recordings, once all but `live` and `requests` are bound: mels, units and states are the
     group's long log-mels, transcript units and AlignStates, by position in the group. A round is ONE encode_batch of the live rows'
-    windows and ONE align_batch, whose rows may mix open and closed windows."""
+    windows and ONE align_batch, whose rows may mix open and closed windows (with path_scores where the states ask for word scores)."""
     from .timing import words_from_jump_frames
     windows = cut_windows(model, mels, [(i, seek, size) for i, (seek, size, _w0, _w1, _c) in zip(live, requests)])
     runs = [units[i][slice(*states[i].unit_span(w0, w1))] for i, (_s, _z, w0, w1, _c) in zip(live, requests)]
     rows = [[*tokenizer.sot_sequence, tokenizer.no_timestamps, *run, tokenizer.eot] for run in runs]
     model.encode_batch(mel=windows)
-    jump, _sel, end_rows, scores = model.align_batch(None, None, pad_token_rows(rows, tokenizer.eot).to(model.device), [len(r) for r in rows],
-                                                     [size // INPUT_STRIDE for _s, size, _w0, _w1, _c in requests], opts,
-                                                     open_end=[not closed for _s, _z, _w0, _w1, closed in requests])
+    want_scores = any(states[i].word_scores for i in live)
+    res = model.align_batch(None, None, pad_token_rows(rows, tokenizer.eot).to(model.device), [len(r) for r in rows],
+                            [size // INPUT_STRIDE for _s, size, _w0, _w1, _c in requests], opts,
+                            open_end=[not closed for _s, _z, _w0, _w1, closed in requests], **({"path_scores": True} if want_scores else {}))
+    jump, _sel, end_rows, scores = res[:4]
     outs = []
     for b, (run, req) in enumerate(zip(runs, requests)):
         # a closed window: today's DTW and words_from_jump_frames, unchanged -- its (starts, ends)
         times = words_from_jump_frames(jump[b], run, tokenizer, aligned_unit_type, want_words=False)[1:] if req[4] else None
-        outs.append((jump[b], end_rows[b], scores[b], times))
+        outs.append((jump[b], end_rows[b], scores[b], times) + (((res[4][b], res[5][b]),) if want_scores else ()))
     return outs
 
 
-def force_align_long_batch(model, audios, texts, *, language, vocab_path, aligned_unit_type="char", sample_rate=SAMPLE_RATE, **aligner):
+def force_align_long_batch(model, audios, texts, *, language, vocab_path, aligned_unit_type="char", sample_rate=SAMPLE_RATE, word_scores=False,
+                           **aligner):
     """force_align_long() of several recordings in lock-step: a list with force_align_long()'s result for every (audio, text) pair, in
     order. Every round cuts the next window of every unfinished recording and aligns them in ONE encode_batch + align_batch, whose rows
     may mix open and closed windows; the batch shrinks as recordings end, and more recordings than model.max_batch go in groups of
     max_batch. sample_rate is one int for every array / tensor input or one per recording (a path carries its own rate); aligner: aggr="topk",
-    topk=10, medfilt_width=3, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0 (longform.aligner_options)."""
+    topk=10, medfilt_width=3, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0 (longform.aligner_options). word_scores=True: every word gets
+    a "score" and every window a "mean_word_score" (module docstring)."""
     from .tokenizer import get_tokenizer
     audios, texts = list(audios), list(texts)
     if len(audios) != len(texts):
@@ -240,7 +271,7 @@ def force_align_long_batch(model, audios, texts, *, language, vocab_path, aligne
     results = []
     for group in groups_of(range(len(audios)), int(getattr(model, "max_batch", 1))):
         mels = [model.log_mel_long(as_pcm(audios[i], model, rates[i])) for i in group]
-        states = [AlignState(mel.shape[1], prepared[i][1], prepared[i][2], sot_len) for i, mel in zip(group, mels)]
+        states = [AlignState(mel.shape[1], prepared[i][1], prepared[i][2], sot_len, word_scores=word_scores) for i, mel in zip(group, mels)]
         units = [prepared[i][0] for i in group]
         results.extend(align_loop(states, functools.partial(align_group_rows, model, tokenizer, opts, aligned_unit_type, mels, units, states)))
     return results
@@ -265,6 +296,9 @@ def parse_args(argv=None):
     p.add_argument("--vocab", type=str, required=True, help="local tiktoken vocabulary file")
     p.add_argument("--language", type=str, default="en")
     add_aligner_options(p)
+    # (absent from the namespace unless given: the parsed defaults are what they were)
+    p.add_argument("--word_scores", action="store_true", default=argparse.SUPPRESS, help="every word also gets a `score`, the mean of the aggregated attention matrix along "
+                   "its stretch of the DTW path (in [0, 1]; uncalibrated), and every window its `mean_word_score`")
     return p.parse_args(argv)
 
 
@@ -292,6 +326,8 @@ def main(args, model=None):
         model = load_model(args)
     os.makedirs(args.output_dir, exist_ok=True)
     kw = dict(language=args.language, vocab_path=args.vocab, sample_rate=args.sample_rate, **{k: getattr(args, k) for k in ALIGNER_KEYWORDS})
+    if getattr(args, "word_scores", False):   # (otherwise the call is what it was)
+        kw["word_scores"] = True
     paths = []
     for group in groups_of(recordings, args.batch):
         texts = [open(t, encoding="utf-8").read() for _a, t in group]

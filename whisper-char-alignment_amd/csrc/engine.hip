@@ -241,6 +241,7 @@ void wca_engine_destroy(wca_engine* e) {
   e->probe_jump.release();
   e->dtw_out.release();
   e->dtw_meta.release();
+  e->pscore.release();
   e->quiet_out.release();
   for (auto& t : e->rs_tables) (void)hipFree(t.dev);
   for (int i = 0; i < 2; ++i) {

@@ -88,8 +88,9 @@ namespace {
 // N_max x M_max. Trace, path and path length go to e->trace / e->path / e->pathlen; jump_ld > 0 also asks for the jump frames in e->jump, rows
 // jump_ld apart. open_dev ([P] device flags, 1 = open end) or open_all asks for the open-end kernel: the end rows [P] and then the scores [P]
 // land in e->dtw_out, and a closed problem of such a launch gets what the closed kernel gives it (end row N - 1).
+// launched (nullable): the arguments of that launch, for run_path_score behind it.
 int run_dtw(wca_engine* e, hipStream_t s, const float* matrix, long m_bs, int ld, int P, int N_max, int M_max, const int* N_dev, const int* M_dev,
-            int jump_ld, const int* open_dev = nullptr, bool open_all = false) {
+            int jump_ld, const int* open_dev = nullptr, bool open_all = false, DtwArgs* launched = nullptr) {
   const int wpr = (M_max + 15) / 16, cap = N_max + M_max + 2;
   HIPCHK(e->trace.ensure(sizeof(uint32_t) * (size_t)P * N_max * wpr));
   HIPCHK(e->path.ensure(sizeof(int) * (size_t)P * 2 * cap));
@@ -119,6 +120,22 @@ int run_dtw(wca_engine* e, hipStream_t s, const float* matrix, long m_bs, int ld
     dg.score = (float*)e->dtw_out.p + P;
   }
   HIPCHK(launch_dtw(dg, s));
+  if (launched) *launched = dg;
+  return WCA_OK;
+}
+
+// The per-row path scores of the DTW launch dg (run_dtw's `launched`, which asked for jump frames) on s behind it: e->pscore holds the means
+// [P][out_ld] f32 and then the cell counts [P][out_ld], both 0 wherever the kernel writes nothing (columns past dg.N_max).
+int run_path_score(wca_engine* e, hipStream_t s, const DtwArgs& dg, int out_ld) {
+  const size_t n = (size_t)dg.P * out_ld;
+  HIPCHK(e->pscore.ensure(2 * sizeof(int) * n));
+  HIPCHK(hipMemsetAsync(e->pscore.p, 0, 2 * sizeof(int) * n, s));
+  PathScoreArgs ps{};
+  ps.d = dg;
+  ps.mean = (float*)e->pscore.p;
+  ps.cells = (int*)e->pscore.p + n;
+  ps.out_ld = out_ld;
+  HIPCHK(launch_path_score(ps, s));
   return WCA_OK;
 }
 
@@ -149,9 +166,10 @@ int read_path(wca_engine* e, int N, int M, int32_t* text_idx_host, int32_t* time
 
 // top-k / aggregate / DTW on s behind the head statistics h of run_head_stats: on the dense maps h read (input_is_weights), or re-derived
 // from the captured logits and row statistics h kept. The jump frames land in e->jump [B][n_tok_max]. open_dev: run_dtw's per-utterance
-// open-end flags (end rows and scores in e->dtw_out; -1 / NaN where no DTW ran).
+// open-end flags (end rows and scores in e->dtw_out; -1 / NaN where no DTW ran). path_scores: run_path_score behind the DTW, rows n_tok_max
+// apart like the jump frames (all 0 where no DTW ran).
 int wca::run_select_aggregate_dtw(wca_engine* e, hipStream_t s, const HeadStatsArgs& h, const int* dtwN_dev, const wca_align_opts* o,
-                                  int L_layers, const int* open_dev) {
+                                  int L_layers, const int* open_dev, bool path_scores) {
   const int B = h.B, LH = h.LH, n_max = h.n_tok_max, Fmax = h.n_frames_max;
   const int k = o->aggregation == WCA_AGGR_TOPK ? o->topk : 0;
   if (o->aggregation == WCA_AGGR_TOPK) {
@@ -199,10 +217,18 @@ int wca::run_select_aggregate_dtw(wca_engine* e, hipStream_t s, const HeadStatsA
     // caller that compares or stores whole rows must not see what an earlier allocation left there)
     HIPCHK(e->jump.ensure(sizeof(int) * (size_t)B * n_max));
     HIPCHK(hipMemsetAsync(e->jump.p, 0, sizeof(int) * (size_t)B * n_max, s));
-    WCA_TRY(run_dtw(e, s, (const float*)e->matrix.p, (long)n_max * Fmax, Fmax, B, Nmax, Fmax, dtwN_dev, h.n_frames, n_max, open_dev));
-  } else if (open_dev) {
-    HIPCHK(e->dtw_out.ensure(2 * sizeof(int) * (size_t)B));
-    HIPCHK(hipMemsetAsync(e->dtw_out.p, 0xFF, 2 * sizeof(int) * (size_t)B, s));
+    DtwArgs dg;
+    WCA_TRY(run_dtw(e, s, (const float*)e->matrix.p, (long)n_max * Fmax, Fmax, B, Nmax, Fmax, dtwN_dev, h.n_frames, n_max, open_dev, false, &dg));
+    if (path_scores) WCA_TRY(run_path_score(e, s, dg, n_max));
+  } else {
+    if (open_dev) {
+      HIPCHK(e->dtw_out.ensure(2 * sizeof(int) * (size_t)B));
+      HIPCHK(hipMemsetAsync(e->dtw_out.p, 0xFF, 2 * sizeof(int) * (size_t)B, s));
+    }
+    if (path_scores) {
+      HIPCHK(e->pscore.ensure(2 * sizeof(int) * (size_t)B * n_max));
+      HIPCHK(hipMemsetAsync(e->pscore.p, 0, 2 * sizeof(int) * (size_t)B * n_max, s));
+    }
   }
   return WCA_OK;
 }
@@ -211,18 +237,20 @@ namespace {
 
 // The pinned results slot of one enqueued batch, in ints: jump frames [batch][n_tok_max], top-k heads [batch][max(k, 1)], two flag words
 // (phase 2's, and the one phase 1 raised for the batch's cross-K/V slot), then (token log-probs only) the log-probs [batch][n_tok_max] as f32,
-// then (open-end batches only) the end rows [batch] and the scores [batch] as f32.
+// then (open-end batches only) the end rows [batch] and the scores [batch] as f32, then (path-score batches only) the per-row means
+// [batch][n_tok_max] as f32 and the cell counts [batch][n_tok_max].
 struct ResLayout {
-  size_t jump, sel, flags, lp, open, ints;
+  size_t jump, sel, flags, lp, open, ps, ints;
 };
-ResLayout res_layout(int batch, int n_tok_max, int k, bool want_lp, bool want_open = false) {
+ResLayout res_layout(int batch, int n_tok_max, int k, bool want_lp, bool want_open = false, bool want_ps = false) {
   ResLayout r;
   r.jump = 0;
   r.sel = r.jump + (size_t)batch * n_tok_max;
   r.flags = r.sel + (size_t)batch * (k > 0 ? k : 1);
   r.lp = r.flags + 2;
   r.open = r.lp + (want_lp ? (size_t)batch * n_tok_max : 0);
-  r.ints = r.open + (want_open ? 2 * (size_t)batch : 0);
+  r.ps = r.open + (want_open ? 2 * (size_t)batch : 0);
+  r.ints = r.ps + (want_ps ? 2 * (size_t)batch * n_tok_max : 0);
   return r;
 }
 
@@ -411,17 +439,21 @@ int wca_dtw_open(wca_engine* e, const float* matrix_host, int N, int M, int32_t*
   return read_path(e, N, M, text_idx_host, time_idx_host, path_len_host);
 }
 
-int wca_dtw_batch_dev_open(wca_engine* e, const float* matrix_dev, int P, int N, int M, const int32_t* n_rows_host, const int32_t* n_cols_host,
-                           const int32_t* open_end_host, int32_t* jump_frame_host, int32_t* end_row_host, float* score_host) {
-  if (!e || !matrix_dev || !open_end_host || !jump_frame_host || !end_row_host) return fail(WCA_ERR_INVALID, "null argument");
+// wca_dtw_batch_dev_open and wca_dtw_path_scores: the ragged, mixed open / closed DTW on `stream`, with the path-score kernel behind it where the
+// two score outputs are given
+static int dtw_batch_open_common(wca_engine* e, const float* matrix_dev, int P, int N, int M, const int32_t* n_rows_host, const int32_t* n_cols_host,
+                                 const int32_t* open_end_host, int32_t* jump_frame_host, int32_t* end_row_host, float* score_host,
+                                 float* path_mean_host, int32_t* path_cells_host) {
+  const int least = path_mean_host ? 0 : 1;   // (the score entry also takes an empty problem: no path, end row -1, every row (0, 0.0))
   if (P < 1) return fail(WCA_ERR_INVALID, "P < 1");
   if (N < 1 || N > 512 || M < 1 || M > 4096) return fail(WCA_ERR_INVALID, "DTW shape N=%d M=%d unsupported (N<=512, M<=4096)", N, M);
   // the per-problem tables travel as one block: open flags, then (ragged launches) the row and column counts
   std::vector<int32_t> meta(3 * (size_t)P);
   for (int p = 0; p < P; ++p) {
     const int n = n_rows_host ? n_rows_host[p] : N, m = n_cols_host ? n_cols_host[p] : M;
-    if (n < 1 || n > N || m < 1 || m > M) return fail(WCA_ERR_INVALID, "problem %d is %d x %d, outside [1,%d] x [1,%d]", p, n, m, N, M);
-    meta[p] = open_end_host[p] ? 1 : 0;
+    if (n < least || n > N || m < least || m > M)
+      return fail(WCA_ERR_INVALID, "problem %d is %d x %d, outside [%d,%d] x [%d,%d]", p, n, m, least, N, least, M);
+    meta[p] = open_end_host && open_end_host[p] ? 1 : 0;
     meta[(size_t)P + p] = n;
     meta[2 * (size_t)P + p] = m;
   }
@@ -432,12 +464,33 @@ int wca_dtw_batch_dev_open(wca_engine* e, const float* matrix_dev, int P, int N,
   // rows of a problem that the DTW does not write (beyond its own row count) are defined as 0, as on the fused path
   HIPCHK(e->jump.ensure(sizeof(int) * (size_t)P * N));
   HIPCHK(hipMemsetAsync(e->jump.p, 0, sizeof(int) * (size_t)P * N, e->stream));
-  WCA_TRY(run_dtw(e, e->stream, matrix_dev, (long)N * M, M, P, N, M, md + P, md + 2 * (size_t)P, N, md));
+  DtwArgs dg;
+  WCA_TRY(run_dtw(e, e->stream, matrix_dev, (long)N * M, M, P, N, M, md + P, md + 2 * (size_t)P, N, md, false, &dg));
   HIPCHK(hipMemcpyAsync(jump_frame_host, e->jump.p, sizeof(int) * (size_t)P * N, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipMemcpyAsync(end_row_host, e->dtw_out.p, sizeof(int) * (size_t)P, hipMemcpyDeviceToHost, e->stream));
   if (score_host) HIPCHK(hipMemcpyAsync(score_host, (const float*)e->dtw_out.p + P, sizeof(float) * (size_t)P, hipMemcpyDeviceToHost, e->stream));
+  if (path_mean_host) {
+    WCA_TRY(run_path_score(e, e->stream, dg, N));
+    HIPCHK(hipMemcpyAsync(path_mean_host, e->pscore.p, sizeof(float) * (size_t)P * N, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(path_cells_host, (const int*)e->pscore.p + (size_t)P * N, sizeof(int) * (size_t)P * N, hipMemcpyDeviceToHost, e->stream));
+  }
   HIPCHK(hipStreamSynchronize(e->stream));   // (meta is a stack-lifetime host buffer)
   return WCA_OK;
+}
+
+int wca_dtw_batch_dev_open(wca_engine* e, const float* matrix_dev, int P, int N, int M, const int32_t* n_rows_host, const int32_t* n_cols_host,
+                           const int32_t* open_end_host, int32_t* jump_frame_host, int32_t* end_row_host, float* score_host) {
+  if (!e || !matrix_dev || !open_end_host || !jump_frame_host || !end_row_host) return fail(WCA_ERR_INVALID, "null argument");
+  return dtw_batch_open_common(e, matrix_dev, P, N, M, n_rows_host, n_cols_host, open_end_host, jump_frame_host, end_row_host, score_host, nullptr,
+                               nullptr);
+}
+
+int wca_dtw_path_scores(wca_engine* e, const float* matrix_dev, int P, int N, int M, const int32_t* n_rows_host, const int32_t* n_cols_host,
+                        const int32_t* open_end_host, int32_t* jump_frame_host, int32_t* end_row_host, float* path_mean_host,
+                        int32_t* path_cells_host) {
+  if (!e || !matrix_dev || !jump_frame_host || !end_row_host || !path_mean_host || !path_cells_host) return fail(WCA_ERR_INVALID, "null argument");
+  return dtw_batch_open_common(e, matrix_dev, P, N, M, n_rows_host, n_cols_host, open_end_host, jump_frame_host, end_row_host, nullptr,
+                               path_mean_host, path_cells_host);
 }
 
 int wca_probe_heads(wca_engine* e, const float* ws_dev, int L, int H, int n, int F, int sot_len, float* scores_host,
@@ -568,6 +621,7 @@ int wca_align_batch_enqueue(wca_engine* e, const wca_align_desc* d) {
   const int n_tok_max = d->n_tok_max, batch = d->batch, vocab_end = d->vocab_end;
   const wca_align_opts* o = d->opts;
   const bool want_open = open_end_host != nullptr;
+  const bool want_ps = d->path_scores != 0;
   if (vocab_end < 0 || vocab_end > e->dims.n_vocab) return fail(WCA_ERR_INVALID, "vocab_end %d outside (0, %d] (0 = no token log-probs)", vocab_end, e->dims.n_vocab);
   const bool want_lp = vocab_end > 0;
   const bool reuse_enc = (pcm_dev == nullptr);  // consume the oldest encoded state (wca_encode_batch / wca_decode)
@@ -656,7 +710,7 @@ int wca_align_batch_enqueue(wca_engine* e, const wca_align_desc* d) {
   WCA_TRY(run_head_stats(e, s2, &h, (const float*)e->cap.p, Fpad, false, nullptr, true, rows[1], rows[2], n_tok_max, Fmax, LH, batch, o->medfilt_width,
                          o->qk_scale, o->w_colnorm, o->w_rownorm, o->w_coverage));
   record(e, 5, s2);
-  WCA_TRY(run_select_aggregate_dtw(e, s2, h, rows[3], o, D.n_text_layer, open_rows[0]));
+  WCA_TRY(run_select_aggregate_dtw(e, s2, h, rows[3], o, D.n_text_layer, open_rows[0], want_ps));
   if (want_lp) {
     HIPCHK(e->lp_out.ensure(sizeof(float) * (size_t)batch * n_tok_max));
     WCA_TRY(run_token_logprobs(e, s2, tokens_dev, batch, n_tok_max, o->sot_len, vocab_end, rows[1], lp_rows[0], lp_R, lp_nmax, (float*)e->lp_out.p));
@@ -667,7 +721,7 @@ int wca_align_batch_enqueue(wca_engine* e, const wca_align_desc* d) {
   // behind that encoder)
   const int k = o->aggregation == WCA_AGGR_TOPK ? o->topk : 0;
   const int rs = (int)(e->enq_count & 1);
-  const ResLayout at = res_layout(batch, n_tok_max, k, want_lp, want_open);
+  const ResLayout at = res_layout(batch, n_tok_max, k, want_lp, want_open, want_ps);
   WCA_TRY(ensure_res_host(e, rs, at.ints));
   int* res = e->res_host[rs];
   if (want_lp) HIPCHK(hipMemcpyAsync(res + at.lp, e->lp_out.p, sizeof(float) * (size_t)batch * n_tok_max, hipMemcpyDeviceToHost, s2));
@@ -676,6 +730,7 @@ int wca_align_batch_enqueue(wca_engine* e, const wca_align_desc* d) {
   if (n_tok_max - o->sot_len - 1 >= 1) HIPCHK(hipMemcpyAsync(res + at.jump, e->jump.p, sizeof(int) * (size_t)batch * n_tok_max, hipMemcpyDeviceToHost, s2));
   if (k > 0) HIPCHK(hipMemcpyAsync(res + at.sel, e->sel.p, sizeof(int) * (size_t)batch * k, hipMemcpyDeviceToHost, s2));
   if (want_open) HIPCHK(hipMemcpyAsync(res + at.open, e->dtw_out.p, 2 * sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, s2));
+  if (want_ps) HIPCHK(hipMemcpyAsync(res + at.ps, e->pscore.p, 2 * sizeof(int) * (size_t)batch * n_tok_max, hipMemcpyDeviceToHost, s2));
   record(e, 8, s2);
   HIPCHK(hipEventRecord(e->res_ev[rs], s2));
   e->res_batch[rs] = batch;
@@ -683,6 +738,7 @@ int wca_align_batch_enqueue(wca_engine* e, const wca_align_desc* d) {
   e->res_topk[rs] = k;
   e->res_lp[rs] = want_lp;
   e->res_open[rs] = want_open;
+  e->res_ps[rs] = want_ps;
   e->res_kvslot[rs] = bs;
   e->last_batch = batch;
   e->enq_count++;
@@ -724,7 +780,7 @@ int wca_align_batch_fetch(wca_engine* e, int batch, int n_tok_max, int topk, con
     return fail(WCA_ERR_STATE, "end rows requested, but the pending batch was enqueued without open_end_host");
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipEventSynchronize(e->res_ev[rs]));
-  const ResLayout at = res_layout(batch, n_tok_max, e->res_topk[rs], e->res_lp[rs], e->res_open[rs]);
+  const ResLayout at = res_layout(batch, n_tok_max, e->res_topk[rs], e->res_lp[rs], e->res_open[rs], e->res_ps[rs]);
   const int* res = e->res_host[rs];
   if (jump_frame_host) memcpy(jump_frame_host, res + at.jump, sizeof(int) * (size_t)batch * n_tok_max);
   if (sel_idx_host && e->res_topk[rs] > 0) memcpy(sel_idx_host, res + at.sel, sizeof(int) * (size_t)batch * topk);
@@ -740,6 +796,22 @@ int wca_align_batch_fetch(wca_engine* e, int batch, int n_tok_max, int topk, con
     return fail(WCA_ERR_INVALID, "a teacher token is outside the scored vocabulary [0, vocab_end) (its log-prob is NaN)");
   if (flag)
     return fail(WCA_ERR_INVALID, "a token id is outside the model's vocabulary [0, %d) (tokenizer / checkpoint mismatch?)", e->dims.n_vocab);
+  return WCA_OK;
+}
+
+int wca_align_batch_path_scores(wca_engine* e, int batch, int n_tok_max, float* path_mean_host, int32_t* path_cells_host) {
+  if (!e || !path_mean_host || !path_cells_host) return fail(WCA_ERR_INVALID, "null argument");
+  if (e->fetch_count >= e->enq_count) return fail(WCA_ERR_STATE, "nothing to fetch");
+  const int rs = (int)(e->fetch_count & 1);  // oldest un-fetched batch, which stays pending
+  if (batch != e->res_batch[rs] || n_tok_max != e->res_ntok[rs]) return fail(WCA_ERR_STATE, "call does not match the oldest pending enqueue");
+  if (!e->res_ps[rs]) return fail(WCA_ERR_STATE, "path scores requested, but the pending batch was enqueued without them (path_scores = 0)");
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipEventSynchronize(e->res_ev[rs]));
+  const ResLayout at = res_layout(batch, n_tok_max, e->res_topk[rs], e->res_lp[rs], e->res_open[rs], true);
+  const int* res = e->res_host[rs];
+  const size_t n = (size_t)batch * n_tok_max;
+  memcpy(path_mean_host, res + at.ps, sizeof(float) * n);
+  memcpy(path_cells_host, res + at.ps + n, sizeof(int) * n);
   return WCA_OK;
 }
 

@@ -169,6 +169,7 @@ struct wca_engine {
   // ---- run-time sized buffers
   wca::GrowBuf cap, wws, colnorm, scores, sel, selsc, matrix, trace, path, pathlen, jump, tmp0, tmp1;
   wca::GrowBuf dtw_out, dtw_meta;   // open-end DTW: end rows [P] then scores [P] of the last launch; wca_dtw_batch_dev_open's flags / row / column counts
+  wca::GrowBuf pscore;              // run_path_score: the per-row path means [P][ld] f32, then the cell counts [P][ld], of the last DTW launch that asked for them
   wca::GrowBuf quiet_out;           // wca_quiet_cuts: the interior cuts [n_pieces - 1] then their levels [n_pieces - 1], copied to the host before the call returns
   wca::GrowBuf probe_jump;          // the last wca_probe_heads' jump frames [LH][N], kept on the device for wca_probe_strict_tp
   int probe_LH = 0, probe_N = 0;
@@ -203,6 +204,7 @@ struct wca_engine {
   hipEvent_t res_ev[2] = {};
   int res_topk[2] = {0, 0}, res_ntok[2] = {0, 0}, res_batch[2] = {0, 0};
   bool res_open[2] = {false, false}; // the batch in that slot was enqueued open-ended (its staging slot holds end rows and scores)
+  bool res_ps[2] = {false, false};   // the batch in that slot was enqueued with path_scores (its staging slot holds the means and cell counts)
   bool res_lp[2] = {false, false};   // the batch in that slot was enqueued with token log-probs (its staging slot holds them)
   // teacher-token log-probs of wca_align_batch_enqueue with vocab_end (phase 2's stream): compact f32 rows, their final-LayerNorm output (pairs when DEC
   // is split), the row map, the chunked [rows][ldc] f32 logits scratch and the [B][n_tok_max] results
@@ -330,7 +332,7 @@ int run_head_stats(wca_engine* e, hipStream_t s, HeadStatsArgs* h, const float* 
                    bool want_rowstats, const int* n_tok_dev, const int* n_frames_dev, int n_max, int Fmax, int LH, int B, int medfilt_width,
                    float qk_scale, float w_col, float w_row, float w_cov);
 int run_select_aggregate_dtw(wca_engine* e, hipStream_t s, const HeadStatsArgs& h, const int* dtwN_dev, const wca_align_opts* o, int L_layers,
-                             const int* open_dev = nullptr);
+                             const int* open_dev = nullptr, bool path_scores = false);
 
 // ---- engine_audio.hip
 int check_pcm_lengths(const int32_t* n_samples_host, int batch, int64_t pcm_stride);

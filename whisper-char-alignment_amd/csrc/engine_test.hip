@@ -379,7 +379,16 @@ int wca_test_last_scores(wca_engine* e, int batch, float* scores_host) {
   return WCA_OK;
 }
 
-int wca_test_align_postproc(wca_engine* e, const wca_test_postproc_desc* d) {
+static int align_postproc(wca_engine* e, const wca_test_postproc_desc* d, float* path_mean_host, int32_t* path_cells_host);
+
+int wca_test_align_postproc(wca_engine* e, const wca_test_postproc_desc* d) { return align_postproc(e, d, nullptr, nullptr); }
+
+int wca_test_align_postproc_scores(wca_engine* e, const wca_test_postproc_desc* d, float* path_mean_host, int32_t* path_cells_host) {
+  if (!path_mean_host || !path_cells_host) return fail(WCA_ERR_INVALID, "null argument");
+  return align_postproc(e, d, path_mean_host, path_cells_host);
+}
+
+static int align_postproc(wca_engine* e, const wca_test_postproc_desc* d, float* path_mean_host, int32_t* path_cells_host) {
   if (!e || !d || !d->qk_dev || !d->n_tok_host || !d->n_frames_host || !d->opts) return fail(WCA_ERR_INVALID, "null argument");
   const wca_align_opts* o = d->opts;
   const int B = d->B, LH = d->L * d->H, n_max = d->n_tok_max, F = d->n_frames_max;
@@ -406,7 +415,7 @@ int wca_test_align_postproc(wca_engine* e, const wca_test_postproc_desc* d) {
   HeadStatsArgs h;
   WCA_TRY(run_head_stats(e, s, &h, d->qk_dev, d->ld, false, nullptr, true, rows[1], rows[2], n_max, F, LH, B, o->medfilt_width, o->qk_scale,
                          o->w_colnorm, o->w_rownorm, o->w_coverage));
-  WCA_TRY(run_select_aggregate_dtw(e, s, h, rows[3], o, d->L, open_rows[0]));
+  WCA_TRY(run_select_aggregate_dtw(e, s, h, rows[3], o, d->L, open_rows[0], path_mean_host != nullptr));
   const bool topk = o->aggregation == WCA_AGGR_TOPK;
   const size_t BLH = (size_t)B * LH;
   if (d->scores_host) HIPCHK(hipMemcpyAsync(d->scores_host, e->scores.p, sizeof(float) * BLH, hipMemcpyDeviceToHost, s));
@@ -419,6 +428,11 @@ int wca_test_align_postproc(wca_engine* e, const wca_test_postproc_desc* d) {
       HIPCHK(hipMemcpyAsync(d->jump_host, e->jump.p, sizeof(int) * (size_t)B * n_max, hipMemcpyDeviceToHost, s));
     else
       memset(d->jump_host, 0, sizeof(int) * (size_t)B * n_max);
+  }
+  if (path_mean_host) {
+    const size_t n = (size_t)B * n_max;
+    HIPCHK(hipMemcpyAsync(path_mean_host, e->pscore.p, sizeof(float) * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(path_cells_host, (const int*)e->pscore.p + n, sizeof(int) * n, hipMemcpyDeviceToHost, s));
   }
   HIPCHK(hipStreamSynchronize(s));
   return WCA_OK;

@@ -433,4 +433,18 @@ struct DtwArgs {
 };
 hipError_t launch_dtw(const DtwArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- per-row score of the DTW path (path_score.hip)
+// Behind launch_dtw(d) on the same stream: for text row i of problem p, cells = the number of path cells in that row and mean = the f32
+// rounding of the f64 mean of matrix[i][j] (NOT negated) over them. Within a row the path only moves along the frame axis, so the cells are
+// the frames jump[i] .. last[i]: last = M - 1 for the end row, else jump[i+1] where the trace enters row i + 1 vertically (that column is in
+// both rows) and jump[i+1] - 1 where it enters diagonally. Rows the path does not reach (past an open end row, a problem the DTW refused,
+// i >= N[p]) get (0, 0.0). Reads d.matrix, d.N / d.M, d.trace, d.jump_frame (required), d.path_len and d.end_row (null: N - 1).
+struct PathScoreArgs {
+  DtwArgs d;
+  float* mean;             // [P][out_ld]; rows [0, d.N_max) of every problem are written
+  int* cells;              // [P][out_ld]
+  int out_ld;              // >= d.N_max
+};
+hipError_t launch_path_score(const PathScoreArgs& a, hipStream_t s);
+
 }  // namespace wca

@@ -10,6 +10,8 @@ default_find_alignment = _t.default_find_alignment
 median_filter = _t.median_filter
 dtw = _t.dtw
 dtw_open = _t.dtw_open
+path_scores = _t.path_scores
+word_alignment_scores = _t.word_alignment_scores
 force_align_long = _t.force_align_long
 force_align_long_batch = _t.force_align_long_batch
 HOP_LENGTH, SAMPLE_RATE, TOKENS_PER_SECOND = _t.HOP_LENGTH, _t.SAMPLE_RATE, _t.TOKENS_PER_SECOND

@@ -19,6 +19,7 @@ N_FRAMES = 3000
 N_SAMPLES = 480000
 MAX_FRAMES = 1500   # infer_ali.py:25
 MAX_LENGTH = 448    # infer_ali.py:26
+_pf32, _pi32 = C.POINTER(C.c_float), C.POINTER(C.c_int32)
 
 
 @dataclass
@@ -452,7 +453,8 @@ class WhisperAMD:
         return _lib.AlignOpts(_lib.AGGR_TOPK if aggregation == "topk" else _lib.AGGR_MEAN, int(topk), float(w_colnorm),
                               float(w_rownorm), float(w_coverage), int(sot_len), int(medfilt_width), float(qk_scale))
 
-    def align_batch(self, pcm, n_samples, tokens, n_tok, max_frames, opts, enqueue_only=False, token_logprobs_vocab_end=None, open_end=None):
+    def align_batch(self, pcm, n_samples, tokens, n_tok, max_frames, opts, enqueue_only=False, token_logprobs_vocab_end=None, open_end=None,
+                    path_scores=False):
         """Fused pipeline. pcm [B,stride] f32 cuda, tokens [B,n_max] int64 cuda. Returns (jump_frames [B,n_max] int32, sel [B,topk]).
         token_logprobs_vocab_end (tokenizer.eot): the teacher tokens' log-probabilities are computed on the GPU as well
         (wca_align_desc.vocab_end) and returned as a third value [B,n_max] f32 (row b: n_tok[b] - sot_len - 2 entries, then 0);
@@ -460,7 +462,10 @@ class WhisperAMD:
         open_end (B bools): row b's DTW is open-ended where open_end[b] (wca_align_desc.open_end_host: the path ends in the last frame at
         the text row that fits best; a row with False gets exactly the closed result). The end rows [B] int32 and the scores [B] f32 are
         returned as two further values, after the log-probs where those are asked for; rows past a row's end row have jump frame -1.
-        After enqueue_only=True, fetch them with fetch(..., with_end_rows=True). None: nothing changes."""
+        After enqueue_only=True, fetch them with fetch(..., with_end_rows=True). None: nothing changes.
+        path_scores: the path-score kernel runs behind the DTW (wca_align_desc.path_scores) and (path_mean [B,n_max] f32, path_cells
+        [B,n_max] int32) are the LAST two values returned: per DTW row, laid out like the jump frames, the mean of the aggregated matrix
+        over the path's cells in that row and their number. After enqueue_only=True, fetch them with fetch(..., with_path_scores=True)."""
         B, n_max = tokens.shape
         if open_end is not None and len(open_end) != B:
             raise ValueError("open_end lists %d flags for %d rows" % (len(open_end), B))
@@ -471,11 +476,12 @@ class WhisperAMD:
         oe = _lib.i32_array([bool(v) for v in open_end]) if open_end is not None else None
         d = _lib.AlignDesc(pcm_dev=_ptr(pcm), n_samples_host=_ptr(ns), tokens_dev=_ptr(tokens), n_tok_host=_ptr(nt), max_frames_host=_ptr(mf),
                            opts=C.pointer(opts), open_end_host=_ptr(oe), pcm_stride=pcm.shape[1] if pcm is not None else 0, n_tok_max=n_max,
-                           batch=B, vocab_end=int(token_logprobs_vocab_end or 0))
+                           batch=B, vocab_end=int(token_logprobs_vocab_end or 0), path_scores=1 if path_scores else 0)
         _lib.check(self._lib.wca_align_batch_enqueue(self._h, C.byref(d)))
         if enqueue_only:
             return None
-        return self.fetch(B, n_max, opts, with_token_logprobs=token_logprobs_vocab_end is not None, with_end_rows=open_end is not None)
+        return self.fetch(B, n_max, opts, with_token_logprobs=token_logprobs_vocab_end is not None, with_end_rows=open_end is not None,
+                          with_path_scores=bool(path_scores))
 
     def encode_batch(self, mel=None, pcm=None, n_samples=None):
         """C ABI wca_encode_batch: enqueue log-mel/encoder/cross-K/V of a micro-batch (no host sync). The state is picked up
@@ -665,11 +671,12 @@ class WhisperAMD:
         from . import decoding
         return decoding.decode(self, mel, options if options is not None else decoding.DecodingOptions())
 
-    def align_postproc(self, qk, n_tok, n_frames, opts, L, H, n_frames_max=None, open_end=None):
+    def align_postproc(self, qk, n_tok, n_frames, opts, L, H, n_frames_max=None, open_end=None, path_scores=False):
         """C ABI wca_test_align_postproc (tests): phase 2's post-processing of align_batch on given logits qk [B, L*H, n_tok_max, ld] f32
         cuda. Returns a dict of numpy arrays: scores [B,LH], colnorm [B,LH,F], rowstats [B,LH,n_tok_max,2], sel [B,topk] (None for
         'mean'), matrix [B,n_tok_max,F], jump [B,n_tok_max]; F = n_frames_max (default: the largest n_frames). Only utterance b's own
-        corner of an array is defined."""
+        corner of an array is defined. path_scores: through wca_test_align_postproc_scores, which adds path_mean [B,n_tok_max] f32 and
+        path_cells [B,n_tok_max] int32."""
         qk = qk.to(self.device, torch.float32).contiguous()
         B, LH, n_max, ld = qk.shape
         if LH != L * H:
@@ -686,21 +693,52 @@ class WhisperAMD:
                               scores_host=_ptr(out["scores"]), colnorm_host=_ptr(out["colnorm"]), rowstats_host=_ptr(out["rowstats"]),
                               sel_idx_host=_ptr(out["sel"]), matrix_host=_ptr(out["matrix"]), jump_host=_ptr(out["jump"]),
                               B=B, L=L, H=H, n_tok_max=n_max, ld=ld, n_frames_max=F)
-        _lib.check(self._lib.wca_test_align_postproc(self._h, C.byref(d)))
+        if path_scores:
+            out["path_mean"], out["path_cells"] = np.zeros((B, n_max), np.float32), np.zeros((B, n_max), np.int32)
+            _lib.check(self._lib.wca_test_align_postproc_scores(self._h, C.byref(d), out["path_mean"].ctypes.data_as(_pf32),
+                                                                out["path_cells"].ctypes.data_as(_pi32)))
+        else:
+            _lib.check(self._lib.wca_test_align_postproc(self._h, C.byref(d)))
         return out
 
-    def fetch(self, B, n_max, opts, with_token_logprobs=False, with_end_rows=False):
+    def dtw_path_scores(self, matrix_dev, n_rows=None, n_cols=None, open_end=None):
+        """C ABI wca_dtw_path_scores: P DTW problems matrix_dev [P, N, M] f32 cuda (NOT negated), problem p the n_rows[p] x n_cols[p] corner
+        of its slice (None: all N / all M), open-ended where open_end[p] (None: all closed), each followed by the path-score kernel.
+        Returns (jump [P,N] int32, end_rows [P] int32, path_mean [P,N] f32, path_cells [P,N] int32)."""
+        m = matrix_dev.to(self.device, torch.float32).contiguous()
+        if m.dim() != 3:
+            raise ValueError("matrix_dev must be [P, N, M]")
+        P, N, M = m.shape
+        for name, v in (("n_rows", n_rows), ("n_cols", n_cols), ("open_end", open_end)):
+            if v is not None and len(v) != P:
+                raise ValueError("%s lists %d values for %d problems" % (name, len(v), P))
+        nr = _lib.i32_array(n_rows) if n_rows is not None else None
+        nc = _lib.i32_array(n_cols) if n_cols is not None else None
+        oe = _lib.i32_array([bool(v) for v in open_end]) if open_end is not None else None
+        jump, end_rows = np.zeros((P, N), np.int32), np.zeros(P, np.int32)
+        mean, cells = np.zeros((P, N), np.float32), np.zeros((P, N), np.int32)
+        self._bind_stream()
+        _lib.check(self._lib.wca_dtw_path_scores(self._h, _ptr(m), P, N, M, nr, nc, oe, jump.ctypes.data_as(_pi32), end_rows.ctypes.data_as(_pi32),
+                                                 mean.ctypes.data_as(_pf32), cells.ctypes.data_as(_pi32)))
+        return jump, end_rows, mean, cells
+
+    def fetch(self, B, n_max, opts, with_token_logprobs=False, with_end_rows=False, with_path_scores=False):
         """Results of the oldest enqueued align_batch: (jump, sel), or (jump, sel, token_logprobs [B,n_max] f32) with
         with_token_logprobs (the batch must have been enqueued with token_logprobs_vocab_end). with_end_rows (the batch must have been
-        enqueued with open_end) appends the end rows [B] int32 and the scores [B] f32."""
+        enqueued with open_end) appends the end rows [B] int32 and the scores [B] f32. with_path_scores (the batch must have been enqueued
+        with path_scores) appends, last, path_mean [B,n_max] f32 and path_cells [B,n_max] int32 (wca_align_batch_path_scores)."""
         k = opts.topk if opts.aggregation == _lib.AGGR_TOPK else 0
         jump = np.zeros((B, n_max), dtype=np.int32)
         sel = np.zeros((B, max(k, 1)), dtype=np.int32)
         lp = np.zeros((B, n_max), dtype=np.float32) if with_token_logprobs else None
         end_rows, scores = (np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.float32)) if with_end_rows else (None, None)
+        ps = ()
+        if with_path_scores:   # read before the fetch, which consumes the batch
+            ps = (np.zeros((B, n_max), dtype=np.float32), np.zeros((B, n_max), dtype=np.int32))
+            _lib.check(self._lib.wca_align_batch_path_scores(self._h, B, n_max, ps[0].ctypes.data_as(_pf32), ps[1].ctypes.data_as(_pi32)))
         r = _lib.AlignResult(_ptr(jump), _ptr(sel), _ptr(lp), _ptr(end_rows), _ptr(scores))
         _lib.check(self._lib.wca_align_batch_fetch(self._h, B, n_max, k, C.byref(r)))
-        return (jump, (sel if k > 0 else None)) + ((lp,) if with_token_logprobs else ()) + ((end_rows, scores) if with_end_rows else ())
+        return (jump, (sel if k > 0 else None)) + ((lp,) if with_token_logprobs else ()) + ((end_rows, scores) if with_end_rows else ()) + ps
 
     def set_profiling(self, on):
         _lib.check(self._lib.wca_set_profiling(self._h, 1 if on else 0))

@@ -47,7 +47,7 @@ from .dataset import AMI, TIMIT, LibriSpeech  # noqa: E402
 from .engine import WhisperAMD, dims_for, MAX_FRAMES, MAX_LENGTH  # noqa: E402
 from .metrics import eval_n1, eval_n1_strict, get_seg_metrics  # noqa: E402
 from .retokenize import encode, remove_punctuation  # noqa: E402
-from .timing import words_from_jump_frames, default_find_alignment, word_probabilities  # noqa: E402
+from .timing import words_from_jump_frames, default_find_alignment, word_probabilities, word_alignment_scores  # noqa: E402
 from .timing import get_attentions, token_logprobs, _default_alignment_from_weights  # noqa: E402
 from .audio import log_mel_spectrogram, pad_or_trim  # noqa: E402
 from .tokenizer import get_tokenizer  # noqa: E402
@@ -181,6 +181,11 @@ def infer_dataset(args, model=None):
     local_conf = {}   # --word_confidence: utterance index -> per-word probabilities
     word_conf = bool(getattr(args, "word_confidence", False))
     lp_vocab_end = tokenizer.eot if word_conf else None   # teacher-token log-probs over the text vocabulary [:eot]
+    local_align = {}   # --word_alignment_score: utterance index -> per-word alignment scores
+    word_align = bool(getattr(args, "word_alignment_score", False))
+    if word_align and args.default_whisper_timing:
+        raise SystemExit("--word_alignment_score reads the batched path's DTW: it cannot be combined with --default_whisper_timing")
+    ps_kw = {"path_scores": True} if word_align else {}   # (otherwise every align_batch call is what it was)
     stager = PinnedStager(device)
 
     def prepare(n, item):
@@ -197,19 +202,23 @@ def infer_dataset(args, model=None):
         return dict(index=n, pcm=pcm, tokens=tokens, text_tokens=text_tokens, max_frames=int(max_frames), texts=texts,
                     starts=starts, ends=ends, fid=fid, skip_early=skip)
 
-    def score(b, words, start_times, end_times, confidence=None):
+    def score(b, words, start_times, end_times, confidence=None, align_scores=None):
         """infer_ali.py:114-132 for one utterance. confidence (--word_confidence): (per-word probabilities, sum of the teacher
-        tokens' log-probs)."""
+        tokens' log-probs). align_scores (--word_alignment_score): the per-word alignment scores."""
         nonlocal corrects, total_preds, total_gts
         ends_hat = end_times
         local_times[b["index"]] = (np.asarray(start_times, dtype=np.float64), np.asarray(end_times, dtype=np.float64))
         if confidence is not None:
             local_conf[b["index"]] = np.asarray(confidence[0], dtype=np.float64)
+        if align_scores is not None:
+            local_align[b["index"]] = np.asarray(align_scores, dtype=np.float64)
         if args.save_prediction:
             all_predictions[b["index"]] = dict(starts=b["starts"], ends=b["ends"], texts=b["texts"].split(), starts_hat=start_times,
                                                ends_hat=ends_hat, predwords=words, fids=b["fid"])
             if confidence is not None:
                 all_predictions[b["index"]].update(word_probs_hat=confidence[0], text_logprob=confidence[1])
+            if align_scores is not None:
+                all_predictions[b["index"]].update(word_align_scores_hat=align_scores)
         if not args.strict:
             c, _ = eval_n1(b["ends"], ends_hat, args.tolerance)
             total_gts += len(b["ends"])
@@ -239,7 +248,7 @@ def infer_dataset(args, model=None):
     def finish(entry):
         """Host tail of a micro-batch whose GPU work was enqueued earlier: fetch the jump frames, merge words, score."""
         batch, n_max, _keep = entry
-        res = model.fetch(len(batch), n_max, opts, with_token_logprobs=word_conf)
+        res = model.fetch(len(batch), n_max, opts, with_token_logprobs=word_conf, **({"with_path_scores": True} if word_align else {}))
         jump = res[0]
         for j, b in enumerate(batch):
             if b.get("skip"):
@@ -249,7 +258,10 @@ def infer_dataset(args, model=None):
             if word_conf:
                 lp = res[2][j][:len(b["text_tokens"])]
                 confidence = (word_probabilities(lp, b["text_tokens"], tokenizer, args.aligned_unit_type), float(np.sum(lp, dtype=np.float64)))
-            score(b, words, start_times, end_times, confidence)
+            align_scores = None
+            if word_align:
+                align_scores = word_alignment_scores(res[-2][j], res[-1][j], b["text_tokens"], tokenizer, args.aligned_unit_type)
+            score(b, words, start_times, end_times, confidence, align_scores)
 
     enqueued = collections.deque()  # micro-batches in flight in the engine (at most 2)
 
@@ -260,7 +272,7 @@ def infer_dataset(args, model=None):
         pcm_dev, n_samples = stager.upload(batch)
         toks_dev, n_max = token_matrix(batch)
         model.align_batch(pcm_dev, n_samples, toks_dev, [len(b["tokens"]) for b in batch], [b["max_frames"] for b in batch], opts,
-                          enqueue_only=True, token_logprobs_vocab_end=lp_vocab_end)
+                          enqueue_only=True, token_logprobs_vocab_end=lp_vocab_end, **ps_kw)
         enqueued.append((batch, n_max, (pcm_dev, toks_dev)))  # the device buffers stay alive until the fetch
         while len(enqueued) > 1:
             finish(enqueued.popleft())
@@ -287,7 +299,7 @@ def infer_dataset(args, model=None):
                 b["tokens"] = [*tokenizer.sot_sequence, tokenizer.no_timestamps, tokenizer.eot]
         toks_dev, n_max = token_matrix(batch)
         model.align_batch(None, None, toks_dev, [len(b["tokens"]) for b in batch], [b["max_frames"] for b in batch], opts, enqueue_only=True,
-                          token_logprobs_vocab_end=lp_vocab_end)
+                          token_logprobs_vocab_end=lp_vocab_end, **ps_kw)
         finish((batch, n_max, toks_dev))
 
     pending, in_flight = [], []
@@ -349,6 +361,8 @@ def infer_dataset(args, model=None):
     if word_conf:
         # the word probabilities travel in the same packed collective as the word times (both halves of an entry carry them)
         all_conf = _shard.allgather_results({i: (p, p) for i, p in local_conf.items()})
+    if word_align:
+        all_align = _shard.allgather_results({i: (p, p) for i, p in local_align.items()})
     if args.save_prediction:
         all_predictions = _shard.gather_predictions(all_predictions)  # every rank's dict on rank 0 (None elsewhere)
     if rank == 0:
@@ -362,10 +376,14 @@ def infer_dataset(args, model=None):
         if word_conf:
             conf = np.concatenate([p for p, _ in all_conf.values()]) if all_conf else np.zeros(0)
             notes["mean_word_prob"] = float(np.mean(conf)) if conf.size else None
+        if word_align:   # (nan: a word without a path cell, which the closed DTW of this path never leaves)
+            sc = np.concatenate([p for p, _ in all_align.values()]) if all_align else np.zeros(0)
+            sc = sc[~np.isnan(sc)]
+            notes["mean_word_align_score"] = float(np.mean(sc)) if sc.size else None
         if args.teacher == "text":
             notes["teacher_note"] = "ground-truth transcript teacher-forced; the reference aligns the ASR hypothesis (infer_ali.py:60-68)"
         with open(os.path.join(args.output_dir, filename + ".json"), "w") as f:
-            json.dump({**{k: v for k, v in vars(args).items() if k not in ("word_confidence", "initial_prompt") or v}, **results, **notes, "utterances": len(all_times), "seconds": elapsed}, f)
+            json.dump({**{k: v for k, v in vars(args).items() if k not in ("word_confidence", "word_alignment_score", "initial_prompt") or v}, **results, **notes, "utterances": len(all_times), "seconds": elapsed}, f)
         if args.save_prediction:
             import joblib
             joblib.dump(all_predictions, os.path.join(args.output_dir, filename + "-predictions.pkl"))
@@ -415,6 +433,10 @@ def parse_args(argv=None):
                    help="per-word probabilities (openai-whisper's word `probability`: the mean over a word's tokens of the teacher token's "
                         "softmax probability over the text vocabulary [:eot]), computed on the GPU; with --save_prediction every record "
                         "gains word_probs_hat and text_logprob, and the result JSON gains mean_word_prob")
+    p.add_argument("--word_alignment_score", action="store_true",
+                   help="per-word alignment scores: the mean of the aggregated attention matrix along each word's stretch of the DTW path (in "
+                        "[0, 1]; uncalibrated), computed on the GPU behind the DTW of the batched path; with --save_prediction every record "
+                        "gains word_align_scores_hat, and the result JSON gains mean_word_align_score")
     return p.parse_args(argv)
 
 

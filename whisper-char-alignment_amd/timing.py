@@ -104,6 +104,22 @@ def dtw_open(x):
     return ti[:n.value].astype(np.int64), tj[:n.value].astype(np.int64), int(end_row.value), float(score.value)
 
 
+def path_scores(matrix):
+    """The DTW of one (N, M) matrix (NOT negated: what force_align returns as `matrix`; host or device) with the per-row score of its path,
+    through wca_dtw_path_scores. Returns (text_indices, time_indices, path_mean, path_cells): the path as dtw(-matrix) gives it, and for
+    every text row the float32 mean of `matrix` over the path's cells in that row and their int32 count (a column the path leaves
+    vertically counts in both rows)."""
+    matrix = torch.as_tensor(matrix) if not isinstance(matrix, torch.Tensor) else matrix
+    if matrix.dim() != 2:
+        raise ValueError("matrix must be (N, M)")
+    m = _as_cuda_f32(matrix)
+    jump, _end, mean, cells = _engine_for(m.device).dtw_path_scores(m.unsqueeze(0))
+    # row i holds the frames jump[i] .. jump[i] + cells[i] - 1
+    text_indices = np.repeat(np.arange(len(cells[0]), dtype=np.int64), cells[0])
+    time_indices = np.concatenate([np.arange(j, j + c, dtype=np.int64) for j, c in zip(jump[0], cells[0])])
+    return text_indices, time_indices, mean[0], cells[0]
+
+
 def force_align_long(model, audio, text, **kw):
     """Word times of a recording of any length against its given transcript: align_long.force_align_long."""
     from . import align_long
@@ -287,6 +303,25 @@ def word_probabilities(token_logprobs, text_tokens, tokenizer, aligned_unit_type
     lp = token_logprobs.detach().cpu().numpy() if isinstance(token_logprobs, torch.Tensor) else np.asarray(token_logprobs)
     probs = np.exp(lp[:len(text_tokens)].astype(np.float64)).tolist()
     return [float(np.mean(probs[i:j])) for i, j in zip(wb[:-1], wb[1:])]
+
+
+def word_alignment_scores(path_mean, path_cells, text_tokens, tokenizer, aligned_unit_type="char"):
+    """Per-word alignment score: the mean of the aggregated attention matrix over the cells of the DTW path that lie in the word's token
+    rows, i.e. the cell-weighted mean sum(path_mean * path_cells) / sum(path_cells) over rows [wb[w], wb[w+1]) in float64, with the word
+    boundaries of force_align / words_from_jump_frames. One value per returned word, nan for a word whose rows hold no path cell (past
+    the end row of an open-end alignment); [] when the text has at most one word, like word_probabilities.
+    path_mean / path_cells: one utterance's row of align_batch(path_scores=True), or path_scores()'s last two values."""
+    wb = _word_boundaries(text_tokens, tokenizer, aligned_unit_type)
+    if wb is None:
+        return []
+    to_np = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    n = len(text_tokens) + 1
+    mean, cells = to_np(path_mean)[:n].astype(np.float64), to_np(path_cells)[:n].astype(np.float64)
+    out = []
+    for i, j in zip(wb[:-1], wb[1:]):
+        c = cells[i:j].sum()
+        out.append(float((mean[i:j] * cells[i:j]).sum() / c) if c > 0 else float("nan"))
+    return out
 
 
 def words_from_jump_frames(jump_frames, tokens, tokenizer, aligned_unit_type="char", want_words=True):

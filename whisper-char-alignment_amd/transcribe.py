@@ -310,8 +310,9 @@ def attach_words(segments, words):
 class WindowAligner:
     """The paper's aligner on the encoder state a round's decode left in the engine (make_aligner's result)."""
 
-    def __init__(self, model, tokenizer, *, aligned_unit_type="char", word_confidence=False, **options):
+    def __init__(self, model, tokenizer, *, aligned_unit_type="char", word_confidence=False, word_alignment_score=False, **options):
         self.model, self.tokenizer, self.unit, self.word_confidence = model, tokenizer, aligned_unit_type, word_confidence
+        self.word_alignment_score = word_alignment_score
         self.opts = aligner_options(model, tokenizer, **options)
         self.placeholder = [*tokenizer.sot_sequence, tokenizer.no_timestamps, tokenizer.encode(" a")[-1], tokenizer.eot]   # a row without words
 
@@ -329,15 +330,19 @@ class WindowAligner:
             return None
         return tokens, text_tokens
 
-    def attach(self, seek, segments, text_tokens, jump_row, logprob_row):
-        from .timing import word_probabilities, words_from_jump_frames
+    def attach(self, seek, segments, text_tokens, jump_row, logprob_row, path_rows=None):
+        from .timing import word_alignment_scores, word_probabilities, words_from_jump_frames
         words, starts, ends = words_from_jump_frames(jump_row, text_tokens, self.tokenizer, self.unit)
         if not len(starts):
             return False
         probs = word_probabilities(logprob_row[:len(text_tokens)], text_tokens, self.tokenizer, self.unit) if self.word_confidence else None
         offset = seek * FRAME_SECONDS
-        attach_words(segments, [{"word": words[i], "start": offset + float(starts[i]), "end": offset + float(ends[i]),
-                                 "probability": probs[i] if probs is not None else None} for i in range(len(starts))])
+        out = [{"word": words[i], "start": offset + float(starts[i]), "end": offset + float(ends[i]),
+                "probability": probs[i] if probs is not None else None} for i in range(len(starts))]
+        if path_rows is not None:   # (only then do the words carry the key)
+            for w, s in zip(out, word_alignment_scores(path_rows[0], path_rows[1], text_tokens, self.tokenizer, self.unit)):
+                w["alignment_score"] = s
+        attach_words(segments, out)
         return True
 
     def align_round(self, rows):
@@ -350,7 +355,8 @@ class WindowAligner:
         token_rows = [p[0] if p is not None else self.placeholder for p in preps]
         max_frames = [r[2] if p is not None else PLACEHOLDER_FRAMES for r, p in zip(rows, preps)]
         res = self.model.align_batch(None, None, pad_token_rows(token_rows, self.tokenizer.eot).to(self.model.device), [len(t) for t in token_rows],
-                                     max_frames, self.opts, token_logprobs_vocab_end=self.tokenizer.eot if self.word_confidence else None)
+                                     max_frames, self.opts, token_logprobs_vocab_end=self.tokenizer.eot if self.word_confidence else None,
+                                     **({"path_scores": True} if self.word_alignment_score else {}))
         out = []
         for b, (r, p) in enumerate(zip(rows, preps)):
             if r is None:
@@ -358,7 +364,8 @@ class WindowAligner:
             elif p is None:
                 out.append(False)
             else:
-                out.append(self.attach(r[0], r[3], p[1], res[0][b][:len(token_rows[b])], res[2][b] if self.word_confidence else None))
+                out.append(self.attach(r[0], r[3], p[1], res[0][b][:len(token_rows[b])], res[2][b] if self.word_confidence else None,
+                                       (res[-2][b], res[-1][b]) if self.word_alignment_score else None))
         return out
 
     def align_window(self, seek, size, max_frames, segments):
@@ -416,7 +423,9 @@ def transcribe(model, audio, *, language, decode_window=None, **options):
     audio: a path (audio.load_audio: any rate from 2 to 384 kHz, up to 8 channels), or a numpy array or tensor of mono samples [n] (or
     [channels, n]) at `sample_rate` Hz, any length. Audio that is not at 16 kHz is resampled on the GPU first (WhisperAMD.resample), as
     upstream's load_audio has ffmpeg do. word_timestamps=True: word times
-    from the character aligner per window (module docstring); word_confidence=True adds each word's probability (None otherwise).
+    from the character aligner per window (module docstring); word_confidence=True adds each word's probability (None otherwise);
+    word_alignment_score=True adds each word's "alignment_score" (timing.word_alignment_scores: the mean of the aggregated attention
+    matrix along the word's stretch of the DTW path, in [0, 1]; uncalibrated), a key the words carry only then.
     clip_timestamps: upstream's "start,end,start,end,..." in seconds (a str or a list; an odd count runs to the end of the recording): only
     those ranges are transcribed, one after the other. pieces: an int or "auto" (plan_pieces): the recording is cut at quiet frames
     (WhisperAMD.quiet_cuts) into that many pieces, which are decoded side by side as the rows of ONE batch per round; every piece starts
@@ -625,7 +634,7 @@ def merge_pieces(outs, pieces, *, tokenizer, language, extra, n_prompt):
 
 def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_on_previous_text=True, no_speech_threshold=0.6,
                      logprob_threshold=-1.0, word_timestamps=False, word_confidence=False, aligned_unit_type="char", aggr="topk", topk=10,
-                     medfilt_width=3, vocab_path=None, temperature=0.0, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0, decode_windows=None,
+                     medfilt_width=3, word_alignment_score=False, vocab_path=None, temperature=0.0, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0, decode_windows=None,
                      detect_languages=None, sample_rate=SAMPLE_RATE, clip_timestamps=None, pieces=None, seed=None,
                      compression_ratio_threshold=2.4, beam_size=None, patience=None, length_penalty=None, best_of=None, **decode_options):
     """transcribe() of several recordings in lock-step: a list with transcribe()'s result for every recording of `audios`, in order.
@@ -688,6 +697,8 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
         raise ValueError("pieces cuts the whole recording: it cannot be combined with clip_timestamps")
     if word_confidence and not word_timestamps:
         raise ValueError("word_confidence is a property of the aligned words: it needs word_timestamps=True")
+    if word_alignment_score and not word_timestamps:
+        raise ValueError("word_alignment_score is a property of the aligned words: it needs word_timestamps=True")
     if word_timestamps and vocab_path is None:
         raise ValueError("word_timestamps aligns the decoded TEXT: pass vocab_path=<local *.tiktoken file>")
     max_batch = int(getattr(model, "max_batch", 1))
@@ -702,6 +713,8 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
     seek = dict(condition_on_previous_text=condition_on_previous_text, no_speech_threshold=no_speech_threshold, logprob_threshold=logprob_threshold)
     words = dict(aligned_unit_type=aligned_unit_type, aggr=aggr, topk=topk, medfilt_width=medfilt_width, w_colnorm=w_colnorm,
                  w_rownorm=w_rownorm, w_coverage=w_coverage, word_confidence=word_confidence) if word_timestamps else None
+    if word_alignment_score:   # (otherwise the aligner is made as it always was)
+        words["word_alignment_score"] = True
     call = _Call(model, language, initial_prompt, vocab_path, decode_options, decode_windows, detect_languages, seek, words,
                  *(() if seed is None else (temperatures, int(seed), compression_ratio_threshold)), group_options=group_options)
     audios = list(audios)
@@ -737,6 +750,9 @@ def parse_args(argv=None):
     p.add_argument("--no_condition_on_previous_text", action="store_true")
     p.add_argument("--word_timestamps", action="store_true")
     p.add_argument("--word_confidence", action="store_true")
+    # (absent from the namespace unless given, like the ladder's options below: the parsed defaults are what they were)
+    p.add_argument("--word_alignment_score", action="store_true", default=argparse.SUPPRESS, help="with --word_timestamps: every word also gets its `alignment_score`, the "
+                   "mean of the aggregated attention matrix along its stretch of the DTW path (in [0, 1]; uncalibrated)")
     add_aligner_options(p)
     p.add_argument("--pieces", type=_pieces_arg, default=None, metavar="N|auto", help="cut every recording at quiet frames into N pieces that are "
                    "decoded side by side (auto: as many as --batch rows allow, at least 60 s each); needs --batch >= N")
@@ -802,6 +818,8 @@ def main(args, model=None):
                   temperature=temperature_ladder(getattr(args, "temperature", 0.0), getattr(args, "temperature_increment_on_fallback", None)))
     elif getattr(args, "temperature", 0.0) != 0.0 or getattr(args, "temperature_increment_on_fallback", None) is not None:
         raise SystemExit("--temperature / --temperature_increment_on_fallback sample: pass --seed <int>")
+    if getattr(args, "word_alignment_score", False):   # (likewise)
+        kw["word_alignment_score"] = True
     for name in ("beam_size", "patience", "length_penalty", "best_of"):   # (likewise: given options only)
         if getattr(args, name, None) is not None:
             kw[name] = getattr(args, name)
