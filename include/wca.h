@@ -15,6 +15,9 @@
  *   wca_mel_window         whisper.pad_or_trim(mel[:, seek : seek + segment_size], N_FRAMES), the window cut of whisper.transcribe's loop
  *   wca_quiet_cuts         no counterpart in the reference or upstream: the quietest even frame near each equal share of a long recording,
  *                          where transcribe(pieces=...) cuts it into pieces that are decoded side by side
+ *   wca_speech_segments    no counterpart in the reference or upstream (faster-whisper's vad_filter runs a neural detector on the host): the
+ *                          frame ranges of a long recording whose smoothed log-mel level stands out of its noise floor, which
+ *                          transcribe(vad_filter=True) decodes instead of every window and force_align_long(trim_silence=...) trims words to
  *   wca_get_attentions     timing.py:45-67   get_attentions(): teacher-forced forward with every
  *                          cross-attention QK captured (timing.py:50-58), [:max_frames] slice,
  *                          median_filter, *qk_scale, softmax (timing.py:63-66); logits returned
@@ -109,7 +112,7 @@ typedef struct {
 } wca_align_opts;
 
 const char* wca_last_error(void);
-int wca_version(void);   /* 18: wca_decode_group (beam search and best_of: G decoder rows per audio, a beam step and a cache reorder on the GPU); 17: one descriptor call each for decode (wca_decode, wca_decode_desc) and the fused alignment (wca_align_desc, wca_align_result) in place of the eleven entry points that had grown feature by feature; 16: the CU-partition and two-stream decode experiments are gone; 15: wca_quiet_cuts (where to cut one long recording into pieces decoded side by side); 14: the open-end DTW entry points; 13: wca_detect_language (the language head on the encoded state; the decode that follows re-uses the state); 12: wca_resample_plan, wca_resample_table, wca_resample_16k (any input rate to 16 kHz); 11: per-row prompts and sample budgets in the decode; 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: prompt / prefix in the decode (sot_index, batched prefill); 7: exactly two precision modes */
+int wca_version(void);   /* 19: wca_speech_segments (the speech segments of a long recording: what transcribe(vad_filter=True) decodes); 18: wca_decode_group (beam search and best_of: G decoder rows per audio, a beam step and a cache reorder on the GPU); 17: one descriptor call each for decode (wca_decode, wca_decode_desc) and the fused alignment (wca_align_desc, wca_align_result) in place of the eleven entry points that had grown feature by feature; 16: the CU-partition and two-stream decode experiments are gone; 15: wca_quiet_cuts (where to cut one long recording into pieces decoded side by side); 14: the open-end DTW entry points; 13: wca_detect_language (the language head on the encoded state; the decode that follows re-uses the state); 12: wca_resample_plan, wca_resample_table, wca_resample_16k (any input rate to 16 kHz); 11: per-row prompts and sample budgets in the decode; 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: prompt / prefix in the decode (sot_index, batched prefill); 7: exactly two precision modes */
 
 /* ---- engine lifetime ------------------------------------------------------------------------ */
 /* A new engine is in the CONTRACT precision mode (WCA_PRECISION_REFERENCE: every stage on (hi, lo) operand pairs = the fp32 forward of
@@ -203,6 +206,45 @@ int wca_mel_window(wca_engine* e, const float* mel_long_dev, int64_t ld, int64_t
  * (the search ranges are then disjoint and inside (0, content_frames)). Synchronous on the engine's stream: the host needs the cuts. */
 int wca_quiet_cuts(wca_engine* e, const float* mel_long_dev, int64_t ld, int64_t content_frames, int n_pieces, int radius, int half_width,
                    int32_t* cuts_host, int32_t* level_host /* nullable */);
+
+/* Speech activity of one long recording: the frame ranges whose level stands out of the recording's own noise floor. An energy detector
+ * with an exact definition, not a trained one: the kernels are bit-exact against it (tests/test_speech_segments_gpu.py), the quality of
+ * the DEFAULTS on real speech is NOT established (one 2.9 s recording was looked at; no corpus). mel_long_dev [n_mels][ld] f32 as
+ * wca_log_mel_long leaves it; with cf = content_frames only frames [0, cf) are read. Integers from the first sum on:
+ *   q(x), e[t], s[t]  exactly wca_quiet_cuts' (the frame index of the box sum clamped to [0, cf - 1]); |s| < 2^30 for n_mels <= 128
+ *   lo, hi            the r-th smallest (0-based) of the multiset {s[t]}, r = floor((cf - 1) floor_permille / 1000) and
+ *                     floor((cf - 1) peak_permille / 1000) in 64-bit
+ *   flat              (hi - lo) < min_range n_mels (2 half_width + 1)                                                   (64-bit)
+ *   on_thr, off_thr   lo + (((hi - lo) on_share) >> 10), lo + (((hi - lo) off_share) >> 10)      (64-bit product; the result fits int32)
+ *   a0[t]             1 if s[t] >= on_thr; 0 if s[t] < off_thr; else a0[t - 1], with a0[-1] = 0                         (hysteresis)
+ *   close             a maximal run of 0 shorter than min_silence with a 1 on BOTH sides becomes 1 (leading / trailing silence never)
+ *   open              then a maximal run of 1 shorter than min_speech becomes 0
+ *   pad               then every run [a, b) becomes [max(0, a - pad), min(cf, b + pad)); runs that overlap OR TOUCH merge
+ *   result            the runs in order as (start, stop) pairs; if flat: the one pair (0, cf), whatever the steps above would give
+ * Consequences: a NaN frame is loud, so it is never dropped; on_thr <= hi, so a recording that is not flat has at least one active frame
+ * before `open`; zero segments is a legal result.
+ * segments_host [max_segments][2] receives the first min(n_segments, max_segments) pairs (NULL is allowed with max_segments 0);
+ * stats_host [6] = {lo, hi, on_thr, off_thr, flat, n_segments}, n_segments being the TRUE count also where it exceeds max_segments (the
+ * call still succeeds; n_segments <= (cf + 1) / 2).
+ * WCA_ERR_INVALID, with nothing launched and nothing written, unless 1 <= cf <= ld, cf < 2^31, max_segments >= 0 and the options are in
+ * range: half_width 0..100, 0 <= floor_permille <= peak_permille <= 1000, 1 <= on_share <= 1023, 0 <= off_share <= on_share, min_range
+ * 0..32768, min_speech and min_silence 1..2^24, pad 0..2^24. The defaults (WCA_VAD_DEFAULTS): 7, 50, 950, 410, 307, 1024 (10 dB averaged
+ * over the mel rows), 25, 200, 40 (faster-whisper's 250 ms / 2 s / 400 ms). Synchronous on the engine's stream: the host needs the pairs.
+ * Nothing returns to the host between the kernels. */
+typedef struct {
+  int32_t half_width;
+  int32_t floor_permille;
+  int32_t peak_permille;
+  int32_t on_share;
+  int32_t off_share;
+  int32_t min_range;
+  int32_t min_speech;
+  int32_t min_silence;
+  int32_t pad;
+} wca_vad_opts;
+#define WCA_VAD_DEFAULTS {7, 50, 950, 410, 307, 1024, 25, 200, 40}
+int wca_speech_segments(wca_engine* e, const float* mel_long_dev, int64_t ld, int64_t content_frames, const wca_vad_opts* opts,
+                        int32_t* segments_host /* nullable with max_segments 0 */, int max_segments, int32_t* stats_host);
 
 /* mel_dev [batch][n_mels][3000] f32; tokens_dev [batch][n_tok] int64 (already sot..eot framed,
  * infer_ali.py:69-76; shorter utterances padded with any valid token id, true lengths in n_tok_host,

@@ -32,6 +32,16 @@ class AlignOpts(C.Structure):
                 ("medfilt_width", C.c_int32), ("qk_scale", C.c_float)]
 
 
+class VadOpts(C.Structure):
+    """wca_vad_opts of include/wca.h; VAD_DEFAULTS is WCA_VAD_DEFAULTS"""
+    _fields_ = [(n, C.c_int32) for n in ("half_width", "floor_permille", "peak_permille", "on_share", "off_share", "min_range", "min_speech",
+                                         "min_silence", "pad")]
+
+
+VAD_DEFAULTS = dict(half_width=7, floor_permille=50, peak_permille=950, on_share=410, off_share=307, min_range=1024, min_speech=25,
+                    min_silence=200, pad=40)
+
+
 class DecodeOpts(C.Structure):
     _fields_ = [("sample_len", C.c_int32), ("eot", C.c_int32), ("timestamp_begin", C.c_int32),
                 ("apply_timestamp_rules", C.c_int32), ("max_initial_timestamp_index", C.c_int32), ("no_speech", C.c_int32)]
@@ -134,6 +144,7 @@ SIGNATURES = {
     "wca_resample_16k": (_i, [_vp, _vp, _i, _i64, _i64, _i, _vp, _i64, C.POINTER(_i64)]),
     "wca_mel_window": (_i, [_vp, _vp, _i64, _i64, _pi32, _pi32, _i, _vp]),
     "wca_quiet_cuts": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _pi32, _pi32]),
+    "wca_speech_segments": (_i, [_vp, _vp, _i64, _i64, C.POINTER(VadOpts), _pi32, _i, _pi32]),
     "wca_get_attentions": (_i, [_vp, _vp, _vp, _i, _i, _pi32, _pi32, _i, _f, _vp, _vp]),
     "wca_median_filter": (_i, [_vp, _vp, _vp, _i64, _i, _i]),
     "wca_filter_attention": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _pf, _pi32, _pf]),

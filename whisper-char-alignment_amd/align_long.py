@@ -45,8 +45,16 @@ The loop's rules
     entry carries "mean_word_score": the mean of the scores of the words it committed, None where it committed none. No decision reads
     either.
 
+  * trim_silence (off by default; without it no result changes): the DTW gives every frame to some unit, so a word's end is the next
+    word's start and a pause counts as part of the word before it. trim_silence=True, or a dict of VAD options, runs the engine's level
+    detector once per recording on the log-mel the loop already has (WhisperAMD.speech_segments; under True with min_speech=5,
+    min_silence=20, pad=3: pad and the shortest silence must be short here, a dict changes single options of these), passes the
+    committed words through timing.trim_words_to_speech at the end -- a word is cut back to the speech its frames meet, a word that meets
+    none is left alone -- and adds "speech_segments": [{"start_frame", "stop_frame"}] to the result. The window loop never sees the
+    segments. An energy detector: music and noise count as speech, and its defaults are UNVALIDATED on real speech.
+
 Limits: 448 framed tokens and 1500 encoder frames per window (the engine's), so at most 446 - len(sot_sequence) units per window; no
-per-word confidence, no silence or music detection, no fallback to ASR for a window that fails, one GPU.
+per-word confidence, no music detection (trim_silence is by level only), no fallback to ASR for a window that fails, one GPU.
 """
 import argparse
 import functools
@@ -247,15 +255,29 @@ def align_group_rows(model, tokenizer, opts, aligned_unit_type, mels, units, sta
     return outs
 
 
+TRIM_SILENCE_OPTIONS = dict(min_speech=5, min_silence=20, pad=3)   # trim_silence=True: pauses between words are short
+
+
+def trim_result(result, segments):
+    """force_align_long's result with its words trimmed to the speech segments (timing.trim_words_to_speech) and "speech_segments" added."""
+    from .timing import trim_words_to_speech
+    return {**result, "words": trim_words_to_speech(result["words"], segments),
+            "speech_segments": [{"start_frame": int(a), "stop_frame": int(b)} for a, b in segments]}
+
+
 def force_align_long_batch(model, audios, texts, *, language, vocab_path, aligned_unit_type="char", sample_rate=SAMPLE_RATE, word_scores=False,
-                           **aligner):
+                           trim_silence=False, **aligner):
     """force_align_long() of several recordings in lock-step: a list with force_align_long()'s result for every (audio, text) pair, in
     order. Every round cuts the next window of every unfinished recording and aligns them in ONE encode_batch + align_batch, whose rows
     may mix open and closed windows; the batch shrinks as recordings end, and more recordings than model.max_batch go in groups of
     max_batch. sample_rate is one int for every array / tensor input or one per recording (a path carries its own rate); aligner: aggr="topk",
     topk=10, medfilt_width=3, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0 (longform.aligner_options). word_scores=True: every word gets
-    a "score" and every window a "mean_word_score" (module docstring)."""
+    a "score" and every window a "mean_word_score" (module docstring). trim_silence=True or a dict of VAD options: the words are trimmed
+    to the recording's speech segments and the result gains "speech_segments" (module docstring)."""
     from .tokenizer import get_tokenizer
+    if trim_silence is not False and trim_silence is not True and not isinstance(trim_silence, dict):
+        raise ValueError("trim_silence is False, True or a dict of VAD options, not %r" % (trim_silence,))
+    vad = None if trim_silence is False else dict(TRIM_SILENCE_OPTIONS, **(trim_silence if isinstance(trim_silence, dict) else {}))
     audios, texts = list(audios), list(texts)
     if len(audios) != len(texts):
         raise ValueError("%d recordings for %d transcripts" % (len(audios), len(texts)))
@@ -273,7 +295,10 @@ def force_align_long_batch(model, audios, texts, *, language, vocab_path, aligne
         mels = [model.log_mel_long(as_pcm(audios[i], model, rates[i])) for i in group]
         states = [AlignState(mel.shape[1], prepared[i][1], prepared[i][2], sot_len, word_scores=word_scores) for i, mel in zip(group, mels)]
         units = [prepared[i][0] for i in group]
-        results.extend(align_loop(states, functools.partial(align_group_rows, model, tokenizer, opts, aligned_unit_type, mels, units, states)))
+        # (one detector call per recording with content, on the mel the loop runs over, before the loop: the words are trimmed at the end)
+        segments = [model.speech_segments(mel, **vad)[0] if mel.shape[1] > N_FRAMES else [] for mel in mels] if vad is not None else None
+        outs = align_loop(states, functools.partial(align_group_rows, model, tokenizer, opts, aligned_unit_type, mels, units, states))
+        results.extend(outs if vad is None else [trim_result(out, seg) for out, seg in zip(outs, segments)])
     return results
 
 
@@ -299,6 +324,8 @@ def parse_args(argv=None):
     # (absent from the namespace unless given: the parsed defaults are what they were)
     p.add_argument("--word_scores", action="store_true", default=argparse.SUPPRESS, help="every word also gets a `score`, the mean of the aggregated attention matrix along "
                    "its stretch of the DTW path (in [0, 1]; uncalibrated), and every window its `mean_word_score`")
+    p.add_argument("--trim_silence", action="store_true", default=argparse.SUPPRESS, help="trim every word to the speech its frames meet (a level "
+                   "detector on the GPU; its defaults are unvalidated on real speech) and add `speech_segments` to the output")
     return p.parse_args(argv)
 
 
@@ -328,6 +355,8 @@ def main(args, model=None):
     kw = dict(language=args.language, vocab_path=args.vocab, sample_rate=args.sample_rate, **{k: getattr(args, k) for k in ALIGNER_KEYWORDS})
     if getattr(args, "word_scores", False):   # (otherwise the call is what it was)
         kw["word_scores"] = True
+    if getattr(args, "trim_silence", False):   # (likewise)
+        kw["trim_silence"] = True
     paths = []
     for group in groups_of(recordings, args.batch):
         texts = [open(t, encoding="utf-8").read() for _a, t in group]

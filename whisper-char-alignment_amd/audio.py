@@ -145,6 +145,15 @@ def resample(audio, sr_in, model=None):
     return model.resample(audio, sr_in)
 
 
+def speech_segments(mel_long, model=None, **vad_options):
+    """The frame ranges of a long recording's log-mel (log_mel_spectrogram_long) that hold speech, by level (WhisperAMD.speech_segments:
+    the options, the returned (segments, stats) and what is and is not validated). mel_long [n_mels, T] f32 on the GPU."""
+    if model is None:
+        from .engine import default_engine
+        model = default_engine(mel_long.device.index or 0 if mel_long.is_cuda else 0)
+    return model.speech_segments(mel_long, **vad_options)
+
+
 # ------------------------------------------------------------------------------ file readers
 def _read_sphere(buf):
     if buf[:7] != b"NIST_1A":

@@ -1,5 +1,6 @@
 // libwca.so engine, audio front end: the resampler to 16 kHz with its table cache (wca_resample_*), the two log-mel forms (wca_log_mel and
-// phase 1's run_logmel; wca_log_mel_long) the window cut wca_mel_window and the quiet cuts wca_quiet_cuts. Host code only: the kernels live in resample.hip / logmel.hip / quiet_cuts.hip.
+// phase 1's run_logmel; wca_log_mel_long) the window cut wca_mel_window, the quiet cuts wca_quiet_cuts and the speech segments wca_speech_segments. Host code only: the kernels
+// live in resample.hip / logmel.hip / quiet_cuts.hip / speech_segments.hip.
 #include "engine_internal.h"
 
 using namespace wca;
@@ -152,6 +153,41 @@ int wca_quiet_cuts(wca_engine* e, const float* mel_long_dev, int64_t ld, int64_t
   memcpy(cuts_host + 1, out.data(), sizeof(int32_t) * (size_t)n);
   cuts_host[n_pieces] = (int32_t)content_frames;
   if (level_host) memcpy(level_host, out.data() + n, sizeof(int32_t) * (size_t)n);
+  return WCA_OK;
+}
+
+int wca_speech_segments(wca_engine* e, const float* mel_long_dev, int64_t ld, int64_t content_frames, const wca_vad_opts* opts,
+                        int32_t* segments_host, int max_segments, int32_t* stats_host) {
+  if (!e || !mel_long_dev || !opts || !stats_host || (!segments_host && max_segments != 0)) return fail(WCA_ERR_INVALID, "null argument");
+  if (max_segments < 0) return fail(WCA_ERR_INVALID, "max_segments %d negative", max_segments);
+  if (content_frames < 1 || content_frames > ld || content_frames > INT32_MAX)
+    return fail(WCA_ERR_INVALID, "content_frames %lld outside [1, min(ld = %lld, 2^31 - 1)]", (long long)content_frames, (long long)ld);
+  const wca_vad_opts& o = *opts;
+  constexpr int DUR_MAX = 1 << 24;
+  if (o.half_width < 0 || o.half_width > QUIET_HALF_WIDTH_MAX) return fail(WCA_ERR_INVALID, "half_width %d outside [0,%d]", o.half_width, QUIET_HALF_WIDTH_MAX);
+  if (o.floor_permille < 0 || o.floor_permille > o.peak_permille || o.peak_permille > 1000)
+    return fail(WCA_ERR_INVALID, "0 <= floor_permille %d <= peak_permille %d <= 1000 does not hold", o.floor_permille, o.peak_permille);
+  if (o.on_share < 1 || o.on_share > 1023 || o.off_share < 0 || o.off_share > o.on_share)
+    return fail(WCA_ERR_INVALID, "0 <= off_share %d <= on_share %d, 1 <= on_share <= 1023 does not hold", o.off_share, o.on_share);
+  if (o.min_range < 0 || o.min_range > 32768) return fail(WCA_ERR_INVALID, "min_range %d outside [0,32768]", o.min_range);
+  if (o.min_speech < 1 || o.min_speech > DUR_MAX || o.min_silence < 1 || o.min_silence > DUR_MAX || o.pad < 0 || o.pad > DUR_MAX)
+    return fail(WCA_ERR_INVALID, "min_speech %d / min_silence %d outside [1,2^24] or pad %d outside [0,2^24]", o.min_speech, o.min_silence, o.pad);
+  if (e->dims.n_mels > 128) return fail(WCA_ERR_INVALID, "n_mels %d > 128: the smoothed level would leave int32", e->dims.n_mels);
+  WCA_TRY(enter(e));
+  const long cap = std::min<long>(max_segments, (content_frames + 1) / 2);   // more runs than that do not fit into content_frames frames
+  HIPCHK(e->vad_buf.ensure(vad_scratch(nullptr, content_frames, cap).bytes));
+  const VadScratch sc = vad_scratch(e->vad_buf.p, content_frames, cap);
+  const VadOpts vo{o.half_width, o.floor_permille, o.peak_permille, o.on_share, o.off_share, o.min_range, o.min_speech, o.min_silence, o.pad};
+  HIPCHK(launch_speech_segments(mel_long_dev, ld, e->dims.n_mels, content_frames, vo, cap, sc, e->stream));
+  int32_t stats[6];
+  HIPCHK(hipMemcpyAsync(stats, sc.stats, sizeof(stats), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  const long n = std::min<long>(stats[5], cap);
+  if (n > 0) {
+    HIPCHK(hipMemcpyAsync(segments_host, sc.segs, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+  }
+  memcpy(stats_host, stats, sizeof(stats));
   return WCA_OK;
 }
 

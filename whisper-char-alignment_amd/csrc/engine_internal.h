@@ -171,7 +171,8 @@ struct wca_engine {
   wca::GrowBuf dtw_out, dtw_meta;   // open-end DTW: end rows [P] then scores [P] of the last launch; wca_dtw_batch_dev_open's flags / row / column counts
   wca::GrowBuf pscore;              // run_path_score: the per-row path means [P][ld] f32, then the cell counts [P][ld], of the last DTW launch that asked for them
   wca::GrowBuf quiet_out;           // wca_quiet_cuts: the interior cuts [n_pieces - 1] then their levels [n_pieces - 1], copied to the host before the call returns
-  wca::GrowBuf probe_jump;          // the last wca_probe_heads' jump frames [LH][N], kept on the device for wca_probe_strict_tp
+  wca::GrowBuf vad_buf;             // wca_speech_segments: the call's whole device scratch (VadScratch), result included
+  wca::GrowBuf probe_jump;         // the last wca_probe_heads' jump frames [LH][N], kept on the device for wca_probe_strict_tp
   int probe_LH = 0, probe_N = 0;
   // greedy ASR pre-pass (wca_decode): self-attention K/V cache [L][2][B][T_max][d], token rows, masks, logits
   wca::GrowBuf dec_cache, dec_tokens, dec_masks, dec_logits, dec_state;

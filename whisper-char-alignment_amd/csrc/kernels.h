@@ -338,6 +338,29 @@ constexpr int QUIET_PIECES_MAX = 4096, QUIET_RADIUS_MAX = 1500, QUIET_HALF_WIDTH
 hipError_t launch_quiet_cuts(const float* mel_long, long ld, int n_mels, long content_frames, int n_pieces, int radius, int half_width,
                              int* cuts, int* level, hipStream_t s);
 
+// ---------------------------------------------------------------- speech segments of a long recording (speech_segments.hip)
+// The options of wca_speech_segments, in the order of wca_vad_opts (include/wca.h has the definition and the ranges).
+struct VadOpts {
+  int half_width, floor_permille, peak_permille, on_share, off_share, min_range, min_speech, min_silence, pad;
+};
+// The device scratch of one call, carved out of one allocation: vad_scratch(nullptr, ...) gives the size in `bytes`, a second call with
+// the allocation's base the pointers. cap = the (start, stop) pairs `segs` holds.
+struct VadScratch {
+  int *e, *s;                    // [cf] frame levels and smoothed levels
+  unsigned char *f0, *f1;        // [cf] the activity flags of the stages, ping-pong
+  int *agg_last, *agg_first;     // [tiles] per tile of VAD_TILE frames: the last / first frame the next stage's scan starts from
+  int *carry_f, *carry_b;        // [tiles + 1] what enters a tile from the tiles before / after it
+  unsigned *hist, *sel;          // [2][256] radix histograms of both ranks; {prefix lo, prefix hi, rank lo, rank hi}
+  int *stats, *segs;             // [6] as stats_host; [cap][2]
+  size_t bytes;
+};
+constexpr int VAD_TILE = 1024;
+VadScratch vad_scratch(void* base, long content_frames, long cap);
+// Everything of wca_speech_segments on the device, with no return to the host in between: sc.stats and sc.segs hold the result.
+// The caller has checked the ranges of include/wca.h, n_mels <= 128 and 1 <= content_frames <= ld.
+hipError_t launch_speech_segments(const float* mel_long, long ld, int n_mels, long content_frames, const VadOpts& o, long cap,
+                                  const VadScratch& sc, hipStream_t s);
+
 // ---------------------------------------------------------------- resampler to 16 kHz (resample.hip)
 constexpr int RESAMPLE_SR_OUT = 16000, RESAMPLE_SR_MIN = 2000, RESAMPLE_SR_MAX = 384000;
 enum { RESAMPLE_HOME_UNIFORM = 0, RESAMPLE_HOME_LDS = 1, RESAMPLE_HOME_GLOBAL = 2 };   // where the kernel reads the polyphase table from

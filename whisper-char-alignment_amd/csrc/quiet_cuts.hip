@@ -9,6 +9,7 @@
 //                 can see go to LDS (lanes stride over frames, so every mel row is read coalesced), then every even candidate sums its
 //                 window from LDS and the three-part key, packed into one 64-bit integer, is reduced by shuffles and through LDS.
 #include "kernels.h"
+#include "level_quant.h"
 #include "wca_common.h"
 
 namespace wca {
@@ -17,11 +18,6 @@ namespace {
 
 constexpr int QC_WAVES = 4;
 constexpr int QC_SPAN_MAX = 2 * QUIET_RADIUS_MAX + 1 + 2 * QUIET_HALF_WIDTH_MAX;   // 3201 frame levels, 12.5 KiB of LDS
-
-__device__ __forceinline__ int quantise(float x) {
-  const float c = (x != x) ? 8.0f : fminf(fmaxf(x, -8.0f), 8.0f);
-  return __float2int_rn(4096.0f * c);   // (the product is exact: a power of two, |c| <= 8)
-}
 
 __global__ __launch_bounds__(QC_WAVES * 64) void quiet_cuts_kernel(const float* __restrict__ mel, long ld, int n_mels, long content_frames,
                                                                   int n_pieces, int radius, int half_width, int* __restrict__ cuts,

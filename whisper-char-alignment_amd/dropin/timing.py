@@ -14,4 +14,5 @@ path_scores = _t.path_scores
 word_alignment_scores = _t.word_alignment_scores
 force_align_long = _t.force_align_long
 force_align_long_batch = _t.force_align_long_batch
+trim_words_to_speech = _t.trim_words_to_speech
 HOP_LENGTH, SAMPLE_RATE, TOKENS_PER_SECOND = _t.HOP_LENGTH, _t.SAMPLE_RATE, _t.TOKENS_PER_SECOND

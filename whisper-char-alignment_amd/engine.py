@@ -397,6 +397,35 @@ class WhisperAMD:
                                             cuts.ctypes.data_as(_lib._pi32), levels.ctypes.data_as(_lib._pi32)))
         return [int(v) for v in cuts], [int(v) for v in levels[:n - 1]]
 
+    def speech_segments(self, mel_long, content_frames=None, **vad_options):
+        """Speech activity of a long recording (C ABI wca_speech_segments; include/wca.h has the exact definition): the frame ranges whose
+        smoothed log-mel level stands out of the recording's own noise floor, after hysteresis, closing of short gaps, removal of short
+        runs and padding. mel_long [n_mels, T] f32 cuda as log_mel_long leaves it; content_frames defaults to T - 3000. vad_options:
+        half_width, floor_permille, peak_permille, on_share, off_share, min_range, min_speech, min_silence, pad (_lib.VAD_DEFAULTS; the
+        durations in frames of 10 ms). Returns (segments: list of (start, stop) frames, in order, never truncated; stats: {"lo", "hi",
+        "on_thr", "off_thr", "flat", "n_segments"}). A recording whose level range is below min_range is "flat": one segment (0,
+        content_frames). The kernels are exact against the definition; the defaults' quality on real speech is not established."""
+        unknown = set(vad_options) - set(_lib.VAD_DEFAULTS)
+        if unknown:
+            raise ValueError("unknown VAD option(s) %s; the options are %s" % (sorted(unknown), list(_lib.VAD_DEFAULTS)))
+        if mel_long.dim() != 2 or mel_long.shape[0] != self.dims.n_mels or mel_long.dtype != torch.float32 or mel_long.stride(1) != 1:
+            raise ValueError("mel_long must be an f32 [n_mels, T] tensor with unit frame stride")
+        mel_long = mel_long.to(self.device)
+        if content_frames is None:
+            content_frames = mel_long.shape[1] - N_FRAMES
+        content_frames = int(content_frames)
+        if content_frames > mel_long.shape[1]:
+            raise ValueError("content_frames %d beyond the %d frames of mel_long" % (content_frames, mel_long.shape[1]))
+        opts = _lib.VadOpts(**{k: int(v) for k, v in dict(_lib.VAD_DEFAULTS, **vad_options).items()})
+        cap = (max(content_frames, 0) + 1) // 2   # more runs than that do not fit
+        pairs = np.zeros((max(cap, 1), 2), dtype=np.int32)
+        stats = np.zeros(6, dtype=np.int32)
+        self._bind_stream()
+        _lib.check(self._lib.wca_speech_segments(self._h, _ptr(mel_long), mel_long.stride(0), content_frames, C.byref(opts),
+                                                 pairs.ctypes.data_as(_lib._pi32), cap, stats.ctypes.data_as(_lib._pi32)))
+        names = ("lo", "hi", "on_thr", "off_thr", "flat", "n_segments")
+        return [(int(a), int(b)) for a, b in pairs[:int(stats[5])]], {k: int(v) for k, v in zip(names, stats)}
+
     def transcribe(self, audio, **kw):
         """whisper.transcribe(model, audio, ...) at temperature 0 with this project's word aligner (transcribe.transcribe)."""
         from . import transcribe as _t

@@ -132,6 +132,25 @@ def force_align_long_batch(model, audios, texts, **kw):
     return align_long.force_align_long_batch(model, audios, texts, **kw)
 
 
+def trim_words_to_speech(words, segments):
+    """Pause-aware word times: the DTW gives every frame to some unit, so a word's end is the next word's start and a pause counts as
+    part of the word before it. words: [{"start", "end", ...}] in seconds; segments: (start, stop) frame pairs of 10 ms in order, as
+    WhisperAMD.speech_segments returns them. Word by word, with a = round(start * 100) and b = round(end * 100): if segments intersect
+    [a, b) the word becomes [max(a, start of the first of them), min(b, stop of the last of them)) / 100; otherwise, and where start or
+    end is None, the word is unchanged. Returns new dicts; no other key is touched."""
+    out = []
+    for w in words:
+        w = dict(w)
+        out.append(w)
+        if w.get("start") is None or w.get("end") is None:
+            continue
+        a, b = round(w["start"] * 100), round(w["end"] * 100)
+        met = [(int(x), int(y)) for x, y in segments if x < b and y > a]
+        if met:
+            w["start"], w["end"] = max(a, met[0][0]) / 100, min(b, met[-1][1]) / 100
+    return out
+
+
 def median_filter(x, filter_width):
     """whisper.timing.median_filter drop-in (reflect padding, last axis)."""
     x = _as_cuda_f32(x)

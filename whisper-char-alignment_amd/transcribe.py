@@ -53,8 +53,15 @@ Limits (part of the contract):
     text around it on real speech -- a word split where no quiet frame was in reach, a piece that starts without the context the
     sequential loop would have carried over -- is UNVALIDATED: no checkpoint is at hand here, the tests run on random weights and compare
     pieces=N with the same ranges given as clip_timestamps.
+  * vad_filter=True (off by default; faster-whisper's and WhisperX's keyword, not upstream's) finds the speech first and decodes only
+    that: the recording's log-mel goes through the engine's level detector (WhisperAMD.speech_segments, C ABI wca_speech_segments: a noise
+    floor and a peak from two order statistics of the smoothed level, hysteresis, minimum durations, padding; all on the GPU, exact
+    against its integer definition) and the segments it returns are the clips of the seek loop, the mechanism clip_timestamps uses, so
+    segment and word times stay absolute. It is an ENERGY detector, not a trained one: music and loud noise count as speech, and the
+    quality of its defaults on real speech is UNVALIDATED (they were looked at on one 2.9 s recording laid out between stretches of
+    silence; no corpus is at hand). Not together with clip_timestamps or pieces.
   * hallucination_silence_threshold, prepend_punctuations / append_punctuations are not built (they belong to upstream's own word
-    aligner).
+    aligner); vad_filter is this project's remedy for text invented over silence.
 
 Decisions the upstream text leaves open:
   * a window that ended inside speech (its tokens do not end in a single timestamp; seek advances to the last consecutive
@@ -430,7 +437,9 @@ def transcribe(model, audio, *, language, decode_window=None, **options):
     those ranges are transcribed, one after the other. pieces: an int or "auto" (plan_pieces): the recording is cut at quiet frames
     (WhisperAMD.quiet_cuts) into that many pieces, which are decoded side by side as the rows of ONE batch per round; every piece starts
     from initial_prompt only and conditions on its own previous text. The result then carries "pieces" and every window its "piece"
-    (transcribe_batch has the details). pieces and clip_timestamps together are a ValueError.
+    (transcribe_batch has the details). pieces and clip_timestamps together are a ValueError. vad_filter=True (with vad_options, a dict, or
+    None for the defaults): only the speech segments the engine's level detector finds are decoded, and the result gains
+    "speech_segments" and "vad" (transcribe_batch has the details; not together with clip_timestamps or pieces).
     decode_window(mel_window, prompt_tokens) -> DecodingResult replaces the engine's greedy decode (tests; with pieces it is called row by
     row; with seed= it is also given temperature= and seed=, transcribe_batch's temperatures= / seeds= for its row); decode_options go to DecodingOptions. Limits: module docstring. It is transcribe_batch of one recording, whose single row is
     decoded and aligned alone. The other keywords and their defaults are transcribe_batch's."""
@@ -533,10 +542,18 @@ class _Call:
         return decoding.decode(self.model, mel_windows, rows, want_text=want_text)
 
 
-def plan_recording(mel, clip_timestamps, pieces, max_batch, model):
+def plan_recording(mel, clip_timestamps, pieces, max_batch, model, vad=None):
     """What one recording contributes to the lock-step loop: (clips, pieces). clips: one SeekState(clips=...) argument per decode row it
-    takes; pieces: the result's "pieces" entry (None unless pieces were asked for)."""
+    takes; pieces: the result's "pieces" entry (None unless pieces were asked for). vad (None, or the VAD options of vad_filter=True): the
+    clips are the speech segments model.speech_segments finds in the mel, and a third entry holds the keys the result gains,
+    {"speech_segments": [{"start_frame", "stop_frame"}], "vad": the stats}."""
     content = mel.shape[1] - N_FRAMES
+    if vad is not None:
+        if clip_timestamps is not None or pieces is not None:
+            raise ValueError("vad_filter chooses the frame ranges itself: it cannot be combined with clip_timestamps or pieces")
+        segments, stats = model.speech_segments(mel, **vad) if content >= 1 else ([], None)
+        return ([[(int(a), int(b)) for a, b in segments]], None,
+                {"speech_segments": [{"start_frame": int(a), "stop_frame": int(b)} for a, b in segments], "vad": stats})
     if clip_timestamps is not None:
         return [clip_frames(clip_timestamps, content)], None
     if pieces is None:
@@ -548,25 +565,25 @@ def plan_recording(mel, clip_timestamps, pieces, max_batch, model):
             [{"start_frame": cuts[k], "stop_frame": cuts[k + 1], "level": levels[k]} for k in range(n)])
 
 
-def _prepared(model, audio, rate, clip_timestamps, pieces, max_batch):
+def _prepared(model, audio, rate, clip_timestamps, pieces, max_batch, vad=None):
     mel = model.log_mel_long(as_pcm(audio, model, rate))
-    return mel, plan_recording(mel, clip_timestamps, pieces, max_batch, model)
+    return mel, plan_recording(mel, clip_timestamps, pieces, max_batch, model, vad)
 
 
-def form_groups(model, audios, rates, clip_timestamps, pieces, max_batch):
+def form_groups(model, audios, rates, clip_timestamps, pieces, max_batch, vad=None):
     """The groups of recordings that share the decode batch: yields (indices, mels, plans), mels and plans by index. A group holds as
     many recordings as their decode rows fit into max_batch (without pieces: max_batch recordings). A recording's log-mel is computed as
     it joins its group -- or one recording ahead, where the rows it takes depend on its length (pieces="auto") -- and is dropped when the
     next group is asked for: both dicts are valid until then."""
     group, mels, plans, used = [], {}, {}, 0
     for i, (audio, rate) in enumerate(zip(audios, rates)):
-        ahead = _prepared(model, audio, rate, clip_timestamps, pieces, max_batch) if isinstance(pieces, str) else None
+        ahead = _prepared(model, audio, rate, clip_timestamps, pieces, max_batch, vad) if isinstance(pieces, str) else None
         rows = 1 if pieces is None else len(ahead[1][0]) if ahead is not None else int(pieces)   # decode rows it takes in a round
         if group and used + rows > max_batch:
             yield group, mels, plans
             group, used = [], 0
             mels.clear(), plans.clear()
-        mels[i], plans[i] = ahead or _prepared(model, audio, rate, clip_timestamps, pieces, max_batch)
+        mels[i], plans[i] = ahead or _prepared(model, audio, rate, clip_timestamps, pieces, max_batch, vad)
         group.append(i)
         used += rows
     if group:
@@ -576,13 +593,17 @@ def form_groups(model, audios, rates, clip_timestamps, pieces, max_batch):
 def detect_group(call, group, mels, plans):
     """language="auto" for one group, its first windows detected in ONE batch: (codes, extra) by recording, the language code (None
     where there was no window to look at) and {"language_probability": p}. The state detection left in the engine is dropped unless the
-    detected rows are the first round's rows: one language, every recording heard, none with clips or pieces."""
+    detected rows are the first round's rows: one language, every recording heard, none with clips or pieces. With vad_filter the window
+    starts at the first speech segment's start (an intro of silence is what a detection on frame 0 gets wrong), and a recording without
+    a segment has no window."""
     codes, extra = {i: None for i in group}, {i: {"language_probability": None} for i in group}
-    heard = [i for i in group if mels[i].shape[1] > N_FRAMES]   # recordings that have a first window
+    first = {i: plans[i][0][0][0][0] if plans[i][0][0] else None for i in group if len(plans[i]) > 2}   # vad_filter: where speech starts
+    heard = [i for i in group if mels[i].shape[1] > N_FRAMES and first.get(i, 0) is not None]   # recordings that have a first window
     if call.detect_languages is None and call.detect_tokenizer is None:   # an English-only model: "en" without a detection pass, as upstream
         codes.update({i: "en" for i in heard})
     elif heard:
-        found, probs = call.detect(cut_windows(call.model, mels, [(i, 0, min(N_FRAMES, mels[i].shape[1] - N_FRAMES)) for i in heard]))
+        found, probs = call.detect(cut_windows(call.model, mels, [(i, first.get(i, 0), min(N_FRAMES, mels[i].shape[1] - N_FRAMES - first.get(i, 0)))
+                                                                  for i in heard]))
         for i, code, prob in zip(heard, found, probs):
             codes[i], extra[i] = code, {"language_probability": None if prob is None else float(prob)}
     if len(set(codes.values())) != 1 or heard != group or any(plans[i][0] != [None] for i in group):
@@ -636,7 +657,8 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
                      logprob_threshold=-1.0, word_timestamps=False, word_confidence=False, aligned_unit_type="char", aggr="topk", topk=10,
                      medfilt_width=3, word_alignment_score=False, vocab_path=None, temperature=0.0, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0, decode_windows=None,
                      detect_languages=None, sample_rate=SAMPLE_RATE, clip_timestamps=None, pieces=None, seed=None,
-                     compression_ratio_threshold=2.4, beam_size=None, patience=None, length_penalty=None, best_of=None, **decode_options):
+                     compression_ratio_threshold=2.4, beam_size=None, patience=None, length_penalty=None, best_of=None, vad_filter=False,
+                     vad_options=None, **decode_options):
     """transcribe() of several recordings in lock-step: a list with transcribe()'s result for every recording of `audios`, in order.
     Each round cuts the next window of every unfinished recording, decodes them in ONE batch with every row's own previous text as its
     prompt (decoding.decode with one DecodingOptions per row: wca_decode with per_row 1) and, with word_timestamps, aligns the rows that
@@ -662,6 +684,12 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
     at, None for the first. language="auto" still detects on the recording's first window and all its pieces take that language; the first
     round then has other rows than the detection saw, so the state detection left in the engine is simply dropped and the round encodes
     its own windows. Without pieces and clip_timestamps the result is what it was before either existed.
+    vad_filter (False: no key is added and no kernel launched; not together with clip_timestamps or pieces): every recording's speech
+    segments (WhisperAMD.speech_segments on its log-mel, with vad_options: a dict of its options, None for the defaults) are the clips its
+    loop runs over, so silence is never decoded; times stay absolute. The result gains "speech_segments": [{"start_frame", "stop_frame"}]
+    and "vad": the detector's stats. language="auto" then detects on the window that starts at the first segment, and a recording
+    without a segment reports "language": None. The detector is exact against its definition; its defaults are UNVALIDATED on real
+    speech (module docstring).
     seed (an int; None: temperature 0.0 only, every call as it always was) switches on upstream's temperature fallback: temperature may
     then be a number or a tuple such as upstream's default (0.0, 0.2, 0.4, 0.6, 0.8, 1.0), and a window whose result is too repetitive
     (compression_ratio > compression_ratio_threshold) or too improbable (avg_logprob < logprob_threshold), and not taken for silence, is
@@ -695,6 +723,12 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
                                        grouped=True)
     if pieces is not None and clip_timestamps is not None:
         raise ValueError("pieces cuts the whole recording: it cannot be combined with clip_timestamps")
+    if vad_filter and (clip_timestamps is not None or pieces is not None):
+        raise ValueError("vad_filter chooses the frame ranges itself: it cannot be combined with clip_timestamps or pieces (cutting pieces "
+                         "inside speech only is not built)")
+    if vad_options is not None and not vad_filter:
+        raise ValueError("vad_options are the options of vad_filter=True")
+    vad = dict(vad_options or {}) if vad_filter else None
     if word_confidence and not word_timestamps:
         raise ValueError("word_confidence is a property of the aligned words: it needs word_timestamps=True")
     if word_alignment_score and not word_timestamps:
@@ -719,7 +753,7 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
                  *(() if seed is None else (temperatures, int(seed), compression_ratio_threshold)), group_options=group_options)
     audios = list(audios)
     results = [None] * len(audios)
-    for group, mels, plans in form_groups(model, audios, sample_rates(sample_rate, len(audios)), clip_timestamps, pieces, max_batch):
+    for group, mels, plans in form_groups(model, audios, sample_rates(sample_rate, len(audios)), clip_timestamps, pieces, max_batch, vad):
         codes, extra = detect_group(call, group, mels, plans) if call.auto else ({i: language for i in group}, {})
         for code in dict.fromkeys(codes[i] for i in group):   # one decode cannot mix languages: the loop runs once per language
             rows = [i for i in group if codes[i] == code]
@@ -727,11 +761,25 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
             for i in rows:
                 outs = [states[(i, k)].result() for k in range(len(plans[i][0]))]
                 results[i] = merge_pieces(outs, plans[i][1], tokenizer=call.tokenizer_for(code) if vocab_path is not None else None,
-                                          language=code, extra=extra.get(i, {}), n_prompt=len(call.prompt_tokens))
+                                          language=code, extra={**extra.get(i, {}), **(plans[i][2] if len(plans[i]) > 2 else {})},
+                                          n_prompt=len(call.prompt_tokens))
     return results
 
 
 # ------------------------------------------------------------------------------------------------ command line
+VAD_OPTION_HELP = {   # the options of WhisperAMD.speech_segments (include/wca.h: wca_vad_opts), durations in frames of 10 ms
+    "half_width": "the level is smoothed over 2 half_width + 1 frames (default 7)",
+    "floor_permille": "the noise floor is this permille quantile of the level (default 50)",
+    "peak_permille": "the peak is this permille quantile of the level (default 950)",
+    "on_share": "speech starts above floor + on_share / 1024 of the range (default 410)",
+    "off_share": "and ends below floor + off_share / 1024 of the range (default 307)",
+    "min_range": "a range below this, in 1/4096 of a log-mel unit per mel row, is no speech / silence contrast: nothing is dropped (default 1024)",
+    "min_speech": "shorter runs of speech are dropped (default 25)",
+    "min_silence": "shorter gaps between speech are closed (default 200)",
+    "pad": "every run is widened by this on both sides (default 40)",
+}
+
+
 def _pieces_arg(value):
     return "auto" if value.lower() == "auto" else int(value)
 
@@ -772,6 +820,11 @@ def parse_args(argv=None):
     p.add_argument("--patience", type=float, help="the search ends after round(beam_size * patience) finished sequences (default 1.0)", **ladder)
     p.add_argument("--length_penalty", type=float, help="alpha of the ranker's length normalisation (default: none, sum / length)", **ladder)
     p.add_argument("--best_of", type=int, help="independent samples per window on the rungs above temperature 0 (needs --seed)", **ladder)
+    # speech activity first (likewise absent unless given): --vad_filter, and one option per parameter of the detector
+    p.add_argument("--vad_filter", action="store_true", help="find the speech first (a level detector on the GPU) and decode only that; its "
+                   "defaults are unvalidated on real speech", **ladder)
+    for name, text in VAD_OPTION_HELP.items():
+        p.add_argument("--vad_" + name, type=int, help="with --vad_filter: " + text, **ladder)
     return p.parse_args(argv)
 
 
@@ -804,6 +857,11 @@ def main(args, model=None):
         raise SystemExit("--pieces %d needs --batch >= %d: every piece is one row of the decode batch" % (args.pieces, args.pieces))
     if args.pieces is not None and args.clip_timestamps is not None:
         raise SystemExit("--pieces cuts the whole recording: it cannot be combined with --clip_timestamps")
+    vad_options = {name: getattr(args, "vad_" + name) for name in VAD_OPTION_HELP if getattr(args, "vad_" + name, None) is not None}
+    if vad_options and not getattr(args, "vad_filter", False):
+        raise SystemExit("--vad_%s is an option of --vad_filter" % next(iter(vad_options)))
+    if getattr(args, "vad_filter", False) and (args.pieces is not None or args.clip_timestamps is not None):
+        raise SystemExit("--vad_filter chooses the frame ranges itself: it cannot be combined with --pieces or --clip_timestamps")
     if model is None:
         model = load_model(args)
     os.makedirs(args.output_dir, exist_ok=True)
@@ -820,6 +878,10 @@ def main(args, model=None):
         raise SystemExit("--temperature / --temperature_increment_on_fallback sample: pass --seed <int>")
     if getattr(args, "word_alignment_score", False):   # (likewise)
         kw["word_alignment_score"] = True
+    if getattr(args, "vad_filter", False):   # (likewise)
+        kw["vad_filter"] = True
+        if vad_options:
+            kw["vad_options"] = vad_options
     for name in ("beam_size", "patience", "length_penalty", "best_of"):   # (likewise: given options only)
         if getattr(args, name, None) is not None:
             kw[name] = getattr(args, name)
