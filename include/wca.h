@@ -34,6 +34,10 @@
  *                          no counterpart in the reference or upstream (their aligners stop at one 30 s window): the OPEN-END form
  *                          of the same DTW, for a window of a long recording that holds only a prefix of the text it is offered
  *                          (align_long.py: a recording of any length against a given transcript)
+ *   wca_dtw_windows, wca_dtw_batch_dev_windows, wca_align_batch_enqueue_windows, wca_align_batch_windows
+ *                          no counterpart in the reference or upstream: the WINDOWED form of the same DTW, in which every text row
+ *                          has a permitted frame interval (align_long.py force_align_cues: a recording against its subtitles, whose
+ *                          cue times bound where each cue's text may lie)
  *   wca_probe_heads        probe_oracle.py:83-90  per-head force_align sweep (one DTW per head)
  *   wca_decode             infer_ali.py:40,60-61, probe_oracle.py:59-60, README.md:107-108:
  *                          whisper.decode(model, mels, DecodingOptions(language="en")) -- the greedy ASR pre-pass
@@ -330,6 +334,23 @@ int wca_dtw_path_scores(wca_engine* e, const float* matrix_dev, int P, int N, in
                         const int32_t* open_end_host, int32_t* jump_frame_host, int32_t* end_row_host, float* path_mean_host,
                         int32_t* path_cells_host);
 
+/* Windowed DTW: wca_dtw in which text row i may only sit at the frames row_lo[i] <= j <= row_hi[i]. The recurrence, the f64-add / f32-store
+ * and the tie rule are wca_dtw's; a cell outside its row's window costs +inf and the matrix is not modified. One exception to the tie rule:
+ * where it chose "left", the left cost is +inf and the diagonal and upper costs are equal and finite (the left edge of a row's window under
+ * an exact 0), the move is "up". Without windows that case cannot occur, so full windows [0, M-1] give wca_dtw's path bit for bit.
+ * The windows are checked on the host before anything is launched; WCA_ERR_INVALID unless, for every problem (n rows, m columns):
+ * 0 <= lo[i] <= hi[i] <= m-1, lo[0] == 0, hi[n-1] == m-1, lo and hi non-decreasing, lo[i+1] <= hi[i] + 1 -- which guarantees a finite path
+ * from (0, 0) to (n-1, m-1) inside the windows. row_lo_host / row_hi_host [N] int32. Limits as wca_dtw (N <= 512, M <= 4096). */
+int wca_dtw_windows(wca_engine* e, const float* matrix_host, int N, int M, const int32_t* row_lo_host, const int32_t* row_hi_host,
+                    int32_t* text_idx_host, int32_t* time_idx_host, int32_t* path_len_host);
+
+/* wca_dtw_batch_dev with windows: P closed problems, ragged through n_rows_host / n_cols_host [P] (each nullable) as in
+ * wca_dtw_batch_dev_open. row_lo_host / row_hi_host [P][N] (row stride N): only the first n_rows[p] entries of problem p are read.
+ * jump_frame_host [P][N]: the frame at which the path enters each row, 0 beyond n_rows[p]. The result of a problem does not depend on P or
+ * on its position. */
+int wca_dtw_batch_dev_windows(wca_engine* e, const float* matrix_dev, int P, int N, int M, const int32_t* n_rows_host, const int32_t* n_cols_host,
+                              const int32_t* row_lo_host, const int32_t* row_hi_host, int32_t* jump_frame_host);
+
 /* probe_oracle.py:83-90: one alignment PER HEAD (aggregation "mean" on a single head = column
  * normalisation only), all L*H DTWs in one launch. ws_dev [L][H][n][F]; scores_host [L*H] = the
  * filter_attention scores (w_col = w_row = 1); jump_frame_host [L*H][n - sot_len - 1]. */
@@ -390,6 +411,15 @@ typedef struct {
 int wca_align_batch_enqueue(wca_engine* e, const wca_align_desc* d);
 int wca_align_batch_fetch(wca_engine* e, int batch, int n_tok_max, int topk, const wca_align_result* r);
 int wca_align_batch(wca_engine* e, const wca_align_desc* d, const wca_align_result* r);
+/* wca_align_batch_enqueue / wca_align_batch with row windows for the DTW (wca_dtw_windows); the entry points above are these with null
+ * windows. row_lo_host / row_hi_host [batch][n_tok_max] int32 (row stride n_tok_max; both or neither), counted in DTW rows -- entry 0 of
+ * row b belongs to the first token after the sot sequence and no_timestamps, entry n_tok[b] - sot_len - 2 to the eot, later entries are not
+ * read -- and in encoder frames of that row's max_frames. They are checked on the host before anything is enqueued (WCA_ERR_INVALID, and
+ * nothing is consumed), and a row with open_end_host[b] != 0 takes full windows [0, max_frames[b] - 1] only: one batch may mix open rows and
+ * windowed closed ones. path_scores, vocab_end and open_end_host work as without windows; everything upstream of the DTW is unchanged. */
+int wca_align_batch_enqueue_windows(wca_engine* e, const wca_align_desc* d, const int32_t* row_lo_host, const int32_t* row_hi_host);
+int wca_align_batch_windows(wca_engine* e, const wca_align_desc* d, const int32_t* row_lo_host, const int32_t* row_hi_host,
+                            const wca_align_result* r);
 /* The path scores of the OLDEST pending batch, which must have been enqueued with path_scores != 0 (WCA_ERR_STATE otherwise, or when nothing
  * is pending): waits for that batch like the fetch, copies path_mean_host / path_cells_host [batch][n_tok_max] -- laid out like
  * jump_frame_host: entry i of row b belongs to DTW row i, 0 beyond the DTW's rows -- and does NOT consume the batch: the

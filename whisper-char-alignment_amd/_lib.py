@@ -157,10 +157,14 @@ SIGNATURES = {
     "wca_dtw_batch_dev": (_i, [_vp, _vp, _i, _i, _i, _pi32]),
     "wca_dtw_open": (_i, [_vp, _pf, _i, _i, _pi32, _pi32, _pi32, _pi32, _pf]),
     "wca_dtw_batch_dev_open": (_i, [_vp, _vp, _i, _i, _i, _pi32, _pi32, _pi32, _pi32, _pi32, _pf]),
+    "wca_dtw_windows": (_i, [_vp, _pf, _i, _i, _pi32, _pi32, _pi32, _pi32, _pi32]),
+    "wca_dtw_batch_dev_windows": (_i, [_vp, _vp, _i, _i, _i, _pi32, _pi32, _pi32, _pi32, _pi32]),
     "wca_dtw_path_scores": (_i, [_vp, _vp, _i, _i, _i, _pi32, _pi32, _pi32, _pi32, _pi32, _pf, _pi32]),
     "wca_probe_heads": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _pf, _pi32]),
     "wca_align_batch": (_i, [_vp, C.POINTER(AlignDesc), C.POINTER(AlignResult)]),
     "wca_align_batch_enqueue": (_i, [_vp, C.POINTER(AlignDesc)]),
+    "wca_align_batch_windows": (_i, [_vp, C.POINTER(AlignDesc), _pi32, _pi32, C.POINTER(AlignResult)]),
+    "wca_align_batch_enqueue_windows": (_i, [_vp, C.POINTER(AlignDesc), _pi32, _pi32]),
     "wca_align_batch_fetch": (_i, [_vp, _i, _i, _i, C.POINTER(AlignResult)]),
     "wca_align_batch_path_scores": (_i, [_vp, _i, _i, _pf, _pi32]),
     "wca_token_logprobs": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -18,6 +18,15 @@
 // comparison is exact: row a beats row b iff (double)C_a * L_b < (double)C_b * L_a (C has 24 significant bits and L < 2^13, so both
 // products are exact in f64), equal scores go to the lower row. Lane 0 then backtraces from (n*, M-1). The closed instantiations carry
 // none of this: `if constexpr` keeps their registers and shuffles what they were.
+//
+// WIN (the windowed form, for text rows whose frames are known to within an interval: subtitle cues): cell (i, j) is allowed iff
+// row_lo[p][i] <= j <= row_hi[p][i]; a cell that is not allowed stores C = +inf (its trace bits are unspecified: no backtrace reaches
+// it), and the matrix is never modified. Each lane loads the lo / hi of its R rows into registers once, before the sweep; every sweep
+// step still runs. One exception to the tie rule: where it chose left, c2 is +inf and c0 == c1 is finite (the left edge of a row's window
+// under an exact 0 in the matrix), the move is UP -- left would make a reachable cell infinite. Without windows c2 = +inf only in column
+// 0, where c0 is +inf too, so full windows are bit-identical to the closed form. The host checks the windows before the launch
+// (dtw_windows_valid): they then hold a finite path from (0, 0) to (N-1, M-1). WIN together with OPEN serves launches that mix open
+// problems (full windows only, the host's check again) with windowed closed ones.
 #include "kernels.h"
 #include "wca_common.h"
 
@@ -34,7 +43,7 @@ __device__ __forceinline__ bool end_row_beats(float Ca, int La, int ia, float Cb
   return pa < pb || (pa == pb && ia < ib);
 }
 
-template <int R, int U, bool OPEN>
+template <int R, int U, bool OPEN, bool WIN>
 __global__ __launch_bounds__(64) void dtw_kernel(DtwArgs a) {
   const int p = blockIdx.x;
   const int lane = threadIdx.x;
@@ -58,6 +67,19 @@ __global__ __launch_bounds__(64) void dtw_kernel(DtwArgs a) {
   uint32_t* __restrict__ tr = a.trace + (long)p * a.N_max * wpr;
 
   const int i0 = lane * R;
+  // WIN: the permitted frame interval of each of this lane's rows (rows past N repeat row N - 1's: their cells are never stored)
+  int wlo[WIN ? R : 1], whi[WIN ? R : 1];
+  if constexpr (WIN) {
+    const int* __restrict__ rlo = a.row_lo + (long)p * a.win_ld;
+    const int* __restrict__ rhi = a.row_hi + (long)p * a.win_ld;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int i = i0 + r;
+      i = i < N ? i : N - 1;
+      wlo[r] = rlo[i];
+      whi[r] = rhi[i];
+    }
+  }
   float prev[R];
   uint32_t tw[R];
 #pragma unroll
@@ -127,9 +149,19 @@ __global__ __launch_bounds__(64) void dtw_kernel(DtwArgs a) {
           } else {
             c = c2;
             t = 2u;
+            if constexpr (WIN) {
+              if (c2 == INFINITY && c0 == c1 && c0 < INFINITY) {   // the one exception (header): up, not left
+                c = c1;
+                t = 1u;
+              }
+            }
           }
           const float nv = (float)((double)(-xv[u][r]) + (double)c);
-          newv[r] = (i < N) ? nv : INFINITY;
+          if constexpr (WIN) {
+            newv[r] = (i < N && j >= wlo[r] && j <= whi[r]) ? nv : INFINITY;
+          } else {
+            newv[r] = (i < N) ? nv : INFINITY;
+          }
           if constexpr (OPEN) {
             const int l1 = (r == 0) ? up_len : newl[r > 0 ? r - 1 : 0];
             const int l0 = (r == 0) ? diag_len : plen[r > 0 ? r - 1 : 0];
@@ -227,35 +259,53 @@ __global__ __launch_bounds__(64) void dtw_kernel(DtwArgs a) {
 
 }  // namespace
 
+namespace {
+
+// the launch of one (OPEN, WIN) form: rows per lane R = ceil(N_max / 64), unroll U by R
+template <bool OPEN, bool WIN>
+void launch_form(const DtwArgs& a, int R, hipStream_t s) {
+  dim3 grid(a.P), block(64);
+  switch (R) {
+    case 1: hipLaunchKernelGGL((dtw_kernel<1, 8, OPEN, WIN>), grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((dtw_kernel<2, 8, OPEN, WIN>), grid, block, 0, s, a); break;
+    case 3: hipLaunchKernelGGL((dtw_kernel<3, 4, OPEN, WIN>), grid, block, 0, s, a); break;
+    case 4: hipLaunchKernelGGL((dtw_kernel<4, 4, OPEN, WIN>), grid, block, 0, s, a); break;
+    case 5: hipLaunchKernelGGL((dtw_kernel<5, 2, OPEN, WIN>), grid, block, 0, s, a); break;
+    case 6: hipLaunchKernelGGL((dtw_kernel<6, 2, OPEN, WIN>), grid, block, 0, s, a); break;
+    case 7: hipLaunchKernelGGL((dtw_kernel<7, 2, OPEN, WIN>), grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL((dtw_kernel<8, 2, OPEN, WIN>), grid, block, 0, s, a); break;
+  }
+}
+
+}  // namespace
+
 hipError_t launch_dtw(const DtwArgs& a, hipStream_t s) {
   if (a.P <= 0) return hipSuccess;
   if (a.N_max <= 0 || a.M_max <= 0 || a.N_max > 512) return hipErrorInvalidValue;
+  if ((a.row_lo == nullptr) != (a.row_hi == nullptr) || (a.row_lo && a.win_ld < a.N_max)) return hipErrorInvalidValue;
   const int R = (a.N_max + 63) / 64;
-  dim3 grid(a.P), block(64);
-  if (a.open_end || a.open_all) {
-    switch (R) {
-      case 1: hipLaunchKernelGGL((dtw_kernel<1, 8, true>), grid, block, 0, s, a); break;
-      case 2: hipLaunchKernelGGL((dtw_kernel<2, 8, true>), grid, block, 0, s, a); break;
-      case 3: hipLaunchKernelGGL((dtw_kernel<3, 4, true>), grid, block, 0, s, a); break;
-      case 4: hipLaunchKernelGGL((dtw_kernel<4, 4, true>), grid, block, 0, s, a); break;
-      case 5: hipLaunchKernelGGL((dtw_kernel<5, 2, true>), grid, block, 0, s, a); break;
-      case 6: hipLaunchKernelGGL((dtw_kernel<6, 2, true>), grid, block, 0, s, a); break;
-      case 7: hipLaunchKernelGGL((dtw_kernel<7, 2, true>), grid, block, 0, s, a); break;
-      default: hipLaunchKernelGGL((dtw_kernel<8, 2, true>), grid, block, 0, s, a); break;
-    }
-    return hipGetLastError();
-  }
-  switch (R) {
-    case 1: hipLaunchKernelGGL((dtw_kernel<1, 8, false>), grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((dtw_kernel<2, 8, false>), grid, block, 0, s, a); break;
-    case 3: hipLaunchKernelGGL((dtw_kernel<3, 4, false>), grid, block, 0, s, a); break;
-    case 4: hipLaunchKernelGGL((dtw_kernel<4, 4, false>), grid, block, 0, s, a); break;
-    case 5: hipLaunchKernelGGL((dtw_kernel<5, 2, false>), grid, block, 0, s, a); break;
-    case 6: hipLaunchKernelGGL((dtw_kernel<6, 2, false>), grid, block, 0, s, a); break;
-    case 7: hipLaunchKernelGGL((dtw_kernel<7, 2, false>), grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL((dtw_kernel<8, 2, false>), grid, block, 0, s, a); break;
-  }
+  const bool open = a.open_end || a.open_all, win = a.row_lo != nullptr;
+  if (open && win) launch_form<true, true>(a, R, s);
+  else if (open) launch_form<true, false>(a, R, s);
+  else if (win) launch_form<false, true>(a, R, s);
+  else launch_form<false, false>(a, R, s);
   return hipGetLastError();
+}
+
+// Valid windows of one n x m problem: 0 <= lo[i] <= hi[i] <= m-1, lo[0] == 0, hi[n-1] == m-1, lo and hi non-decreasing, lo[i+1] <= hi[i] + 1.
+// They hold a finite path from (0, 0) to (n-1, m-1). Returns nullptr, or which condition fails (*row: at which row).
+const char* dtw_windows_invalid(const int* lo, const int* hi, int n, int m, int* row) {
+  for (int i = 0; i < n; ++i) {
+    *row = i;
+    if (lo[i] < 0 || lo[i] > hi[i] || hi[i] > m - 1) return "0 <= lo <= hi <= M-1 fails";
+    if (i > 0 && (lo[i] < lo[i - 1] || hi[i] < hi[i - 1])) return "lo and hi must be non-decreasing";
+    if (i > 0 && lo[i] > hi[i - 1] + 1) return "lo[i] <= hi[i-1] + 1 fails (no step from the row above)";
+  }
+  *row = 0;
+  if (lo[0] != 0) return "lo[0] must be 0";
+  *row = n - 1;
+  if (hi[n - 1] != m - 1) return "hi[N-1] must be M-1";
+  return nullptr;
 }
 
 }  // namespace wca

@@ -88,9 +88,11 @@ namespace {
 // N_max x M_max. Trace, path and path length go to e->trace / e->path / e->pathlen; jump_ld > 0 also asks for the jump frames in e->jump, rows
 // jump_ld apart. open_dev ([P] device flags, 1 = open end) or open_all asks for the open-end kernel: the end rows [P] and then the scores [P]
 // land in e->dtw_out, and a closed problem of such a launch gets what the closed kernel gives it (end row N - 1).
-// launched (nullable): the arguments of that launch, for run_path_score behind it.
+// launched (nullable): the arguments of that launch, for run_path_score behind it. win_lo_dev / win_hi_dev ([P][win_ld] device, both or
+// neither): the windowed kernel, on windows the caller has checked (check_windows).
 int run_dtw(wca_engine* e, hipStream_t s, const float* matrix, long m_bs, int ld, int P, int N_max, int M_max, const int* N_dev, const int* M_dev,
-            int jump_ld, const int* open_dev = nullptr, bool open_all = false, DtwArgs* launched = nullptr) {
+            int jump_ld, const int* open_dev = nullptr, bool open_all = false, DtwArgs* launched = nullptr, const int* win_lo_dev = nullptr,
+            const int* win_hi_dev = nullptr, int win_ld = 0) {
   const int wpr = (M_max + 15) / 16, cap = N_max + M_max + 2;
   HIPCHK(e->trace.ensure(sizeof(uint32_t) * (size_t)P * N_max * wpr));
   HIPCHK(e->path.ensure(sizeof(int) * (size_t)P * 2 * cap));
@@ -119,8 +121,31 @@ int run_dtw(wca_engine* e, hipStream_t s, const float* matrix, long m_bs, int ld
     dg.end_row = (int*)e->dtw_out.p;
     dg.score = (float*)e->dtw_out.p + P;
   }
+  dg.row_lo = win_lo_dev;
+  dg.row_hi = win_hi_dev;
+  dg.win_ld = win_ld;
   HIPCHK(launch_dtw(dg, s));
   if (launched) *launched = dg;
+  return WCA_OK;
+}
+
+// The host check of the row windows lo / hi [P][ld] before anything is launched: problem p is n[p] x m[p] (a null n / m: n_all / m_all), and
+// only its first n[p] entries are read; a problem without rows has none to check. The windows of an open problem (open[p] != 0, nullable)
+// must be full, [0, m - 1] in every row: end-row selection among infinite cells is not defined.
+int check_windows(const int32_t* lo, const int32_t* hi, int ld, int P, const int32_t* n, int n_all, const int32_t* m, int m_all, const int32_t* open) {
+  for (int p = 0; p < P; ++p) {
+    const int np = n ? n[p] : n_all, mp = m ? m[p] : m_all;
+    if (np < 1) continue;
+    const int32_t *l = lo + (size_t)p * ld, *h = hi + (size_t)p * ld;
+    int row = 0;
+    if (const char* why = dtw_windows_invalid(l, h, np, mp, &row))
+      return fail(WCA_ERR_INVALID, "row windows of problem %d (%d x %d), row %d [%d, %d]: %s", p, np, mp, row, l[row], h[row], why);
+    if (open && open[p])
+      for (int i = 0; i < np; ++i)
+        if (l[i] != 0 || h[i] != mp - 1)
+          return fail(WCA_ERR_INVALID, "problem %d is open-ended and row %d has the window [%d, %d]: an open end takes full windows [0, %d] only", p, i,
+                      l[i], h[i], mp - 1);
+  }
   return WCA_OK;
 }
 
@@ -169,7 +194,7 @@ int read_path(wca_engine* e, int N, int M, int32_t* text_idx_host, int32_t* time
 // open-end flags (end rows and scores in e->dtw_out; -1 / NaN where no DTW ran). path_scores: run_path_score behind the DTW, rows n_tok_max
 // apart like the jump frames (all 0 where no DTW ran).
 int wca::run_select_aggregate_dtw(wca_engine* e, hipStream_t s, const HeadStatsArgs& h, const int* dtwN_dev, const wca_align_opts* o,
-                                  int L_layers, const int* open_dev, bool path_scores) {
+                                  int L_layers, const int* open_dev, bool path_scores, const int* win_lo_dev, const int* win_hi_dev) {
   const int B = h.B, LH = h.LH, n_max = h.n_tok_max, Fmax = h.n_frames_max;
   const int k = o->aggregation == WCA_AGGR_TOPK ? o->topk : 0;
   if (o->aggregation == WCA_AGGR_TOPK) {
@@ -218,7 +243,8 @@ int wca::run_select_aggregate_dtw(wca_engine* e, hipStream_t s, const HeadStatsA
     HIPCHK(e->jump.ensure(sizeof(int) * (size_t)B * n_max));
     HIPCHK(hipMemsetAsync(e->jump.p, 0, sizeof(int) * (size_t)B * n_max, s));
     DtwArgs dg;
-    WCA_TRY(run_dtw(e, s, (const float*)e->matrix.p, (long)n_max * Fmax, Fmax, B, Nmax, Fmax, dtwN_dev, h.n_frames, n_max, open_dev, false, &dg));
+    WCA_TRY(run_dtw(e, s, (const float*)e->matrix.p, (long)n_max * Fmax, Fmax, B, Nmax, Fmax, dtwN_dev, h.n_frames, n_max, open_dev, false, &dg,
+                    win_lo_dev, win_hi_dev, n_max));
     if (path_scores) WCA_TRY(run_path_score(e, s, dg, n_max));
   } else {
     if (open_dev) {
@@ -425,6 +451,53 @@ int wca_dtw_batch_dev(wca_engine* e, const float* matrix_dev, int P, int N, int 
   return WCA_OK;
 }
 
+int wca_dtw_windows(wca_engine* e, const float* matrix_host, int N, int M, const int32_t* row_lo_host, const int32_t* row_hi_host,
+                    int32_t* text_idx_host, int32_t* time_idx_host, int32_t* path_len_host) {
+  if (!e || !matrix_host || !row_lo_host || !row_hi_host || !text_idx_host || !time_idx_host || !path_len_host) return fail(WCA_ERR_INVALID, "null argument");
+  if (N < 1 || N > 512 || M < 1 || M > 4096) return fail(WCA_ERR_INVALID, "DTW shape N=%d M=%d unsupported (N<=512, M<=4096)", N, M);
+  WCA_TRY(check_windows(row_lo_host, row_hi_host, N, 1, nullptr, N, nullptr, M, nullptr));
+  WCA_TRY(enter(e));
+  HIPCHK(e->tmp0.ensure(sizeof(float) * (size_t)N * M));
+  HIPCHK(e->dtw_meta.ensure(sizeof(int) * 2 * (size_t)N));
+  int* wd = (int*)e->dtw_meta.p;
+  HIPCHK(hipMemcpyAsync(e->tmp0.p, matrix_host, sizeof(float) * (size_t)N * M, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(wd, row_lo_host, sizeof(int) * (size_t)N, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(wd + N, row_hi_host, sizeof(int) * (size_t)N, hipMemcpyHostToDevice, e->stream));
+  WCA_TRY(run_dtw(e, e->stream, (const float*)e->tmp0.p, (long)N * M, M, 1, N, M, nullptr, nullptr, 0, nullptr, false, nullptr, wd, wd + N, N));
+  return read_path(e, N, M, text_idx_host, time_idx_host, path_len_host);   // (synchronises: the caller's pageable buffers are read by then)
+}
+
+int wca_dtw_batch_dev_windows(wca_engine* e, const float* matrix_dev, int P, int N, int M, const int32_t* n_rows_host, const int32_t* n_cols_host,
+                              const int32_t* row_lo_host, const int32_t* row_hi_host, int32_t* jump_frame_host) {
+  if (!e || !matrix_dev || !row_lo_host || !row_hi_host || !jump_frame_host) return fail(WCA_ERR_INVALID, "null argument");
+  if (P < 1) return fail(WCA_ERR_INVALID, "P < 1");
+  if (N < 1 || N > 512 || M < 1 || M > 4096) return fail(WCA_ERR_INVALID, "DTW shape N=%d M=%d unsupported (N<=512, M<=4096)", N, M);
+  // the per-problem tables travel as one block: the row and column counts [P] each, then the windows lo [P][N] and hi [P][N]
+  const size_t PN = (size_t)P * N;
+  std::vector<int32_t> meta(2 * (size_t)P + 2 * PN);
+  for (int p = 0; p < P; ++p) {
+    const int n = n_rows_host ? n_rows_host[p] : N, m = n_cols_host ? n_cols_host[p] : M;
+    if (n < 1 || n > N || m < 1 || m > M) return fail(WCA_ERR_INVALID, "problem %d is %d x %d, outside [1,%d] x [1,%d]", p, n, m, N, M);
+    meta[p] = n;
+    meta[(size_t)P + p] = m;
+    for (int i = 0; i < N; ++i) {   // (entries past a problem's rows are not read by anyone: defined as 0)
+      meta[2 * (size_t)P + (size_t)p * N + i] = i < n ? row_lo_host[(size_t)p * N + i] : 0;
+      meta[2 * (size_t)P + PN + (size_t)p * N + i] = i < n ? row_hi_host[(size_t)p * N + i] : 0;
+    }
+  }
+  WCA_TRY(check_windows(row_lo_host, row_hi_host, N, P, meta.data(), N, meta.data() + P, M, nullptr));
+  WCA_TRY(enter(e));
+  HIPCHK(e->dtw_meta.ensure(sizeof(int) * meta.size()));
+  const int* md = (const int*)e->dtw_meta.p;
+  HIPCHK(hipMemcpyAsync(e->dtw_meta.p, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e->jump.ensure(sizeof(int) * PN));
+  HIPCHK(hipMemsetAsync(e->jump.p, 0, sizeof(int) * PN, e->stream));
+  WCA_TRY(run_dtw(e, e->stream, matrix_dev, (long)N * M, M, P, N, M, md, md + P, N, nullptr, false, nullptr, md + 2 * (size_t)P, md + 2 * (size_t)P + PN, N));
+  HIPCHK(hipMemcpyAsync(jump_frame_host, e->jump.p, sizeof(int) * PN, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));   // (meta is a stack-lifetime host buffer)
+  return WCA_OK;
+}
+
 int wca_dtw_open(wca_engine* e, const float* matrix_host, int N, int M, int32_t* text_idx_host, int32_t* time_idx_host, int32_t* path_len_host,
                  int32_t* end_row_host, float* score_host) {
   if (!e || !matrix_host || !text_idx_host || !time_idx_host || !path_len_host || !end_row_host) return fail(WCA_ERR_INVALID, "null argument");
@@ -610,9 +683,12 @@ int wca_default_find_alignment(wca_engine* e, const float* ws_dev, int L, int H,
   return read_path(e, N, F, text_idx_host, time_idx_host, path_len_host, matrix_host);
 }
 
-// the fused pipeline, enqueued: d->open_end_host [batch] (nullable) makes the DTW of the flagged rows open-ended
-int wca_align_batch_enqueue(wca_engine* e, const wca_align_desc* d) {
+// the fused pipeline, enqueued: d->open_end_host [batch] (nullable) makes the DTW of the flagged rows open-ended; row_lo_host / row_hi_host
+// [batch][n_tok_max] (both or neither) give every DTW row its permitted frame interval
+int wca_align_batch_enqueue_windows(wca_engine* e, const wca_align_desc* d, const int32_t* row_lo_host, const int32_t* row_hi_host) {
   if (!e || !d || !d->tokens_dev || !d->n_tok_host || !d->max_frames_host || !d->opts) return fail(WCA_ERR_INVALID, "null argument");
+  if ((row_lo_host == nullptr) != (row_hi_host == nullptr)) return fail(WCA_ERR_INVALID, "row_lo_host and row_hi_host go together");
+  const bool want_win = row_lo_host != nullptr;
   const float* pcm_dev = d->pcm_dev;
   const int64_t pcm_stride = d->pcm_stride;
   const int64_t* tokens_dev = d->tokens_dev;
@@ -651,6 +727,8 @@ int wca_align_batch_enqueue(wca_engine* e, const wca_align_desc* d) {
     dn[b] = n_tok_host[b] - o->sot_len - 1;
     if (dn[b] < 0) dn[b] = 0;
   }
+  // (before anything is staged or launched; validate_lengths has bounded n_tok and max_frames)
+  if (want_win) WCA_TRY(check_windows(row_lo_host, row_hi_host, n_tok_max, batch, dn.data(), 0, max_frames_host, 0, open_end_host));
   int* rows[4];
   // (re-use: the metadata is only read by phase 2, so it travels on that stream -- `stream` may already hold the next
   // batch's phase 1, and an event recorded behind it would serialise this batch's phase 2 after it)
@@ -675,6 +753,26 @@ int wca_align_batch_enqueue(wca_engine* e, const wca_align_desc* d) {
     std::vector<int32_t> flags(batch);
     for (int b = 0; b < batch; ++b) flags[b] = open_end_host[b] ? 1 : 0;
     WCA_TRY(stage_meta(e, batch, flags.data(), nullptr, nullptr, nullptr, open_rows, reuse_enc ? s2 : nullptr));
+  }
+  // the row windows travel like the metadata, through a pinned mirror of their own (they are [batch][n_tok_max], not [batch]): the slot of
+  // this enqueue's parity, whose previous batch has been fetched (at most two are in flight)
+  const int *win_lo_dev = nullptr, *win_hi_dev = nullptr;
+  if (want_win) {
+    const int ws = (int)(e->enq_count & 1);
+    const size_t n = (size_t)batch * n_tok_max;
+    if (e->win_host_ints[ws] < 2 * n) {
+      if (e->win_host[ws]) (void)hipHostFree(e->win_host[ws]);
+      e->win_host[ws] = nullptr;
+      e->win_host_ints[ws] = 0;
+      HIPCHK(hipHostMalloc((void**)&e->win_host[ws], 2 * n * sizeof(int), hipHostMallocDefault));
+      e->win_host_ints[ws] = 2 * n;
+    }
+    HIPCHK(e->win_dev[ws].ensure(2 * n * sizeof(int)));
+    memcpy(e->win_host[ws], row_lo_host, n * sizeof(int));
+    memcpy(e->win_host[ws] + n, row_hi_host, n * sizeof(int));
+    HIPCHK(hipMemcpyAsync(e->win_dev[ws].p, e->win_host[ws], 2 * n * sizeof(int), hipMemcpyHostToDevice, reuse_enc ? s2 : e->stream));
+    win_lo_dev = (const int*)e->win_dev[ws].p;
+    win_hi_dev = win_lo_dev + n;
   }
   // ---- phase 1 on `stream`: log-mel, encoder, cross-K/V of all decoder layers into a free K/V slot (a slot is busy
   // from its encode until the alignment that read it has been fetched; at most 2 alignments are in flight), or the
@@ -710,7 +808,7 @@ int wca_align_batch_enqueue(wca_engine* e, const wca_align_desc* d) {
   WCA_TRY(run_head_stats(e, s2, &h, (const float*)e->cap.p, Fpad, false, nullptr, true, rows[1], rows[2], n_tok_max, Fmax, LH, batch, o->medfilt_width,
                          o->qk_scale, o->w_colnorm, o->w_rownorm, o->w_coverage));
   record(e, 5, s2);
-  WCA_TRY(run_select_aggregate_dtw(e, s2, h, rows[3], o, D.n_text_layer, open_rows[0], want_ps));
+  WCA_TRY(run_select_aggregate_dtw(e, s2, h, rows[3], o, D.n_text_layer, open_rows[0], want_ps, win_lo_dev, win_hi_dev));
   if (want_lp) {
     HIPCHK(e->lp_out.ensure(sizeof(float) * (size_t)batch * n_tok_max));
     WCA_TRY(run_token_logprobs(e, s2, tokens_dev, batch, n_tok_max, o->sot_len, vocab_end, rows[1], lp_rows[0], lp_R, lp_nmax, (float*)e->lp_out.p));
@@ -813,6 +911,14 @@ int wca_align_batch_path_scores(wca_engine* e, int batch, int n_tok_max, float* 
   memcpy(path_mean_host, res + at.ps, sizeof(float) * n);
   memcpy(path_cells_host, res + at.ps + n, sizeof(int) * n);
   return WCA_OK;
+}
+
+int wca_align_batch_enqueue(wca_engine* e, const wca_align_desc* d) { return wca_align_batch_enqueue_windows(e, d, nullptr, nullptr); }
+
+int wca_align_batch_windows(wca_engine* e, const wca_align_desc* d, const int32_t* row_lo_host, const int32_t* row_hi_host, const wca_align_result* r) {
+  if (!e || !d || !r) return fail(WCA_ERR_INVALID, "null argument");
+  WCA_TRY(wca_align_batch_enqueue_windows(e, d, row_lo_host, row_hi_host));
+  return wca_align_batch_fetch(e, d->batch, d->n_tok_max, d->opts->aggregation == WCA_AGGR_TOPK ? d->opts->topk : 0, r);
 }
 
 int wca_align_batch(wca_engine* e, const wca_align_desc* d, const wca_align_result* r) {

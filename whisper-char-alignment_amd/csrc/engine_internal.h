@@ -169,6 +169,11 @@ struct wca_engine {
   // ---- run-time sized buffers
   wca::GrowBuf cap, wws, colnorm, scores, sel, selsc, matrix, trace, path, pathlen, jump, tmp0, tmp1;
   wca::GrowBuf dtw_out, dtw_meta;   // open-end DTW: end rows [P] then scores [P] of the last launch; wca_dtw_batch_dev_open's flags / row / column counts
+  // windowed DTW of the fused alignment: the row windows [2][batch][n_tok_max] (lo, then hi) of the two batches that may be in flight, by
+  // enqueue parity like res_host -- pinned host mirror and device copy (a slot is free again once its batch has been fetched)
+  wca::GrowBuf win_dev[2];
+  int* win_host[2] = {nullptr, nullptr};
+  size_t win_host_ints[2] = {0, 0};
   wca::GrowBuf pscore;              // run_path_score: the per-row path means [P][ld] f32, then the cell counts [P][ld], of the last DTW launch that asked for them
   wca::GrowBuf quiet_out;           // wca_quiet_cuts: the interior cuts [n_pieces - 1] then their levels [n_pieces - 1], copied to the host before the call returns
   wca::GrowBuf vad_buf;             // wca_speech_segments: the call's whole device scratch (VadScratch), result included
@@ -333,7 +338,8 @@ int run_head_stats(wca_engine* e, hipStream_t s, HeadStatsArgs* h, const float* 
                    bool want_rowstats, const int* n_tok_dev, const int* n_frames_dev, int n_max, int Fmax, int LH, int B, int medfilt_width,
                    float qk_scale, float w_col, float w_row, float w_cov);
 int run_select_aggregate_dtw(wca_engine* e, hipStream_t s, const HeadStatsArgs& h, const int* dtwN_dev, const wca_align_opts* o, int L_layers,
-                             const int* open_dev = nullptr, bool path_scores = false);
+                             const int* open_dev = nullptr, bool path_scores = false, const int* win_lo_dev = nullptr,
+                             const int* win_hi_dev = nullptr);   // win_*: row windows [B][n_tok_max] in DTW rows, checked by the caller
 
 // ---- engine_audio.hip
 int check_pcm_lengths(const int32_t* n_samples_host, int batch, int64_t pcm_stride);

@@ -453,8 +453,15 @@ struct DtwArgs {
   int open_all;
   int* end_row;            // [P] n* (N - 1 for a closed problem, -1 for a refused one), or nullptr
   float* score;            // [P] C / L at the end cell, for diagnostics (no decision reads it), or nullptr
+  // windowed form (both set, or both null): cell (i, j) of problem p is allowed iff row_lo[p*win_ld + i] <= j <= row_hi[p*win_ld + i]; the
+  // launch takes the windowed kernel. The windows must be valid (dtw_windows_invalid), and an open problem's must be full ([0, M-1]).
+  const int* row_lo;       // [P][win_ld] device, entries [0, N[p]) of a problem are read
+  const int* row_hi;
+  int win_ld;              // row stride of row_lo / row_hi (>= N_max)
 };
 hipError_t launch_dtw(const DtwArgs& a, hipStream_t s);
+// host check of one n x m problem's windows: nullptr if valid, else the failed condition (*row: where)
+const char* dtw_windows_invalid(const int* lo, const int* hi, int n, int m, int* row);
 
 // ---------------------------------------------------------------- per-row score of the DTW path (path_score.hip)
 // Behind launch_dtw(d) on the same stream: for text row i of problem p, cells = the number of path cells in that row and mean = the f32

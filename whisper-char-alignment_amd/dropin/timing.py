@@ -10,9 +10,12 @@ default_find_alignment = _t.default_find_alignment
 median_filter = _t.median_filter
 dtw = _t.dtw
 dtw_open = _t.dtw_open
+dtw_windows = _t.dtw_windows
 path_scores = _t.path_scores
 word_alignment_scores = _t.word_alignment_scores
 force_align_long = _t.force_align_long
 force_align_long_batch = _t.force_align_long_batch
+force_align_cues = _t.force_align_cues
+force_align_cues_batch = _t.force_align_cues_batch
 trim_words_to_speech = _t.trim_words_to_speech
 HOP_LENGTH, SAMPLE_RATE, TOKENS_PER_SECOND = _t.HOP_LENGTH, _t.SAMPLE_RATE, _t.TOKENS_PER_SECOND

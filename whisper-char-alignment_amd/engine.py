@@ -436,6 +436,17 @@ class WhisperAMD:
         from . import align_long as _a
         return _a.force_align_long(self, audio, text, **kw)
 
+    def force_align_cues(self, audio, cues, **kw):
+        """Word times of a recording against its subtitle cues, a list of (start_s, end_s, text) or an .srt / .vtt path
+        (align_long.force_align_cues)."""
+        from . import align_long as _a
+        return _a.force_align_cues(self, audio, cues, **kw)
+
+    def force_align_cues_batch(self, audios, cues, **kw):
+        """force_align_cues() of several recordings, their windows sharing the rounds (align_long.force_align_cues_batch)."""
+        from . import align_long as _a
+        return _a.force_align_cues_batch(self, audios, cues, **kw)
+
     def force_align_long_batch(self, audios, texts, **kw):
         """force_align_long() of several recordings in lock-step, one align_batch per round (align_long.force_align_long_batch)."""
         from . import align_long as _a
@@ -483,7 +494,7 @@ class WhisperAMD:
                               float(w_rownorm), float(w_coverage), int(sot_len), int(medfilt_width), float(qk_scale))
 
     def align_batch(self, pcm, n_samples, tokens, n_tok, max_frames, opts, enqueue_only=False, token_logprobs_vocab_end=None, open_end=None,
-                    path_scores=False):
+                    path_scores=False, row_windows=None):
         """Fused pipeline. pcm [B,stride] f32 cuda, tokens [B,n_max] int64 cuda. Returns (jump_frames [B,n_max] int32, sel [B,topk]).
         token_logprobs_vocab_end (tokenizer.eot): the teacher tokens' log-probabilities are computed on the GPU as well
         (wca_align_desc.vocab_end) and returned as a third value [B,n_max] f32 (row b: n_tok[b] - sot_len - 2 entries, then 0);
@@ -494,7 +505,12 @@ class WhisperAMD:
         After enqueue_only=True, fetch them with fetch(..., with_end_rows=True). None: nothing changes.
         path_scores: the path-score kernel runs behind the DTW (wca_align_desc.path_scores) and (path_mean [B,n_max] f32, path_cells
         [B,n_max] int32) are the LAST two values returned: per DTW row, laid out like the jump frames, the mean of the aggregated matrix
-        over the path's cells in that row and their number. After enqueue_only=True, fetch them with fetch(..., with_path_scores=True)."""
+        over the path's cells in that row and their number. After enqueue_only=True, fetch them with fetch(..., with_path_scores=True).
+        row_windows = (lo, hi), each [B, n_max] int32 (or nested lists of that shape): DTW row i of batch row b may only sit at the encoder
+        frames lo[b][i] <= j <= hi[b][i] (wca_align_batch_enqueue_windows; DTW rows count from the first token after the sot sequence and
+        no_timestamps, the eot is the last, later entries are not read). The windows must be valid (include/wca.h wca_dtw_windows), and an
+        open_end row takes full windows only; otherwise the engine refuses the call (WcaError) before anything is enqueued. The returned
+        values are those without windows. None: nothing changes and no new code runs."""
         B, n_max = tokens.shape
         if open_end is not None and len(open_end) != B:
             raise ValueError("open_end lists %d flags for %d rows" % (len(open_end), B))
@@ -506,7 +522,13 @@ class WhisperAMD:
         d = _lib.AlignDesc(pcm_dev=_ptr(pcm), n_samples_host=_ptr(ns), tokens_dev=_ptr(tokens), n_tok_host=_ptr(nt), max_frames_host=_ptr(mf),
                            opts=C.pointer(opts), open_end_host=_ptr(oe), pcm_stride=pcm.shape[1] if pcm is not None else 0, n_tok_max=n_max,
                            batch=B, vocab_end=int(token_logprobs_vocab_end or 0), path_scores=1 if path_scores else 0)
-        _lib.check(self._lib.wca_align_batch_enqueue(self._h, C.byref(d)))
+        if row_windows is not None:
+            lo, hi = (np.ascontiguousarray(w, dtype=np.int32) for w in row_windows)
+            if lo.shape != (B, n_max) or hi.shape != (B, n_max):
+                raise ValueError("row_windows are two [%d, %d] tables, got %s and %s" % (B, n_max, lo.shape, hi.shape))
+            _lib.check(self._lib.wca_align_batch_enqueue_windows(self._h, C.byref(d), lo.ctypes.data_as(_pi32), hi.ctypes.data_as(_pi32)))
+        else:
+            _lib.check(self._lib.wca_align_batch_enqueue(self._h, C.byref(d)))
         if enqueue_only:
             return None
         return self.fetch(B, n_max, opts, with_token_logprobs=token_logprobs_vocab_end is not None, with_end_rows=open_end is not None,
@@ -750,6 +772,29 @@ class WhisperAMD:
         _lib.check(self._lib.wca_dtw_path_scores(self._h, _ptr(m), P, N, M, nr, nc, oe, jump.ctypes.data_as(_pi32), end_rows.ctypes.data_as(_pi32),
                                                  mean.ctypes.data_as(_pf32), cells.ctypes.data_as(_pi32)))
         return jump, end_rows, mean, cells
+
+    def dtw_windows(self, matrix_dev, row_lo, row_hi, n_rows=None, n_cols=None):
+        """C ABI wca_dtw_batch_dev_windows: P closed DTW problems matrix_dev [P, N, M] f32 cuda (NOT negated) in which text row i of problem
+        p may only sit at the frames row_lo[p][i] <= j <= row_hi[p][i] ([P, N] int32 each); problem p is the n_rows[p] x n_cols[p] corner
+        of its slice (None: all N / all M) and only its first n_rows[p] window entries are read. Invalid windows are refused before
+        anything runs (include/wca.h wca_dtw_windows). Returns the jump frames [P, N] int32 (0 beyond a problem's rows)."""
+        m = matrix_dev.to(self.device, torch.float32).contiguous()
+        if m.dim() != 3:
+            raise ValueError("matrix_dev must be [P, N, M]")
+        P, N, M = m.shape
+        lo, hi = np.ascontiguousarray(row_lo, dtype=np.int32), np.ascontiguousarray(row_hi, dtype=np.int32)
+        if lo.shape != (P, N) or hi.shape != (P, N):
+            raise ValueError("row_lo / row_hi must be [%d, %d], got %s and %s" % (P, N, lo.shape, hi.shape))
+        for name, v in (("n_rows", n_rows), ("n_cols", n_cols)):
+            if v is not None and len(v) != P:
+                raise ValueError("%s lists %d values for %d problems" % (name, len(v), P))
+        nr = _lib.i32_array(n_rows) if n_rows is not None else None
+        nc = _lib.i32_array(n_cols) if n_cols is not None else None
+        jump = np.zeros((P, N), np.int32)
+        self._bind_stream()
+        _lib.check(self._lib.wca_dtw_batch_dev_windows(self._h, _ptr(m), P, N, M, nr, nc, lo.ctypes.data_as(_pi32), hi.ctypes.data_as(_pi32),
+                                                       jump.ctypes.data_as(_pi32)))
+        return jump
 
     def fetch(self, B, n_max, opts, with_token_logprobs=False, with_end_rows=False, with_path_scores=False):
         """Results of the oldest enqueued align_batch: (jump, sel), or (jump, sel, token_logprobs [B,n_max] f32) with

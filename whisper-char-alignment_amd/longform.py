@@ -2,6 +2,7 @@
 once: the frame constants, a recording's way to 16 kHz mono, one round's window cut, the padded token matrix, the aligner's options, and
 the pieces of the two command lines that are the same. Host Python only: what runs on the GPU is in the drivers' docstrings."""
 import os
+import re
 
 import numpy as np
 import torch
@@ -66,6 +67,42 @@ def pad_token_rows(rows, eot):
     for b, r in enumerate(rows):
         toks[b, :len(r)] = torch.tensor(r, dtype=torch.int64)
     return toks
+
+
+_CUE_TIME = r"(?:(\d+):)?(\d{1,2}):(\d{2})[.,](\d{1,3})"   # [hours:]minutes:seconds, then `,` (SRT) or `.` (WebVTT) and the fraction
+_CUE_TIMING = re.compile(r"^\s*" + _CUE_TIME + r"\s*-->\s*" + _CUE_TIME)
+_CUE_TAG = re.compile(r"<[^>]*>|\{\\[^}]*\}")   # <i>, </b>, <c.colour>, <00:01.000> (WebVTT); {\an8} (SubStation overrides inside SRT)
+
+
+def _cue_seconds(h, m, s, frac):
+    return int(h or 0) * 3600 + int(m) * 60 + int(s) + int(frac.ljust(3, "0")) / 1000.0
+
+
+def parse_cues(text):
+    """The cues of an SRT or WebVTT file's text as [(start_s, end_s, text)], in file order. A cue is a block of lines (blocks are
+    separated by blank lines) with a timing line `start --> end`, `[hh:]mm:ss,mmm` or `[hh:]mm:ss.mmm`; whatever follows the end time on
+    that line (WebVTT cue settings) is ignored, as are lines before it (the SRT counter, a WebVTT cue identifier). The lines after it are
+    the cue's text: joined with one space, tags like <i> or <c.yellow> and override blocks like {\\an8} removed, white space collapsed.
+    Blocks without a timing line -- the WEBVTT header, NOTE, STYLE and REGION blocks -- are skipped; a cue without text is kept (it
+    carries no words). No ordering is checked here: force_align_cues does that."""
+    cues = []
+    for block in re.split(r"\n[ \t]*\n", text.lstrip("\ufeff").replace("\r\n", "\n").replace("\r", "\n")):
+        lines = block.strip("\n").split("\n")
+        if lines[0].startswith(("WEBVTT", "NOTE", "STYLE", "REGION")):
+            continue
+        for k, line in enumerate(lines[:2]):   # (the timing line is the first line, or the second after a counter / identifier)
+            m = _CUE_TIMING.match(line)
+            if m:
+                body = " ".join(_CUE_TAG.sub("", ln) for ln in lines[k + 1:])
+                cues.append((_cue_seconds(*m.groups()[:4]), _cue_seconds(*m.groups()[4:]), " ".join(body.split())))
+                break
+    return cues
+
+
+def read_cues(path):
+    """parse_cues of a UTF-8 .srt / .vtt file."""
+    with open(path, encoding="utf-8") as f:
+        return parse_cues(f.read())
 
 
 def aligner_options(model, tokenizer, *, aggr="topk", topk=10, medfilt_width=3, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0):

@@ -104,6 +104,28 @@ def dtw_open(x):
     return ti[:n.value].astype(np.int64), tj[:n.value].astype(np.int64), int(end_row.value), float(score.value)
 
 
+def dtw_windows(x, lo, hi):
+    """The windowed form of dtw(x) (C ABI wca_dtw_windows; no counterpart upstream): x is the ALREADY NEGATED cost matrix (N, M), and text
+    row i may only sit at the frames lo[i] <= j <= hi[i]. The windows must satisfy 0 <= lo <= hi <= M-1, lo[0] == 0, hi[N-1] == M-1, both
+    non-decreasing and lo[i+1] <= hi[i] + 1 (else the engine refuses them before anything runs); full windows give dtw(x) bit for bit.
+    Returns (text_indices, time_indices)."""
+    x = torch.as_tensor(x)
+    dev = x.device if x.is_cuda else torch.device("cuda:0")
+    eng = _engine_for(dev)
+    m = np.ascontiguousarray((-x).float().cpu().numpy(), dtype=np.float32)
+    N, M = m.shape
+    lo, hi = np.ascontiguousarray(lo, dtype=np.int32), np.ascontiguousarray(hi, dtype=np.int32)
+    if lo.shape != (N,) or hi.shape != (N,):
+        raise ValueError("lo and hi hold one entry per text row (%d), got %s and %s" % (N, lo.shape, hi.shape))
+    ti = np.zeros(N + M, dtype=np.int32)
+    tj = np.zeros(N + M, dtype=np.int32)
+    n = C.c_int32(0)
+    eng._bind_stream()
+    _lib.check(eng._lib.wca_dtw_windows(eng._h, m.ctypes.data_as(_pf), N, M, lo.ctypes.data_as(_pi), hi.ctypes.data_as(_pi),
+                                        ti.ctypes.data_as(_pi), tj.ctypes.data_as(_pi), C.byref(n)))
+    return ti[:n.value].astype(np.int64), tj[:n.value].astype(np.int64)
+
+
 def path_scores(matrix):
     """The DTW of one (N, M) matrix (NOT negated: what force_align returns as `matrix`; host or device) with the per-row score of its path,
     through wca_dtw_path_scores. Returns (text_indices, time_indices, path_mean, path_cells): the path as dtw(-matrix) gives it, and for
@@ -124,6 +146,18 @@ def force_align_long(model, audio, text, **kw):
     """Word times of a recording of any length against its given transcript: align_long.force_align_long."""
     from . import align_long
     return align_long.force_align_long(model, audio, text, **kw)
+
+
+def force_align_cues(model, audio, cues, **kw):
+    """Word times of a recording against its subtitle cues [(start_s, end_s, text)] or an .srt / .vtt file: align_long.force_align_cues."""
+    from . import align_long
+    return align_long.force_align_cues(model, audio, cues, **kw)
+
+
+def force_align_cues_batch(model, audios, cues, **kw):
+    """force_align_cues of several recordings, their windows sharing the rounds: align_long.force_align_cues_batch."""
+    from . import align_long
+    return align_long.force_align_cues_batch(model, audios, cues, **kw)
 
 
 def force_align_long_batch(model, audios, texts, **kw):
