@@ -116,7 +116,7 @@ typedef struct {
 } wca_align_opts;
 
 const char* wca_last_error(void);
-int wca_version(void);   /* 19: wca_speech_segments (the speech segments of a long recording: what transcribe(vad_filter=True) decodes); 18: wca_decode_group (beam search and best_of: G decoder rows per audio, a beam step and a cache reorder on the GPU); 17: one descriptor call each for decode (wca_decode, wca_decode_desc) and the fused alignment (wca_align_desc, wca_align_result) in place of the eleven entry points that had grown feature by feature; 16: the CU-partition and two-stream decode experiments are gone; 15: wca_quiet_cuts (where to cut one long recording into pieces decoded side by side); 14: the open-end DTW entry points; 13: wca_detect_language (the language head on the encoded state; the decode that follows re-uses the state); 12: wca_resample_plan, wca_resample_table, wca_resample_16k (any input rate to 16 kHz); 11: per-row prompts and sample budgets in the decode; 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: prompt / prefix in the decode (sot_index, batched prefill); 7: exactly two precision modes */
+int wca_version(void);   /* 21: wca_align_batch_enqueue_heads / wca_align_batch_heads (openai-whisper's alignment-heads post-processing on the fused path); 20: the windowed DTW (wca_dtw_windows, wca_align_batch*_windows); 19: wca_speech_segments (the speech segments of a long recording: what transcribe(vad_filter=True) decodes); 18: wca_decode_group (beam search and best_of: G decoder rows per audio, a beam step and a cache reorder on the GPU); 17: one descriptor call each for decode (wca_decode, wca_decode_desc) and the fused alignment (wca_align_desc, wca_align_result) in place of the eleven entry points that had grown feature by feature; 16: the CU-partition and two-stream decode experiments are gone; 15: wca_quiet_cuts (where to cut one long recording into pieces decoded side by side); 14: the open-end DTW entry points; 13: wca_detect_language (the language head on the encoded state; the decode that follows re-uses the state); 12: wca_resample_plan, wca_resample_table, wca_resample_16k (any input rate to 16 kHz); 11: per-row prompts and sample budgets in the decode; 10: wca_log_mel_long, wca_mel_window; 9: the diagnostic stamp entry points are gone, switches no longer read the environment; 8: prompt / prefix in the decode (sot_index, batched prefill); 7: exactly two precision modes */
 
 /* ---- engine lifetime ------------------------------------------------------------------------ */
 /* A new engine is in the CONTRACT precision mode (WCA_PRECISION_REFERENCE: every stage on (hi, lo) operand pairs = the fp32 forward of
@@ -420,6 +420,20 @@ int wca_align_batch(wca_engine* e, const wca_align_desc* d, const wca_align_resu
 int wca_align_batch_enqueue_windows(wca_engine* e, const wca_align_desc* d, const int32_t* row_lo_host, const int32_t* row_hi_host);
 int wca_align_batch_windows(wca_engine* e, const wca_align_desc* d, const int32_t* row_lo_host, const int32_t* row_hi_host,
                             const wca_align_result* r);
+/* wca_align_batch_enqueue / wca_align_batch on the ALIGNMENT-HEADS route: openai-whisper's own word aligner (whisper/timing.py
+ * find_alignment) in place of head statistics, top-k and aggregation. Phase 1, the teacher-forced decoder with its capture, the ragged DTW,
+ * the fetch and the vocab_end log-probabilities are those of wca_align_batch_enqueue. Between them, for the n_heads heads of heads_host
+ * (host, layer * n_text_head + head, 1 <= n_heads <= n_text_layer * n_text_head, each in [0, n_text_layer * n_text_head); summed in
+ * the order given) and utterance b's
+ * n_tok[b] x max_frames[b] corner of the captured logits: softmax over the frames of logits * qk_scale; per head and frame (w - mean) / std
+ * over the n_tok[b] token rows (population std, a plain division: a constant column gives NaN, as upstream); the median filter of
+ * medfilt_width along the frames (reflect padding; skipped where max_frames[b] <= medfilt_width / 2); the mean over the heads; rows
+ * [sot_len, n_tok[b] - 1) go to the DTW, negated. Of d->opts only sot_len, medfilt_width and qk_scale are read. Refused with
+ * WCA_ERR_INVALID before anything is enqueued or consumed: a head out of range, n_heads outside that range, d->path_scores != 0 (the score is defined on
+ * the [0, 1] aggregation), d->open_end_host != NULL. The results are fetched with wca_align_batch_fetch(..., topk = 0, ...); sel_idx_host
+ * is left untouched. */
+int wca_align_batch_enqueue_heads(wca_engine* e, const wca_align_desc* d, const int32_t* heads_host, int n_heads);
+int wca_align_batch_heads(wca_engine* e, const wca_align_desc* d, const int32_t* heads_host, int n_heads, const wca_align_result* r);
 /* The path scores of the OLDEST pending batch, which must have been enqueued with path_scores != 0 (WCA_ERR_STATE otherwise, or when nothing
  * is pending): waits for that batch like the fetch, copies path_mean_host / path_cells_host [batch][n_tok_max] -- laid out like
  * jump_frame_host: entry i of row b belongs to DTW row i, 0 beyond the DTW's rows -- and does NOT consume the batch: the
@@ -766,6 +780,28 @@ int wca_test_align_postproc(wca_engine* e, const wca_test_postproc_desc* desc);
 /* wca_test_align_postproc with the path-score kernel behind the DTW, as wca_align_desc.path_scores asks for it (the same function of the
  * fused path): path_mean_host / path_cells_host [B][n_tok_max], laid out like jump_host, both required. */
 int wca_test_align_postproc_scores(wca_engine* e, const wca_test_postproc_desc* desc, float* path_mean_host, int32_t* path_cells_host);
+/* wca_test_align_postproc's sibling for the alignment-heads route (kernel parity test, tests/align_heads_ref.py): the metadata staging, the
+ * three passes of align_heads.hip over the S = n_heads heads of heads_host and the ragged DTW -- the very functions
+ * wca_align_batch_enqueue_heads calls, on the engine's stream, then the copies and one synchronisation. No weights are needed. qk_dev, the
+ * lengths and B, L, H, n_tok_max, ld, n_frames_max as wca_test_postproc_desc's; of opts only sot_len, medfilt_width and qk_scale are read;
+ * heads as wca_align_batch_enqueue_heads checks them. Every host output is nullable; F = n_frames_max: rowstats [B][S][n_tok_max][2] =
+ * (max, sum), colstats [B][S][F][2] = (mean, std), matrix [B][n_tok_max][F], jump [B][n_tok_max]. The whole device buffers are copied: only
+ * utterance b's own corner of an array is DEFINED (rows [0, n_tok[b]) of rowstats, columns [0, n_frames[b]) of colstats, rows
+ * [0, n_tok[b] - sot_len - 1) x columns [0, n_frames[b]) of matrix), the rest holds what a recycled workspace held; the jump rows are whole,
+ * 0 past the DTW's rows. */
+typedef struct {
+  const float* qk_dev;
+  const int32_t* n_tok_host;
+  const int32_t* n_frames_host;
+  const int32_t* heads_host;
+  const wca_align_opts* opts;
+  float* rowstats_host;
+  float* colstats_host;
+  float* matrix_host;
+  int32_t* jump_host;
+  int32_t B, L, H, n_tok_max, ld, n_frames_max, n_heads;
+} wca_test_heads_postproc_desc;
+int wca_test_align_heads_postproc(wca_engine* e, const wca_test_heads_postproc_desc* desc);
 /* the first `count` floats of the column norms [B][L*H][F] that the LAST head-statistics launch on the engine's stream left (after
  * wca_force_align on one utterance: [L*H][F]); reads only, launches nothing */
 int wca_test_last_colnorm(wca_engine* e, int64_t count, float* colnorm_host);

@@ -90,6 +90,13 @@ class PostprocDesc(C.Structure):
                 [(n, C.c_int32) for n in ("B", "L", "H", "n_tok_max", "ld", "n_frames_max")])
 
 
+class HeadsPostprocDesc(C.Structure):
+    """wca_test_heads_postproc_desc of include/wca.h"""
+    _fields_ = ([(n, C.c_void_p) for n in ("qk_dev", "n_tok_host", "n_frames_host", "heads_host")] + [("opts", C.POINTER(AlignOpts))] +
+                [(n, C.c_void_p) for n in ("rowstats_host", "colstats_host", "matrix_host", "jump_host")] +
+                [(n, C.c_int32) for n in ("B", "L", "H", "n_tok_max", "ld", "n_frames_max", "n_heads")])
+
+
 class GemmDesc(C.Structure):
     """wca_test_gemm_desc of include/wca.h"""
     _fields_ = ([(n, C.c_void_p) for n in ("a", "w", "bias", "c", "addend", "pos")] +
@@ -165,6 +172,8 @@ SIGNATURES = {
     "wca_align_batch_enqueue": (_i, [_vp, C.POINTER(AlignDesc)]),
     "wca_align_batch_windows": (_i, [_vp, C.POINTER(AlignDesc), _pi32, _pi32, C.POINTER(AlignResult)]),
     "wca_align_batch_enqueue_windows": (_i, [_vp, C.POINTER(AlignDesc), _pi32, _pi32]),
+    "wca_align_batch_heads": (_i, [_vp, C.POINTER(AlignDesc), _pi32, _i, C.POINTER(AlignResult)]),
+    "wca_align_batch_enqueue_heads": (_i, [_vp, C.POINTER(AlignDesc), _pi32, _i]),
     "wca_align_batch_fetch": (_i, [_vp, _i, _i, _i, C.POINTER(AlignResult)]),
     "wca_align_batch_path_scores": (_i, [_vp, _i, _i, _pf, _pi32]),
     "wca_token_logprobs": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -191,6 +200,7 @@ SIGNATURES = {
     "wca_test_last_scores": (_i, [_vp, _i, _pf]),
     "wca_test_align_postproc": (_i, [_vp, C.POINTER(PostprocDesc)]),
     "wca_test_align_postproc_scores": (_i, [_vp, C.POINTER(PostprocDesc), _pf, _pi32]),
+    "wca_test_align_heads_postproc": (_i, [_vp, C.POINTER(HeadsPostprocDesc)]),
     "wca_test_last_colnorm": (_i, [_vp, _i64, _pf]),
     "wca_test_decode_state": (_i, [_vp, _i, _i, _i, _pf, _vp]),
     "wca_test_gemm_pairs": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),

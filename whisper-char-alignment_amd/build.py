@@ -12,8 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libwca.so")
-SOURCES = ["gemm.hip", "gemm_plan.cpp", "gemm_rows.hip", "attention.hip", "attention_split.hip", "elementwise.hip", "logmel.hip", "quiet_cuts.hip", "speech_segments.hip", "resample.hip", "postproc.hip", "dtw.hip", "path_score.hip", "decode.hip", "beam.hip", "language_head.hip", "token_prob.hip", "engine.hip", "engine_weights.hip", "engine_forward.hip", "engine_align.hip", "engine_audio.hip", "engine_decode.hip", "engine_comm.hip", "engine_test.hip", "flac.cpp", "debug_switch.cpp"]
-HEADERS = ["kernels.h", "wca_common.h", "decode_filter.h", "level_quant.h", "launch.h", "attn_common.h", "gemm_epilogue.h", "engine_internal.h", os.path.join("..", "..", "include", "wca.h")]
+SOURCES = ["gemm.hip", "gemm_plan.cpp", "gemm_rows.hip", "attention.hip", "attention_split.hip", "elementwise.hip", "logmel.hip", "quiet_cuts.hip", "speech_segments.hip", "resample.hip", "postproc.hip", "align_heads.hip", "dtw.hip", "path_score.hip", "decode.hip", "beam.hip", "language_head.hip", "token_prob.hip", "engine.hip", "engine_weights.hip", "engine_forward.hip", "engine_align.hip", "engine_audio.hip", "engine_decode.hip", "engine_comm.hip", "engine_test.hip", "flac.cpp", "debug_switch.cpp"]
+HEADERS = ["kernels.h", "wca_common.h", "decode_filter.h", "level_quant.h", "launch.h", "median.h", "attn_common.h", "gemm_epilogue.h", "engine_internal.h", os.path.join("..", "..", "include", "wca.h")]
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs (the softmax / epilogue VALU code reads them
 # directly; the AGPR form costs a v_accvgpr_read/write pair per element in the attention loop)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-mllvm", "-amdgpu-mfma-vgpr-form"]

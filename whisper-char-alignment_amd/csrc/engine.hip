@@ -138,7 +138,7 @@ int take_kv_slot(wca_engine* e) {
 extern "C" {
 
 const char* wca_last_error(void) { return g_err.c_str(); }
-int wca_version(void) { return 20; }   // 20: windowed DTW (wca_dtw_windows, wca_dtw_batch_dev_windows, wca_align_batch*_windows: every text row has a permitted frame interval); 19: wca_speech_segments (speech activity of a long recording; speech_segments.hip); 18: wca_decode_group (beam search / best_of on grouped decoder rows; beam.hip); 17: one descriptor call each for decode (wca_decode) and the fused alignment (wca_align_batch*) in place of eleven entry points (HISTORY.md); 16: the CU-partition and two-stream decode experiments removed (HISTORY.md; wca_set_decode_mode refuses streams != 1); 15: wca_quiet_cuts (the quietest even frame near each equal share of a long recording); 14: open-end DTW (wca_dtw_open, wca_dtw_batch_dev_open, open-end rows in the fused alignment); 13: wca_detect_language (language identification on the state a decode then takes); 12: wca_resample_plan / wca_resample_table / wca_resample_16k (polyphase resampler to 16 kHz); 11: per-row decode (per-row initial tokens / sample budgets: the rows of a batch at different decoder positions); 10: wca_log_mel_long / wca_mel_window (whole-recording log-mel, window cut); 9: the two diagnostic stamp entry points removed, no switch read from the environment; 8: prompted greedy decode (sot_index, batched prefill); 7: two precision modes only (the per-stage precision mask, its setter / getter and the mixed
+int wca_version(void) { return 21; }   // 21: the alignment-heads route of the fused alignment (wca_align_batch*_heads: upstream's find_alignment post-processing; align_heads.hip); 20: windowed DTW (wca_dtw_windows, wca_dtw_batch_dev_windows, wca_align_batch*_windows: every text row has a permitted frame interval); 19: wca_speech_segments (speech activity of a long recording; speech_segments.hip); 18: wca_decode_group (beam search / best_of on grouped decoder rows; beam.hip); 17: one descriptor call each for decode (wca_decode) and the fused alignment (wca_align_batch*) in place of eleven entry points (HISTORY.md); 16: the CU-partition and two-stream decode experiments removed (HISTORY.md; wca_set_decode_mode refuses streams != 1); 15: wca_quiet_cuts (the quietest even frame near each equal share of a long recording); 14: open-end DTW (wca_dtw_open, wca_dtw_batch_dev_open, open-end rows in the fused alignment); 13: wca_detect_language (language identification on the state a decode then takes); 12: wca_resample_plan / wca_resample_table / wca_resample_16k (polyphase resampler to 16 kHz); 11: per-row decode (per-row initial tokens / sample budgets: the rows of a batch at different decoder positions); 10: wca_log_mel_long / wca_mel_window (whole-recording log-mel, window cut); 9: the two diagnostic stamp entry points removed, no switch read from the environment; 8: prompted greedy decode (sot_index, batched prefill); 7: two precision modes only (the per-stage precision mask, its setter / getter and the mixed
                                       // state are gone); 6: teacher-token log-probs (in the fused alignment, and wca_token_logprobs);
                                       // 5: a new engine is in the contract mode; wca_engine_create_ex, W_lo slab, switch table
 

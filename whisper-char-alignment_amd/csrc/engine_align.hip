@@ -164,6 +164,33 @@ int run_path_score(wca_engine* e, hipStream_t s, const DtwArgs& dg, int out_ld) 
   return WCA_OK;
 }
 
+// The ragged DTW on s behind an aggregation that left e->matrix [B][n_max][Fmax] (rows [0, dtwN[b]) x columns [0, n_frames[b]) of utterance b):
+// the jump frames land in e->jump [B][n_max]; open_dev, path_scores and the row windows as run_select_aggregate_dtw describes them.
+int run_matrix_dtw(wca_engine* e, hipStream_t s, int B, int n_max, int Fmax, int sot_len, const int* dtwN_dev, const int* n_frames_dev,
+                   const int* open_dev, bool path_scores, const int* win_lo_dev, const int* win_hi_dev) {
+  const int Nmax = n_max - sot_len - 1;
+  if (Nmax >= 1) {
+    // the DTW writes n_tok[b] - sot_len - 1 entries per utterance; the rest of a row is defined as 0 (the buffer is recycled memory, and a
+    // caller that compares or stores whole rows must not see what an earlier allocation left there)
+    HIPCHK(e->jump.ensure(sizeof(int) * (size_t)B * n_max));
+    HIPCHK(hipMemsetAsync(e->jump.p, 0, sizeof(int) * (size_t)B * n_max, s));
+    DtwArgs dg;
+    WCA_TRY(run_dtw(e, s, (const float*)e->matrix.p, (long)n_max * Fmax, Fmax, B, Nmax, Fmax, dtwN_dev, n_frames_dev, n_max, open_dev, false, &dg,
+                    win_lo_dev, win_hi_dev, n_max));
+    if (path_scores) WCA_TRY(run_path_score(e, s, dg, n_max));
+  } else {
+    if (open_dev) {
+      HIPCHK(e->dtw_out.ensure(2 * sizeof(int) * (size_t)B));
+      HIPCHK(hipMemsetAsync(e->dtw_out.p, 0xFF, 2 * sizeof(int) * (size_t)B, s));
+    }
+    if (path_scores) {
+      HIPCHK(e->pscore.ensure(2 * sizeof(int) * (size_t)B * n_max));
+      HIPCHK(hipMemsetAsync(e->pscore.p, 0, 2 * sizeof(int) * (size_t)B * n_max, s));
+    }
+  }
+  return WCA_OK;
+}
+
 // The path of the N x M DTW that `stream` ran last on one problem, to the host: path_len entries of (text_idx, time_idx), which the kernel
 // leaves right-aligned in rows of N + M + 2. The copies a caller wants with it share the one synchronisation: the first N rows of e->matrix
 // (matrix_host), the keff selected heads and their scores (sel_idx_host / sel_score_host).
@@ -236,27 +263,47 @@ int wca::run_select_aggregate_dtw(wca_engine* e, hipStream_t s, const HeadStatsA
   HIPCHK(launch_aggregate(g, s));
   record(e, 6, s);
 
-  const int Nmax = n_max - o->sot_len - 1;
-  if (Nmax >= 1) {
-    // the DTW writes n_tok[b] - sot_len - 1 entries per utterance; the rest of a row is defined as 0 (the buffer is recycled memory, and a
-    // caller that compares or stores whole rows must not see what an earlier allocation left there)
-    HIPCHK(e->jump.ensure(sizeof(int) * (size_t)B * n_max));
-    HIPCHK(hipMemsetAsync(e->jump.p, 0, sizeof(int) * (size_t)B * n_max, s));
-    DtwArgs dg;
-    WCA_TRY(run_dtw(e, s, (const float*)e->matrix.p, (long)n_max * Fmax, Fmax, B, Nmax, Fmax, dtwN_dev, h.n_frames, n_max, open_dev, false, &dg,
-                    win_lo_dev, win_hi_dev, n_max));
-    if (path_scores) WCA_TRY(run_path_score(e, s, dg, n_max));
-  } else {
-    if (open_dev) {
-      HIPCHK(e->dtw_out.ensure(2 * sizeof(int) * (size_t)B));
-      HIPCHK(hipMemsetAsync(e->dtw_out.p, 0xFF, 2 * sizeof(int) * (size_t)B, s));
-    }
-    if (path_scores) {
-      HIPCHK(e->pscore.ensure(2 * sizeof(int) * (size_t)B * n_max));
-      HIPCHK(hipMemsetAsync(e->pscore.p, 0, 2 * sizeof(int) * (size_t)B * n_max, s));
-    }
-  }
+  return run_matrix_dtw(e, s, B, n_max, Fmax, o->sot_len, dtwN_dev, h.n_frames, open_dev, path_scores, win_lo_dev, win_hi_dev);
+}
+
+int wca::check_heads(const int32_t* heads_host, int n_heads, int LH) {
+  if (n_heads < 1) return fail(WCA_ERR_INVALID, "empty alignment head list");
+  if (n_heads > LH) return fail(WCA_ERR_INVALID, "%d alignment heads for a model of %d", n_heads, LH);
+  for (int i = 0; i < n_heads; ++i)
+    if (heads_host[i] < 0 || heads_host[i] >= LH) return fail(WCA_ERR_INVALID, "alignment head %d outside [0, %d)", heads_host[i], LH);
   return WCA_OK;
+}
+
+// upstream's post-processing (align_heads.hip) of the S heads heads_dev on s over qk [B][LH][n_max][ld], in place of head statistics, top-k
+// and aggregation: the row statistics land in e->wws [B][S][n_max][2], the column statistics in e->colnorm [B][S][Fmax][2], the matrix in
+// e->matrix, and the ragged closed DTW behind it leaves the jump frames in e->jump. Of o only sot_len, medfilt_width and qk_scale are read.
+int wca::run_align_heads(wca_engine* e, hipStream_t s, const float* qk, int ld, const int* heads_dev, int S, const int* n_tok_dev,
+                         const int* n_frames_dev, const int* dtwN_dev, int n_max, int Fmax, int LH, int B, const wca_align_opts* o) {
+  HIPCHK(e->wws.ensure(sizeof(float) * (size_t)B * S * n_max * 2));
+  HIPCHK(e->colnorm.ensure(sizeof(float) * (size_t)B * S * Fmax * 2));
+  HIPCHK(e->matrix.ensure(sizeof(float) * (size_t)B * n_max * Fmax));
+  AlignHeadsArgs a{};
+  a.qk = qk;
+  a.qk_bs = (long)LH * n_max * ld;
+  a.qk_hs = (long)n_max * ld;
+  a.qk_ld = ld;
+  a.heads = heads_dev;
+  a.S = S;
+  a.n_tok = n_tok_dev;
+  a.n_frames = n_frames_dev;
+  a.n_tok_max = n_max;
+  a.n_frames_max = Fmax;
+  a.B = B;
+  a.sot_len = o->sot_len;
+  a.medfilt_width = o->medfilt_width;
+  a.qk_scale = o->qk_scale;
+  a.rowstats = (float*)e->wws.p;
+  a.colstats = (float*)e->colnorm.p;
+  a.matrix = (float*)e->matrix.p;
+  HIPCHK(launch_align_heads(a, s));
+  record(e, 5, s);   // (profiling: the head-statistics stage holds the three passes, the aggregation stage nothing)
+  record(e, 6, s);
+  return run_matrix_dtw(e, s, B, n_max, Fmax, o->sot_len, dtwN_dev, n_frames_dev, nullptr, false, nullptr, nullptr);
 }
 
 namespace {
@@ -287,6 +334,27 @@ int ensure_res_host(wca_engine* e, int slot, size_t ints) {
   e->res_host_ints[slot] = 0;
   HIPCHK(hipHostMalloc((void**)&e->res_host[slot], ints * sizeof(int), hipHostMallocDefault));
   e->res_host_ints[slot] = ints;
+  return WCA_OK;
+}
+
+// One batch's int table that is too long for the metadata ring -- a [na], then b [nb] (nullable) behind it -- to the device on s without a
+// synchronisation: through the pinned mirror and device buffer of this enqueue's parity, whose previous batch has been fetched (at most two
+// are in flight). A batch has row windows (lo, then hi) or a head list, never both, so the two share the slot. *dev: where a starts.
+int stage_table(wca_engine* e, const int32_t* a, size_t na, const int32_t* b, size_t nb, hipStream_t s, const int** dev) {
+  const int ws = (int)(e->enq_count & 1);
+  const size_t total = na + nb;
+  if (e->win_host_ints[ws] < total) {
+    if (e->win_host[ws]) (void)hipHostFree(e->win_host[ws]);
+    e->win_host[ws] = nullptr;
+    e->win_host_ints[ws] = 0;
+    HIPCHK(hipHostMalloc((void**)&e->win_host[ws], total * sizeof(int), hipHostMallocDefault));
+    e->win_host_ints[ws] = total;
+  }
+  HIPCHK(e->win_dev[ws].ensure(total * sizeof(int)));
+  memcpy(e->win_host[ws], a, na * sizeof(int));
+  if (nb) memcpy(e->win_host[ws] + na, b, nb * sizeof(int));
+  HIPCHK(hipMemcpyAsync(e->win_dev[ws].p, e->win_host[ws], total * sizeof(int), hipMemcpyHostToDevice, s));
+  *dev = (const int*)e->win_dev[ws].p;
   return WCA_OK;
 }
 
@@ -684,11 +752,19 @@ int wca_default_find_alignment(wca_engine* e, const float* ws_dev, int L, int H,
 }
 
 // the fused pipeline, enqueued: d->open_end_host [batch] (nullable) makes the DTW of the flagged rows open-ended; row_lo_host / row_hi_host
-// [batch][n_tok_max] (both or neither) give every DTW row its permitted frame interval
-int wca_align_batch_enqueue_windows(wca_engine* e, const wca_align_desc* d, const int32_t* row_lo_host, const int32_t* row_hi_host) {
+// [batch][n_tok_max] (both or neither) give every DTW row its permitted frame interval; heads_host [n_heads] (nullable, and then without
+// windows) takes the alignment-heads route: upstream's post-processing of those heads in place of head statistics, top-k and aggregation
+static int enqueue_batch(wca_engine* e, const wca_align_desc* d, const int32_t* row_lo_host, const int32_t* row_hi_host, const int32_t* heads_host,
+                         int n_heads) {
   if (!e || !d || !d->tokens_dev || !d->n_tok_host || !d->max_frames_host || !d->opts) return fail(WCA_ERR_INVALID, "null argument");
   if ((row_lo_host == nullptr) != (row_hi_host == nullptr)) return fail(WCA_ERR_INVALID, "row_lo_host and row_hi_host go together");
   const bool want_win = row_lo_host != nullptr;
+  const bool by_heads = heads_host != nullptr;
+  if (by_heads) {   // (refused before anything is consumed or enqueued)
+    if (d->path_scores) return fail(WCA_ERR_INVALID, "path scores are defined on the [0, 1] aggregation, not on the alignment-heads matrix");
+    if (d->open_end_host) return fail(WCA_ERR_INVALID, "the alignment-heads route has no open-ended DTW");
+    WCA_TRY(check_heads(heads_host, n_heads, e->dims.n_text_layer * e->dims.n_text_head));
+  }
   const float* pcm_dev = d->pcm_dev;
   const int64_t pcm_stride = d->pcm_stride;
   const int64_t* tokens_dev = d->tokens_dev;
@@ -713,7 +789,8 @@ int wca_align_batch_enqueue_windows(wca_engine* e, const wca_align_desc* d, cons
   }
   if (e->enq_count - e->fetch_count >= 2) return fail(WCA_ERR_STATE, "two batches already in flight: call wca_align_batch_fetch first");
   if (batch < 1 || batch > e->max_batch) return fail(WCA_ERR_INVALID, "batch %d outside [1,%d]", batch, e->max_batch);
-  WCA_TRY(check_aggregation(o));
+  if (!by_heads) WCA_TRY(check_aggregation(o));
+  if (by_heads && o->sot_len < 0) return fail(WCA_ERR_INVALID, "sot_len %d < 0", o->sot_len);
   WCA_TRY(check_medfilt(o->medfilt_width));
   int Fmax = 0;
   WCA_TRY(validate_lengths(batch, n_tok_max, n_tok_host, max_frames_host, &Fmax));
@@ -754,25 +831,15 @@ int wca_align_batch_enqueue_windows(wca_engine* e, const wca_align_desc* d, cons
     for (int b = 0; b < batch; ++b) flags[b] = open_end_host[b] ? 1 : 0;
     WCA_TRY(stage_meta(e, batch, flags.data(), nullptr, nullptr, nullptr, open_rows, reuse_enc ? s2 : nullptr));
   }
-  // the row windows travel like the metadata, through a pinned mirror of their own (they are [batch][n_tok_max], not [batch]): the slot of
-  // this enqueue's parity, whose previous batch has been fetched (at most two are in flight)
-  const int *win_lo_dev = nullptr, *win_hi_dev = nullptr;
+  // the row windows ([batch][n_tok_max] each, not [batch]) and the head list [n_heads] travel like the metadata, through stage_table
+  const int *win_lo_dev = nullptr, *win_hi_dev = nullptr, *heads_dev = nullptr;
+  hipStream_t ts = reuse_enc ? s2 : e->stream;
   if (want_win) {
-    const int ws = (int)(e->enq_count & 1);
     const size_t n = (size_t)batch * n_tok_max;
-    if (e->win_host_ints[ws] < 2 * n) {
-      if (e->win_host[ws]) (void)hipHostFree(e->win_host[ws]);
-      e->win_host[ws] = nullptr;
-      e->win_host_ints[ws] = 0;
-      HIPCHK(hipHostMalloc((void**)&e->win_host[ws], 2 * n * sizeof(int), hipHostMallocDefault));
-      e->win_host_ints[ws] = 2 * n;
-    }
-    HIPCHK(e->win_dev[ws].ensure(2 * n * sizeof(int)));
-    memcpy(e->win_host[ws], row_lo_host, n * sizeof(int));
-    memcpy(e->win_host[ws] + n, row_hi_host, n * sizeof(int));
-    HIPCHK(hipMemcpyAsync(e->win_dev[ws].p, e->win_host[ws], 2 * n * sizeof(int), hipMemcpyHostToDevice, reuse_enc ? s2 : e->stream));
-    win_lo_dev = (const int*)e->win_dev[ws].p;
+    WCA_TRY(stage_table(e, row_lo_host, n, row_hi_host, n, ts, &win_lo_dev));
     win_hi_dev = win_lo_dev + n;
+  } else if (by_heads) {
+    WCA_TRY(stage_table(e, heads_host, (size_t)n_heads, nullptr, 0, ts, &heads_dev));
   }
   // ---- phase 1 on `stream`: log-mel, encoder, cross-K/V of all decoder layers into a free K/V slot (a slot is busy
   // from its encode until the alignment that read it has been fetched; at most 2 alignments are in flight), or the
@@ -804,11 +871,15 @@ int wca_align_batch_enqueue_windows(wca_engine* e, const wca_align_desc* d, cons
   record(e, 4, s2);
   // the softmaxed maps are NOT materialised on this path (53 MB per utterance): head_stats keeps per-row
   // (max, sum) and the aggregation re-derives the values of the few selected heads from the captured logits
-  HeadStatsArgs h;
-  WCA_TRY(run_head_stats(e, s2, &h, (const float*)e->cap.p, Fpad, false, nullptr, true, rows[1], rows[2], n_tok_max, Fmax, LH, batch, o->medfilt_width,
-                         o->qk_scale, o->w_colnorm, o->w_rownorm, o->w_coverage));
-  record(e, 5, s2);
-  WCA_TRY(run_select_aggregate_dtw(e, s2, h, rows[3], o, D.n_text_layer, open_rows[0], want_ps, win_lo_dev, win_hi_dev));
+  if (by_heads) {
+    WCA_TRY(run_align_heads(e, s2, (const float*)e->cap.p, Fpad, heads_dev, n_heads, rows[1], rows[2], rows[3], n_tok_max, Fmax, LH, batch, o));
+  } else {
+    HeadStatsArgs h;
+    WCA_TRY(run_head_stats(e, s2, &h, (const float*)e->cap.p, Fpad, false, nullptr, true, rows[1], rows[2], n_tok_max, Fmax, LH, batch,
+                           o->medfilt_width, o->qk_scale, o->w_colnorm, o->w_rownorm, o->w_coverage));
+    record(e, 5, s2);
+    WCA_TRY(run_select_aggregate_dtw(e, s2, h, rows[3], o, D.n_text_layer, open_rows[0], want_ps, win_lo_dev, win_hi_dev));
+  }
   if (want_lp) {
     HIPCHK(e->lp_out.ensure(sizeof(float) * (size_t)batch * n_tok_max));
     WCA_TRY(run_token_logprobs(e, s2, tokens_dev, batch, n_tok_max, o->sot_len, vocab_end, rows[1], lp_rows[0], lp_R, lp_nmax, (float*)e->lp_out.p));
@@ -817,7 +888,7 @@ int wca_align_batch_enqueue_windows(wca_engine* e, const wca_align_desc* d, cons
   // results -> pinned staging (ring of 2 so the host can post-process batch i while batch i+1 runs). The flags of this batch travel with
   // its results: phase 2's word, and the word phase 1 raised for this batch's cross-K/V slot (complete: s2 waited for ev_kv[bs], recorded
   // behind that encoder)
-  const int k = o->aggregation == WCA_AGGR_TOPK ? o->topk : 0;
+  const int k = !by_heads && o->aggregation == WCA_AGGR_TOPK ? o->topk : 0;
   const int rs = (int)(e->enq_count & 1);
   const ResLayout at = res_layout(batch, n_tok_max, k, want_lp, want_open, want_ps);
   WCA_TRY(ensure_res_host(e, rs, at.ints));
@@ -913,7 +984,22 @@ int wca_align_batch_path_scores(wca_engine* e, int batch, int n_tok_max, float* 
   return WCA_OK;
 }
 
-int wca_align_batch_enqueue(wca_engine* e, const wca_align_desc* d) { return wca_align_batch_enqueue_windows(e, d, nullptr, nullptr); }
+int wca_align_batch_enqueue_windows(wca_engine* e, const wca_align_desc* d, const int32_t* row_lo_host, const int32_t* row_hi_host) {
+  return enqueue_batch(e, d, row_lo_host, row_hi_host, nullptr, 0);
+}
+
+int wca_align_batch_enqueue(wca_engine* e, const wca_align_desc* d) { return enqueue_batch(e, d, nullptr, nullptr, nullptr, 0); }
+
+int wca_align_batch_enqueue_heads(wca_engine* e, const wca_align_desc* d, const int32_t* heads_host, int n_heads) {
+  if (!e || !d || !heads_host) return fail(WCA_ERR_INVALID, "null argument");
+  return enqueue_batch(e, d, nullptr, nullptr, heads_host, n_heads);
+}
+
+int wca_align_batch_heads(wca_engine* e, const wca_align_desc* d, const int32_t* heads_host, int n_heads, const wca_align_result* r) {
+  if (!e || !d || !heads_host || !r) return fail(WCA_ERR_INVALID, "null argument");
+  WCA_TRY(wca_align_batch_enqueue_heads(e, d, heads_host, n_heads));
+  return wca_align_batch_fetch(e, d->batch, d->n_tok_max, 0, r);
+}
 
 int wca_align_batch_windows(wca_engine* e, const wca_align_desc* d, const int32_t* row_lo_host, const int32_t* row_hi_host, const wca_align_result* r) {
   if (!e || !d || !r) return fail(WCA_ERR_INVALID, "null argument");

@@ -170,7 +170,8 @@ struct wca_engine {
   wca::GrowBuf cap, wws, colnorm, scores, sel, selsc, matrix, trace, path, pathlen, jump, tmp0, tmp1;
   wca::GrowBuf dtw_out, dtw_meta;   // open-end DTW: end rows [P] then scores [P] of the last launch; wca_dtw_batch_dev_open's flags / row / column counts
   // windowed DTW of the fused alignment: the row windows [2][batch][n_tok_max] (lo, then hi) of the two batches that may be in flight, by
-  // enqueue parity like res_host -- pinned host mirror and device copy (a slot is free again once its batch has been fetched)
+  // enqueue parity like res_host -- pinned host mirror and device copy (a slot is free again once its batch has been fetched). A batch on
+  // the alignment-heads route takes no windows: its slot carries the head list [n_heads] instead
   wca::GrowBuf win_dev[2];
   int* win_host[2] = {nullptr, nullptr};
   size_t win_host_ints[2] = {0, 0};
@@ -340,6 +341,11 @@ int run_head_stats(wca_engine* e, hipStream_t s, HeadStatsArgs* h, const float* 
 int run_select_aggregate_dtw(wca_engine* e, hipStream_t s, const HeadStatsArgs& h, const int* dtwN_dev, const wca_align_opts* o, int L_layers,
                              const int* open_dev = nullptr, bool path_scores = false, const int* win_lo_dev = nullptr,
                              const int* win_hi_dev = nullptr);   // win_*: row windows [B][n_tok_max] in DTW rows, checked by the caller
+// the alignment-heads route (align_heads.hip) in place of the two calls above: the head list's host check, and the three passes with the
+// ragged closed DTW behind them
+int check_heads(const int32_t* heads_host, int n_heads, int LH);
+int run_align_heads(wca_engine* e, hipStream_t s, const float* qk, int ld, const int* heads_dev, int S, const int* n_tok_dev,
+                    const int* n_frames_dev, const int* dtwN_dev, int n_max, int Fmax, int LH, int B, const wca_align_opts* o);
 
 // ---- engine_audio.hip
 int check_pcm_lengths(const int32_t* n_samples_host, int batch, int64_t pcm_stride);

@@ -438,6 +438,43 @@ static int align_postproc(wca_engine* e, const wca_test_postproc_desc* d, float*
   return WCA_OK;
 }
 
+int wca_test_align_heads_postproc(wca_engine* e, const wca_test_heads_postproc_desc* d) {
+  if (!e || !d || !d->qk_dev || !d->n_tok_host || !d->n_frames_host || !d->heads_host || !d->opts) return fail(WCA_ERR_INVALID, "null argument");
+  const wca_align_opts* o = d->opts;
+  const int B = d->B, LH = d->L * d->H, n_max = d->n_tok_max, F = d->n_frames_max, S = d->n_heads;
+  if (B < 1 || B > e->max_batch) return fail(WCA_ERR_INVALID, "batch %d outside [1,%d]", B, e->max_batch);
+  if (d->L < 1 || d->H < 1 || LH > 8192) return fail(WCA_ERR_INVALID, "bad shape L=%d H=%d", d->L, d->H);
+  if (o->sot_len < 0) return fail(WCA_ERR_INVALID, "sot_len %d < 0", o->sot_len);
+  WCA_TRY(check_heads(d->heads_host, S, LH));
+  WCA_TRY(check_medfilt(o->medfilt_width));
+  int Fmax = 0;
+  WCA_TRY(validate_lengths(B, n_max, d->n_tok_host, d->n_frames_host, &Fmax));
+  if (F > N_CTX) return fail(WCA_ERR_TOO_LONG, "n_frames_max=%d > %d", F, N_CTX);
+  if (F < Fmax || d->ld < F) return fail(WCA_ERR_INVALID, "need the largest n_frames %d <= n_frames_max %d <= ld %d", Fmax, F, d->ld);
+  WCA_TRY(enter(e));
+  std::vector<int32_t> dn(B);
+  for (int b = 0; b < B; ++b) dn[b] = std::max(0, d->n_tok_host[b] - o->sot_len - 1);
+  int* rows[4];
+  WCA_TRY(stage_meta(e, B, nullptr, d->n_tok_host, d->n_frames_host, dn.data(), rows));
+  hipStream_t s = e->stream;
+  HIPCHK(e->tmp1.ensure(sizeof(int) * (size_t)S));
+  HIPCHK(hipMemcpyAsync(e->tmp1.p, d->heads_host, sizeof(int) * (size_t)S, hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));   // heads_host is caller-owned pageable memory
+  WCA_TRY(run_align_heads(e, s, d->qk_dev, d->ld, (const int*)e->tmp1.p, S, rows[1], rows[2], rows[3], n_max, F, LH, B, o));
+  const size_t BS = (size_t)B * S;
+  if (d->rowstats_host) HIPCHK(hipMemcpyAsync(d->rowstats_host, e->wws.p, sizeof(float) * BS * n_max * 2, hipMemcpyDeviceToHost, s));
+  if (d->colstats_host) HIPCHK(hipMemcpyAsync(d->colstats_host, e->colnorm.p, sizeof(float) * BS * F * 2, hipMemcpyDeviceToHost, s));
+  if (d->matrix_host) HIPCHK(hipMemcpyAsync(d->matrix_host, e->matrix.p, sizeof(float) * (size_t)B * n_max * F, hipMemcpyDeviceToHost, s));
+  if (d->jump_host) {
+    if (n_max - o->sot_len - 1 >= 1)   // (otherwise no DTW ran and nothing wrote e->jump: the rows are 0 by definition)
+      HIPCHK(hipMemcpyAsync(d->jump_host, e->jump.p, sizeof(int) * (size_t)B * n_max, hipMemcpyDeviceToHost, s));
+    else
+      memset(d->jump_host, 0, sizeof(int) * (size_t)B * n_max);
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  return WCA_OK;
+}
+
 int wca_test_last_colnorm(wca_engine* e, int64_t count, float* colnorm_host) {
   if (!e || !colnorm_host) return fail(WCA_ERR_INVALID, "null argument");
   if (count < 1 || (size_t)count * sizeof(float) > e->colnorm.bytes) return fail(WCA_ERR_INVALID, "%lld column norms are not held", (long long)count);

@@ -433,6 +433,26 @@ hipError_t launch_probe_strict(const int* jump, int jump_ld, int LH, const int* 
 // standalone median filter along the last axis with reflect padding (whisper.timing.median_filter)
 hipError_t launch_median_filter(const float* in, float* out, long rows, int F, int width, hipStream_t s);
 
+// ---------------------------------------------------------------- alignment-heads post-processing (align_heads.hip)
+// openai-whisper's find_alignment on the captured logits of a ragged batch, over a fixed list of S heads: softmax over the frames, then
+// (w - mean) / std per head and frame over the token axis, then the median filter, then the mean over the heads, for the rows
+// [sot_len, n_tok - 1) the DTW is given. Three launches; the S maps are never written out, only their row and column statistics.
+struct AlignHeadsArgs {
+  const float* qk;         // captured logits: qk[b*qk_bs + head*qk_hs + t*qk_ld + f], as HeadStatsArgs
+  long qk_bs; long qk_hs; int qk_ld;
+  const int* heads;        // [S] device: layer * H + head, summed in this order
+  int S;
+  const int* n_tok;        // [B] decoder rows per utterance (device)
+  const int* n_frames;     // [B] F per utterance (device)
+  int n_tok_max, n_frames_max, B;
+  int sot_len, medfilt_width;
+  float qk_scale;
+  float* rowstats;         // [B][S][n_tok_max][2] = (row max of qk*scale, sum of exp)
+  float* colstats;         // [B][S][n_frames_max][2] = (mean, population std) of the softmaxed column over the n_tok rows
+  float* matrix;           // [B][n_tok_max][n_frames_max], rows [0, n_tok - sot_len - 1) of an utterance, as AggregateArgs::matrix
+};
+hipError_t launch_align_heads(const AlignHeadsArgs& a, hipStream_t s);
+
 // ---------------------------------------------------------------- DTW (dtw.hip)
 struct DtwArgs {
   const float* matrix;     // P problems: matrix + p*m_bs, rows ld apart; DTW runs on the NEGATED matrix

@@ -494,7 +494,7 @@ class WhisperAMD:
                               float(w_rownorm), float(w_coverage), int(sot_len), int(medfilt_width), float(qk_scale))
 
     def align_batch(self, pcm, n_samples, tokens, n_tok, max_frames, opts, enqueue_only=False, token_logprobs_vocab_end=None, open_end=None,
-                    path_scores=False, row_windows=None):
+                    path_scores=False, row_windows=None, alignment_heads=None):
         """Fused pipeline. pcm [B,stride] f32 cuda, tokens [B,n_max] int64 cuda. Returns (jump_frames [B,n_max] int32, sel [B,topk]).
         token_logprobs_vocab_end (tokenizer.eot): the teacher tokens' log-probabilities are computed on the GPU as well
         (wca_align_desc.vocab_end) and returned as a third value [B,n_max] f32 (row b: n_tok[b] - sot_len - 2 entries, then 0);
@@ -510,8 +510,20 @@ class WhisperAMD:
         frames lo[b][i] <= j <= hi[b][i] (wca_align_batch_enqueue_windows; DTW rows count from the first token after the sot sequence and
         no_timestamps, the eot is the last, later entries are not read). The windows must be valid (include/wca.h wca_dtw_windows), and an
         open_end row takes full windows only; otherwise the engine refuses the call (WcaError) before anything is enqueued. The returned
-        values are those without windows. None: nothing changes and no new code runs."""
+        values are those without windows. None: nothing changes and no new code runs.
+        alignment_heads: a list of (layer, head) pairs, or True for self.alignment_heads: the batch takes the ALIGNMENT-HEADS route
+        (wca_align_batch_enqueue_heads): openai-whisper's own post-processing of those heads -- softmax, (w - mean) / std per frame over the
+        tokens, median filter, mean over the heads in the order given -- in place of head scoring, top-k and aggregation; of opts only
+        sot_len, medfilt_width and qk_scale are read. The return shape is unchanged (sel is None). Not together with path_scores,
+        open_end or row_windows (ValueError). After enqueue_only=True the batch holds no top-k slot whatever opts says: fetch it with
+        fetch(B, n_max, None, ...) (opts=None: no selected heads), not with top-k opts. None: nothing changes and no new code runs."""
         B, n_max = tokens.shape
+        heads = None
+        if alignment_heads is not None and alignment_heads is not False:
+            if path_scores or open_end is not None or row_windows is not None:
+                raise ValueError("alignment_heads cannot be combined with path_scores, open_end or row_windows: the path score is defined on "
+                                 "the [0, 1] aggregation, and the alignment-heads matrix has no open-ended or windowed DTW")
+            heads = self.flat_heads(self.alignment_heads if alignment_heads is True else alignment_heads)
         if open_end is not None and len(open_end) != B:
             raise ValueError("open_end lists %d flags for %d rows" % (len(open_end), B))
         self._bind_stream()
@@ -522,7 +534,10 @@ class WhisperAMD:
         d = _lib.AlignDesc(pcm_dev=_ptr(pcm), n_samples_host=_ptr(ns), tokens_dev=_ptr(tokens), n_tok_host=_ptr(nt), max_frames_host=_ptr(mf),
                            opts=C.pointer(opts), open_end_host=_ptr(oe), pcm_stride=pcm.shape[1] if pcm is not None else 0, n_tok_max=n_max,
                            batch=B, vocab_end=int(token_logprobs_vocab_end or 0), path_scores=1 if path_scores else 0)
-        if row_windows is not None:
+        if heads is not None:
+            _lib.check(self._lib.wca_align_batch_enqueue_heads(self._h, C.byref(d), heads.ctypes.data_as(_pi32), len(heads)))
+            opts = None   # (what fetch reads of it: no top-k slot)
+        elif row_windows is not None:
             lo, hi = (np.ascontiguousarray(w, dtype=np.int32) for w in row_windows)
             if lo.shape != (B, n_max) or hi.shape != (B, n_max):
                 raise ValueError("row_windows are two [%d, %d] tables, got %s and %s" % (B, n_max, lo.shape, hi.shape))
@@ -533,6 +548,17 @@ class WhisperAMD:
             return None
         return self.fetch(B, n_max, opts, with_token_logprobs=token_logprobs_vocab_end is not None, with_end_rows=open_end is not None,
                           with_path_scores=bool(path_scores))
+
+    def flat_heads(self, heads):
+        """(layer, head) pairs -> the int32 array layer * n_text_head + head the C ABI takes, in the order given; ValueError for an empty
+        list or a pair outside the model."""
+        pairs = [(int(l), int(h)) for l, h in heads]
+        if not pairs:
+            raise ValueError("alignment_heads is empty")
+        for l, h in pairs:
+            if not (0 <= l < self.dims.n_text_layer and 0 <= h < self.dims.n_text_head):
+                raise ValueError("alignment head (%d, %d) out of range" % (l, h))
+        return np.ascontiguousarray([l * self.dims.n_text_head + h for l, h in pairs], dtype=np.int32)
 
     def encode_batch(self, mel=None, pcm=None, n_samples=None):
         """C ABI wca_encode_batch: enqueue log-mel/encoder/cross-K/V of a micro-batch (no host sync). The state is picked up
@@ -752,6 +778,28 @@ class WhisperAMD:
             _lib.check(self._lib.wca_test_align_postproc(self._h, C.byref(d)))
         return out
 
+    def align_heads_postproc(self, qk, n_tok, n_frames, opts, L, H, heads, n_frames_max=None):
+        """C ABI wca_test_align_heads_postproc (tests): the alignment-heads post-processing of align_batch(alignment_heads=...) on given
+        logits qk [B, L*H, n_tok_max, ld] f32 cuda, over `heads`, flat indices layer * H + head in the order they are summed. Returns a dict
+        of numpy arrays: rowstats [B,S,n_tok_max,2] = (max, sum), colstats [B,S,F,2] = (mean, std), matrix [B,n_tok_max,F], jump
+        [B,n_tok_max]; F = n_frames_max (default: the largest n_frames). Only utterance b's own corner of an array is defined."""
+        qk = qk.to(self.device, torch.float32).contiguous()
+        B, LH, n_max, ld = qk.shape
+        if LH != L * H:
+            raise ValueError("qk holds %d heads, not %d x %d" % (LH, L, H))
+        F = int(n_frames_max) if n_frames_max is not None else max(int(v) for v in n_frames)
+        hd = np.ascontiguousarray(heads, dtype=np.int32)
+        S = len(hd)
+        out = {"rowstats": np.zeros((B, max(S, 1), n_max, 2), np.float32), "colstats": np.zeros((B, max(S, 1), max(F, 1), 2), np.float32),
+               "matrix": np.zeros((B, n_max, max(F, 1)), np.float32), "jump": np.zeros((B, n_max), np.int32)}
+        nt, nf = _lib.i32_array(n_tok), _lib.i32_array(n_frames)
+        self._bind_stream()
+        d = _lib.HeadsPostprocDesc(qk_dev=_ptr(qk), n_tok_host=_ptr(nt), n_frames_host=_ptr(nf), heads_host=_ptr(hd), opts=C.pointer(opts),
+                                   rowstats_host=_ptr(out["rowstats"]), colstats_host=_ptr(out["colstats"]), matrix_host=_ptr(out["matrix"]),
+                                   jump_host=_ptr(out["jump"]), B=B, L=L, H=H, n_tok_max=n_max, ld=ld, n_frames_max=F, n_heads=S)
+        _lib.check(self._lib.wca_test_align_heads_postproc(self._h, C.byref(d)))
+        return out
+
     def dtw_path_scores(self, matrix_dev, n_rows=None, n_cols=None, open_end=None):
         """C ABI wca_dtw_path_scores: P DTW problems matrix_dev [P, N, M] f32 cuda (NOT negated), problem p the n_rows[p] x n_cols[p] corner
         of its slice (None: all N / all M), open-ended where open_end[p] (None: all closed), each followed by the path-score kernel.
@@ -800,8 +848,9 @@ class WhisperAMD:
         """Results of the oldest enqueued align_batch: (jump, sel), or (jump, sel, token_logprobs [B,n_max] f32) with
         with_token_logprobs (the batch must have been enqueued with token_logprobs_vocab_end). with_end_rows (the batch must have been
         enqueued with open_end) appends the end rows [B] int32 and the scores [B] f32. with_path_scores (the batch must have been enqueued
-        with path_scores) appends, last, path_mean [B,n_max] f32 and path_cells [B,n_max] int32 (wca_align_batch_path_scores)."""
-        k = opts.topk if opts.aggregation == _lib.AGGR_TOPK else 0
+        with path_scores) appends, last, path_mean [B,n_max] f32 and path_cells [B,n_max] int32 (wca_align_batch_path_scores).
+        opts=None: a batch enqueued with alignment_heads, which selects no heads (sel is None)."""
+        k = opts.topk if opts is not None and opts.aggregation == _lib.AGGR_TOPK else 0
         jump = np.zeros((B, n_max), dtype=np.int32)
         sel = np.zeros((B, max(k, 1)), dtype=np.int32)
         lp = np.zeros((B, n_max), dtype=np.float32) if with_token_logprobs else None

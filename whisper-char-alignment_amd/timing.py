@@ -283,13 +283,25 @@ def _default_alignment_from_weights(eng, weights, heads, text_tokens, tokenizer)
                                                    tj.ctypes.data_as(_pi), C.byref(plen)))
     text_indices = ti[:plen.value].astype(np.int64)
     time_indices = tj[:plen.value].astype(np.int64)
+    jumps = np.pad(np.diff(text_indices), (1, 0), constant_values=1).astype(bool)
+    spans = default_word_spans(time_indices[jumps] / TOKENS_PER_SECOND, text_tokens, tokenizer)
+    if spans is None:
+        return [[], [], [], [], None]
+    words, _word_tokens, _boundaries, start_times, end_times = spans
+    return words, start_times, end_times, norm, None
+
+
+def default_word_spans(jump_times, text_tokens, tokenizer):
+    """The tail of the reference's default_find_alignment (timing.py:171-180) and of upstream's find_alignment: jump_times[i] is the time
+    at which the DTW path enters text row i of text_tokens + [eot]. Returns (words, word_tokens, word_boundaries, start_times, end_times)
+    -- words and word_tokens by tokenizer.split_to_word_tokens, the eot their last entry; the times one per word but that last -- or
+    None when the text has at most one word. The one place this slice and boundary arithmetic is written (word_timing uses it too)."""
     words, word_tokens = tokenizer.split_to_word_tokens(list(text_tokens) + [tokenizer.eot])
     if len(word_tokens) <= 1:
-        return [[], [], [], [], None]
+        return None
     word_boundaries = np.pad(np.cumsum([len(t) for t in word_tokens[:-1]]), (1, 0))
-    jumps = np.pad(np.diff(text_indices), (1, 0), constant_values=1).astype(bool)
-    jump_times = time_indices[jumps] / TOKENS_PER_SECOND
-    return words, jump_times[word_boundaries[:-1]], jump_times[word_boundaries[1:]], norm, None
+    jump_times = np.asarray(jump_times)
+    return words, word_tokens, word_boundaries, jump_times[word_boundaries[:-1]], jump_times[word_boundaries[1:]]
 
 
 def default_find_alignment(model, tokenizer, text_tokens, mel, max_frames, *, medfilt_width=7, qk_scale=1.0):

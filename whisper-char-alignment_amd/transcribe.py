@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Long-form transcription: `whisper.transcribe(model, audio, ...)` at temperature 0 on the MI355X engine, with word times
-from this project's character aligner instead of upstream's alignment-heads aligner.
+from this project's character aligner or (word_aligner="heads") from upstream's alignment-heads aligner.
 
 Upstream openai-whisper `transcribe.py` is an absent third-party dependency (like `decoding.py`, see decoding.py's
 docstring); its published seek loop is restated here: PARITY UNPINNED against upstream itself. The reference
@@ -60,8 +60,12 @@ Limits (part of the contract):
     segment and word times stay absolute. It is an ENERGY detector, not a trained one: music and loud noise count as speech, and the
     quality of its defaults on real speech is UNVALIDATED (they were looked at on one 2.9 s recording laid out between stretches of
     silence; no corpus is at hand). Not together with clip_timestamps or pieces.
-  * hallucination_silence_threshold, prepend_punctuations / append_punctuations are not built (they belong to upstream's own word
-    aligner); vad_filter is this project's remedy for text invented over silence.
+  * hallucination_silence_threshold is not built (it belongs to upstream's own word aligner's seek loop); vad_filter is this project's
+    remedy for text invented over silence.
+  * word_aligner="heads" (the default stays "char") takes upstream's own word aligner instead: find_alignment over model.alignment_heads
+    on the GPU (align_batch(alignment_heads=True), csrc/align_heads.hip) and a restatement of add_word_timestamps with
+    prepend_punctuations / append_punctuations (word_timing.py). Pinned: the kernels against float64, every host rule on hand-computed
+    numbers. Not pinned: parity with upstream itself (its source is not at hand), and quality on speech is UNVALIDATED.
 
 Decisions the upstream text leaves open:
   * a window that ended inside speech (its tokens do not end in a single timestamp; seek advances to the last consecutive
@@ -352,10 +356,11 @@ class WindowAligner:
         attach_words(segments, out)
         return True
 
-    def align_round(self, rows):
+    def align_round(self, rows, keys=None):
         """rows: one entry per row of the batch the last decode left in the engine, in order: (seek, size, max_frames, segments), or
         None for a row that was skipped. ONE align_batch(pcm=None) for the rows that have words; a row without (skipped, or refused by
-        `prepare`) rides along as a minimal placeholder row whose output is dropped. Returns one bool per row (None for a skipped row)."""
+        `prepare`) rides along as a minimal placeholder row whose output is dropped. Returns one bool per row (None for a skipped row).
+        keys (which recording and piece a row belongs to) are HeadsWindowAligner's; this aligner carries nothing from round to round."""
         preps = [self.prepare(r[2], r[3]) if r is not None else None for r in rows]
         if not any(p is not None for p in preps):
             return [None if r is None else False for r in rows]   # nothing to align: the next decode drops the state
@@ -380,7 +385,72 @@ class WindowAligner:
         return self.align_round([(seek, size, max_frames, segments)])[0]
 
 
-make_aligner = WindowAligner   # (`.align_window` is the align_window that seek_loop takes)
+class HeadsWindowAligner:
+    """Upstream's aligner on the encoder state a round's decode left in the engine (word_aligner="heads"): the decoded text tokens of the
+    kept segments themselves are framed -- no re-tokenisation, so a window has a few dozen rows, not hundreds of characters --, one
+    align_batch(pcm=None, alignment_heads=True) per round runs upstream's find_alignment on the GPU (csrc/align_heads.hip), and
+    word_timing.add_word_timestamps hands the words out: each with its leading space and its punctuation, so that a segment's words join
+    to its text. last_speech_timestamp is carried from window to window per recording (and piece): `keys`."""
+
+    def __init__(self, model, tokenizer, *, word_confidence=False, medfilt_width=3, prepend_punctuations=None, append_punctuations=None,
+                 aligned_unit_type=None, aggr=None, topk=None, w_colnorm=None, w_rownorm=None, w_coverage=None):
+        # (the last six are the character aligner's, which transcribe hands to either aligner: taken and not read; anything else is a TypeError)
+        from . import word_timing
+        self.model, self.tokenizer, self.word_confidence = model, tokenizer, word_confidence
+        self.prepend = word_timing.PREPEND_PUNCTUATIONS if prepend_punctuations is None else prepend_punctuations
+        self.append = word_timing.APPEND_PUNCTUATIONS if append_punctuations is None else append_punctuations
+        self.opts = model.make_opts(sot_len=len(tokenizer.sot_sequence), medfilt_width=medfilt_width, qk_scale=1.0)
+        self.placeholder = [*tokenizer.sot_sequence, tokenizer.no_timestamps, tokenizer.encode(" a")[-1], tokenizer.eot]   # a row without words
+        self.last_speech = {}   # key -> the end of the last word of that recording's (piece's) windows so far
+
+    def prepare(self, max_frames, segments):
+        """The framed token row the window is aligned with and its text tokens, or None where the window gets no words."""
+        tokenizer = self.tokenizer
+        text_tokens = [t for seg in segments for t in seg["tokens"] if t < tokenizer.eot]
+        tokens = [*tokenizer.sot_sequence, tokenizer.no_timestamps, *text_tokens, tokenizer.eot]
+        if not text_tokens or len(tokens) > MAX_LENGTH or not 1 <= max_frames <= self.model.dims.n_audio_ctx:
+            return None
+        return tokens, text_tokens
+
+    def attach(self, seek, segments, text_tokens, jump_row, logprob_row, key=None):
+        from . import word_timing
+        alignment = word_timing.alignment_from_jump_frames(jump_row, text_tokens, self.tokenizer, logprob_row if self.word_confidence else None)
+        if not alignment:
+            return False
+        self.last_speech[key] = word_timing.add_word_timestamps(
+            segments, alignment, self.tokenizer, time_offset=seek * FRAME_SECONDS, last_speech_timestamp=self.last_speech.get(key, 0.0),
+            prepend_punctuations=self.prepend, append_punctuations=self.append)
+        return any(seg["words"] for seg in segments)
+
+    def align_round(self, rows, keys=None):
+        """WindowAligner.align_round on the alignment-heads route; keys[b]: whose last_speech_timestamp row b reads and leaves."""
+        preps = [self.prepare(r[2], r[3]) if r is not None else None for r in rows]
+        if not any(p is not None for p in preps):
+            return [None if r is None else False for r in rows]   # nothing to align: the next decode drops the state
+        token_rows = [p[0] if p is not None else self.placeholder for p in preps]
+        max_frames = [r[2] if p is not None else PLACEHOLDER_FRAMES for r, p in zip(rows, preps)]
+        res = self.model.align_batch(None, None, pad_token_rows(token_rows, self.tokenizer.eot).to(self.model.device), [len(t) for t in token_rows],
+                                     max_frames, self.opts, token_logprobs_vocab_end=self.tokenizer.eot if self.word_confidence else None,
+                                     alignment_heads=True)
+        out = []
+        for b, (r, p) in enumerate(zip(rows, preps)):
+            if r is None:
+                out.append(None)
+            elif p is None:
+                out.append(False)
+            else:
+                out.append(self.attach(r[0], r[3], p[1], res[0][b][:len(token_rows[b])], res[2][b] if self.word_confidence else None,
+                                       keys[b] if keys is not None else None))
+        return out
+
+    def align_window(self, seek, size, max_frames, segments):
+        """seek_loop's align_window: a round of one row."""
+        return self.align_round([(seek, size, max_frames, segments)])[0]
+
+
+def make_aligner(model, tokenizer, *, word_aligner="char", **options):
+    """The window aligner of a call: `.align_window` is the align_window that seek_loop takes, `.align_round` what the lock-step loop calls."""
+    return (HeadsWindowAligner if word_aligner == "heads" else WindowAligner)(model, tokenizer, **options)
 
 
 def clip_frames(clip_timestamps, content_frames):
@@ -626,7 +696,7 @@ def lock_step(call, code, rows, mels, plans):
         windows = cut_windows(call.model, mels, [(u[0], seek, size) for u, (seek, size, _) in zip(live, requests)])
         decoded = call.decode(code, windows, [prompt for _, _, prompt in requests], [seek for seek, _, _ in requests])
         pending = [states[u].receive(r) for u, r in zip(live, decoded)]
-        aligned = aligner.align_round(pending) if aligner is not None else [None] * len(live)
+        aligned = aligner.align_round(pending, live) if aligner is not None else [None] * len(live)
         for u, pend, al in zip(live, pending, aligned):
             if pend is not None:
                 states[u].commit(al)
@@ -658,7 +728,7 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
                      medfilt_width=3, word_alignment_score=False, vocab_path=None, temperature=0.0, w_colnorm=1.0, w_rownorm=1.0, w_coverage=0.0, decode_windows=None,
                      detect_languages=None, sample_rate=SAMPLE_RATE, clip_timestamps=None, pieces=None, seed=None,
                      compression_ratio_threshold=2.4, beam_size=None, patience=None, length_penalty=None, best_of=None, vad_filter=False,
-                     vad_options=None, **decode_options):
+                     vad_options=None, word_aligner="char", prepend_punctuations=None, append_punctuations=None, **decode_options):
     """transcribe() of several recordings in lock-step: a list with transcribe()'s result for every recording of `audios`, in order.
     Each round cuts the next window of every unfinished recording, decodes them in ONE batch with every row's own previous text as its
     prompt (decoding.decode with one DecodingOptions per row: wca_decode with per_row 1) and, with word_timestamps, aligns the rows that
@@ -705,7 +775,18 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
     MaximumLikelihoodRanker's, with length_penalty. Every window then takes G = max(beam_size, best_of) decoder rows (C ABI
     wca_decode_group), so a round holds at most max_batch // G windows and G above max_batch is a ValueError. What is pinned: the beam
     step and the cache reorder against a float64 restatement of upstream's BeamSearchDecoder, the loop against the fp32 oracle
-    (tests/test_beam_step_gpu.py, tests/test_decode_beam_gpu.py). PARITY with upstream itself stays UNPINNED, as for decode."""
+    (tests/test_beam_step_gpu.py, tests/test_decode_beam_gpu.py). PARITY with upstream itself stays UNPINNED, as for decode.
+    word_aligner ("char", the default: every call as it always was, and nothing new runs; or "heads"): with word_timestamps, "heads" takes
+    upstream's words instead of the character aligner's (HeadsWindowAligner): the decoded tokens themselves are aligned over
+    model.alignment_heads by upstream's find_alignment on the GPU (align_batch(alignment_heads=True)) and handed out by a restatement of
+    upstream's add_word_timestamps (word_timing), so every word carries its leading space and its punctuation and a segment's words join
+    to its text; segment starts and ends follow their first and last word as upstream's do. prepend_punctuations / append_punctuations
+    are upstream's (None: upstream's defaults) and belong to "heads" only, as word_alignment_score belongs to "char" only: the other
+    combination is a ValueError before any audio is read. medfilt_width is this keyword's value (3 here; upstream's own default is 7);
+    aligned_unit_type, aggr, topk and the w_* weights are the character aligner's and are not read. A model without an official head
+    table (model.alignment_heads_source) aligns over every head of the upper decoder half, and a warning says so. "probability" stays
+    None unless word_confidence=True. hallucination_silence_threshold and upstream's re-seek to the last word's end are not built.
+    PARITY with upstream is UNPINNED and quality on speech UNVALIDATED (word_timing's docstring)."""
     temperatures = check_supported(temperature, language, seed)
     group_options = dict(beam_size=beam_size, patience=patience, best_of=best_of)
     if length_penalty is not None:
@@ -735,6 +816,19 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
         raise ValueError("word_alignment_score is a property of the aligned words: it needs word_timestamps=True")
     if word_timestamps and vocab_path is None:
         raise ValueError("word_timestamps aligns the decoded TEXT: pass vocab_path=<local *.tiktoken file>")
+    if word_aligner not in ("char", "heads"):
+        raise ValueError("word_aligner is \"char\" or \"heads\", not %r" % (word_aligner,))
+    if word_aligner == "char" and (prepend_punctuations is not None or append_punctuations is not None):
+        raise ValueError("prepend_punctuations / append_punctuations belong to upstream's word aligner: pass word_aligner=\"heads\"")
+    if word_aligner == "heads":
+        if not word_timestamps:
+            raise ValueError("word_aligner chooses how the words are aligned: it needs word_timestamps=True")
+        if word_alignment_score:
+            raise ValueError("word_alignment_score is defined on the character aligner's [0, 1] matrix: not with word_aligner=\"heads\"")
+        if str(getattr(model, "alignment_heads_source", "")).startswith("default"):
+            import warnings
+            warnings.warn("word_aligner=\"heads\" on a model without an official alignment-head table: aligning over %s "
+                          "(model.alignment_heads_source; see use_official_alignment_heads / set_alignment_heads)" % model.alignment_heads_source)
     max_batch = int(getattr(model, "max_batch", 1))
     if max_batch < 1:
         raise ValueError("transcribe_batch needs model.max_batch >= 1")
@@ -749,6 +843,8 @@ def transcribe_batch(model, audios, *, language, initial_prompt=None, condition_
                  w_rownorm=w_rownorm, w_coverage=w_coverage, word_confidence=word_confidence) if word_timestamps else None
     if word_alignment_score:   # (otherwise the aligner is made as it always was)
         words["word_alignment_score"] = True
+    if word_aligner == "heads":   # (likewise)
+        words.update(word_aligner="heads", prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations)
     call = _Call(model, language, initial_prompt, vocab_path, decode_options, decode_windows, detect_languages, seek, words,
                  *(() if seed is None else (temperatures, int(seed), compression_ratio_threshold)), group_options=group_options)
     audios = list(audios)
@@ -802,6 +898,13 @@ def parse_args(argv=None):
     p.add_argument("--word_alignment_score", action="store_true", default=argparse.SUPPRESS, help="with --word_timestamps: every word also gets its `alignment_score`, the "
                    "mean of the aggregated attention matrix along its stretch of the DTW path (in [0, 1]; uncalibrated)")
     add_aligner_options(p)
+    # upstream's own word aligner (likewise absent unless given)
+    p.add_argument("--word_aligner", choices=["char", "heads"], default=argparse.SUPPRESS, help="with --word_timestamps: `heads` aligns the decoded "
+                   "tokens over the model's alignment heads as openai-whisper does (words keep their spaces and punctuation); default char")
+    p.add_argument("--prepend_punctuations", type=str, default=argparse.SUPPRESS, help="with --word_aligner heads: merged with the next word "
+                   "(default: upstream's)")
+    p.add_argument("--append_punctuations", type=str, default=argparse.SUPPRESS, help="with --word_aligner heads: merged with the previous word "
+                   "(default: upstream's)")
     p.add_argument("--pieces", type=_pieces_arg, default=None, metavar="N|auto", help="cut every recording at quiet frames into N pieces that are "
                    "decoded side by side (auto: as many as --batch rows allow, at least 60 s each); needs --batch >= N")
     p.add_argument("--clip_timestamps", type=str, default=None, metavar="a,b,...", help="transcribe only these ranges: start,end,start,end,... in "
@@ -882,7 +985,7 @@ def main(args, model=None):
         kw["vad_filter"] = True
         if vad_options:
             kw["vad_options"] = vad_options
-    for name in ("beam_size", "patience", "length_penalty", "best_of"):   # (likewise: given options only)
+    for name in ("beam_size", "patience", "length_penalty", "best_of", "word_aligner", "prepend_punctuations", "append_punctuations"):   # (likewise: given options only)
         if getattr(args, name, None) is not None:
             kw[name] = getattr(args, name)
     for group in groups_of(_recordings(args), args.batch):   # a group's files are written before the next group starts
