@@ -13,8 +13,6 @@ import decode_cache_ref as R
 
 pytestmark = pytest.mark.gpu
 
-dref = importlib.import_module("oracle.decoding_ref")
-
 
 @pytest.fixture(scope="module")
 def sc():
@@ -44,47 +42,7 @@ def mel_dev(sc):
     return sc["mel"].cuda()
 
 
-def _check_state(tag, cache, logits, want_planes, fed, want_logits):
-    """cache [L][2][B][T][d] f16 and logits [R][V] f32 of the GPU against the float64 planes (row b: slots [0, fed[b])) and logits rows: prints the three
-    maxima, then asserts them."""
-    cache = torch.from_numpy(cache.astype(np.float64))
-    d0 = dd = 0.0
-    for b, n in enumerate(fed):
-        diff = (cache[:, :, b, :n] - want_planes[:, :, b, :n]).abs()
-        d0 = max(d0, float(diff[0].max()))
-        dd = max(dd, float(diff[1:].max()))
-    dl = float((torch.from_numpy(logits.astype(np.float64)) - want_logits).abs().max())
-    print("decode-cache measure %s: plane0 %.3e plane_deep %.3e logits %.3e (|logits| max %.2f)" % (tag, d0, dd, dl, float(want_logits.abs().max())))
-    assert np.isfinite(logits).all()
-    assert d0 <= R.TOL["plane0"], (tag, "layer-0 planes", d0, R.TOL["plane0"])
-    assert dd <= R.TOL["plane_deep"], (tag, "deeper planes", dd, R.TOL["plane_deep"])
-    assert dl <= R.TOL["logits"], (tag, "logits", dl, R.TOL["logits"])
-
-
-def _check_choices(tag, step_logits, chosen, sum_logprob, tol_logits):
-    """The sampled tokens and sum_logprob against oracle.decoding_ref.select_step on the float64 logits step_logits [B][S][V] (teacher-forced on the
-    GPU's tokens `chosen` [B][S]): the oracle's choice wherever its margin exceeds the logits bound, and the log-probability of the GPU's tokens
-    (log-softmax moves by at most twice the largest logit change, per step)."""
-    Bc, S = chosen.shape
-    filters = R.text_filters()
-    want_lp = torch.zeros(Bc, dtype=torch.float64)
-    n_decided = 0
-    for i in range(S):
-        last = torch.zeros(Bc, 1, dtype=torch.long)   # no row has ended: <|endoftext|> is suppressed
-        new, _, filt = dref.select_step(step_logits[:, i], last, torch.zeros(Bc), filters, R.N_TEXT)
-        top2 = filt.topk(2, dim=-1).values
-        for b in range(Bc):
-            assert chosen[b, i] < R.N_TEXT, (tag, b, i, int(chosen[b, i]))
-            if float(top2[b, 0] - top2[b, 1]) > tol_logits:
-                n_decided += 1
-                assert int(chosen[b, i]) == int(new[b, -1]), (tag, b, i, int(chosen[b, i]), int(new[b, -1]), float(top2[b, 0] - top2[b, 1]))
-        masked = step_logits[:, i].clone()
-        masked[:, R.N_TEXT:] = float("-inf")
-        want_lp += masked.log_softmax(-1)[torch.arange(Bc), torch.from_numpy(chosen[:, i].astype(np.int64))]
-    err = float((torch.from_numpy(sum_logprob.astype(np.float64)) - want_lp).abs().max())
-    print("decode-cache choices %s: %d of %d decided by the reference margin, max |d sum_logprob| %.3e" % (tag, n_decided, Bc * S, err))
-    assert n_decided >= 1
-    assert err <= S * 2 * tol_logits + 1e-4, (tag, err)
+_check_state, _check_choices = R.check_state, R.check_choices      # shared with tests/test_decode_widths_gpu.py; here on the 256-wide TOL
 
 
 # f16 at every length; the reference-precision engine (the loop computes in f16 there too, on the hi halves of the pair-format cross-K/V) at the tile boundaries

@@ -88,9 +88,12 @@ def _head_reference(sd, x, lang_begin, n_lang):
 
 @pytest.mark.parametrize("B", [1, 3])
 @pytest.mark.parametrize("n_lang", [99, 100])
-@pytest.mark.parametrize("d", [256, 384])
+@pytest.mark.parametrize("d", [256, 384, 512, 768, 1024, 1280])
 def test_language_head_vs_float64(mods, d, n_lang, B):
-    """d = 256: half the lanes of a wave hold no half8 chunk of the row; d = 384: 48 chunks on 64 lanes."""
+    """d = 256: half the lanes of a wave hold no half8 chunk of the row; d = 384: 48 chunks on 64 lanes. The chunk loop of a lane (d / 8 half8
+    chunks over the 64 lanes of a wave) then takes 1 trip at d = 512, 2 on half the lanes at 768 (96 chunks), 2 at 1024 and 3 on half the lanes
+    at 1280 (160 chunks); the LayerNorm loop (d elements over a workgroup of 256) takes 1, 2 (half the threads), 2, 3, 4 and 5 trips at the six
+    widths. The bound below is derived from d."""
     n_vocab = 51865 if n_lang == 99 else 51866
     m, sd = _head_engine(d, n_vocab)
     g = torch.Generator().manual_seed(1000 * d + 10 * n_lang + B)
@@ -138,10 +141,19 @@ def test_language_head_refuses_what_it_cannot_address(mods):
 
 
 def test_language_head_tie_goes_to_the_lower_id(pkg, mods):
-    dims = _dims(pkg, 256, 51865)
+    _tie_goes_to_the_lower_id(pkg, mods, 256)
+
+
+def test_language_head_tie_goes_to_the_lower_id_1280_wide(pkg, mods):
+    """The same construction at the widest model (the planted logit is 0.1 |xn|^2, about 0.1 d = 128): three trips of the chunk loop on half the lanes."""
+    _tie_goes_to_the_lower_id(pkg, mods, 1280)
+
+
+def _tie_goes_to_the_lower_id(pkg, mods, d):
+    dims = _dims(pkg, d, 51865)
     sd = _head_state_dict(mods, dims, seed=3)
     g = torch.Generator().manual_seed(8)
-    x0 = torch.randn(256, generator=g)
+    x0 = torch.randn(d, generator=g)
     x = torch.stack([x0, 1.5 * x0 + 0.5])                              # two rows with (mathematically) the same LayerNorm'd direction
     lang_begin, lo, hi = SOT + 1, 5, 40
     others = float(_head_reference(sd, x, lang_begin, 99)[0].abs().max())   # (only to size the planted logit against the random rows'
